@@ -20,6 +20,8 @@ Workloads (``--workload``):
                       hyper-parameters + predictions to rank 0 in the reference's tile order.  Strong scaling.
 ``--exact-iters`` switches the optimiser's early stopping off (ftol = gtol = off): every tile runs exactly max_iter
 iterations unless its line search fails; the CPU baseline then runs SciPy with ftol = gtol = 0 on matched work.
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (see dump_outputs); the inputs depend
+on the arguments only, so two builds run with the same arguments can be compared array for array.
 
 ``python bench.py --gpus N`` without a torch.distributed environment starts the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py``, before this process touches the GPU) and relays the line.
@@ -107,12 +109,21 @@ def _gen_tile(args):
     return syn.make_tile(seed, N, P, D, kid)
 
 
+def _one_blas_thread():
+    from threadpoolctl import threadpool_limits
+    threadpool_limits(1)
+
+
 def gen_tiles(jobs, workers):
+    """BLAS on one thread: the Cholesky factor that draws a tile's observations rounds differently with the BLAS thread
+    count, which follows the host's CPU count -- one thread gives the same inputs on every host (--dump-outputs)."""
     from multiprocessing import get_context
+    from threadpoolctl import threadpool_limits
     if workers > 1 and len(jobs) > 1:
-        with get_context("fork").Pool(workers) as pool:
+        with get_context("fork").Pool(workers, initializer=_one_blas_thread) as pool:
             return pool.map(_gen_tile, jobs, chunksize=max(1, len(jobs) // (workers * 8)))
-    return [_gen_tile(j) for j in jobs]
+    with threadpool_limits(1):
+        return [_gen_tile(j) for j in jobs]
 
 
 def build_workload(a, rank, world, workers):
@@ -342,6 +353,44 @@ def cpu_baseline(w, a, workers):
             "modes": modes, "_nll": cpu_nll}
 
 
+# ----------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step, for comparing two builds output for output
+# ----------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 * 10 ** 6
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, r, pred_off, budget=DUMP_BYTES):
+    """Writes the BatchResult of one step as out_dir/<name>.npy: per tile theta, nll, status, n_eval, n_iter (float64) and
+    the predictions f_mean, f_var, y_var (the step's float32 / float64).  When every tile's outputs would exceed `budget`
+    bytes, the arrays hold a fixed sample of tiles (seed DUMP_SEED, the same for the same tile count and prediction
+    offsets), in tile order, and tile_index.npy names them.  Returns {name: shape}."""
+    def host(v):
+        return v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+    pred_off = np.asarray(pred_off, dtype=np.int64)
+    T = len(pred_off) - 1
+    per_tile = {"theta": r.theta, "nll": r.nll, "status": r.status, "n_eval": r.n_eval, "n_iter": r.n_iter}
+    per_tile = {k: np.asarray(v, dtype=np.float64) for k, v in per_tile.items()}
+    preds = {k: host(getattr(r, k))[:pred_off[-1]] for k in ("f_mean", "f_var", "y_var")}
+    tile_bytes = sum(v.nbytes // max(T, 1) for v in per_tile.values()) + np.diff(pred_off) * sum(v.itemsize for v in preds.values())
+    headers = 128 * (len(per_tile) + len(preds) + 1)
+    idx = None
+    if int(tile_bytes.sum()) + headers > budget:
+        order = np.random.default_rng(DUMP_SEED).permutation(T)
+        fits = np.cumsum(tile_bytes[order] + 8) + headers <= budget      # + 8: the tile's entry in tile_index
+        idx = np.sort(order[fits])
+        per_tile = {k: v[idx] for k, v in per_tile.items()}
+        rows = np.concatenate([np.arange(pred_off[t], pred_off[t + 1]) for t in idx]) if len(idx) else np.zeros(0, np.int64)
+        preds = {k: v[rows] for k, v in preds.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(per_tile, **preds)
+    if idx is not None:
+        arrays["tile_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,7 +415,12 @@ def main():
     ap.add_argument("--no-quality", action="store_true", help="skip the result-quality block (fp64 converged reference run)")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the two-step runs of configs[2], configs[4] per GPU and the "
                     "fp64 fit that follow the headline's timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's tiles) as DIR/<name>.npy, "
+                    f"at most {DUMP_BYTES // 10 ** 6} MB (a fixed sample of tiles beyond that)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: start the N ranks as a CHILD torch.distributed.run (this process has not touched the
@@ -471,6 +525,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if a.dump_outputs and rank == 0:                      # outside the timed region, before anything else runs
+        dump_outputs(a.dump_outputs, r, w["pred_off"])
 
     # ---- the same step from packed host arrays to outputs on the host; context, never `value`
     host_ms = None
