@@ -14,8 +14,6 @@
 #include "gpsat_hip.h"
 #include "gpsat_kernels.h"
 
-#define GPSAT_PT_MAXNB_HOST 100        // colrow[] words in a CoopCtl (gpsat_coop.h: GPSAT_PT_MAXNB)
-
 namespace {
 
 thread_local std::string g_err;
@@ -119,12 +117,16 @@ int gpsat_device_count(void) {
 }
 
 int gpsat_max_tile_obs(int dtype, int D) {
-    // the largest tile whose workgroup state (coordinates, y, z, alpha, factor buffers, optimiser state) fits the
-    // 160 KiB LDS of a CU with one workgroup per CU (8-wave builds)
+    // the largest tile, at most GPSAT_MAX_TILE_OBS observations, whose workgroup state (coordinates, y, z, alpha, factor
+    // buffers, optimiser state) fits the 160 KiB LDS of a CU with one workgroup per CU (8-wave builds); fp32 tiles also
+    // have at most GPSAT_PT_MAXNB block columns (the sweep flags).  D = 1 / 2 / 3 / 4:
+    //   fp32  4096 / 4096 / 3168 / 2592        fp64  4096 / 3392 / 2832 / 2416
+    // (pinned by tests/test_abi.py)
     if (D < 1 || D > 4 || (dtype != GPSAT_F32 && dtype != GPSAT_F64)) return 0;
     const bool f64 = dtype == GPSAT_F64;
     const int bs = f64 ? 16 : 32;
-    for (int NB = 4096 / bs; NB >= 1; --NB) {
+    const int nb_max = f64 ? GPSAT_MAX_TILE_OBS / bs : std::min(GPSAT_MAX_TILE_OBS / bs, GPSAT_PT_MAXNB);
+    for (int NB = nb_max; NB >= 1; --NB) {
         const size_t smem = f64 ? gpsat::shared_bytes_f64(D, NB) : gpsat::shared_bytes_w8(D, NB);
         if (smem <= 160 * 1024) return NB * bs;
     }
@@ -475,7 +477,7 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (!coop_host.empty()) {
         long long st[8] = {0};
-        for (int g = 0; g < grid; ++g) for (int i = 0; i < 8; ++i) st[i] += coop_host[(size_t)g * 256 + 32 + GPSAT_PT_MAXNB_HOST + i];
+        for (int g = 0; g < grid; ++g) for (int i = 0; i < 8; ++i) st[i] += coop_host[(size_t)g * 256 + 32 + GPSAT_PT_MAXNB + i];
         std::fprintf(stderr, "gpsat coop: grid %d T %d: cooperative evaluations %lld, helper phases %lld, helper groups (sweep) %lld, "
                              "flag waits given up %lld, owner waits given up %lld, pivot failures %lld, helper unwinds %lld\n",
                      grid, T, st[0], st[1], st[2], st[3], st[4], st[5], st[6]);

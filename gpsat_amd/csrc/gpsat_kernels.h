@@ -4,6 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+// Largest tile the C ABI accepts in any dtype (gpsat_max_tile_obs searches down from here), and the block columns (32
+// observations each) of the largest fp32 tile: the words of the fp32 sweep flags colrow[] in the workgroup state
+// (gpsat_opt.h Shared) and in each cooperative control block (gpsat_coop.h CoopCtl).  phase_pt writes colrow[0 .. NB-1].
+#define GPSAT_MAX_TILE_OBS 4096
+#define GPSAT_PT_MAXNB 128
+static_assert(32 * GPSAT_PT_MAXNB >= GPSAT_MAX_TILE_OBS, "fp32 sweep flags must cover the largest tile gpsat_max_tile_obs allows");
+
 namespace gpsat {
 
 // All pointers are DEVICE pointers.

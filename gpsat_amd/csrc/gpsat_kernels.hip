@@ -304,7 +304,7 @@ __device__ __forceinline__ void kfun(float r2, float& kf, float& gg) {
     }
 }
 
-#define GPSAT_PT_MAXNB 100      // block columns of the largest tile (gpsat_max_tile_obs: 3168 = 99 * 32)
+#define GPSAT_PT_FLAGS          // Shared carries the sweep flags of phase_pt: colrow[GPSAT_PT_MAXNB] (gpsat_kernels.h)
 #include "gpsat_opt.h"
 #include "gpsat_coop.h"
 

@@ -46,6 +46,12 @@ extern __shared__ __attribute__((aligned(16))) double lds_d[];
 
 constexpr int BS = 16;         // block size
 constexpr int BLK = 256;       // doubles per block
+// Exchange area at the end of a workspace, in blocks below the zero block: the diagonal region of a panel and tp (12 blocks),
+// then z and alpha of the tile (xvec_blocks each, at least 14: the layout of every tile up to 224 blocks stays where it was).
+// Teams exchange all of it; the one-workgroup 8-wave build keeps its look-ahead sums in the first 12 blocks.
+__host__ __device__ constexpr int xvec_blocks(int NBmax) { return (NBmax * BS + BLK - 1) / BLK > 14 ? (NBmax * BS + BLK - 1) / BLK : 14; }
+__host__ __device__ constexpr int xchg_blocks(int NBmax) { return 12 + 2 * xvec_blocks(NBmax); }
+static_assert(xchg_blocks(1) == 40 && xvec_blocks(224) == 14 && xvec_blocks(256) == 16, "exchange area layout");
 
 // Diagnostic build only (-DGPSAT_PROFILE, scripts/phase_profile_f64.py): per-wave cycle counters per code segment in LDS,
 // flushed to KernelArgs::prof.  No stamp executes in the product build.
@@ -1205,7 +1211,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
     c.zb = (int)(stride / BLK) - 1;
     for (int i = c.tid; i < BLK; i += NT) c.ws[(size_t)c.zb * BLK + i] = 0.0;
     c.vw = c.w; c.nwt = NW; c.member = 0; c.G = 1; c.tc = nullptr; c.tpg = nullptr; c.zg = nullptr; c.ag = nullptr;
-    c.pn0 = c.zb - 40;           // the exchange area of teams doubles as the look-ahead store of the 8-wave build
+    c.pn0 = c.zb - xchg_blocks(A.NBmax);       // the exchange area of teams doubles as the look-ahead store of the 8-wave build
     const double* X = reinterpret_cast<const double*>(A.X);
     const double* y = reinterpret_cast<const double*>(A.y);
     const double* Xs = reinterpret_cast<const double*>(A.Xs);
@@ -1398,10 +1404,11 @@ __global__ void __launch_bounds__(NT, 1) gp_team_kernel_f64(const KernelArgs A) 
     const size_t stride = A.ws_stride;
     c.ws = reinterpret_cast<double*>(A.ws) + (size_t)team * stride;               // one slab per team
     c.zb = (int)(stride / BLK) - 1;
-    c.pn0 = c.zb - 40;
-    c.tpg = (gdouble*)(c.ws + (size_t)(c.zb - 29) * BLK);
-    c.zg = (gdouble*)(c.ws + (size_t)(c.zb - 28) * BLK);
-    c.ag = (gdouble*)(c.ws + (size_t)(c.zb - 14) * BLK);
+    const int xv = xvec_blocks(A.NBmax);         // z and alpha hold Npad <= NBmax * BS doubles each
+    c.pn0 = c.zb - xchg_blocks(A.NBmax);
+    c.tpg = (gdouble*)(c.ws + (size_t)(c.zb - 2 * xv - 1) * BLK);
+    c.zg = (gdouble*)(c.ws + (size_t)(c.zb - 2 * xv) * BLK);
+    c.ag = (gdouble*)(c.ws + (size_t)(c.zb - xv) * BLK);
     if (c.member == 0 && c.w == 0) { const f64x4 z0 = zero4(); stg(c.ws, c.zb, c.lane, z0); }
     if (c.tid == 0) sh->hp[0] = 0;                      // team barriers passed
     const double* X = reinterpret_cast<const double*>(A.X);
@@ -1600,8 +1607,9 @@ int F64FN(state_words_f64)() { return (int)((sizeof(F64NS::Shared) + 15) / 16) *
 size_t F64FN(workspace_doubles_per_wg_f64)(int NBmax, int PCcov) {
     // + V of all prediction chunks when the full covariance is wanted (spare chunks: a wave always solves 2 at a time)
     const size_t cov = PCcov > 0 ? (size_t)(PCcov + 3) * NBmax : 0;
-    // ... 40 blocks of exchange areas for teams (diagonal region of a panel, z, alpha), and the zero block
-    return (size_t)F64NS::BLK * ((size_t)NBmax * NBmax + (size_t)NBmax + (size_t)F64NS::NW * 4 * NBmax + cov + 40 + 1);
+    // ... the exchange area of teams (diagonal region of a panel, z, alpha), and the zero block
+    return (size_t)F64NS::BLK * ((size_t)NBmax * NBmax + (size_t)NBmax + (size_t)F64NS::NW * 4 * NBmax + cov +
+                                 F64NS::xchg_blocks(NBmax) + 1);
 }
 
 hipError_t F64FN(launch_tiles_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {

@@ -40,7 +40,7 @@ struct Shared {
     // flags of the Cholesky / inverse sweep (phase_pt of the fp32 kernels; the fp64 kernels use g0done and gnext)
     int g0done;                 // panel index up to which group 0 of the previous panel is in memory
     int gnext[2];               // fp64 kernels: dynamic group queue heads of the PT slots (alternating)
-#ifdef GPSAT_PT_MAXNB
+#ifdef GPSAT_PT_FLAGS
     int ready, parked, whfree;  // panels: chain complete / group-0 k-loop parked / parked k-loop consumed
     int gdone[2];               // groups of the panel of that parity that are finished
     int qhead;                  // bulk group queue head (all panels)

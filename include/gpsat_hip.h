@@ -156,9 +156,10 @@ int gpsat_device_count(void);
 
 /*
  * Largest number of observations one tile may hold for `dtype` (GPSAT_F32 / GPSAT_F64) and input dimension D: the
- * tile's coordinates, observations and solve vectors stay in the 160 KiB LDS of its CU for the whole fit (D = 3:
- * 2,800 in fp64 -- the reference's published N = 2,500 fp64 fit, docs/notebooks/using_gpus.ipynb:77,165, fits -- and
- * 3,168 in fp32).  A batch holding a larger tile is refused with GPSAT_EINVAL.  0 for unsupported arguments.  ABI >= 3.
+ * tile's coordinates, observations and solve vectors stay in the 160 KiB LDS of its CU for the whole fit, and no tile
+ * holds more than 4,096.  D = 1 / 2 / 3 / 4: 4,096 / 3,392 / 2,832 / 2,416 in fp64 (the reference's published N = 2,500
+ * fp64 fit, docs/notebooks/using_gpus.ipynb:77,165, fits) and 4,096 / 4,096 / 3,168 / 2,592 in fp32.  A batch holding a
+ * larger tile is refused with GPSAT_EINVAL.  0 for unsupported arguments.  ABI >= 3.
  */
 int gpsat_max_tile_obs(int dtype, int D);
 

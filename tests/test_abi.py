@@ -43,6 +43,52 @@ def test_header_constants_match_binding():
     assert (const("GPSAT_MEM_HOST"), const("GPSAT_MEM_DEVICE")) == (L.MEM_HOST, L.MEM_DEVICE)
 
 
+MAX_TILE_OBS = {"f32": (4096, 4096, 3168, 2592), "f64": (4096, 3392, 2832, 2416)}     # D = 1 .. 4
+
+
+def test_max_tile_obs_table_is_pinned():
+    """gpsat_max_tile_obs decides which tiles the orchestrator sends: the whole table, and 0 outside it."""
+    lib = L.load()
+    for dtype, code in (("f32", 0), ("f64", 1)):
+        assert tuple(lib.gpsat_max_tile_obs(code, D) for D in range(1, 5)) == MAX_TILE_OBS[dtype]
+        assert tuple(L.max_tile_obs(dtype, D) for D in range(1, 5)) == MAX_TILE_OBS[dtype]
+        assert lib.gpsat_max_tile_obs(code, 0) == 0 and lib.gpsat_max_tile_obs(code, 5) == 0
+    for D in range(0, 6):
+        assert lib.gpsat_max_tile_obs(2, D) == 0 and lib.gpsat_max_tile_obs(-1, D) == 0
+
+
+def test_fp32_tile_limit_fits_the_sweep_flags():
+    """phase_pt writes colrow[0 .. NB-1] (NB = ceil(N / 32)) into arrays of GPSAT_PT_MAXNB words: no fp32 tile the ABI
+    accepts may have more block columns than that."""
+    src = open(os.path.join(ROOT, "gpsat_amd", "csrc", "gpsat_kernels.h")).read()
+    maxnb = int(re.search(r"#define\s+GPSAT_PT_MAXNB\s+(\d+)", src).group(1))
+    cap = int(re.search(r"#define\s+GPSAT_MAX_TILE_OBS\s+(\d+)", src).group(1))
+    assert 32 * maxnb >= cap
+    lib = L.load()
+    for D in range(1, 5):
+        assert 0 < lib.gpsat_max_tile_obs(0, D) <= 32 * maxnb
+        assert max(lib.gpsat_max_tile_obs(0, D), lib.gpsat_max_tile_obs(1, D)) <= cap
+    # the flag words are declared with that size, and nowhere with a literal
+    csrc = os.path.join(ROOT, "gpsat_amd", "csrc")
+    decls = [re.findall(r"\bcolrow\[([^\]]*)\];", open(os.path.join(csrc, f)).read()) for f in ("gpsat_opt.h", "gpsat_coop.h")]
+    assert decls == [["GPSAT_PT_MAXNB"], ["GPSAT_PT_MAXNB"]], decls
+    srcs = "".join(open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".cpp", ".hip", ".h")))
+    assert len(re.findall(r"#define\s+GPSAT_PT_MAXNB\b", srcs)) == 1
+
+
+def test_four_wave_thresholds_of_the_build_matrix():
+    """tests/test_gpu_build_matrix.py sizes its 4-wave batches from W4_NB / D4_NB: the largest tile (blocks) whose 4-wave LDS
+    layout fits 80 KiB, the rule by which gpsat_capi.cpp picks the 4-wave builds.  If the layouts drift, those batches would
+    quietly run on the 8-wave builds; this fails instead."""
+    from test_gpu_build_matrix import D4_NB, W4_NB
+    lib = L.load()
+    for name, table in (("_ZN5gpsat12shared_bytesEii", W4_NB), ("_ZN5gpsat19shared_bytes_f64_w4Eii", D4_NB)):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = C.c_size_t, [C.c_int, C.c_int]
+        got = {D: max(nb for nb in range(1, 512) if fn(D, nb) <= 80 * 1024) for D in range(1, 5)}
+        assert got == table, (name, got)
+
+
 def test_struct_layout_matches_c(tmp_path):
     """Compile a tiny C program against the header and compare sizeof/offsetof with ctypes."""
     fields = [f[0] for f in L.GpsatBatch._fields_]
