@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPSAT_LIB") or os.path.join(_HERE, "csrc", "libgpsat_hip.so")
 
 # constants mirrored from include/gpsat_hip.h
-ABI_VERSION = 3
+ABI_VERSION = 4
 F32, F64 = 0, 1
 KERNEL_IDS = {"RBF": 0, "SquaredExponential": 0, "Matern12": 1, "Exponential": 1, "Matern32": 2, "Matern52": 3}
 OPT_NONE, OPT_LBFGS, OPT_ADAM = 0, 1, 2
@@ -23,7 +23,8 @@ STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5:
 
 EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
-           "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs"]
+           "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
+           "gpsat_max_inducing"]
 
 
 class GpsatOpts(C.Structure):
@@ -42,6 +43,10 @@ class GpsatBatch(C.Structure):
         ("n_eval", C.c_void_p), ("f_mean", C.c_void_p), ("f_var", C.c_void_p), ("y_var", C.c_void_p),
         ("cov_off", C.c_void_p), ("f_cov", C.c_void_p), ("n_iter", C.c_void_p),
     ]
+
+
+class GpsatSparse(C.Structure):
+    _fields_ = [("z_off", C.c_void_p), ("Z", C.c_void_p), ("jitter", C.c_double), ("reserved", C.c_int32 * 8)]
 
 
 SEL_MAXCRIT = 4
@@ -130,6 +135,10 @@ def load():
                                      C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     lib.gpsat_max_tile_obs.restype = C.c_int
     lib.gpsat_max_tile_obs.argtypes = [C.c_int, C.c_int]
+    lib.gpsat_sgpr_fit_predict_batch.restype = C.c_int
+    lib.gpsat_sgpr_fit_predict_batch.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatSparse)]
+    lib.gpsat_max_inducing.restype = C.c_int
+    lib.gpsat_max_inducing.argtypes = [C.c_int, C.c_int]
     lib.gpsat_last_timing.restype = C.c_int
     lib.gpsat_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if lib.gpsat_version() != ABI_VERSION:
@@ -140,6 +149,11 @@ def load():
 def max_tile_obs(dtype: str, D: int) -> int:
     """Largest tile (observations) the kernels take for this dtype / input dimension (gpsat_max_tile_obs)."""
     return int(get_lib().gpsat_max_tile_obs(F32 if dtype == "f32" else F64, int(D)))
+
+
+def max_inducing(dtype: str, D: int) -> int:
+    """Largest number of inducing points per sparse tile (gpsat_max_inducing); 0 for fp32 in this build."""
+    return int(get_lib().gpsat_max_inducing(F32 if dtype == "f32" else F64, int(D)))
 
 
 _lib = None

@@ -521,6 +521,160 @@ int gpsat_debug_set_dump(gpsat_handle* h, void* dev, unsigned long long stride_f
 }
 #endif
 
+int gpsat_max_inducing(int dtype, int D) {
+    if (D < 1 || D > 4 || dtype != GPSAT_F64) return 0;       // fp32 SGPR is not built (a 1e-6 jitter on an fp32 Cholesky)
+    return GPSAT_MAX_INDUCING;
+}
+
+int gpsat_sgpr_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b, const gpsat_sparse* sp) {
+    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_sgpr_fit_predict_batch: NULL handle or batch");
+    h->selc.total = -1;
+    if (!sp || !sp->z_off) return fail(GPSAT_EINVAL, "gpsat_sgpr_fit_predict_batch: NULL sparse description or z_off");
+    if (b->T < 0) return fail(GPSAT_EINVAL, "T < 0");
+    if (b->T == 0) return GPSAT_OK;
+    if (b->D < 1 || b->D > 4) return fail(GPSAT_EINVAL, "D must be 1..4 in this build");
+    if (b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "sparse GP experts are built for GPSAT_F64 only");
+    if (b->cov_off || b->f_cov) return fail(GPSAT_EINVAL, "sparse GP experts do not return the full covariance: cov_off / f_cov must be NULL");
+    if (b->kernel < 0 || b->kernel > 3) return fail(GPSAT_EINVAL, "unknown kernel id");
+    if (b->optimiser < 0 || b->optimiser > 2) return fail(GPSAT_EINVAL, "unknown optimiser id");
+    if (b->memory != GPSAT_MEM_HOST && b->memory != GPSAT_MEM_DEVICE) return fail(GPSAT_EINVAL, "bad memory flag");
+    if (!b->obs_off || !b->pred_off || !b->theta0 || !b->lo || !b->hi || !b->trainable)
+        return fail(GPSAT_EINVAL, "metadata pointer is NULL");
+    if (!b->theta || !b->nll || !b->status || !b->n_eval) return fail(GPSAT_EINVAL, "output pointer is NULL");
+    if (!(sp->jitter >= 0.0) || !std::isfinite(sp->jitter)) return fail(GPSAT_EINVAL, "jitter must be finite and >= 0");
+    const int T = b->T, D = b->D, H = D + 2;
+    const int mlim = gpsat_max_inducing(b->dtype, D);
+    if (b->obs_off[0] != 0 || b->pred_off[0] != 0 || sp->z_off[0] != 0) return fail(GPSAT_EINVAL, "offsets must start at 0");
+    int Mmax = 1;
+    for (int t = 0; t < T; ++t) {
+        const long long n = b->obs_off[t + 1] - b->obs_off[t], p = b->pred_off[t + 1] - b->pred_off[t];
+        const long long m = sp->z_off[t + 1] - sp->z_off[t];
+        if (n < 0 || p < 0) return fail(GPSAT_EINVAL, "offsets must be non-decreasing");
+        if (n > 0x7fffffffLL || p > 0x7fffffffLL) return fail(GPSAT_EINVAL, "a tile holds more than 2^31-1 rows");
+        if (m < 1 || m > mlim)
+            return fail(GPSAT_EINVAL, "every tile needs 1.." + std::to_string(mlim) + " inducing points (gpsat_max_inducing); tile " +
+                                          std::to_string(t) + " has " + std::to_string(m));
+        Mmax = std::max(Mmax, (int)m);
+    }
+    const long long sumN = b->obs_off[T], sumP = b->pred_off[T], sumM = sp->z_off[T];
+    if (!sp->Z) return fail(GPSAT_EINVAL, "Z is NULL");
+    if (sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
+    if (sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < H; ++i) {
+            const double v = b->theta0[(size_t)t * H + i];
+            if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
+        }
+    const size_t esz = sizeof(double);
+    const size_t smem = gpsat::sgpr_shared_bytes(D, Mmax);
+    if (smem > 160 * 1024) return fail(GPSAT_EINVAL, "inducing points do not fit the LDS");
+
+    HIP_TRY(hipSetDevice(h->device));
+    // tile order: largest cost first (N M^2), stable
+    std::vector<int> order(T);
+    std::iota(order.begin(), order.end(), 0);
+    auto cost = [&](int t) {
+        const double m = (double)(sp->z_off[t + 1] - sp->z_off[t]);
+        return (double)(b->obs_off[t + 1] - b->obs_off[t]) * m * m + m * m * m;
+    };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return cost(a) > cost(c); });
+    // one workgroup per CU; the workspaces together stay below 16 GiB
+    const size_t wsd = gpsat::sgpr_workspace_doubles_per_wg(D, Mmax);
+    int grid = std::min(T, h->num_cu);
+    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)16 << 30) / (wsd * esz)));
+    int rc;
+    if ((rc = h->meta_i64.reserve(3 * (size_t)(T + 1) * sizeof(long long)))) return rc;
+    if ((rc = h->meta_f64.reserve(3 * (size_t)T * H * sizeof(double)))) return rc;
+    if ((rc = h->meta_misc.reserve((size_t)T * sizeof(int) + 64 + 16))) return rc;
+    if ((rc = h->out_f64.reserve(((size_t)T * H * 2 + (size_t)T) * sizeof(double)))) return rc;
+    if ((rc = h->out_i32.reserve((size_t)T * 3 * sizeof(int)))) return rc;
+    if ((rc = h->ws.reserve((size_t)grid * wsd * esz))) return rc;
+
+    const char *dX = nullptr, *dy = nullptr, *dXs = nullptr, *dZ = nullptr;
+    char *dfm = nullptr, *dfv = nullptr, *dyv = nullptr;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (b->memory == GPSAT_MEM_HOST) {
+        const size_t in_e = (size_t)sumN * D + (size_t)sumN + (size_t)sumP * D + (size_t)sumM * D;
+        if ((rc = h->bulk_in.reserve(std::max<size_t>(in_e, 1) * esz))) return rc;
+        if ((rc = h->bulk_out.reserve(std::max<size_t>((size_t)sumP * 3, 1) * esz))) return rc;
+        char* base = static_cast<char*>(h->bulk_in.p);
+        dX = base; dy = dX + (size_t)sumN * D * esz; dXs = dy + (size_t)sumN * esz; dZ = dXs + (size_t)sumP * D * esz;
+        if (sumN > 0) {
+            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dX), b->X, (size_t)sumN * D * esz, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dy), b->y, (size_t)sumN * esz, hipMemcpyHostToDevice, h->stream));
+        }
+        if (sumP > 0)
+            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dXs), b->Xs, (size_t)sumP * D * esz, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(const_cast<char*>(dZ), sp->Z, (size_t)sumM * D * esz, hipMemcpyHostToDevice, h->stream));
+        dfm = static_cast<char*>(h->bulk_out.p); dfv = dfm + (size_t)sumP * esz; dyv = dfv + (size_t)sumP * esz;
+    } else {
+        dX = static_cast<const char*>(b->X); dy = static_cast<const char*>(b->y); dXs = static_cast<const char*>(b->Xs);
+        dZ = static_cast<const char*>(sp->Z);
+        dfm = static_cast<char*>(b->f_mean); dfv = static_cast<char*>(b->f_var); dyv = static_cast<char*>(b->y_var);
+    }
+    long long* d_i64 = static_cast<long long*>(h->meta_i64.p);
+    HIP_TRY(hipMemcpyAsync(d_i64, b->obs_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_i64 + (T + 1), b->pred_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_i64 + 2 * (T + 1), sp->z_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    double* d_f64 = static_cast<double*>(h->meta_f64.p);
+    HIP_TRY(hipMemcpyAsync(d_f64, b->theta0, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_f64 + (size_t)T * H, b->lo, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_f64 + 2 * (size_t)T * H, b->hi, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    unsigned char* d_misc = static_cast<unsigned char*>(h->meta_misc.p);
+    int* d_queue = reinterpret_cast<int*>(d_misc);
+    unsigned char* d_train = d_misc + 16;
+    int* d_order = reinterpret_cast<int*>(d_misc + 16 + 64);
+    HIP_TRY(hipMemsetAsync(d_queue, 0, 16, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_train, b->trainable, (size_t)H, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
+
+    gpsat::SgprArgs a;
+    a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
+    a.max_ls = b->max_ls > 0 ? b->max_ls : 20;
+    a.Mmax = Mmax;
+    a.ftol = b->ftol > 0 ? b->ftol : (b->ftol < 0 ? -1.0 : 2.220446049250313e-9);
+    a.gtol = b->gtol > 0 ? b->gtol : (b->gtol < 0 ? -1.0 : 1e-5);
+    a.adam_lr = b->adam_lr > 0 ? b->adam_lr : 0.1;
+    a.noise_rel = 1e-12;
+    a.jitter = sp->jitter > 0.0 ? sp->jitter : 1e-6;
+    a.obs_off = d_i64; a.pred_off = d_i64 + (T + 1); a.z_off = d_i64 + 2 * (T + 1);
+    a.theta0 = d_f64; a.lo = d_f64 + (size_t)T * H; a.hi = d_f64 + 2 * (size_t)T * H;
+    a.trainable = d_train;
+    a.X = reinterpret_cast<const double*>(dX); a.y = reinterpret_cast<const double*>(dy);
+    a.Xs = reinterpret_cast<const double*>(dXs); a.Z = reinterpret_cast<const double*>(dZ);
+    double* d_out = static_cast<double*>(h->out_f64.p);
+    a.theta = d_out; a.nll = d_out + (size_t)T * H;
+    a.grad = b->grad ? d_out + (size_t)T * H + T : nullptr;
+    int* d_oi = static_cast<int*>(h->out_i32.p);
+    a.status = d_oi; a.n_eval = d_oi + T; a.n_iter = d_oi + 2 * (size_t)T;
+    a.f_mean = reinterpret_cast<double*>(dfm); a.f_var = reinterpret_cast<double*>(dfv); a.y_var = reinterpret_cast<double*>(dyv);
+    a.order = d_order; a.queue = d_queue;
+    a.ws = static_cast<double*>(h->ws.p); a.ws_stride = wsd;
+
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::launch_sgpr(D, a, grid, smem, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    HIP_TRY(hipMemcpyAsync(b->theta, a.theta, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->nll, a.nll, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, a.grad, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->status, a.status, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->n_eval, a.n_eval, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (b->n_iter) HIP_TRY(hipMemcpyAsync(b->n_iter, a.n_iter, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (b->memory == GPSAT_MEM_HOST && sumP > 0) {
+        HIP_TRY(hipMemcpyAsync(b->f_mean, dfm, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(b->f_var, dfv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(b->y_var, dyv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    float km = 0.f, tm = 0.f;
+    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
+    h->last_kernel_ms = km;
+    h->last_total_ms = tm;
+    return GPSAT_OK;
+}
+
 int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, int32_t C, const double* points,
                        int32_t T, const double* refs, int64_t* off, int32_t* idx, int64_t capacity) {
     if (!h || !sp || !off) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL argument");

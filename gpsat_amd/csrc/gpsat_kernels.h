@@ -137,5 +137,40 @@ hipError_t launch_smooth(int T, const double* x, const double* y, const double* 
 hipError_t launch_glue(int G, int ndim, int nvars, long long R, const long long* seg, const double* pred, const double* xprt,
                        const double* vals, double sigma, const double* sigma_rows, double* out, hipStream_t stream);
 
+// sparse GP experts (gpsat_sgpr.hip, fp64 only); device pointers.  One workgroup per tile from an atomic queue.
+struct SgprArgs {
+    int T, kernel, optimiser, max_iter, max_ls, Mmax;
+    double ftol, gtol, adam_lr, noise_rel, jitter;
+    const long long* obs_off;     // [T+1]
+    const long long* pred_off;    // [T+1]
+    const long long* z_off;       // [T+1] rows of Z per tile
+    const double* theta0;         // [T*H]
+    const double* lo;
+    const double* hi;
+    const unsigned char* trainable;
+    const double* X;              // [sumN*D]
+    const double* y;              // [sumN]
+    const double* Xs;             // [sumP*D]
+    const double* Z;              // [sumM*D]
+    double* theta;
+    double* nll;
+    double* grad;                 // or nullptr
+    int* status;
+    int* n_eval;
+    int* n_iter;                  // or nullptr
+    double* f_mean;
+    double* f_var;
+    double* y_var;
+    const int* order;             // [T] processing order
+    int* queue;                   // zeroed before launch
+    double* ws;                   // per-workgroup workspace
+    size_t ws_stride;             // doubles per workgroup
+};
+#define GPSAT_MAX_INDUCING 1024    // largest M per tile (workspace: (7 + D) M^2 doubles per workgroup)
+size_t sgpr_shared_bytes(int D, int Mmax);
+size_t sgpr_workspace_doubles_per_wg(int D, int Mmax);
+int sgpr_threads();
+hipError_t launch_sgpr(int D, const SgprArgs& a, int grid, size_t smem, hipStream_t stream);
+
 }  // namespace gpsat
 #endif

@@ -187,6 +187,100 @@ class Engine:
                            grad=grad, kernel_ms=km.value, total_ms=tm.value,
                            f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
 
+    def sgpr_fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, z_off, Z, theta0, lo=None, hi=None,
+                               trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000, max_ls=0,
+                               ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False, jitter=0.0, out=None,
+                               dtype="f64", full_cov=False) -> BatchResult:
+        """Sparse GP experts (gpsat_sgpr_fit_predict_batch): GPflow SGPR with fixed inducing points Z [sumM, D] per tile
+        (CSR ``z_off`` [T+1]).  Arguments and result as ``fit_predict_batch``, except: fp64 only, no ``full_cov``, no
+        per-tile observation limit, ``nll`` is the negative ELBO.  Host coordinates are centred per tile (X, Xs and Z by
+        the tile's mean observation coordinate) before the call; device tensors are taken as they are."""
+        if dtype != "f64":
+            raise NotImplementedError("sparse GP experts are built in fp64 only (dtype='f64')")
+        if full_cov:
+            raise NotImplementedError("sparse GP experts do not return the full covariance")
+        obs_off = np.ascontiguousarray(obs_off, dtype=np.int64)
+        pred_off = np.ascontiguousarray(pred_off, dtype=np.int64)
+        z_off = np.ascontiguousarray(z_off, dtype=np.int64)
+        T = len(obs_off) - 1
+        H = D + 2
+        assert len(pred_off) == T + 1 and len(z_off) == T + 1
+        theta0 = np.ascontiguousarray(np.broadcast_to(np.asarray(theta0, dtype=np.float64), (T, H)))
+        lo = np.full((T, H), np.nan) if lo is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (T, H)))
+        hi = np.full((T, H), np.nan) if hi is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (T, H)))
+        trainable = np.ones(H, dtype=np.uint8) if trainable is None else \
+            np.ascontiguousarray(np.asarray(trainable).astype(bool).astype(np.uint8))
+        assert trainable.shape == (H,)
+        sumN, sumP, sumM = int(obs_off[-1]), int(pred_off[-1]), int(z_off[-1])
+        device_mode = not isinstance(X, np.ndarray)
+        if device_mode:
+            import torch
+            for tname, t_ in (("X", X), ("y", y), ("Xs", Xs), ("Z", Z)):
+                if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()):
+                    raise GpsatError(f"{tname}: device mode needs contiguous f64 CUDA tensors")
+            if X.device.index != self.device_id:
+                raise GpsatError(f"tensors live on cuda:{X.device.index}, engine on device {self.device_id}")
+            assert X.numel() == sumN * D and y.numel() == sumN and Xs.numel() == sumP * D and Z.numel() == sumM * D
+            if out is None:
+                fm = torch.empty(max(sumP, 1), dtype=torch.float64, device=X.device)
+                fv = torch.empty_like(fm)
+                yv = torch.empty_like(fm)
+            else:
+                fm, fv, yv = out
+            torch.cuda.current_stream(X.device).synchronize()
+            pX, py, pXs, pZ = X.data_ptr(), y.data_ptr(), Xs.data_ptr(), Z.data_ptr()
+            pfm, pfv, pyv = fm.data_ptr(), fv.data_ptr(), yv.data_ptr()
+        else:
+            X = np.asarray(X, dtype=np.float64).reshape(sumN, D)
+            Xs = np.asarray(Xs, dtype=np.float64).reshape(sumP, D)
+            Z = np.asarray(Z, dtype=np.float64).reshape(sumM, D)
+            Ns = np.diff(obs_off)
+            c = np.zeros((T, D))
+            nz = Ns > 0
+            if nz.any():
+                c[nz] = np.add.reduceat(X, obs_off[:-1][nz], axis=0) / Ns[nz, None]
+            X = np.ascontiguousarray(X - np.repeat(c, Ns, axis=0))
+            Xs = np.ascontiguousarray(Xs - np.repeat(c, np.diff(pred_off), axis=0))
+            Z = np.ascontiguousarray(Z - np.repeat(c, np.diff(z_off), axis=0))
+            y = np.ascontiguousarray(y, dtype=np.float64).reshape(sumN)
+            fm = np.empty(sumP, dtype=np.float64)
+            fv = np.empty(sumP, dtype=np.float64)
+            yv = np.empty(sumP, dtype=np.float64)
+            pX, py, pXs, pZ = _ptr(X), _ptr(y), _ptr(Xs), _ptr(Z)
+            pfm, pfv, pyv = _ptr(fm), _ptr(fv), _ptr(yv)
+        theta = np.empty((T, H), dtype=np.float64)
+        nll = np.empty(T, dtype=np.float64)
+        grad = np.empty((T, H), dtype=np.float64) if want_grad else None
+        status = np.empty(T, dtype=np.int32)
+        n_eval = np.empty(T, dtype=np.int32)
+        n_iter = np.zeros(T, dtype=np.int32)
+        b = L.GpsatBatch()
+        b.T, b.D, b.dtype = T, D, L.F64
+        b.kernel = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        b.memory = L.MEM_DEVICE if device_mode else L.MEM_HOST
+        b.optimiser = L.OPT_IDS[optimiser] if not isinstance(optimiser, int) else optimiser
+        b.max_iter, b.max_ls = int(max_iter), int(max_ls)
+        b.ftol, b.gtol, b.adam_lr = float(ftol), float(gtol), float(adam_lr)
+        b.obs_off, b.pred_off = _ptr(obs_off), _ptr(pred_off)
+        b.theta0, b.lo, b.hi, b.trainable = _ptr(theta0), _ptr(lo), _ptr(hi), _ptr(trainable)
+        b.X, b.y, b.Xs = pX, py, pXs
+        b.theta, b.nll, b.grad = _ptr(theta), _ptr(nll), _ptr(grad)
+        b.status, b.n_eval, b.n_iter = _ptr(status), _ptr(n_eval), _ptr(n_iter)
+        b.f_mean, b.f_var, b.y_var = pfm, pfv, pyv
+        b.cov_off, b.f_cov = None, None
+        sp = L.GpsatSparse()
+        sp.z_off, sp.Z, sp.jitter = _ptr(z_off), pZ, float(jitter)
+        rc = self._lib.gpsat_sgpr_fit_predict_batch(self._h, C.byref(b), C.byref(sp))
+        if rc != 0:
+            raise GpsatError(f"gpsat_sgpr_fit_predict_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        km, tm = C.c_double(), C.c_double()
+        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
+        if device_mode:
+            fm, fv, yv = fm[:sumP], fv[:sumP], yv[:sumP]
+        return BatchResult(theta=theta, nll=nll, status=status, n_eval=n_eval, n_iter=n_iter, f_mean=fm, f_var=fv, y_var=yv,
+                           grad=grad, kernel_ms=km.value, total_ms=tm.value)
 
     def select_batch(self, points: np.ndarray, refs: np.ndarray, criteria, points_cm: np.ndarray = None):
         """Batched tile selection on the GPU (gpsat_select_batch).

@@ -34,11 +34,18 @@ Supported config subset (anything else raises ``NotImplementedError`` -- never a
   pred_loc_config   : {"method": "expert_loc"} | {"method": "from_dataframe", "df": DataFrame, "max_dist": float,
                        "local_select": optional} | {"method": "from_source", "load_kwargs": {"source": DataFrame | path},
                        "max_dist": ..} | {"method": "shift_arrays", "<coord>": array, ...}
-  model_config      : {"oi_model": "HipGPRModel" | "GPflowGPRModel" | {"path_to_model", "model_name"},
+  model_config      : {"oi_model": "HipGPRModel" | "GPflowGPRModel" | "HipSGPRModel" | "GPflowSGPRModel" |
+                                   {"path_to_model", "model_name"},
                        "init_params", "constraints", "optim_kwargs", "pred_kwargs", "params_to_store",
                        "load_params": {"file": store dir | dict of tables, "table_suffix": str, "param_names": [..],
                                        "index_adjust": {col: {"func": callable | "lambda ..."}}} |
                                       {<param>: value, ...}  (set directly on every tile)}
+Sparse experts (``oi_model`` GPflowSGPRModel / HipSGPRModel, fp64): the main profile runs through
+``gpsat_sgpr_fit_predict_batch`` with no per-tile observation limit; ``init_params`` may hold ``num_inducing_points``
+(default 500) and ``inducing_seed`` (default 0); every expert's inducing points are those HipSGPRModel picks
+(``select_inducing_points`` with the expert's position in the expert locations), stored in the table ``inducing_points``
+(``_dim_0`` inducing index, ``_dim_1`` coordinate, scaled coordinates); ``objective_value`` is the ELBO.  The replacement
+profile stays an exact GP.
 ``replacement_*`` model settings for tiles below ``replacement_threshold`` observations are honoured (one engine call
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
@@ -65,11 +72,14 @@ from scipy.spatial import cKDTree
 
 from . import _lib as L
 from . import sharding
-from .models import HipGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND, clamp_within
+from .models import (HipGPRModel, HipSGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND, SGPR_MODEL_NAMES, clamp_within,
+                     select_inducing_points)
 
 _COMPS = {">=": np.greater_equal, ">": np.greater, "==": np.equal, "<": np.less, "<=": np.less_equal}
 PARAM_NAMES = ["lengthscales", "kernel_variance", "likelihood_variance"]
 MODEL_NAME = f"{HipGPRModel.__module__}.{HipGPRModel.__name__}"[:64]
+SGPR_MODEL_NAME = f"{HipSGPRModel.__module__}.{HipSGPRModel.__name__}"[:64]
+SGPR_INIT_KEYS = ("num_inducing_points", "inducing_seed")
 DTYPES = ("f32", "f64")
 
 
@@ -641,11 +651,21 @@ def _adjust_func(spec):
 # ----------------------------------------------------------------------------------------------------------
 class BatchedLocalExpertOI:
     def __init__(self, expert_loc_config: dict, data_config: dict, model_config: dict, pred_loc_config: dict,
-                 engine=None, device_select: bool = False, dtype: str = "f32"):
+                 engine=None, device_select: bool = False, dtype: Optional[str] = None):
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
+        om = model_config.get("oi_model", "HipGPRModel")
+        name = om["model_name"] if isinstance(om, dict) else om
+        if name not in ("HipGPRModel", "GPflowGPRModel") + SGPR_MODEL_NAMES:
+            raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP and SGPR experts only")
+        self.sgpr = name in SGPR_MODEL_NAMES
+        # dtype None: fp32 for exact-GP experts, fp64 for sparse ones (built in fp64 only -- an explicit fp32 is refused)
+        if dtype is None:
+            dtype = "f64" if self.sgpr else "f32"
         if dtype not in DTYPES:
-            raise ValueError("dtype must be 'f32' (default) or 'f64' (the reference's precision)")
+            raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
+        if self.sgpr and dtype != "f64":
+            raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
         self.dtype = dtype
         # ---- data (local_experts.py:266-290)
         self.obs_col = data_config["obs_col"]
@@ -665,10 +685,6 @@ class BatchedLocalExpertOI:
                 raise NotImplementedError(f"expert_loc_config key '{k}' is not supported by the batched backend")
         self.expert_locs = xl.reset_index(drop=True)
         # ---- model (local_experts.py:292-346)
-        om = model_config.get("oi_model", "HipGPRModel")
-        name = om["model_name"] if isinstance(om, dict) else om
-        if name not in ("HipGPRModel", "GPflowGPRModel"):
-            raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP expert only")
         self.init_params = dict(model_config.get("init_params") or {})
         self.constraints = model_config.get("constraints")
         self.optim_kwargs = dict(model_config.get("optim_kwargs") or {})
@@ -678,7 +694,16 @@ class BatchedLocalExpertOI:
         # optim_kwargs / pred_kwargs to {}
         self.replacement_threshold = model_config.get("replacement_threshold")
         self.profiles = {"main": dict(init_params=self.init_params, constraints=self.constraints,
-                                      optim_kwargs=self.optim_kwargs, pred_kwargs=self.pred_kwargs)}
+                                      optim_kwargs=self.optim_kwargs, pred_kwargs=self.pred_kwargs, sgpr=self.sgpr)}
+        if self.sgpr:
+            if self.pred_kwargs.get("full_cov", False):
+                raise NotImplementedError("sparse (SGPR) experts do not return the full covariance (pred_kwargs.full_cov)")
+            if self.optim_kwargs.get("train_inducing_points", False):
+                raise NotImplementedError("train_inducing_points=True is not built: the inducing points stay fixed")
+            M = int(self.init_params.get("num_inducing_points", 500))
+            if not 1 <= M <= L.max_inducing("f64", len(data_config["coords_col"])):
+                raise ValueError(f"num_inducing_points={M}: 1..{L.max_inducing('f64', len(data_config['coords_col']))} "
+                                 f"are built (gpsat_max_inducing)")
         if self.replacement_threshold is not None:
             rm = model_config.get("replacement_model")
             rname = rm["model_name"] if isinstance(rm, dict) else rm
@@ -686,13 +711,26 @@ class BatchedLocalExpertOI:
                 raise NotImplementedError(f"replacement_model '{rname}': the batched backend builds the exact-GP expert only")
             rip = model_config.get("replacement_init_params")
             rco = model_config.get("replacement_constraints")
+            main_ip = {k: v for k, v in self.init_params.items() if k not in SGPR_INIT_KEYS}
             self.profiles["replacement"] = dict(
-                init_params=self.init_params if rip is None else dict(rip),
+                sgpr=False,
+                init_params=main_ip if rip is None else dict(rip),
                 constraints=self.constraints if rco is None else rco,
                 optim_kwargs=dict(model_config.get("replacement_optim_kwargs") or {}),
                 pred_kwargs=dict(model_config.get("replacement_pred_kwargs") or {}))
-        self.params_to_store = model_config.get("params_to_store") or PARAM_NAMES
+        self.params_to_store = model_config.get("params_to_store") or (PARAM_NAMES + ["inducing_points"] if self.sgpr
+                                                                        else PARAM_NAMES)
+        bad = [p_ for p_ in self.params_to_store if p_ not in PARAM_NAMES + (["inducing_points"] if self.sgpr else [])]
+        if bad:
+            raise NotImplementedError(f"params_to_store {bad}: not a parameter of this model")
         self.load_params = model_config.get("load_params")
+        if self.sgpr and self.load_params is not None:
+            lp_ = self.load_params
+            if lp_.get("previous"):
+                raise NotImplementedError("load_params.previous=True is not built for sparse (SGPR) experts")
+            if "inducing_points" in (lp_.get("param_names") or []) or "inducing_points" in lp_:
+                raise NotImplementedError("loading inducing_points is not built: every expert picks its own "
+                                          "(num_inducing_points / inducing_seed); load the three hyper-parameters only")
         # load_params.previous (local_experts.py:1059-1064): start every tile from the running average of earlier optima.
         # What the reference's load_params does with the combinations (local_experts.py:553-609: `if file is not None: ...
         # elif previous is not None: param_dict = previous_params`):
@@ -729,8 +767,9 @@ class BatchedLocalExpertOI:
     def _template(self, pf):
         D = len(self.coords_col)
         dummy = pd.DataFrame({**{c: [0.0, 1.0] for c in self.coords_col}, self.obs_col: [0.0, 1.0]})
+        ip = {k: v for k, v in pf["init_params"].items() if k not in SGPR_INIT_KEYS}
         m = HipGPRModel(data=dummy, obs_col=self.obs_col, coords_col=self.coords_col, engine=self.engine,
-                        verbose=False, dtype=self.dtype, **pf["init_params"])
+                        verbose=False, dtype=self.dtype, **ip)
         theta_default = m._theta.copy()
         cons = None
         if pf["constraints"] is not None:
@@ -750,7 +789,10 @@ class BatchedLocalExpertOI:
                     clamp=clamp, coords_scale=np.broadcast_to(m.coords_scale, (1, D)).astype(np.float64),
                     obs_scale=float(m.obs_scale.reshape(-1)[0]),
                     local_mean=isinstance(pf["init_params"].get("obs_mean"), str) and pf["init_params"]["obs_mean"] == "local",
-                    unconstrained_noise=not np.isfinite(m._lo[D + 1]), device=str(m.gpu_name)[:64])
+                    unconstrained_noise=not np.isfinite(m._lo[D + 1]), device=str(m.gpu_name)[:64],
+                    sgpr=bool(pf.get("sgpr")), model=SGPR_MODEL_NAME if pf.get("sgpr") else MODEL_NAME,
+                    n_inducing=int(pf["init_params"].get("num_inducing_points", 500)),
+                    inducing_seed=int(pf["init_params"].get("inducing_seed", 0)))
 
     def _load_param_tables(self, store: "ResultStore", table_suffix):
         """load_params tables, read ONCE per run and indexed by expert coordinates (local_experts.py:553-689)."""
@@ -898,19 +940,20 @@ class BatchedLocalExpertOI:
         # item kinds: 0 skipped silently (no prediction locations, local_experts.py:962-965), 1 stub row
         # (N < min_obs, :988-1012), 2 tile, 3 error row (tile larger than the kernels take)
         kind = np.full(len(ex), 2, dtype=np.int8)
-        # largest tile the kernels take (gpsat_max_tile_obs): larger ones get an explicit error row instead of failing
-        # the whole batch
-        max_obs = L.max_tile_obs(self.dtype, D)
-        kind[n_obs > max_obs] = 3
-        kind[n_obs < min_obs] = 1
-        kind[n_pred == 0] = 0
-        if (kind == 3).any():
-            warnings.warn(f"{int((kind == 3).sum())} expert locations select more than {max_obs} "
-                          f"observations: not run (error row in run_details)")
         is_repl = (n_obs < self.replacement_threshold) if self.replacement_threshold is not None \
             else np.zeros(len(ex), dtype=bool)                      # local_experts.py:1021-1041
         prof_names = list(self.profiles)
         prof_id = np.where(is_repl, prof_names.index("replacement") if "replacement" in prof_names else 0, 0)
+        sgpr_prof = np.array([bool(self.profiles[p_].get("sgpr")) for p_ in prof_names])
+        # largest tile the exact kernels take (gpsat_max_tile_obs): larger ones get an explicit error row instead of failing
+        # the whole batch.  Sparse tiles have no such limit (the kernel counts rows in 32-bit integers).
+        max_obs = L.max_tile_obs(self.dtype, D)
+        kind[np.where(sgpr_prof[prof_id], n_obs > 2 ** 31 - 1, n_obs > max_obs)] = 3
+        kind[n_obs < min_obs] = 1
+        kind[n_pred == 0] = 0
+        if (kind == 3).any():
+            warnings.warn(f"{int((kind == 3).sum())} expert locations select more observations than the kernels take "
+                          f"(exact GP: {max_obs}): not run (error row in run_details)")
         tmpl, pinfo = {}, {}
         for pi, pname in enumerate(prof_names):
             pf = self.profiles[pname]
@@ -977,10 +1020,19 @@ class BatchedLocalExpertOI:
         self.timings.update(engine_s=0.0, engine_call_s=0.0, kernel_s=0.0, tables_s=0.0, flush_s=0.0)
         self.timings["calls"] = []          # per engine call: (job, tiles, start, end, kernel seconds), times from the start of run()
 
+        def inducing_for(i):
+            """The inducing points of item i (scaled coordinates): what HipSGPRModel picks for the same rows."""
+            t_ = tmpl[prof_id[i]]
+            Xd = coords_all[idx[off[i]:off[i + 1]]] / t_["coords_scale"]
+            return select_inducing_points(Xd, t_["n_inducing"], t_["inducing_seed"], int(ex[i]))
+
         def tables_for(items, fixed, pred_cat, cov_cat=None, with_preds=True):
             return self._tables(ex[items], locs[items], kind[items], n_obs[items], fixed, pred_cat,
                                 (pcs, items) if predict else None, save_params[items],
                                 [tmpl[p]["device"] for p in prof_id[items]], optimise, config_id, table_suffix,
+                                models=[tmpl[p]["model"] for p in prof_id[items]],
+                                inducing=[inducing_for(i) if (kind[i] == 2 and tmpl[prof_id[i]]["sgpr"]) else None
+                                          for i in items] if "inducing_points" in self.params_to_store else None,
                                 cov_cat=cov_cat, cov_tiles=(kind[items] == 2) & np.array([pinfo[p]["full_cov"] for p in prof_id[items]], dtype=bool)
                                 if want_cov else None, with_preds=with_preds)
 
@@ -1035,7 +1087,14 @@ class BatchedLocalExpertOI:
             else:
                 for f_ in [self._sub_pool().submit(sub, int(bounds[j]), int(bounds[j + 1])) for j in range(nsub)]:
                     f_.result()
-            return dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
+            out = dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
+            if t_["sgpr"]:
+                # per tile the inducing points HipSGPRModel picks: a seeded subset of the tile's scaled coordinates
+                Zs = [select_inducing_points(X[o_off[j]:o_off[j + 1]], t_["n_inducing"], t_["inducing_seed"], int(ex[i]))
+                      for j, i in enumerate(ids)]
+                out["z_off"] = np.concatenate([[0], np.cumsum([len(z) for z in Zs])]).astype(np.int64)
+                out["Z"] = np.concatenate(Zs) if Zs else np.zeros((0, D))
+            return out
 
         # ---------------- pass 2: waves of one shard ----------------
         # A wave (the flush unit) is cut into engine calls of at most `engine_chunk` tiles; the next call's arrays are packed
@@ -1132,12 +1191,19 @@ class BatchedLocalExpertOI:
                 eng_ = free_engines.get()
                 try:
                     te = time.perf_counter()
-                    r = eng_.fit_predict_batch(D=D, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"],
-                                               Xs=pk["Xs"], theta0=theta0[ids] if th_override is None else th_override,
-                                               lo=lo[ids], hi=hi[ids], trainable=t_["trainable"], kernel=p_["kernel"],
-                                               optimiser=p_["optimiser"], max_iter=p_["max_iter"],
-                                               dtype=self.dtype, **p_["eng_kw"],
-                                               **({"full_cov": True} if p_["full_cov"] else {}))
+                    if t_["sgpr"]:
+                        r = eng_.sgpr_fit_predict_batch(D=D, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"],
+                                                        Xs=pk["Xs"], z_off=pk["z_off"], Z=pk["Z"], theta0=theta0[ids],
+                                                        lo=lo[ids], hi=hi[ids], trainable=t_["trainable"],
+                                                        kernel=p_["kernel"], optimiser=p_["optimiser"],
+                                                        max_iter=p_["max_iter"], dtype="f64", **p_["eng_kw"])
+                    else:
+                        r = eng_.fit_predict_batch(D=D, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"],
+                                                   Xs=pk["Xs"], theta0=theta0[ids] if th_override is None else th_override,
+                                                   lo=lo[ids], hi=hi[ids], trainable=t_["trainable"], kernel=p_["kernel"],
+                                                   optimiser=p_["optimiser"], max_iter=p_["max_iter"],
+                                                   dtype=self.dtype, **p_["eng_kw"],
+                                                   **({"full_cov": True} if p_["full_cov"] else {}))
                     t1 = time.perf_counter()
                     self.timings["calls"].append((k, len(ids), round(te - t_start, 4), round(t1 - t_start, 4), round(r.kernel_ms * 1e-3, 4)))
                     return pk, r, t1 - te
@@ -1186,7 +1252,7 @@ class BatchedLocalExpertOI:
                         self.timings["kernel_s"] += r.kernel_ms * 1e-3
                         dt = call_s / len(ids)
                         fixed[loc_ids, :H] = r.theta
-                        fixed[loc_ids, H] = r.nll
+                        fixed[loc_ids, H] = -r.nll if t_["sgpr"] else r.nll      # SGPR: the ELBO (gpflow_models.py:860-862)
                         fixed[loc_ids, H + 1] = r.status
                         fixed[loc_ids, H + 2] = r.n_eval
                         fixed[loc_ids, H + 3] = r.n_iter if getattr(r, "n_iter", None) is not None else np.nan
@@ -1321,7 +1387,7 @@ class BatchedLocalExpertOI:
         return pd.DataFrame(pr, index=_index_for_repeated(cc, locs, cnt))
 
     def _tables(self, ex_ids, locs, kind, n_obs, fixed, pred_cat, pcs, save_params, devices, optimise, config_id,
-                table_suffix, cov_cat=None, cov_tiles=None, with_preds=True):
+                table_suffix, cov_cat=None, cov_tiles=None, with_preds=True, models=None, inducing=None):
         """Reference-layout tables for a run of items (rows of ``fixed`` align with the items, ``pred_cat`` holds the
         predictions of the tiles among them back to back).  Pure array assembly (GPSat/local_experts.py:691-747)."""
         cc = self.coords_col
@@ -1335,12 +1401,22 @@ class BatchedLocalExpertOI:
             "run_time": np.where(tile, fixed[:, H + 4], np.nan), "objective_value": np.where(tile, fixed[:, H], np.nan),
             "parameters_optimised": np.full(n, bool(optimise)),
             "optimise_success": tile & bool(optimise) & (status == 0),
-            "model": np.full(n, MODEL_NAME, dtype=object),
+            "model": np.full(n, MODEL_NAME, dtype=object) if models is None else np.array(models, dtype=object),
             "device": np.array([d if t else "" for d, t in zip(devices, tile)], dtype=object),
             "config_id": np.full(n, config_id, dtype=np.int64)}, index=_index_for(cc, locs))
         sp = tile & save_params
         slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
         for pn in self.params_to_store:
+            if pn == "inducing_points":
+                # [M, D] per expert: _dim_0 inducing index, _dim_1 coordinate (dict_of_array_to_table of a 2-D array)
+                zs = [(j, z) for j, z in enumerate(inducing or []) if z is not None and sp[j]]
+                cnt = np.array([z.size for _, z in zs], dtype=np.int64)
+                out[pn] = pd.DataFrame({
+                    "_dim_0": np.concatenate([np.repeat(np.arange(len(z)), z.shape[1]) for _, z in zs]) if zs else np.zeros(0, np.int64),
+                    "_dim_1": np.concatenate([np.tile(np.arange(z.shape[1]), len(z)) for _, z in zs]) if zs else np.zeros(0, np.int64),
+                    pn: np.concatenate([z.reshape(-1) for _, z in zs]) if zs else np.zeros(0)},
+                    index=_index_for_repeated(cc, locs[[j for j, _ in zs]] if zs else np.zeros((0, D)), cnt))
+                continue
             start, width = slots[pn]
             vals = fixed[sp, start:start + width].reshape(-1)
             out[pn] = pd.DataFrame({"_dim_0": np.tile(np.arange(width), int(sp.sum())), pn: vals},

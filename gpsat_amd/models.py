@@ -343,9 +343,101 @@ class HipGPRModel:
         return out
 
 
+def select_inducing_points(coords: np.ndarray, num_inducing_points: int, seed: int = 0, expert_index: int = 0) -> np.ndarray:
+    """Inducing points of one expert (GPflowSGPRModel.__init__, gpflow_models.py:836-847, made reproducible): all the
+    coordinates when there are at most ``num_inducing_points`` of them, else a random subset of that many rows drawn
+    with ``np.random.default_rng([seed, expert_index])`` (the reference shuffles with the unseeded global generator).
+    The batched orchestrator and the per-tile model pick the same rows."""
+    assert num_inducing_points is not None, "num_inducing_points is None, must be specified for SGPR"
+    coords = np.asarray(coords, dtype=np.float64)
+    M = int(num_inducing_points)
+    if M < 1:
+        raise ValueError("num_inducing_points must be at least 1")
+    if len(coords) <= M:
+        return coords.copy()
+    rows = np.random.default_rng([int(seed), int(expert_index)]).permutation(len(coords))[:M]
+    return coords[rows].copy()
+
+
+class HipSGPRModel(HipGPRModel):
+    """Sparse GP regression (SGPR, the collapsed Titsias bound) for one expert tile on MI355X, with fixed inducing points
+    (mirror of GPflowSGPRModel, gpflow_models.py:666-901).  For tiles larger than the exact path takes
+    (gpsat_max_tile_obs): cost O(N M^2) per evaluation, no limit on N.  fp64 only."""
+
+    def __init__(self, data=None, coords_col=None, obs_col=None, coords=None, obs=None,
+                 coords_scale=None, obs_scale=None, obs_mean=None, verbose=True, *,
+                 kernel="Matern32", num_inducing_points=500, kernel_kwargs=None, mean_function=None,
+                 mean_func_kwargs=None, noise_variance=None, likelihood=None, engine=None, dtype="f64",
+                 inducing_seed=0, expert_index=0, **kwargs):
+        if dtype != "f64":
+            raise NotImplementedError("HipSGPRModel is built in fp64 only (dtype='f64')")
+        super().__init__(data=data, coords_col=coords_col, obs_col=obs_col, coords=coords, obs=obs,
+                         coords_scale=coords_scale, obs_scale=obs_scale, obs_mean=obs_mean, verbose=verbose,
+                         kernel=kernel, kernel_kwargs=kernel_kwargs, mean_function=mean_function,
+                         mean_func_kwargs=mean_func_kwargs, noise_variance=noise_variance, likelihood=likelihood,
+                         engine=engine, dtype="f64", **kwargs)
+        self.num_inducing_points = int(num_inducing_points)
+        if self.num_inducing_points > L.max_inducing("f64", self.D):
+            raise ValueError(f"num_inducing_points={num_inducing_points}: at most {L.max_inducing('f64', self.D)} "
+                             f"are built (gpsat_max_inducing)")
+        self.inducing_points = select_inducing_points(self.coords, self.num_inducing_points, inducing_seed, expert_index)
+
+    @property
+    def param_names(self) -> List[str]:
+        return ["lengthscales", "kernel_variance", "likelihood_variance", "inducing_points"]
+
+    def get_inducing_points(self) -> np.ndarray:
+        """Inducing points [M, D] in the model's (scaled) coordinates."""
+        return self.inducing_points.copy()
+
+    def set_inducing_points(self, inducing_points):
+        Z = np.atleast_2d(np.asarray(inducing_points, dtype=np.float64))
+        if Z.shape[1] != self.D:
+            raise AssertionError(f"inducing_points must have shape [M, {self.D}]")
+        if not 1 <= len(Z) <= L.max_inducing("f64", self.D):
+            raise ValueError(f"1..{L.max_inducing('f64', self.D)} inducing points are built")
+        self.inducing_points = Z.copy()
+
+    def set_inducing_points_constraints(self, *args, **kwargs):
+        raise NotImplementedError("inducing points are fixed in the HIP backend (no constraints)")
+
+    def _run(self, *, optimiser, max_iter=0, pred_coords=None, full_cov=False, **opt_kwargs):
+        if full_cov:
+            raise NotImplementedError("HipSGPRModel.predict(full_cov=True) is not built")
+        N, D = self.coords.shape
+        P = 0 if pred_coords is None else len(pred_coords)
+        Xs = np.zeros((0, D)) if pred_coords is None else pred_coords
+        Z = self.inducing_points
+        return self._engine.sgpr_fit_predict_batch(
+            D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, P]), Xs=Xs,
+            z_off=np.array([0, len(Z)]), Z=Z, theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
+            trainable=self._trainable, kernel=self.kernel, optimiser=optimiser, max_iter=max_iter, **opt_kwargs)
+
+    def optimise_parameters(self, train_inducing_points=False, max_iter=10_000, fixed_params=None, **opt_kwargs):
+        """L-BFGS on the three hyper-parameters with Z fixed (gpflow_models.py:865-901)."""
+        if train_inducing_points:
+            raise NotImplementedError("train_inducing_points=True is not built: the inducing points stay fixed")
+        return super().optimise_parameters(max_iter=max_iter, fixed_params=fixed_params, **opt_kwargs)
+
+    def get_objective_function_value(self):
+        """The ELBO at the current parameters (gpflow_models.py:860-862) -- not its negative."""
+        r = self._run(optimiser="none")
+        return -float(r.nll[0])
+
+    def predict(self, coords, full_cov=False, apply_scale=True) -> Dict[str, np.ndarray]:
+        if full_cov:
+            raise NotImplementedError("HipSGPRModel.predict(full_cov=True) is not built")
+        return super().predict(coords, full_cov=False, apply_scale=apply_scale)
+
+
+SGPR_MODEL_NAMES = ("HipSGPRModel", "GPflowSGPRModel")
+
+
 def get_model(name):
-    """Registry hook with the reference's semantics (GPSat/models/__init__.py:3-28): the exact-GP
-    names resolve to the HIP backend; anything else is NotImplementedError."""
+    """Registry hook with the reference's semantics (GPSat/models/__init__.py:3-28): the exact-GP names resolve to
+    HipGPRModel, the sparse ones to HipSGPRModel; anything else is NotImplementedError."""
     if name in ("HipGPRModel", "GPflowGPRModel"):
         return HipGPRModel
+    if name in SGPR_MODEL_NAMES:
+        return HipSGPRModel
     raise NotImplementedError(f"model with name: '{name}' is not implemented")

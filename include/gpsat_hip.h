@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GPSAT_ABI_VERSION 3
+#define GPSAT_ABI_VERSION 4
 
 /* error codes */
 #define GPSAT_OK            0
@@ -236,6 +236,35 @@ int gpsat_glue_batch(gpsat_handle *h, int64_t R, int32_t G, int32_t ndim, int32_
  * handle's stream: kernel_ms = the persistent tile kernel alone, total_ms = H2D + kernel + D2H.
  */
 int gpsat_last_timing(gpsat_handle *h, double *kernel_ms, double *total_ms);
+
+/*
+ * Sparse GP experts (ABI >= 4): GPflow SGPR, the collapsed Titsias bound, with FIXED inducing points Z
+ * (GPflowSGPRModel, GPSat/models/gpflow_models.py:666-901, train_inducing_points=False).  Replaces, per tile,
+ * model = GPflowSGPRModel(...); model.optimise_parameters(); model.get_objective_function_value(); model.predict(...).
+ * A tile holds at most 2^31 - 1 observations and prediction points (the kernel counts rows in 32-bit integers), no
+ * other limit than device memory, and 1 <= M_t <= gpsat_max_inducing(dtype, D) inducing points.
+ * Workspace: (7 + D) Mmax^2 + (16 + 1024) Mmax doubles per resident workgroup (Mmax = the batch's largest M_t; about
+ * 100 MB at Mmax = 1024, D = 4), at most one workgroup per CU and at most 16 GiB in all.  The handle keeps the largest
+ * workspace it has allocated until gpsat_destroy.
+ */
+typedef struct gpsat_sparse {
+    const int64_t *z_off;   /* [T+1] host: CSR row offsets into Z; 1 <= M_t <= gpsat_max_inducing(dtype, D) */
+    const void    *Z;       /* [sum M, D] inducing points, same frame / memory / dtype as X                  */
+    double         jitter;  /* 0 = 1e-6 (GPflow default_jitter)                                              */
+    int32_t        reserved[8];
+} gpsat_sparse;
+
+/*
+ * fit (optional) + objective + predict of T sparse expert tiles.  `b` as for gpsat_fit_predict_batch, except:
+ * dtype must be GPSAT_F64, cov_off / f_cov must be NULL (no full covariance), there is no per-tile observation limit,
+ * nll is the negative ELBO and grad its gradient.  Status codes as for the exact path: a failed Cholesky of Kuu or of
+ * I + A A^T gives GPSAT_STATUS_NOT_PD, a tile without observations GPSAT_STATUS_SKIPPED.  gpsat_last_timing covers it.
+ */
+int gpsat_sgpr_fit_predict_batch(gpsat_handle *h, const gpsat_batch *b, const gpsat_sparse *s);
+
+/* Largest number of inducing points per tile for gpsat_sgpr_fit_predict_batch: 1024 for GPSAT_F64 and D = 1..4
+ * (a workspace choice: (7 + D) M^2 doubles per workgroup); 0 for GPSAT_F32 and unsupported arguments.  ABI >= 4. */
+int gpsat_max_inducing(int dtype, int D);
 
 #ifdef __cplusplus
 }
