@@ -24,7 +24,7 @@ STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5:
 EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
-           "gpsat_max_inducing"]
+           "gpsat_max_inducing", "gpsat_select_batch_ex"]
 
 
 class GpsatOpts(C.Structure):
@@ -128,6 +128,9 @@ def load():
     lib.gpsat_select_batch.restype = C.c_int
     lib.gpsat_select_batch.argtypes = [C.c_void_p, C.POINTER(GpsatSelectSpec), C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.gpsat_select_batch_ex.restype = C.c_int
+    lib.gpsat_select_batch_ex.argtypes = [C.c_void_p, C.POINTER(GpsatSelectSpec), C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.gpsat_smooth_batch.restype = C.c_int
     lib.gpsat_smooth_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
     lib.gpsat_glue_batch.restype = C.c_int

@@ -59,9 +59,10 @@ struct DevBuf {
 
 }  // namespace
 
-// FNV-1a over all of `refs` and a sample of at most 65 536 evenly spaced elements of `points` (plus both ends): a caller who
-// refills the same host buffers between the sizes call and the fill call gets a fresh selection, not the cached one
-static unsigned long long sel_fingerprint(const double* points, long long nP, const double* refs, long long nR) {
+// FNV-1a over all of `refs` and `bounds` and a sample of at most 65 536 evenly spaced elements of `points` (plus both ends): a
+// caller who refills the same host buffers between the sizes call and the fill call gets a fresh selection, not the cached one
+static unsigned long long sel_fingerprint(const double* points, long long nP, const double* refs, long long nR,
+                                          const double* bounds, long long nB) {
     unsigned long long h = 1469598103934665603ull;
     auto mix = [&](const double* p) {
         unsigned long long v;
@@ -69,6 +70,7 @@ static unsigned long long sel_fingerprint(const double* points, long long nP, co
         h = (h ^ v) * 1099511628211ull;
     };
     for (long long i = 0; i < nR; ++i) mix(refs + i);
+    for (long long i = 0; i < nB; ++i) mix(bounds + i);
     const long long step = std::max<long long>(1, nP / 65536);
     for (long long i = 0; i < nP; i += step) mix(points + i);
     for (long long i = std::max<long long>(0, nP - 64); i < nP; ++i) mix(points + i);
@@ -88,9 +90,9 @@ struct gpsat_handle {
     // gpsat_select_batch is called twice per selection (sizes, then indices): the first call already leaves the indices on
     // the device; the second, when it repeats the first call's arguments, only copies them out
     struct {
-        const void *pts = nullptr, *refs = nullptr;
+        const void *pts = nullptr, *refs = nullptr, *bounds = nullptr;
         int64_t M = 0, total = -1;
-        int C = 0, T = 0;
+        int C = 0, T = 0, n_bounds = 0;
         gpsat_select_spec sp;
         unsigned long long fp = 0;     // fingerprint of the tables' CONTENTS at the sizes call
         const int* d_result = nullptr;
@@ -98,7 +100,7 @@ struct gpsat_handle {
     } selc;
     // device buffers (grown lazily, owned by the handle)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop;
-    DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord;
+    DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 2048] = {0};     // counters + event trace + per-workgroup start / end (diagnostic build)
@@ -171,7 +173,7 @@ int gpsat_destroy(gpsat_handle* h) {
     h->meta_i64.release(); h->meta_f64.release(); h->meta_misc.release(); h->out_f64.release();
     h->out_i32.release(); h->bulk_in.release(); h->bulk_out.release(); h->ws.release(); h->prof.release(); h->ring.release(); h->state.release(); h->coop.release();
     h->sel_pts.release(); h->sel_refs.release(); h->sel_cnt.release(); h->sel_idx.release(); h->sel_box.release();
-    h->sel_perm.release(); h->sel_keys.release(); h->sel_tmp.release(); h->sel_ord.release();
+    h->sel_perm.release(); h->sel_keys.release(); h->sel_tmp.release(); h->sel_ord.release(); h->sel_bnd.release();
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -677,16 +679,31 @@ int gpsat_sgpr_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b, const gp
 
 int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, int32_t C, const double* points,
                        int32_t T, const double* refs, int64_t* off, int32_t* idx, int64_t capacity) {
+    return gpsat_select_batch_ex(h, sp, M, C, points, T, refs, 0, nullptr, off, idx, capacity);
+}
+
+int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, int32_t C, const double* points,
+                          int32_t T, const double* refs, int32_t n_bounds, const double* bounds, int64_t* off, int32_t* idx,
+                          int64_t capacity) {
     if (!h || !sp || !off) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL argument");
-    if (T < 0 || M < 0 || C < 1) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad sizes");
+    if (T < 0 || M < 0 || C < 1 || n_bounds < 0) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad sizes");
     if (M > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_select_batch: more than 2^31-1 rows");
     if (sp->n_crit < 1 || sp->n_crit > GPSAT_SEL_MAXCRIT) return fail(GPSAT_EINVAL, "gpsat_select_batch: n_crit out of range");
     gpsat::SelectArgs a;
     std::memset(&a, 0, sizeof(a));
     a.n_crit = sp->n_crit;
     for (int k = 0; k < sp->n_crit; ++k) {
-        if (sp->kind[k] != 0 && sp->kind[k] != 1) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad criterion kind");
+        // kind 2 (per-expert interval) only through gpsat_select_batch_ex, which passes the bounds
+        if (sp->kind[k] != 0 && sp->kind[k] != 1 && !(sp->kind[k] == 2 && n_bounds > 0))
+            return fail(GPSAT_EINVAL, "gpsat_select_batch: bad criterion kind");
         if (sp->comp[k] < 0 || sp->comp[k] > 4) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad comparison");
+        if (sp->kind[k] == 2) {
+            if (sp->cols[k][0] < 0 || sp->cols[k][0] >= C) return fail(GPSAT_EINVAL, "gpsat_select_batch: column index out of range");
+            if (sp->cols[k][1] < 0 || sp->cols[k][1] >= n_bounds) return fail(GPSAT_EINVAL, "gpsat_select_batch: bound index out of range");
+            a.kind[k] = 2; a.comp[k] = sp->comp[k]; a.ncols[k] = 1;
+            a.cols[k][0] = sp->cols[k][0]; a.cols[k][1] = sp->cols[k][1];
+            continue;
+        }
         const int nc = sp->kind[k] == 0 ? 1 : sp->ncols[k];
         if (nc < 1 || nc > 3) return fail(GPSAT_EINVAL, "gpsat_select_batch: ball criteria take 1..3 columns");
         if (sp->kind[k] == 1 && sp->comp[k] != 3 && sp->comp[k] != 4) return fail(GPSAT_EINVAL, "gpsat_select_batch: ball criteria are < or <=");
@@ -698,10 +715,11 @@ int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, 
     }
     off[0] = 0;
     if (T == 0) return GPSAT_OK;
-    if ((M > 0 && !points) || !refs) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL table");
+    if ((M > 0 && !points) || !refs || (n_bounds > 0 && !bounds)) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL table");
+    const long long nB = (long long)T * n_bounds * 2;
     if (idx && h->selc.total >= 0 && h->selc.pts == points && h->selc.refs == refs && h->selc.M == M && h->selc.C == C &&
-        h->selc.T == T && std::memcmp(&h->selc.sp, sp, sizeof(*sp)) == 0 &&
-        h->selc.fp == sel_fingerprint(points, (long long)M * C, refs, (long long)T * C)) {
+        h->selc.T == T && h->selc.n_bounds == n_bounds && h->selc.bounds == bounds && std::memcmp(&h->selc.sp, sp, sizeof(*sp)) == 0 &&
+        h->selc.fp == sel_fingerprint(points, (long long)M * C, refs, (long long)T * C, bounds, nB)) {
         const int64_t total = h->selc.total;
         h->selc.total = -1;
         std::memcpy(off, h->selc.off.data(), (size_t)(T + 1) * sizeof(int64_t));
@@ -726,6 +744,13 @@ int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, 
     if ((rc = h->sel_cnt.reserve(2 * ncell * sizeof(long long)))) return rc;
     if (M > 0) HIP_TRY(hipMemcpyAsync(h->sel_pts.p, points, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->sel_refs.p, refs, (size_t)T * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.n_bounds = n_bounds;
+    a.bounds = nullptr;
+    if (n_bounds > 0) {
+        if ((rc = h->sel_bnd.reserve((size_t)nB * sizeof(double)))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->sel_bnd.p, bounds, (size_t)nB * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        a.bounds = static_cast<const double*>(h->sel_bnd.p);
+    }
     a.M = M; a.C = C; a.T = T;
     a.n_chunks = n_chunks; a.chunk_rows = chunk_rows;
     a.eorder = nullptr;
@@ -856,8 +881,9 @@ int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, 
     if (!idx) {
         // sizes asked for: the indices stay on the device for the call that follows with the same arguments
         h->selc.pts = points; h->selc.refs = refs; h->selc.M = M; h->selc.C = C; h->selc.T = T; h->selc.sp = *sp;
+        h->selc.bounds = bounds; h->selc.n_bounds = n_bounds;
         h->selc.d_result = d_final; h->selc.total = off[T];
-        h->selc.fp = sel_fingerprint(points, (long long)M * C, refs, (long long)T * C);
+        h->selc.fp = sel_fingerprint(points, (long long)M * C, refs, (long long)T * C, bounds, nB);
         h->selc.off.assign(off, off + T + 1);
     }
     return GPSAT_OK;

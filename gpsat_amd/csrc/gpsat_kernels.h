@@ -93,7 +93,7 @@ int state_words_w8();
 // tile selection (gpsat_select.hip); all pointers are device pointers
 struct SelectArgs {
     int n_crit;
-    int kind[GPSAT_SEL_MAXCRIT];      // 0: 1-D compare, 1: Euclidean ball
+    int kind[GPSAT_SEL_MAXCRIT];      // 0: 1-D compare, 1: Euclidean ball, 2: per-expert interval on cols[k][0], bounds cols[k][1]
     int comp[GPSAT_SEL_MAXCRIT];      // 0 >=, 1 >, 2 ==, 3 <, 4 <=
     int ncols[GPSAT_SEL_MAXCRIT];
     int cols[GPSAT_SEL_MAXCRIT][3];
@@ -110,6 +110,8 @@ struct SelectArgs {
     int* idx;                         // [off[T]] (fill pass)
     const double* box;                // [ceil(M / sub)][C][2] per-column [min, max] of every sub-chunk of rows, or nullptr
     const int* eorder;                // [T] order in which the experts are dealt to the waves (neighbours together), or nullptr
+    int n_bounds;                     // interval bound pairs per expert (kind 2)
+    const double* bounds;             // [T][n_bounds][2] {lo, hi}: lo <= x < hi, or nullptr when n_bounds == 0
 };
 
 hipError_t launch_select(const SelectArgs& a, bool fill, hipStream_t stream);

@@ -7,6 +7,9 @@
 //   * ball criterion:  sum_k (x[c_k] - ref[c_k])^2  <= r*r     (KDTree.query_ball_point compares the squared distance,
 //                      accumulated left to right from 0.0, with r*r; inclusive whatever `comp` says, :2439-2444)
 //                      or  < r*r for prediction locations (strict, prediction_locations.py:37,43)
+//   * interval      :  lo_e <= x[col] < hi_e, per-expert bounds (a dynamic global_select entry, dataloader.py:2893-2978,
+//                      rank-coded on the host: x is the row's rank in the sorted distinct values of the source column);
+//                      a NaN x is never inside
 //   products and sums are NOT contracted into FMAs (__dmul_rn / __dadd_rn), as in the reference's host code.
 // Output per expert: the selected row indices in SOURCE ROW ORDER (dataloader.py:2447), CSR-packed.
 //
@@ -86,7 +89,9 @@ __device__ __forceinline__ bool cmp1d(int comp, double x, double y) {
     }
 }
 
-template <bool FILL>
+// IVL: the launch has interval criteria (kind 2).  Their upper bounds hold 2 more VGPRs per (expert, criterion), which halves the
+// occupancy (110 -> 170 VGPRs); launches without them run the instantiation that has no kind-2 code at all.
+template <bool FILL, bool IVL>
 __global__ void __launch_bounds__(SEL_NT) select_kernel(const SelectArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * (SEL_NT / 64) + (threadIdx.x >> 6);
@@ -98,9 +103,9 @@ __global__ void __launch_bounds__(SEL_NT) select_kernel(const SelectArgs a) {
     const long long r_beg = (long long)ch * a.chunk_rows;
     const long long r_end = min(a.M, r_beg + a.chunk_rows);
     const int ne = min(SEL_EB, a.T - e0);
-    // per expert, per criterion: the right-hand side (1-D: ref + val; ball: r*r) -- wave-uniform
+    // per expert, per criterion: the right-hand side (1-D: ref + val; ball: r*r; interval: lo) -- wave-uniform
     double rhs[SEL_EB][GPSAT_SEL_MAXCRIT];
-    double rc[SEL_EB][GPSAT_SEL_MAXCRIT][3];
+    double rc[SEL_EB][GPSAT_SEL_MAXCRIT][3];   // ball: the centre; interval: rc[e][k][0] = hi
     int eid[SEL_EB];                       // the experts of this wave
 #pragma unroll
     for (int e = 0; e < SEL_EB; ++e) eid[e] = a.eorder ? a.eorder[e0 + min(e, ne - 1)] : e0 + min(e, ne - 1);
@@ -114,6 +119,10 @@ __global__ void __launch_bounds__(SEL_NT) select_kernel(const SelectArgs a) {
             if (k < a.n_crit) {
                 if (a.kind[k] == 0) {
                     rhs[e][k] = __dadd_rn(a.refs[(size_t)ee * a.C + a.cols[k][0]], a.val[k]);
+                } else if (IVL && a.kind[k] == 2) {
+                    const double* bd = a.bounds + ((size_t)ee * a.n_bounds + a.cols[k][1]) * 2;
+                    rhs[e][k] = bd[0];
+                    rc[e][k][0] = bd[1];
                 } else {
                     rhs[e][k] = __dmul_rn(a.val[k], a.val[k]);
                     for (int m = 0; m < a.ncols[k]; ++m) rc[e][k][m] = a.refs[(size_t)ee * a.C + a.cols[k][m]];
@@ -138,6 +147,9 @@ __global__ void __launch_bounds__(SEL_NT) select_kernel(const SelectArgs a) {
                     if (a.kind[k] == 0) {
                         const int cl = a.cols[k][0];
                         poss = poss && cmp1d_possible(a.comp[k], bx[cl * 2], bx[cl * 2 + 1], rhs[e][k]);
+                    } else if (IVL && a.kind[k] == 2) {
+                        const int cl = a.cols[k][0];      // some x in [box_min, box_max] with lo <= x < hi
+                        poss = poss && bx[cl * 2 + 1] >= rhs[e][k] && bx[cl * 2] < rc[e][k][0];
                     } else {
                         double sl = 0.0;     // squared distance of the box's nearest point, the reference's operation order
                         for (int m = 0; m < a.ncols[k]; ++m) {
@@ -170,6 +182,10 @@ __global__ void __launch_bounds__(SEL_NT) select_kernel(const SelectArgs a) {
                     const double x = inb ? a.pts[(size_t)a.cols[k][0] * a.M + i] : 0.0;
 #pragma unroll
                     for (int e = 0; e < SEL_EB; ++e) match[e] = match[e] && cmp1d(a.comp[k], x, rhs[e][k]);
+                } else if (IVL && a.kind[k] == 2) {
+                    const double x = inb ? a.pts[(size_t)a.cols[k][0] * a.M + i] : 0.0;
+#pragma unroll
+                    for (int e = 0; e < SEL_EB; ++e) match[e] = match[e] && rhs[e][k] <= x && x < rc[e][k][0];
                 } else {
                     double x[3] = {0.0, 0.0, 0.0};
                     for (int m = 0; m < a.ncols[k]; ++m) x[m] = inb ? a.pts[(size_t)a.cols[k][m] * a.M + i] : 0.0;
@@ -270,8 +286,15 @@ hipError_t select_unbin(int T, long long total, const unsigned* seg_off, const i
 hipError_t launch_select(const SelectArgs& a, bool fill, hipStream_t stream) {
     const int waves = (a.T + SEL_EB - 1) / SEL_EB;
     const int grid = (waves + (SEL_NT / 64) - 1) / (SEL_NT / 64);
-    if (fill) hipLaunchKernelGGL(select_kernel<true>, dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
-    else hipLaunchKernelGGL(select_kernel<false>, dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
+    bool ivl = false;
+    for (int k = 0; k < a.n_crit; ++k) ivl = ivl || a.kind[k] == 2;
+    if (ivl) {
+        if (fill) hipLaunchKernelGGL((select_kernel<true, true>), dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
+        else hipLaunchKernelGGL((select_kernel<false, true>), dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
+    } else {
+        if (fill) hipLaunchKernelGGL((select_kernel<true, false>), dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
+        else hipLaunchKernelGGL((select_kernel<false, false>), dim3(grid, a.n_chunks), dim3(SEL_NT), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

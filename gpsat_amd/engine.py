@@ -282,12 +282,15 @@ class Engine:
         return BatchResult(theta=theta, nll=nll, status=status, n_eval=n_eval, n_iter=n_iter, f_mean=fm, f_var=fv, y_var=yv,
                            grad=grad, kernel_ms=km.value, total_ms=tm.value)
 
-    def select_batch(self, points: np.ndarray, refs: np.ndarray, criteria, points_cm: np.ndarray = None):
-        """Batched tile selection on the GPU (gpsat_select_batch).
+    def select_batch(self, points: np.ndarray, refs: np.ndarray, criteria, points_cm: np.ndarray = None,
+                     bounds: np.ndarray = None):
+        """Batched tile selection on the GPU (gpsat_select_batch, or gpsat_select_batch_ex when ``bounds`` is given).
 
         points [M, C] fp64, refs [T, C] fp64 (same column numbering); criteria: list of
         ("cmp", col, comp, val)  ->  points[:, col] <comp> refs[:, col] + val
-        ("ball", [cols], comp, r) -> Euclidean ball, comp "<=" (inclusive) or "<" (strict).
+        ("ball", [cols], comp, r) -> Euclidean ball, comp "<=" (inclusive) or "<" (strict)
+        ("interval", col, j)     ->  bounds[:, j, 0] <= points[:, col] < bounds[:, j, 1]  (per expert; NaN never inside)
+        bounds: [T, n_bounds, 2] fp64, required by "interval" criteria.
         Returns (off [T+1] int64, idx [off[-1]] int32): selected rows per expert in source order."""
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         T = refs.shape[0]
@@ -303,7 +306,21 @@ class Engine:
         if not 1 <= len(criteria) <= L.SEL_MAXCRIT:
             raise GpsatError(f"1..{L.SEL_MAXCRIT} criteria supported")
         sp.n_crit = len(criteria)
-        for k, (kind, cols, comp, val) in enumerate(criteria):
+        nb = 0
+        if bounds is not None:
+            bounds = np.ascontiguousarray(bounds, dtype=np.float64)
+            if bounds.ndim != 3 or bounds.shape[0] != T or bounds.shape[2] != 2 or bounds.shape[1] < 1:
+                raise GpsatError(f"bounds must be [T={T}, n_bounds >= 1, 2], got {bounds.shape}")
+            nb = bounds.shape[1]
+        for k, crit in enumerate(criteria):
+            if crit[0] == "interval":
+                _, col, j = crit
+                if not 0 <= int(j) < nb:
+                    raise GpsatError(f"interval criterion {k}: bound pair {j} not in bounds (n_bounds={nb})")
+                sp.kind[k], sp.comp[k], sp.ncols[k] = 2, 0, 1
+                sp.cols[k][0], sp.cols[k][1] = int(col), int(j)
+                continue
+            kind, cols, comp, val = crit
             sp.kind[k] = 0 if kind == "cmp" else 1
             sp.comp[k] = L.COMP_IDS[comp]
             cl = [cols] if kind == "cmp" else list(cols)
@@ -312,13 +329,14 @@ class Engine:
                 sp.cols[k][m_] = int(c_)
             sp.val[k] = float(val)
         off = np.zeros(T + 1, dtype=np.int64)
-        rc = self._lib.gpsat_select_batch(self._h, C.byref(sp), M, Cc, _ptr(pts_cm), T, _ptr(refs), _ptr(off), None, 0)
+        pb = _ptr(bounds) if nb else None
+        rc = self._lib.gpsat_select_batch_ex(self._h, C.byref(sp), M, Cc, _ptr(pts_cm), T, _ptr(refs), nb, pb, _ptr(off), None, 0)
         if rc != 0:
             raise GpsatError(f"gpsat_select_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         idx = np.empty(int(off[-1]), dtype=np.int32)
         if len(idx):
-            rc = self._lib.gpsat_select_batch(self._h, C.byref(sp), M, Cc, _ptr(pts_cm), T, _ptr(refs), _ptr(off),
-                                              _ptr(idx), len(idx))
+            rc = self._lib.gpsat_select_batch_ex(self._h, C.byref(sp), M, Cc, _ptr(pts_cm), T, _ptr(refs), nb, pb, _ptr(off),
+                                                 _ptr(idx), len(idx))
             if rc != 0:
                 raise GpsatError(f"gpsat_select_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         return off, idx

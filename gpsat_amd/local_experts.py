@@ -30,7 +30,8 @@ when pyarrow is absent; pytables / HDF5 is not a dependency of this backend -- `
 Supported config subset (anything else raises ``NotImplementedError`` -- never a silent fallback):
   expert_loc_config : {"source": DataFrame | csv/parquet path, "sort_by": optional col(s)}
   data_config       : {"data_source": DataFrame | path, "obs_col": str, "coords_col": [..],
-                       "local_select": [{"col", "comp", "val"}, ...], "global_select": [static {"col","comp","val"}]}
+                       "local_select": [{"col", "comp", "val"}, ...],
+                       "global_select": [static {"col","comp","val"} | dynamic {"loc_col","src_col","func"}]}
   pred_loc_config   : {"method": "expert_loc"} | {"method": "from_dataframe", "df": DataFrame, "max_dist": float,
                        "local_select": optional} | {"method": "from_source", "load_kwargs": {"source": DataFrame | path},
                        "max_dist": ..} | {"method": "shift_arrays", "<coord>": array, ...}
@@ -40,6 +41,12 @@ Supported config subset (anything else raises ``NotImplementedError`` -- never a
                        "load_params": {"file": store dir | dict of tables, "table_suffix": str, "param_names": [..],
                                        "index_adjust": {col: {"func": callable | "lambda ..."}}} |
                                       {<param>: value, ...}  (set directly on every tile)}
+Dynamic ``global_select`` entries (``get_where_list``, GPSat/dataloader.py:2893-2978): for every ``local_select`` entry on
+``loc_col`` an expert keeps the rows with ``src_col <comp> func(ref[loc_col], val)`` (pandas' comparison; ``func`` a callable or
+a ``"lambda ..."`` string evaluated with ``np`` and ``pd``, called once per distinct ``(ref[loc_col], val)`` with the value
+``rl.iloc[0, :].to_dict()`` gives).  ``src_col`` is rank-coded once per run and every threshold becomes a half-open rank interval,
+so the criterion is exact for any ordered dtype; the entries on one ``src_col`` make one interval per expert, a device criterion of
+its own (at most 4 device criteria in all).
 Sparse experts (``oi_model`` GPflowSGPRModel / HipSGPRModel, fp64): the main profile runs through
 ``gpsat_sgpr_fit_predict_batch`` with no per-tile observation limit; ``init_params`` may hold ``num_inducing_points``
 (default 500) and ``inducing_seed`` (default 0); every expert's inducing points are those HipSGPRModel picks
@@ -108,16 +115,124 @@ def data_select(df, selects):
     return df.loc[keep]
 
 
+_DYNAMIC_KEYS = ["loc_col", "src_col", "func"]
+
+
+def split_global_select(selects):
+    """(static, dynamic) entries of a ``global_select`` list (GPSat/dataloader.py:2944-2960): an entry with col, comp and val
+    is static, any other must have loc_col, src_col and func."""
+    static, dynamic = [], []
+    for gs in selects or []:
+        if all(c in gs for c in ["col", "comp", "val"]):
+            static.append(gs)
+        else:
+            assert all(c in gs for c in _DYNAMIC_KEYS), \
+                f"dynamic where had keys: {list(gs.keys())}, must have: {_DYNAMIC_KEYS} "
+            dynamic.append(gs)
+    return static, dynamic
+
+
+def _rank_interval(u: pd.Series, comp: str, c):
+    """Positions of the sorted distinct values ``u`` for which pandas' ``u <comp> c`` holds, as a half-open interval."""
+    m = np.asarray(_PD_COMPS[comp](u, c).to_numpy(dtype=bool, na_value=False))
+    nz = np.flatnonzero(m)
+    if len(nz) == 0:
+        return 0.0, 0.0
+    if nz[-1] + 1 - nz[0] != len(nz):
+        raise NotImplementedError(f"dynamic global_select: '{comp} {c!r}' does not select one contiguous run of the sorted "
+                                  f"values of its src_col")
+    return float(nz[0]), float(nz[-1] + 1)
+
+
+_PD_COMPS = {">=": lambda x, y: x >= y, ">": lambda x, y: x > y, "==": lambda x, y: x == y, "<": lambda x, y: x < y,
+             "<=": lambda x, y: x <= y}
+
+
+class DynamicSelect:
+    """The dynamic ``global_select`` entries of a config as per-expert rank intervals (GPSat/dataloader.py:2893-2978,
+    local_experts.py:426-472,971-985).
+
+    Every ``local_select`` entry whose ``col`` is an entry's ``loc_col`` adds the criterion
+    ``df[src_col] <comp> func(ref[loc_col], val)`` (``comp``, ``val`` from the local entry); an entry no local entry matches adds
+    nothing.  ``src_col`` is rank-coded once (``code`` = position in its sorted distinct non-null values, null -> NaN) and the
+    rows a threshold keeps are found by pandas' own comparison on the distinct values: a rank interval ``[lo, hi)``.  All
+    criteria on one ``src_col`` are intersected, so an expert keeps a row iff ``lo <= code < hi`` -- bit for bit what the
+    comparisons on the frame keep, for any ordered dtype."""
+
+    def __init__(self, dynamic: List[dict], local_select: Optional[List[dict]], df: pd.DataFrame, loc_columns):
+        self.items = []                          # (src_col, func, comp, val, loc_col)
+        for gs in dynamic:
+            assert local_select is not None, f"dynamic where provide: {gs}, however local_select is: {type(local_select)}"
+            assert all(c in gs for c in _DYNAMIC_KEYS), \
+                f"dynamic where had keys: {list(gs.keys())}, must have: {_DYNAMIC_KEYS} "
+            loc_col = gs["loc_col"]
+            assert loc_col in loc_columns, f"loc_col: {loc_col} not in ref_loc: {list(loc_columns)}"
+            func = gs["func"]
+            if isinstance(func, str):
+                func = eval(func, {"np": np, "pd": pd})          # as the reference: eval with np and pd in scope
+            if not callable(func):
+                raise NotImplementedError(f"dynamic global_select func must be callable or a 'lambda ...' string: {gs['func']!r}")
+            for ls in local_select:
+                if isinstance(ls["col"], str) and ls["col"] == loc_col:
+                    assert gs["src_col"] in df, f"col: '{gs['src_col']}' is not in coords: {list(df.columns)}"
+                    assert ls["comp"] in _PD_COMPS, f"comp: {ls['comp']} is not valid"
+                    self.items.append((gs["src_col"], func, ls["comp"], ls["val"], loc_col))
+        self.src_cols = list(dict.fromkeys(it[0] for it in self.items))
+        self.df = df
+        self._codes = None
+
+    def codes(self):
+        """[n_src, M] fp64 rank codes (NaN for null) and, per src_col, its sorted distinct values (a Series)."""
+        if self._codes is None:
+            codes, uniq = np.empty((len(self.src_cols), len(self.df))), []
+            for j, sc in enumerate(self.src_cols):
+                cd, u = pd.factorize(self.df[sc], sort=True)
+                codes[j] = np.where(cd < 0, np.nan, cd.astype(np.float64))
+                uniq.append(pd.Series(u))
+            self._codes = (codes, uniq)
+        return self._codes
+
+    def bounds(self, refs: pd.DataFrame) -> np.ndarray:
+        """[T, n_src, 2] rank interval {lo, hi} of every expert (row of ``refs``) and src_col."""
+        T = len(refs)
+        out = np.empty((T, len(self.src_cols), 2))
+        out[:, :, 0], out[:, :, 1] = -np.inf, np.inf
+        if T == 0:
+            return out
+        _, uniq = self.codes()
+        boxed = {}
+        for src, func, comp, val, loc_col in self.items:
+            if loc_col not in boxed:
+                # the value the reference passes: rl.iloc[0, :].to_dict()[loc_col], once per distinct value
+                ecode, _ = pd.factorize(refs[loc_col], use_na_sentinel=False)
+                first = np.unique(ecode, return_index=True)[1]
+                row_dtype = refs.iloc[int(first[0])].dtype
+                if isinstance(row_dtype, np.dtype) and row_dtype.kind in "biuf":
+                    col = refs[loc_col].to_numpy().astype(row_dtype)
+                    vals = [col[i].item() for i in first]
+                else:
+                    vals = [refs.iloc[int(i)].to_dict()[loc_col] for i in first]
+                boxed[loc_col] = (ecode, vals)
+            ecode, vals = boxed[loc_col]
+            j = self.src_cols.index(src)
+            iv = np.array([_rank_interval(uniq[j], comp, func(v, val)) for v in vals]).reshape(-1, 2)[ecode]
+            out[:, j, 0] = np.maximum(out[:, j, 0], iv[:, 0])
+            out[:, j, 1] = np.minimum(out[:, j, 1], iv[:, 1])
+        return out
+
+
 class LocalSelector:
     """``DataLoader.local_data_select`` for many reference locations against one frame.
 
     1-D criteria: ``df[col] <comp> ref[col] + val``; multi-column criteria: Euclidean ball through
     ``KDTree.query_ball_point(x=ref[cols], r=val)`` -- inclusive of points exactly at ``r`` whatever ``comp`` says
     (GPSat/dataloader.py:2413-2444).  The KD-tree is built once (the reference rebuilds it per tile on the same
-    frame).  Returns boolean masks, so source row order is kept (dataloader.py:2447)."""
+    frame).  Returns boolean masks, so source row order is kept (dataloader.py:2447).  ``interval_codes`` [n, M]: columns
+    that ``select`` also restricts per expert to ``bounds[e, j, 0] <= code < bounds[e, j, 1]`` (``DynamicSelect``)."""
 
-    def __init__(self, df: pd.DataFrame, local_select: List[dict]):
+    def __init__(self, df: pd.DataFrame, local_select: List[dict], interval_codes: Optional[np.ndarray] = None):
         self.df = df
+        self.interval_codes = interval_codes
         self.local_select = local_select or []
         self._trees = {}
         self._cols = {}
@@ -149,13 +264,17 @@ class LocalSelector:
                 select &= m
         return select
 
-    def select(self, refs: pd.DataFrame):
+    def select(self, refs: pd.DataFrame, bounds: Optional[np.ndarray] = None):
         """CSR (off [T+1], idx) of selected row POSITIONS for every row of ``refs`` (same layout as DeviceSelector)."""
         cols = list(refs.columns)
         vals = refs.values
         chunks, off = [], np.zeros(len(refs) + 1, dtype=np.int64)
         for i in range(len(refs)):
-            ids = np.nonzero(self.mask(dict(zip(cols, vals[i]))))[0]
+            m = self.mask(dict(zip(cols, vals[i])))
+            if self.interval_codes is not None:
+                for j, code in enumerate(self.interval_codes):
+                    m &= (bounds[i, j, 0] <= code) & (code < bounds[i, j, 1])
+            ids = np.nonzero(m)[0]
             chunks.append(ids)
             off[i + 1] = off[i] + len(ids)
         return off, (np.concatenate(chunks) if chunks else np.zeros(0, np.int64)).astype(np.int64)
@@ -166,9 +285,11 @@ class DeviceSelector:
     (``gpsat_select_batch``: fp64 predicates with the reference's arithmetic, bit-exact, source row order).
 
     ``local_select`` entries as in the reference; ``strict_ball=True`` gives the prediction-location semantics
-    (strict ``<`` on the squared distance, GPSat/prediction_locations.py:37,43)."""
+    (strict ``<`` on the squared distance, GPSat/prediction_locations.py:37,43); ``interval_codes`` as for ``LocalSelector``
+    (one interval criterion each, kind 2 of gpsat_select_batch_ex)."""
 
-    def __init__(self, df: pd.DataFrame, local_select: List[dict], engine, strict_ball: bool = False):
+    def __init__(self, df: pd.DataFrame, local_select: List[dict], engine, strict_ball: bool = False,
+                 interval_codes: Optional[np.ndarray] = None):
         self.engine = engine
         cols = []
         for ls in local_select:
@@ -179,6 +300,9 @@ class DeviceSelector:
         self.cols = cols
         self.points = df.loc[:, cols].values.astype(np.float64)
         self.points_cm = np.ascontiguousarray(self.points.T)          # what the C ABI takes: column-major, made once
+        self.n_ivl = 0 if interval_codes is None else len(interval_codes)
+        if self.n_ivl:
+            self.points_cm = np.ascontiguousarray(np.concatenate([self.points_cm, np.asarray(interval_codes, np.float64)]))
         self.criteria = []
         for ls in local_select:
             if isinstance(ls["col"], str):
@@ -189,14 +313,23 @@ class DeviceSelector:
                 if len(ls["col"]) > 3:
                     raise NotImplementedError("device ball selection takes 1..3 columns")
                 self.criteria.append(("ball", [cols.index(c_) for c_ in ls["col"]], "<" if strict_ball else "<=", ls["val"]))
+        for j in range(self.n_ivl):
+            self.criteria.append(("interval", len(cols) + j, j))
+        if self.n_ivl and len(self.criteria) > L.SEL_MAXCRIT:
+            raise NotImplementedError(f"device selection takes at most {L.SEL_MAXCRIT} criteria (GPSAT_SEL_MAXCRIT); this "
+                                      f"one needs {len(self.criteria)}: {len(local_select)} local_select entries and "
+                                      f"{self.n_ivl} dynamic global_select interval(s)")
 
-    def select(self, refs: pd.DataFrame):
-        """refs: one row per expert with (at least) the columns used by the criteria.
-        Returns CSR (off [T+1], idx [off[-1]]) of selected row POSITIONS of the frame, ascending per expert."""
+    def select(self, refs: pd.DataFrame, bounds: Optional[np.ndarray] = None):
+        """refs: one row per expert with (at least) the columns used by the criteria; bounds [T, n_ivl, 2] with
+        ``interval_codes``.  Returns CSR (off [T+1], idx [off[-1]]) of selected row POSITIONS of the frame, ascending per expert."""
         for c_ in self.cols:
             assert c_ in refs, f"col: {c_} is not in reference_location - {list(refs.columns)}"
-        return self.engine.select_batch(None, refs.loc[:, self.cols].values.astype(np.float64), self.criteria,
-                                        points_cm=self.points_cm)
+        r = refs.loc[:, self.cols].values.astype(np.float64)
+        if self.n_ivl:
+            r = np.concatenate([r, np.zeros((len(r), self.n_ivl))], axis=1)      # the code columns have no reference value
+        return self.engine.select_batch(None, r, self.criteria, points_cm=self.points_cm,
+                                        bounds=bounds if self.n_ivl else None)
 
 
 def max_dist_bool(loc: np.ndarray, ref_loc: np.ndarray, max_dist: float) -> np.ndarray:
@@ -674,7 +807,8 @@ class BatchedLocalExpertOI:
             assert len(self.obs_col) == 1
             self.obs_col = self.obs_col[0]
         self.local_select = data_config.get("local_select", [])
-        df = data_select(_load_frame(data_config["data_source"]), data_config.get("global_select"))
+        static_gs, dynamic_gs = split_global_select(data_config.get("global_select"))
+        df = data_select(_load_frame(data_config["data_source"]), static_gs)
         self.df = df
         # ---- expert locations (local_experts.py:349-422)
         xl = _load_frame(expert_loc_config["source"])
@@ -684,6 +818,16 @@ class BatchedLocalExpertOI:
             if k not in ("source", "sort_by"):
                 raise NotImplementedError(f"expert_loc_config key '{k}' is not supported by the batched backend")
         self.expert_locs = xl.reset_index(drop=True)
+        # dynamic global_select entries: per-expert rank intervals (DynamicSelect)
+        self.dynamic = DynamicSelect(dynamic_gs, data_config.get("local_select"), df, self.expert_locs.columns) \
+            if dynamic_gs else None
+        if self.dynamic is not None and not self.dynamic.items:
+            self.dynamic = None                   # no local_select entry on its loc_col: it adds nothing
+        if device_select and self.dynamic is not None and len(self.local_select) + len(self.dynamic.src_cols) > L.SEL_MAXCRIT:
+            raise NotImplementedError(f"device_select=True takes at most {L.SEL_MAXCRIT} selection criteria (GPSAT_SEL_MAXCRIT); "
+                                      f"this config needs {len(self.local_select) + len(self.dynamic.src_cols)}: "
+                                      f"{len(self.local_select)} local_select entries and {len(self.dynamic.src_cols)} "
+                                      f"dynamic global_select interval(s), one per src_col")
         # ---- model (local_experts.py:292-346)
         self.init_params = dict(model_config.get("init_params") or {})
         self.constraints = model_config.get("constraints")
@@ -921,10 +1065,16 @@ class BatchedLocalExpertOI:
             from concurrent.futures import ThreadPoolExecutor
             sel_pool = ThreadPoolExecutor(max_workers=1)
             pcs_f = sel_pool.submit(self.pred_loc.batch, locs, sel_engines[1])
+        self.timings["dynamic_select_s"] = 0.0
         if len(self.local_select):
-            sel = DeviceSelector(self.df, self.local_select, self.engine) if self.device_select \
-                else LocalSelector(self.df, self.local_select)
-            off, idx = sel.select(refs)
+            codes = bounds = None
+            if self.dynamic is not None:
+                td = time.perf_counter()          # rank coding of the src_cols and the func calls
+                codes, bounds = self.dynamic.codes()[0], self.dynamic.bounds(refs)
+                self.timings["dynamic_select_s"] = time.perf_counter() - td
+            sel = DeviceSelector(self.df, self.local_select, self.engine, interval_codes=codes) if self.device_select \
+                else LocalSelector(self.df, self.local_select, interval_codes=codes)
+            off, idx = sel.select(refs, bounds=bounds)
         else:
             off, idx = np.arange(len(ex) + 1, dtype=np.int64) * len(self.df), np.tile(np.arange(len(self.df)), len(ex))
         n_obs = np.diff(off)

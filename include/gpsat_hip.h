@@ -186,6 +186,10 @@ int gpsat_fit_predict_batch(gpsat_handle *h, const gpsat_batch *b);
  *   kind 0: points[cols[k][0]] <comp> (refs[cols[k][0]] + val[k])       comp: 0 >=, 1 >, 2 ==, 3 <, 4 <=
  *   kind 1: sum_m (points[cols[k][m]] - refs[cols[k][m]])^2 <= val[k]^2  (comp 4, observations: inclusive ball)
  *                                                          <  val[k]^2  (comp 3, prediction locations: strict)
+ *   kind 2: bounds[t][cols[k][1]][0] <= points[cols[k][0]] < bounds[t][cols[k][1]][1]   (per-expert interval, fp64; a NaN
+ *           point is never inside; comp, ncols and val are not read).  Only gpsat_select_batch_ex takes it.  GPSat's dynamic
+ *           global_select entries (dataloader.py:2893-2978) arrive this way: the source column rank-coded, one rank
+ *           interval per expert.
  */
 #define GPSAT_SEL_MAXCRIT 4
 typedef struct gpsat_select_spec {
@@ -210,6 +214,15 @@ typedef struct gpsat_select_spec {
  */
 int gpsat_select_batch(gpsat_handle *h, const gpsat_select_spec *spec, int64_t M, int32_t C, const double *points,
                        int32_t T, const double *refs, int64_t *off, int32_t *idx, int64_t capacity);
+
+/*
+ * gpsat_select_batch with per-expert interval criteria (kind 2; added within ABI 4, check for the symbol).
+ * bounds: host [T][n_bounds][2] fp64 {lo, hi}; a kind-2 criterion k reads bound pair cols[k][1] (0 <= cols[k][1] < n_bounds).
+ * n_bounds = 0 with bounds = NULL is gpsat_select_batch.  The two-call cache also compares `bounds` (pointer and contents).
+ */
+int gpsat_select_batch_ex(gpsat_handle *h, const gpsat_select_spec *spec, int64_t M, int32_t C, const double *points,
+                          int32_t T, const double *refs, int32_t n_bounds, const double *bounds, int64_t *off, int32_t *idx,
+                          int64_t capacity);
 
 /*
  * Gaussian smoothing of one hyper-parameter field over T expert locations (one "other dimensions" slice).

@@ -24,6 +24,19 @@ dss.select(xl.iloc[:8])
 t0 = time.perf_counter(); off2, idx2 = dss.select(xl); dt2 = time.perf_counter() - t0
 eng._lib.gpsat_last_timing(eng._h, C.byref(km), C.byref(tm))
 print(f"device, rows ordered by day: kernels {km.value:.1f} ms, {dt2*1e3:.1f} ms wall ({T/dt2:.0f} tiles/s), same selection size: {off2[-1] == off[-1]}")
+# the same day-ordered table plus GPSat's dynamic global_select entry on `date` (configs/example_local_expert_oi.json): one
+# more interval criterion (kind 2) on the rank-coded date column; here it selects exactly what the t window selects
+from gpsat_amd.local_experts import DynamicSelect
+dfs["date"] = pd.to_datetime(dfs["t"], unit="D")
+dyn = DynamicSelect([{"loc_col": "t", "src_col": "date", "func": "lambda x,y: np.datetime64(pd.to_datetime(x+y, unit='D'))"}],
+                    ls, dfs, xl.columns)
+th = time.perf_counter(); codes = dyn.codes()[0]; bnd = dyn.bounds(xl); dh5 = time.perf_counter() - th
+dsd = DeviceSelector(dfs, ls, eng, interval_codes=codes)
+dsd.select(xl.iloc[:8], bounds=bnd[:8])
+t0 = time.perf_counter(); off5, idx5 = dsd.select(xl, bounds=bnd); dt5 = time.perf_counter() - t0
+eng._lib.gpsat_last_timing(eng._h, C.byref(km), C.byref(tm))
+print(f"device, rows ordered by day + dynamic date interval: kernels {km.value:.1f} ms, {dt5*1e3:.1f} ms wall ({T/dt5:.0f} tiles/s), "
+      f"host rank coding + bounds {dh5*1e3:.0f} ms, same selection: {np.array_equal(off5, off2) and np.array_equal(idx5, idx2)}")
 # GPSat's usual sweep: all expert locations of one run share the day (a grid at t = const)
 xl1 = xl.assign(t=15.0)
 dss.select(xl1.iloc[:8])
