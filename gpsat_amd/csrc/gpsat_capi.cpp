@@ -99,11 +99,11 @@ struct gpsat_handle {
         std::vector<int64_t> off;
     } selc;
     // device buffers (grown lazily, owned by the handle)
-    DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop;
+    DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
-    unsigned long long prof_host[64 + 8 * 1024 + 2048] = {0};     // counters + event trace + per-workgroup start / end (diagnostic build)
+    unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
 };
 
 extern "C" {
@@ -171,7 +171,7 @@ int gpsat_destroy(gpsat_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->meta_i64.release(); h->meta_f64.release(); h->meta_misc.release(); h->out_f64.release();
-    h->out_i32.release(); h->bulk_in.release(); h->bulk_out.release(); h->ws.release(); h->prof.release(); h->ring.release(); h->state.release(); h->coop.release();
+    h->out_i32.release(); h->bulk_in.release(); h->bulk_out.release(); h->ws.release(); h->prof.release(); h->ring.release(); h->state.release(); h->coop.release(); h->pq.release();
     h->sel_pts.release(); h->sel_refs.release(); h->sel_cnt.release(); h->sel_idx.release(); h->sel_box.release();
     h->sel_perm.release(); h->sel_keys.release(); h->sel_tmp.release(); h->sel_ord.release(); h->sel_bnd.release();
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -429,6 +429,34 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
     a.f_cov = want_cov ? reinterpret_cast<float*>(dcov) : nullptr;
     a.PCmax = PCcov;
     a.dump = nullptr; a.dump_stride = 0;
+    // ---- deferred predictions (fp32 4-wave build, time-sliced, no full covariance): a tile that finishes while others wait
+    // leaves its prediction in a snapshot slot for the workgroups that idle at the end of the launch (gpsat_ring.h).  One slot
+    // per tile up to a fixed budget; tiles past it predict inline.
+    a.pq = nullptr; a.pq_ctl = nullptr; a.cu_busy = nullptr; a.pq_snap = nullptr; a.pq_stride = 0; a.pq_slots = 0;
+    if (seg_cost > 0 && !f64 && !w8 && !want_cov && sumP > 0) {
+        const size_t stride = gpsat::pq_floats_per_slot(D, NBmax);
+        const size_t budget = (size_t)5 << 29;                    // 2.5 GiB: every tile of a 4096-tile launch of N = 500
+        long long slots = std::min<long long>(T, (long long)(budget / (stride * sizeof(float))));
+        // developer / tests: 0 = every prediction inline, n = at most n snapshot slots
+        if (const char* e = dev_env("GPSAT_DEBUG_DEFER")) slots = std::min<long long>(slots, std::max(0, std::atoi(e)));
+        // (head rounded to 256 B: the snapshots move as 16-B block accesses)
+        const size_t head = (256 + 2048 * sizeof(int) + (size_t)slots * sizeof(unsigned long long) + 255) & ~size_t(255);
+        if (slots > 0 && h->pq.reserve(head + (size_t)slots * stride * sizeof(float)) != GPSAT_OK) {
+            // no memory for the pool: every prediction inline (the same results), not an error
+            g_err.clear();
+            (void)hipGetLastError();
+            slots = 0;
+        }
+        if (slots > 0) {
+            HIP_TRY(hipMemsetAsync(h->pq.p, 0, head, h->stream));
+            char* p = static_cast<char*>(h->pq.p);
+            a.pq_ctl = reinterpret_cast<int*>(p);
+            a.cu_busy = reinterpret_cast<int*>(p + 256);
+            a.pq = reinterpret_cast<unsigned long long*>(p + 256 + 2048 * sizeof(int));
+            a.pq_snap = reinterpret_cast<float*>(p + head);
+            a.pq_stride = stride; a.pq_slots = (int)slots;
+        }
+    }
 #ifdef GPSAT_DUMP
     if (h->dump_dev && !f64) {
         const size_t need = ((size_t)NBmax * NBmax + NBmax) * 1024 + 2 * (size_t)NBmax * 32 + 16 + 8 * 1024;
@@ -473,6 +501,9 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
         coop_host.resize((size_t)grid * 256);
         HIP_TRY(hipMemcpyAsync(coop_host.data(), h->coop.p, (size_t)grid * 1024, hipMemcpyDeviceToHost, h->stream));
     }
+    int pq_taken = -1;
+    if (a.pq_ctl && dev_env("GPSAT_DEBUG_DEFER_STATS"))
+        HIP_TRY(hipMemcpyAsync(&pq_taken, a.pq_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     int unfinished = 0;
     if (seg_cost > 0) HIP_TRY(hipMemcpyAsync(&unfinished, d_ring_ctl + 32, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
@@ -484,6 +515,9 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
                              "flag waits given up %lld, owner waits given up %lld, pivot failures %lld, helper unwinds %lld\n",
                      grid, T, st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
     }
+    if (dev_env("GPSAT_DEBUG_DEFER_STATS"))       // developer / tests: how many predictions were deferred
+        std::fprintf(stderr, "gpsat defer: T %d: deferred predictions %d of %d snapshot slots\n", T,
+                     pq_taken < 0 ? 0 : std::min(pq_taken, a.pq_slots), a.pq_slots);
     if (!team_host.empty() && dev_env("GPSAT_DEBUG_TEAM_STATS"))
         std::fprintf(stderr, "gpsat team 0 (size %d), factorisation, owner thread 0, s_memtime ticks: own work of (A) %d, (A) wait + barrier %d, (B) + barrier %d, "
                              "(C) + barrier %d\n", team, team_host[24], team_host[25], team_host[26], team_host[27]);
@@ -956,6 +990,13 @@ int gpsat_debug_profile(gpsat_handle* h, unsigned long long* out64) {
 int gpsat_debug_spans(gpsat_handle* h, unsigned long long* out2048) {
     if (!h || !out2048) return GPSAT_EINVAL;
     std::memcpy(out2048, h->prof_host + 64 + 8 * 1024, 2048 * sizeof(unsigned long long));
+    return GPSAT_OK;
+}
+// per-workgroup time it first found the time-sliced ring without a waiting tile (100 MHz ticks, 0 = never) and its CU
+// (XCC_ID << 8 | HW_ID[15:8]): [1024] times then [1024] CUs
+int gpsat_debug_idle(gpsat_handle* h, unsigned long long* out2048) {
+    if (!h || !out2048) return GPSAT_EINVAL;
+    std::memcpy(out2048, h->prof_host + 64 + 8 * 1024 + 2048, 2048 * sizeof(unsigned long long));
     return GPSAT_OK;
 }
 // event trace of the first evaluation of workgroup 0: [8 waves][1024] entries (cycle << 16 | arg << 8 | code), 0 = unused

@@ -66,6 +66,15 @@ struct KernelArgs {
     // log-determinant of its LAST evaluation, [T][dump_stride] floats in device memory; nullptr in the product
     float* dump;
     size_t dump_stride;
+    // deferred predictions (fp32 4-wave build, time-sliced launches without f_cov; pq == nullptr: every prediction inline):
+    // a tile that finishes its fit while other tiles wait in the ring leaves a snapshot of what its prediction reads and
+    // takes the next tile; workgroups that find the ring empty run the predictions (gpsat_ring.h)
+    unsigned long long* pq;       // [pq_slots] published entries (tile + 1; 0: not yet), zeroed before the launch
+    int* pq_ctl;                  // [0] snapshot slots taken, [16] entries claimed; zeroed before the launch
+    int* cu_busy;                 // [2048] per CU (XCC_ID << 8 | HW_ID[15:8]): workgroups running a tile; zeroed
+    float* pq_snap;               // [pq_slots][pq_stride] snapshots
+    size_t pq_stride;             // floats per snapshot slot
+    int pq_slots;
 };
 
 size_t shared_bytes(int D, int NBmax);
@@ -79,6 +88,7 @@ size_t shared_bytes_f64_w4(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
 hipError_t launch_tiles_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 int state_words();                                        // 32-bit words of saved optimiser state per tile (time slicing)

@@ -1912,6 +1912,80 @@ __device__ __noinline__ void helper_episode(Ctx<D, KN> c, const HelpArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// deferred predictions (4-wave build, KernelArgs::pq; gpsat_ring.h).  A snapshot slot holds what predict_tile reads besides
+// the prediction points: the U blocks k < j (packed by block column: block j (j - 1) / 2 + k), the NB DinvT blocks, then z
+// [Npad], the scaled coordinates of the final evaluation [D][Npad], sf2, sn2 and invl[D].  The same code then runs on the
+// same values elsewhere: the outputs are bit for bit those of the inline prediction.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int pq_block(int b, int NB) {            // packed block b -> workspace block
+    const int nu = NB * (NB - 1) / 2;
+    if (b >= nu) return NB * NB + (b - nu);
+    int j = 1;
+    while ((j + 1) * j / 2 <= b) ++j;
+    return (b - j * (j - 1) / 2) * NB + j;
+}
+
+template <int D, int KN>
+__device__ void pq_save(Ctx<D, KN>& c, const KernelArgs& A, int s, int t, const float (&invl)[D]) {
+    const int NB = c.NB, nblk = NB * (NB - 1) / 2 + NB;
+    float* snap = A.pq_snap + (size_t)s * A.pq_stride;
+    for (int b = c.w; b < nblk; b += NW) stg(snap, b, c.lane, ldg(c.ws, pq_block(b, NB), c.lane));
+    unsigned* tail = reinterpret_cast<unsigned*>(snap + (size_t)nblk * BLK);
+    for (int i = c.tid; i < (D + 1) * c.Npad; i += NT) {
+        const float v = i < c.Npad ? lds_f[c.L.z + i] : lds_f[c.L.xsc + i - c.Npad];
+        __hip_atomic_store(&tail[i], __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (c.tid == 0) {
+        unsigned* hdr = tail + (D + 1) * c.Npad;
+        __hip_atomic_store(&hdr[0], __float_as_uint(c.sf2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&hdr[1], __float_as_uint(c.sn2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int d = 0; d < D; ++d) __hip_atomic_store(&hdr[2 + d], __float_as_uint(invl[d]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // every storing wave drains its stores, then the barrier, then one lane publishes (as for a suspended tile's state)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (c.tid == 0) pq_publish(A, s, t);
+}
+
+// the deferred prediction of tile t from snapshot slot s, in this workgroup's own workspace (ws_own)
+template <int D, int KN>
+__device__ void pq_predict(Ctx<D, KN>& c, const KernelArgs& A, int s, int t, float* ws_own) {
+    const long long o0 = A.obs_off[t], o1 = A.obs_off[t + 1];
+    const long long p0 = A.pred_off[t], p1 = A.pred_off[t + 1];
+    c.N = (int)(o1 - o0);
+    c.P = (int)(p1 - p0);
+    c.NB = (c.N + 31) / 32;
+    c.Npad = c.NB * 32;
+    const int NB = c.NB, nblk = NB * (NB - 1) / 2 + NB;
+    c.dT0 = NB * NB;
+    c.vs0 = c.dT0 + NB;
+    c.cv0 = c.vs0 + NW * 2 * NB;
+    c.ws = ws_own;
+    const float* snap = A.pq_snap + (size_t)s * A.pq_stride;
+    // the snapshot was written by another workgroup, possibly on another XCD: sc1 block loads and agent-scope word loads
+    // after the poll of the published entry and the barrier behind it (the protocol of a resumed tile's state)
+    for (int b = c.w; b < nblk; b += NW) stg(c.ws, pq_block(b, NB), c.lane, ldg(snap, b, c.lane));
+    const unsigned* tail = reinterpret_cast<const unsigned*>(snap + (size_t)nblk * BLK);
+    for (int i = c.tid; i < (D + 1) * c.Npad; i += NT) {
+        const float v = __uint_as_float(__hip_atomic_load(&tail[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (i < c.Npad) lds_f[c.L.z + i] = v; else lds_f[c.L.xsc + i - c.Npad] = v;
+    }
+    c.sf2 = __uint_as_float(__hip_atomic_load(&tail[(D + 1) * c.Npad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    c.sn2 = __uint_as_float(__hip_atomic_load(&tail[(D + 1) * c.Npad + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    float invl[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+        invl[d] = __uint_as_float(__hip_atomic_load(&tail[(D + 1) * c.Npad + 2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the blocks other waves read in predict_tile
+    __syncthreads();
+    predict_tile<D, KN>(c, A.Xs + (size_t)p0 * D, A.f_mean + p0, A.f_var + p0, A.y_var + p0, invl, nullptr);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------------------------------------
 // the persistent kernel
 // ---------------------------------------------------------------------------------------------
 template <int D, int KN>
@@ -1957,6 +2031,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     if (blockIdx.x == 0 && A.prof) c.trace = A.prof + 64;
     if (c.tid < NW) sh->tcnt[c.tid] = 0;
     int prof_ntiles = 0;                          // the evaluations of the THIRD tile of workgroup 0 are traced
+    unsigned long long prof_empty = 0;            // when this workgroup first found no tile waiting in the ring (100 MHz ticks)
     if (c.tid < NW * 16) sh->prof[c.tid] = 0ull;
     const unsigned long long prof_k0 = __builtin_amdgcn_s_memtime(), prof_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1965,6 +2040,12 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
 
     const bool sliced = A.seg_cost > 0;
+    // deferred predictions: 4-wave build only (the 8-wave build's idle workgroups help running tiles instead)
+    const bool defer_on = (NW == 4) && sliced && A.pq != nullptr;
+    const int my_cu = defer_on ? cu_index() : 0;
+#ifdef GPSAT_PROFILE
+    unsigned long long prof_pred = 0;             // time spent in deferred predictions while waiting for a tile
+#endif
     for (;;) {
         __syncthreads();
         HelpArgs ha;
@@ -1981,10 +2062,52 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
                 if (sh->tile != -2) break;
                 helper_episode<D, KN>(c, ha);
             }
+        } else if (defer_on) {
+            // claim a ring slot; while it is empty (the end of the launch), run deferred predictions -- only while no tile
+            // runs on this CU: a prediction beside a running fit slows that fit by ~30 % (E57)
+#ifdef GPSAT_PROFILE
+            const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
+            if (c.tid == 0 && prof_empty == 0 && ring_waiting_tiles(A) <= 0) prof_empty = __builtin_amdgcn_s_memrealtime();
+            prof_pred = 0;
+#endif
+            if (c.tid == 0) sh->hp[7] = (int)ring_claim(A);
+            for (int spins = 0;;) {
+                if (c.tid == 0) {
+                    int e = ring_look(A, (unsigned)sh->hp[7]);
+                    sh->hp[5] = -1;
+                    if (e == -2) {
+                        // never reached by design (minutes of polling): a lost entry must not hang the GPU
+                        if (spins > (1 << 25)) e = -1;
+                        else {
+                            const int q = __hip_atomic_load(&A.cu_busy[my_cu], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 ? pq_claim(A) : -1;
+                            if (q >= 0) { sh->hp[5] = q; sh->hp[4] = pq_wait_entry(A, q); }
+                            else { ++spins; __builtin_amdgcn_s_sleep(64); }
+                        }
+                    }
+                    sh->tile = e;
+                }
+                __syncthreads();
+                const int e = sh->tile, q = sh->hp[5], qt = sh->hp[4];
+                __syncthreads();              // every wave has read them before thread 0 writes them again
+                if (e != -2) break;
+                if (q >= 0 && qt >= 0) {
+#ifdef GPSAT_PROFILE
+                    const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
+#endif
+                    pq_predict<D, KN>(c, A, q, qt, ws_own);
+#ifdef GPSAT_PROFILE
+                    prof_pred += __builtin_amdgcn_s_memtime() - tp0;
+#endif
+                }
+            }
+#ifdef GPSAT_PROFILE
+            if (c.tid == 0) sh->prof[13] += __builtin_amdgcn_s_memtime() - tw0 - prof_pred;
+#endif
         } else if (c.tid == 0) {
             if (sliced) {
 #ifdef GPSAT_PROFILE
                 const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
+                if (prof_empty == 0 && ring_waiting_tiles(A) <= 0) prof_empty = __builtin_amdgcn_s_memrealtime();
 #endif
                 sh->tile = ring_pop(A);
 #ifdef GPSAT_PROFILE
@@ -2060,6 +2183,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
             if (coop_on && c.tid == 0) __hip_atomic_fetch_add(A.coop_live, -1, RLX_AGENT);
             continue;
         }
+        if (defer_on && c.tid == 0) __hip_atomic_fetch_add(&A.cu_busy[my_cu], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // this workgroup owns the tile: its own workspace and control block (it may have helped another tile while it
         // waited for this one: it lets go of it)
         if (coop_on && c.tid == 0 && sh->hp[0] >= 0) {
@@ -2166,7 +2290,10 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
             // so that no compiler pass can drop or move it), THEN the barrier, THEN one lane publishes the ring entry
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (c.tid == 0) ring_push(A, t);
+            if (c.tid == 0) {
+                if (defer_on) __hip_atomic_fetch_add(&A.cu_busy[my_cu], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ring_push(A, t);
+            }
             continue;
         }
 
@@ -2201,13 +2328,23 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
                 if (A.grad) A.grad[(size_t)t * H + i] = sh->fail ? __builtin_nan("") : sh->gth[i];
             }
         }
+        bool deferred = false;
         if (c.P > 0) {
             if (!sh->fail) {
                 float invl[D];
 #pragma unroll
                 for (int d = 0; d < D; ++d) invl[d] = (float)((double)KScale<KN>::c / sh->theta[d]);
-                predict_tile<D, KN>(c, A.Xs + (size_t)p0 * D, A.f_mean + p0, A.f_var + p0, A.y_var + p0, invl,
-                                    A.f_cov ? A.f_cov + A.cov_off[t] : nullptr);
+                if (defer_on && !A.f_cov) {
+                    // other tiles wait for a workgroup: leave the prediction to the end of the launch, where workgroups idle
+                    if (c.tid == 0) sh->hp[6] = ring_waiting_tiles(A) > 0 ? pq_take_slot(A) : -1;
+                    __syncthreads();
+                    deferred = sh->hp[6] >= 0;
+                }
+                if (deferred)
+                    pq_save<D, KN>(c, A, sh->hp[6], t, invl);
+                else
+                    predict_tile<D, KN>(c, A.Xs + (size_t)p0 * D, A.f_mean + p0, A.f_var + p0, A.y_var + p0, invl,
+                                        A.f_cov ? A.f_cov + A.cov_off[t] : nullptr);
             } else {
                 for (long long q = p0 + c.tid; q < p1; q += NT) {
                     A.f_mean[q] = __builtin_nanf(""); A.f_var[q] = __builtin_nanf(""); A.y_var[q] = __builtin_nanf("");
@@ -2216,7 +2353,9 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
                     for (long long q = A.cov_off[t] + c.tid; q < A.cov_off[t + 1]; q += NT) A.f_cov[q] = __builtin_nanf("");
             }
         }
-        if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // a deferred tile stays unfinished until its prediction is written (pq_predict)
+        if (sliced && !deferred && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (defer_on && c.tid == 0) __hip_atomic_fetch_add(&A.cu_busy[my_cu], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (coop_on && c.tid == 0) __hip_atomic_fetch_add(A.coop_live, -1, RLX_AGENT);
     }
 #ifdef GPSAT_PROFILE
@@ -2224,6 +2363,8 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     if (A.prof && c.tid == 0 && blockIdx.x < 1024) {       // when did this workgroup start and run out of work (100 MHz ticks)
         A.prof[64 + 8 * 1024 + blockIdx.x] = prof_r0;
         A.prof[64 + 8 * 1024 + 1024 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+        A.prof[64 + 8 * 1024 + 2048 + blockIdx.x] = prof_empty;
+        A.prof[64 + 8 * 1024 + 3072 + blockIdx.x] = (unsigned long long)cu_index();
     }
     if (blockIdx.x == 0 && c.tid == 0) {       // whole-kernel span of workgroup 0 in both clocks: s_memtime ticks per 100 MHz tick
         sh->prof[14] = __builtin_amdgcn_s_memtime() - prof_k0;
@@ -2238,6 +2379,11 @@ size_t shared_bytes(int D, int NBmax) {
     const size_t NP = (size_t)NBmax * 32;
     size_t fl = (size_t)SHARED_FLOATS + 2 * D * NP + 3 * NP + 10 * BLK + 32 * 33 + 3 + 4 + 32 + 64;
     return (fl * sizeof(float) + 15) & ~size_t(15);
+}
+
+size_t pq_floats_per_slot(int D, int NBmax) {       // pq_save's layout, rounded to whole KiB
+    const size_t fl = (size_t)BLK * ((size_t)NBmax * (NBmax - 1) / 2 + NBmax) + (size_t)(D + 1) * NBmax * 32 + 2 + D;
+    return (fl + 255) & ~size_t(255);
 }
 
 size_t workspace_floats_per_wg(int NBmax, int PCcov) {
@@ -2284,6 +2430,7 @@ hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipSt
 
 size_t GPSAT_VFN(shared_bytes)(int D, int NBmax) { return GPSAT_VNS::shared_bytes(D, NBmax); }
 int GPSAT_VFN(state_words)() { return GPSAT_VNS::SHARED_FLOATS; }
+size_t GPSAT_VFN(pq_floats_per_slot)(int D, int NBmax) { return GPSAT_VNS::pq_floats_per_slot(D, NBmax); }
 size_t GPSAT_VFN(workspace_floats_per_wg)(int NBmax, int PCcov) { return GPSAT_VNS::workspace_floats_per_wg(NBmax, PCcov); }
 hipError_t GPSAT_VFN(launch_tiles)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
     return GPSAT_VNS::launch_tiles(D, a, grid, smem, stream);

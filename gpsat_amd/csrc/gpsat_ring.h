@@ -55,5 +55,46 @@ static __device__ __forceinline__ void ring_push(const KernelArgs& A, int tile) 
     __hip_atomic_store(A.ring + (s & (unsigned)A.ring_mask), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---------------------------------------------------------------------------------------------
+// deferred predictions (KernelArgs::pq): snapshot slot s is taken once per launch (no reuse: the predictions run at the end
+// of the launch, when no fit is left to defer), its entry published after the snapshot's stores have drained.  A slot number
+// past pq_slots means the pool is full: the tile predicts inline.  One thread per workgroup calls these.
+// ---------------------------------------------------------------------------------------------
+static __device__ __forceinline__ int pq_take_slot(const KernelArgs& A) {
+    const int s = __hip_atomic_fetch_add(&A.pq_ctl[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return s < A.pq_slots ? s : -1;
+}
+
+static __device__ __forceinline__ void pq_publish(const KernelArgs& A, int s, int tile) {
+    __hip_atomic_store(&A.pq[s], (unsigned long long)tile + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the next taken slot, -1 when every taken slot is claimed already
+static __device__ __forceinline__ int pq_claim(const KernelArgs& A) {
+    int c = __hip_atomic_load(&A.pq_ctl[16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n = min(__hip_atomic_load(&A.pq_ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), A.pq_slots);
+    while (c < n)
+        if (__hip_atomic_compare_exchange_strong(&A.pq_ctl[16], &c, c + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return c;
+    return -1;
+}
+
+// the tile of a claimed slot: its owner publishes it once the snapshot is written (microseconds).  -1 only after minutes
+// (never by design): the tile stays unfinished, the ring's waits give up, and the host sees unfinished tiles.
+static __device__ __forceinline__ int pq_wait_entry(const KernelArgs& A, int s) {
+    for (int spins = 0;; ++spins) {
+        const unsigned long long v = __hip_atomic_load(&A.pq[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v) return (int)(v - 1ull);
+        if (spins > (1 << 25)) return -1;
+        __builtin_amdgcn_s_sleep(64);
+    }
+}
+
+// this workgroup's CU: XCC_ID << 8 | HW_ID[15:8] (SE, SH, CU), < 2048 (KernelArgs::cu_busy)
+static __device__ __forceinline__ int cu_index() {
+    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 7;
+    return (int)((xcc << 8) | ((hw >> 8) & 0xff));
+}
+
 }  // namespace gpsat
 #endif

@@ -41,3 +41,32 @@ pv = np.array(pb[:], dtype=np.float64).reshape(4, 16)
 if pv[0, 14] > 0:
     print(f"time-sliced queue: the workgroups waited for a tile {100 * pv[0, 13] / (m.sum() * pv[0, 14]):.1f} % of the launch "
           f"(sum of the waits / workgroups x launch, s_memtime ticks)")
+# Where the idle time sits: per workgroup, when it first found no tile waiting in the ring, and its CU.  A CU whose workgroups
+# are both idle could run deferred work without slowing a fit (E57: a CU-mate slows every phase by ~30 %).
+if hasattr(lib, "gpsat_debug_idle"):
+    ib = (C.c_ulonglong * 2048)()
+    lib.gpsat_debug_idle.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    lib.gpsat_debug_idle(eng._h, ib)
+    iv = np.array(ib[:], dtype=np.float64)
+    first_empty, cu = iv[:1024], iv[1024:].astype(np.int64)
+    kend = en[m].max()
+    idle0 = np.where(first_empty[m] > 0, first_empty[m], en[m])          # never found it empty: idle from its exit
+    idle_ms = (kend - idle0) / 1e5
+    print(f"idle after the first empty ring: {idle_ms.sum():.0f} workgroup-ms ({100 * idle_ms.sum() / (m.sum() * (kend - t0) / 1e5):.1f} % "
+          f"of the launch); workgroups that found it empty: {(first_empty[m] > 0).sum()}")
+    cus = {}
+    for i0, c in zip(idle0, cu[m]):
+        cus.setdefault(int(c), []).append(i0)
+    both = {c: max(v) for c, v in cus.items() if len(v) >= 2}
+    print(f"{len(cus)} CUs, {len(both)} with two workgroups; workgroups per CU: {np.bincount([len(v) for v in cus.values()]).tolist()}")
+    for win in (6.0, 12.0, 18.0):
+        w0 = kend - win * 1e5
+        n_full = sum(1 for v in both.values() if v <= w0)
+        full_ms = sum(len(cus[c]) * (kend - max(v, w0)) / 1e5 for c, v in both.items() if v < kend)
+        all_ms = ((kend - np.maximum(idle0, w0)) / 1e5).sum()
+        print(f"last {win:4.1f} ms: CUs with both workgroups idle for all of it {n_full}, at its end {len(both)}; idle "
+              f"workgroup-ms {all_ms:.0f}, of which on CUs whose workgroups are all idle {full_ms:.0f}")
+    full_total = sum(len(cus[c]) * (kend - v) / 1e5 for c, v in both.items())
+    curve = [sum(1 for v in both.values() if v <= kend - q * 1e5) for q in (1, 2, 4, 8, 12, 16, 24)]
+    print(f"workgroup-ms idle on fully idle CUs, whole launch: {full_total:.0f} (prediction work to place: ~3300, E61); "
+          f"fully idle CUs 1/2/4/8/12/16/24 ms before the end: {curve}")
