@@ -15,10 +15,12 @@ Here the SAME four config dicts are accepted (the in-memory subset listed below)
           model object, no per-tile DataFrame;
   shard   with ``world_size > 1`` the global tile list is split by ``sharding.partition_tiles`` (LPT on
           E*N^3 + N^2*P); every rank packs and runs only its own tiles; no data-path collective;
-  pass 2  waves of ``store_every`` expert locations: one ``gpsat_fit_predict_batch`` call per wave (and per model
-          profile), tables assembled with array operations and flushed to the store as one append-only, atomically
-          committed part per wave -- a fault at tile 99 999 loses at most the running wave, and a re-run resumes
-          after the last committed wave (the reference's resume contract, local_experts.py:475-497,908-912);
+  pass 2  waves of ``store_every`` expert locations, each cut per model profile into calls of ``engine_chunk`` tiles that
+          go out on up to ``engine_workers`` engines while the next calls are packed; tables assembled with array
+          operations and flushed to the store as one append-only, atomically committed part per wave (when a wave is
+          one profile, its preds rows are written as pieces as its calls return) -- a fault at tile 99 999 loses at
+          most the running wave, and a re-run resumes after the last committed wave (the reference's resume contract,
+          local_experts.py:475-497,908-912);
   gather  with ``world_size > 1`` ONE gather (``sharding.gather_results``: RCCL over xGMI on the GPU node) returns
           per-tile hyper-parameters + predictions to rank 0, which assembles the tables in the reference's expert order.
 
@@ -68,9 +70,12 @@ from __future__ import annotations
 
 import json
 import os
+import queue
 import re
 import time
 import warnings
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import make_dataclass
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -779,6 +784,25 @@ def _adjust_func(spec):
     raise NotImplementedError("load_params.index_adjust takes {col: {'func': callable or 'lambda x: ...'}}")
 
 
+# The per-tile result matrix ``fixed`` [n, H + _N_RES] (H = D + 2 parameters) holds, after the parameters, these columns at
+# ``H + <name>``.  It stays one float64 matrix so that ``sharding.gather_arrays`` carries it in one piece.
+_NLL, _STATUS, _N_EVAL, _N_ITER, _SECONDS, _OBS_MEAN = range(6)
+_N_RES = 6
+
+
+# One model profile (main, replacement) as a run uses it: what a model decides without the tile's rows (default parameters,
+# box, trainable mask, the clamp's (slice, tol) pairs, scales, local mean) and the profile's engine and predict settings.
+_Profile = make_dataclass("_Profile", [
+    "theta_default", "lo", "hi", "trainable", "clamp", "coords_scale", "obs_scale", "local_mean", "unconstrained_noise",
+    "device", "sgpr", "n_inducing", "inducing_seed", "kernel", "max_iter", "eng_kw", "optimiser", "apply_scale", "full_cov"])
+# Pass 1: the expert locations of a run -- item i is expert ex[i] at locs[i]; its observation rows are idx[off[i]:off[i + 1]]
+# of coords_all / obs_all (fp64), its prediction coordinates pcs[i]; kind 0 skipped silently, 1 stub row, 2 tile, 3 error
+# row; prof_id indexes profiles; theta0, lo, hi [T, H] its start parameters and box.
+_Plan = make_dataclass("_Plan", [
+    "ex", "locs", "off", "idx", "n_obs", "pcs", "n_pred", "kind", "prof_id", "profiles", "theta0", "lo", "hi", "save_params",
+    "want_cov", "coords_all", "obs_all", "config_id", "table_suffix", "optimise", "predict"])
+
+
 # ----------------------------------------------------------------------------------------------------------
 # the batched orchestrator
 # ----------------------------------------------------------------------------------------------------------
@@ -867,12 +891,26 @@ class BatchedLocalExpertOI:
         bad = [p_ for p_ in self.params_to_store if p_ not in PARAM_NAMES + (["inducing_points"] if self.sgpr else [])]
         if bad:
             raise NotImplementedError(f"params_to_store {bad}: not a parameter of this model")
-        self.load_params = model_config.get("load_params")
-        if self.sgpr and self.load_params is not None:
-            lp_ = self.load_params
-            if lp_.get("previous"):
+        self._set_load_params(model_config.get("load_params"))
+        # ---- prediction locations (local_experts.py:254-264)
+        plc = dict(pred_loc_config or {"method": "expert_loc"})
+        self.pred_loc = PredictionLocations(coords_col=self.coords_col, **plc)
+        from .engine import default_engine
+        self.engine = engine if engine is not None else default_engine()
+        self.engine_workers = 2          # engines (HIP streams) that take the chunks of a wave in turn; see _ShardRunner.run
+        self._extra_engines = []
+        self.pack_threads = 4            # host threads that pack one engine call's arrays
+        self._pack_pool = None
+        # tile membership for all experts in one GPU call (bit-identical to the host selector)
+        self.device_select = device_select
+        self.timings = {}
+
+    def _set_load_params(self, lp):
+        """``load_params`` as the run reads it: ``use_previous``, and the file / direct values without ``previous``."""
+        if self.sgpr and lp is not None:
+            if lp.get("previous"):
                 raise NotImplementedError("load_params.previous=True is not built for sparse (SGPR) experts")
-            if "inducing_points" in (lp_.get("param_names") or []) or "inducing_points" in lp_:
+            if "inducing_points" in (lp.get("param_names") or []) or "inducing_points" in lp:
                 raise NotImplementedError("loading inducing_points is not built: every expert picks its own "
                                           "(num_inducing_points / inducing_seed); load the three hyper-parameters only")
         # load_params.previous (local_experts.py:1059-1064): start every tile from the running average of earlier optima.
@@ -883,32 +921,20 @@ class BatchedLocalExpertOI:
         #                              previous=False: nothing is set at all);
         # and `previous` among the keys makes _same_param_table False (:749-758), i.e. parameters are always stored.
         self.use_previous = False
-        self._lp_keys = set(self.load_params) if self.load_params is not None else set()
-        lp = self.load_params
+        self._lp_keys = set(lp) if lp is not None else set()
+        self.load_params = lp
         if lp is not None and lp.get("file") is None and lp.get("previous") is not None:
             self.use_previous = bool(lp["previous"])
             self.load_params = None
         elif lp is not None and "previous" in lp:
             self.load_params = {k: v for k, v in lp.items() if k not in ("previous", "previous_params")}
-        # ---- prediction locations (local_experts.py:254-264)
-        plc = dict(pred_loc_config or {"method": "expert_loc"})
-        self.pred_loc = PredictionLocations(coords_col=self.coords_col, **plc)
-        from .engine import default_engine
-        self.engine = engine if engine is not None else default_engine()
-        self.engine_workers = 2          # engines (HIP streams) that take the chunks of a wave in turn; see run_shard
-        self._extra_engines = []
-        self.pack_threads = 4            # host threads that pack one engine call's arrays
-        self._pack_pool = None
-        # tile membership for all experts in one GPU call (bit-identical to the host selector)
-        self.device_select = device_select
-        self.timings = {}
 
-    # ------------------------------------------------------------------------------------------------------
-    # per-profile template: everything HipGPRModel's constructor + set_parameter_constraints decide that does not
-    # depend on the tile's rows (defaults, scales, box, trainable mask).  One throw-away model on a two-row frame,
-    # as the reference itself does to read param_names (postprocessing.py:202-211).
-    # ------------------------------------------------------------------------------------------------------
-    def _template(self, pf):
+    def _template(self, pf, optimise, predict) -> _Profile:
+        """The profile's record: HipGPRModel's defaults, scales, box and trainable mask from one throw-away model on a
+        two-row frame, as the reference itself does to read param_names (postprocessing.py:202-211)."""
+        kernel = pf["init_params"].get("kernel", "Matern32")
+        if kernel not in L.KERNEL_IDS:
+            raise NotImplementedError(f"kernel {kernel!r}")
         D = len(self.coords_col)
         dummy = pd.DataFrame({**{c: [0.0, 1.0] for c in self.coords_col}, self.obs_col: [0.0, 1.0]})
         ip = {k: v for k, v in pf["init_params"].items() if k not in SGPR_INIT_KEYS}
@@ -924,34 +950,18 @@ class BatchedLocalExpertOI:
         ok = pf["optim_kwargs"]
         m._fix_hyperparameters(list(ok.get("fixed_params") or []))
         # per constrained slice: the tolerance the clamp uses (gpflow_models.py:471-479 with run()'s tol = 1e-2)
-        clamp = []
-        for pn, c in (cons or {}).items():
-            sl = m._slice(pn)
-            if c.get("move_within_tol", True):
-                clamp.append((sl, float(c.get("tol", 1e-2))))
-        return dict(theta_default=theta_default, lo=m._lo.copy(), hi=m._hi.copy(), trainable=m._trainable.copy(),
-                    clamp=clamp, coords_scale=np.broadcast_to(m.coords_scale, (1, D)).astype(np.float64),
-                    obs_scale=float(m.obs_scale.reshape(-1)[0]),
-                    local_mean=isinstance(pf["init_params"].get("obs_mean"), str) and pf["init_params"]["obs_mean"] == "local",
-                    unconstrained_noise=not np.isfinite(m._lo[D + 1]), device=str(m.gpu_name)[:64],
-                    sgpr=bool(pf.get("sgpr")), model=SGPR_MODEL_NAME if pf.get("sgpr") else MODEL_NAME,
-                    n_inducing=int(pf["init_params"].get("num_inducing_points", 500)),
-                    inducing_seed=int(pf["init_params"].get("inducing_seed", 0)))
-
-    def _load_param_tables(self, store: "ResultStore", table_suffix):
-        """load_params tables, read ONCE per run and indexed by expert coordinates (local_experts.py:553-689)."""
-        lp = self.load_params
-        src = lp.get("file")
-        tsuf = lp.get("table_suffix", "")                  # load_params(table_suffix="") default, local_experts.py:561
-        names = lp.get("param_names") or PARAM_NAMES
-        out = {}
-        reader = None if isinstance(src, dict) else ResultStore(src)
-        for pn in names:
-            assert pn in PARAM_NAMES, f"provide param name:{pn}\nis not in param_names:{PARAM_NAMES}"
-            tab = src.get(f"{pn}{tsuf}") if isinstance(src, dict) else reader.read(f"{pn}{tsuf}")
-            if tab is not None and len(tab):
-                out[pn] = tab
-        return out
+        clamp = [(m._slice(pn), float(c.get("tol", 1e-2))) for pn, c in (cons or {}).items() if c.get("move_within_tol", True)]
+        return _Profile(
+            theta_default=theta_default, lo=m._lo.copy(), hi=m._hi.copy(), trainable=m._trainable.copy(), clamp=clamp,
+            coords_scale=np.broadcast_to(m.coords_scale, (1, D)).astype(np.float64),
+            obs_scale=float(m.obs_scale.reshape(-1)[0]),
+            local_mean=isinstance(pf["init_params"].get("obs_mean"), str) and pf["init_params"]["obs_mean"] == "local",
+            unconstrained_noise=not np.isfinite(m._lo[D + 1]), device=str(m.gpu_name)[:64], sgpr=bool(pf.get("sgpr")),
+            n_inducing=int(pf["init_params"].get("num_inducing_points", 500)),
+            inducing_seed=int(pf["init_params"].get("inducing_seed", 0)), kernel=kernel, max_iter=int(ok.get("max_iter", 10_000)),
+            eng_kw={k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok},
+            optimiser=ok.get("optimiser", "lbfgs") if optimise else "none", apply_scale=pf["pred_kwargs"].get("apply_scale", True),
+            full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict)
 
     def _loaded_theta(self, tabs, locs, theta, unconstrained_noise):
         """Overwrite rows of ``theta`` [T, H] with the stored parameters of each expert location.  Returns the mask of
@@ -960,8 +970,7 @@ class BatchedLocalExpertOI:
         found_any = np.zeros(len(locs), dtype=bool)
         look = locs.copy()
         for col, spec in (self.load_params.get("index_adjust") or {}).items():
-            j = cc.index(col)
-            f = _adjust_func(spec)
+            j, f = cc.index(col), _adjust_func(spec)
             look[:, j] = [f(v) for v in look[:, j]]
         key = _index_for(cc, look)
         slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
@@ -990,17 +999,16 @@ class BatchedLocalExpertOI:
             check_config_compatible: bool = True, skip_valid_checks_on: Optional[List[str]] = None,
             rank: Optional[int] = None, world_size: Optional[int] = None, gather: bool = True,
             engine_chunk: Optional[int] = None):
-        """See the module docstring.  ``store_every``: expert locations per flushed wave (default 4096;
-        ``max_tiles_per_call`` is the older name of the same knob).  ``engine_chunk``: tiles per engine call inside a wave
-        (default 1024: with two engines the kernel of one call runs while the other call's arrays are copied and unpacked, and the
-        tail of one kernel is filled by the next -- 4096 experts 18.0 -> 19.3 k tiles/s, 16 384 experts 19.5 -> 22.2 k against calls of
-        4096): while the GPU works on one call the host packs the next (gather, scale, de-mean, centre, cast).  ``rank`` / ``world_size``: tile-sharded run, one
-        process per GPU (default: taken from an initialised ``torch.distributed`` group, else 0 / 1); with
-        ``gather=True`` rank 0 returns the global tables in expert order, the other ranks their own shard's
-        (``gather="always"`` runs the exchange in a group of one rank too).
-        ``world_size > 1`` with ``rank=None`` and no process group runs all the LOGICAL shards one after the other on
-        this process's engine and merges them with the routine that closes the gather -- the one-GPU rehearsal of the
-        multi-GPU path."""
+        """See the module docstring.  ``store_every``: expert locations per flushed wave (default 4096; ``max_tiles_per_call``
+        is the older name of the same knob).  ``engine_chunk``: tiles per engine call inside a wave (default 1024: with two
+        engines the kernel of one call runs while the other call's arrays are copied and unpacked, and the tail of one kernel
+        is filled by the next -- 4096 experts 18.0 -> 19.3 k tiles/s, 16 384 experts 19.5 -> 22.2 k against calls of 4096):
+        while the GPU works on one call the host packs the next (gather, scale, de-mean, centre, cast).  ``rank`` /
+        ``world_size``: tile-sharded run, one process per GPU (default: taken from an initialised ``torch.distributed``
+        group, else 0 / 1); with ``gather=True`` rank 0 returns the global tables in expert order, the other ranks their own
+        shard's (``gather="always"`` runs the exchange in a group of one rank too).  ``world_size > 1`` with ``rank=None``
+        and no process group runs all the LOGICAL shards one after the other on this process's engine and merges them with
+        the routine that closes the gather -- the one-GPU rehearsal of the multi-GPU path."""
         t_start = time.perf_counter()
         d_rank, d_world = _dist_rank_world()
         logical = world_size is not None and world_size > 1 and rank is None and d_world == 1
@@ -1009,24 +1017,66 @@ class BatchedLocalExpertOI:
         elif rank is None or world_size is None:
             rank, world_size = d_rank, d_world
         in_group = (not logical) and world_size > 1 and d_world == world_size
-        if world_size > 1 and not logical and not in_group:
+        if world_size > 1 and not logical and not in_group and gather:
             # explicit rank / world_size without a process group of that size: the caller synchronises the ranks itself
             # (nothing here can separate reading the resume state from rank 0's writes, and nothing can gather)
-            if gather:
-                raise RuntimeError(f"run(rank={rank}, world_size={world_size}, gather=True) needs an initialised "
-                                   f"torch.distributed group of {world_size} ranks (found {d_world}); pass gather=False to run "
-                                   f"this rank's shard on its own (start the ranks only after the store directory exists)")
+            raise RuntimeError(f"run(rank={rank}, world_size={world_size}, gather=True) needs an initialised "
+                               f"torch.distributed group of {world_size} ranks (found {d_world}); pass gather=False to run "
+                               f"this rank's shard on its own (start the ranks only after the store directory exists)")
         store = ResultStore(store_path, rank=rank)
-        cc = self.coords_col
-        D, H = len(cc), len(cc) + 2
-        xl = self.expert_locs
         wave_n = int(store_every or max_tiles_per_call or 4096)
         chunk_n = max(1, int(engine_chunk or 1024))
-        # ---- expert_locs table + config bookkeeping (local_experts.py:873-903); rank 0 owns the shared files
-        config_id = 1
-        if store_path:
+        config_id, ex = self._open_store(store, table_suffix, check_config_compatible, skip_valid_checks_on, in_group,
+                                         {"optimise": optimise, "predict": predict, "min_obs": min_obs,
+                                          "table_suffix": table_suffix, "store_every": wave_n, "dtype": self.dtype})
+        self.timings["setup_s"] = time.perf_counter() - t_start
+        self.timings["flush_wait_s"] = 0.0
+        plan = self._plan(ex, store_path, optimise, predict, min_obs, table_suffix, config_id)
+        # shard: LPT on the cost model over the items of this run; silently skipped locations produce nothing
+        tile = plan.kind == 2
+        parts = sharding.partition_tiles(np.where(tile, plan.n_obs, 0), np.where(tile, plan.n_pred if predict else 0, 0),
+                                         world_size) if world_size > 1 else [np.arange(len(ex), dtype=np.int64)]
+        parts = [p_[plan.kind[p_] != 0] for p_ in parts]
+        self.timings.update(engine_s=0.0, engine_call_s=0.0, kernel_s=0.0, tables_s=0.0, flush_s=0.0)
+        self.timings["calls"] = []          # per engine call: (job, tiles, start, end, kernel seconds), times from the start of run()
+        shards, got = [], None
+        try:
+            if logical:
+                # every logical shard on this engine, merged by the routine that closes the gather
+                for r_ in range(world_size):
+                    st_r = ResultStore(store_path, rank=r_)
+                    st_r.drop_uncommitted()
+                    shards.append(_ShardRunner(self, plan, parts[r_], st_r, wave_n, chunk_n, t_start).run())
+                got = self._merge(plan, shards)
+            else:
+                shards.append(_ShardRunner(self, plan, parts[rank] if world_size > 1 else parts[0], store, wave_n, chunk_n,
+                                           t_start).run())
+                if gather and (world_size > 1 or (gather == "always" and d_world == 1 and _dist_initialised())):
+                    got = self._gather(plan, shards[0], world_size, rank)          # None on the ranks other than 0
+            if got is not None:
+                all_items = np.nonzero(plan.kind != 0)[0]
+                out = self._tables(plan, all_items, got[0][all_items], got[1], got[2])
+            else:
+                sh = shards[0]
+                out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
+        finally:
+            tf = time.perf_counter()                               # also after a fault: what was committed is on disk
+            for sh in reversed(shards):
+                while sh.flush:
+                    sh.flush.pop().result()
+            self.timings["flush_wait_s"] += time.perf_counter() - tf
+        self.run_seconds = time.perf_counter() - t_start
+        self.timings["total_s"] = self.run_seconds
+        return out
+
+    def _open_store(self, store, table_suffix, check_config_compatible, skip_valid_checks_on, in_group, run_kwargs):
+        """expert_locs and config bookkeeping (local_experts.py:873-903; rank 0 owns the shared files) and resume: the config
+        id and the positions of the expert locations not yet in run_details (local_experts.py:475-497,908-912)."""
+        cc, xl = self.coords_col, self.expert_locs
+        config_id, done = 1, None
+        if store.path:
             store.drop_uncommitted()
-            cfg_file = os.path.join(store_path, f"oi_config{table_suffix}.json")
+            cfg_file = os.path.join(store.path, f"oi_config{table_suffix}.json")
             prev = json.load(open(cfg_file)) if os.path.exists(cfg_file) else []
             if prev and check_config_compatible:
                 check_prev_oi_config(prev[-1]["config"], self.config, skip_valid_checks_on)
@@ -1035,36 +1085,45 @@ class BatchedLocalExpertOI:
             if in_group:
                 import torch.distributed as dist
                 dist.barrier()
-            if rank == 0:
+            if store.rank == 0:
                 prev.append({"idx": config_id, "datetime": time.strftime("%Y-%m-%d %H:%M:%S"), "config": self.config,
-                             "run_kwargs": {"optimise": optimise, "predict": predict, "min_obs": min_obs,
-                                            "table_suffix": table_suffix, "store_every": wave_n, "dtype": self.dtype}})
+                             "run_kwargs": run_kwargs})
                 with open(cfg_file + ".tmp", "w") as f:
                     json.dump(prev, f)
                 os.replace(cfg_file + ".tmp", cfg_file)
                 if store.read(f"expert_locs{table_suffix}") is None:
                     store.put(f"expert_locs{table_suffix}", xl.set_index(cc))
-        # ---- resume: drop expert locations already in run_details (local_experts.py:475-497,908-912)
         todo = np.ones(len(xl), dtype=bool)
-        if not store_path:
-            done = None
         if done is not None and len(done):
             todo = ~np.asarray(_index_for(cc, xl[cc].values.astype(np.float64)).isin(done.index))
-        ex = np.nonzero(todo)[0]                                   # global expert positions still to run
-        locs = xl[cc].values.astype(np.float64)[ex]
+        return config_id, np.nonzero(todo)[0]
 
-        # ---------------- pass 1: membership, prediction coordinates, parameter vectors (whole-array) ----------------
-        self.timings["setup_s"] = time.perf_counter() - t_start
-        self.timings["flush_wait_s"] = 0.0
+    # ---------------- pass 1: membership, prediction coordinates, parameter vectors (whole-array) ----------------
+    def _plan(self, ex, store_path, optimise, predict, min_obs, table_suffix, config_id) -> _Plan:
+        cc = self.coords_col
+        locs = self.expert_locs[cc].values.astype(np.float64)[ex]
+        off, idx, pcs = self._select(self.expert_locs.iloc[ex], locs)
         t0 = time.perf_counter()
-        refs = xl.iloc[ex]
-        # the prediction locations of all experts on a second engine (another HIP stream) while the first selects the observations
-        pcs_f = None
-        sel_engines = self._engine_pool(2) if (self.device_select and len(ex)) else [self.engine]
-        if len(sel_engines) > 1:
-            from concurrent.futures import ThreadPoolExecutor
-            sel_pool = ThreadPoolExecutor(max_workers=1)
-            pcs_f = sel_pool.submit(self.pred_loc.batch, locs, sel_engines[1])
+        n_obs, n_pred = np.diff(off), pcs.counts.astype(np.int64)
+        kind, prof_id = self._kinds(n_obs, n_pred, min_obs)
+        profiles = [self._template(self.profiles[pname], optimise, predict) for pname in self.profiles]
+        theta0, lo, hi, save_params = self._start_params(profiles, prof_id, kind, locs, store_path, table_suffix, optimise)
+        self.timings["params_s"] = time.perf_counter() - t0
+        coords_all, obs_all = self.df.loc[:, cc].values.astype(np.float64), self.df[self.obs_col].values.astype(np.float64)
+        assert not np.isnan(coords_all).any(), "nans found in coords"
+        assert not np.isnan(obs_all).any(), "nans found in obs"
+        return _Plan(ex=ex, locs=locs, off=off, idx=idx, n_obs=n_obs, pcs=pcs, n_pred=n_pred, kind=kind, prof_id=prof_id,
+                     profiles=profiles, theta0=theta0, lo=lo, hi=hi, save_params=save_params, coords_all=coords_all,
+                     want_cov=any(pf.full_cov for pf in profiles), obs_all=obs_all, config_id=config_id,
+                     table_suffix=table_suffix, optimise=optimise, predict=predict)
+
+    def _select(self, refs, locs):
+        """Membership CSR (off, idx) of every expert in ``refs`` and its prediction coordinates; with ``device_select`` the
+        prediction locations are built on a second engine (another HIP stream) while the first selects the observations."""
+        t0 = time.perf_counter()
+        sel_engines = self._engine_pool(2) if (self.device_select and len(locs)) else [self.engine]
+        sel_pool = ThreadPoolExecutor(max_workers=1) if len(sel_engines) > 1 else None
+        pcs_f = sel_pool.submit(self.pred_loc.batch, locs, sel_engines[1]) if sel_pool is not None else None
         self.timings["dynamic_select_s"] = 0.0
         if len(self.local_select):
             codes = bounds = None
@@ -1076,437 +1135,160 @@ class BatchedLocalExpertOI:
                 else LocalSelector(self.df, self.local_select, interval_codes=codes)
             off, idx = sel.select(refs, bounds=bounds)
         else:
-            off, idx = np.arange(len(ex) + 1, dtype=np.int64) * len(self.df), np.tile(np.arange(len(self.df)), len(ex))
-        n_obs = np.diff(off)
+            off, idx = np.arange(len(locs) + 1, dtype=np.int64) * len(self.df), np.tile(np.arange(len(self.df)), len(locs))
         if pcs_f is not None:
             pcs = pcs_f.result()
             sel_pool.shutdown(wait=True)
         else:
-            pcs = self.pred_loc.batch(locs, self.engine if self.device_select else None) if len(ex) \
-                else RaggedRows(np.zeros((0, D)), np.zeros(1, dtype=np.int64))
-        n_pred = pcs.counts.astype(np.int64)
+            pcs = self.pred_loc.batch(locs, self.engine if self.device_select else None) if len(locs) \
+                else RaggedRows(np.zeros((0, len(self.coords_col))), np.zeros(1, dtype=np.int64))
         self.timings["select_s"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        # item kinds: 0 skipped silently (no prediction locations, local_experts.py:962-965), 1 stub row
-        # (N < min_obs, :988-1012), 2 tile, 3 error row (tile larger than the kernels take)
-        kind = np.full(len(ex), 2, dtype=np.int8)
+        return off, idx, pcs
+
+    def _kinds(self, n_obs, n_pred, min_obs):
+        """Item kinds -- 0 skipped silently (no prediction locations, local_experts.py:962-965), 1 stub row (N < min_obs,
+        :988-1012), 2 tile, 3 error row (tile larger than the kernels take) -- and model profiles (:1021-1041)."""
+        kind = np.full(len(n_obs), 2, dtype=np.int8)
         is_repl = (n_obs < self.replacement_threshold) if self.replacement_threshold is not None \
-            else np.zeros(len(ex), dtype=bool)                      # local_experts.py:1021-1041
+            else np.zeros(len(n_obs), dtype=bool)
         prof_names = list(self.profiles)
         prof_id = np.where(is_repl, prof_names.index("replacement") if "replacement" in prof_names else 0, 0)
         sgpr_prof = np.array([bool(self.profiles[p_].get("sgpr")) for p_ in prof_names])
         # largest tile the exact kernels take (gpsat_max_tile_obs): larger ones get an explicit error row instead of failing
         # the whole batch.  Sparse tiles have no such limit (the kernel counts rows in 32-bit integers).
-        max_obs = L.max_tile_obs(self.dtype, D)
+        max_obs = L.max_tile_obs(self.dtype, len(self.coords_col))
         kind[np.where(sgpr_prof[prof_id], n_obs > 2 ** 31 - 1, n_obs > max_obs)] = 3
         kind[n_obs < min_obs] = 1
         kind[n_pred == 0] = 0
         if (kind == 3).any():
             warnings.warn(f"{int((kind == 3).sum())} expert locations select more observations than the kernels take "
                           f"(exact GP: {max_obs}): not run (error row in run_details)")
-        tmpl, pinfo = {}, {}
-        for pi, pname in enumerate(prof_names):
-            pf = self.profiles[pname]
-            kernel = pf["init_params"].get("kernel", "Matern32")
-            if kernel not in L.KERNEL_IDS:
-                raise NotImplementedError(f"kernel {kernel!r}")
-            ok = pf["optim_kwargs"]
-            tmpl[pi] = self._template(pf)
-            pinfo[pi] = dict(kernel=kernel, max_iter=int(ok.get("max_iter", 10_000)),
-                             eng_kw={k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok},
-                             optimiser=ok.get("optimiser", "lbfgs") if optimise else "none",
-                             apply_scale=pf["pred_kwargs"].get("apply_scale", True),
-                             full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict)
-        theta0 = np.zeros((len(ex), H))
-        lo = np.full((len(ex), H), np.nan)
-        hi = np.full((len(ex), H), np.nan)
-        save_params = np.ones(len(ex), dtype=bool)
-        for pi in tmpl:
-            m_ = prof_id == pi
-            theta0[m_], lo[m_], hi[m_] = tmpl[pi]["theta_default"], tmpl[pi]["lo"], tmpl[pi]["hi"]
-        if self.load_params is not None:
-            lp = self.load_params
-            if lp.get("file") is not None:
-                tabs = self._load_param_tables(store, table_suffix)
-                for pi in tmpl:
-                    m_ = np.nonzero((prof_id == pi) & (kind == 2))[0]
-                    th = theta0[m_]
-                    got = self._loaded_theta(tabs, locs[m_], th, tmpl[pi]["unconstrained_noise"])
-                    theta0[m_] = th
-                    kind[m_[~got]] = 0                              # nothing loadable: tile skipped (:1099-1101)
-                same = (lp.get("file") == store_path and lp.get("table_suffix", None) == table_suffix and
-                        self._lp_keys <= {"file", "table_suffix"})           # _same_param_table, :749-758
-                save_params[:] = not (same and not optimise)        # local_experts.py:1090-1097
-            else:
-                # parameters given directly (load_params(**param_dict), local_experts.py:553-604)
-                direct = {k: v for k, v in lp.items() if k in PARAM_NAMES}
-                if not direct:
-                    raise NotImplementedError("load_params needs 'file' or parameter values")
-                for pn, v in direct.items():
-                    v = np.asarray(v, dtype=np.float64).reshape(-1)
-                    if pn == "lengthscales":
-                        theta0[:, :D] = v
-                    else:
-                        theta0[:, D + PARAM_NAMES.index(pn) - 1] = v[0]
-        for pi, t_ in tmpl.items():                                  # move within tol of the box (gpflow_models.py:471-479)
-            m_ = prof_id == pi
-            for sl, tol in t_["clamp"]:
-                theta0[m_, sl] = clamp_within(theta0[m_, sl], t_["lo"][sl], t_["hi"][sl], tol)
-        self.timings["params_s"] = time.perf_counter() - t0
-        want_cov = any(p_["full_cov"] for p_ in pinfo.values())
+        return kind, prof_id
 
-        # ---------------- shard: LPT on the cost model over the items of this run ----------------
-        cost_n = np.where(kind == 2, n_obs, 0)
-        if world_size > 1:
-            parts = sharding.partition_tiles(cost_n, np.where(kind == 2, n_pred if predict else 0, 0), world_size)
+    def _start_params(self, profiles, prof_id, kind, locs, store_path, table_suffix, optimise):
+        """theta0, lo, hi [T, H] and the mask of items whose parameters are stored: the profile's defaults, then ``load_params``
+        (a file's tables -- an item with nothing loadable is skipped, kind 0 -- or direct values), then the move within tol."""
+        D, save_params = len(self.coords_col), np.ones(len(kind), dtype=bool)
+        theta0, lo, hi = (np.array([getattr(pf, f) for pf in profiles], dtype=np.float64)[prof_id]
+                          for f in ("theta_default", "lo", "hi"))
+        lp = self.load_params
+        if lp is not None and lp.get("file") is not None:
+            # the tables, read ONCE per run and indexed by expert coordinates (local_experts.py:553-689)
+            src, tsuf = lp.get("file"), lp.get("table_suffix", "")   # load_params(table_suffix="") default, :561
+            reader, tabs = None if isinstance(src, dict) else ResultStore(src), {}
+            for pn in lp.get("param_names") or PARAM_NAMES:
+                assert pn in PARAM_NAMES, f"provide param name:{pn}\nis not in param_names:{PARAM_NAMES}"
+                tab = src.get(f"{pn}{tsuf}") if isinstance(src, dict) else reader.read(f"{pn}{tsuf}")
+                if tab is not None and len(tab):
+                    tabs[pn] = tab
+            for pi, pf in enumerate(profiles):
+                m_ = np.nonzero((prof_id == pi) & (kind == 2))[0]
+                th = theta0[m_]
+                got = self._loaded_theta(tabs, locs[m_], th, pf.unconstrained_noise)
+                theta0[m_] = th
+                kind[m_[~got]] = 0                              # nothing loadable: tile skipped (:1099-1101)
+            same = (lp.get("file") == store_path and lp.get("table_suffix", None) == table_suffix and
+                    self._lp_keys <= {"file", "table_suffix"})           # _same_param_table, :749-758
+            save_params[:] = not (same and not optimise)        # local_experts.py:1090-1097
+        elif lp is not None:
+            # parameters given directly (load_params(**param_dict), local_experts.py:553-604)
+            direct = {k: v for k, v in lp.items() if k in PARAM_NAMES}
+            if not direct:
+                raise NotImplementedError("load_params needs 'file' or parameter values")
+            for pn, v in direct.items():
+                v = np.asarray(v, dtype=np.float64).reshape(-1)
+                if pn == "lengthscales":
+                    theta0[:, :D] = v
+                else:
+                    theta0[:, D + PARAM_NAMES.index(pn) - 1] = v[0]
+        for pi, pf in enumerate(profiles):                      # move within tol of the box (gpflow_models.py:471-479)
+            m_ = prof_id == pi
+            for sl, tol in pf.clamp:
+                theta0[m_, sl] = clamp_within(theta0[m_, sl], pf.lo[sl], pf.hi[sl], tol)
+        return theta0, lo, hi, save_params
+
+    # ---------------- pass 2 helpers: one engine call's arrays; merge / gather of the shards ----------------
+    def _pack_job(self, plan, pf, ids):
+        """Host-side intake of one engine call (a1 of the reference in fp64): gather the tiles' rows, scale, de-mean, centre,
+        cast -- by `pack_threads` threads, each writing its range of tiles (NumPy releases the GIL in gathers and arithmetic)."""
+        D = len(self.coords_col)
+        Ns = plan.n_obs[ids]
+        o_off = np.concatenate([[0], np.cumsum(Ns)]).astype(np.int64)
+        Ps = plan.n_pred[ids] if plan.predict else np.zeros(len(ids), dtype=np.int64)
+        p_off = np.concatenate([[0], np.cumsum(Ps)]).astype(np.int64)
+        out_dt = np.float32 if self.dtype == "f32" else np.float64
+        X, y = np.empty((int(o_off[-1]), D), dtype=out_dt), np.empty(int(o_off[-1]), dtype=out_dt)
+        Xs, mean = np.empty((int(p_off[-1]), D), dtype=out_dt), np.zeros(len(ids))
+        consecutive = len(ids) > 0 and bool(np.all(np.diff(ids) == 1))
+        idx, off = plan.idx, plan.off
+
+        def sub(a, b):
+            sl = ids[a:b]
+            if consecutive:
+                rows = idx[off[sl[0]]:off[sl[-1] + 1]]
+            else:
+                rows = np.concatenate([idx[off[i]:off[i + 1]] for i in sl])
+            ns, oo = Ns[a:b], o_off[a:b + 1] - o_off[a]
+            Xd = plan.coords_all[rows] / pf.coords_scale        # base_model.py:243
+            yv_ = plan.obs_all[rows]
+            if pf.local_mean:
+                mean[a:b] = np.add.reduceat(yv_, oo[:-1]) / ns
+            yd = (yv_ - np.repeat(mean[a:b], ns)) / pf.obs_scale   # base_model.py:244-245
+            if plan.predict:
+                Xsd = plan.pcs.take(sl)
+                if pf.apply_scale:
+                    Xsd = Xsd / pf.coords_scale
+            else:
+                Xsd = np.zeros((0, D))
+            if self.dtype == "f32" and len(Xd):
+                # what the engine does with fp64 host arrays for the fp32 kernels (per-tile centring, then the cast), done
+                # here so that it too overlaps the previous call
+                from .engine import centre_tiles
+                Xd, Xsd = centre_tiles(Xd, Xsd, oo, p_off[a:b + 1] - p_off[a])
+            X[o_off[a]:o_off[b]] = Xd
+            y[o_off[a]:o_off[b]] = yd
+            Xs[p_off[a]:p_off[b]] = Xsd
+
+        nsub = max(1, min(self.pack_threads, len(ids) // 128))
+        bounds = np.linspace(0, len(ids), nsub + 1).astype(np.int64)
+        if nsub == 1:
+            sub(0, len(ids))
         else:
-            parts = [np.arange(len(ex), dtype=np.int64)]
-        parts = [p_[kind[p_] != 0] for p_ in parts]                  # silently skipped locations produce nothing
-
-        coords_all = self.df.loc[:, cc].values.astype(np.float64)
-        obs_all = self.df[self.obs_col].values.astype(np.float64)
-        assert not np.isnan(coords_all).any(), "nans found in coords"
-        assert not np.isnan(obs_all).any(), "nans found in obs"
-        self.timings.update(engine_s=0.0, engine_call_s=0.0, kernel_s=0.0, tables_s=0.0, flush_s=0.0)
-        self.timings["calls"] = []          # per engine call: (job, tiles, start, end, kernel seconds), times from the start of run()
-
-        def inducing_for(i):
-            """The inducing points of item i (scaled coordinates): what HipSGPRModel picks for the same rows."""
-            t_ = tmpl[prof_id[i]]
-            Xd = coords_all[idx[off[i]:off[i + 1]]] / t_["coords_scale"]
-            return select_inducing_points(Xd, t_["n_inducing"], t_["inducing_seed"], int(ex[i]))
-
-        def tables_for(items, fixed, pred_cat, cov_cat=None, with_preds=True):
-            return self._tables(ex[items], locs[items], kind[items], n_obs[items], fixed, pred_cat,
-                                (pcs, items) if predict else None, save_params[items],
-                                [tmpl[p]["device"] for p in prof_id[items]], optimise, config_id, table_suffix,
-                                models=[tmpl[p]["model"] for p in prof_id[items]],
-                                inducing=[inducing_for(i) if (kind[i] == 2 and tmpl[prof_id[i]]["sgpr"]) else None
-                                          for i in items] if "inducing_points" in self.params_to_store else None,
-                                cov_cat=cov_cat, cov_tiles=(kind[items] == 2) & np.array([pinfo[p]["full_cov"] for p in prof_id[items]], dtype=bool)
-                                if want_cov else None, with_preds=with_preds)
-
-        # ---------------- pass 2: waves of one shard ----------------
-        def pack_job(ids, pi):
-            """Host-side intake of one engine call (a1 of the reference in fp64): gather the tiles' rows, scale, de-mean, centre,
-            cast -- by `pack_threads` threads, each writing its range of tiles into the call's arrays (NumPy releases the GIL
-            in the gathers and the arithmetic)."""
-            t_, p_ = tmpl[pi], pinfo[pi]
-            Ns = n_obs[ids]
-            o_off = np.concatenate([[0], np.cumsum(Ns)]).astype(np.int64)
-            Ps = n_pred[ids] if predict else np.zeros(len(ids), dtype=np.int64)
-            p_off = np.concatenate([[0], np.cumsum(Ps)]).astype(np.int64)
-            out_dt = np.float32 if self.dtype == "f32" else np.float64
-            X = np.empty((int(o_off[-1]), D), dtype=out_dt)
-            y = np.empty(int(o_off[-1]), dtype=out_dt)
-            Xs = np.empty((int(p_off[-1]), D), dtype=out_dt)
-            mean = np.zeros(len(ids))
-            consecutive = len(ids) > 0 and bool(np.all(np.diff(ids) == 1))
-
-            def sub(a, b):
-                sl = ids[a:b]
-                if consecutive:
-                    rows = idx[off[sl[0]]:off[sl[-1] + 1]]
-                else:
-                    rows = np.concatenate([idx[off[i]:off[i + 1]] for i in sl])
-                ns, oo = Ns[a:b], o_off[a:b + 1] - o_off[a]
-                Xd = coords_all[rows] / t_["coords_scale"]        # base_model.py:243
-                yv_ = obs_all[rows]
-                if t_["local_mean"]:
-                    mean[a:b] = np.add.reduceat(yv_, oo[:-1]) / ns
-                yd = (yv_ - np.repeat(mean[a:b], ns)) / t_["obs_scale"]   # base_model.py:244-245
-                if predict:
-                    Xsd = pcs.take(sl)
-                    if p_["apply_scale"]:
-                        Xsd = Xsd / t_["coords_scale"]
-                else:
-                    Xsd = np.zeros((0, D))
-                if self.dtype == "f32" and len(Xd):
-                    # what the engine does with fp64 host arrays for the fp32 kernels (per-tile centring, then the cast), done
-                    # here so that it too overlaps the previous call
-                    from .engine import centre_tiles
-                    Xd, Xsd = centre_tiles(Xd, Xsd, oo, p_off[a:b + 1] - p_off[a])
-                X[o_off[a]:o_off[b]] = Xd
-                y[o_off[a]:o_off[b]] = yd
-                Xs[p_off[a]:p_off[b]] = Xsd
-
-            nsub = max(1, min(self.pack_threads, len(ids) // 128))
-            bounds = np.linspace(0, len(ids), nsub + 1).astype(np.int64)
-            if nsub == 1:
-                sub(0, len(ids))
-            else:
-                for f_ in [self._sub_pool().submit(sub, int(bounds[j]), int(bounds[j + 1])) for j in range(nsub)]:
-                    f_.result()
-            out = dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
-            if t_["sgpr"]:
-                # per tile the inducing points HipSGPRModel picks: a seeded subset of the tile's scaled coordinates
-                Zs = [select_inducing_points(X[o_off[j]:o_off[j + 1]], t_["n_inducing"], t_["inducing_seed"], int(ex[i]))
-                      for j, i in enumerate(ids)]
-                out["z_off"] = np.concatenate([[0], np.cumsum([len(z) for z in Zs])]).astype(np.int64)
-                out["Z"] = np.concatenate(Zs) if Zs else np.zeros((0, D))
-            return out
-
-        # ---------------- pass 2: waves of one shard ----------------
-        # A wave (the flush unit) is cut into engine calls of at most `engine_chunk` tiles; the next call's arrays are packed
-        # by a helper thread while the GPU works on the current one (ctypes releases the GIL during the call).  Per-tile
-        # results do not depend on how tiles are batched (tests/test_gpu_parity.py::test_ragged_batch_tile_indexing_is_bit_exact).
-        def run_shard(mine, shard_store):
-            from concurrent.futures import ThreadPoolExecutor
-            fixed_rows, pred_rows, cov_rows = [], [], []
-            # load_params.previous: the running average of earlier optima (rho = 0.95, local_experts.py:1200-1217); it starts
-            # from the default parameters of the first model built (:1053-1054)
-            prev = {"theta": None}
-            jobs = []                                                  # (wave index, profile, positions within the wave)
-            waves = [mine[w0:w0 + wave_n] for w0 in range(0, len(mine), wave_n)]
-            for wi, items in enumerate(waves):
-                for pi in tmpl:
-                    loc_ids = np.nonzero((kind[items] == 2) & (prof_id[items] == pi))[0]
-                    for c0 in range(0, len(loc_ids), chunk_n):
-                        jobs.append((wi, pi, loc_ids[c0:c0 + chunk_n]))
-            last_job_of_wave = {wi: k for k, (wi, _, _) in enumerate(jobs)}
-            state = {}
-            # The predictions are most of a wave's bytes: when a wave's tiles run as consecutive calls of ONE model profile (the
-            # rows of its preds table are then the calls' rows back to back), every call's rows go to the store as a row piece
-            # as soon as the call returns, and the wave's flush is left with the small tables and the marker.
-            jobs_of_wave = {}
-            for k, (wi, pi, _) in enumerate(jobs):
-                jobs_of_wave.setdefault(wi, []).append(k)
-            incremental = {wi: bool(shard_store.path) and predict and len(ks) <= 64 and len({jobs[k][1] for k in ks}) == 1
-                           for wi, ks in jobs_of_wave.items()}
-            piece_futs = {}
-            preds_name = f"preds{table_suffix}"
-
-            def open_wave(wi):
-                items = waves[wi]
-                state[wi] = (np.full((len(items), H + 6), np.nan),       # theta, nll, status, n_eval, n_iter, seconds, obs mean
-                             [np.zeros((0, 3))] * len(items), [np.zeros((0, 2))] * len(items))
-
-            def close_wave(wi):
-                items = waves[wi]
-                fixed, preds, covs = state.pop(wi)
-                tt = time.perf_counter()
-                pred_cat = np.concatenate(preds) if len(preds) else np.zeros((0, 3))
-                cov_cat = (np.concatenate(covs) if len(covs) else np.zeros((0, 2))) if want_cov else None
-                pf_ = piece_futs.pop(wi, [])
-                # the predictions went out as pieces: the wave's flush needs the small tables only, and the wave's preds frame
-                # is built (after the flush is queued) only where it is returned -- the only wave of a run
-                lazy = bool(pf_) and not want_cov
-                tables = tables_for(items, fixed, pred_cat, cov_cat, with_preds=not lazy)
-                self.timings["tables_s"] += time.perf_counter() - tt
-                tf = time.perf_counter()
-                # commit: these experts are done.  The parts are written by a helper thread while the next wave runs (one
-                # writer, waves in order, marker last); a flush that fails surfaces when the next one is queued or at the end
-                if pending:
-                    pending.pop().result()
-
-                def commit(pf_=pf_, tables=dict(tables), n_pred_rows=len(pred_cat)):
-                    for f_ in pf_:                                     # done by now (one writer, in order): a failed piece fails the wave
-                        f_.result()
-                    shard_store.write_wave(tables, prewritten={preds_name: n_pred_rows} if pf_ else {})
-                pending.append(flusher.submit(commit))
-                self.timings["flush_s"] += time.perf_counter() - tf
-                if len(waves) == 1:
-                    if lazy:
-                        tt = time.perf_counter()
-                        tile_ = kind[items] == 2
-                        cnt_ = np.where(tile_, pcs.counts[items], 0).astype(np.int64)
-                        tables[preds_name] = self._preds_frame(locs[items], fixed[:, H + 5], pred_cat, pcs,
-                                                               np.asarray(items, dtype=np.int64), tile_, cnt_)
-                        self.timings["tables_s"] += time.perf_counter() - tt
-                    single["tables"] = tables                          # the only wave's tables ARE the shard's tables
-                fixed_rows.append(fixed)
-                pred_rows.append(pred_cat)
-                if want_cov:
-                    cov_rows.append(cov_cat)
-
-            pending = []
-            single = {}
-            # Engine calls of consecutive chunks are issued from `n_eng` threads, each with an engine (HIP stream, workspace)
-            # of its own: the second call's kernel is queued on the GPU while the first one runs and its workgroups take
-            # over the CUs the first one's tail leaves idle; packing, the copies and the unpacking of one call overlap the
-            # kernel of the other.  `load_params.previous` makes every call depend on the one before: one engine then.
-            engines = self._engine_pool(1 if self.use_previous else self.engine_workers)
-            n_eng = len(engines)
-            import queue
-            free_engines = queue.Queue()
-            for e_ in engines:
-                free_engines.put(e_)
-            pk_f, r_f = {}, {}
-
-            def call_engine(k, th_override=None):
-                wi, pi, loc_ids = jobs[k]
-                ids = waves[wi][loc_ids]
-                pk = pk_f.pop(k).result()
-                t_, p_ = tmpl[pi], pinfo[pi]
-                eng_ = free_engines.get()
-                try:
-                    te = time.perf_counter()
-                    if t_["sgpr"]:
-                        r = eng_.sgpr_fit_predict_batch(D=D, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"],
-                                                        Xs=pk["Xs"], z_off=pk["z_off"], Z=pk["Z"], theta0=theta0[ids],
-                                                        lo=lo[ids], hi=hi[ids], trainable=t_["trainable"],
-                                                        kernel=p_["kernel"], optimiser=p_["optimiser"],
-                                                        max_iter=p_["max_iter"], dtype="f64", **p_["eng_kw"])
-                    else:
-                        r = eng_.fit_predict_batch(D=D, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"],
-                                                   Xs=pk["Xs"], theta0=theta0[ids] if th_override is None else th_override,
-                                                   lo=lo[ids], hi=hi[ids], trainable=t_["trainable"], kernel=p_["kernel"],
-                                                   optimiser=p_["optimiser"], max_iter=p_["max_iter"],
-                                                   dtype=self.dtype, **p_["eng_kw"],
-                                                   **({"full_cov": True} if p_["full_cov"] else {}))
-                    t1 = time.perf_counter()
-                    self.timings["calls"].append((k, len(ids), round(te - t_start, 4), round(t1 - t_start, 4), round(r.kernel_ms * 1e-3, 4)))
-                    return pk, r, t1 - te
-                finally:
-                    free_engines.put(eng_)
-
-            flusher = ThreadPoolExecutor(max_workers=1)
-            with ThreadPoolExecutor(max_workers=max(1, n_eng)) as pack_pool, ThreadPoolExecutor(max_workers=n_eng) as eng_pool:
-                try:
-                    def submit(k):
-                        if k < len(jobs):
-                            pk_f[k] = pack_pool.submit(pack_job, waves[jobs[k][0]][jobs[k][2]], jobs[k][1])
-                            if not self.use_previous:
-                                r_f[k] = eng_pool.submit(call_engine, k)
-                    for k in range(min(len(jobs), n_eng + 1)):
-                        submit(k)
-                    done_waves = 0
-                    for k, (wi, pi, loc_ids) in enumerate(jobs):
-                        while done_waves < wi:                            # waves without a single model tile (stubs, errors only)
-                            if done_waves not in state:
-                                open_wave(done_waves)
-                            close_wave(done_waves)
-                            done_waves += 1
-                        if wi not in state:
-                            open_wave(wi)
-                        fixed, preds, covs = state[wi]
-                        ids = waves[wi][loc_ids]
-                        t_, p_ = tmpl[pi], pinfo[pi]
-                        te = time.perf_counter()
-                        if self.use_previous:
-                            if prev["theta"] is None:
-                                prev["theta"] = t_["theta_default"].copy()
-                            th_call = np.tile(prev["theta"], (len(ids), 1))
-                            for sl, tol in t_["clamp"]:                   # set_parameters(prev), then the constraints' clamp
-                                th_call[:, sl] = clamp_within(th_call[:, sl], t_["lo"][sl], t_["hi"][sl], tol)
-                            pk, r, call_s = call_engine(k, th_call)
-                            for kk in range(len(ids)):                    # expert order; only successful optimisations, no NaN
-                                if p_["optimiser"] != "none" and r.status[kk] == 0 and save_params[ids[kk]] \
-                                        and not np.isnan(r.theta[kk]).any():
-                                    prev["theta"] = 0.95 * prev["theta"] + 0.05 * r.theta[kk]
-                        else:
-                            pk, r, call_s = r_f.pop(k).result()
-                        submit(k + n_eng + 1)
-                        self.timings["engine_s"] += time.perf_counter() - te     # what the main thread waited for this call
-                        self.timings["engine_call_s"] += call_s                  # the calls themselves (they overlap)
-                        self.timings["kernel_s"] += r.kernel_ms * 1e-3
-                        dt = call_s / len(ids)
-                        fixed[loc_ids, :H] = r.theta
-                        fixed[loc_ids, H] = -r.nll if t_["sgpr"] else r.nll      # SGPR: the ELBO (gpflow_models.py:860-862)
-                        fixed[loc_ids, H + 1] = r.status
-                        fixed[loc_ids, H + 2] = r.n_eval
-                        fixed[loc_ids, H + 3] = r.n_iter if getattr(r, "n_iter", None) is not None else np.nan
-                        fixed[loc_ids, H + 4] = dt
-                        fixed[loc_ids, H + 5] = pk["mean"]
-                        if predict:
-                            pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
-                                           np.asarray(r.y_var, dtype=np.float64)], axis=1)
-                            p_off = pk["p_off"]
-                            for kk, j in enumerate(loc_ids):
-                                preds[j] = pr[p_off[kk]:p_off[kk + 1]]
-                            if incremental.get(wi):
-                                piece = self._preds_frame(locs[ids], pk["mean"], pr, pcs, ids, np.ones(len(ids), dtype=bool),
-                                                          pcs.counts[ids].astype(np.int64))
-                                piece_futs.setdefault(wi, []).append(
-                                    flusher.submit(shard_store.write_piece, preds_name, jobs_of_wave[wi].index(k), piece))
-                            if p_["full_cov"]:
-                                fc = np.asarray(r.f_cov, dtype=np.float64)
-                                for kk, j in enumerate(loc_ids):
-                                    P_ = int(p_off[kk + 1] - p_off[kk])
-                                    fcov = fc[r.cov_off[kk]:r.cov_off[kk + 1]].reshape(P_, P_)
-                                    ycov = fcov.copy()                     # y_cov = f*_cov + diag(y_var - f*_var), gpflow_models.py:250-254
-                                    seg = pr[p_off[kk]:p_off[kk + 1]]
-                                    ycov[np.arange(P_), np.arange(P_)] += seg[:, 2] - seg[:, 1]
-                                    covs[j] = np.stack([fcov.reshape(-1), ycov.reshape(-1)], axis=1)
-                        if last_job_of_wave[wi] == k:
-                            close_wave(wi)
-                            done_waves = wi + 1
-                    while done_waves < len(waves):
-                        if done_waves not in state:
-                            open_wave(done_waves)
-                        close_wave(done_waves)
-                        done_waves += 1
-                except BaseException:
-                    # after a fault the flush of the last complete wave is on disk before the fault propagates: a committed
-                    # wave survives whatever happens to the next one
-                    while pending:
-                        pending.pop().result()
-                    flusher.shutdown(wait=True)
-                    raise
-                # the last queued flush goes on while the caller's tables are assembled; run() waits for it before it returns
-                # (the flusher pool's exit below would wait as well: the writer thread is handed over instead)
-                last_flush.extend(pending)
-                flusher_keep.append(flusher)
-            fixed_all = np.concatenate(fixed_rows) if fixed_rows else np.zeros((0, H + 6))
-            preds_all = np.concatenate(pred_rows) if pred_rows else np.zeros((0, 3))
-            cnt = np.where(kind[mine] == 2, n_pred[mine] if predict else 0, 0).astype(np.int64)
-            cov_all = (np.concatenate(cov_rows) if cov_rows else np.zeros((0, 2))) if want_cov else None
-            shard_tables.append(single.get("tables"))
-            return fixed_all, preds_all, cnt, mine, cov_all
-
-        last_flush, flusher_keep, shard_tables = [], [], []
-
-        def finish_flushes():
-            tf = time.perf_counter()
-            while last_flush:
-                last_flush.pop().result()
-            for fl in flusher_keep:
-                fl.shutdown(wait=True)
-            del flusher_keep[:]
-            self.timings["flush_wait_s"] += time.perf_counter() - tf
-
-        try:
-            all_items = np.nonzero(kind != 0)[0]
-            if logical:
-                # every logical shard on this engine, merged by the routine that closes the gather
-                shards = []
-                for r_ in range(world_size):
-                    st_r = ResultStore(store_path, rank=r_)
-                    st_r.drop_uncommitted()
-                    shards.append(run_shard(parts[r_], st_r))
-                fixed_g, preds_g, _ = sharding.assemble_global([sh[:4] for sh in shards], len(ex))
-                cov_g = None
-                if want_cov:
-                    cc2 = [np.where(np.array([pinfo[p]["full_cov"] for p in prof_id[sh[3]]], dtype=bool), sh[2] ** 2, 0) for sh in shards]
-                    cov_g = sharding.assemble_global([(sh[0], sh[4], c2, sh[3]) for sh, c2 in zip(shards, cc2)], len(ex))[1]
-                out = tables_for(all_items, fixed_g[all_items], preds_g, cov_g)
-            else:
-                mine = parts[rank] if world_size > 1 else parts[0]
-                fixed_all, preds_all, cnt, _, cov_all = run_shard(mine, store)
-                out = None
-                if gather and (world_size > 1 or (gather == "always" and d_world == 1 and _dist_initialised())):
-                    # ONE exchange of per-tile results (RCCL over xGMI on the GPU node); tables in expert order on rank 0
-                    # (gather="always": also in a group of ONE rank -- the one-GPU rehearsal of the exchange on RCCL)
-                    dev_id = getattr(self.engine, "device_id", None)
-                    got = sharding.gather_arrays(fixed_all, preds_all, cnt, mine, len(ex), world_size, rank, dev_id)
-                    got_c = None
-                    if want_cov:                                         # the P x P blocks travel the same way (counts P^2)
-                        c2 = np.where(np.array([pinfo[p]["full_cov"] for p in prof_id[mine]], dtype=bool), cnt ** 2, 0)
-                        got_c = sharding.gather_arrays(fixed_all, cov_all, c2, mine, len(ex), world_size, rank, dev_id)
-                    if rank == 0:
-                        fixed_g, preds_g, _ = got
-                        out = tables_for(all_items, fixed_g[all_items], preds_g, got_c[1] if got_c is not None else None)
-                if out is None:
-                    out = shard_tables[-1] if shard_tables and shard_tables[-1] is not None else tables_for(mine, fixed_all, preds_all, cov_all)
-        finally:
-            finish_flushes()                                       # also after a fault: what was committed is on disk
-        self.run_seconds = time.perf_counter() - t_start
-        self.timings["total_s"] = self.run_seconds
+            for f_ in [self._sub_pool().submit(sub, int(bounds[j]), int(bounds[j + 1])) for j in range(nsub)]:
+                f_.result()
+        out = dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
+        if pf.sgpr:
+            # per tile the inducing points HipSGPRModel picks: a seeded subset of the tile's scaled coordinates
+            Zs = [select_inducing_points(X[o_off[j]:o_off[j + 1]], pf.n_inducing, pf.inducing_seed, int(plan.ex[i]))
+                  for j, i in enumerate(ids)]
+            out["z_off"] = np.concatenate([[0], np.cumsum([len(z) for z in Zs])]).astype(np.int64)
+            out["Z"] = np.concatenate(Zs) if Zs else np.zeros((0, D))
         return out
+
+    def _cov_counts(self, plan, items, counts):
+        """Full-covariance rows per item: P^2 where the item's profile wants ``full_cov``, else 0."""
+        return np.where(np.array([plan.profiles[p].full_cov for p in plan.prof_id[items]], dtype=bool), counts ** 2, 0)
+
+    def _merge(self, plan, shards):
+        """(fixed, preds, cov) of all items in expert order from the logical shards, by the routine that closes the gather."""
+        n = len(plan.ex)
+        fixed_g, preds_g, _ = sharding.assemble_global([(s.fixed, s.preds, s.counts, s.items) for s in shards], n)
+        cov_g = sharding.assemble_global([(s.fixed, s.cov, self._cov_counts(plan, s.items, s.counts), s.items)
+                                          for s in shards], n)[1] if plan.want_cov else None
+        return fixed_g, preds_g, cov_g
+
+    def _gather(self, plan, sh, world_size, rank):
+        """ONE exchange of per-tile results (RCCL over xGMI on the GPU node; gather="always": also in a group of ONE rank --
+        the one-GPU rehearsal of the exchange on RCCL): (fixed, preds, cov) of all items on rank 0, None on the others."""
+        n, dev_id = len(plan.ex), getattr(self.engine, "device_id", None)
+        got = sharding.gather_arrays(sh.fixed, sh.preds, sh.counts, sh.items, n, world_size, rank, dev_id)
+        # the P x P blocks travel the same way (counts P^2)
+        got_c = sharding.gather_arrays(sh.fixed, sh.cov, self._cov_counts(plan, sh.items, sh.counts), sh.items, n,
+                                       world_size, rank, dev_id) if plan.want_cov else None
+        return None if rank != 0 else (got[0], got[1], got_c[1] if got_c is not None else None)
 
     def _sub_pool(self):
         if self._pack_pool is None:
-            from concurrent.futures import ThreadPoolExecutor
             self._pack_pool = ThreadPoolExecutor(max_workers=self.pack_threads)
         return self._pack_pool
 
@@ -1523,43 +1305,49 @@ class BatchedLocalExpertOI:
         return [self.engine] + self._extra_engines[:max(0, n - 1)]
 
     # ------------------------------------------------------------------------------------------------------
-    def _preds_frame(self, locs, f_bar, pred_cat, rag, items, tile, cnt):
-        """The ``preds`` table of a run of items (``pred_cat``: the predictions of the tiles among them, back to back)."""
-        cc = self.coords_col
+    def _preds_frame(self, plan, items, f_bar, pred_cat):
+        """The ``preds`` table of the plan's ``items`` (``pred_cat``: the predictions of the tiles among them, back to back)."""
+        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
+        tile = plan.kind[items] == 2
+        cnt = np.where(tile, plan.pcs.counts[items], 0).astype(np.int64)
         tot = int(cnt.sum())
         assert tot == len(pred_cat), (tot, len(pred_cat))
-        raw = rag.take(items[tile]) if tot else np.zeros((0, len(cc)))
+        raw = plan.pcs.take(items[tile]) if tot else np.zeros((0, len(cc)))
         dim0 = np.arange(tot) - np.repeat(np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt)
         pr = {"_dim_0": dim0, "f*": pred_cat[:, 0], "f*_var": pred_cat[:, 1], "y_var": pred_cat[:, 2],
               "f_bar": np.repeat(f_bar, cnt)}
         for ci, c_ in enumerate(cc):
             pr[f"pred_loc_{c_}"] = raw[:, ci]
-        return pd.DataFrame(pr, index=_index_for_repeated(cc, locs, cnt))
+        return pd.DataFrame(pr, index=_index_for_repeated(cc, plan.locs[items], cnt))
 
-    def _tables(self, ex_ids, locs, kind, n_obs, fixed, pred_cat, pcs, save_params, devices, optimise, config_id,
-                table_suffix, cov_cat=None, cov_tiles=None, with_preds=True, models=None, inducing=None):
-        """Reference-layout tables for a run of items (rows of ``fixed`` align with the items, ``pred_cat`` holds the
-        predictions of the tiles among them back to back).  Pure array assembly (GPSat/local_experts.py:691-747)."""
+    def _tables(self, plan, items, fixed, pred_cat, cov_cat=None, with_preds=True):
+        """Reference-layout tables of the plan's ``items`` (rows of ``fixed`` align with them; ``pred_cat`` / ``cov_cat``: their
+        tiles' predictions / covariance blocks back to back), pure array assembly (GPSat/local_experts.py:691-747).
+        ``with_preds=False``: the caller has written the preds rows as pieces and builds that frame itself."""
         cc = self.coords_col
         D, H = len(cc), len(cc) + 2
-        n = len(ex_ids)
-        tile = kind == 2
-        status = fixed[:, H + 1]
-        out = {}
-        out["run_details"] = pd.DataFrame({
-            "_dim_0": np.zeros(n, dtype=np.int64), "num_obs": n_obs.astype(np.int64),
-            "run_time": np.where(tile, fixed[:, H + 4], np.nan), "objective_value": np.where(tile, fixed[:, H], np.nan),
-            "parameters_optimised": np.full(n, bool(optimise)),
-            "optimise_success": tile & bool(optimise) & (status == 0),
-            "model": np.full(n, MODEL_NAME, dtype=object) if models is None else np.array(models, dtype=object),
-            "device": np.array([d if t else "" for d, t in zip(devices, tile)], dtype=object),
-            "config_id": np.full(n, config_id, dtype=np.int64)}, index=_index_for(cc, locs))
-        sp = tile & save_params
+        items = np.asarray(items, dtype=np.int64)
+        n, locs, tile = len(items), plan.locs[items], plan.kind[items] == 2
+        profs = [plan.profiles[p] for p in plan.prof_id[items]]
+        out = {"run_details": pd.DataFrame({
+            "_dim_0": np.zeros(n, dtype=np.int64), "num_obs": plan.n_obs[items].astype(np.int64),
+            "run_time": np.where(tile, fixed[:, H + _SECONDS], np.nan),
+            "objective_value": np.where(tile, fixed[:, H + _NLL], np.nan),
+            "parameters_optimised": np.full(n, bool(plan.optimise)),
+            "optimise_success": tile & bool(plan.optimise) & (fixed[:, H + _STATUS] == 0),
+            "model": np.array([SGPR_MODEL_NAME if pf.sgpr else MODEL_NAME for pf in profs], dtype=object),
+            "device": np.array([pf.device if t else "" for pf, t in zip(profs, tile)], dtype=object),
+            "config_id": np.full(n, plan.config_id, dtype=np.int64)}, index=_index_for(cc, locs))}
+        sp = tile & plan.save_params[items]
         slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
         for pn in self.params_to_store:
             if pn == "inducing_points":
                 # [M, D] per expert: _dim_0 inducing index, _dim_1 coordinate (dict_of_array_to_table of a 2-D array)
-                zs = [(j, z) for j, z in enumerate(inducing or []) if z is not None and sp[j]]
+                zs = []
+                for j, i in enumerate(items):
+                    if sp[j] and profs[j].sgpr:          # the points HipSGPRModel picks for the same rows (scaled coordinates)
+                        Xd = plan.coords_all[plan.idx[plan.off[i]:plan.off[i + 1]]] / profs[j].coords_scale
+                        zs.append((j, select_inducing_points(Xd, profs[j].n_inducing, profs[j].inducing_seed, int(plan.ex[i]))))
                 cnt = np.array([z.size for _, z in zs], dtype=np.int64)
                 out[pn] = pd.DataFrame({
                     "_dim_0": np.concatenate([np.repeat(np.arange(len(z)), z.shape[1]) for _, z in zs]) if zs else np.zeros(0, np.int64),
@@ -1571,26 +1359,238 @@ class BatchedLocalExpertOI:
             vals = fixed[sp, start:start + width].reshape(-1)
             out[pn] = pd.DataFrame({"_dim_0": np.tile(np.arange(width), int(sp.sum())), pn: vals},
                                    index=_index_for_repeated(cc, locs[sp], np.full(int(sp.sum()), width)))
-        if pcs is not None and not with_preds:
-            pass                                                   # the caller has written the rows as pieces and builds the frame itself
-        elif pcs is not None:
-            rag, items = pcs                                       # the run's prediction coordinates and these items' positions
-            items = np.asarray(items, dtype=np.int64)
-            cnt = np.where(tile, rag.counts[items], 0).astype(np.int64)
-            out["preds"] = self._preds_frame(locs, fixed[:, H + 5], pred_cat, rag, items, tile, cnt)
+        if not plan.predict:
+            out["preds"] = pd.DataFrame()
+        elif with_preds:
+            out["preds"] = self._preds_frame(plan, items, fixed[:, H + _OBS_MEAN], pred_cat)
             if cov_cat is not None:
                 # 2-D arrays of the prediction dict -> table "preds_2" with _dim_0, _dim_1 (row-major), local_experts.py:735-745
-                c2 = np.where(cov_tiles, cnt, 0)
-                tot2 = int((c2 * c2).sum())
-                assert tot2 == len(cov_cat), (tot2, len(cov_cat))
-                if tot2:
-                    d0 = np.concatenate([np.repeat(np.arange(c), c) for c in c2 if c])
-                    d1 = np.concatenate([np.tile(np.arange(c), c) for c in c2 if c])
+                cnt = np.where(tile, plan.pcs.counts[items], 0).astype(np.int64)
+                c2 = self._cov_counts(plan, items, cnt)
+                assert int(c2.sum()) == len(cov_cat), (int(c2.sum()), len(cov_cat))
+                blk = cnt[c2 > 0]
+                if len(blk):
+                    d0 = np.concatenate([np.repeat(np.arange(c), c) for c in blk])
+                    d1 = np.concatenate([np.tile(np.arange(c), c) for c in blk])
                     out["preds_2"] = pd.DataFrame({"_dim_0": d0, "_dim_1": d1, "f*_cov": cov_cat[:, 0], "y_cov": cov_cat[:, 1]},
-                                                  index=_index_for(cc, np.repeat(locs, c2 * c2, axis=0)))
-        else:
-            out["preds"] = pd.DataFrame()
-        return {f"{k}{table_suffix}": v for k, v in out.items()}
+                                                  index=_index_for(cc, np.repeat(locs, c2, axis=0)))
+        return {f"{k}{plan.table_suffix}": v for k, v in out.items()}
+
+
+def _cat(rows, width):
+    return np.concatenate(rows) if rows else np.zeros((0, width))
+
+
+class _ShardRunner:
+    """Pass 2 of one shard (one ``run()`` per runner).  A wave of ``wave_n`` items (the flush unit) is cut per model profile
+    into engine calls (jobs) of at most ``chunk_n`` tiles; helper threads pack the next calls' arrays while the GPU works on
+    the current one, one writer thread flushes the waves in order.  Per-tile results do not depend on how tiles are batched
+    (tests/test_gpu_parity.py::test_ragged_batch_tile_indexing_is_bit_exact).  ``run()`` returns the runner holding the
+    result: ``fixed`` rows in the order of ``items``, ``preds`` / ``cov`` rows of its tiles back to back, prediction rows
+    per item (``counts``), the only wave's ``tables`` (else None) and the ``flush`` in flight."""
+
+    def __init__(self, oi: BatchedLocalExpertOI, plan: _Plan, items, store: ResultStore, wave_n, chunk_n, t_start):
+        self.oi, self.plan, self.items, self.store, self.t_start = oi, plan, items, store, t_start
+        self.H = len(oi.coords_col) + 2
+        self.waves = [items[w0:w0 + wave_n] for w0 in range(0, len(items), wave_n)]
+        self.jobs, self.jobs_of_wave = [], {}          # jobs: (wave, profile, positions within the wave, items)
+        for wi, w in enumerate(self.waves):
+            for pi in range(len(plan.profiles)):
+                loc_ids = np.nonzero((plan.kind[w] == 2) & (plan.prof_id[w] == pi))[0]
+                for c0 in range(0, len(loc_ids), chunk_n):
+                    self.jobs_of_wave.setdefault(wi, []).append(len(self.jobs))
+                    self.jobs.append((wi, pi, loc_ids[c0:c0 + chunk_n], w[loc_ids[c0:c0 + chunk_n]]))
+        # The predictions are most of a wave's bytes: when a wave's tiles run as consecutive calls of ONE model profile (the
+        # rows of its preds table are then the calls' rows back to back), every call's rows go to the store as a row piece
+        # as soon as the call returns, and the wave's flush is left with the small tables and the marker.
+        self.incremental = {wi: bool(store.path) and plan.predict and len(ks) <= 64 and len({self.jobs[k][1] for k in ks}) == 1
+                            for wi, ks in self.jobs_of_wave.items()}
+        self.preds_name = f"preds{plan.table_suffix}"
+        self.open, self.closed = {}, 0         # the open waves' (fixed, preds per item, cov rows per item); waves closed
+        self.piece_futs, self.packs = {}, {}   # wave -> writes of its preds pieces; job -> its packed arrays (future)
+        self.rows = ([], [], [])               # fixed, preds, cov of the closed waves
+        self.tables, self.flush = None, []     # the only wave's tables; the flush queued last
+        self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
+        self.counts = np.where(plan.kind[items] == 2, plan.n_pred[items] if plan.predict else 0, 0).astype(np.int64)
+
+    def run(self) -> "_ShardRunner":
+        # Engine calls of consecutive chunks are issued from `n_eng` threads, each with an engine (HIP stream, workspace)
+        # of its own: the second call's kernel is queued on the GPU while the first one runs and its workgroups take
+        # over the CUs the first one's tail leaves idle; packing, the copies and the unpacking of one call overlap the
+        # kernel of the other.  `load_params.previous` makes every call depend on the one before: one engine then.
+        engines = self.oi._engine_pool(1 if self.oi.use_previous else self.oi.engine_workers)
+        for e_ in engines:
+            self.free_engines.put(e_)
+        with ThreadPoolExecutor(max_workers=len(engines)) as packer, ThreadPoolExecutor(max_workers=len(engines)) as callers:
+            try:
+                if self.oi.use_previous:
+                    self._run_previous(packer)
+                else:
+                    self._run_pipelined(packer, callers, len(engines))
+                self._close_waves_to(len(self.waves))
+            except BaseException:
+                # after a fault the flush of the last complete wave is on disk before the fault propagates: a committed
+                # wave survives whatever happens to the next one
+                while self.flush:
+                    self.flush.pop().result()
+                self.flusher.shutdown(wait=True)
+                raise
+        # the last queued flush goes on while the caller's tables are assembled (run() waits for it), then the writer ends
+        self.flusher.shutdown(wait=False)
+        self.fixed, self.preds = _cat(self.rows[0], self.H + _N_RES), _cat(self.rows[1], 3)
+        self.cov = _cat(self.rows[2], 2) if self.plan.want_cov else None
+        return self
+
+    def _pack(self, packer, k):
+        if k < len(self.jobs):
+            self.packs[k] = packer.submit(self.oi._pack_job, self.plan, self.plan.profiles[self.jobs[k][1]], self.jobs[k][3])
+
+    def _run_pipelined(self, packer, callers, n_eng):
+        """Calls from ``n_eng`` engine threads; packs and calls are queued ``n_eng + 1`` jobs ahead."""
+        calls = {}
+
+        def submit(k):
+            if k < len(self.jobs):
+                self._pack(packer, k)
+                calls[k] = callers.submit(self._call, k)
+        for k in range(n_eng + 1):
+            submit(k)
+        for k, job in enumerate(self.jobs):
+            self._close_waves_to(job[0])
+            te = time.perf_counter()
+            pk, r, call_s = calls.pop(k).result()
+            submit(k + n_eng + 1)
+            self._scatter(k, pk, r, call_s, time.perf_counter() - te)
+
+    def _run_previous(self, packer):
+        """``load_params.previous``: serial calls on one engine, packs two jobs ahead; every call starts from the running average
+        of earlier optima (rho = 0.95, local_experts.py:1200-1217), first the first model's defaults (:1053-1054)."""
+        theta = None
+        for k in range(2):
+            self._pack(packer, k)
+        for k, (wi, pi, _, ids) in enumerate(self.jobs):
+            self._close_waves_to(wi)
+            pf = self.plan.profiles[pi]
+            te = time.perf_counter()
+            if theta is None:
+                theta = pf.theta_default.copy()
+            th_call = np.tile(theta, (len(ids), 1))
+            for sl, tol in pf.clamp:                                  # set_parameters(prev), then the constraints' clamp
+                th_call[:, sl] = clamp_within(th_call[:, sl], pf.lo[sl], pf.hi[sl], tol)
+            pk, r, call_s = self._call(k, th_call)
+            for kk in range(len(ids)):                                # expert order; only successful optimisations, no NaN
+                if pf.optimiser != "none" and r.status[kk] == 0 and self.plan.save_params[ids[kk]] \
+                        and not np.isnan(r.theta[kk]).any():
+                    theta = 0.95 * theta + 0.05 * r.theta[kk]
+            self._pack(packer, k + 2)
+            self._scatter(k, pk, r, call_s, time.perf_counter() - te)
+
+    def _call(self, k, th_override=None):
+        """Job k on a free engine: (packed arrays, engine result, seconds of the call)."""
+        p, pf, ids = self.plan, self.plan.profiles[self.jobs[k][1]], self.jobs[k][3]
+        pk = self.packs.pop(k).result()
+        kw = dict(D=self.H - 2, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"], Xs=pk["Xs"], lo=p.lo[ids],
+                  hi=p.hi[ids], trainable=pf.trainable, kernel=pf.kernel, optimiser=pf.optimiser, max_iter=pf.max_iter,
+                  **pf.eng_kw)
+        eng_ = self.free_engines.get()
+        try:
+            te = time.perf_counter()
+            if pf.sgpr:
+                r = eng_.sgpr_fit_predict_batch(z_off=pk["z_off"], Z=pk["Z"], theta0=p.theta0[ids], dtype="f64", **kw)
+            else:
+                r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
+                                           **kw, **({"full_cov": True} if pf.full_cov else {}))
+            t1 = time.perf_counter()
+            self.oi.timings["calls"].append((k, len(ids), round(te - self.t_start, 4), round(t1 - self.t_start, 4),
+                                             round(r.kernel_ms * 1e-3, 4)))
+            return pk, r, t1 - te
+        finally:
+            self.free_engines.put(eng_)
+
+    def _scatter(self, k, pk, r, call_s, waited_s):
+        """Job k's results into its wave: fixed columns, preds slices (and the call's preds piece to the store when the wave's
+        predictions go out as pieces), full-covariance blocks with ``y_cov``.  The wave closes after its last job."""
+        tm = self.oi.timings
+        tm["engine_s"] += waited_s                                 # what the main thread waited for this call
+        tm["engine_call_s"] += call_s                              # the calls themselves (they overlap)
+        tm["kernel_s"] += r.kernel_ms * 1e-3
+        wi, pi, loc_ids, ids = self.jobs[k]
+        p, pf, H = self.plan, self.plan.profiles[pi], self.H
+        fixed, preds, covs = self._wave(wi)
+        fixed[loc_ids, :H] = r.theta
+        fixed[loc_ids, H + _NLL] = -r.nll if pf.sgpr else r.nll        # SGPR: the ELBO (gpflow_models.py:860-862)
+        fixed[loc_ids, H + _STATUS] = r.status
+        fixed[loc_ids, H + _N_EVAL] = r.n_eval
+        fixed[loc_ids, H + _N_ITER] = r.n_iter if getattr(r, "n_iter", None) is not None else np.nan
+        fixed[loc_ids, H + _SECONDS] = call_s / len(ids)
+        fixed[loc_ids, H + _OBS_MEAN] = pk["mean"]
+        if p.predict:
+            pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
+                           np.asarray(r.y_var, dtype=np.float64)], axis=1)
+            p_off = pk["p_off"]
+            for kk, j in enumerate(loc_ids):
+                preds[j] = pr[p_off[kk]:p_off[kk + 1]]
+            if self.incremental.get(wi):
+                piece = self.oi._preds_frame(p, ids, pk["mean"], pr)
+                self.piece_futs.setdefault(wi, []).append(
+                    self.flusher.submit(self.store.write_piece, self.preds_name, self.jobs_of_wave[wi].index(k), piece))
+            if pf.full_cov:
+                fc = np.asarray(r.f_cov, dtype=np.float64)
+                for kk, j in enumerate(loc_ids):
+                    P_ = int(p_off[kk + 1] - p_off[kk])
+                    fcov = fc[r.cov_off[kk]:r.cov_off[kk + 1]].reshape(P_, P_)
+                    ycov = fcov.copy()                             # y_cov = f*_cov + diag(y_var - f*_var), gpflow_models.py:250-254
+                    seg = pr[p_off[kk]:p_off[kk + 1]]
+                    ycov[np.arange(P_), np.arange(P_)] += seg[:, 2] - seg[:, 1]
+                    covs[j] = np.stack([fcov.reshape(-1), ycov.reshape(-1)], axis=1)
+        if self.jobs_of_wave[wi][-1] == k:
+            self._close_waves_to(wi + 1)
+
+    def _wave(self, wi):
+        """The state of wave wi, opened on first use: (fixed, preds per item, covariance rows per item)."""
+        if wi not in self.open:
+            n = len(self.waves[wi])
+            self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
+        return self.open[wi]
+
+    def _close_waves_to(self, w):
+        """Close the waves before ``w`` in order (waves without a single model tile -- stubs, error rows -- included)."""
+        while self.closed < w:
+            self._close_wave(self.closed)
+            self.closed += 1
+
+    def _close_wave(self, wi):
+        oi, p, items = self.oi, self.plan, self.waves[wi]
+        self._wave(wi)                                             # a wave without model tiles opens here
+        fixed, preds, covs = self.open.pop(wi)
+        tt = time.perf_counter()
+        pred_cat, cov_cat = _cat(preds, 3), _cat(covs, 2) if p.want_cov else None
+        pieces = self.piece_futs.pop(wi, [])
+        # the predictions went out as pieces: the wave's flush needs the small tables only, and the wave's preds frame is
+        # built (after the flush is queued) only where it is returned -- the only wave of a run
+        lazy = bool(pieces) and not p.want_cov
+        tables = oi._tables(p, items, fixed, pred_cat, cov_cat, with_preds=not lazy)
+        oi.timings["tables_s"] += time.perf_counter() - tt
+        tf = time.perf_counter()
+        # commit: these experts are done.  The parts are written by the writer thread while the next wave runs (one writer,
+        # waves in order, marker last); a flush that fails surfaces when the next one is queued or at the end
+        if self.flush:
+            self.flush.pop().result()
+
+        def commit(tables=dict(tables), n_pred_rows=len(pred_cat)):
+            for f_ in pieces:                                      # done by now (one writer, in order): a failed piece fails the wave
+                f_.result()
+            self.store.write_wave(tables, prewritten={self.preds_name: n_pred_rows} if pieces else {})
+        self.flush.append(self.flusher.submit(commit))
+        oi.timings["flush_s"] += time.perf_counter() - tf
+        if len(self.waves) == 1:
+            if lazy:
+                tt = time.perf_counter()
+                tables[self.preds_name] = oi._preds_frame(p, items, fixed[:, self.H + _OBS_MEAN], pred_cat)
+                oi.timings["tables_s"] += time.perf_counter() - tt
+            self.tables = tables                                   # the only wave's tables ARE the shard's tables
+        for rows, a in zip(self.rows, (fixed, pred_cat, cov_cat)):
+            rows.append(a)
 
 
 def _dist_initialised():
