@@ -24,7 +24,9 @@ STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5:
 EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
-           "gpsat_max_inducing", "gpsat_select_batch_ex"]
+           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms"]
+# ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
+OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms"]
 
 
 class GpsatOpts(C.Structure):
@@ -47,6 +49,14 @@ class GpsatBatch(C.Structure):
 
 class GpsatSparse(C.Structure):
     _fields_ = [("z_off", C.c_void_p), ("Z", C.c_void_p), ("jitter", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+TRANSFORM_LOG = 1
+
+
+class GpsatMultistart(C.Structure):
+    _fields_ = [("n_starts", C.c_int32), ("transform", C.c_int32), ("starts", C.c_void_p), ("f_start", C.c_void_p),
+                ("reserved", C.c_int32 * 8)]
 
 
 SEL_MAXCRIT = 4
@@ -112,7 +122,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     _check_one_hip_runtime()
     for name in EXPORTS:
-        if not hasattr(lib, name):
+        if name not in OPTIONAL_EXPORTS and not hasattr(lib, name):
             raise LibraryMissing(f"{LIB_PATH} does not export {name}")
     lib.gpsat_version.restype = C.c_int
     lib.gpsat_last_error.restype = C.c_char_p
@@ -142,6 +152,9 @@ def load():
     lib.gpsat_sgpr_fit_predict_batch.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatSparse)]
     lib.gpsat_max_inducing.restype = C.c_int
     lib.gpsat_max_inducing.argtypes = [C.c_int, C.c_int]
+    if hasattr(lib, "gpsat_fit_predict_batch_ms"):
+        lib.gpsat_fit_predict_batch_ms.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMultistart)]
+        lib.gpsat_fit_predict_batch_ms.restype = C.c_int
     lib.gpsat_last_timing.restype = C.c_int
     lib.gpsat_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if lib.gpsat_version() != ABI_VERSION:

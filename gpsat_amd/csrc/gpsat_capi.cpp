@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -100,6 +101,7 @@ struct gpsat_handle {
     } selc;
     // device buffers (grown lazily, owned by the handle)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
+    DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
@@ -187,7 +189,16 @@ int gpsat_last_timing(gpsat_handle* h, double* kernel_ms, double* total_ms) {
     return GPSAT_OK;
 }
 
-int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
+static int fit_predict_impl(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms);
+
+int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_predict_impl(h, b, nullptr); }
+
+int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
+    if (!ms) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_ms: NULL multistart");
+    return fit_predict_impl(h, b, ms);
+}
+
+static int fit_predict_impl(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     h->selc.total = -1;               // any other call on the handle ends a pending two-call selection
     if (b->T < 0) return fail(GPSAT_EINVAL, "T < 0");
@@ -235,11 +246,57 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
             const double v = b->theta0[(size_t)t * H + i];
             if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
         }
+    // ---- multi-start bounded L-BFGS-B (gpsat_fit_predict_batch_ms)
+    const bool ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
+    const int S = ms ? ms->n_starts : 1;
+    std::vector<double> theta0_clipped, starts_clipped;
+    if (ms) {
+        if (S < 1) return fail(GPSAT_EINVAL, "multistart: n_starts must be >= 1");
+        if (ms->transform != GPSAT_TRANSFORM_LOG) return fail(GPSAT_EINVAL, "multistart: unknown transform (GPSAT_TRANSFORM_LOG only)");
+        if (S > 1 && !ms->starts) return fail(GPSAT_EINVAL, "multistart: starts is NULL with n_starts > 1");
+        if (b->optimiser == GPSAT_OPT_ADAM) return fail(GPSAT_EINVAL, "multistart: the optimiser must be L-BFGS-B or none");
+        for (int t = 0; t < T; ++t)
+            for (int i = 0; i < H; ++i) {
+                if (!b->trainable[i]) continue;
+                const double lo = b->lo[(size_t)t * H + i], hi = b->hi[(size_t)t * H + i];
+                if (!(lo > 0.0) || !(hi > 0.0) || !(lo <= hi))
+                    return fail(GPSAT_EINVAL, "multistart: the bounds of a trainable parameter must be positive with lo <= hi (log transform)");
+                if (S > 1 && (!std::isfinite(lo) || !std::isfinite(hi)))
+                    return fail(GPSAT_EINVAL, "multistart: restarts require that all bounds are finite");
+            }
+        if (S > 1)
+            for (size_t e = 0; e < (size_t)T * (S - 1) * H; ++e)
+                if (!(ms->starts[e] > 0.0) || !std::isfinite(ms->starts[e]))
+                    return fail(GPSAT_EINVAL, "multistart: starts must be finite and positive");
+        if (ms_on) {
+            // SciPy clips x0 into the bounds (_minimize_lbfgsb)
+            theta0_clipped.assign(b->theta0, b->theta0 + (size_t)T * H);
+            for (int t = 0; t < T; ++t)
+                for (int i = 0; i < H; ++i)
+                    if (b->trainable[i]) {
+                        double& v = theta0_clipped[(size_t)t * H + i];
+                        v = std::min(std::max(v, b->lo[(size_t)t * H + i]), b->hi[(size_t)t * H + i]);
+                    }
+        }
+    }
+    // the further starts likewise: L-BFGS-B works inside the box only
+    if (ms_on && S > 1) {
+        starts_clipped.assign(ms->starts, ms->starts + (size_t)T * (S - 1) * H);
+        for (int t = 0; t < T; ++t)
+            for (int k = 0; k < S - 1; ++k)
+                for (int i = 0; i < H; ++i)
+                    if (b->trainable[i]) {
+                        double& v = starts_clipped[((size_t)t * (S - 1) + k) * H + i];
+                        v = std::min(std::max(v, b->lo[(size_t)t * H + i]), b->hi[(size_t)t * H + i]);
+                    }
+    }
+    const double* theta0_host = ms_on ? theta0_clipped.data() : b->theta0;
     const int bs = f64 ? 16 : 32;
     const int NBmax = std::max(1, (int)((maxN + bs - 1) / bs));
 
     HIP_TRY(hipSetDevice(h->device));
-    // ---- tile order: largest cost first (N^3), stable so equal tiles keep the reference order
+    // ---- tile order: largest cost first (N^3), stable so equal tiles keep the reference order.  A multi-start batch costs
+    // S times as much per tile, alike for every tile: neither the order nor the slicing decision below changes with S.
     std::vector<int> order(T);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int c) {
@@ -333,7 +390,7 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
     if (want_cov)
         HIP_TRY(hipMemcpyAsync(d_i64 + 2 * (T + 1), b->cov_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     double* d_f64 = static_cast<double*>(h->meta_f64.p);
-    HIP_TRY(hipMemcpyAsync(d_f64, b->theta0, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_f64, theta0_host, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_f64 + (size_t)T * H, b->lo, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_f64 + 2 * (size_t)T * H, b->hi, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
     unsigned char* d_misc = static_cast<unsigned char*>(h->meta_misc.p);
@@ -429,6 +486,25 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
     a.f_cov = want_cov ? reinterpret_cast<float*>(dcov) : nullptr;
     a.PCmax = PCcov;
     a.dump = nullptr; a.dump_stride = 0;
+    if (ms_on) {
+        const size_t n_state = (size_t)T * gpsat::MS_WORDS, n_starts = (size_t)T * (S - 1) * H, n_f = (size_t)T * S;
+        if ((rc = h->ms.reserve((n_state + n_starts + n_f) * sizeof(double)))) return rc;
+        // state, then NaN in f_start for tiles that run no start (no observations)
+        std::vector<double> init(n_state + n_f, 0.0);
+        std::fill(init.begin() + n_state, init.end(), std::numeric_limits<double>::quiet_NaN());
+        for (int t = 0; t < T; ++t) {
+            double* st = init.data() + (size_t)t * gpsat::MS_WORDS;
+            st[1] = std::numeric_limits<double>::infinity();     // best f
+            st[4] = -1.0;                                         // best start: none yet
+            for (int i = 0; i < H; ++i) st[5 + i] = std::log(theta0_host[(size_t)t * H + i]);
+        }
+        double* d_ms = static_cast<double*>(h->ms.p);
+        HIP_TRY(hipMemcpyAsync(d_ms, init.data(), n_state * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (n_starts) HIP_TRY(hipMemcpyAsync(d_ms + n_state, starts_clipped.data(), n_starts * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_ms + n_state + n_starts, init.data() + n_state, n_f * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));          // `init` is local host memory
+        a.ms_S = S; a.ms_state = d_ms; a.ms_starts = d_ms + n_state; a.ms_fout = d_ms + n_state + n_starts;
+    }
     // ---- deferred predictions (fp32 4-wave build, time-sliced, no full covariance): a tile that finishes while others wait
     // leaves its prediction in a snapshot slot for the workgroups that idle at the end of the launch (gpsat_ring.h).  One slot
     // per tile up to a fixed budget; tiles past it predict inline.
@@ -481,6 +557,8 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
     HIP_TRY(hipMemcpyAsync(b->status, a.status, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(b->n_eval, a.n_eval, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (b->n_iter) HIP_TRY(hipMemcpyAsync(b->n_iter, a.n_iter, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (ms_on && ms->f_start)
+        HIP_TRY(hipMemcpyAsync(ms->f_start, a.ms_fout, (size_t)T * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (b->memory == GPSAT_MEM_HOST && sumP > 0) {
         HIP_TRY(hipMemcpyAsync(b->f_mean, dfm, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(b->f_var, dfv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
@@ -525,7 +603,7 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
         if (team_host[g * 64 + 5]) {          // TeamCtl::timeout: a team barrier gave up (never by design) -- run the batch again, one workgroup per tile
             std::fprintf(stderr, "gpsat: a team barrier gave up; re-running the batch with one workgroup per tile\n");
             h->force_solo = true;
-            const int rc2 = gpsat_fit_predict_batch(h, b);
+            const int rc2 = fit_predict_impl(h, b, ms);
             h->force_solo = false;
             return rc2;
         }
@@ -536,7 +614,7 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) {
         if (h->force_unsliced) return fail(GPSAT_EHIP, "tile queue ended with " + std::to_string(unfinished) + " unfinished tiles");
         std::fprintf(stderr, "gpsat: time-sliced tile queue ended with %d unfinished tiles; re-running the batch unsliced\n", unfinished);
         h->force_unsliced = true;
-        const int rc2 = gpsat_fit_predict_batch(h, b);
+        const int rc2 = fit_predict_impl(h, b, ms);
         h->force_unsliced = false;
         return rc2;
     }

@@ -14,6 +14,9 @@ static_assert(32 * GPSAT_PT_MAXNB >= GPSAT_MAX_TILE_OBS, "fp32 sweep flags must 
 namespace gpsat {
 
 // All pointers are DEVICE pointers.
+// per-tile words of multi-start state (gpsat_opt.h ms_end_start)
+constexpr int MS_WORDS = 16;
+
 struct KernelArgs {
     int T, kernel, optimiser, max_iter, max_ls, NBmax;
     double ftol, gtol, adam_lr;
@@ -75,6 +78,11 @@ struct KernelArgs {
     float* pq_snap;               // [pq_slots][pq_stride] snapshots
     size_t pq_stride;             // floats per snapshot slot
     int pq_slots;
+    // multi-start bounded L-BFGS-B in log space (gpsat_fit_predict_batch_ms; ms_S = 0: off), device pointers (gpsat_opt.h)
+    int ms_S = 0;                 // starts per tile
+    const double* ms_starts = nullptr;   // [T][ms_S - 1][H]
+    double* ms_state = nullptr;   // [T][MS_WORDS]
+    double* ms_fout = nullptr;    // [T][ms_S] or nullptr
 };
 
 size_t shared_bytes(int D, int NBmax);

@@ -2038,6 +2038,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     OptCfg o;
     o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
     o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    o.ms_S = A.ms_S; o.ms_starts = A.ms_starts; o.ms_state = A.ms_state; o.ms_fout = A.ms_fout;
 
     const bool sliced = A.seg_cost > 0;
     // deferred predictions: 4-wave build only (the 8-wave build's idle workgroups help running tiles instead)

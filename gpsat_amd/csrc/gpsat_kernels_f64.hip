@@ -1222,6 +1222,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
     OptCfg o;
     o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
     o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    o.ms_S = A.ms_S; o.ms_starts = A.ms_starts; o.ms_state = A.ms_state; o.ms_fout = A.ms_fout;
 
     const bool sliced = A.seg_cost > 0;          // time-sliced tile queue, as in the fp32 kernels (gpsat_kernels.hip)
     for (;;) {
@@ -1421,6 +1422,7 @@ __global__ void __launch_bounds__(NT, 1) gp_team_kernel_f64(const KernelArgs A) 
     OptCfg o;
     o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
     o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    o.ms_S = A.ms_S; o.ms_starts = A.ms_starts; o.ms_state = A.ms_state; o.ms_fout = A.ms_fout;
     __syncthreads();
 
     auto set_tile = [&](int t) {

@@ -66,11 +66,13 @@ struct Shared {
 static __device__ inline double softplus_d(double x) { return log1p(exp(-fabs(x))) + fmax(x, 0.0); }
 
 static __device__ __noinline__ double theta_of_u(const Shared* sh, int i, double u) {
+    if (sh->box[i] == 2) return exp(u);          // log transform (bounded L-BFGS-B in log space, gpsat_fit_predict_batch_ms)
     if (sh->box[i]) return sh->lo[i] + (sh->hi[i] - sh->lo[i]) / (1.0 + exp(-u));
     return softplus_d(u) + sh->shift[i];
 }
 
 static __device__ __noinline__ double u_of_theta(const Shared* sh, int i, double th) {
+    if (sh->box[i] == 2) return log(th);
     if (sh->box[i]) {
         const double lo = sh->lo[i], hi = sh->hi[i];
         double t = (th - lo) / (hi - lo);
@@ -85,6 +87,7 @@ static __device__ __noinline__ double u_of_theta(const Shared* sh, int i, double
 }
 
 static __device__ inline double dtheta_du(const Shared* sh, int i, double th) {
+    if (sh->box[i] == 2) return th;
     if (sh->box[i]) return (th - sh->lo[i]) * (sh->hi[i] - th) / (sh->hi[i] - sh->lo[i]);
     return -expm1(-(th - sh->shift[i]));
 }
@@ -150,7 +153,8 @@ static __device__ inline double cubic_min(double a, double fa, double da, double
 
 // strong-Wolfe line search step (thread 0).  Called after each trial evaluation.
 // Sets sh->ls_done (1 accepted / 2 failed) or the next sh->t.
-static __device__ __noinline__ void ls_step(Shared* sh, int H, int max_ls) {
+// stpmax: largest step that keeps the trial point in the box (bounded L-BFGS-B); >= 1e300 = no limit
+static __device__ __noinline__ void ls_step(Shared* sh, int H, int max_ls, double stpmax = 1e300) {
     const double c1 = 1e-4, c2 = 0.9;
     const double t = sh->t, ft = sh->ft;
     double dphit = 0.0;
@@ -196,11 +200,13 @@ static __device__ __noinline__ void ls_step(Shared* sh, int H, int max_ls) {
             // not bracketed yet (sufficient decrease, still descending): extrapolate as More-Thuente / SciPy's dcsrch do --
             // the cubic through the last two points when its minimiser lies ahead, safeguarded to
             // [t + 1.1 (t - t_prev), t + 4 (t - t_prev)]
+            if (stpmax < 1e300 && t >= stpmax) { sh->ls_done = 1; return; }   // dcsrch: "STP = STPMAX", taken by lnsrlb
             const double tp = sh->t_prev, dt = t - tp;
             double tn = cubic_min(tp, sh->f_prev, sh->dphi_prev, t, ft, dphit);
             const double lo_b = t + 1.1 * dt, hi_b = t + 4.0 * dt;
             if (!(tn > lo_b)) tn = hi_b;          // minimiser behind us or undefined: the cubic has no minimum ahead
             tn = fmin(tn, hi_b);
+            if (stpmax < 1e300) tn = fmin(tn, stpmax);
             sh->t_prev = t; sh->f_prev = ft; sh->dphi_prev = dphit;
             sh->t = tn;
             return;
@@ -234,10 +240,277 @@ enum { ST_CONVERGED = 0, ST_MAXITER = 1, ST_LS_FAILED = 6 };
 
 enum { PH_INIT = 0, PH_LS = 1, PH_ADAM = 2, PH_FINAL = 3, PH_EXIT = 4 };
 
-struct OptCfg { int optimiser, max_iter, max_ls, want_grad_out; double ftol, gtol, adam_lr, noise_rel; };
+struct OptCfg {
+    int optimiser, max_iter, max_ls, want_grad_out; double ftol, gtol, adam_lr, noise_rel;
+    // bounded L-BFGS-B in log space with ms_S starts per tile (gpsat_fit_predict_batch_ms; ms_S = 0: the optimisers above).
+    // Per-tile state lives in device memory, indexed by tile: a suspended tile resumes on any workgroup.
+    int ms_S = 0;
+    const double* ms_starts = nullptr;   // [T][ms_S - 1][H] further starts, constrained space, inside the bounds
+    double* ms_state = nullptr;          // [T][MS_WORDS] (see ms_end_start), preset by the host
+    double* ms_fout = nullptr;           // [T][ms_S] final objective of every start, or nullptr
+};
+
+// per-tile multi-start state, MS_WORDS (gpsat_kernels.h) doubles: [0] index of the running start, [1] best f, [2] its
+// iterations, [3] its status, [4] its start index (-1: none yet), [5 .. 5 + H) its u; the host presets 0, +inf, 0, 0, -1,
+// u of start 0
+// thread 0 reads and writes it with agent-scope word accesses, as the saved state of a suspended tile (memory, not L2)
+static __device__ inline double ms_ld(const double* p) {
+    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT));
+}
+static __device__ inline void ms_st(double* p, double v) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// u-space box of parameter i (log transform); a fixed parameter is pinned at its value
+static __device__ inline void lb_bounds(const Shared* sh, int i, double& l, double& h) {
+    if (!sh->trainable[i]) { l = h = sh->u[i]; return; }
+    l = log(sh->lo[i]);                       // the host refuses lo <= 0; an infinite bound stays infinite
+    h = log(sh->hi[i]);
+    if (!(l == l)) l = -__builtin_inf();      // NaN bound: unbounded on that side
+    if (!(h == h)) h = __builtin_inf();
+}
+
+// projected gradient max-norm (L-BFGS-B projgr) at the accepted point
+static __device__ __noinline__ double lb_projgr(const Shared* sh, int H) {
+    double m = 0.0;
+    for (int i = 0; i < H; ++i) {
+        if (!sh->trainable[i]) continue;
+        double l, h; lb_bounds(sh, i, l, h);
+        double gi = sh->g[i];
+        if (gi < 0.0) gi = fmax(sh->u[i] - h, gi);
+        else gi = fmin(sh->u[i] - l, gi);
+        m = fmax(m, fabs(gi));
+    }
+    return m;
+}
+
+// ---------------------------------------------------------------------------------------------
+// bounded L-BFGS-B (Byrd, Lu, Nocedal, Zhu 1995; SciPy's lbfgsb 3.0) for H <= 6 parameters.  The limited-memory matrix
+// B = theta I - W M W^T is formed densely (H x H) by applying the stored pairs, oldest first, to theta I -- the same
+// matrix as the compact form -- and the generalised Cauchy point and the subspace minimisation work on it directly.
+// ---------------------------------------------------------------------------------------------
+static __device__ __noinline__ void lb_matrix(const Shared* sh, int H, double B[HMAX][HMAX]) {
+    double th = 1.0;
+    const int n = sh->hist_n;
+    if (n > 0) {
+        const int last = (sh->hist_pos - 1 + MH) % MH;
+        double yy = 0.0;
+        for (int i = 0; i < H; ++i) yy += sh->Y[last][i] * sh->Y[last][i];
+        th = yy * sh->rho_[last];                 // y'y / s'y of the newest pair (mainlb: theta = rr / dr)
+    }
+    for (int i = 0; i < H; ++i) for (int j = 0; j < H; ++j) B[i][j] = (i == j) ? th : 0.0;
+    for (int m = n - 1; m >= 0; --m) {
+        const int idx = (sh->hist_pos - 1 - m + 2 * MH) % MH;
+        double Bs[HMAX], sBs = 0.0;
+        for (int i = 0; i < H; ++i) {
+            double a = 0.0;
+            for (int j = 0; j < H; ++j) a += B[i][j] * sh->S[idx][j];
+            Bs[i] = a;
+            sBs += sh->S[idx][i] * a;
+        }
+        if (!(sBs > 0.0)) continue;
+        for (int i = 0; i < H; ++i)
+            for (int j = 0; j < H; ++j)
+                B[i][j] += sh->rho_[idx] * sh->Y[idx][i] * sh->Y[idx][j] - Bs[i] * Bs[j] / sBs;
+    }
+}
+
+// largest step along sh->d from sh->u that stays in the box (lnsrlb's stpmx: 1 in the first iteration; recomputed
+// for every trial of the line search rather than kept in Shared)
+static __device__ __noinline__ double lb_stpmax(const Shared* sh, int H) {
+    if (sh->iter == 0) return 1.0;
+    double stpmx = 1e10;
+    for (int i = 0; i < H; ++i) {
+        double l, h; lb_bounds(sh, i, l, h);
+        const double a1 = sh->d[i];
+        if (a1 < 0.0 && l > -__builtin_inf()) {
+            const double a2 = l - sh->u[i];
+            if (a2 >= 0.0) stpmx = 0.0; else if (a1 * stpmx < a2) stpmx = a2 / a1;
+        } else if (a1 > 0.0 && h < __builtin_inf()) {
+            const double a2 = h - sh->u[i];
+            if (a2 <= 0.0) stpmx = 0.0; else if (a1 * stpmx > a2) stpmx = a2 / a1;
+        }
+    }
+    return stpmx;
+}
+
+// one L-BFGS-B iteration up to the line search: Cauchy point, subspace minimisation, search direction sh->d and the
+// largest feasible step; returns that step (0: no descent direction)
+static __device__ __noinline__ double lb_direction(Shared* sh, int H) {
+    const double eps = 2.220446049250313e-16;
+    double B[HMAX][HMAX];
+    lb_matrix(sh, H, B);
+    double l[HMAX], h[HMAX], x[HMAX], g[HMAX], d[HMAX], tb[HMAX], xc[HMAX];
+    int fix[HMAX];
+    for (int i = 0; i < H; ++i) {
+        lb_bounds(sh, i, l[i], h[i]);
+        x[i] = sh->u[i];
+        g[i] = sh->trainable[i] ? sh->g[i] : 0.0;
+        fix[i] = !sh->trainable[i] || l[i] == h[i];
+        tb[i] = __builtin_inf();
+        if (!fix[i]) {
+            if (g[i] < 0.0 && h[i] < __builtin_inf()) tb[i] = (x[i] - h[i]) / g[i];
+            else if (g[i] > 0.0 && l[i] > -__builtin_inf()) tb[i] = (x[i] - l[i]) / g[i];
+        }
+        if (fix[i] || tb[i] <= 0.0) { d[i] = 0.0; if (!fix[i] && g[i] != 0.0) fix[i] = 1; }
+        else d[i] = -g[i];
+        xc[i] = x[i];
+    }
+    // ---- generalised Cauchy point: piecewise search along the projected steepest-descent path
+    auto quad = [&](double& f1, double& f2) {
+        f1 = 0.0; f2 = 0.0;
+        for (int i = 0; i < H; ++i) {
+            double Bd = 0.0, Bz = 0.0;
+            for (int j = 0; j < H; ++j) { Bd += B[i][j] * d[j]; Bz += B[i][j] * (xc[j] - x[j]); }
+            f1 += d[i] * (g[i] + Bz);
+            f2 += d[i] * Bd;
+        }
+    };
+    double f1, f2;
+    quad(f1, f2);
+    const double f2_org = f2;
+    double told = 0.0;
+    for (;;) {
+        bool moving = false;
+        for (int i = 0; i < H; ++i) moving |= d[i] != 0.0;
+        if (!moving) break;
+        f2 = fmax(eps * f2_org, f2);
+        const double dtm = -f1 / f2;
+        int ib = -1;
+        for (int i = 0; i < H; ++i)
+            if (d[i] != 0.0 && tb[i] < __builtin_inf() && (ib < 0 || tb[i] < tb[ib])) ib = i;
+        if (ib < 0 || dtm < tb[ib] - told) {
+            const double tt = told + fmax(dtm, 0.0);
+            for (int i = 0; i < H; ++i) if (d[i] != 0.0) xc[i] = x[i] + tt * d[i];
+            break;
+        }
+        // the next breakpoint: variable ib reaches its bound and leaves the path
+        told = tb[ib];
+        for (int i = 0; i < H; ++i) if (d[i] != 0.0) xc[i] = x[i] + told * d[i];
+        xc[ib] = d[ib] > 0.0 ? h[ib] : l[ib];
+        d[ib] = 0.0;
+        fix[ib] = 1;
+        quad(f1, f2);
+    }
+    // ---- subspace minimisation over the variables that are free at the Cauchy point (direct primal method)
+    int F[HMAX], nf = 0;
+    for (int i = 0; i < H; ++i) if (!fix[i]) F[nf++] = i;
+    double z[HMAX];
+    for (int i = 0; i < H; ++i) z[i] = xc[i];
+    if (nf > 0 && sh->hist_n > 0) {
+        double A[HMAX][HMAX], r[HMAX];
+        for (int a = 0; a < nf; ++a) {
+            const int i = F[a];
+            double Bz = 0.0;
+            for (int j = 0; j < H; ++j) Bz += B[i][j] * (xc[j] - x[j]);
+            r[a] = -(g[i] + Bz);
+            for (int b = 0; b < nf; ++b) A[a][b] = B[i][F[b]];
+        }
+        bool ok = true;                            // Cholesky of the reduced matrix, then two triangular solves
+        for (int a = 0; a < nf && ok; ++a) {
+            for (int b = 0; b <= a; ++b) {
+                double v = A[a][b];
+                for (int k = 0; k < b; ++k) v -= A[a][k] * A[b][k];
+                if (a == b) { if (!(v > 0.0)) { ok = false; break; } A[a][a] = sqrt(v); }
+                else A[a][b] = v / A[b][b];
+            }
+        }
+        if (ok) {
+            for (int a = 0; a < nf; ++a) { double v = r[a]; for (int k = 0; k < a; ++k) v -= A[a][k] * r[k]; r[a] = v / A[a][a]; }
+            for (int a = nf - 1; a >= 0; --a) { double v = r[a]; for (int k = a + 1; k < nf; ++k) v -= A[k][a] * r[k]; r[a] = v / A[a][a]; }
+            // projection of the Newton point onto the box; if that is not a descent direction, the backtracking step
+            double xp[HMAX], ddp = 0.0;
+            for (int i = 0; i < H; ++i) xp[i] = xc[i];
+            for (int a = 0; a < nf; ++a) { const int i = F[a]; xp[i] = fmin(h[i], fmax(l[i], xc[i] + r[a])); }
+            for (int i = 0; i < H; ++i) ddp += (xp[i] - x[i]) * g[i];
+            if (!(ddp > 0.0)) {
+                for (int i = 0; i < H; ++i) z[i] = xp[i];
+            } else {
+                double alpha = 1.0; int ibd = -1;
+                for (int a = 0; a < nf; ++a) {
+                    const int i = F[a];
+                    const double dk = r[a];
+                    double t1 = alpha;
+                    if (dk < 0.0 && l[i] > -__builtin_inf()) {
+                        const double t2 = l[i] - xc[i];
+                        if (t2 >= 0.0) t1 = 0.0; else if (dk * alpha < t2) t1 = t2 / dk;
+                    } else if (dk > 0.0 && h[i] < __builtin_inf()) {
+                        const double t2 = h[i] - xc[i];
+                        if (t2 <= 0.0) t1 = 0.0; else if (dk * alpha > t2) t1 = t2 / dk;
+                    }
+                    if (t1 < alpha) { alpha = t1; ibd = a; }
+                }
+                for (int a = 0; a < nf; ++a) if (a != ibd || alpha >= 1.0) z[F[a]] = xc[F[a]] + alpha * r[a];
+                if (alpha < 1.0 && ibd >= 0) z[F[ibd]] = r[ibd] > 0.0 ? h[F[ibd]] : l[F[ibd]];
+            }
+        }
+    }
+    // ---- search direction and the largest feasible step (lnsrlb)
+    double dn = 0.0, gd = 0.0;
+    bool boxed = true;
+    for (int i = 0; i < H; ++i) {
+        sh->d[i] = z[i] - x[i];
+        dn += sh->d[i] * sh->d[i];
+        gd += g[i] * sh->d[i];
+        if (sh->trainable[i]) boxed = boxed && l[i] > -__builtin_inf() && h[i] < __builtin_inf();
+    }
+    sh->dphi0 = gd;
+    if (!(gd < 0.0)) return 0.0;
+    const double stpmx = lb_stpmax(sh, H);
+    sh->t = (sh->iter == 0 && !boxed) ? fmin(1.0 / sqrt(dn), stpmx) : 1.0;
+    return stpmx;
+}
+
+// trial point u + t d, kept inside the box (the step 1 lands on the subspace point, bounds exactly)
+static __device__ __noinline__ void lb_set_trial(Shared* sh, int H) {
+    double un[HMAX];
+    for (int i = 0; i < H; ++i) {
+        double l, h; lb_bounds(sh, i, l, h);
+        un[i] = sh->trainable[i] ? fmin(h, fmax(l, sh->u[i] + sh->t * sh->d[i])) : sh->u[i];
+    }
+    set_trial(sh, H, un);
+}
 
 // the accepted point is sh->u; decide whether the factorisation in memory already belongs to it
+// multi-start (o.ms_S > 0): one start's run has ended at sh->u with value sh->f.  Keep it if strictly below the best so
+// far (the first start wins a tie, as sklearn's argmin), then load the next start with an empty history, or after the
+// last one run the final evaluation at the best point (sklearn refits at its best theta).
+static __device__ __noinline__ void ms_end_start(Shared* sh, int H, const OptCfg& o, bool factor_is_current) {
+    const int t = sh->tile & 0x7fffffff;
+    double* st = o.ms_state + (size_t)t * MS_WORDS;
+    const int k = (int)ms_ld(st);
+    const double f = sh->f;
+    if (o.ms_fout) ms_st(o.ms_fout + (size_t)t * o.ms_S + k, f);
+    if (f < ms_ld(st + 1)) {
+        ms_st(st + 1, f); ms_st(st + 2, (double)sh->iter); ms_st(st + 3, (double)sh->status); ms_st(st + 4, (double)k);
+        for (int i = 0; i < H; ++i) ms_st(st + 5 + i, sh->u[i]);
+    }
+    ms_st(st, (double)(k + 1));
+    if (k + 1 < o.ms_S) {
+        const double* th = o.ms_starts + ((size_t)t * (o.ms_S - 1) + k) * H;
+        for (int i = 0; i < H; ++i)
+            if (sh->trainable[i]) { sh->theta[i] = th[i]; sh->u[i] = log(th[i]); }
+        sh->iter = 0; sh->hist_n = 0; sh->hist_pos = 0; sh->last_dec = 1e300; sh->fail = 0; sh->status = 1;
+        sh->want_grad = 1;
+        sh->phase = PH_INIT;
+        return;
+    }
+    const int best = (int)ms_ld(st + 4);
+    sh->iter = (int)ms_ld(st + 2);
+    sh->status = best < 0 ? 2 : (int)ms_ld(st + 3);        // every start failed at its first evaluation: NOT_PD
+    sh->f = ms_ld(st + 1);
+    if (best == k && factor_is_current && !sh->fail) { sh->n_eval_opt = sh->n_eval; sh->phase = PH_EXIT; return; }
+    for (int i = 0; i < H; ++i) sh->u[i] = ms_ld(st + 5 + i);
+    set_trial(sh, H, sh->u);
+    sh->want_grad = o.want_grad_out;
+    sh->n_eval_opt = sh->n_eval + 1;              // n_eval counts every start and the final evaluation
+    sh->phase = PH_FINAL;
+}
+
 static __device__ __noinline__ void opt_finish(Shared* sh, int H, const OptCfg& o, bool factor_is_current) {
+    if (o.ms_S > 0) { ms_end_start(sh, H, o, factor_is_current); return; }
     sh->n_eval_opt = sh->n_eval;
     if (factor_is_current && !sh->fail) { sh->phase = PH_EXIT; return; }
     set_trial(sh, H, sh->u);
@@ -258,6 +531,23 @@ static __device__ __noinline__ void opt_start_iteration(Shared* sh, int H, const
         }
         set_trial(sh, H, un);
         sh->phase = PH_ADAM;
+        return;
+    }
+    if (o.ms_S > 0) {
+        // no descent direction inside the box (lnsrlb info = -4) is handled as a failed line search: refresh the memory
+        // once, with an empty history give up
+        bool descent = lb_direction(sh, H) > 0.0;
+        if (!descent && sh->hist_n > 0) { sh->hist_n = 0; descent = lb_direction(sh, H) > 0.0; }
+        if (!descent) {
+            sh->status = ST_LS_FAILED;
+            opt_finish(sh, H, o, true);
+            return;
+        }
+        sh->ls_phase = 0; sh->ls_iter = 0; sh->ls_done = 0;
+        sh->t_prev = 0.0; sh->f_prev = sh->f; sh->dphi_prev = sh->dphi0;
+        sh->t_best = 0.0; sh->f_best = sh->f;
+        lb_set_trial(sh, H);
+        sh->phase = PH_LS;
         return;
     }
     lbfgs_direction(sh, H);
@@ -283,6 +573,19 @@ static __device__ __noinline__ void opt_start_iteration(Shared* sh, int H, const
 static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg& o) {
     switch (sh->phase) {
         case PH_INIT: {
+            if (o.ms_S > 0) {
+                // log transform at the evaluated point (the host clipped it into the bounds, as SciPy clips x0)
+                for (int i = 0; i < H; ++i) { sh->box[i] = 2; sh->u[i] = log(sh->theta[i]); sh->ut[i] = sh->u[i]; }
+                fetch_trial(sh, H);
+                sh->f = sh->ft;
+                for (int i = 0; i < H; ++i) sh->g[i] = sh->gt[i];
+                // a start whose first evaluation fails has f = +inf (sklearn's LML is -inf on LinAlgError): skipped
+                if (sh->fail) { sh->f = __builtin_inf(); sh->status = 2; ms_end_start(sh, H, o, false); return; }
+                sh->status = 1;
+                if (o.gtol > 0.0 && lb_projgr(sh, H) <= o.gtol) { sh->status = 0; opt_finish(sh, H, o, true); return; }
+                opt_start_iteration(sh, H, o);
+                return;
+            }
             set_trial(sh, H, sh->u);
             fetch_trial(sh, H);
             sh->f = sh->ft;
@@ -310,7 +613,8 @@ static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg&
         }
         case PH_LS: {
             fetch_trial(sh, H);
-            ls_step(sh, H, o.max_ls);
+            ls_step(sh, H, o.max_ls, o.ms_S > 0 ? lb_stpmax(sh, H) : 1e300);
+            if (!sh->ls_done && o.ms_S > 0) { lb_set_trial(sh, H); return; }
             if (!sh->ls_done) {
                 double un[HMAX];
                 for (int i = 0; i < H; ++i) un[i] = sh->u[i] + sh->t * sh->d[i];
@@ -328,7 +632,11 @@ static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg&
                     sy += sv[i] * yvv[i];
                     yy += yvv[i] * yvv[i];
                 }
-                if (sy > 1e-10 * yy && yy > 0.0) {
+                // L-BFGS-B (mainlb) skips the update when s'y <= eps (-g's); the unbounded driver when s'y <= 1e-10 y'y
+                double gs = 0.0;
+                for (int i = 0; i < H; ++i) gs -= sh->g[i] * sv[i];
+                const bool keep = o.ms_S > 0 ? (sy > 2.220446049250313e-16 * gs && yy > 0.0) : (sy > 1e-10 * yy && yy > 0.0);
+                if (keep) {
                     const int pos = sh->hist_pos;
                     for (int i = 0; i < H; ++i) { sh->S[pos][i] = sv[i]; sh->Y[pos][i] = yvv[i]; }
                     sh->rho_[pos] = 1.0 / sy;
@@ -341,6 +649,7 @@ static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg&
                 for (int i = 0; i < H; ++i) { sh->u[i] = sh->ut[i]; sh->g[i] = sh->gt[i]; gmax = fmax(gmax, fabs(sh->gt[i])); }
                 sh->iter += 1;
                 const double den = fmax(fmax(fabs(fold), fabs(fnew)), 1.0);
+                if (o.ms_S > 0) gmax = lb_projgr(sh, H);          // L-BFGS-B: the projected gradient
                 if ((fold - fnew) <= o.ftol * den || gmax <= o.gtol) { sh->status = 0; opt_finish(sh, H, o, current); return; }
                 if (sh->iter >= o.max_iter) { sh->status = 1; opt_finish(sh, H, o, current); return; }
                 opt_start_iteration(sh, H, o);
@@ -354,7 +663,8 @@ static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg&
             //    steepest descent at the accepted point (the restart is not an iteration); with an empty history give up
             //    -- SciPy reports ABNORMAL_TERMINATION_IN_LNSRCH, success=False, hence a status of its own.  The best
             //    sufficient-decrease point seen by the failed search (if any) is kept rather than thrown away.
-            if (sh->iter > 0 && o.ftol >= 0.0 && sh->last_dec <= o.noise_rel * fmax(fabs(sh->f), 1.0)) {
+            //  * Bounded L-BFGS-B (o.ms_S > 0) keeps SciPy's semantics only: no noise-floor convergence.
+            if (o.ms_S == 0 && sh->iter > 0 && o.ftol >= 0.0 && sh->last_dec <= o.noise_rel * fmax(fabs(sh->f), 1.0)) {
                 sh->status = ST_CONVERGED;
                 opt_finish(sh, H, o, false);
                 return;

@@ -31,6 +31,7 @@ class BatchResult:
     f_cov: object = None   # full_cov: flat [sum P_t^2] (numpy / torch as f_mean); tile t = f_cov[cov_off[t]:cov_off[t+1]].reshape(P_t, P_t)
     cov_off: np.ndarray | None = None
     n_iter: np.ndarray | None = None   # [T] optimiser iterations completed (scipy nit)
+    f_start: np.ndarray | None = None  # [T, S] multi-start: final objective of every start (+inf: its first evaluation failed)
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -85,7 +86,7 @@ class Engine:
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
-                          out=None, dtype="f32", full_cov=False) -> BatchResult:
+                          out=None, dtype="f32", full_cov=False, n_starts=None, starts=None) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -93,6 +94,9 @@ class Engine:
         kernels); host arrays are cast, device tensors must already have that dtype.  Offsets / theta0 / bounds
         are always host numpy (fp64).  ``full_cov``: also return the P_t x P_t posterior covariance of every tile
         (predict(full_cov=True), gpflow_models.py:245-263).
+        ``n_starts`` (an int): multi-start bounded L-BFGS-B in log space (gpsat_fit_predict_batch_ms): theta0 and the
+        ``starts`` [T, n_starts - 1, H] (constrained space) per tile, the best final objective wins; ``f_start`` of the
+        result holds every start's final objective.  None: the optimisers of gpsat_fit_predict_batch.
         """
         obs_off = np.ascontiguousarray(obs_off, dtype=np.int64)
         pred_off = np.ascontiguousarray(pred_off, dtype=np.int64)
@@ -176,15 +180,29 @@ class Engine:
         b.status, b.n_eval, b.n_iter = _ptr(status), _ptr(n_eval), _ptr(n_iter)
         b.f_mean, b.f_var, b.y_var = pfm, pfv, pyv
         b.cov_off, b.f_cov = (_ptr(cov_off), pfc) if full_cov else (None, None)
-        rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
+        f_start = None
+        if n_starts is not None:
+            if not hasattr(self._lib, "gpsat_fit_predict_batch_ms"):
+                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_ms (multi-start L-BFGS-B)")
+            ms = L.GpsatMultistart()
+            ms.n_starts, ms.transform = int(n_starts), L.TRANSFORM_LOG
+            st = None
+            if starts is not None and int(n_starts) > 1:
+                st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(T, max(int(n_starts) - 1, 0), H))
+            f_start = np.full((T, max(int(n_starts), 1)), np.nan)
+            ms.starts, ms.f_start = _ptr(st), _ptr(f_start)
+            rc = self._lib.gpsat_fit_predict_batch_ms(self._h, C.byref(b), C.byref(ms))
+        else:
+            rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
         if rc != 0:
-            raise GpsatError(f"gpsat_fit_predict_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+            name = "gpsat_fit_predict_batch_ms" if n_starts is not None else "gpsat_fit_predict_batch"
+            raise GpsatError(f"{name} failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         km, tm = C.c_double(), C.c_double()
         self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
         if device_mode:
             fm, fv, yv = fm[:sumP], fv[:sumP], yv[:sumP]
         return BatchResult(theta=theta, nll=nll, status=status, n_eval=n_eval, n_iter=n_iter, f_mean=fm, f_var=fv, y_var=yv,
-                           grad=grad, kernel_ms=km.value, total_ms=tm.value,
+                           grad=grad, kernel_ms=km.value, total_ms=tm.value, f_start=f_start,
                            f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
 
     def sgpr_fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, z_off, Z, theta0, lo=None, hi=None,

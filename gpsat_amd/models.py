@@ -433,11 +433,175 @@ class HipSGPRModel(HipGPRModel):
 SGPR_MODEL_NAMES = ("HipSGPRModel", "GPflowSGPRModel")
 
 
+SKLEARN_MODEL_NAMES = ("HipSklearnGPRModel", "sklearnGPRModel")
+SKLEARN_NU = {0.5: "Matern12", 1.5: "Matern32", 2.5: "Matern52", np.inf: "RBF"}
+SKLEARN_BOUNDS = (1e-5, 1e5)              # sklearn's default hyperparameter bounds (length_scale, constant_value)
+
+
+def sklearn_restart_starts(rng, log_lo, log_hi, n_restarts):
+    """The further starts of sklearn's GaussianProcessRegressor.fit: ``n_restarts`` draws of
+    ``rng.uniform(log_lo, log_hi)`` over the trainable hyperparameters (sklearn's order), returned in log space [n, k]."""
+    return np.array([rng.uniform(log_lo, log_hi) for _ in range(int(n_restarts))]).reshape(int(n_restarts), len(log_lo))
+
+
+class HipSklearnGPRModel(HipGPRModel):
+    """Exact GP regression for one expert tile with the interface and behaviour of the reference's sklearnGPRModel
+    (GPSat/models/sklearn_models.py): sklearn's GaussianProcessRegressor(kernel * ConstantKernel(sqrt(kernel_variance)),
+    alpha=likelihood_variance, n_restarts_optimizer) fitted by multi-start bounded L-BFGS-B in log space on the GPU
+    (gpsat_fit_predict_batch_ms).  fp64 by default, as sklearn."""
+
+    def __init__(self, data=None, coords_col=None, obs_col=None, coords=None, obs=None,
+                 coords_scale=None, obs_scale=None, obs_mean=None, verbose=True, *,
+                 kernel="Matern", kernel_kwargs=None, mean_value=None, kernel_variance=1., likelihood_variance=None,
+                 param_bounds=None, n_restarts_optimizer=2, random_state=None, engine=None, dtype="f64", **kwargs):
+        kk = dict(kernel_kwargs or {})
+        if kernel == "Matern":
+            nu = float(kk.pop("nu", 1.5))
+            if nu not in SKLEARN_NU:
+                raise NotImplementedError(f"Matern nu={nu}: this backend builds nu in {sorted(SKLEARN_NU)}")
+            dev_kernel = SKLEARN_NU[nu]
+        elif kernel == "RBF":
+            dev_kernel = "RBF"
+        else:
+            raise NotImplementedError(f"kernel {kernel!r}: the sklearn model builds 'Matern' and 'RBF'")
+        if mean_value is not None:
+            raise NotImplementedError("mean_value (a trainable ConstantKernel summand) is not built")
+        ls = kk.pop("length_scale", None)
+        ls_bounds = kk.pop("length_scale_bounds", SKLEARN_BOUNDS)
+        if kk:
+            raise NotImplementedError(f"kernel_kwargs {sorted(kk)} are not built")
+        super().__init__(data=data, coords_col=coords_col, obs_col=obs_col, coords=coords, obs=obs,
+                         coords_scale=coords_scale, obs_scale=obs_scale, obs_mean=obs_mean, verbose=verbose,
+                         kernel=dev_kernel, engine=engine, dtype=dtype)
+        D = self.D
+        if ls is None:
+            ls = np.ones(D)
+        ls = np.asarray(ls, dtype=np.float64)
+        if ls.ndim != 1 or len(ls) != D:
+            raise NotImplementedError("an isotropic (scalar) length_scale is not built: give one per dimension")
+        # amplitude quirk of the reference: kernel * ConstantKernel(sqrt(kernel_variance)) -- the device sees sf2 = c
+        self._has_constant = kernel_variance is not None
+        c = float(np.sqrt(kernel_variance)) if self._has_constant else 1.0
+        alpha = 1.0 if likelihood_variance is None else float(likelihood_variance)
+        self._theta = np.concatenate([ls, [c], [alpha]])
+        lsb = np.broadcast_to(np.asarray(ls_bounds, dtype=np.float64), (D, 2)) if np.ndim(ls_bounds) == 2 else \
+            np.broadcast_to(np.asarray(ls_bounds, dtype=np.float64), (2,))[None, :].repeat(D, 0)
+        self._lo = np.concatenate([lsb[:, 0], [SKLEARN_BOUNDS[0]], [np.nan]])
+        self._hi = np.concatenate([lsb[:, 1], [SKLEARN_BOUNDS[1]], [np.nan]])
+        self._trainable = np.array([True] * D + [self._has_constant, False])
+        if param_bounds is not None:
+            # the reference assigns to a Hyperparameter namedtuple field
+            raise AttributeError("can't set attribute")
+        self.n_restarts_optimizer = int(n_restarts_optimizer)
+        self.random_state = random_state
+        self._lml = None                   # +LML of the last fit (sklearn's log_marginal_likelihood_value_)
+        self.f_start = None
+
+    # -- getters / setters (sklearn_models.py:186-240)
+    def get_kernel_variance(self) -> float:
+        return float(self._theta[self.D]) ** 2 if self._has_constant else 1.0
+
+    def set_kernel_variance(self, kernel_variance):
+        if self._has_constant:
+            self._theta[self.D] = float(np.sqrt(np.asarray(kernel_variance, dtype=np.float64).reshape(-1)[0]))
+
+    def set_likelihood_variance(self, likelihood_variance):
+        self._theta[self.D + 1] = float(np.asarray(likelihood_variance, dtype=np.float64).reshape(-1)[0])
+
+    def set_lengthscales(self, lengthscales):
+        v = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
+        assert len(v) == self.D, f"lengthscales must have length {self.D}"
+        self._theta[:self.D] = v
+
+    # -- constraints (sklearn_models.py:282-360): only the length-scale bounds reach the kernel
+    def set_lengthscales_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
+        lo = np.atleast_1d(np.asarray(low, dtype=np.float64))
+        hi = np.atleast_1d(np.asarray(high, dtype=np.float64))
+        assert len(lo) == self.D, "len of low constraint does not match size of parameter lengthscales"
+        assert len(hi) == self.D, "len of high constraint does not match size of parameter lengthscales"
+        assert np.all(lo <= hi), "all values in high constraint must be greater than low"
+        if scale:
+            div = self.coords_scale[0, :] if scale_magnitude is None else scale_magnitude
+            lo, hi = lo / div, hi / div
+        # move_within_tol edits a copy in the reference: the current values stay
+        self._lo[:self.D], self._hi[:self.D] = lo, hi
+
+    def set_kernel_variance_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
+        """No effect, as in the reference: it sets an attribute of the Product kernel that sklearn never reads."""
+
+    def set_likelihood_variance_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
+        """No effect: alpha is fixed, never trained."""
+
+    # -- fit / objective / predict
+    def restart_starts(self, rng=None):
+        """The n_restarts_optimizer further starts, constrained space [n, D + 2], drawn as sklearn draws them from
+        ``check_random_state(random_state)`` (or ``rng``)."""
+        from sklearn.utils import check_random_state
+        rng = check_random_state(self.random_state) if rng is None else rng
+        tr = self._trainable
+        log_lo, log_hi = np.log(self._lo[tr]), np.log(self._hi[tr])
+        draws = sklearn_restart_starts(rng, log_lo, log_hi, self.n_restarts_optimizer)
+        out = np.repeat(self._theta[None, :], self.n_restarts_optimizer, axis=0)
+        out[:, tr] = np.exp(draws)
+        return out
+
+    def _run(self, *, optimiser, max_iter=0, pred_coords=None, starts=None, **opt_kwargs):
+        N, D = self.coords.shape
+        P = 0 if pred_coords is None else len(pred_coords)
+        Xs = np.zeros((0, D)) if pred_coords is None else pred_coords
+        S = 1 if starts is None else 1 + len(starts)
+        return self._engine.fit_predict_batch(
+            dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0],
+            pred_off=np.array([0, P]), Xs=Xs, theta0=self._theta[None, :], lo=self._lo[None, :],
+            hi=self._hi[None, :], trainable=self._trainable, kernel=self.kernel, optimiser=optimiser,
+            max_iter=max_iter, n_starts=S, starts=starts, **opt_kwargs)
+
+    def optimise_parameters(self, opt=None, **kwargs):
+        """sklearn's fit: L-BFGS-B from the current parameters and from n_restarts_optimizer random starts, the best
+        optimum kept.  ``max_iter`` and ``fixed_params`` are ignored, as by the reference.  True unless the fit failed."""
+        if self.n_restarts_optimizer > 0 and not (np.isfinite(self._lo[self._trainable]).all()
+                                                  and np.isfinite(self._hi[self._trainable]).all()):
+            raise ValueError("Multiple optimizer restarts (n_restarts_optimizer>0) requires that all bounds are finite.")
+        starts = self.restart_starts() if self.n_restarts_optimizer > 0 else None
+        # SciPy's L-BFGS-B defaults: maxiter 15000, maxls 20, ftol = factr * eps, pgtol 1e-5
+        r = self._run(optimiser="lbfgs", max_iter=15000, starts=starts)
+        self.status = int(r.status[0])
+        self.n_eval = int(r.n_eval[0])
+        self.f_start = r.f_start[0].copy()
+        if self.status in (2, 3):
+            print("*" * 10)
+            print("optimization failed!")
+            return False
+        self._theta = r.theta[0].copy()
+        self._lml = -float(r.nll[0])
+        return True
+
+    def get_objective_function_value(self):
+        """+LML after a fit (sklearn's log_marginal_likelihood_value_); without one -LML at the current parameters
+        (the reference's _fake_fit branch)."""
+        if self._lml is not None:
+            return self._lml
+        r = self._run(optimiser="none")
+        return float(r.nll[0])
+
+    def predict(self, coords, full_cov=False, apply_scale=True) -> Dict[str, np.ndarray]:
+        """f* and the latent variance f*_var (clipped at 0) as sklearn returns them: no y_var, no f_bar, no rescale by
+        obs_scale (sklearn_models.py:116-178); ``full_cov`` adds f*_cov."""
+        out = super().predict(coords, full_cov=full_cov, apply_scale=apply_scale)
+        res = {"f*": np.atleast_1d(out["f*"]), "f*_var": np.maximum(np.atleast_1d(out["f*_var"]), 0.0)}
+        if full_cov:
+            res["f*_cov"] = out["f*_cov"]
+        return res
+
+
 def get_model(name):
     """Registry hook with the reference's semantics (GPSat/models/__init__.py:3-28): the exact-GP names resolve to
-    HipGPRModel, the sparse ones to HipSGPRModel; anything else is NotImplementedError."""
+    HipGPRModel, the sparse ones to HipSGPRModel, the sklearn ones to HipSklearnGPRModel; anything else is
+    NotImplementedError."""
     if name in ("HipGPRModel", "GPflowGPRModel"):
         return HipGPRModel
     if name in SGPR_MODEL_NAMES:
         return HipSGPRModel
+    if name in SKLEARN_MODEL_NAMES:
+        return HipSklearnGPRModel
     raise NotImplementedError(f"model with name: '{name}' is not implemented")

@@ -145,6 +145,37 @@ typedef struct gpsat_batch {
     int32_t *n_iter;           /* [T] host, optional (may be NULL): optimiser iterations completed (scipy nit)  */
 } gpsat_batch;
 
+/*
+ * Multi-start bounded L-BFGS-B in log space (sklearn's GaussianProcessRegressor.fit with n_restarts_optimizer,
+ * GPSat/models/sklearn_models.py): the extension of gpsat_fit_predict_batch_ms.  Callers detect it by the presence of
+ * that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ *
+ * Every trainable parameter is optimised over u = log(theta) with SciPy's L-BFGS-B and its box constraints
+ * [log lo, log hi] (generalised Cauchy point, subspace minimisation, feasible line search), from theta0 -- clipped into
+ * the bounds, as SciPy clips x0 -- and from the S - 1 further starts, in that order.  A start whose first evaluation is
+ * not positive definite has the objective +inf and is skipped.  The start with the lowest final objective wins (the
+ * first one on a tie); the tile's factorisation, nll, grad and predictions are those at its parameters.
+ * Outputs: n_eval counts the evaluations of every start plus the final one; n_iter and status are the winning start's;
+ * status is GPSAT_STATUS_NOT_PD only when the factorisation at the winning parameters fails (or every start failed).
+ * With optimiser GPSAT_OPT_NONE the batch is evaluated at theta0 as by gpsat_fit_predict_batch and f_start is not
+ * written.  GPSAT_OPT_ADAM is refused.
+ */
+#define GPSAT_TRANSFORM_LOG 1
+typedef struct gpsat_multistart {
+    int32_t       n_starts;   /* S >= 1: theta0 and S - 1 further starts per tile                                  */
+    int32_t       transform;  /* GPSAT_TRANSFORM_LOG                                                                */
+    const double *starts;     /* [T*(S-1)*H] host, constrained space, clipped into the bounds like theta0; may be   */
+                              /*   NULL if S = 1                                                                    */
+    double       *f_start;    /* [T*S] host, optional (may be NULL): final objective (-LML) of every start, +inf when */
+                              /*   its first evaluation failed, NaN for a tile without observations                 */
+    int32_t       reserved[8];
+} gpsat_multistart;
+
+/* as gpsat_fit_predict_batch, with the multi-start extension above.  GPSAT_EINVAL (with a message) for S < 1, an
+ * unknown transform, NULL starts with S > 1, a bound <= 0 (or NaN) on a trainable parameter, and non-finite bounds
+ * with S > 1 (sklearn: "requires that all bounds are finite"). */
+int gpsat_fit_predict_batch_ms(gpsat_handle *h, const gpsat_batch *b, const gpsat_multistart *ms);
+
 /* library / ABI version (GPSAT_ABI_VERSION) */
 int gpsat_version(void);
 
