@@ -5,8 +5,9 @@ Only what the hot path needs lives here:
   _lib.py     ctypes binding
   engine.py   packed-ragged batch API (fit + objective + predict for thousands of tiles per launch)
   models.py   HipGPRModel: per-tile class with the reference's BaseGPRModel interface
+  dataprep.py DataPrep.bin_data / bin_data_by: raw observations -> binned table (gpsat_bin_batch)
 """
-__all__ = ["Engine", "default_engine", "HipGPRModel", "get_model"]
+__all__ = ["Engine", "default_engine", "HipGPRModel", "get_model", "DataPrep"]
 
 
 def __getattr__(name):
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name in ("HipGPRModel", "get_model"):
         from . import models
         return getattr(models, name)
+    if name == "DataPrep":
+        from . import dataprep
+        return dataprep.DataPrep
     raise AttributeError(name)

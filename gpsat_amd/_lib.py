@@ -24,9 +24,9 @@ STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5:
 EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
-           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms"]
+           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
-OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms"]
+OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch"]
 
 
 class GpsatOpts(C.Structure):
@@ -67,6 +67,10 @@ class GpsatSelectSpec(C.Structure):
     _fields_ = [("n_crit", C.c_int32), ("kind", C.c_int32 * SEL_MAXCRIT), ("comp", C.c_int32 * SEL_MAXCRIT),
                 ("ncols", C.c_int32 * SEL_MAXCRIT), ("cols", (C.c_int32 * 3) * SEL_MAXCRIT),
                 ("val", C.c_double * SEL_MAXCRIT)]
+
+
+# statistics of gpsat_bin_batch (GPSAT_BIN_*), in the order of their bits = the order of the output rows
+BIN_STATS = {"count": 1, "sum": 2, "mean": 4, "std": 8, "min": 16, "max": 32, "median": 64}
 
 
 class LibraryMissing(ImportError):
@@ -155,6 +159,11 @@ def load():
     if hasattr(lib, "gpsat_fit_predict_batch_ms"):
         lib.gpsat_fit_predict_batch_ms.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMultistart)]
         lib.gpsat_fit_predict_batch_ms.restype = C.c_int
+    if hasattr(lib, "gpsat_bin_batch"):
+        lib.gpsat_bin_batch.restype = C.c_int
+        lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_double, C.c_uint32,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gpsat_last_timing.restype = C.c_int
     lib.gpsat_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if lib.gpsat_version() != ABI_VERSION:

@@ -103,6 +103,7 @@ struct gpsat_handle {
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
+    DevBuf bin_in, bin_keys, bin_rows, bin_vals, bin_runs, bin_tmp, bin_out;     // gpsat_bin_batch
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
@@ -176,6 +177,8 @@ int gpsat_destroy(gpsat_handle* h) {
     h->out_i32.release(); h->bulk_in.release(); h->bulk_out.release(); h->ws.release(); h->prof.release(); h->ring.release(); h->state.release(); h->coop.release(); h->pq.release();
     h->sel_pts.release(); h->sel_refs.release(); h->sel_cnt.release(); h->sel_idx.release(); h->sel_box.release();
     h->sel_perm.release(); h->sel_keys.release(); h->sel_tmp.release(); h->sel_ord.release(); h->sel_bnd.release();
+    h->bin_in.release(); h->bin_keys.release(); h->bin_rows.release(); h->bin_vals.release(); h->bin_runs.release();
+    h->bin_tmp.release(); h->bin_out.release();
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -998,6 +1001,130 @@ int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t 
         h->selc.fp = sel_fingerprint(points, (long long)M * C, refs, (long long)T * C, bounds, nB);
         h->selc.off.assign(off, off + T + 1);
     }
+    return GPSAT_OK;
+}
+
+int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y, const double* v, const int32_t* gid,
+                    int32_t G, int32_t nx, const double* ex, double x_hi, int32_t ny, const double* ey, double y_hi,
+                    uint32_t stats, int64_t capacity, int64_t* n_cells, int64_t* keys, double* out) {
+    if (!h || !n_cells) return fail(GPSAT_EINVAL, "gpsat_bin_batch: NULL handle or n_cells");
+    *n_cells = 0;
+    if (R < 0 || G < 0 || capacity < 0) return fail(GPSAT_EINVAL, "gpsat_bin_batch: bad sizes");
+    if (R > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_bin_batch: more than 2^31-1 rows in one call");
+    const uint32_t all = GPSAT_BIN_COUNT | GPSAT_BIN_SUM | GPSAT_BIN_MEAN | GPSAT_BIN_STD | GPSAT_BIN_MIN | GPSAT_BIN_MAX | GPSAT_BIN_MEDIAN;
+    if (stats == 0 || (stats & ~all)) return fail(GPSAT_EINVAL, "gpsat_bin_batch: stats must be a non-empty OR of GPSAT_BIN_*");
+    const bool two_d = y != nullptr;
+    auto check_axis = [](const char* name, int n, const double* e, double hi) -> std::string {
+        if (n < 2 || !e) return std::string("gpsat_bin_batch: ") + name + " needs at least 2 edges";
+        for (int i = 0; i < n; ++i) {
+            if (!std::isfinite(e[i])) return std::string("gpsat_bin_batch: ") + name + " edges must be finite";
+            if (i > 0 && !(e[i] > e[i - 1])) return std::string("gpsat_bin_batch: ") + name + " edges must be strictly increasing";
+        }
+        if (!(hi >= e[n - 1])) return std::string("gpsat_bin_batch: the upper limit of the last ") + name + " bin is below the last edge";
+        return std::string();
+    };
+    std::string msg = check_axis("x", nx, ex, x_hi);
+    if (msg.empty() && two_d) msg = check_axis("y", ny, ey, y_hi);
+    if (!msg.empty()) return fail(GPSAT_EINVAL, msg);
+    const unsigned long long cells = (unsigned long long)(nx - 1) * (unsigned long long)(two_d ? ny - 1 : 1);
+    if (cells >= (1ull << 31)) return fail(GPSAT_EINVAL, "gpsat_bin_batch: 2^31 or more cells per group");
+    if (G > 0 && cells > ((1ull << 63) - 1) / (unsigned long long)G) return fail(GPSAT_EINVAL, "gpsat_bin_batch: G * cells must stay below 2^63");
+    if (R == 0 || G == 0) return GPSAT_OK;
+    if (!x || !v) return fail(GPSAT_EINVAL, "gpsat_bin_batch: x / v is NULL");
+    if (gid)
+        for (int64_t i = 0; i < R; ++i)
+            if (gid[i] < 0 || gid[i] >= G)
+                return fail(GPSAT_EINVAL, "gpsat_bin_batch: gid[" + std::to_string(i) + "] = " + std::to_string(gid[i]) + " is not in 0.." + std::to_string(G - 1));
+    int n_stat = 0;
+    for (uint32_t b = 1; b <= GPSAT_BIN_MEDIAN; b <<= 1) n_stat += (stats & b) ? 1 : 0;
+    h->selc.total = -1;
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    const size_t nR = (size_t)R;
+    const size_t edge_bytes = ((size_t)(nx + (two_d ? ny : 0)) * sizeof(double) + 255) & ~size_t(255);
+    if ((rc = h->bin_in.reserve(edge_bytes + (two_d ? 3 : 2) * nR * sizeof(double) + nR * sizeof(int)))) return rc;
+    if ((rc = h->bin_keys.reserve(2 * nR * sizeof(unsigned long long)))) return rc;
+    if ((rc = h->bin_rows.reserve(2 * nR * sizeof(unsigned)))) return rc;
+    const bool median = (stats & GPSAT_BIN_MEDIAN) != 0;
+    if ((rc = h->bin_vals.reserve((median ? 3 : 1) * nR * sizeof(double)))) return rc;
+    const size_t starts_bytes = ((nR + 1) * sizeof(unsigned) + 255) & ~size_t(255);
+    const size_t flag_bytes = (nR + 255) & ~size_t(255);
+    if ((rc = h->bin_runs.reserve(starts_bytes + 256 + flag_bytes + (nR / gpsat::bin_long_rows() + 1) * sizeof(unsigned)))) return rc;
+    gpsat::BinArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.R = R; a.nx = nx; a.ny = two_d ? ny : 2;
+    double* d_e = static_cast<double*>(h->bin_in.p);
+    double* d_col = reinterpret_cast<double*>(static_cast<char*>(h->bin_in.p) + edge_bytes);
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    HIP_TRY(hipMemcpyAsync(d_e, ex, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.ex = d_e;
+    if (two_d) {
+        HIP_TRY(hipMemcpyAsync(d_e + nx, ey, (size_t)ny * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        a.ey = d_e + nx;
+    }
+    HIP_TRY(hipMemcpyAsync(d_col, x, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.x = d_col; d_col += nR;
+    HIP_TRY(hipMemcpyAsync(d_col, v, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.v = d_col; d_col += nR;
+    if (two_d) {
+        HIP_TRY(hipMemcpyAsync(d_col, y, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        a.y = d_col; d_col += nR;
+    }
+    if (gid) {
+        HIP_TRY(hipMemcpyAsync(d_col, gid, nR * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        a.gid = reinterpret_cast<const int*>(d_col);
+    }
+    a.x_hi = x_hi; a.y_hi = y_hi;
+    a.inv_x = (double)(nx - 1) / (ex[nx - 1] - ex[0]);
+    a.inv_y = two_d ? (double)(ny - 1) / (ey[ny - 1] - ey[0]) : 0.0;
+    if (!std::isfinite(a.inv_x)) a.inv_x = 0.0;           // the range overflowed: the guess is bin 0, the correction does the rest
+    if (!std::isfinite(a.inv_y)) a.inv_y = 0.0;
+    a.sentinel = cells * (unsigned long long)G;
+    a.keys = static_cast<unsigned long long*>(h->bin_keys.p); a.keys_sorted = a.keys + nR;
+    a.rows = static_cast<unsigned*>(h->bin_rows.p); a.perm = a.rows + nR;
+    a.vs = static_cast<double*>(h->bin_vals.p);
+    if (median) { a.vcanon = a.vs + nR; a.vsorted = a.vs + 2 * nR; }
+    a.starts = static_cast<unsigned*>(h->bin_runs.p);
+    char* d_info = static_cast<char*>(h->bin_runs.p) + starts_bytes;
+    a.n_cells = reinterpret_cast<long long*>(d_info);
+    a.n_runs = reinterpret_cast<unsigned*>(d_info + 16);
+    a.n_long = reinterpret_cast<unsigned*>(d_info + 32);
+    a.flags = reinterpret_cast<unsigned char*>(d_info + 256);
+    a.long_list = reinterpret_cast<unsigned*>(d_info + 256 + flag_bytes);
+    a.mask = stats;
+    size_t tb = 0;
+    HIP_TRY(gpsat::bin_sort_rows(a, nullptr, tb, h->stream));
+    if ((rc = h->bin_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::bin_sort_rows(a, h->bin_tmp.p, tb, h->stream));
+    long long info[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(info, a.n_cells, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const long long nc = info[0], n_valid = info[1];
+    *n_cells = nc;
+    if (nc > 0 && capacity >= nc) {
+        if (!keys || !out) return fail(GPSAT_EINVAL, "gpsat_bin_batch: keys / out is NULL");
+        if ((rc = h->bin_out.reserve((size_t)nc * (n_stat + 1) * sizeof(double)))) return rc;
+        a.out_keys = static_cast<long long*>(h->bin_out.p);
+        a.out = reinterpret_cast<double*>(a.out_keys + nc);
+        HIP_TRY(gpsat::bin_cell_stats(a, nc, n_valid, nullptr, tb, h->stream));
+        if ((rc = h->bin_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
+        HIP_TRY(gpsat::bin_cell_stats(a, nc, n_valid, h->bin_tmp.p, tb, h->stream));
+        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        HIP_TRY(hipMemcpyAsync(keys, a.out_keys, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        for (int s = 0; s < n_stat; ++s)
+            HIP_TRY(hipMemcpyAsync(out + (size_t)s * capacity, a.out + (size_t)s * nc, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    } else {
+        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    float km = 0.f, tm = 0.f;
+    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
+    h->last_kernel_ms = km;
+    h->last_total_ms = tm;
+    if (capacity < nc) return fail(GPSAT_EINVAL, "gpsat_bin_batch: capacity " + std::to_string(capacity) + " < n_cells " + std::to_string(nc));
     return GPSAT_OK;
 }
 

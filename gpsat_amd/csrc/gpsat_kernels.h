@@ -150,6 +150,44 @@ hipError_t select_bin_rows(long long M, int C, const double* pts, const BinSpec&
 hipError_t select_unbin(int T, long long total, const unsigned* seg_off, const int* perm, int* idx, int* idx_out, void* temp,
                         size_t& temp_bytes, hipStream_t stream);
 
+// binning of raw observations (gpsat_bin.hip); device pointers.  The statistic bits are those of include/gpsat_hip.h.
+#ifndef GPSAT_BIN_COUNT
+#define GPSAT_BIN_COUNT  1u
+#define GPSAT_BIN_SUM    2u
+#define GPSAT_BIN_MEAN   4u
+#define GPSAT_BIN_STD    8u
+#define GPSAT_BIN_MIN    16u
+#define GPSAT_BIN_MAX    32u
+#define GPSAT_BIN_MEDIAN 64u
+#endif
+struct BinArgs {
+    long long R;                      // rows (< 2^31)
+    int nx, ny;                       // edges per axis (>= 2); ny is not read when y == nullptr (1-D)
+    const double *x, *y, *v;          // [R] coordinates and values; y == nullptr: 1-D
+    const int* gid;                   // [R] group of every row, or nullptr (all rows in group 0)
+    const double *ex, *ey;            // [nx], [ny] increasing bin edges
+    double x_hi, y_hi;                // inclusive upper limit of the last bin (>= the last edge)
+    double inv_x, inv_y;              // bins / (last edge - first edge): the guess of bin_index
+    unsigned long long sentinel;      // G * cells: the key of rows outside the grid
+    unsigned long long *keys, *keys_sorted;   // [R]
+    unsigned *rows, *perm;            // [R] source rows, and the same in sorted order
+    double* vs;                       // [R] values in sorted order
+    double *vcanon, *vsorted;         // [R] median only: vs with one NaN pattern, and every cell's values ascending
+    unsigned char* flags;             // [R] 1 at the first row of every run of equal keys
+    unsigned* starts;                 // [R + 1] first sorted row of every run; starts[n_cells] = rows inside the grid
+    unsigned* n_runs;                 // [1]
+    long long* n_cells;               // [2] non-empty cells, rows inside the grid
+    unsigned* n_long;                 // [1] cells of bin_long_rows() rows or more (zeroed by bin_cell_stats)
+    unsigned* long_list;              // [R / bin_long_rows() + 1] those cells, in no particular order
+    unsigned mask;                    // GPSAT_BIN_* statistics wanted
+    long long* out_keys;              // [n_cells] ascending
+    double* out;                      // [statistics in bit order][n_cells]
+};
+// key per row, stable sort, gather, run heads; leaves n_cells[0..1] on the device
+hipError_t bin_sort_rows(const BinArgs& a, void* temp, size_t& temp_bytes, hipStream_t stream);
+hipError_t bin_cell_stats(const BinArgs& a, long long n_cells, long long n_valid, void* temp, size_t& temp_bytes, hipStream_t stream);
+int bin_long_rows();                  // rows from which a cell's sums are walked by a wave instead of a lane
+
 #define GPSAT_GLUE_MAXVARS 4
 // post-processing (gpsat_post.hip); device pointers
 hipError_t launch_smooth(int T, const double* x, const double* y, const double* vals, double lx, double ly, double* out,

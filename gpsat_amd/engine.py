@@ -36,6 +36,18 @@ class BatchResult:
     total_ms: float = 0.0
 
 
+@dataclass
+class BinResult:
+    """Sparse result of Engine.bin_batch: one record per non-empty cell, ascending ``keys``."""
+    keys: np.ndarray       # [n] int64, (gid (ny-1) + iy)(nx-1) + ix
+    gid: np.ndarray        # [n] int64 group
+    iy: np.ndarray         # [n] int64 bin along y (0 in one dimension)
+    ix: np.ndarray         # [n] int64 bin along x
+    stats: dict            # statistic name -> [n] fp64
+    kernel_ms: float = 0.0
+    total_ms: float = 0.0
+
+
 def centre_tiles(X, Xs, obs_off, pred_off):
     """Subtract every tile's mean coordinate from its observations and prediction points (fp64).
 
@@ -394,6 +406,63 @@ class Engine:
         if rc != 0:
             raise GpsatError(f"gpsat_glue_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         return out
+
+    def bin_batch(self, x, y, v, gid, n_groups, x_edges, y_edges, statistics, x_hi=None, y_hi=None) -> BinResult:
+        """Binned statistics of raw observations, all groups in one call (gpsat_bin_batch; scipy.stats.binned_statistic_2d
+        per group, bit for bit).  x, y, v: [R] (y None: one dimension, y_edges is not read); gid: [R] groups 0..n_groups-1 or
+        None (one group); x_edges, y_edges: the bin edges as np.linspace made them; statistics: names out of count, sum,
+        mean, std, min, max, median.  x_hi / y_hi: inclusive upper limit of the last bin, by default scipy's rounded
+        right-edge rule (dataprep.right_edge_limit)."""
+        if not hasattr(self._lib, "gpsat_bin_batch"):
+            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_bin_batch: rebuild the library (there is no host fallback)")
+        from .dataprep import right_edge_limit
+        names = [statistics] if isinstance(statistics, str) else list(statistics)
+        unknown = [s for s in names if s not in L.BIN_STATS]
+        if unknown or not names:
+            raise GpsatError(f"statistics {unknown or names}: choose from {list(L.BIN_STATS)}")
+        mask = 0
+        for s in names:
+            mask |= L.BIN_STATS[s]
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        R = x.shape[0]
+        assert x.ndim == 1 and v.shape == (R,)
+        if R > 2**31 - 1:
+            raise GpsatError(f"bin_batch takes at most 2^31 - 1 rows per call, got {R}: bin the table in parts of whole groups")
+        ex = np.ascontiguousarray(x_edges, dtype=np.float64)
+        xh = right_edge_limit(ex) if x_hi is None else float(x_hi)
+        ey, yh, ny = None, 0.0, 0
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            assert y.shape == (R,)
+            ey = np.ascontiguousarray(y_edges, dtype=np.float64)
+            yh = right_edge_limit(ey) if y_hi is None else float(y_hi)
+            ny = len(ey)
+        G = int(n_groups)
+        if gid is not None:
+            gid = np.ascontiguousarray(gid, dtype=np.int32)
+            assert gid.shape == (R,)
+        elif G > 1:
+            raise GpsatError("gid is None: n_groups must be 1")
+        rows_y = max(ny - 1, 1)
+        cap = int(min(R, G * max(len(ex) - 1, 0) * rows_y))
+        keys = np.empty(cap, dtype=np.int64)
+        out = np.empty((bin(mask).count("1"), cap), dtype=np.float64)
+        n = C.c_int64(0)
+        rc = self._lib.gpsat_bin_batch(self._h, R, _ptr(x), _ptr(y), _ptr(v), _ptr(gid), G, len(ex), _ptr(ex), xh, ny, _ptr(ey), yh,
+                                       mask, cap, C.byref(n), _ptr(keys), _ptr(out))
+        if rc != 0:
+            raise GpsatError(f"gpsat_bin_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        n = int(n.value)
+        keys = keys[:n].copy()
+        order = [s for s in L.BIN_STATS if L.BIN_STATS[s] & mask]             # output rows: ascending bit
+        stats = {s: out[order.index(s), :n].copy() for s in names}
+        nxb = len(ex) - 1
+        cell, ix = np.divmod(keys, nxb) if nxb > 0 else (keys, keys)
+        g, iy = np.divmod(cell, rows_y)
+        km, tm = C.c_double(0.0), C.c_double(0.0)
+        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
+        return BinResult(keys=keys, gid=g, iy=iy, ix=ix, stats=stats, kernel_ms=km.value, total_ms=tm.value)
 
 
 _default_engine = None

@@ -276,6 +276,49 @@ int gpsat_glue_batch(gpsat_handle *h, int64_t R, int32_t G, int32_t ndim, int32_
                      const double *sigma_rows, double *out);
 
 /*
+ * Binning of raw observations on a regular grid, all groups in one call (added within ABI 4, check for the symbol).
+ * Replaces DataPrep.bin_data_by / DataPrep.bin_data (GPSat/dataprepper.py:21-401): per group (day, satellite, ...) a
+ * scipy.stats.binned_statistic_2d (1-D: binned_statistic) of `v` over the bins of `ex` x `ey`.  Every statistic of every
+ * cell equals scipy's bit for bit for finite values: membership is np.digitize on the edge values (edges[i] <= x <
+ * edges[i+1], rows below the first edge, beyond the last bin or with a NaN coordinate are outside), and sum / mean / std
+ * add a cell's rows one after the other in source row order, as np.bincount does.  NaN values follow scipy: counted by
+ * count; sum, mean, std and max NaN; ignored by min (NaN when the cell holds nothing else); ordered last by the median.
+ *
+ * x, y, v : host fp64 [R]; y = NULL bins in one dimension (ny, ey and y_hi are then not read).
+ * gid     : host [R], the group of every row, 0 <= gid < G; NULL puts every row into group 0.
+ * ex, ey  : host fp64 [nx], [ny]: the bin EDGES, finite and strictly increasing, at least 2 per axis, exactly as the
+ *           caller's np.linspace made them (the library never restates them).
+ * x_hi, y_hi: inclusive upper limit of the LAST bin, >= the last edge: scipy puts x >= edges[-1] into the last bin when
+ *           np.around(x, d) == np.around(edges[-1], d), d = int(-log10(min(diff(edges)))) + 6; np.around is monotone, so
+ *           that set is the interval [edges[-1], x_hi], which the caller finds with np.around itself.  x_hi = edges[-1]
+ *           takes the edge alone.
+ * stats   : a non-empty OR of GPSAT_BIN_*.
+ * Output, sparse: one record per non-empty cell, ascending key; key = (gid (ny-1) + iy)(nx-1) + ix (1-D: gid (nx-1) + ix).
+ *   n_cells: host out [1], always written;  keys: host out [capacity];
+ *   out    : host out fp64 [number of statistics][capacity], the statistics asked for in ascending bit order, statistic s
+ *            of record j at out[s * capacity + j] (count is returned as fp64, exact below 2^53).
+ * The caller sizes the outputs: capacity >= min(R, G (nx-1)(ny-1)) always suffices.  GPSAT_EINVAL when capacity < n_cells
+ * (n_cells is valid: call again), for bad sizes, fewer than 2 edges, edges that do not increase, a limit below the last
+ * edge, gid out of range, an empty or unknown `stats`.  R = 0 and G = 0 are valid and return n_cells = 0.
+ * Limits: R <= 2^31 - 1 rows per call (the sort carries a 32-bit source row), (nx-1)(ny-1) < 2^31 cells per group,
+ * G (nx-1)(ny-1) < 2^63.  A cell's rows are added one after the other, in order (by one lane, by one wave from 1,024
+ * rows): that is what keeps scipy's bits, and it makes a table whose rows all fall into a few cells slow next to a tree
+ * reduction, which is not used (10 M rows in one cell: 0.13 s per sum).
+ * The device workspace (about 60 bytes per row, 16 more with the median) is owned by the handle and kept until
+ * gpsat_destroy.  gpsat_last_timing covers it: kernel_ms = keys, sort and statistics, total_ms = with the copies.
+ */
+#define GPSAT_BIN_COUNT  1u
+#define GPSAT_BIN_SUM    2u
+#define GPSAT_BIN_MEAN   4u
+#define GPSAT_BIN_STD    8u
+#define GPSAT_BIN_MIN    16u
+#define GPSAT_BIN_MAX    32u
+#define GPSAT_BIN_MEDIAN 64u
+int gpsat_bin_batch(gpsat_handle *h, int64_t R, const double *x, const double *y, const double *v, const int32_t *gid,
+                    int32_t G, int32_t nx, const double *ex, double x_hi, int32_t ny, const double *ey, double y_hi,
+                    uint32_t stats, int64_t capacity, int64_t *n_cells, int64_t *keys, double *out);
+
+/*
  * Timing of the last gpsat_fit_predict_batch on this handle, measured with HIP events on the
  * handle's stream: kernel_ms = the persistent tile kernel alone, total_ms = H2D + kernel + D2H.
  */
