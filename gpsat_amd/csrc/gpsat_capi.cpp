@@ -1,6 +1,8 @@
 // gpsat_capi.cpp -- C ABI of libgpsat_hip.so (see include/gpsat_hip.h for the contract and the
 // reference interfaces each entry point replaces).  Host-side responsibilities only: argument
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
+// gpsat_fit_predict_batch in steps: check_batch / check_multistart, plan_tiles (gpsat_plan.h), stage_batch, setup_*, launch,
+// fetch_batch, record_timing.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -14,6 +16,7 @@
 
 #include "gpsat_hip.h"
 #include "gpsat_kernels.h"
+#include "gpsat_plan.h"
 
 namespace {
 
@@ -40,9 +43,26 @@ inline const char* dev_env(const char* name) {
     return std::getenv(name);
 }
 
+// the knobs of the launch plan, read once per call
+gpsat::DevKnobs read_dev_knobs() {
+    gpsat::DevKnobs k;
+    auto read = [](const char* name, gpsat::Knob& kn) {
+        if (const char* e = dev_env(name)) { kn.set = 1; kn.v = std::atoi(e); }
+    };
+    read("GPSAT_DEBUG_TEAM", k.team); read("GPSAT_DEBUG_COOP", k.coop); read("GPSAT_DEBUG_COOP_XCD", k.coop_xcd);
+    read("GPSAT_DEBUG_COOP_MIN_NB", k.coop_min_nb); read("GPSAT_DEBUG_COOP_HDIV", k.coop_hdiv);
+    read("GPSAT_DEBUG_GRID", k.grid); read("GPSAT_DEBUG_SEG", k.seg); read("GPSAT_DEBUG_DEFER", k.defer);
+    return k;
+}
+
+// A device allocation that grows on demand and frees itself with its owner (the handle).
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int reserve(size_t bytes) {
         if (bytes <= cap) return GPSAT_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -55,7 +75,17 @@ struct DevBuf {
         cap = want;
         return GPSAT_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Stream and events of a handle.  A base of gpsat_handle, so that they are destroyed AFTER the handle's members: the device
+// buffers are freed first, then the events, then the stream.
+struct HandleQueue {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~HandleQueue() {
+        for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 }  // namespace
@@ -78,16 +108,12 @@ static unsigned long long sel_fingerprint(const double* points, long long nP, co
     return h;
 }
 
-struct gpsat_handle {
+struct gpsat_handle : HandleQueue {
     int device = 0;
     int num_cu = 0;
     int wg_per_cu = 2;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     char name[256] = {0};
     double last_kernel_ms = 0.0, last_total_ms = 0.0;
-    bool force_unsliced = false;       // retry of a batch whose time-sliced queue ended with unfinished tiles
-    bool force_solo = false;           // retry of a batch in which a team barrier gave up
     // gpsat_select_batch is called twice per selection (sizes, then indices): the first call already leaves the indices on
     // the device; the second, when it repeats the first call's arguments, only copies them out
     struct {
@@ -99,7 +125,7 @@ struct gpsat_handle {
         const int* d_result = nullptr;
         std::vector<int64_t> off;
     } selc;
-    // device buffers (grown lazily, owned by the handle)
+    // device buffers (grown lazily, owned by the handle, freed by its destructor)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
@@ -108,6 +134,471 @@ struct gpsat_handle {
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
 };
+
+namespace {
+
+// Every entry point that uses the device starts its device work here.  Any call on the handle ends a pending two-call
+// selection (the selection's own sizes call sets it up again at its end).
+int begin_call(gpsat_handle* h) {
+    h->selc.total = -1;
+    HIP_TRY(hipSetDevice(h->device));
+    return GPSAT_OK;
+}
+
+// Kernel time ev[1]..ev[2] and total time ev[t0]..ev[t1] of the call that just synchronised the stream.
+int record_timing(gpsat_handle* h, int t0 = 0, int t1 = 3) {
+    float km = 0.f, tm = 0.f;
+    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&tm, h->ev[t0], h->ev[t1]));
+    h->last_kernel_ms = km;
+    h->last_total_ms = tm;
+    return GPSAT_OK;
+}
+
+struct BatchDims { long long sumN = 0, sumP = 0, sumC = 0, sumM = 0, maxN = 0, maxP = 0; bool want_cov = false; };
+
+// The argument checks the dense and the sparse entry point share, in the order of the dense one, up to the CSR offsets
+// (largest tile and sums into `d`).  `f64_only`: the sparse entry point's dtype rule.  T == 0 is the caller's early return.
+int check_batch(const gpsat_batch* b, bool f64_only, BatchDims& d) {
+    if (b->T < 0) return fail(GPSAT_EINVAL, "T < 0");
+    if (b->D < 1 || b->D > 4) return fail(GPSAT_EINVAL, "D must be 1..4 in this build");
+    if (f64_only && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "sparse GP experts are built for GPSAT_F64 only");
+    if (b->dtype != GPSAT_F32 && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "unknown dtype");
+    if (b->kernel < 0 || b->kernel > 3) return fail(GPSAT_EINVAL, "unknown kernel id");
+    if (b->optimiser < 0 || b->optimiser > 2) return fail(GPSAT_EINVAL, "unknown optimiser id");
+    if (b->memory != GPSAT_MEM_HOST && b->memory != GPSAT_MEM_DEVICE) return fail(GPSAT_EINVAL, "bad memory flag");
+    if (!b->obs_off || !b->pred_off || !b->theta0 || !b->lo || !b->hi || !b->trainable)
+        return fail(GPSAT_EINVAL, "metadata pointer is NULL");
+    if (!b->theta || !b->nll || !b->status || !b->n_eval) return fail(GPSAT_EINVAL, "output pointer is NULL");
+    // ---- validate CSR offsets, find the largest tile
+    if (b->obs_off[0] != 0 || b->pred_off[0] != 0) return fail(GPSAT_EINVAL, "offsets must start at 0");
+    for (int t = 0; t < b->T; ++t) {
+        const long long n = b->obs_off[t + 1] - b->obs_off[t], p = b->pred_off[t + 1] - b->pred_off[t];
+        if (n < 0 || p < 0) return fail(GPSAT_EINVAL, "offsets must be non-decreasing");
+        d.maxN = std::max(d.maxN, n);
+    }
+    d.sumN = b->obs_off[b->T]; d.sumP = b->pred_off[b->T];
+    return GPSAT_OK;
+}
+
+// ... and the checks that follow the offsets in both: data pointers against the sums, theta0
+int check_batch_data(const gpsat_batch* b, const BatchDims& d) {
+    if (d.sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
+    if (d.sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
+    for (size_t e = 0; e < (size_t)b->T * (b->D + 2); ++e)
+        if (!(b->theta0[e] > 0.0) || !std::isfinite(b->theta0[e])) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
+    return GPSAT_OK;
+}
+
+// x clipped into the bounds of the trainable parameters, n rows of H per tile (SciPy clips x0 into the bounds,
+// _minimize_lbfgsb; the further starts likewise: L-BFGS-B works inside the box only)
+std::vector<double> clip_to_bounds(const gpsat_batch* b, const double* x, int n) {
+    const int T = b->T, H = b->D + 2;
+    std::vector<double> out(x, x + (size_t)T * n * H);
+    for (int t = 0; t < T; ++t)
+        for (int k = 0; k < n; ++k)
+            for (int i = 0; i < H; ++i)
+                if (b->trainable[i]) {
+                    double& v = out[((size_t)t * n + k) * H + i];
+                    v = std::min(std::max(v, b->lo[(size_t)t * H + i]), b->hi[(size_t)t * H + i]);
+                }
+    return out;
+}
+
+// ---- multi-start bounded L-BFGS-B (gpsat_fit_predict_batch_ms): checks, then theta0 and the starts clipped into the box
+// when the optimiser runs at all (`ms_on`)
+int check_multistart(const gpsat_batch* b, const gpsat_multistart* ms, bool ms_on, std::vector<double>& theta0_clipped,
+                     std::vector<double>& starts_clipped) {
+    const int T = b->T, H = b->D + 2, S = ms->n_starts;
+    if (S < 1) return fail(GPSAT_EINVAL, "multistart: n_starts must be >= 1");
+    if (ms->transform != GPSAT_TRANSFORM_LOG) return fail(GPSAT_EINVAL, "multistart: unknown transform (GPSAT_TRANSFORM_LOG only)");
+    if (S > 1 && !ms->starts) return fail(GPSAT_EINVAL, "multistart: starts is NULL with n_starts > 1");
+    if (b->optimiser == GPSAT_OPT_ADAM) return fail(GPSAT_EINVAL, "multistart: the optimiser must be L-BFGS-B or none");
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < H; ++i) {
+            if (!b->trainable[i]) continue;
+            const double lo = b->lo[(size_t)t * H + i], hi = b->hi[(size_t)t * H + i];
+            if (!(lo > 0.0) || !(hi > 0.0) || !(lo <= hi))
+                return fail(GPSAT_EINVAL, "multistart: the bounds of a trainable parameter must be positive with lo <= hi (log transform)");
+            if (S > 1 && (!std::isfinite(lo) || !std::isfinite(hi)))
+                return fail(GPSAT_EINVAL, "multistart: restarts require that all bounds are finite");
+        }
+    if (S > 1)
+        for (size_t e = 0; e < (size_t)T * (S - 1) * H; ++e)
+            if (!(ms->starts[e] > 0.0) || !std::isfinite(ms->starts[e]))
+                return fail(GPSAT_EINVAL, "multistart: starts must be finite and positive");
+    if (ms_on) theta0_clipped = clip_to_bounds(b, b->theta0, 1);
+    if (ms_on && S > 1) starts_clipped = clip_to_bounds(b, ms->starts, S - 1);
+    return GPSAT_OK;
+}
+
+// Device pointers of a staged batch.
+struct Staged {
+    const char *X = nullptr, *y = nullptr, *Xs = nullptr, *Z = nullptr;
+    char *fm = nullptr, *fv = nullptr, *yv = nullptr, *cov = nullptr;
+    long long* i64 = nullptr;         // [3][T+1]: obs_off, pred_off, then cov_off (dense) or z_off (sparse)
+    double *f64 = nullptr, *out_f64 = nullptr;    // [3][T*H]: theta0, lo, hi; theta [T*H], nll [T], grad [T*H]
+    int *out_i32 = nullptr, *queue = nullptr, *order = nullptr;   // status, n_eval, n_iter: [T] each; queue head; [T] tile order
+    unsigned char* train = nullptr;
+};
+
+// Reserve the metadata, output, workspace and (host mode) bulk buffers, lay them out, record ev[0] and issue the host-to-device
+// copies.  `off3`: the third offset table or nullptr; `Z`: the sparse path's inducing points (d.sumM rows) or nullptr.
+// `order` is pageable host memory of the caller and must outlive the launch.
+int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const double* theta0, const std::vector<int>& order,
+                const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s) {
+    const int T = b->T, D = b->D, H = D + 2;
+    const size_t esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
+    const size_t sumN = (size_t)d.sumN, sumP = (size_t)d.sumP, sumM = (size_t)d.sumM;
+    int rc;
+    if ((rc = h->meta_i64.reserve(3 * (size_t)(T + 1) * sizeof(long long)))) return rc;
+    if ((rc = h->meta_f64.reserve(3 * (size_t)T * H * sizeof(double)))) return rc;
+    if ((rc = h->meta_misc.reserve((size_t)T * sizeof(int) + 64 + 16))) return rc;
+    if ((rc = h->out_f64.reserve(((size_t)T * H * 2 + (size_t)T) * sizeof(double)))) return rc;
+    if ((rc = h->out_i32.reserve((size_t)T * 3 * sizeof(int)))) return rc;
+    if ((rc = h->ws.reserve(ws_bytes))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (b->memory == GPSAT_MEM_HOST) {
+        const size_t in_e = sumN * D + sumN + sumP * D + sumM * D;
+        if ((rc = h->bulk_in.reserve(std::max<size_t>(in_e, 1) * esz))) return rc;
+        if ((rc = h->bulk_out.reserve(std::max<size_t>(sumP * 3 + (size_t)d.sumC, 1) * esz))) return rc;
+        char* base = static_cast<char*>(h->bulk_in.p);
+        s.X = base; s.y = s.X + sumN * D * esz; s.Xs = s.y + sumN * esz; s.Z = s.Xs + sumP * D * esz;
+        if (sumN > 0) {
+            HIP_TRY(hipMemcpyAsync(base, b->X, sumN * D * esz, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(const_cast<char*>(s.y), b->y, sumN * esz, hipMemcpyHostToDevice, h->stream));
+        }
+        if (sumP > 0) HIP_TRY(hipMemcpyAsync(const_cast<char*>(s.Xs), b->Xs, sumP * D * esz, hipMemcpyHostToDevice, h->stream));
+        if (Z) HIP_TRY(hipMemcpyAsync(const_cast<char*>(s.Z), Z, sumM * D * esz, hipMemcpyHostToDevice, h->stream));
+        s.fm = static_cast<char*>(h->bulk_out.p); s.fv = s.fm + sumP * esz; s.yv = s.fv + sumP * esz;
+        if (d.want_cov) s.cov = s.yv + sumP * esz;
+    } else {
+        s.cov = static_cast<char*>(b->f_cov);
+        s.X = static_cast<const char*>(b->X); s.y = static_cast<const char*>(b->y); s.Xs = static_cast<const char*>(b->Xs);
+        s.Z = static_cast<const char*>(Z);
+        s.fm = static_cast<char*>(b->f_mean); s.fv = static_cast<char*>(b->f_var); s.yv = static_cast<char*>(b->y_var);
+    }
+    s.i64 = static_cast<long long*>(h->meta_i64.p);
+    s.f64 = static_cast<double*>(h->meta_f64.p);
+    const int64_t* offs[3] = {b->obs_off, b->pred_off, off3};
+    const double* pars[3] = {theta0, b->lo, b->hi};
+    for (int i = 0; i < 3; ++i)
+        if (offs[i]) HIP_TRY(hipMemcpyAsync(s.i64 + i * (T + 1), offs[i], (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    for (int i = 0; i < 3; ++i)
+        HIP_TRY(hipMemcpyAsync(s.f64 + i * (size_t)T * H, pars[i], (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    unsigned char* d_misc = static_cast<unsigned char*>(h->meta_misc.p);
+    s.queue = reinterpret_cast<int*>(d_misc);                 // 16 bytes reserved
+    s.train = d_misc + 16;                                    // 64 bytes reserved
+    s.order = reinterpret_cast<int*>(d_misc + 16 + 64);
+    HIP_TRY(hipMemsetAsync(s.queue, 0, 16, h->stream));
+    HIP_TRY(hipMemcpyAsync(s.train, b->trainable, (size_t)H, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s.order, order.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    s.out_f64 = static_cast<double*>(h->out_f64.p);
+    s.out_i32 = static_cast<int*>(h->out_i32.p);
+    return GPSAT_OK;
+}
+
+// The fields KernelArgs and SgprArgs have in common: sizes, optimiser settings with their defaults, staged pointers.
+template <class Args>
+void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s) {
+    const int T = b->T, H = b->D + 2;
+    const bool f64 = b->dtype == GPSAT_F64;
+    a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
+    a.max_ls = b->max_ls > 0 ? b->max_ls : 20;                                 // SciPy L-BFGS-B maxls
+    // 0 = default (fp64: SciPy's factr*eps; fp32: its analogue above the fp32 noise floor); negative = criterion off
+    a.ftol = b->ftol > 0 ? b->ftol : (b->ftol < 0 ? -1.0 : (f64 ? 2.220446049250313e-9 : 1e-6));
+    a.gtol = b->gtol > 0 ? b->gtol : (b->gtol < 0 ? -1.0 : 1e-5);
+    a.adam_lr = b->adam_lr > 0 ? b->adam_lr : 0.1;
+    // relative resolution of the objective: fp32 rounding ~ cond(K) eps N reaches 2e-4 |f| on the reference's 1-D tutorial
+    // tile (cond ~ 2e4, docs/notebooks/1d_local_expert_model_part_2.ipynb); fp64: rounding level only
+    a.noise_rel = f64 ? 1e-12 : 1e-3;
+    a.obs_off = s.i64; a.pred_off = s.i64 + (T + 1);
+    a.theta0 = s.f64; a.lo = s.f64 + (size_t)T * H; a.hi = s.f64 + 2 * (size_t)T * H;
+    a.trainable = s.train;
+    a.X = reinterpret_cast<decltype(a.X)>(s.X); a.y = reinterpret_cast<decltype(a.y)>(s.y); a.Xs = reinterpret_cast<decltype(a.Xs)>(s.Xs);
+    a.theta = s.out_f64; a.nll = s.out_f64 + (size_t)T * H;
+    a.grad = b->grad ? s.out_f64 + (size_t)T * H + T : nullptr;
+    a.status = s.out_i32; a.n_eval = s.out_i32 + T; a.n_iter = s.out_i32 + 2 * (size_t)T;
+    a.f_mean = reinterpret_cast<decltype(a.f_mean)>(s.fm); a.f_var = reinterpret_cast<decltype(a.f_var)>(s.fv);
+    a.y_var = reinterpret_cast<decltype(a.y_var)>(s.yv);
+    a.order = s.order; a.queue = s.queue;
+}
+
+// Device-to-host copies of the results (host mode: the predictions and the covariance too).
+int fetch_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const Staged& s) {
+    const size_t T = (size_t)b->T, H = (size_t)b->D + 2, esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
+    HIP_TRY(hipMemcpyAsync(b->theta, s.out_f64, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->nll, s.out_f64 + T * H, T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, s.out_f64 + T * H + T, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->status, s.out_i32, T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(b->n_eval, s.out_i32 + T, T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (b->n_iter) HIP_TRY(hipMemcpyAsync(b->n_iter, s.out_i32 + 2 * T, T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    void* const host[3] = {b->f_mean, b->f_var, b->y_var};
+    const char* const dev[3] = {s.fm, s.fv, s.yv};
+    for (int i = 0; i < 3 && b->memory == GPSAT_MEM_HOST && d.sumP > 0; ++i)
+        HIP_TRY(hipMemcpyAsync(host[i], dev[i], (size_t)d.sumP * esz, hipMemcpyDeviceToHost, h->stream));
+    if (b->memory == GPSAT_MEM_HOST && d.want_cov && d.sumC > 0)
+        HIP_TRY(hipMemcpyAsync(b->f_cov, s.cov, (size_t)d.sumC * esz, hipMemcpyDeviceToHost, h->stream));
+    return GPSAT_OK;
+}
+
+// ---- time slicing: the ring preset with the tiles in `order`, its counters, the saved-state area
+int setup_ring(gpsat_handle* h, const gpsat::TilePlan& p, const std::vector<int>& order, gpsat::KernelArgs& a) {
+    a.ring = nullptr; a.ring_ctl = nullptr; a.state = nullptr;
+    a.ring_mask = 0; a.state_words = p.state_words; a.seg_cost = p.seg_cost;
+    if (p.seg_cost <= 0) return GPSAT_OK;
+    const int T = (int)order.size();
+    const size_t cap = p.ring_cap;
+    int rc;
+    if ((rc = h->ring.reserve(cap * sizeof(unsigned long long) + 256))) return rc;
+    if ((rc = h->state.reserve((size_t)T * p.state_words * sizeof(unsigned)))) return rc;
+    a.ring_mask = (int)(cap - 1);
+    a.ring_ctl = static_cast<int*>(h->ring.p);
+    a.ring = reinterpret_cast<unsigned long long*>(static_cast<char*>(h->ring.p) + 256);
+    a.state = static_cast<unsigned*>(h->state.p);
+    std::vector<unsigned long long> init(cap, 0ull);       // local host memory, like `ctl`: synchronised below, before they go
+    for (int i = 0; i < T; ++i) init[i] = ((unsigned long long)(i + 1) << 32) | (unsigned)order[i];
+    int ctl[64] = {0};
+    ctl[16] = T; ctl[32] = T;
+    HIP_TRY(hipMemcpyAsync(a.ring_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a.ring, init.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // `init` and `ctl` are stack / local host memory
+    return GPSAT_OK;
+}
+
+// ---- cooperative tiles, or teams: both keep their control blocks in h->coop (fp32 / fp64 kernels, never both)
+int setup_coop_and_team(gpsat_handle* h, const gpsat::TilePlan& p, const int* T_host, gpsat::KernelArgs& a) {
+    int rc;
+    a.coop = nullptr; a.coop_live = nullptr; a.coop_min_nb = p.coop_min_nb; a.coop_hdiv = p.coop_hdiv; a.coop_force = p.coop_force;
+    if (p.coop) {
+        // [grid] control blocks of 1 KiB, zeroed every launch, then the count of unfinished tiles
+        const size_t cb = (size_t)p.grid * 1024;
+        if ((rc = h->coop.reserve(cb + 64))) return rc;
+        HIP_TRY(hipMemsetAsync(h->coop.p, 0, cb + 64, h->stream));
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(h->coop.p) + cb, T_host, sizeof(int), hipMemcpyHostToDevice, h->stream));
+        a.coop = h->coop.p;
+        a.coop_live = reinterpret_cast<int*>(static_cast<char*>(h->coop.p) + cb);
+    }
+    a.team_size = p.team; a.team_ctl = nullptr;
+    if (p.team > 1) {
+        const size_t tb = (size_t)(p.grid / p.team) * 256;
+        if ((rc = h->coop.reserve(tb))) return rc;
+        HIP_TRY(hipMemsetAsync(h->coop.p, 0, tb, h->stream));
+        a.team_ctl = h->coop.p;
+    }
+    return GPSAT_OK;
+}
+
+// ---- multi-start: per-tile state (log theta0, best so far), the clipped further starts, the objectives of every start
+int setup_multistart(gpsat_handle* h, const gpsat_batch* b, int S, const double* theta0, const std::vector<double>& starts,
+                     gpsat::KernelArgs& a) {
+    const int T = b->T, H = b->D + 2;
+    const size_t n_state = (size_t)T * gpsat::MS_WORDS, n_starts = (size_t)T * (S - 1) * H, n_f = (size_t)T * S;
+    int rc;
+    if ((rc = h->ms.reserve((n_state + n_starts + n_f) * sizeof(double)))) return rc;
+    // state, then NaN in f_start for tiles that run no start (no observations)
+    std::vector<double> init(n_state + n_f, 0.0);          // local host memory: synchronised below, before it goes
+    std::fill(init.begin() + n_state, init.end(), std::numeric_limits<double>::quiet_NaN());
+    for (int t = 0; t < T; ++t) {
+        double* st = init.data() + (size_t)t * gpsat::MS_WORDS;
+        st[1] = std::numeric_limits<double>::infinity();     // best f
+        st[4] = -1.0;                                         // best start: none yet
+        for (int i = 0; i < H; ++i) st[5 + i] = std::log(theta0[(size_t)t * H + i]);
+    }
+    double* d_ms = static_cast<double*>(h->ms.p);
+    HIP_TRY(hipMemcpyAsync(d_ms, init.data(), n_state * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (n_starts) HIP_TRY(hipMemcpyAsync(d_ms + n_state, starts.data(), n_starts * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_ms + n_state + n_starts, init.data() + n_state, n_f * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // `init` is local host memory
+    a.ms_S = S; a.ms_state = d_ms; a.ms_starts = d_ms + n_state; a.ms_fout = d_ms + n_state + n_starts;
+    return GPSAT_OK;
+}
+
+// ---- deferred predictions: the snapshot pool the plan asked for (gpsat_ring.h), or none when there is no memory for it
+int setup_deferred(gpsat_handle* h, const gpsat::TilePlan& p, gpsat::KernelArgs& a) {
+    a.pq = nullptr; a.pq_ctl = nullptr; a.cu_busy = nullptr; a.pq_snap = nullptr; a.pq_stride = 0; a.pq_slots = 0;
+    size_t slots = (size_t)p.pq_slots;
+    // (head rounded to 256 B: the snapshots move as 16-B block accesses)
+    const size_t head = (256 + 2048 * sizeof(int) + slots * sizeof(unsigned long long) + 255) & ~size_t(255);
+    if (slots > 0 && h->pq.reserve(head + slots * p.pq_stride * sizeof(float)) != GPSAT_OK) {
+        // no memory for the pool: every prediction inline (the same results), not an error
+        g_err.clear();
+        (void)hipGetLastError();
+        slots = 0;
+    }
+    if (slots == 0) return GPSAT_OK;
+    HIP_TRY(hipMemsetAsync(h->pq.p, 0, head, h->stream));
+    char* q = static_cast<char*>(h->pq.p);
+    a.pq_ctl = reinterpret_cast<int*>(q);
+    a.cu_busy = reinterpret_cast<int*>(q + 256);
+    a.pq = reinterpret_cast<unsigned long long*>(q + 256 + 2048 * sizeof(int));
+    a.pq_snap = reinterpret_cast<float*>(q + head);
+    a.pq_stride = p.pq_stride; a.pq_slots = (int)slots;
+    return GPSAT_OK;
+}
+
+// What the host reads back about a launch besides the results: the two rerun conditions and the developer statistics.
+struct LaunchReport {
+    std::vector<int> team, coop;      // TeamCtl / CoopCtl blocks
+    int pq_taken = -1, unfinished = 0;
+    bool team_gave_up = false;
+};
+
+// the copies of the report, queued behind the results; the caller synchronises the stream before `r` is read or goes
+int queue_report(gpsat_handle* h, const gpsat::TilePlan& p, const gpsat::KernelArgs& a, LaunchReport& r) {
+    if (p.team > 1) {
+        r.team.resize((size_t)(p.grid / p.team) * 64);
+        HIP_TRY(hipMemcpyAsync(r.team.data(), h->coop.p, r.team.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (p.coop && dev_env("GPSAT_DEBUG_COOP_STATS")) {
+        r.coop.resize((size_t)p.grid * 256);
+        HIP_TRY(hipMemcpyAsync(r.coop.data(), h->coop.p, (size_t)p.grid * 1024, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (a.pq_ctl && dev_env("GPSAT_DEBUG_DEFER_STATS"))
+        HIP_TRY(hipMemcpyAsync(&r.pq_taken, a.pq_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (p.seg_cost > 0) HIP_TRY(hipMemcpyAsync(&r.unfinished, a.ring_ctl + 32, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return GPSAT_OK;
+}
+
+// after the synchronisation: the developer statistics on stderr, and whether a team barrier gave up
+void read_report(const gpsat::TilePlan& p, const gpsat::KernelArgs& a, LaunchReport& r) {
+    const int grid = p.grid, T = a.T;
+    if (!r.coop.empty()) {
+        long long st[8] = {0};
+        for (int g = 0; g < grid; ++g) for (int i = 0; i < 8; ++i) st[i] += r.coop[(size_t)g * 256 + 32 + GPSAT_PT_MAXNB + i];
+        std::fprintf(stderr, "gpsat coop: grid %d T %d: cooperative evaluations %lld, helper phases %lld, helper groups (sweep) %lld, "
+                             "flag waits given up %lld, owner waits given up %lld, pivot failures %lld, helper unwinds %lld\n",
+                     grid, T, st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
+    }
+    if (dev_env("GPSAT_DEBUG_DEFER_STATS"))       // developer / tests: how many predictions were deferred
+        std::fprintf(stderr, "gpsat defer: T %d: deferred predictions %d of %d snapshot slots\n", T,
+                     r.pq_taken < 0 ? 0 : std::min(r.pq_taken, a.pq_slots), a.pq_slots);
+    if (!r.team.empty() && dev_env("GPSAT_DEBUG_TEAM_STATS"))
+        std::fprintf(stderr, "gpsat team 0 (size %d), factorisation, owner thread 0, s_memtime ticks: own work of (A) %d, (A) wait + barrier %d, (B) + barrier %d, "
+                             "(C) + barrier %d\n", p.team, r.team[24], r.team[25], r.team[26], r.team[27]);
+    for (size_t g = 0; g < r.team.size() / 64; ++g)
+        if (r.team[g * 64 + 5]) r.team_gave_up = true;    // TeamCtl::timeout: a team barrier gave up (never by design)
+}
+
+// What check_* leave for the runs of one dense batch.
+struct DenseJob {
+    const gpsat_batch* b;
+    const gpsat_multistart* ms;       // nullptr: gpsat_fit_predict_batch
+    bool ms_on;                       // ms given and the optimiser runs
+    BatchDims dims;
+    const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
+    std::vector<double> theta0_clipped, starts_clipped;
+    std::vector<int> order;           // tiles, largest cost first
+};
+
+// One run of a checked batch: plan, stage, set up, launch, fetch, synchronise.  `solo` / `unsliced`: the two reruns.
+int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, LaunchReport& r) {
+    const gpsat_batch* b = j.b;
+    const BatchDims& d = j.dims;
+    const bool f64 = b->dtype == GPSAT_F64;
+    gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
+                           h->num_cu, h->wg_per_cu, solo, unsliced, read_dev_knobs()};
+    gpsat::TilePlan p;
+    if (!gpsat::plan_tiles(in, p)) return fail(GPSAT_EINVAL, "tile too large for LDS");
+    Staged s;
+    int rc;
+    // one workspace per workgroup, or per team
+    const size_t ws_bytes = (size_t)(p.grid / p.team) * p.ws_stride * (f64 ? sizeof(double) : sizeof(float));
+    if ((rc = stage_batch(h, b, d, j.theta0, j.order, d.want_cov ? b->cov_off : nullptr, nullptr, ws_bytes, s))) return rc;
+    gpsat::KernelArgs a;
+    fill_common_args(a, b, s);
+    a.NBmax = p.NBmax;
+    a.ws = static_cast<float*>(h->ws.p); a.ws_stride = p.ws_stride;     // fp64: the kernel reinterprets ws as doubles
+    a.prof = nullptr;
+    a.cov_off = d.want_cov ? s.i64 + 2 * (b->T + 1) : nullptr;
+    a.f_cov = d.want_cov ? reinterpret_cast<float*>(s.cov) : nullptr;
+    a.PCmax = p.PCcov;
+    a.dump = nullptr; a.dump_stride = 0;
+    if ((rc = setup_ring(h, p, j.order, a))) return rc;
+    if ((rc = setup_coop_and_team(h, p, &b->T, a))) return rc;
+    if (j.ms_on && (rc = setup_multistart(h, b, j.ms->n_starts, j.theta0, j.starts_clipped, a))) return rc;
+    if ((rc = setup_deferred(h, p, a))) return rc;
+#ifdef GPSAT_DUMP
+    if (h->dump_dev && !f64) {
+        const size_t need = ((size_t)p.NBmax * p.NBmax + p.NBmax) * 1024 + 2 * (size_t)p.NBmax * 32 + 16 + 8 * 1024;
+        if (h->dump_stride < need) return fail(GPSAT_EINVAL, "dump stride too small: need " + std::to_string(need) + " floats per tile");
+        a.dump = h->dump_dev; a.dump_stride = h->dump_stride;
+    }
+#endif
+#ifdef GPSAT_PROFILE
+    if ((rc = h->prof.reserve(sizeof(h->prof_host)))) return rc;
+    HIP_TRY(hipMemsetAsync(h->prof.p, 0, sizeof(h->prof_host), h->stream));
+    a.prof = static_cast<unsigned long long*>(h->prof.p);
+#endif
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    if ((rc = fetch_batch(h, b, d, s))) return rc;
+    if (j.ms_on && j.ms->f_start)
+        HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+#ifdef GPSAT_PROFILE
+    HIP_TRY(hipMemcpyAsync(h->prof_host, h->prof.p, sizeof(h->prof_host), hipMemcpyDeviceToHost, h->stream));
+#endif
+    if ((rc = queue_report(h, p, a, r))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    read_report(p, a, r);
+    return GPSAT_OK;
+}
+
+int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
+    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
+    if (b->T == 0) return GPSAT_OK;
+    DenseJob j;
+    j.b = b; j.ms = ms;
+    int rc;
+    if ((rc = check_batch(b, false, j.dims))) return rc;
+    BatchDims& d = j.dims;
+    d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
+    if (d.want_cov) {
+        if (!b->cov_off) return fail(GPSAT_EINVAL, "f_cov given without cov_off");
+        if (b->cov_off[0] != 0) return fail(GPSAT_EINVAL, "cov_off must start at 0");
+        for (int t = 0; t < b->T; ++t) {
+            const long long p = b->pred_off[t + 1] - b->pred_off[t];
+            if (b->cov_off[t + 1] - b->cov_off[t] != p * p) return fail(GPSAT_EINVAL, "cov_off[t+1]-cov_off[t] must equal P_t^2");
+            d.maxP = std::max(d.maxP, p);
+        }
+        d.sumC = b->cov_off[b->T];
+    }
+    if (d.maxN > gpsat_max_tile_obs(b->dtype, b->D))
+        return fail(GPSAT_EINVAL, "tile too large for the LDS of a CU: at most " + std::to_string(gpsat_max_tile_obs(b->dtype, b->D)) +
+                                      " observations per tile for this dtype and D (gpsat_max_tile_obs)");
+    if ((rc = check_batch_data(b, d))) return rc;
+    j.ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
+    if (ms && (rc = check_multistart(b, ms, j.ms_on, j.theta0_clipped, j.starts_clipped))) return rc;
+    j.theta0 = j.ms_on ? j.theta0_clipped.data() : b->theta0;
+    if ((rc = begin_call(h))) return rc;
+    // ---- tile order: largest cost first (N^3), stable so equal tiles keep the reference order.  A multi-start batch costs
+    // S times as much per tile, alike for every tile: neither the order nor the slicing decision of the plan changes with S.
+    j.order.resize(b->T);
+    std::iota(j.order.begin(), j.order.end(), 0);
+    std::stable_sort(j.order.begin(), j.order.end(), [&](int a, int c) {
+        return (b->obs_off[a + 1] - b->obs_off[a]) > (b->obs_off[c + 1] - b->obs_off[c]);
+    });
+    for (bool solo = false, unsliced = false;;) {
+        LaunchReport r;
+        if ((rc = run_tiles(h, j, solo, unsliced, r))) return rc;
+        if (r.team_gave_up) {             // run the batch again, one workgroup per tile
+            std::fprintf(stderr, "gpsat: a team barrier gave up; re-running the batch with one workgroup per tile\n");
+            solo = true;
+        } else if (r.unfinished != 0) {
+            // A queue anomaly (an escape hatch of ring_pop taken: gpsat_ring.h) must not cost the caller the batch: run it again
+            // with every tile run to completion from the plain queue (same results: slicing does not change a bit of them).
+            if (unsliced) return fail(GPSAT_EHIP, "tile queue ended with " + std::to_string(r.unfinished) + " unfinished tiles");
+            std::fprintf(stderr, "gpsat: time-sliced tile queue ended with %d unfinished tiles; re-running the batch unsliced\n", r.unfinished);
+            unsliced = true;
+        } else {
+            return record_timing(h);
+        }
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -131,10 +622,9 @@ int gpsat_max_tile_obs(int dtype, int D) {
     const bool f64 = dtype == GPSAT_F64;
     const int bs = f64 ? 16 : 32;
     const int nb_max = f64 ? GPSAT_MAX_TILE_OBS / bs : std::min(GPSAT_MAX_TILE_OBS / bs, GPSAT_PT_MAXNB);
-    for (int NB = nb_max; NB >= 1; --NB) {
-        const size_t smem = f64 ? gpsat::shared_bytes_f64(D, NB) : gpsat::shared_bytes_w8(D, NB);
-        if (smem <= 160 * 1024) return NB * bs;
-    }
+    const gpsat::Build& w8 = gpsat::builds[f64 ? gpsat::BUILD_F64_W8 : gpsat::BUILD_F32_W8];
+    for (int NB = nb_max; NB >= 1; --NB)
+        if (w8.shared_bytes(D, NB) <= 160 * 1024) return NB * bs;
     return 0;
 }
 
@@ -173,15 +663,7 @@ int gpsat_destroy(gpsat_handle* h) {
     if (!h) return GPSAT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->meta_i64.release(); h->meta_f64.release(); h->meta_misc.release(); h->out_f64.release();
-    h->out_i32.release(); h->bulk_in.release(); h->bulk_out.release(); h->ws.release(); h->prof.release(); h->ring.release(); h->state.release(); h->coop.release(); h->pq.release();
-    h->sel_pts.release(); h->sel_refs.release(); h->sel_cnt.release(); h->sel_idx.release(); h->sel_box.release();
-    h->sel_perm.release(); h->sel_keys.release(); h->sel_tmp.release(); h->sel_ord.release(); h->sel_bnd.release();
-    h->bin_in.release(); h->bin_keys.release(); h->bin_rows.release(); h->bin_vals.release(); h->bin_runs.release();
-    h->bin_tmp.release(); h->bin_out.release();
-    for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                         // every device buffer, then the events, then the stream
     return GPSAT_OK;
 }
 
@@ -192,441 +674,11 @@ int gpsat_last_timing(gpsat_handle* h, double* kernel_ms, double* total_ms) {
     return GPSAT_OK;
 }
 
-static int fit_predict_impl(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms);
-
-int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_predict_impl(h, b, nullptr); }
+int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_predict(h, b, nullptr); }
 
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
     if (!ms) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_ms: NULL multistart");
-    return fit_predict_impl(h, b, ms);
-}
-
-static int fit_predict_impl(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
-    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
-    h->selc.total = -1;               // any other call on the handle ends a pending two-call selection
-    if (b->T < 0) return fail(GPSAT_EINVAL, "T < 0");
-    if (b->T == 0) return GPSAT_OK;
-    if (b->D < 1 || b->D > 4) return fail(GPSAT_EINVAL, "D must be 1..4 in this build");
-    if (b->dtype != GPSAT_F32 && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "unknown dtype");
-    const bool f64 = b->dtype == GPSAT_F64;
-    const size_t esz = f64 ? sizeof(double) : sizeof(float);
-    if (b->kernel < 0 || b->kernel > 3) return fail(GPSAT_EINVAL, "unknown kernel id");
-    if (b->optimiser < 0 || b->optimiser > 2) return fail(GPSAT_EINVAL, "unknown optimiser id");
-    if (b->memory != GPSAT_MEM_HOST && b->memory != GPSAT_MEM_DEVICE) return fail(GPSAT_EINVAL, "bad memory flag");
-    if (!b->obs_off || !b->pred_off || !b->theta0 || !b->lo || !b->hi || !b->trainable)
-        return fail(GPSAT_EINVAL, "metadata pointer is NULL");
-    if (!b->theta || !b->nll || !b->status || !b->n_eval) return fail(GPSAT_EINVAL, "output pointer is NULL");
-    const int T = b->T, D = b->D, H = D + 2;
-    // ---- validate CSR offsets, find the largest tile
-    long long maxN = 0;
-    if (b->obs_off[0] != 0 || b->pred_off[0] != 0) return fail(GPSAT_EINVAL, "offsets must start at 0");
-    for (int t = 0; t < T; ++t) {
-        const long long n = b->obs_off[t + 1] - b->obs_off[t], p = b->pred_off[t + 1] - b->pred_off[t];
-        if (n < 0 || p < 0) return fail(GPSAT_EINVAL, "offsets must be non-decreasing");
-        maxN = std::max(maxN, n);
-    }
-    const long long sumN = b->obs_off[T], sumP = b->pred_off[T];
-    // optional full posterior covariance: one P_t x P_t block per tile
-    const bool want_cov = b->f_cov != nullptr;
-    long long sumC = 0, maxP = 0;
-    if (want_cov) {
-        if (!b->cov_off) return fail(GPSAT_EINVAL, "f_cov given without cov_off");
-        if (b->cov_off[0] != 0) return fail(GPSAT_EINVAL, "cov_off must start at 0");
-        for (int t = 0; t < T; ++t) {
-            const long long p = b->pred_off[t + 1] - b->pred_off[t];
-            if (b->cov_off[t + 1] - b->cov_off[t] != p * p) return fail(GPSAT_EINVAL, "cov_off[t+1]-cov_off[t] must equal P_t^2");
-            maxP = std::max(maxP, p);
-        }
-        sumC = b->cov_off[T];
-    }
-    if (maxN > gpsat_max_tile_obs(b->dtype, b->D))
-        return fail(GPSAT_EINVAL, "tile too large for the LDS of a CU: at most " + std::to_string(gpsat_max_tile_obs(b->dtype, b->D)) +
-                                      " observations per tile for this dtype and D (gpsat_max_tile_obs)");
-    if (sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
-    if (sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
-    for (int t = 0; t < T; ++t)
-        for (int i = 0; i < H; ++i) {
-            const double v = b->theta0[(size_t)t * H + i];
-            if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
-        }
-    // ---- multi-start bounded L-BFGS-B (gpsat_fit_predict_batch_ms)
-    const bool ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
-    const int S = ms ? ms->n_starts : 1;
-    std::vector<double> theta0_clipped, starts_clipped;
-    if (ms) {
-        if (S < 1) return fail(GPSAT_EINVAL, "multistart: n_starts must be >= 1");
-        if (ms->transform != GPSAT_TRANSFORM_LOG) return fail(GPSAT_EINVAL, "multistart: unknown transform (GPSAT_TRANSFORM_LOG only)");
-        if (S > 1 && !ms->starts) return fail(GPSAT_EINVAL, "multistart: starts is NULL with n_starts > 1");
-        if (b->optimiser == GPSAT_OPT_ADAM) return fail(GPSAT_EINVAL, "multistart: the optimiser must be L-BFGS-B or none");
-        for (int t = 0; t < T; ++t)
-            for (int i = 0; i < H; ++i) {
-                if (!b->trainable[i]) continue;
-                const double lo = b->lo[(size_t)t * H + i], hi = b->hi[(size_t)t * H + i];
-                if (!(lo > 0.0) || !(hi > 0.0) || !(lo <= hi))
-                    return fail(GPSAT_EINVAL, "multistart: the bounds of a trainable parameter must be positive with lo <= hi (log transform)");
-                if (S > 1 && (!std::isfinite(lo) || !std::isfinite(hi)))
-                    return fail(GPSAT_EINVAL, "multistart: restarts require that all bounds are finite");
-            }
-        if (S > 1)
-            for (size_t e = 0; e < (size_t)T * (S - 1) * H; ++e)
-                if (!(ms->starts[e] > 0.0) || !std::isfinite(ms->starts[e]))
-                    return fail(GPSAT_EINVAL, "multistart: starts must be finite and positive");
-        if (ms_on) {
-            // SciPy clips x0 into the bounds (_minimize_lbfgsb)
-            theta0_clipped.assign(b->theta0, b->theta0 + (size_t)T * H);
-            for (int t = 0; t < T; ++t)
-                for (int i = 0; i < H; ++i)
-                    if (b->trainable[i]) {
-                        double& v = theta0_clipped[(size_t)t * H + i];
-                        v = std::min(std::max(v, b->lo[(size_t)t * H + i]), b->hi[(size_t)t * H + i]);
-                    }
-        }
-    }
-    // the further starts likewise: L-BFGS-B works inside the box only
-    if (ms_on && S > 1) {
-        starts_clipped.assign(ms->starts, ms->starts + (size_t)T * (S - 1) * H);
-        for (int t = 0; t < T; ++t)
-            for (int k = 0; k < S - 1; ++k)
-                for (int i = 0; i < H; ++i)
-                    if (b->trainable[i]) {
-                        double& v = starts_clipped[((size_t)t * (S - 1) + k) * H + i];
-                        v = std::min(std::max(v, b->lo[(size_t)t * H + i]), b->hi[(size_t)t * H + i]);
-                    }
-    }
-    const double* theta0_host = ms_on ? theta0_clipped.data() : b->theta0;
-    const int bs = f64 ? 16 : 32;
-    const int NBmax = std::max(1, (int)((maxN + bs - 1) / bs));
-
-    HIP_TRY(hipSetDevice(h->device));
-    // ---- tile order: largest cost first (N^3), stable so equal tiles keep the reference order.  A multi-start batch costs
-    // S times as much per tile, alike for every tile: neither the order nor the slicing decision below changes with S.
-    std::vector<int> order(T);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) {
-        return (b->obs_off[a + 1] - b->obs_off[a]) > (b->obs_off[c + 1] - b->obs_off[c]);
-    });
-
-    // ---- device buffers
-    const size_t n_i64 = 3 * (size_t)(T + 1);
-    const int PCcov = want_cov ? std::max(1, (int)((maxP + bs - 1) / bs)) : 0;
-    const size_t n_f64 = 3 * (size_t)T * H;
-    int rc;
-    if ((rc = h->meta_i64.reserve(n_i64 * sizeof(long long)))) return rc;
-    if ((rc = h->meta_f64.reserve(n_f64 * sizeof(double)))) return rc;
-    if ((rc = h->meta_misc.reserve((size_t)T * sizeof(int) + 64 + 16))) return rc;
-    if ((rc = h->out_f64.reserve(((size_t)T * H * 2 + (size_t)T) * sizeof(double)))) return rc;
-    if ((rc = h->out_i32.reserve((size_t)T * 3 * sizeof(int)))) return rc;
-    // fp32: two 4-wave workgroups per CU while a workgroup's LDS fits twice; beyond that one 8-wave workgroup per CU
-    // (the 8-wave build of the same kernels), so that every SIMD still has two waves to overlap
-    // ... and launches with fewer tiles than CUs: every tile has a CU to itself, eight waves use it better than four, and
-    // the 8-wave build is the one with cooperative tiles
-    const bool w8 = !f64 && (gpsat::shared_bytes(D, NBmax) > 80 * 1024 || h->wg_per_cu == 1 || T < h->num_cu);
-    // fp64: the same rule with the 4-wave / 8-wave builds of the fp64 kernels
-    const bool d4 = f64 && gpsat::shared_bytes_f64_w4(D, NBmax) <= 80 * 1024 && h->wg_per_cu != 1;
-    const size_t wsf = f64 ? (d4 ? gpsat::workspace_doubles_per_wg_f64_w4(NBmax, PCcov) : gpsat::workspace_doubles_per_wg_f64(NBmax, PCcov))
-                           : (w8 ? gpsat::workspace_floats_per_wg_w8(NBmax, PCcov) : gpsat::workspace_floats_per_wg(NBmax, PCcov));
-    int grid = std::min(T, h->num_cu * (f64 ? 2 : h->wg_per_cu));
-    const size_t smem = f64 ? (d4 ? gpsat::shared_bytes_f64_w4(D, NBmax) : gpsat::shared_bytes_f64(D, NBmax))
-                            : (w8 ? gpsat::shared_bytes_w8(D, NBmax) : gpsat::shared_bytes(D, NBmax));
-    if (smem > 160 * 1024) return fail(GPSAT_EINVAL, "tile too large for LDS");
-    if (w8 || (f64 && !d4)) grid = std::min(grid, h->num_cu);
-    // teams (fp64 kernels, 8-wave build): with few large tiles, G workgroups run every tile together (gpsat_kernels_f64.hip)
-    int team = 1;
-    if (f64 && !d4 && NBmax >= 64 && 2 * T <= h->num_cu) team = std::min(16, h->num_cu / T);
-    if (const char* e = dev_env("GPSAT_DEBUG_TEAM")) { if (f64 && !d4) team = std::max(1, std::min(32, std::atoi(e))); }
-    if (h->force_solo) team = 1;
-    if (team > 1) grid = std::min(T, std::max(1, h->num_cu / team)) * team;
-    // cooperative tiles (fp32 kernels): a workgroup without a tile helps a running one (gpsat_coop.h).  With fewer tiles than
-    // resident workgroups the launch is widened by the helpers the large tiles can use.
-    bool coop = !f64;
-    int coop_min_nb = 12, coop_hdiv = 12;
-    int coop_force = 0;
-    if (const char* e = dev_env("GPSAT_DEBUG_COOP")) {           // developer: 0 = off, 2 = cooperative code path always
-        coop = coop && std::atoi(e) != 0;
-        coop_force = std::atoi(e) == 2;
-    }
-    if (const char* e = dev_env("GPSAT_DEBUG_COOP_XCD")) coop_force |= (std::atoi(e) & 3) << 2;   // developer: 1 same-XCD helpers only, 2 others only
-    if (const char* e = dev_env("GPSAT_DEBUG_COOP_MIN_NB")) coop_min_nb = std::max(2, std::atoi(e));
-    if (const char* e = dev_env("GPSAT_DEBUG_COOP_HDIV")) coop_hdiv = std::max(1, std::atoi(e));
-    // Helpers must be capacity that would otherwise idle.  8-wave build: one workgroup per CU, a workgroup without a tile
-    // leaves its CU empty -- always on.  4-wave build (two workgroups per CU): an idle workgroup's CU-mate already runs 1.4 x
-    // faster alone, and a helper takes that back (measured on BASELINE configs[1]: the helped tail is 2 % SLOWER) -- off; a
-    // launch with fewer tiles than CUs runs the 8-wave build anyway, widened to at most one workgroup per CU.
-    if (coop && !w8) coop = false;
-    if (coop) {
-        const int cap = h->num_cu;
-        long long want = grid;
-        for (int t = 0; t < T && want < cap; ++t) {
-            const int nb = (int)((b->obs_off[t + 1] - b->obs_off[t] + bs - 1) / bs);
-            if (nb >= coop_min_nb) want += std::min(7, std::max(1, nb / coop_hdiv));
-        }
-        if (T < cap) grid = (int)std::min<long long>(cap, want);
-    }
-    if (const char* e = dev_env("GPSAT_DEBUG_GRID")) grid = std::max(1, std::min(grid, std::atoi(e)));   // developer: fewer resident workgroups
-    if ((rc = h->ws.reserve((size_t)(grid / team) * wsf * esz))) return rc;      // one workspace per workgroup, or per team
-
-    const char *dX = nullptr, *dy = nullptr, *dXs = nullptr;
-    char *dfm = nullptr, *dfv = nullptr, *dyv = nullptr, *dcov = nullptr;
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    if (b->memory == GPSAT_MEM_HOST) {
-        const size_t in_e = (size_t)sumN * D + (size_t)sumN + (size_t)sumP * D;
-        if ((rc = h->bulk_in.reserve(std::max<size_t>(in_e, 1) * esz))) return rc;
-        if ((rc = h->bulk_out.reserve(std::max<size_t>((size_t)sumP * 3 + (size_t)sumC, 1) * esz))) return rc;
-        char* base = static_cast<char*>(h->bulk_in.p);
-        dX = base; dy = base + (size_t)sumN * D * esz; dXs = base + (size_t)sumN * (D + 1) * esz;
-        if (sumN > 0) {
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dX), b->X, (size_t)sumN * D * esz, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dy), b->y, (size_t)sumN * esz, hipMemcpyHostToDevice, h->stream));
-        }
-        if (sumP > 0)
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dXs), b->Xs, (size_t)sumP * D * esz, hipMemcpyHostToDevice, h->stream));
-        dfm = static_cast<char*>(h->bulk_out.p); dfv = dfm + (size_t)sumP * esz; dyv = dfv + (size_t)sumP * esz;
-        if (want_cov) dcov = dyv + (size_t)sumP * esz;
-    } else {
-        dcov = static_cast<char*>(b->f_cov);
-        dX = static_cast<const char*>(b->X); dy = static_cast<const char*>(b->y); dXs = static_cast<const char*>(b->Xs);
-        dfm = static_cast<char*>(b->f_mean); dfv = static_cast<char*>(b->f_var); dyv = static_cast<char*>(b->y_var);
-    }
-    long long* d_i64 = static_cast<long long*>(h->meta_i64.p);
-    HIP_TRY(hipMemcpyAsync(d_i64, b->obs_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_i64 + (T + 1), b->pred_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    if (want_cov)
-        HIP_TRY(hipMemcpyAsync(d_i64 + 2 * (T + 1), b->cov_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    double* d_f64 = static_cast<double*>(h->meta_f64.p);
-    HIP_TRY(hipMemcpyAsync(d_f64, theta0_host, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_f64 + (size_t)T * H, b->lo, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_f64 + 2 * (size_t)T * H, b->hi, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    unsigned char* d_misc = static_cast<unsigned char*>(h->meta_misc.p);
-    int* d_queue = reinterpret_cast<int*>(d_misc);            // 16 bytes reserved
-    unsigned char* d_train = d_misc + 16;                     // 64 bytes reserved
-    int* d_order = reinterpret_cast<int*>(d_misc + 16 + 64);
-    HIP_TRY(hipMemsetAsync(d_queue, 0, 16, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_train, b->trainable, (size_t)H, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
-
-    // ---- time slicing of the optimisation (fp32): with few tiles per resident workgroup, whole tiles as the scheduling unit
-    // leave the GPU half empty while the last ones finish (4096 tiles on 512 workgroups: 8 % of the launch).  Tiles of
-    // similar cost are therefore served in slices of ~4 evaluations of a 512-point tile (both precisions); a batch whose largest tile
-    // dominates keeps the largest-first run-to-completion order (its critical path must not wait in a queue).
-    int seg_cost = 0;
-    if (b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0) {
-        double sum_cost = 0.0, max_cost = 0.0;
-        for (int t = 0; t < T; ++t) {
-            const double nb = (double)((b->obs_off[t + 1] - b->obs_off[t] + bs - 1) / bs);
-            sum_cost += nb * nb * nb;
-            max_cost = std::max(max_cost, nb * nb * nb);
-        }
-        const double tiles_per_wg = (double)T / grid;
-        if (T > grid && max_cost * 4.0 * grid <= sum_cost && tiles_per_wg <= 64.0) seg_cost = 4 * (512 / bs) * (512 / bs) * (512 / bs);
-        // developer / tests: slice length in NB^3 units (0 = off, 1 = every evaluation), whatever the batch looks like
-        if (const char* e = dev_env("GPSAT_DEBUG_SEG")) seg_cost = std::max(0, std::atoi(e));
-        if (h->force_unsliced || team > 1) seg_cost = 0;
-    }
-    unsigned long long* d_ring = nullptr; int* d_ring_ctl = nullptr; unsigned* d_state = nullptr;
-    int ring_mask = 0;
-    const int state_words = f64 ? (d4 ? gpsat::state_words_f64_w4() : gpsat::state_words_f64())
-                                : (w8 ? gpsat::state_words_w8() : gpsat::state_words());
-    if (seg_cost > 0) {
-        size_t cap = 1; while (cap < (size_t)T + (size_t)grid + 1) cap <<= 1;
-        ring_mask = (int)(cap - 1);
-        if ((rc = h->ring.reserve(cap * sizeof(unsigned long long) + 256))) return rc;
-        if ((rc = h->state.reserve((size_t)T * state_words * sizeof(unsigned)))) return rc;
-        d_ring_ctl = static_cast<int*>(h->ring.p);
-        d_ring = reinterpret_cast<unsigned long long*>(static_cast<char*>(h->ring.p) + 256);
-        d_state = static_cast<unsigned*>(h->state.p);
-        std::vector<unsigned long long> init(cap, 0ull);
-        for (int i = 0; i < T; ++i) init[i] = ((unsigned long long)(i + 1) << 32) | (unsigned)order[i];
-        int ctl[64] = {0};
-        ctl[16] = T; ctl[32] = T;
-        HIP_TRY(hipMemcpyAsync(d_ring_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(d_ring, init.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));          // `init` and `ctl` are stack / local host memory
-    }
-
-    gpsat::KernelArgs a;
-    a.coop = nullptr; a.coop_live = nullptr; a.coop_min_nb = coop_min_nb; a.coop_hdiv = coop_hdiv; a.coop_force = coop_force;
-    if (coop) {
-        // [grid] control blocks of 1 KiB, zeroed every launch, then the count of unfinished tiles
-        const size_t cb = (size_t)grid * 1024;
-        if ((rc = h->coop.reserve(cb + 64))) return rc;
-        HIP_TRY(hipMemsetAsync(h->coop.p, 0, cb + 64, h->stream));
-        HIP_TRY(hipMemcpyAsync(static_cast<char*>(h->coop.p) + cb, &b->T, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        a.coop = h->coop.p;
-        a.coop_live = reinterpret_cast<int*>(static_cast<char*>(h->coop.p) + cb);
-    }
-    a.team_size = team; a.team_ctl = nullptr;
-    if (team > 1) {
-        const size_t tb = (size_t)(grid / team) * 256;
-        if ((rc = h->coop.reserve(tb))) return rc;
-        HIP_TRY(hipMemsetAsync(h->coop.p, 0, tb, h->stream));
-        a.team_ctl = h->coop.p;
-    }
-    a.ring = d_ring; a.ring_ctl = d_ring_ctl; a.state = d_state; a.ring_mask = ring_mask; a.state_words = state_words; a.seg_cost = seg_cost;
-    a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
-    a.max_ls = b->max_ls > 0 ? b->max_ls : 20;                                 // SciPy L-BFGS-B maxls
-    a.NBmax = NBmax;
-    // 0 = default (fp64: SciPy's factr*eps; fp32: its analogue above the fp32 noise floor); negative = criterion off
-    a.ftol = b->ftol > 0 ? b->ftol : (b->ftol < 0 ? -1.0 : (f64 ? 2.220446049250313e-9 : 1e-6));
-    a.gtol = b->gtol > 0 ? b->gtol : (b->gtol < 0 ? -1.0 : 1e-5);
-    a.adam_lr = b->adam_lr > 0 ? b->adam_lr : 0.1;
-    // relative resolution of the objective: fp32 rounding ~ cond(K) eps N reaches 2e-4 |f| on the reference's 1-D tutorial
-    // tile (cond ~ 2e4, docs/notebooks/1d_local_expert_model_part_2.ipynb); fp64: rounding level only
-    a.noise_rel = f64 ? 1e-12 : 1e-3;
-    a.obs_off = d_i64; a.pred_off = d_i64 + (T + 1);
-    a.theta0 = d_f64; a.lo = d_f64 + (size_t)T * H; a.hi = d_f64 + 2 * (size_t)T * H;
-    a.trainable = d_train;
-    a.X = reinterpret_cast<const float*>(dX); a.y = reinterpret_cast<const float*>(dy); a.Xs = reinterpret_cast<const float*>(dXs);
-    double* d_out = static_cast<double*>(h->out_f64.p);
-    a.theta = d_out; a.nll = d_out + (size_t)T * H;
-    a.grad = b->grad ? d_out + (size_t)T * H + T : nullptr;
-    int* d_oi = static_cast<int*>(h->out_i32.p);
-    a.status = d_oi; a.n_eval = d_oi + T; a.n_iter = d_oi + 2 * (size_t)T;
-    a.f_mean = reinterpret_cast<float*>(dfm); a.f_var = reinterpret_cast<float*>(dfv); a.y_var = reinterpret_cast<float*>(dyv);
-    a.order = d_order; a.queue = d_queue;
-    a.ws = static_cast<float*>(h->ws.p); a.ws_stride = wsf;     // fp64: the kernel reinterprets ws as doubles
-    a.prof = nullptr;
-    a.cov_off = want_cov ? d_i64 + 2 * (T + 1) : nullptr;
-    a.f_cov = want_cov ? reinterpret_cast<float*>(dcov) : nullptr;
-    a.PCmax = PCcov;
-    a.dump = nullptr; a.dump_stride = 0;
-    if (ms_on) {
-        const size_t n_state = (size_t)T * gpsat::MS_WORDS, n_starts = (size_t)T * (S - 1) * H, n_f = (size_t)T * S;
-        if ((rc = h->ms.reserve((n_state + n_starts + n_f) * sizeof(double)))) return rc;
-        // state, then NaN in f_start for tiles that run no start (no observations)
-        std::vector<double> init(n_state + n_f, 0.0);
-        std::fill(init.begin() + n_state, init.end(), std::numeric_limits<double>::quiet_NaN());
-        for (int t = 0; t < T; ++t) {
-            double* st = init.data() + (size_t)t * gpsat::MS_WORDS;
-            st[1] = std::numeric_limits<double>::infinity();     // best f
-            st[4] = -1.0;                                         // best start: none yet
-            for (int i = 0; i < H; ++i) st[5 + i] = std::log(theta0_host[(size_t)t * H + i]);
-        }
-        double* d_ms = static_cast<double*>(h->ms.p);
-        HIP_TRY(hipMemcpyAsync(d_ms, init.data(), n_state * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (n_starts) HIP_TRY(hipMemcpyAsync(d_ms + n_state, starts_clipped.data(), n_starts * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(d_ms + n_state + n_starts, init.data() + n_state, n_f * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));          // `init` is local host memory
-        a.ms_S = S; a.ms_state = d_ms; a.ms_starts = d_ms + n_state; a.ms_fout = d_ms + n_state + n_starts;
-    }
-    // ---- deferred predictions (fp32 4-wave build, time-sliced, no full covariance): a tile that finishes while others wait
-    // leaves its prediction in a snapshot slot for the workgroups that idle at the end of the launch (gpsat_ring.h).  One slot
-    // per tile up to a fixed budget; tiles past it predict inline.
-    a.pq = nullptr; a.pq_ctl = nullptr; a.cu_busy = nullptr; a.pq_snap = nullptr; a.pq_stride = 0; a.pq_slots = 0;
-    if (seg_cost > 0 && !f64 && !w8 && !want_cov && sumP > 0) {
-        const size_t stride = gpsat::pq_floats_per_slot(D, NBmax);
-        const size_t budget = (size_t)5 << 29;                    // 2.5 GiB: every tile of a 4096-tile launch of N = 500
-        long long slots = std::min<long long>(T, (long long)(budget / (stride * sizeof(float))));
-        // developer / tests: 0 = every prediction inline, n = at most n snapshot slots
-        if (const char* e = dev_env("GPSAT_DEBUG_DEFER")) slots = std::min<long long>(slots, std::max(0, std::atoi(e)));
-        // (head rounded to 256 B: the snapshots move as 16-B block accesses)
-        const size_t head = (256 + 2048 * sizeof(int) + (size_t)slots * sizeof(unsigned long long) + 255) & ~size_t(255);
-        if (slots > 0 && h->pq.reserve(head + (size_t)slots * stride * sizeof(float)) != GPSAT_OK) {
-            // no memory for the pool: every prediction inline (the same results), not an error
-            g_err.clear();
-            (void)hipGetLastError();
-            slots = 0;
-        }
-        if (slots > 0) {
-            HIP_TRY(hipMemsetAsync(h->pq.p, 0, head, h->stream));
-            char* p = static_cast<char*>(h->pq.p);
-            a.pq_ctl = reinterpret_cast<int*>(p);
-            a.cu_busy = reinterpret_cast<int*>(p + 256);
-            a.pq = reinterpret_cast<unsigned long long*>(p + 256 + 2048 * sizeof(int));
-            a.pq_snap = reinterpret_cast<float*>(p + head);
-            a.pq_stride = stride; a.pq_slots = (int)slots;
-        }
-    }
-#ifdef GPSAT_DUMP
-    if (h->dump_dev && !f64) {
-        const size_t need = ((size_t)NBmax * NBmax + NBmax) * 1024 + 2 * (size_t)NBmax * 32 + 16 + 8 * 1024;
-        if (h->dump_stride < need) return fail(GPSAT_EINVAL, "dump stride too small: need " + std::to_string(need) + " floats per tile");
-        a.dump = h->dump_dev; a.dump_stride = h->dump_stride;
-    }
-#endif
-#ifdef GPSAT_PROFILE
-    if ((rc = h->prof.reserve(sizeof(h->prof_host)))) return rc;
-    HIP_TRY(hipMemsetAsync(h->prof.p, 0, sizeof(h->prof_host), h->stream));
-    a.prof = static_cast<unsigned long long*>(h->prof.p);
-#endif
-
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(f64 ? (d4 ? gpsat::launch_tiles_f64_w4(D, a, grid, smem, h->stream) : gpsat::launch_tiles_f64(D, a, grid, smem, h->stream))
-                : (w8 ? gpsat::launch_tiles_w8(D, a, grid, smem, h->stream) : gpsat::launch_tiles(D, a, grid, smem, h->stream)));
-    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-
-    HIP_TRY(hipMemcpyAsync(b->theta, a.theta, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->nll, a.nll, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, a.grad, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->status, a.status, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->n_eval, a.n_eval, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (b->n_iter) HIP_TRY(hipMemcpyAsync(b->n_iter, a.n_iter, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (ms_on && ms->f_start)
-        HIP_TRY(hipMemcpyAsync(ms->f_start, a.ms_fout, (size_t)T * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (b->memory == GPSAT_MEM_HOST && sumP > 0) {
-        HIP_TRY(hipMemcpyAsync(b->f_mean, dfm, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(b->f_var, dfv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(b->y_var, dyv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (b->memory == GPSAT_MEM_HOST && want_cov && sumC > 0)
-        HIP_TRY(hipMemcpyAsync(b->f_cov, dcov, (size_t)sumC * esz, hipMemcpyDeviceToHost, h->stream));
-#ifdef GPSAT_PROFILE
-    HIP_TRY(hipMemcpyAsync(h->prof_host, h->prof.p, sizeof(h->prof_host), hipMemcpyDeviceToHost, h->stream));
-#endif
-    std::vector<int> team_host;
-    if (team > 1) {
-        team_host.resize((size_t)(grid / team) * 64);
-        HIP_TRY(hipMemcpyAsync(team_host.data(), h->coop.p, team_host.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    }
-    std::vector<int> coop_host;
-    if (coop && dev_env("GPSAT_DEBUG_COOP_STATS")) {
-        coop_host.resize((size_t)grid * 256);
-        HIP_TRY(hipMemcpyAsync(coop_host.data(), h->coop.p, (size_t)grid * 1024, hipMemcpyDeviceToHost, h->stream));
-    }
-    int pq_taken = -1;
-    if (a.pq_ctl && dev_env("GPSAT_DEBUG_DEFER_STATS"))
-        HIP_TRY(hipMemcpyAsync(&pq_taken, a.pq_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    int unfinished = 0;
-    if (seg_cost > 0) HIP_TRY(hipMemcpyAsync(&unfinished, d_ring_ctl + 32, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!coop_host.empty()) {
-        long long st[8] = {0};
-        for (int g = 0; g < grid; ++g) for (int i = 0; i < 8; ++i) st[i] += coop_host[(size_t)g * 256 + 32 + GPSAT_PT_MAXNB + i];
-        std::fprintf(stderr, "gpsat coop: grid %d T %d: cooperative evaluations %lld, helper phases %lld, helper groups (sweep) %lld, "
-                             "flag waits given up %lld, owner waits given up %lld, pivot failures %lld, helper unwinds %lld\n",
-                     grid, T, st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
-    }
-    if (dev_env("GPSAT_DEBUG_DEFER_STATS"))       // developer / tests: how many predictions were deferred
-        std::fprintf(stderr, "gpsat defer: T %d: deferred predictions %d of %d snapshot slots\n", T,
-                     pq_taken < 0 ? 0 : std::min(pq_taken, a.pq_slots), a.pq_slots);
-    if (!team_host.empty() && dev_env("GPSAT_DEBUG_TEAM_STATS"))
-        std::fprintf(stderr, "gpsat team 0 (size %d), factorisation, owner thread 0, s_memtime ticks: own work of (A) %d, (A) wait + barrier %d, (B) + barrier %d, "
-                             "(C) + barrier %d\n", team, team_host[24], team_host[25], team_host[26], team_host[27]);
-    for (size_t g = 0; g < team_host.size() / 64; ++g) {
-        if (team_host[g * 64 + 5]) {          // TeamCtl::timeout: a team barrier gave up (never by design) -- run the batch again, one workgroup per tile
-            std::fprintf(stderr, "gpsat: a team barrier gave up; re-running the batch with one workgroup per tile\n");
-            h->force_solo = true;
-            const int rc2 = fit_predict_impl(h, b, ms);
-            h->force_solo = false;
-            return rc2;
-        }
-    }
-    if (unfinished != 0) {
-        // A queue anomaly (an escape hatch of ring_pop taken: gpsat_ring.h) must not cost the caller the batch: run it again
-        // with every tile run to completion from the plain queue (same results: slicing does not change a bit of them).
-        if (h->force_unsliced) return fail(GPSAT_EHIP, "tile queue ended with " + std::to_string(unfinished) + " unfinished tiles");
-        std::fprintf(stderr, "gpsat: time-sliced tile queue ended with %d unfinished tiles; re-running the batch unsliced\n", unfinished);
-        h->force_unsliced = true;
-        const int rc2 = fit_predict_impl(h, b, ms);
-        h->force_unsliced = false;
-        return rc2;
-    }
-    float km = 0.f, tm = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
-    h->last_kernel_ms = km;
-    h->last_total_ms = tm;
-    return GPSAT_OK;
+    return fit_predict(h, b, ms);
 }
 
 #ifdef GPSAT_DUMP
@@ -645,49 +697,34 @@ int gpsat_max_inducing(int dtype, int D) {
 
 int gpsat_sgpr_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b, const gpsat_sparse* sp) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_sgpr_fit_predict_batch: NULL handle or batch");
-    h->selc.total = -1;
     if (!sp || !sp->z_off) return fail(GPSAT_EINVAL, "gpsat_sgpr_fit_predict_batch: NULL sparse description or z_off");
-    if (b->T < 0) return fail(GPSAT_EINVAL, "T < 0");
     if (b->T == 0) return GPSAT_OK;
-    if (b->D < 1 || b->D > 4) return fail(GPSAT_EINVAL, "D must be 1..4 in this build");
-    if (b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "sparse GP experts are built for GPSAT_F64 only");
+    BatchDims d;
+    int rc;
+    if ((rc = check_batch(b, true, d))) return rc;
     if (b->cov_off || b->f_cov) return fail(GPSAT_EINVAL, "sparse GP experts do not return the full covariance: cov_off / f_cov must be NULL");
-    if (b->kernel < 0 || b->kernel > 3) return fail(GPSAT_EINVAL, "unknown kernel id");
-    if (b->optimiser < 0 || b->optimiser > 2) return fail(GPSAT_EINVAL, "unknown optimiser id");
-    if (b->memory != GPSAT_MEM_HOST && b->memory != GPSAT_MEM_DEVICE) return fail(GPSAT_EINVAL, "bad memory flag");
-    if (!b->obs_off || !b->pred_off || !b->theta0 || !b->lo || !b->hi || !b->trainable)
-        return fail(GPSAT_EINVAL, "metadata pointer is NULL");
-    if (!b->theta || !b->nll || !b->status || !b->n_eval) return fail(GPSAT_EINVAL, "output pointer is NULL");
     if (!(sp->jitter >= 0.0) || !std::isfinite(sp->jitter)) return fail(GPSAT_EINVAL, "jitter must be finite and >= 0");
-    const int T = b->T, D = b->D, H = D + 2;
+    const int T = b->T, D = b->D;
     const int mlim = gpsat_max_inducing(b->dtype, D);
-    if (b->obs_off[0] != 0 || b->pred_off[0] != 0 || sp->z_off[0] != 0) return fail(GPSAT_EINVAL, "offsets must start at 0");
+    if (sp->z_off[0] != 0) return fail(GPSAT_EINVAL, "offsets must start at 0");
     int Mmax = 1;
     for (int t = 0; t < T; ++t) {
         const long long n = b->obs_off[t + 1] - b->obs_off[t], p = b->pred_off[t + 1] - b->pred_off[t];
         const long long m = sp->z_off[t + 1] - sp->z_off[t];
-        if (n < 0 || p < 0) return fail(GPSAT_EINVAL, "offsets must be non-decreasing");
         if (n > 0x7fffffffLL || p > 0x7fffffffLL) return fail(GPSAT_EINVAL, "a tile holds more than 2^31-1 rows");
         if (m < 1 || m > mlim)
             return fail(GPSAT_EINVAL, "every tile needs 1.." + std::to_string(mlim) + " inducing points (gpsat_max_inducing); tile " +
                                           std::to_string(t) + " has " + std::to_string(m));
         Mmax = std::max(Mmax, (int)m);
     }
-    const long long sumN = b->obs_off[T], sumP = b->pred_off[T], sumM = sp->z_off[T];
+    d.sumM = sp->z_off[T];
     if (!sp->Z) return fail(GPSAT_EINVAL, "Z is NULL");
-    if (sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
-    if (sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
-    for (int t = 0; t < T; ++t)
-        for (int i = 0; i < H; ++i) {
-            const double v = b->theta0[(size_t)t * H + i];
-            if (!(v > 0.0) || !std::isfinite(v)) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
-        }
-    const size_t esz = sizeof(double);
+    if ((rc = check_batch_data(b, d))) return rc;
     const size_t smem = gpsat::sgpr_shared_bytes(D, Mmax);
     if (smem > 160 * 1024) return fail(GPSAT_EINVAL, "inducing points do not fit the LDS");
 
-    HIP_TRY(hipSetDevice(h->device));
-    // tile order: largest cost first (N M^2), stable
+    if ((rc = begin_call(h))) return rc;
+    // tile order: largest cost first (N M^2), stable.  Pageable host memory that a copy reads: alive until the final synchronise
     std::vector<int> order(T);
     std::iota(order.begin(), order.end(), 0);
     auto cost = [&](int t) {
@@ -698,99 +735,27 @@ int gpsat_sgpr_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b, const gp
     // one workgroup per CU; the workspaces together stay below 16 GiB
     const size_t wsd = gpsat::sgpr_workspace_doubles_per_wg(D, Mmax);
     int grid = std::min(T, h->num_cu);
-    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)16 << 30) / (wsd * esz)));
-    int rc;
-    if ((rc = h->meta_i64.reserve(3 * (size_t)(T + 1) * sizeof(long long)))) return rc;
-    if ((rc = h->meta_f64.reserve(3 * (size_t)T * H * sizeof(double)))) return rc;
-    if ((rc = h->meta_misc.reserve((size_t)T * sizeof(int) + 64 + 16))) return rc;
-    if ((rc = h->out_f64.reserve(((size_t)T * H * 2 + (size_t)T) * sizeof(double)))) return rc;
-    if ((rc = h->out_i32.reserve((size_t)T * 3 * sizeof(int)))) return rc;
-    if ((rc = h->ws.reserve((size_t)grid * wsd * esz))) return rc;
-
-    const char *dX = nullptr, *dy = nullptr, *dXs = nullptr, *dZ = nullptr;
-    char *dfm = nullptr, *dfv = nullptr, *dyv = nullptr;
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    if (b->memory == GPSAT_MEM_HOST) {
-        const size_t in_e = (size_t)sumN * D + (size_t)sumN + (size_t)sumP * D + (size_t)sumM * D;
-        if ((rc = h->bulk_in.reserve(std::max<size_t>(in_e, 1) * esz))) return rc;
-        if ((rc = h->bulk_out.reserve(std::max<size_t>((size_t)sumP * 3, 1) * esz))) return rc;
-        char* base = static_cast<char*>(h->bulk_in.p);
-        dX = base; dy = dX + (size_t)sumN * D * esz; dXs = dy + (size_t)sumN * esz; dZ = dXs + (size_t)sumP * D * esz;
-        if (sumN > 0) {
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dX), b->X, (size_t)sumN * D * esz, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dy), b->y, (size_t)sumN * esz, hipMemcpyHostToDevice, h->stream));
-        }
-        if (sumP > 0)
-            HIP_TRY(hipMemcpyAsync(const_cast<char*>(dXs), b->Xs, (size_t)sumP * D * esz, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(const_cast<char*>(dZ), sp->Z, (size_t)sumM * D * esz, hipMemcpyHostToDevice, h->stream));
-        dfm = static_cast<char*>(h->bulk_out.p); dfv = dfm + (size_t)sumP * esz; dyv = dfv + (size_t)sumP * esz;
-    } else {
-        dX = static_cast<const char*>(b->X); dy = static_cast<const char*>(b->y); dXs = static_cast<const char*>(b->Xs);
-        dZ = static_cast<const char*>(sp->Z);
-        dfm = static_cast<char*>(b->f_mean); dfv = static_cast<char*>(b->f_var); dyv = static_cast<char*>(b->y_var);
-    }
-    long long* d_i64 = static_cast<long long*>(h->meta_i64.p);
-    HIP_TRY(hipMemcpyAsync(d_i64, b->obs_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_i64 + (T + 1), b->pred_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_i64 + 2 * (T + 1), sp->z_off, (size_t)(T + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    double* d_f64 = static_cast<double*>(h->meta_f64.p);
-    HIP_TRY(hipMemcpyAsync(d_f64, b->theta0, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_f64 + (size_t)T * H, b->lo, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_f64 + 2 * (size_t)T * H, b->hi, (size_t)T * H * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    unsigned char* d_misc = static_cast<unsigned char*>(h->meta_misc.p);
-    int* d_queue = reinterpret_cast<int*>(d_misc);
-    unsigned char* d_train = d_misc + 16;
-    int* d_order = reinterpret_cast<int*>(d_misc + 16 + 64);
-    HIP_TRY(hipMemsetAsync(d_queue, 0, 16, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_train, b->trainable, (size_t)H, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)16 << 30) / (wsd * sizeof(double))));
+    Staged s;
+    if ((rc = stage_batch(h, b, d, b->theta0, order, sp->z_off, sp->Z, (size_t)grid * wsd * sizeof(double), s))) return rc;
 
     gpsat::SgprArgs a;
-    a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
-    a.max_ls = b->max_ls > 0 ? b->max_ls : 20;
+    fill_common_args(a, b, s);
     a.Mmax = Mmax;
-    a.ftol = b->ftol > 0 ? b->ftol : (b->ftol < 0 ? -1.0 : 2.220446049250313e-9);
-    a.gtol = b->gtol > 0 ? b->gtol : (b->gtol < 0 ? -1.0 : 1e-5);
-    a.adam_lr = b->adam_lr > 0 ? b->adam_lr : 0.1;
-    a.noise_rel = 1e-12;
     a.jitter = sp->jitter > 0.0 ? sp->jitter : 1e-6;
-    a.obs_off = d_i64; a.pred_off = d_i64 + (T + 1); a.z_off = d_i64 + 2 * (T + 1);
-    a.theta0 = d_f64; a.lo = d_f64 + (size_t)T * H; a.hi = d_f64 + 2 * (size_t)T * H;
-    a.trainable = d_train;
-    a.X = reinterpret_cast<const double*>(dX); a.y = reinterpret_cast<const double*>(dy);
-    a.Xs = reinterpret_cast<const double*>(dXs); a.Z = reinterpret_cast<const double*>(dZ);
-    double* d_out = static_cast<double*>(h->out_f64.p);
-    a.theta = d_out; a.nll = d_out + (size_t)T * H;
-    a.grad = b->grad ? d_out + (size_t)T * H + T : nullptr;
-    int* d_oi = static_cast<int*>(h->out_i32.p);
-    a.status = d_oi; a.n_eval = d_oi + T; a.n_iter = d_oi + 2 * (size_t)T;
-    a.f_mean = reinterpret_cast<double*>(dfm); a.f_var = reinterpret_cast<double*>(dfv); a.y_var = reinterpret_cast<double*>(dyv);
-    a.order = d_order; a.queue = d_queue;
+    a.z_off = s.i64 + 2 * (T + 1);
+    a.Z = reinterpret_cast<const double*>(s.Z);
     a.ws = static_cast<double*>(h->ws.p); a.ws_stride = wsd;
 
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     HIP_TRY(gpsat::launch_sgpr(D, a, grid, smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    HIP_TRY(hipMemcpyAsync(b->theta, a.theta, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->nll, a.nll, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, a.grad, (size_t)T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->status, a.status, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(b->n_eval, a.n_eval, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (b->n_iter) HIP_TRY(hipMemcpyAsync(b->n_iter, a.n_iter, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (b->memory == GPSAT_MEM_HOST && sumP > 0) {
-        HIP_TRY(hipMemcpyAsync(b->f_mean, dfm, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(b->f_var, dfv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(b->y_var, dyv, (size_t)sumP * esz, hipMemcpyDeviceToHost, h->stream));
-    }
+    if ((rc = fetch_batch(h, b, d, s))) return rc;
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    float km = 0.f, tm = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
-    h->last_kernel_ms = km;
-    h->last_total_ms = tm;
-    return GPSAT_OK;
+    return record_timing(h);
 }
+
 
 int gpsat_select_batch(gpsat_handle* h, const gpsat_select_spec* sp, int64_t M, int32_t C, const double* points,
                        int32_t T, const double* refs, int64_t* off, int32_t* idx, int64_t capacity) {
@@ -839,13 +804,12 @@ int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t 
         h->selc.total = -1;
         std::memcpy(off, h->selc.off.data(), (size_t)(T + 1) * sizeof(int64_t));
         if (capacity < total) return fail(GPSAT_EINVAL, "gpsat_select_batch: idx capacity too small (see off[T])");
-        HIP_TRY(hipSetDevice(h->device));
+        if (int rc0 = begin_call(h)) return rc0;
         if (total > 0) HIP_TRY(hipMemcpy(idx, h->selc.d_result, (size_t)total * sizeof(int), hipMemcpyDeviceToHost));
         return GPSAT_OK;
     }
-    h->selc.total = -1;
-    HIP_TRY(hipSetDevice(h->device));
     int rc;
+    if ((rc = begin_call(h))) return rc;
     if ((rc = h->sel_pts.reserve(std::max<size_t>((size_t)M * C, 1) * sizeof(double)))) return rc;
     if ((rc = h->sel_refs.reserve((size_t)T * C * sizeof(double)))) return rc;
     // row chunks: enough workgroups to fill the chip (T/32 workgroups per chunk), chunk a multiple of 64 rows
@@ -988,11 +952,7 @@ int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t 
     }
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    float km = 0.f, tm = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));      // count + scan round trip + fill
-    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
-    h->last_kernel_ms = km;
-    h->last_total_ms = tm;
+    if ((rc = record_timing(h))) return rc;                     // kernel time: count + scan round trip + fill
     if (!idx) {
         // sizes asked for: the indices stay on the device for the call that follows with the same arguments
         h->selc.pts = points; h->selc.refs = refs; h->selc.M = M; h->selc.C = C; h->selc.T = T; h->selc.sp = *sp;
@@ -1037,9 +997,8 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
                 return fail(GPSAT_EINVAL, "gpsat_bin_batch: gid[" + std::to_string(i) + "] = " + std::to_string(gid[i]) + " is not in 0.." + std::to_string(G - 1));
     int n_stat = 0;
     for (uint32_t b = 1; b <= GPSAT_BIN_MEDIAN; b <<= 1) n_stat += (stats & b) ? 1 : 0;
-    h->selc.total = -1;
-    HIP_TRY(hipSetDevice(h->device));
     int rc;
+    if ((rc = begin_call(h))) return rc;
     const size_t nR = (size_t)R;
     const size_t edge_bytes = ((size_t)(nx + (two_d ? ny : 0)) * sizeof(double) + 255) & ~size_t(255);
     if ((rc = h->bin_in.reserve(edge_bytes + (two_d ? 3 : 2) * nR * sizeof(double) + nR * sizeof(int)))) return rc;
@@ -1119,11 +1078,7 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
     }
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    float km = 0.f, tm = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&tm, h->ev[0], h->ev[3]));
-    h->last_kernel_ms = km;
-    h->last_total_ms = tm;
+    if ((rc = record_timing(h))) return rc;
     if (capacity < nc) return fail(GPSAT_EINVAL, "gpsat_bin_batch: capacity " + std::to_string(capacity) + " < n_cells " + std::to_string(nc));
     return GPSAT_OK;
 }
@@ -1132,10 +1087,9 @@ int gpsat_smooth_batch(gpsat_handle* h, int32_t T, const double* x, const double
                        double l_y, double* out) {
     if (!h || T < 0 || (T > 0 && (!x || !y || !vals || !out))) return fail(GPSAT_EINVAL, "gpsat_smooth_batch: bad argument");
     if (!(l_x > 0.0) || !(l_y > 0.0)) return fail(GPSAT_EINVAL, "gpsat_smooth_batch: length scales must be positive");
-    h->selc.total = -1;
     if (T == 0) return GPSAT_OK;
-    HIP_TRY(hipSetDevice(h->device));
     int rc;
+    if ((rc = begin_call(h))) return rc;
     if ((rc = h->sel_pts.reserve((size_t)4 * T * sizeof(double)))) return rc;
     double* d = static_cast<double*>(h->sel_pts.p);
     HIP_TRY(hipMemcpyAsync(d, x, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1146,10 +1100,7 @@ int gpsat_smooth_batch(gpsat_handle* h, int32_t T, const double* x, const double
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     HIP_TRY(hipMemcpyAsync(out, d + 3 * (size_t)T, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    float km = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
-    h->last_kernel_ms = km; h->last_total_ms = km;
-    return GPSAT_OK;
+    return record_timing(h, 1, 2);                              // no ev[0] / ev[3] here: the total is the kernel time
 }
 
 int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_t nvars, const int64_t* seg,
@@ -1161,8 +1112,8 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     if (G == 0) return GPSAT_OK;
     if (!seg || !pred || !xprt || !vals || !out) return fail(GPSAT_EINVAL, "gpsat_glue_batch: NULL argument");
     if (seg[0] != 0 || seg[G] != R) return fail(GPSAT_EINVAL, "gpsat_glue_batch: seg must run from 0 to R");
-    HIP_TRY(hipSetDevice(h->device));
     int rc;
+    if ((rc = begin_call(h))) return rc;
     const size_t nd = (size_t)(2 * ndim + nvars + 1) * R + (size_t)nvars * G;
     if ((rc = h->sel_pts.reserve(std::max<size_t>(nd, 1) * sizeof(double)))) return rc;
     if ((rc = h->sel_cnt.reserve((size_t)(G + 1) * sizeof(long long)))) return rc;
@@ -1178,10 +1129,7 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)nvars * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    float km = 0.f;
-    HIP_TRY(hipEventElapsedTime(&km, h->ev[1], h->ev[2]));
-    h->last_kernel_ms = km; h->last_total_ms = km;
-    return GPSAT_OK;
+    return record_timing(h, 1, 2);                              // no ev[0] / ev[3] here: the total is the kernel time
 }
 
 #ifdef GPSAT_PROFILE

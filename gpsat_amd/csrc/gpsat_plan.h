@@ -1,0 +1,156 @@
+// gpsat_plan.h -- the launch plan of gpsat_fit_predict_batch: which of the four kernel builds runs a batch, on what grid, with
+// teams, cooperative tiles, time slicing or the deferred-prediction pool.  plan_tiles() is a pure function of host data (no HIP
+// call, no handle, no device allocation), so every launch rule can be exercised without a GPU (tests/test_abi.py calls it
+// through its exported symbol).  Part of gpsat_capi.cpp's translation unit: include it nowhere else.
+#ifndef GPSAT_PLAN_H
+#define GPSAT_PLAN_H
+#include <algorithm>
+
+#include "gpsat_hip.h"
+#include "gpsat_kernels.h"
+
+namespace gpsat {
+
+// The four builds of the tile kernels behind one interface (gpsat_kernels.h declares the functions).
+struct Build {
+    size_t (*shared_bytes)(int D, int NBmax);
+    size_t (*workspace_per_wg)(int NBmax, int PCcov);         // floats (fp32 builds) or doubles (fp64 builds)
+    int (*state_words)();
+    hipError_t (*launch)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+    size_t (*pq_floats_per_slot)(int D, int NBmax);           // nullptr: the build has no deferred predictions
+};
+enum { BUILD_F32_W4 = 0, BUILD_F32_W8 = 1, BUILD_F64_W8 = 2, BUILD_F64_W4 = 3 };
+const Build builds[4] = {
+    {shared_bytes, workspace_floats_per_wg, state_words, launch_tiles, pq_floats_per_slot},
+    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, launch_tiles_w8, nullptr},
+    {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, launch_tiles_f64, nullptr},
+    {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, launch_tiles_f64_w4, nullptr},
+};
+
+// One developer knob (GPSAT_DEBUG_*, read through dev_env() only): whether it is set, and atoi of its text.
+struct Knob { int set = 0, v = 0; };
+struct DevKnobs { Knob team, coop, coop_xcd, coop_min_nb, coop_hdiv, grid, seg, defer; };
+
+// All plain data (ints and one pointer), so that a test can fill it through ctypes.
+struct PlanInput {
+    int T, D, f64;
+    const int64_t* obs_off;       // [T+1] host
+    long long maxP;               // largest prediction count of a tile (read with want_cov only)
+    int want_cov, has_pred;       // full covariance asked for; any prediction point at all
+    int optimiser, max_iter;
+    int num_cu, wg_per_cu;        // of the handle
+    int solo, unsliced;           // the two reruns: one workgroup per tile after a team barrier gave up; no time slicing
+    DevKnobs knobs;
+};
+
+struct TilePlan {
+    int build;                    // index into builds[]
+    int NBmax, PCcov, grid, team;
+    int coop, coop_min_nb, coop_hdiv, coop_force;
+    int seg_cost, state_words;
+    int pq_slots;                 // deferred-prediction snapshot slots wanted (0: every prediction inline)
+    size_t smem, ws_stride;       // LDS bytes; workspace elements per workgroup (or team)
+    size_t ring_cap;              // entries of the time-slicing ring (0 when seg_cost == 0)
+    size_t pq_stride;             // floats per snapshot slot
+};
+
+// false: the largest tile does not fit the LDS of a CU in the build the rules pick
+bool plan_tiles(const PlanInput& in, TilePlan& p) {
+    const int T = in.T, D = in.D, num_cu = in.num_cu;
+    const bool f64 = in.f64 != 0;
+    const DevKnobs& k = in.knobs;
+    const int bs = f64 ? 16 : 32;
+    long long maxN = 0;
+    for (int t = 0; t < T; ++t) maxN = std::max<long long>(maxN, in.obs_off[t + 1] - in.obs_off[t]);
+    const int NBmax = std::max(1, (int)((maxN + bs - 1) / bs));
+    const int PCcov = in.want_cov ? std::max(1, (int)((in.maxP + bs - 1) / bs)) : 0;
+    // fp32: two 4-wave workgroups per CU while a workgroup's LDS fits twice; beyond that one 8-wave workgroup per CU
+    // (the 8-wave build of the same kernels), so that every SIMD still has two waves to overlap
+    // ... and launches with fewer tiles than CUs: every tile has a CU to itself, eight waves use it better than four, and
+    // the 8-wave build is the one with cooperative tiles
+    const bool w8 = !f64 && (builds[BUILD_F32_W4].shared_bytes(D, NBmax) > 80 * 1024 || in.wg_per_cu == 1 || T < num_cu);
+    // fp64: the same rule with the 4-wave / 8-wave builds of the fp64 kernels
+    const bool d4 = f64 && builds[BUILD_F64_W4].shared_bytes(D, NBmax) <= 80 * 1024 && in.wg_per_cu != 1;
+    p.build = f64 ? (d4 ? BUILD_F64_W4 : BUILD_F64_W8) : (w8 ? BUILD_F32_W8 : BUILD_F32_W4);
+    const Build& bd = builds[p.build];
+    p.NBmax = NBmax; p.PCcov = PCcov;
+    p.ws_stride = bd.workspace_per_wg(NBmax, PCcov);
+    p.state_words = bd.state_words();
+    int grid = std::min(T, num_cu * (f64 ? 2 : in.wg_per_cu));
+    p.smem = bd.shared_bytes(D, NBmax);
+    if (p.smem > 160 * 1024) return false;
+    if (w8 || (f64 && !d4)) grid = std::min(grid, num_cu);
+    // teams (fp64 kernels, 8-wave build): with few large tiles, G workgroups run every tile together (gpsat_kernels_f64.hip)
+    int team = 1;
+    if (f64 && !d4 && NBmax >= 64 && 2 * T <= num_cu) team = std::min(16, num_cu / T);
+    if (k.team.set) { if (f64 && !d4) team = std::max(1, std::min(32, k.team.v)); }
+    if (in.solo) team = 1;
+    if (team > 1) grid = std::min(T, std::max(1, num_cu / team)) * team;
+    // cooperative tiles (fp32 kernels): a workgroup without a tile helps a running one (gpsat_coop.h).  With fewer tiles than
+    // resident workgroups the launch is widened by the helpers the large tiles can use.
+    bool coop = !f64;
+    p.coop_min_nb = 12; p.coop_hdiv = 12; p.coop_force = 0;
+    if (k.coop.set) {                                            // developer: 0 = off, 2 = cooperative code path always
+        coop = coop && k.coop.v != 0;
+        p.coop_force = k.coop.v == 2;
+    }
+    if (k.coop_xcd.set) p.coop_force |= (k.coop_xcd.v & 3) << 2;   // developer: 1 same-XCD helpers only, 2 others only
+    if (k.coop_min_nb.set) p.coop_min_nb = std::max(2, k.coop_min_nb.v);
+    if (k.coop_hdiv.set) p.coop_hdiv = std::max(1, k.coop_hdiv.v);
+    // Helpers must be capacity that would otherwise idle.  8-wave build: one workgroup per CU, a workgroup without a tile
+    // leaves its CU empty -- always on.  4-wave build (two workgroups per CU): an idle workgroup's CU-mate already runs 1.4 x
+    // faster alone, and a helper takes that back (measured on BASELINE configs[1]: the helped tail is 2 % SLOWER) -- off; a
+    // launch with fewer tiles than CUs runs the 8-wave build anyway, widened to at most one workgroup per CU.
+    if (coop && !w8) coop = false;
+    if (coop) {
+        const int cap = num_cu;
+        long long want = grid;
+        for (int t = 0; t < T && want < cap; ++t) {
+            const int nb = (int)((in.obs_off[t + 1] - in.obs_off[t] + bs - 1) / bs);
+            if (nb >= p.coop_min_nb) want += std::min(7, std::max(1, nb / p.coop_hdiv));
+        }
+        if (T < cap) grid = (int)std::min<long long>(cap, want);
+    }
+    if (k.grid.set) grid = std::max(1, std::min(grid, k.grid.v));   // developer: fewer resident workgroups
+    p.grid = grid; p.team = team; p.coop = coop;
+    // ---- time slicing of the optimisation (fp32): with few tiles per resident workgroup, whole tiles as the scheduling unit
+    // leave the GPU half empty while the last ones finish (4096 tiles on 512 workgroups: 8 % of the launch).  Tiles of
+    // similar cost are therefore served in slices of ~4 evaluations of a 512-point tile (both precisions); a batch whose largest tile
+    // dominates keeps the largest-first run-to-completion order (its critical path must not wait in a queue).
+    int seg_cost = 0;
+    if (in.optimiser != GPSAT_OPT_NONE && in.max_iter > 0) {
+        double sum_cost = 0.0, max_cost = 0.0;
+        for (int t = 0; t < T; ++t) {
+            const double nb = (double)((in.obs_off[t + 1] - in.obs_off[t] + bs - 1) / bs);
+            sum_cost += nb * nb * nb;
+            max_cost = std::max(max_cost, nb * nb * nb);
+        }
+        const double tiles_per_wg = (double)T / grid;
+        if (T > grid && max_cost * 4.0 * grid <= sum_cost && tiles_per_wg <= 64.0) seg_cost = 4 * (512 / bs) * (512 / bs) * (512 / bs);
+        // developer / tests: slice length in NB^3 units (0 = off, 1 = every evaluation), whatever the batch looks like
+        if (k.seg.set) seg_cost = std::max(0, k.seg.v);
+        if (in.unsliced || team > 1) seg_cost = 0;
+    }
+    p.seg_cost = seg_cost;
+    p.ring_cap = 0;
+    if (seg_cost > 0) {
+        size_t cap = 1; while (cap < (size_t)T + (size_t)grid + 1) cap <<= 1;
+        p.ring_cap = cap;
+    }
+    // ---- deferred predictions (fp32 4-wave build, time-sliced, no full covariance): a tile that finishes while others wait
+    // leaves its prediction in a snapshot slot for the workgroups that idle at the end of the launch (gpsat_ring.h).  One slot
+    // per tile up to a fixed budget; tiles past it predict inline.
+    p.pq_slots = 0; p.pq_stride = 0;
+    if (seg_cost > 0 && bd.pq_floats_per_slot && !in.want_cov && in.has_pred) {
+        p.pq_stride = bd.pq_floats_per_slot(D, NBmax);
+        const size_t budget = (size_t)5 << 29;                    // 2.5 GiB: every tile of a 4096-tile launch of N = 500
+        long long slots = std::min<long long>(T, (long long)(budget / (p.pq_stride * sizeof(float))));
+        // developer / tests: 0 = every prediction inline, n = at most n snapshot slots
+        if (k.defer.set) slots = std::min<long long>(slots, std::max(0, k.defer.v));
+        p.pq_slots = (int)slots;
+    }
+    return true;
+}
+
+}  // namespace gpsat
+#endif

@@ -48,8 +48,9 @@ class BinResult:
     total_ms: float = 0.0
 
 
-def centre_tiles(X, Xs, obs_off, pred_off):
-    """Subtract every tile's mean coordinate from its observations and prediction points (fp64).
+def centre_tiles(X, Xs, obs_off, pred_off, Z=None, z_off=None):
+    """Subtract every tile's mean coordinate from its observations and prediction points (fp64), and from its inducing
+    points ``Z`` (CSR ``z_off``) when given: the result is then (X, Xs, Z).
 
     The covariance functions are stationary, so the model is unchanged; what changes is the rounding of the cast to
     fp32 that follows: GPSat coordinates are typically far from the origin (t ~ 18 000 days against length scales of a
@@ -60,11 +61,28 @@ def centre_tiles(X, Xs, obs_off, pred_off):
     c = np.zeros((len(Ns), X.shape[1]))
     if nz.any():
         c[nz] = np.add.reduceat(X, obs_off[:-1][nz], axis=0) / Ns[nz, None]
-    return X - np.repeat(c, Ns, axis=0), Xs - np.repeat(c, Ps, axis=0)
+    out = X - np.repeat(c, Ns, axis=0), Xs - np.repeat(c, Ps, axis=0)
+    return out if Z is None else out + (Z - np.repeat(c, np.diff(z_off), axis=0),)
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _host_meta(D, offs, theta0, lo, hi, trainable):
+    """The CSR offset tables as contiguous int64, theta0 / lo / hi as [T, H] fp64 (no bounds: NaN) and trainable as [H] uint8."""
+    offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
+    T, H = len(offs[0]) - 1, D + 2
+    assert all(len(o) == T + 1 for o in offs)
+
+    def per_tile(a):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (T, H)))
+    lo = np.full((T, H), np.nan) if lo is None else per_tile(lo)
+    hi = np.full((T, H), np.nan) if hi is None else per_tile(hi)
+    trainable = np.ones(H, dtype=np.uint8) if trainable is None else \
+        np.ascontiguousarray(np.asarray(trainable).astype(bool).astype(np.uint8))
+    assert trainable.shape == (H,)
+    return offs, per_tile(theta0), lo, hi, trainable
 
 
 class Engine:
@@ -95,6 +113,60 @@ class Engine:
         except Exception:
             pass
 
+    def _device_io(self, inputs, dtype, sumP, out):
+        """Device mode: check the input tensors (name -> (tensor, elements)), take or allocate the three prediction outputs
+        and wait for the caller's stream.  Returns (torch dtype, (f_mean, f_var, y_var))."""
+        import torch
+        t_dt = torch.float32 if dtype == "f32" else torch.float64
+        for tname, (t_, _) in inputs.items():
+            if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == t_dt and t_.is_contiguous()):
+                raise GpsatError(f"{tname}: device mode needs contiguous {dtype} CUDA tensors")
+        dev = inputs["X"][0].device
+        if dev.index != self.device_id:
+            raise GpsatError(f"tensors live on cuda:{dev.index}, engine on device {self.device_id}")
+        assert all(t_.numel() == n for t_, n in inputs.values())
+        if out is None:
+            fm = torch.empty(max(sumP, 1), dtype=t_dt, device=dev)
+            out = fm, torch.empty_like(fm), torch.empty_like(fm)
+        torch.cuda.current_stream(dev).synchronize()   # inputs must be complete before our stream reads them
+        return t_dt, tuple(out)
+
+    @staticmethod
+    def _fill_batch(D, dtype, device_mode, meta, data, preds, kernel, optimiser, max_iter, max_ls, ftol, gtol, adam_lr, want_grad):
+        """GpsatBatch over ``meta`` (_host_meta's result), the inputs ``data`` = (X, y, Xs) and the outputs ``preds`` =
+        (f_mean, f_var, y_var), with fresh per-tile result arrays.  Returns (batch, results): ``results`` are BatchResult
+        fields; the caller keeps ``meta``, ``data`` and ``preds`` alive until the library call has returned."""
+        (obs_off, pred_off, *_), theta0, lo, hi, trainable = meta
+        T, H = len(obs_off) - 1, D + 2
+        res = dict(theta=np.empty((T, H), dtype=np.float64), nll=np.empty(T, dtype=np.float64),
+                   grad=np.empty((T, H), dtype=np.float64) if want_grad else None, status=np.empty(T, dtype=np.int32),
+                   n_eval=np.empty(T, dtype=np.int32), n_iter=np.zeros(T, dtype=np.int32))
+        ptr = (lambda a: a.data_ptr()) if device_mode else _ptr
+        b = L.GpsatBatch()
+        b.T, b.D, b.dtype = T, D, (L.F32 if dtype == "f32" else L.F64)
+        b.kernel = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        b.memory = L.MEM_DEVICE if device_mode else L.MEM_HOST
+        b.optimiser = L.OPT_IDS[optimiser] if not isinstance(optimiser, int) else optimiser
+        b.max_iter, b.max_ls = int(max_iter), int(max_ls)
+        b.ftol, b.gtol, b.adam_lr = float(ftol), float(gtol), float(adam_lr)
+        b.obs_off, b.pred_off = _ptr(obs_off), _ptr(pred_off)
+        b.theta0, b.lo, b.hi, b.trainable = _ptr(theta0), _ptr(lo), _ptr(hi), _ptr(trainable)
+        b.X, b.y, b.Xs = (ptr(a) for a in data)
+        b.theta, b.nll, b.grad = _ptr(res["theta"]), _ptr(res["nll"]), _ptr(res["grad"])
+        b.status, b.n_eval, b.n_iter = _ptr(res["status"]), _ptr(res["n_eval"]), _ptr(res["n_iter"])
+        b.f_mean, b.f_var, b.y_var = (ptr(a) for a in preds)
+        b.cov_off, b.f_cov = None, None
+        return b, res
+
+    def _result(self, rc, name, res, preds, sumP, **more) -> BatchResult:
+        """Raise on a failed call; otherwise the BatchResult with the call's timing."""
+        if rc != 0:
+            raise GpsatError(f"{name} failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        km, tm = C.c_double(), C.c_double()
+        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
+        fm, fv, yv = preds if len(preds[0]) == sumP else (a[:sumP] for a in preds)     # device outputs hold at least one element
+        return BatchResult(f_mean=fm, f_var=fv, y_var=yv, kernel_ms=km.value, total_ms=tm.value, **res, **more)
+
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
@@ -110,43 +182,16 @@ class Engine:
         ``starts`` [T, n_starts - 1, H] (constrained space) per tile, the best final objective wins; ``f_start`` of the
         result holds every start's final objective.  None: the optimisers of gpsat_fit_predict_batch.
         """
-        obs_off = np.ascontiguousarray(obs_off, dtype=np.int64)
-        pred_off = np.ascontiguousarray(pred_off, dtype=np.int64)
-        T = len(obs_off) - 1
-        H = D + 2
-        assert len(pred_off) == T + 1
-        theta0 = np.ascontiguousarray(np.broadcast_to(np.asarray(theta0, dtype=np.float64), (T, H)))
-        lo = np.full((T, H), np.nan) if lo is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (T, H)))
-        hi = np.full((T, H), np.nan) if hi is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (T, H)))
-        trainable = np.ones(H, dtype=np.uint8) if trainable is None else \
-            np.ascontiguousarray(np.asarray(trainable).astype(bool).astype(np.uint8))
-        assert trainable.shape == (H,)
+        meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable)
+        obs_off, pred_off = meta[0]
+        T, H = len(obs_off) - 1, D + 2
         sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
-
         if dtype not in ("f32", "f64"):
             raise GpsatError(f"dtype {dtype!r}: use 'f32' or 'f64'")
         np_dt = np.float32 if dtype == "f32" else np.float64
         device_mode = not isinstance(X, np.ndarray)
         if device_mode:
-            import torch
-            t_dt = torch.float32 if dtype == "f32" else torch.float64
-            for tname, t_ in (("X", X), ("y", y), ("Xs", Xs)):
-                if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == t_dt and t_.is_contiguous()):
-                    raise GpsatError(f"{tname}: device mode needs contiguous {dtype} CUDA tensors")
-            if X.device.index != self.device_id:
-                raise GpsatError(f"tensors live on cuda:{X.device.index}, engine on device {self.device_id}")
-            assert X.numel() == sumN * D and y.numel() == sumN and Xs.numel() == sumP * D
-            if out is None:
-                fm = torch.empty(max(sumP, 1), dtype=t_dt, device=X.device)
-                fv = torch.empty_like(fm)
-                yv = torch.empty_like(fm)
-            else:
-                fm, fv, yv = out
-            torch.cuda.current_stream(X.device).synchronize()   # inputs must be complete before our stream reads them
-            pX, py, pXs = X.data_ptr(), y.data_ptr(), Xs.data_ptr()
-            pfm, pfv, pyv = fm.data_ptr(), fv.data_ptr(), yv.data_ptr()
+            t_dt, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D)}, dtype, sumP, out)
         else:
             if dtype == "f32" and sumN > 0 and np.asarray(X).dtype == np.float64:
                 # fp64 coordinates handed to the fp32 kernels: centre per tile before the cast (see centre_tiles)
@@ -155,46 +200,24 @@ class Engine:
             X = np.ascontiguousarray(X, dtype=np_dt).reshape(sumN, D)
             y = np.ascontiguousarray(y, dtype=np_dt).reshape(sumN)
             Xs = np.ascontiguousarray(Xs, dtype=np_dt).reshape(sumP, D)
-            fm = np.empty(sumP, dtype=np_dt)
-            fv = np.empty(sumP, dtype=np_dt)
-            yv = np.empty(sumP, dtype=np_dt)
-            pX, py, pXs = _ptr(X), _ptr(y), _ptr(Xs)
-            pfm, pfv, pyv = _ptr(fm), _ptr(fv), _ptr(yv)
-
-        cov_off = fc = pfc = None
+            preds = tuple(np.empty(sumP, dtype=np_dt) for _ in range(3))
+        b, res = self._fill_batch(D, dtype, device_mode, meta, (X, y, Xs), preds, kernel, optimiser, max_iter, max_ls, ftol, gtol,
+                                  adam_lr, want_grad)
+        cov_off = fc = None
         if full_cov:
             Pt = np.diff(pred_off)
             cov_off = np.concatenate([[0], np.cumsum(Pt * Pt)]).astype(np.int64)
             if device_mode:
+                import torch
                 fc = torch.empty(max(int(cov_off[-1]), 1), dtype=t_dt, device=X.device)
-                pfc = fc.data_ptr()
             else:
                 fc = np.empty(max(int(cov_off[-1]), 1), dtype=np_dt)
-                pfc = _ptr(fc)
-        theta = np.empty((T, H), dtype=np.float64)
-        nll = np.empty(T, dtype=np.float64)
-        grad = np.empty((T, H), dtype=np.float64) if want_grad else None
-        status = np.empty(T, dtype=np.int32)
-        n_eval = np.empty(T, dtype=np.int32)
-        n_iter = np.zeros(T, dtype=np.int32)
-
-        b = L.GpsatBatch()
-        b.T, b.D, b.dtype = T, D, (L.F32 if dtype == "f32" else L.F64)
-        b.kernel = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        b.memory = L.MEM_DEVICE if device_mode else L.MEM_HOST
-        b.optimiser = L.OPT_IDS[optimiser] if not isinstance(optimiser, int) else optimiser
-        b.max_iter, b.max_ls = int(max_iter), int(max_ls)
-        b.ftol, b.gtol, b.adam_lr = float(ftol), float(gtol), float(adam_lr)
-        b.obs_off, b.pred_off = _ptr(obs_off), _ptr(pred_off)
-        b.theta0, b.lo, b.hi, b.trainable = _ptr(theta0), _ptr(lo), _ptr(hi), _ptr(trainable)
-        b.X, b.y, b.Xs = pX, py, pXs
-        b.theta, b.nll, b.grad = _ptr(theta), _ptr(nll), _ptr(grad)
-        b.status, b.n_eval, b.n_iter = _ptr(status), _ptr(n_eval), _ptr(n_iter)
-        b.f_mean, b.f_var, b.y_var = pfm, pfv, pyv
-        b.cov_off, b.f_cov = (_ptr(cov_off), pfc) if full_cov else (None, None)
+            b.cov_off, b.f_cov = _ptr(cov_off), (fc.data_ptr() if device_mode else _ptr(fc))
         f_start = None
+        name = "gpsat_fit_predict_batch"
         if n_starts is not None:
-            if not hasattr(self._lib, "gpsat_fit_predict_batch_ms"):
+            name = "gpsat_fit_predict_batch_ms"
+            if not hasattr(self._lib, name):
                 raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_ms (multi-start L-BFGS-B)")
             ms = L.GpsatMultistart()
             ms.n_starts, ms.transform = int(n_starts), L.TRANSFORM_LOG
@@ -206,16 +229,8 @@ class Engine:
             rc = self._lib.gpsat_fit_predict_batch_ms(self._h, C.byref(b), C.byref(ms))
         else:
             rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
-        if rc != 0:
-            name = "gpsat_fit_predict_batch_ms" if n_starts is not None else "gpsat_fit_predict_batch"
-            raise GpsatError(f"{name} failed ({rc}): {self._lib.gpsat_last_error().decode()}")
-        km, tm = C.c_double(), C.c_double()
-        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
-        if device_mode:
-            fm, fv, yv = fm[:sumP], fv[:sumP], yv[:sumP]
-        return BatchResult(theta=theta, nll=nll, status=status, n_eval=n_eval, n_iter=n_iter, f_mean=fm, f_var=fv, y_var=yv,
-                           grad=grad, kernel_ms=km.value, total_ms=tm.value, f_start=f_start,
-                           f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
+        return self._result(rc, name, res, preds, sumP, f_start=f_start,
+                            f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
 
     def sgpr_fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, z_off, Z, theta0, lo=None, hi=None,
                                trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000, max_ls=0,
@@ -229,88 +244,26 @@ class Engine:
             raise NotImplementedError("sparse GP experts are built in fp64 only (dtype='f64')")
         if full_cov:
             raise NotImplementedError("sparse GP experts do not return the full covariance")
-        obs_off = np.ascontiguousarray(obs_off, dtype=np.int64)
-        pred_off = np.ascontiguousarray(pred_off, dtype=np.int64)
-        z_off = np.ascontiguousarray(z_off, dtype=np.int64)
-        T = len(obs_off) - 1
-        H = D + 2
-        assert len(pred_off) == T + 1 and len(z_off) == T + 1
-        theta0 = np.ascontiguousarray(np.broadcast_to(np.asarray(theta0, dtype=np.float64), (T, H)))
-        lo = np.full((T, H), np.nan) if lo is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (T, H)))
-        hi = np.full((T, H), np.nan) if hi is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (T, H)))
-        trainable = np.ones(H, dtype=np.uint8) if trainable is None else \
-            np.ascontiguousarray(np.asarray(trainable).astype(bool).astype(np.uint8))
-        assert trainable.shape == (H,)
+        meta = _host_meta(D, (obs_off, pred_off, z_off), theta0, lo, hi, trainable)
+        obs_off, pred_off, z_off = meta[0]
         sumN, sumP, sumM = int(obs_off[-1]), int(pred_off[-1]), int(z_off[-1])
         device_mode = not isinstance(X, np.ndarray)
         if device_mode:
-            import torch
-            for tname, t_ in (("X", X), ("y", y), ("Xs", Xs), ("Z", Z)):
-                if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()):
-                    raise GpsatError(f"{tname}: device mode needs contiguous f64 CUDA tensors")
-            if X.device.index != self.device_id:
-                raise GpsatError(f"tensors live on cuda:{X.device.index}, engine on device {self.device_id}")
-            assert X.numel() == sumN * D and y.numel() == sumN and Xs.numel() == sumP * D and Z.numel() == sumM * D
-            if out is None:
-                fm = torch.empty(max(sumP, 1), dtype=torch.float64, device=X.device)
-                fv = torch.empty_like(fm)
-                yv = torch.empty_like(fm)
-            else:
-                fm, fv, yv = out
-            torch.cuda.current_stream(X.device).synchronize()
-            pX, py, pXs, pZ = X.data_ptr(), y.data_ptr(), Xs.data_ptr(), Z.data_ptr()
-            pfm, pfv, pyv = fm.data_ptr(), fv.data_ptr(), yv.data_ptr()
+            _, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D), "Z": (Z, sumM * D)}, dtype, sumP, out)
+            pZ = Z.data_ptr()
         else:
-            X = np.asarray(X, dtype=np.float64).reshape(sumN, D)
-            Xs = np.asarray(Xs, dtype=np.float64).reshape(sumP, D)
-            Z = np.asarray(Z, dtype=np.float64).reshape(sumM, D)
-            Ns = np.diff(obs_off)
-            c = np.zeros((T, D))
-            nz = Ns > 0
-            if nz.any():
-                c[nz] = np.add.reduceat(X, obs_off[:-1][nz], axis=0) / Ns[nz, None]
-            X = np.ascontiguousarray(X - np.repeat(c, Ns, axis=0))
-            Xs = np.ascontiguousarray(Xs - np.repeat(c, np.diff(pred_off), axis=0))
-            Z = np.ascontiguousarray(Z - np.repeat(c, np.diff(z_off), axis=0))
+            X, Xs, Z = centre_tiles(np.asarray(X, dtype=np.float64).reshape(sumN, D), np.asarray(Xs, dtype=np.float64).reshape(sumP, D),
+                                    obs_off, pred_off, np.asarray(Z, dtype=np.float64).reshape(sumM, D), z_off)
+            X, Xs, Z = np.ascontiguousarray(X), np.ascontiguousarray(Xs), np.ascontiguousarray(Z)
             y = np.ascontiguousarray(y, dtype=np.float64).reshape(sumN)
-            fm = np.empty(sumP, dtype=np.float64)
-            fv = np.empty(sumP, dtype=np.float64)
-            yv = np.empty(sumP, dtype=np.float64)
-            pX, py, pXs, pZ = _ptr(X), _ptr(y), _ptr(Xs), _ptr(Z)
-            pfm, pfv, pyv = _ptr(fm), _ptr(fv), _ptr(yv)
-        theta = np.empty((T, H), dtype=np.float64)
-        nll = np.empty(T, dtype=np.float64)
-        grad = np.empty((T, H), dtype=np.float64) if want_grad else None
-        status = np.empty(T, dtype=np.int32)
-        n_eval = np.empty(T, dtype=np.int32)
-        n_iter = np.zeros(T, dtype=np.int32)
-        b = L.GpsatBatch()
-        b.T, b.D, b.dtype = T, D, L.F64
-        b.kernel = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        b.memory = L.MEM_DEVICE if device_mode else L.MEM_HOST
-        b.optimiser = L.OPT_IDS[optimiser] if not isinstance(optimiser, int) else optimiser
-        b.max_iter, b.max_ls = int(max_iter), int(max_ls)
-        b.ftol, b.gtol, b.adam_lr = float(ftol), float(gtol), float(adam_lr)
-        b.obs_off, b.pred_off = _ptr(obs_off), _ptr(pred_off)
-        b.theta0, b.lo, b.hi, b.trainable = _ptr(theta0), _ptr(lo), _ptr(hi), _ptr(trainable)
-        b.X, b.y, b.Xs = pX, py, pXs
-        b.theta, b.nll, b.grad = _ptr(theta), _ptr(nll), _ptr(grad)
-        b.status, b.n_eval, b.n_iter = _ptr(status), _ptr(n_eval), _ptr(n_iter)
-        b.f_mean, b.f_var, b.y_var = pfm, pfv, pyv
-        b.cov_off, b.f_cov = None, None
+            preds = tuple(np.empty(sumP, dtype=np.float64) for _ in range(3))
+            pZ = _ptr(Z)
+        b, res = self._fill_batch(D, dtype, device_mode, meta, (X, y, Xs), preds, kernel, optimiser, max_iter, max_ls, ftol, gtol,
+                                  adam_lr, want_grad)
         sp = L.GpsatSparse()
         sp.z_off, sp.Z, sp.jitter = _ptr(z_off), pZ, float(jitter)
         rc = self._lib.gpsat_sgpr_fit_predict_batch(self._h, C.byref(b), C.byref(sp))
-        if rc != 0:
-            raise GpsatError(f"gpsat_sgpr_fit_predict_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
-        km, tm = C.c_double(), C.c_double()
-        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
-        if device_mode:
-            fm, fv, yv = fm[:sumP], fv[:sumP], yv[:sumP]
-        return BatchResult(theta=theta, nll=nll, status=status, n_eval=n_eval, n_iter=n_iter, f_mean=fm, f_var=fv, y_var=yv,
-                           grad=grad, kernel_ms=km.value, total_ms=tm.value)
+        return self._result(rc, "gpsat_sgpr_fit_predict_batch", res, preds, sumP)
 
     def select_batch(self, points: np.ndarray, refs: np.ndarray, criteria, points_cm: np.ndarray = None,
                      bounds: np.ndarray = None):

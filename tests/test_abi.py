@@ -78,8 +78,8 @@ def test_fp32_tile_limit_fits_the_sweep_flags():
 
 def test_four_wave_thresholds_of_the_build_matrix():
     """tests/test_gpu_build_matrix.py sizes its 4-wave batches from W4_NB / D4_NB: the largest tile (blocks) whose 4-wave LDS
-    layout fits 80 KiB, the rule by which gpsat_capi.cpp picks the 4-wave builds.  If the layouts drift, those batches would
-    quietly run on the 8-wave builds; this fails instead."""
+    layout fits 80 KiB, the rule by which gpsat::plan_tiles (gpsat_plan.h) picks the 4-wave builds.  If the layouts drift, those
+    batches would quietly run on the 8-wave builds; this fails instead."""
     from test_gpu_build_matrix import D4_NB, W4_NB
     lib = L.load()
     for name, table in (("_ZN5gpsat12shared_bytesEii", W4_NB), ("_ZN5gpsat19shared_bytes_f64_w4Eii", D4_NB)):
@@ -145,3 +145,67 @@ def test_developer_knobs_are_gated():
                     plain.append((f, ln, line.strip()))
     assert all('"GPSAT_DEVELOPER"' in l or "return std::getenv(name)" in l for _, _, l in plain), plain
     assert len(plain) == 2, plain
+
+
+class _Knob(C.Structure):
+    _fields_ = [("set", C.c_int), ("v", C.c_int)]
+
+
+class _PlanInput(C.Structure):               # gpsat::PlanInput (gpsat_amd/csrc/gpsat_plan.h)
+    _fields_ = [("T", C.c_int), ("D", C.c_int), ("f64", C.c_int), ("obs_off", C.POINTER(C.c_int64)), ("maxP", C.c_longlong),
+                ("want_cov", C.c_int), ("has_pred", C.c_int), ("optimiser", C.c_int), ("max_iter", C.c_int), ("num_cu", C.c_int),
+                ("wg_per_cu", C.c_int), ("solo", C.c_int), ("unsliced", C.c_int), ("knobs", _Knob * 8)]
+
+
+class _TilePlan(C.Structure):                # gpsat::TilePlan
+    _fields_ = [(n, C.c_int) for n in ("build", "NBmax", "PCcov", "grid", "team", "coop", "coop_min_nb", "coop_hdiv", "coop_force",
+                                       "seg_cost", "state_words", "pq_slots")] + \
+               [(n, C.c_size_t) for n in ("smem", "ws_stride", "ring_cap", "pq_stride")]
+
+
+# build: 0 fp32 4-wave, 1 fp32 8-wave, 2 fp64 8-wave, 3 fp64 4-wave.  The values are those of the launch rules as they stood
+# inside fit_predict_impl before they became gpsat::plan_tiles (computed by that code, not by the function under test).
+_COMMON = dict(PCcov=0, coop_min_nb=12, coop_hdiv=12, coop_force=0)
+MEASURED_PLANS = {
+    "configs1": (dict(f64=0, Ns=[500] * 4096, optimiser=1, max_iter=20),
+                 dict(build=0, NBmax=16, grid=512, team=1, coop=0, seg_cost=16384, state_words=772, pq_slots=4096, smem=67120,
+                      ws_stride=418816, ring_cap=8192, pq_stride=141568)),
+    "configs2": (dict(f64=0, Ns="ragged", optimiser=1, max_iter=20),
+                 dict(build=1, NBmax=64, grid=256, team=1, coop=1, seg_cost=0, state_words=772, pq_slots=0, smem=122416,
+                      ws_stride=5317632, ring_cap=0, pq_stride=0)),
+    "configs4": (dict(f64=1, Ns=[2000] * 1024, optimiser=0, max_iter=0),
+                 dict(build=2, NBmax=125, grid=256, team=1, coop=0, seg_cost=0, state_words=636, pq_slots=0, smem=123904,
+                      ws_stride=5066496, ring_cap=0, pq_stride=0)),
+    "f64fit": (dict(f64=1, Ns=[500] * 4096, optimiser=1, max_iter=20),
+               dict(build=3, NBmax=32, grid=512, team=1, coop=0, seg_cost=131072, state_words=636, pq_slots=0, smem=75008,
+                    ws_stride=411904, ring_cap=8192, pq_stride=0)),
+    # fewer tiles than CUs: the 8-wave build with cooperative tiles, the grid widened by three helpers per tile
+    "64 tiles of 1500": (dict(f64=0, Ns=[1500] * 64, optimiser=1, max_iter=20),
+                         dict(build=1, NBmax=47, grid=256, team=1, coop=1, seg_cost=0, state_words=772, pq_slots=0, smem=102832,
+                              ws_stride=3089408, ring_cap=0, pq_stride=0)),
+    "fp64 teams": (dict(f64=1, Ns=[2000] * 16, optimiser=1, max_iter=20),
+                   dict(build=2, NBmax=125, grid=256, team=16, coop=0, seg_cost=0, state_words=636, pq_slots=0, smem=123904,
+                        ws_stride=5066496, ring_cap=0, pq_stride=0)),
+}
+
+
+@pytest.mark.parametrize("name", list(MEASURED_PLANS))
+def test_launch_plan_of_the_measured_shapes(name):
+    """gpsat::plan_tiles decides build, grid, teams, cooperative tiles, time slicing and the deferred-prediction pool from host
+    data alone: its plan for the shapes the project measures (bench.py's workloads, D = 3, 500 predictions per tile), on 256
+    CUs with the default two workgroups per CU and no developer knob."""
+    import numpy as np
+    lib = L.load()
+    fn = getattr(lib, "_ZN5gpsat10plan_tilesERKNS_9PlanInputERNS_8TilePlanE")
+    fn.restype, fn.argtypes = C.c_bool, [C.POINTER(_PlanInput), C.POINTER(_TilePlan)]
+    case, want = MEASURED_PLANS[name]
+    Ns = case["Ns"]
+    if isinstance(Ns, str):                  # bench.py --workload configs2
+        Ns = np.random.default_rng(0).choice([128, 256, 384, 512, 768, 1024, 1536, 2048], 4096)
+    off = np.concatenate([[0], np.cumsum(Ns)]).astype(np.int64)
+    pin = _PlanInput(T=len(Ns), D=3, f64=case["f64"], obs_off=off.ctypes.data_as(C.POINTER(C.c_int64)), maxP=0, want_cov=0, has_pred=1,
+                     optimiser=case["optimiser"], max_iter=case["max_iter"], num_cu=256, wg_per_cu=2, solo=0, unsliced=0)
+    plan = _TilePlan()
+    assert fn(C.byref(pin), C.byref(plan))
+    got = {n: getattr(plan, n) for n, _ in _TilePlan._fields_}
+    assert got == {**_COMMON, **want}, got

@@ -331,3 +331,26 @@ def test_reference_test_scikit_to_1e6(eng):
     assert abs(m.get_objective_function_value() - float(d["ml"])) < 1e-6
     assert abs(out["f*"][0] - float(d["pred_mean"])) < 1e-6
     assert abs(out["f*_var"][0] - float(d["pred_std"]) ** 2) < 1e-6
+
+
+def test_destroyed_engines_release_the_multistart_state():
+    # gpsat_destroy frees every device buffer of the handle, the multi-start state included.  20 000 tiles of 3 observations,
+    # S = 3, H = 3: that state is T (16 + (S - 1) H + S) doubles = 4 MB per engine, far above what the runtime rounds to.
+    # The first create / run / close cycle absorbs what the runtime itself keeps; after it, free device memory stays put.
+    import torch
+    T, N, S = 20_000, 3, 3
+    rng = np.random.default_rng(5)
+    X = rng.uniform(0, 1, size=(T * N, 1))
+    kw = dict(D=1, obs_off=np.arange(T + 1) * N, X=X, y=np.sin(5 * X[:, 0]), pred_off=np.zeros(T + 1, dtype=np.int64),
+              Xs=np.zeros((0, 1)), theta0=[[1.0, 1.0, 0.01]], lo=[[1e-5, 1e-5, np.nan]], hi=[[1e5, 1e5, np.nan]],
+              trainable=[1, 1, 0], kernel="RBF", optimiser="lbfgs", max_iter=1, dtype="f64", n_starts=S,
+              starts=np.tile([0.5, 2.0, 0.01], (T, S - 1, 1)))
+    free = []
+    for _ in range(4):
+        e = Engine(0)
+        r = e.fit_predict_batch(**kw)
+        assert r.f_start.shape == (T, S) and np.isfinite(r.f_start).all()
+        e.close()
+        free.append(torch.cuda.mem_get_info(0)[0])
+    print("free bytes after each close:", free)
+    assert free[-1] == free[0], free
