@@ -24,9 +24,10 @@ STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5:
 EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
-           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch"]
+           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
+           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
-OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch"]
+OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold"]
 
 
 class GpsatOpts(C.Structure):
@@ -56,6 +57,11 @@ TRANSFORM_LOG = 1
 
 class GpsatMultistart(C.Structure):
     _fields_ = [("n_starts", C.c_int32), ("transform", C.c_int32), ("starts", C.c_void_p), ("f_start", C.c_void_p),
+                ("reserved", C.c_int32 * 8)]
+
+
+class GpsatCv(C.Structure):
+    _fields_ = [("fold", C.c_void_p), ("cv_mean", C.c_void_p), ("cv_f_var", C.c_void_p), ("cv_y_var", C.c_void_p),
                 ("reserved", C.c_int32 * 8)]
 
 
@@ -159,6 +165,11 @@ def load():
     if hasattr(lib, "gpsat_fit_predict_batch_ms"):
         lib.gpsat_fit_predict_batch_ms.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMultistart)]
         lib.gpsat_fit_predict_batch_ms.restype = C.c_int
+    if hasattr(lib, "gpsat_fit_predict_batch_cv"):
+        lib.gpsat_fit_predict_batch_cv.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatCv)]
+        lib.gpsat_fit_predict_batch_cv.restype = C.c_int
+        lib.gpsat_max_cv_fold.argtypes = [C.c_int, C.c_int]
+        lib.gpsat_max_cv_fold.restype = C.c_int
     if hasattr(lib, "gpsat_bin_batch"):
         lib.gpsat_bin_batch.restype = C.c_int
         lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -179,6 +190,14 @@ def max_tile_obs(dtype: str, D: int) -> int:
 def max_inducing(dtype: str, D: int) -> int:
     """Largest number of inducing points per sparse tile (gpsat_max_inducing); 0 for fp32 in this build."""
     return int(get_lib().gpsat_max_inducing(F32 if dtype == "f32" else F64, int(D)))
+
+
+def max_cv_fold(dtype: str, D: int) -> int:
+    """Largest fold (rows held out together) of gpsat_fit_predict_batch_cv; 0 for fp32."""
+    lib = get_lib()
+    if not hasattr(lib, "gpsat_max_cv_fold"):
+        return 0
+    return int(lib.gpsat_max_cv_fold(F32 if dtype == "f32" else F64, int(D)))
 
 
 _lib = None

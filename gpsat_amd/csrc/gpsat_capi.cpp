@@ -1,8 +1,8 @@
 // gpsat_capi.cpp -- C ABI of libgpsat_hip.so (see include/gpsat_hip.h for the contract and the
 // reference interfaces each entry point replaces).  Host-side responsibilities only: argument
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
-// gpsat_fit_predict_batch in steps: check_batch / check_multistart, plan_tiles (gpsat_plan.h), stage_batch, setup_*, launch,
-// fetch_batch, record_timing.
+// gpsat_fit_predict_batch in steps: check_batch / check_multistart / check_cv, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+// setup_*, launch, fetch_batch / fetch_cv, record_timing.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -127,6 +127,7 @@ struct gpsat_handle : HandleQueue {
     } selc;
     // device buffers (grown lazily, owned by the handle, freed by its destructor)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
+    DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
     DevBuf bin_in, bin_keys, bin_rows, bin_vals, bin_runs, bin_tmp, bin_out;     // gpsat_bin_batch
@@ -229,6 +230,92 @@ int check_multistart(const gpsat_batch* b, const gpsat_multistart* ms, bool ms_o
                 return fail(GPSAT_EINVAL, "multistart: starts must be finite and positive");
     if (ms_on) theta0_clipped = clip_to_bounds(b, b->theta0, 1);
     if (ms_on && S > 1) starts_clipped = clip_to_bounds(b, ms->starts, S - 1);
+    return GPSAT_OK;
+}
+
+// ---- held-out predictions (gpsat_fit_predict_batch_cv).  The caller's labels as the tables the kernel reads, all int32 in one
+// host vector (one copy): pair_off [T+1], fold_off [T+1], fold_ptr [F+1], fold_a [F], fold_rows [R], row_fold [sumN],
+// row_pos [sumN], pairs.  Folds of a tile are numbered by ascending label, a fold's rows keep the order of the tile.
+struct CvTables {
+    std::vector<int> all;
+    size_t o_pair_off = 0, o_fold_off = 0, o_fold_ptr = 0, o_fold_a = 0, o_fold_rows = 0, o_row_fold = 0, o_row_pos = 0, o_pairs = 0;
+};
+
+int check_cv(const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, CvTables& tb) {
+    if (b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "held-out predictions are built for GPSAT_F64 only");
+    if (b->cov_off || b->f_cov) return fail(GPSAT_EINVAL, "held-out predictions and the full covariance cannot be asked for in the same call: cov_off / f_cov must be NULL");
+    if (!cv->cv_mean || !cv->cv_f_var) return fail(GPSAT_EINVAL, "gpsat_cv: cv_mean / cv_f_var is NULL");
+    const int T = b->T, gmax = gpsat_max_cv_fold(b->dtype, b->D);
+    const size_t sumN = (size_t)d.sumN;
+    std::vector<int> pair_off(T + 1, 0), fold_off(T + 1, 0), fold_ptr(1, 0), fold_a, fold_rows, row_fold(sumN, -1), row_pos(sumN, 0), pairs;
+    std::vector<int> idx;
+    std::vector<unsigned char> mark;
+    for (int t = 0; t < T; ++t) {
+        const long long o0 = b->obs_off[t];
+        const int N = (int)(b->obs_off[t + 1] - o0), NB = (N + 15) / 16;
+        const int32_t* lab = cv->fold ? cv->fold + o0 : nullptr;
+        idx.clear();
+        for (int i = 0; i < N; ++i) if (!lab || lab[i] >= 0) idx.push_back(i);
+        if (lab) std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return lab[x] < lab[y]; });
+        mark.assign((size_t)NB * NB, 0);
+        int a_off = 0;
+        for (size_t s0 = 0; s0 < idx.size();) {
+            size_t s1 = s0 + 1;
+            while (lab && s1 < idx.size() && lab[idx[s1]] == lab[idx[s0]]) ++s1;
+            const int g = (int)(s1 - s0), f = (int)fold_ptr.size() - 1;
+            if (g > gmax)
+                return fail(GPSAT_EINVAL, "tile " + std::to_string(t) + ": fold " + std::to_string(lab[idx[s0]]) + " holds " + std::to_string(g) +
+                                              " rows, at most " + std::to_string(gmax) + " are held out together (gpsat_max_cv_fold)");
+            for (size_t k = s0; k < s1; ++k) {
+                const int i = idx[k];
+                row_fold[o0 + i] = f; row_pos[o0 + i] = (int)(k - s0);
+                fold_rows.push_back(i);
+                for (size_t k2 = s0; k2 <= k; ++k2) {
+                    const int bi = i / 16, bj = idx[k2] / 16;      // rows of a fold ascend
+                    mark[(size_t)std::max(bi, bj) * NB + std::min(bi, bj)] = 1;
+                }
+            }
+            fold_a.push_back(g > 1 ? a_off : 0);
+            if (g > 1) a_off += g * g;
+            fold_ptr.push_back((int)fold_rows.size());
+            s0 = s1;
+        }
+        for (int a = 0; a < NB; ++a)                                   // ascending a: the longest sums first
+            for (int c = 0; c <= a; ++c)
+                if (mark[(size_t)a * NB + c]) pairs.push_back((a << 16) | c);
+        fold_off[t + 1] = (int)fold_ptr.size() - 1;
+        pair_off[t + 1] = (int)pairs.size();
+    }
+    auto put = [&](const std::vector<int>& v, size_t& off) { off = tb.all.size(); tb.all.insert(tb.all.end(), v.begin(), v.end()); };
+    put(pair_off, tb.o_pair_off); put(fold_off, tb.o_fold_off); put(fold_ptr, tb.o_fold_ptr); put(fold_a, tb.o_fold_a);
+    put(fold_rows, tb.o_fold_rows); put(row_fold, tb.o_row_fold); put(row_pos, tb.o_row_pos); put(pairs, tb.o_pairs);
+    return GPSAT_OK;
+}
+
+// The fold tables to the device; the outputs in the handle's buffer (host mode, or no cv_y_var) or the caller's device arrays.
+int stage_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, const CvTables& tb, gpsat::CvArgs& ca) {
+    const size_t nint = (tb.all.size() + 1) & ~size_t(1), sumN = (size_t)d.sumN;
+    int rc;
+    if ((rc = h->cv.reserve(nint * sizeof(int) + 3 * std::max<size_t>(sumN, 1) * sizeof(double)))) return rc;
+    int* base = static_cast<int*>(h->cv.p);
+    HIP_TRY(hipMemcpyAsync(base, tb.all.data(), tb.all.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    ca.pair_off = base + tb.o_pair_off; ca.pairs = base + tb.o_pairs; ca.fold_off = base + tb.o_fold_off;
+    ca.fold_ptr = base + tb.o_fold_ptr; ca.fold_rows = base + tb.o_fold_rows; ca.fold_a = base + tb.o_fold_a;
+    ca.row_fold = base + tb.o_row_fold; ca.row_pos = base + tb.o_row_pos;
+    double* out = reinterpret_cast<double*>(base + nint);
+    const bool dev = b->memory == GPSAT_MEM_DEVICE;
+    ca.mean = dev ? static_cast<double*>(cv->cv_mean) : out;
+    ca.f_var = dev ? static_cast<double*>(cv->cv_f_var) : out + sumN;
+    ca.y_var = dev && cv->cv_y_var ? static_cast<double*>(cv->cv_y_var) : out + 2 * sumN;
+    return GPSAT_OK;
+}
+
+int fetch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, const gpsat::CvArgs& ca) {
+    if (b->memory != GPSAT_MEM_HOST || d.sumN == 0) return GPSAT_OK;
+    void* const host[3] = {cv->cv_mean, cv->cv_f_var, cv->cv_y_var};
+    const double* const dev[3] = {ca.mean, ca.f_var, ca.y_var};
+    for (int i = 0; i < 3; ++i)
+        if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], (size_t)d.sumN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return GPSAT_OK;
 }
 
@@ -484,6 +571,8 @@ void read_report(const gpsat::TilePlan& p, const gpsat::KernelArgs& a, LaunchRep
 struct DenseJob {
     const gpsat_batch* b;
     const gpsat_multistart* ms;       // nullptr: gpsat_fit_predict_batch
+    const gpsat_cv* cv = nullptr;     // held-out predictions (gpsat_fit_predict_batch_cv), with their fold tables
+    CvTables cv_tables;
     bool ms_on;                       // ms given and the optimiser runs
     BatchDims dims;
     const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
@@ -497,7 +586,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     const BatchDims& d = j.dims;
     const bool f64 = b->dtype == GPSAT_F64;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
-                           h->num_cu, h->wg_per_cu, solo, unsliced, read_dev_knobs()};
+                           h->num_cu, h->wg_per_cu, solo || j.cv, unsliced, read_dev_knobs()};     // held-out: one workgroup per tile
     gpsat::TilePlan p;
     if (!gpsat::plan_tiles(in, p)) return fail(GPSAT_EINVAL, "tile too large for LDS");
     Staged s;
@@ -518,6 +607,11 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if ((rc = setup_coop_and_team(h, p, &b->T, a))) return rc;
     if (j.ms_on && (rc = setup_multistart(h, b, j.ms->n_starts, j.theta0, j.starts_clipped, a))) return rc;
     if ((rc = setup_deferred(h, p, a))) return rc;
+    gpsat::CvArgs ca;
+    if (j.cv) {
+        if (!gpsat::builds[p.build].launch_cv) return fail(GPSAT_EINVAL, "held-out predictions: no kernel in this build");
+        if ((rc = stage_cv(h, b, j.cv, d, j.cv_tables, ca))) return rc;
+    }
 #ifdef GPSAT_DUMP
     if (h->dump_dev && !f64) {
         const size_t need = ((size_t)p.NBmax * p.NBmax + p.NBmax) * 1024 + 2 * (size_t)p.NBmax * 32 + 16 + 8 * 1024;
@@ -531,9 +625,11 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     a.prof = static_cast<unsigned long long*>(h->prof.p);
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
+    if (j.cv) HIP_TRY(gpsat::builds[p.build].launch_cv(b->D, a, ca, p.grid, p.smem, h->stream));
+    else HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s))) return rc;
+    if (j.cv && (rc = fetch_cv(h, b, j.cv, d, ca))) return rc;
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 #ifdef GPSAT_PROFILE
@@ -546,11 +642,11 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     return GPSAT_OK;
 }
 
-int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
+int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
-    j.b = b; j.ms = ms;
+    j.b = b; j.ms = ms; j.cv = cv;
     int rc;
     if ((rc = check_batch(b, false, j.dims))) return rc;
     BatchDims& d = j.dims;
@@ -569,6 +665,7 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
         return fail(GPSAT_EINVAL, "tile too large for the LDS of a CU: at most " + std::to_string(gpsat_max_tile_obs(b->dtype, b->D)) +
                                       " observations per tile for this dtype and D (gpsat_max_tile_obs)");
     if ((rc = check_batch_data(b, d))) return rc;
+    if (cv && (rc = check_cv(b, cv, d, j.cv_tables))) return rc;
     j.ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
     if (ms && (rc = check_multistart(b, ms, j.ms_on, j.theta0_clipped, j.starts_clipped))) return rc;
     j.theta0 = j.ms_on ? j.theta0_clipped.data() : b->theta0;
@@ -679,6 +776,17 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
     if (!ms) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_ms: NULL multistart");
     return fit_predict(h, b, ms);
+}
+
+int gpsat_max_cv_fold(int dtype, int D) {
+    if (D < 1 || D > 4 || dtype != GPSAT_F64) return 0;
+    return GPSAT_MAX_CV_FOLD;
+}
+
+int gpsat_fit_predict_batch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv) {
+    if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv: NULL gpsat_cv");
+    if (b && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "held-out predictions are built for GPSAT_F64 only");
+    return fit_predict(h, b, nullptr, cv);
 }
 
 #ifdef GPSAT_DUMP

@@ -85,17 +85,36 @@ struct KernelArgs {
     double* ms_fout = nullptr;    // [T][ms_S] or nullptr
 };
 
+// Held-out predictions of the fp64 tile kernels (gpsat_fit_predict_batch_cv); device pointers.  Folds are numbered through the
+// batch in tile order; `pairs` lists, per tile, the 16 x 16 blocks (a << 16 | b, a >= b) of K_y^-1 that hold two rows of one fold.
+struct CvArgs {
+    const int* pair_off = nullptr;    // [T+1] into pairs
+    const int* pairs = nullptr;
+    const int* fold_off = nullptr;    // [T+1] folds of a tile
+    const int* fold_ptr = nullptr;    // [F+1] into fold_rows
+    const int* fold_rows = nullptr;   // rows of every fold (positions inside the tile), in the order of the rows
+    const int* fold_a = nullptr;      // [F] doubles in front of the fold's g x g matrix in the tile's scratch
+    const int* row_fold = nullptr;    // [sumN] the row's fold, -1: never held out
+    const int* row_pos = nullptr;     // [sumN] the row's position inside its fold
+    double* mean = nullptr;           // [sumN] outputs
+    double* f_var = nullptr;
+    double* y_var = nullptr;
+};
+#define GPSAT_MAX_CV_FOLD 256         // largest fold: sum g^2 <= 256 N doubles fits the prediction scratch of a tile's workspace
+
 size_t shared_bytes(int D, int NBmax);
 // fp64 kernels (gpsat_kernels_f64.hip): X, y, Xs, f_* and ws of KernelArgs point at doubles, ws_stride counts doubles
 size_t shared_bytes_f64(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64(int NBmax, int PCcov);
 int state_words_f64();
 hipError_t launch_tiles_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+hipError_t launch_tiles_cv_f64(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
 // 4-wave build (gpsat_kernels_f64.hip -DGPSAT_F64_W4): two workgroups per CU for tiles whose LDS fits twice
 size_t shared_bytes_f64_w4(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
 hipError_t launch_tiles_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+hipError_t launch_tiles_cv_f64_w4(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

@@ -30,6 +30,23 @@ namespace gpsat {
 #define F64FN(name) name
 #define F64_MIN_WG 1
 #endif
+// -DGPSAT_F64_CV compiles the one-workgroup-per-tile kernel of either build once more, with the held-out phase (phase_cv)
+// behind every tile's prediction, into objects of their own that export launch_tiles_cv_f64[_w4] only.  Everything the flag
+// adds stands behind these macros, so that without it the translation unit is, token for token, what it was before the
+// held-out phase existed: the kernels of gpsat_fit_predict_batch are compiled from unchanged source.
+#ifdef GPSAT_F64_CV
+#undef F64NS
+#ifdef GPSAT_F64_W4
+#define F64NS f64k4cv
+#else
+#define F64NS f64kcv
+#endif
+#define CV_KERNEL_PARAM , const CvArgs cvA
+#define CV_FINAL_WANTS_M(sh_) || ((sh_)->phase == PH_FINAL)      /* the final evaluation leaves L^-1 and alpha behind */
+#else
+#define CV_KERNEL_PARAM
+#define CV_FINAL_WANTS_M(sh_)
+#endif
 namespace F64NS {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -1014,7 +1031,7 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
         for (int d = 0; d < D; ++d) lds_d[c.L.xsc + d * c.Npad + idx] = (idx < c.N) ? Xg[(size_t)idx * D + d] / sh->theta[d] : 0.0;
     }
     __syncthreads();
-    phase_potrf<D, KN, TEAM>(c, want_grad);
+    phase_potrf<D, KN, TEAM>(c, want_grad CV_FINAL_WANTS_M(sh));
     if (sh->fail) {
         if (c.tid == 0) { sh->nll = __builtin_inf(); for (int i = 0; i < D + 2; ++i) sh->gth[i] = 0.0; }
         __syncthreads();
@@ -1176,8 +1193,148 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
     }
 }
 
+#ifdef GPSAT_F64_CV
+// ---- held-out predictions (gpsat_fit_predict_batch_cv): the rows G of a fold predicted from all other rows of the tile at
+// the returned parameters, from what the last evaluation left behind -- M = L^-1 in the lower slots and alpha = K_y^-1 y in
+// LDS.  With A = K_y^-1 = M^T M:   A_GG = M[:, G]^T M[:, G],   mean = y_G - A_GG^-1 alpha_G,   cov(y_G) = A_GG^-1
+// (g = 1: Rasmussen & Williams eq. 5.12).
+//  (1) the blocks (K_y^-1)_ab = sum_{c >= a} M_ca^T M_cb of the block pairs the host listed (those that hold a pair of rows
+//      of one fold; leave-one-out: the diagonal blocks), one item per wave and step, scattered into the folds' g x g matrices
+//      in the prediction scratch of the workspace (sum g^2 <= 256 N doubles <= the scratch of either build); a one-row fold
+//      is finished right there;
+//  (2) per fold, one wave: Cholesky of A_GG in place (lower triangle), u = L^-1 alpha_G by forward substitution, then the
+//      columns of X = L^-1 (lane j owns column j, kept in the upper triangle): diag(A_GG^-1)_j = sum_i X_ij^2 and
+//      (A_GG^-1 alpha_G)_j = sum_i X_ij u_i.
+// Every element of A_GG has one writer and every sum one fixed order, whatever wave runs an item: a tile's held-out bits do
+// not depend on the batch around it.  The fold arrays are global memory written by the host only; the kernel sorts nothing.
 template <int D, int KN>
-__global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const KernelArgs A) {
+__device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const int t, const long long o0, const bool failed) {
+    const int NB = c.NB, lane = c.lane;
+    double* __restrict__ mean = cv.mean + o0;
+    double* __restrict__ fvar = cv.f_var + o0;
+    double* __restrict__ yvar = cv.y_var + o0;
+    const int* __restrict__ rf = cv.row_fold + o0;
+    const int* __restrict__ rp = cv.row_pos + o0;
+    const double qnan = __builtin_nan("");
+    // rows that are never held out, and every row of a tile without a factor
+    for (int i = c.tid; i < c.N; i += NT)
+        if (failed || rf[i] < 0) { mean[i] = qnan; fvar[i] = qnan; yvar[i] = qnan; }
+    if (failed) return;
+    double* ag = c.ws + (size_t)c.vs0 * BLK;
+    // ---- (1)
+    const int pb = cv.pair_off[t], pe = cv.pair_off[t + 1];
+    for (int it = pb + c.w; it < pe; it += NW) {
+        const int pr = cv.pairs[it];
+        const int a = pr >> 16, b = pr & 0xffff;            // a >= b
+        f64x4 acc = zero4();
+        {
+            constexpr int PF = 4;                            // steps of loads in flight, as diag_chain
+            f64x4 Ar[PF], Br[PF];
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int kk = min(a + u, NB - 1);
+                Ar[u] = ldg_t<false>(c.ws, kk * NB + a, lane);
+                Br[u] = ldg_t<false>(c.ws, kk * NB + b, lane);
+            }
+            for (int k0 = a; k0 < NB; k0 += PF) {
+#pragma unroll
+                for (int u = 0; u < PF; ++u) {
+                    const int k = k0 + u;
+                    if (k < NB) {
+                        mma_blk(acc, Ar[u], Br[u]);
+                        const int kn = min(k + PF, NB - 1);
+                        Ar[u] = ldg_t<false>(c.ws, kn * NB + a, lane);
+                        Br[u] = ldg_t<false>(c.ws, kn * NB + b, lane);
+                    }
+                }
+            }
+        }
+        const int j = BS * b + c.g;
+        const int fj = (j < c.N) ? rf[j] : -1;
+        if (fj >= 0) {
+            const int gsz = cv.fold_ptr[fj + 1] - cv.fold_ptr[fj];
+            const int pj = rp[j];
+            double* Af = ag + cv.fold_a[fj];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = BS * a + rowof(r, c.q);
+                if (i < c.N && rf[i] == fj) {
+                    if (gsz == 1) {                          // i == j
+                        const double var = (acc[r] > 0.0) ? 1.0 / acc[r] : qnan;
+                        mean[i] = lds_d[c.L.y + i] - lds_d[c.L.alpha + i] * var;
+                        fvar[i] = var - c.sn2;
+                        yvar[i] = var;
+                    } else {
+                        const int pi = rp[i];
+                        Af[pi * gsz + pj] = acc[r];
+                        if (a != b) Af[pj * gsz + pi] = acc[r];
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- (2)
+    const int ub = c.L.Pn + c.w * 256;                      // u of this wave's fold (the panel buffer is idle)
+    for (int f = cv.fold_off[t] + c.w; f < cv.fold_off[t + 1]; f += NW) {
+        const int r0 = cv.fold_ptr[f];
+        const int g = cv.fold_ptr[f + 1] - r0;
+        if (g <= 1) continue;
+        const int* __restrict__ rows = cv.fold_rows + r0;
+        double* Af = ag + cv.fold_a[f];
+        bool bad = false;
+        for (int k = 0; k < g; ++k) {                        // left-looking Cholesky, column k
+            double sp = Af[k * g + k];
+            for (int m = 0; m < k; ++m) { const double l = Af[k * g + m]; sp = fma(-l, l, sp); }
+            if (!(sp > 0.0)) { bad = true; break; }
+            const double dk = sqrt(sp);
+            for (int i = k + 1 + lane; i < g; i += 64) {
+                double s = Af[i * g + k];
+#pragma unroll 4
+                for (int m = 0; m < k; ++m) s = fma(-Af[i * g + m], Af[k * g + m], s);
+                Af[i * g + k] = s / dk;
+            }
+            if (lane == 0) Af[k * g + k] = dk;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the column is this wave's operand from the next step on
+        }
+        if (bad) {
+            for (int k = lane; k < g; k += 64) { const int i = rows[k]; mean[i] = qnan; fvar[i] = qnan; yvar[i] = qnan; }
+            continue;
+        }
+        for (int k = 0; k < g; ++k) {                        // u = L^-1 alpha_G
+            double s = 0.0;
+            for (int m = lane; m < k; m += 64) s = fma(Af[k * g + m], lds_d[ub + m], s);
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) lds_d[ub + k] = (lds_d[c.L.alpha + rows[k]] - s) / Af[k * g + k];
+            wave_lds_sync();
+        }
+        for (int j = lane; j < g; j += 64) {                 // column j of X = L^-1
+            const double xjj = 1.0 / Af[j * g + j];
+            double ds = xjj * xjj, wsum = xjj * lds_d[ub + j];
+            for (int i = j + 1; i < g; ++i) {
+                double s = Af[i * g + j] * xjj;
+#pragma unroll 4
+                for (int m = j + 1; m < i; ++m) s = fma(Af[i * g + m], Af[j * g + m], s);
+                const double x = -s / Af[i * g + i];
+                Af[j * g + i] = x;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                ds = fma(x, x, ds);
+                wsum = fma(x, lds_d[ub + i], wsum);
+            }
+            const int i = rows[j];
+            mean[i] = lds_d[c.L.y + i] - wsum;
+            fvar[i] = ds - c.sn2;
+            yvar[i] = ds;
+        }
+        wave_lds_sync();                                     // u is overwritten by this wave's next fold
+    }
+}
+
+#endif
+
+template <int D, int KN>
+__global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const KernelArgs A CV_KERNEL_PARAM) {
     constexpr int H = D + 2;
     Ctx<D, KN> c;
     c.tid = threadIdx.x;
@@ -1358,6 +1515,10 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
                     for (long long qq = A.cov_off[t] + c.tid; qq < A.cov_off[t + 1]; qq += NT) f_cov[qq] = __builtin_nan("");
             }
         }
+#ifdef GPSAT_F64_CV
+        __syncthreads();                             // the prediction scratch of every wave is free
+        phase_cv<D, KN>(c, cvA, t, o0, sh->fail != 0);
+#endif
         if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #ifdef GPSAT_PROFILE
@@ -1366,7 +1527,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
 #endif
 }
 
-#ifndef GPSAT_F64_W4
+#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV)
 // ---------------------------------------------------------------------------------------------
 // the team kernel: KernelArgs::team_size workgroups per tile (see "Teams" above).  Workgroup b is member b % G of team
 // b / G; the team's workspace is the slab of its member 0.  The owner pops tiles, runs the optimiser and, before every
@@ -1564,6 +1725,28 @@ __global__ void __launch_bounds__(NT, 1) gp_team_kernel_f64(const KernelArgs A) 
 }
 #endif
 
+#ifdef GPSAT_F64_CV
+template <int D, int KN>
+static hipError_t launch_one_cv(const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
+    if (a.team_size > 1) return hipErrorInvalidValue;          // one workgroup per tile only
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, KN>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gp_tile_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a, cv);
+    return hipGetLastError();
+}
+
+template <int D>
+static hipError_t launch_d_cv(const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
+    switch (a.kernel) {
+        case 0: return launch_one_cv<D, 0>(a, cv, grid, smem, stream);
+        case 1: return launch_one_cv<D, 1>(a, cv, grid, smem, stream);
+        case 2: return launch_one_cv<D, 2>(a, cv, grid, smem, stream);
+        case 3: return launch_one_cv<D, 3>(a, cv, grid, smem, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+#else
 template <int D, int KN>
 static hipError_t launch_one(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
 #ifndef GPSAT_F64_W4
@@ -1593,8 +1776,21 @@ static hipError_t launch_d(const KernelArgs& a, int grid, size_t smem, hipStream
     }
 }
 
+#endif
+
 }  // namespace F64NS
 
+#ifdef GPSAT_F64_CV
+hipError_t F64FN(launch_tiles_cv_f64)(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
+    switch (D) {
+        case 1: return F64NS::launch_d_cv<1>(a, cv, grid, smem, stream);
+        case 2: return F64NS::launch_d_cv<2>(a, cv, grid, smem, stream);
+        case 3: return F64NS::launch_d_cv<3>(a, cv, grid, smem, stream);
+        case 4: return F64NS::launch_d_cv<4>(a, cv, grid, smem, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+#else
 size_t F64FN(shared_bytes_f64)(int D, int NBmax) {
     const size_t NP = (size_t)NBmax * F64NS::BS;
     size_t dbl = (sizeof(F64NS::Shared) + 15) / 16 * 2 + D * NP + 3 * NP + F64NS::BLK + 16 * 17 + 16 + 10 * F64NS::BLK + 4 * F64NS::BS + 2;
@@ -1623,5 +1819,7 @@ hipError_t F64FN(launch_tiles_f64)(int D, const KernelArgs& a, int grid, size_t 
         default: return hipErrorInvalidValue;
     }
 }
+
+#endif
 
 }  // namespace gpsat

@@ -18,13 +18,15 @@ struct Build {
     int (*state_words)();
     hipError_t (*launch)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
     size_t (*pq_floats_per_slot)(int D, int NBmax);           // nullptr: the build has no deferred predictions
+    // the same tile loop with the held-out phase (gpsat_fit_predict_batch_cv); nullptr: the build has none
+    hipError_t (*launch_cv)(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
 };
 enum { BUILD_F32_W4 = 0, BUILD_F32_W8 = 1, BUILD_F64_W8 = 2, BUILD_F64_W4 = 3 };
 const Build builds[4] = {
-    {shared_bytes, workspace_floats_per_wg, state_words, launch_tiles, pq_floats_per_slot},
-    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, launch_tiles_w8, nullptr},
-    {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, launch_tiles_f64, nullptr},
-    {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, launch_tiles_f64_w4, nullptr},
+    {shared_bytes, workspace_floats_per_wg, state_words, launch_tiles, pq_floats_per_slot, nullptr},
+    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, launch_tiles_w8, nullptr, nullptr},
+    {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, launch_tiles_f64, nullptr, launch_tiles_cv_f64},
+    {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, launch_tiles_f64_w4, nullptr, launch_tiles_cv_f64_w4},
 };
 
 // One developer knob (GPSAT_DEBUG_*, read through dev_env() only): whether it is set, and atoi of its text.

@@ -32,6 +32,9 @@ class BatchResult:
     cov_off: np.ndarray | None = None
     n_iter: np.ndarray | None = None   # [T] optimiser iterations completed (scipy nit)
     f_start: np.ndarray | None = None  # [T, S] multi-start: final objective of every start (+inf: its first evaluation failed)
+    cv_mean: object = None  # [sum N] held-out predictions (cv_fold given): "f*" of every row from the other folds of its tile
+    cv_f_var: object = None
+    cv_y_var: object = None
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -63,6 +66,29 @@ def centre_tiles(X, Xs, obs_off, pred_off, Z=None, z_off=None):
         c[nz] = np.add.reduceat(X, obs_off[:-1][nz], axis=0) / Ns[nz, None]
     out = X - np.repeat(c, Ns, axis=0), Xs - np.repeat(c, Ps, axis=0)
     return out if Z is None else out + (Z - np.repeat(c, np.diff(z_off), axis=0),)
+
+
+def factorise_folds(fold, N=None):
+    """Fold labels of any hashable kind -> int32 codes [N].  ``fold``: array-like of N labels, or a 2-D array whose equal rows
+    form a fold.  Integer labels below 0 keep their meaning (never held out) and are returned as -1; None / NaN labels
+    likewise.  Codes are dense and ascend with the first appearance of a label."""
+    import pandas as pd
+    a = np.asarray(fold)
+    if a.ndim == 2:
+        keys = pd.MultiIndex.from_arrays([a[:, k] for k in range(a.shape[1])]) if a.shape[1] != 1 else pd.Index(a[:, 0])
+        never = np.zeros(len(a), dtype=bool)
+    elif a.ndim == 1:
+        keys = pd.Index(a)
+        never = (a < 0) if np.issubdtype(a.dtype, np.integer) else np.asarray(pd.isna(a))
+    else:
+        raise ValueError(f"fold labels must be 1-D, or 2-D with one row per observation; got shape {a.shape}")
+    if N is not None and len(a) != N:
+        raise ValueError(f"{len(a)} fold labels for {N} rows")
+    codes = np.asarray(pd.factorize(keys)[0], dtype=np.int64)
+    codes[never] = -1
+    if (codes >= 0).any():                       # dense again after the never-held-out labels left
+        codes[codes >= 0] = pd.factorize(codes[codes >= 0])[0]
+    return codes.astype(np.int32)
 
 
 def _ptr(a):
@@ -170,7 +196,7 @@ class Engine:
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
-                          out=None, dtype="f32", full_cov=False, n_starts=None, starts=None) -> BatchResult:
+                          out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -181,6 +207,10 @@ class Engine:
         ``n_starts`` (an int): multi-start bounded L-BFGS-B in log space (gpsat_fit_predict_batch_ms): theta0 and the
         ``starts`` [T, n_starts - 1, H] (constrained space) per tile, the best final objective wins; ``f_start`` of the
         result holds every start's final objective.  None: the optimisers of gpsat_fit_predict_batch.
+        ``cv_fold``: "loo", or an int array [sum N] of fold labels (rows of one tile with equal label >= 0 are held out
+        together, a negative label is never held out): also return, per row, the prediction from the other folds of its
+        tile at the returned parameters (gpsat_fit_predict_batch_cv, fp64 only) as ``cv_mean``, ``cv_f_var``, ``cv_y_var``.
+        None: gpsat_fit_predict_batch, as ever.
         """
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable)
         obs_off, pred_off = meta[0]
@@ -215,6 +245,34 @@ class Engine:
             b.cov_off, b.f_cov = _ptr(cov_off), (fc.data_ptr() if device_mode else _ptr(fc))
         f_start = None
         name = "gpsat_fit_predict_batch"
+        if cv_fold is not None:
+            name = "gpsat_fit_predict_batch_cv"
+            if not hasattr(self._lib, name):
+                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_cv (held-out predictions)")
+            if n_starts is not None:
+                raise GpsatError("cv_fold and n_starts cannot be combined")
+            labels = None
+            if not (isinstance(cv_fold, str) and cv_fold == "loo"):
+                raw = np.asarray(cv_fold).reshape(-1)
+                if not np.issubdtype(raw.dtype, np.integer):
+                    raise GpsatError(f"cv_fold: integer labels wanted, got dtype {raw.dtype} (factorise_folds makes them)")
+                if raw.size and (int(raw.max()) > 2 ** 31 - 1 or int(raw.min()) < -2 ** 31):
+                    raise GpsatError("cv_fold: labels must fit int32 (the C ABI's label type); factorise_folds makes dense codes")
+                labels = np.ascontiguousarray(raw, dtype=np.int32)
+                if labels.shape != (sumN,):
+                    raise GpsatError(f"cv_fold: {labels.size} labels for {sumN} rows")
+            if device_mode:
+                import torch
+                cvo = tuple(torch.empty(max(sumN, 1), dtype=t_dt, device=X.device) for _ in range(3))
+            else:
+                cvo = tuple(np.empty(sumN, dtype=np_dt) for _ in range(3))
+            cv = L.GpsatCv()
+            cv.fold = _ptr(labels)
+            cv.cv_mean, cv.cv_f_var, cv.cv_y_var = ((a.data_ptr() if device_mode else _ptr(a)) for a in cvo)
+            rc = self._lib.gpsat_fit_predict_batch_cv(self._h, C.byref(b), C.byref(cv))
+            cvo = tuple(a[:sumN] for a in cvo)
+            return self._result(rc, name, res, preds, sumP, f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off,
+                                cv_mean=cvo[0], cv_f_var=cvo[1], cv_y_var=cvo[2])
         if n_starts is not None:
             name = "gpsat_fit_predict_batch_ms"
             if not hasattr(self._lib, name):

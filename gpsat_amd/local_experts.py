@@ -65,6 +65,15 @@ definition here is CALL-LAGGED: all tiles of one engine call start from the aver
 issued, and the average is then advanced over that call's tiles in expert order.  ``engine_chunk=1`` reproduces the
 reference's serial recurrence exactly; larger chunks trade its freshness for batching (sharded runs keep one average
 per rank).
+``cv="loo"`` / ``cv={"by": [columns of the data source]}`` (constructor; exact experts, ``dtype="f64"``, one shard): every
+tile also predicts each of its own rows from the tile's other folds (the row alone / the rows with equal values in the ``by``
+columns), at the tile's final parameters, from the factor it already has (theta is not fitted again
+without the fold).  Table ``cv_preds``, committed with the waves like ``preds``: expert index; ``_dim_0`` the row's position in
+the tile, ``obs_index`` its index label in the globally selected frame, the ``by`` columns, ``pred_loc_<c>`` its coordinates,
+the observation under ``obs_col`` (raw), ``f*``, ``f*_var``, ``y_var`` and ``f_bar`` in the units of ``preds``: the held-out
+prediction of the raw observation is ``f_bar + obs_scale * f*`` with variance ``obs_scale**2 * y_var``.  A fold above
+``gpsat_max_cv_fold`` rows, and a row with a missing value in a ``by`` column, is not held out (NaN rows, counted in
+``run_details.cv_rows_skipped``).
 """
 from __future__ import annotations
 
@@ -98,6 +107,10 @@ DTYPES = ("f32", "f64")
 # ----------------------------------------------------------------------------------------------------------
 # selection (fp64, reference semantics)
 # ----------------------------------------------------------------------------------------------------------
+def _as_list(v):
+    return [v] if isinstance(v, str) else list(v)
+
+
 def _load_frame(src):
     if isinstance(src, pd.DataFrame):
         return src
@@ -808,7 +821,7 @@ _Plan = make_dataclass("_Plan", [
 # ----------------------------------------------------------------------------------------------------------
 class BatchedLocalExpertOI:
     def __init__(self, expert_loc_config: dict, data_config: dict, model_config: dict, pred_loc_config: dict,
-                 engine=None, device_select: bool = False, dtype: Optional[str] = None):
+                 engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None):
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
         om = model_config.get("oi_model", "HipGPRModel")
@@ -824,6 +837,21 @@ class BatchedLocalExpertOI:
         if self.sgpr and dtype != "f64":
             raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
         self.dtype = dtype
+        # held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with equal
+        # values in those columns are held out together.  None: nothing of a run differs.
+        if cv is not None:
+            if not (cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
+                raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
+            if self.sgpr:
+                raise NotImplementedError("cv: held-out predictions are not built for SGPR experts (exact GP experts only)")
+            if dtype != "f64":
+                raise NotImplementedError(f"cv: held-out predictions are built in fp64 only: dtype must be 'f64', not {dtype!r}")
+            pks = [model_config.get("pred_kwargs"), model_config.get("replacement_pred_kwargs")]
+            if any((pk or {}).get("full_cov", False) for pk in pks):
+                raise NotImplementedError("cv: held-out predictions and pred_kwargs.full_cov cannot be combined "
+                                          "(the kernel returns one or the other in a call)")
+        self.cv = cv
+        self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
         # ---- data (local_experts.py:266-290)
         self.obs_col = data_config["obs_col"]
         self.coords_col = list(data_config["coords_col"])
@@ -834,6 +862,15 @@ class BatchedLocalExpertOI:
         static_gs, dynamic_gs = split_global_select(data_config.get("global_select"))
         df = data_select(_load_frame(data_config["data_source"]), static_gs)
         self.df = df
+        missing = [c for c in self.cv_by if c not in df.columns]
+        if missing:
+            raise KeyError(f"cv: columns {missing} are not in the data source")
+        # one code per distinct combination of the `by` columns over the whole frame: equal codes inside a tile = one fold;
+        # -1: a missing value in a `by` column, such a row is never held out
+        self._cv_codes = pd.factorize(pd.MultiIndex.from_frame(df[self.cv_by]) if len(self.cv_by) > 1 else df[self.cv_by[0]])[0] \
+            .astype(np.int64) if self.cv_by else None
+        if self.cv_by:
+            self._cv_codes[df[self.cv_by].isna().any(axis=1).values] = -1
         # ---- expert locations (local_experts.py:349-422)
         xl = _load_frame(expert_loc_config["source"])
         if expert_loc_config.get("sort_by") is not None:
@@ -1017,6 +1054,8 @@ class BatchedLocalExpertOI:
         elif rank is None or world_size is None:
             rank, world_size = d_rank, d_world
         in_group = (not logical) and world_size > 1 and d_world == world_size
+        if self.cv is not None and world_size > 1:
+            raise NotImplementedError("cv: held-out predictions are not built for sharded runs (world_size > 1, real or logical)")
         if world_size > 1 and not logical and not in_group and gather:
             # explicit rank / world_size without a process group of that size: the caller synchronises the ranks itself
             # (nothing here can separate reading the resume state from rank 0's writes, and nothing can gather)
@@ -1059,6 +1098,8 @@ class BatchedLocalExpertOI:
             else:
                 sh = shards[0]
                 out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
+                if self.cv is not None and sh.tables is None:
+                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped)
         finally:
             tf = time.perf_counter()                               # also after a fault: what was committed is on disk
             for sh in reversed(shards):
@@ -1257,6 +1298,8 @@ class BatchedLocalExpertOI:
             for f_ in [self._sub_pool().submit(sub, int(bounds[j]), int(bounds[j + 1])) for j in range(nsub)]:
                 f_.result()
         out = dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
+        if self.cv is not None:
+            out["cv_fold"], out["cv_skipped"] = self._cv_labels(plan, ids, Ns)
         if pf.sgpr:
             # per tile the inducing points HipSGPRModel picks: a seeded subset of the tile's scaled coordinates
             Zs = [select_inducing_points(X[o_off[j]:o_off[j + 1]], pf.n_inducing, pf.inducing_seed, int(plan.ex[i]))
@@ -1264,6 +1307,57 @@ class BatchedLocalExpertOI:
             out["z_off"] = np.concatenate([[0], np.cumsum([len(z) for z in Zs])]).astype(np.int64)
             out["Z"] = np.concatenate(Zs) if Zs else np.zeros((0, D))
         return out
+
+    def _cv_labels(self, plan, ids, Ns):
+        """The fold labels of one engine call's rows ("loo", or int32 [sum N]) and, per tile, the rows that are not held out
+        because their fold is above the kernel's limit (label -1)."""
+        skipped = np.zeros(len(ids), dtype=np.int64)
+        if not self.cv_by:
+            return "loo", skipped
+        rows = np.concatenate([plan.idx[plan.off[i]:plan.off[i + 1]] for i in ids]) if len(ids) else np.zeros(0, dtype=np.int64)
+        tile = np.repeat(np.arange(len(ids), dtype=np.int64), Ns)
+        code = self._cv_codes[rows]
+        known = code >= 0
+        key = tile * (int(self._cv_codes.max(initial=0)) + 1) + np.where(known, code, 0)
+        _, inv, cnt = np.unique(key[known], return_inverse=True, return_counts=True)
+        inv = inv.reshape(-1)
+        labels = np.full(len(rows), -1, dtype=np.int32)
+        labels[known] = inv
+        big = np.zeros(len(rows), dtype=bool)
+        if len(inv):
+            big[known] = cnt[inv] > L.max_cv_fold("f64", len(self.coords_col))
+        labels[big] = -1
+        skip = big | ~known
+        np.add.at(skipped, tile[skip], 1)
+        return labels, skipped
+
+    def _cv_frame(self, plan, items, cv_rows, f_bar):
+        """Table ``cv_preds`` of the tiles among ``items`` (``cv_rows``: per item the [N, 3] held-out f*, f*_var, y_var of its
+        rows, in the order of the tile; ``f_bar``: per item the tile's de-meaning constant): expert coordinates as the index,
+        like ``preds``, and the values in the units of ``preds`` -- the observation is ``f_bar + obs_scale f*`` plus noise."""
+        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
+        cnt = np.array([len(c) for c in cv_rows], dtype=np.int64)
+        rows = np.concatenate([plan.idx[plan.off[i]:plan.off[i + 1]] for i, n in zip(items, cnt) if n]).astype(np.int64) \
+            if cnt.sum() else np.zeros(0, dtype=np.int64)
+        vals = _cat([c for c in cv_rows if len(c)], 3)
+        tot = int(cnt.sum())
+        fr = {"_dim_0": np.arange(tot) - np.repeat(np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt),
+              "obs_index": self.df.index.values[rows]}
+        for c_ in self.cv_by:
+            fr[c_] = self.df[c_].values[rows]
+        for ci, c_ in enumerate(cc):
+            fr[f"pred_loc_{c_}"] = plan.coords_all[rows, ci]
+        fr[self.obs_col] = plan.obs_all[rows]
+        fr.update({"f*": vals[:, 0], "f*_var": vals[:, 1], "y_var": vals[:, 2], "f_bar": np.repeat(np.asarray(f_bar, dtype=np.float64), cnt)})
+        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
+
+    def _cv_tables(self, plan, tables, items, frames, skipped):
+        """``cv_preds`` and the run_details column ``cv_rows_skipped`` into a run's (or a wave's) tables."""
+        frames = [f_ for f_ in frames if len(f_)]
+        tables[f"cv_preds{plan.table_suffix}"] = pd.concat(frames) if len(frames) > 1 else (frames[0] if frames else pd.DataFrame())
+        rd = tables[f"run_details{plan.table_suffix}"]
+        assert len(rd) == len(items) == len(skipped)
+        rd["cv_rows_skipped"] = np.asarray(skipped, dtype=np.int64)
 
     def _cov_counts(self, plan, items, counts):
         """Full-covariance rows per item: P^2 where the item's profile wants ``full_cov``, else 0."""
@@ -1410,6 +1504,7 @@ class _ShardRunner:
         self.piece_futs, self.packs = {}, {}   # wave -> writes of its preds pieces; job -> its packed arrays (future)
         self.rows = ([], [], [])               # fixed, preds, cov of the closed waves
         self.tables, self.flush = None, []     # the only wave's tables; the flush queued last
+        self.open_cv, self.cv_frames, self.cv_skipped = {}, [], np.zeros(0, dtype=np.int64)   # held-out rows of the open waves; closed waves' frames
         self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
         self.counts = np.where(plan.kind[items] == 2, plan.n_pred[items] if plan.predict else 0, 0).astype(np.int64)
 
@@ -1498,6 +1593,8 @@ class _ShardRunner:
             if pf.sgpr:
                 r = eng_.sgpr_fit_predict_batch(z_off=pk["z_off"], Z=pk["Z"], theta0=p.theta0[ids], dtype="f64", **kw)
             else:
+                if self.oi.cv is not None:
+                    kw["cv_fold"] = pk["cv_fold"]
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
                                            **kw, **({"full_cov": True} if pf.full_cov else {}))
             t1 = time.perf_counter()
@@ -1524,6 +1621,14 @@ class _ShardRunner:
         fixed[loc_ids, H + _N_ITER] = r.n_iter if getattr(r, "n_iter", None) is not None else np.nan
         fixed[loc_ids, H + _SECONDS] = call_s / len(ids)
         fixed[loc_ids, H + _OBS_MEAN] = pk["mean"]
+        if self.oi.cv is not None:
+            cvr, skp = self.open_cv[wi]
+            cv3 = np.stack([np.asarray(r.cv_mean, dtype=np.float64), np.asarray(r.cv_f_var, dtype=np.float64),
+                            np.asarray(r.cv_y_var, dtype=np.float64)], axis=1)
+            o_off = pk["o_off"]
+            for kk, j in enumerate(loc_ids):
+                cvr[j] = cv3[o_off[kk]:o_off[kk + 1]]
+            skp[loc_ids] = pk["cv_skipped"]
         if p.predict:
             pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
                            np.asarray(r.y_var, dtype=np.float64)], axis=1)
@@ -1551,6 +1656,7 @@ class _ShardRunner:
         if wi not in self.open:
             n = len(self.waves[wi])
             self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
+            self.open_cv[wi] = ([np.zeros((0, 3))] * n, np.zeros(n, dtype=np.int64))
         return self.open[wi]
 
     def _close_waves_to(self, w):
@@ -1570,6 +1676,11 @@ class _ShardRunner:
         # built (after the flush is queued) only where it is returned -- the only wave of a run
         lazy = bool(pieces) and not p.want_cov
         tables = oi._tables(p, items, fixed, pred_cat, cov_cat, with_preds=not lazy)
+        cvr, skp = self.open_cv.pop(wi)
+        if oi.cv is not None:
+            self.cv_frames.append(oi._cv_frame(p, items, cvr, fixed[:, self.H + _OBS_MEAN]))
+            self.cv_skipped = np.concatenate([self.cv_skipped, skp])
+            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp)
         oi.timings["tables_s"] += time.perf_counter() - tt
         tf = time.perf_counter()
         # commit: these experts are done.  The parts are written by the writer thread while the next wave runs (one writer,

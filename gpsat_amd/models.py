@@ -342,6 +342,35 @@ class HipGPRModel:
             out["f_bar"] = f_bar
         return out
 
+    def cross_validate(self, fold=None, apply_scale=True) -> Dict[str, np.ndarray]:
+        """Held-out predictions at the model's current parameters (no optimisation, nothing is fitted again without the
+        fold): every row predicted from the rows of all OTHER folds, from the tile's own factor (gpsat_fit_predict_batch_cv).
+        ``fold``: None = leave-one-out; an array-like of N labels of any hashable kind, or a 2-D array whose equal rows form
+        a fold; integer labels < 0 and None / NaN labels are never held out (NaN results).  Returns "f*", "f*_var" and
+        "y_var", each [N] in the order of the model's rows, in the units ``predict`` returns its own (with "f_bar", the
+        tile's own de-meaning constant: it is not recomputed per fold).  Always computed in fp64, whatever ``dtype``.
+        ``apply_scale`` is accepted for symmetry with ``predict``: the model's coordinates are already scaled."""
+        from .engine import factorise_folds
+        N, D = self.coords.shape
+        nmax = L.max_tile_obs("f64", D)
+        if N > nmax:
+            raise ValueError(f"tile of {N} observations: held-out predictions take at most {nmax} (gpsat_max_tile_obs, fp64, D={D})")
+        labels = "loo"
+        if fold is not None:
+            labels = factorise_folds(fold, N)
+            gmax = L.max_cv_fold("f64", D)
+            counts = np.bincount(labels[labels >= 0]) if (labels >= 0).any() else np.zeros(1, dtype=int)
+            if counts.max() > gmax:
+                raise ValueError(f"a fold of {int(counts.max())} rows: at most {gmax} rows are held out together (gpsat_max_cv_fold)")
+        r = self._engine.fit_predict_batch(
+            dtype="f64", D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, 0]),
+            Xs=np.zeros((0, D)), theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
+            trainable=self._trainable, kernel=self.kernel, optimiser="none", max_iter=0, cv_fold=labels)
+        if r.status[0] in (2, 3):
+            raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
+        return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
+                "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N)}
+
 
 def select_inducing_points(coords: np.ndarray, num_inducing_points: int, seed: int = 0, expert_index: int = 0) -> np.ndarray:
     """Inducing points of one expert (GPflowSGPRModel.__init__, gpflow_models.py:836-847, made reproducible): all the
@@ -385,6 +414,9 @@ class HipSGPRModel(HipGPRModel):
     @property
     def param_names(self) -> List[str]:
         return ["lengthscales", "kernel_variance", "likelihood_variance", "inducing_points"]
+
+    def cross_validate(self, fold=None, apply_scale=True):
+        raise NotImplementedError("held-out predictions are built for exact experts (HipGPRModel) only, not for SGPR")
 
     def get_inducing_points(self) -> np.ndarray:
         """Inducing points [M, D] in the model's (scaled) coordinates."""
@@ -533,6 +565,9 @@ class HipSklearnGPRModel(HipGPRModel):
         """No effect: alpha is fixed, never trained."""
 
     # -- fit / objective / predict
+    def cross_validate(self, fold=None, apply_scale=True):
+        raise NotImplementedError("held-out predictions are built for HipGPRModel only, not for sklearn experts")
+
     def restart_starts(self, rng=None):
         """The n_restarts_optimizer further starts, constrained space [n, D + 2], drawn as sklearn draws them from
         ``check_random_state(random_state)`` (or ``rng``)."""

@@ -176,6 +176,43 @@ typedef struct gpsat_multistart {
  * with S > 1 (sklearn: "requires that all bounds are finite"). */
 int gpsat_fit_predict_batch_ms(gpsat_handle *h, const gpsat_batch *b, const gpsat_multistart *ms);
 
+/*
+ * Held-out (cross-validation) predictions from every tile's own factor: the extension of gpsat_fit_predict_batch_cv
+ * (fp64 only).  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ *
+ * After the tile's last evaluation, at the returned theta, every fold G of the tile (rows with the same label) is predicted
+ * from all OTHER rows of the tile, with A = K_y^-1 = L^-T L^-1 and alpha = K_y^-1 y:
+ *   A_GG = (L^-1[:, G])^T (L^-1[:, G]),  cv_mean_G = y_G - A_GG^-1 alpha_G,  cv_y_var_G = diag(A_GG^-1),
+ *   cv_f_var_G = cv_y_var_G - likelihood variance          (one row: Rasmussen & Williams eq. 5.12).
+ * theta is NOT fitted again without the fold.  Every other output of the call has the bits gpsat_fit_predict_batch returns.
+ * A tile's held-out values have the same bits alone, inside any batch and on a second call.  Rows of a fold whose A_GG is
+ * not positive definite, and all rows of a tile with status NOT_PD or NAN, are NaN.  A fold that is the whole tile returns
+ * the prior (mean 0, cv_f_var = kernel variance) up to rounding.
+ * Limits and memory: a fold holds at most gpsat_max_cv_fold() = 256 rows; the folds' matrices (sum g^2 <= 256 N doubles per
+ * tile) live in the prediction scratch of the tile's workspace, so the call needs no workspace beyond
+ * gpsat_fit_predict_batch's; the handle keeps the fold tables (about 3 int32 per row, 2 per fold, 1 per 16 x 16 block that
+ * holds two rows of one fold) and, in host mode, the three outputs (24 bytes per row) until gpsat_destroy.
+ * One workgroup runs every tile (no teams).
+ */
+typedef struct gpsat_cv {
+    const int32_t *fold;   /* [sum N] host; rows of one tile with equal label >= 0 are held out together;
+                              label < 0: the row is never held out (its outputs are NaN);
+                              NULL: every row is its own fold (leave-one-out).  Any int32 >= 0 is a label; labels need
+                              not be dense or sorted; the same value in two tiles names two unrelated folds */
+    void *cv_mean;         /* [sum N] host|device as b->memory, element type b->dtype */
+    void *cv_f_var;        /* [sum N] */
+    void *cv_y_var;        /* [sum N], may be NULL */
+    int32_t reserved[8];
+} gpsat_cv;
+
+/* as gpsat_fit_predict_batch, with the held-out predictions above.  GPSAT_EINVAL (with a message) for a dtype other than
+ * GPSAT_F64, a fold above the limit (the message names the tile and the label), cov_off / f_cov in the same call, a NULL
+ * cv, and a NULL cv_mean or cv_f_var. */
+int gpsat_fit_predict_batch_cv(gpsat_handle *h, const gpsat_batch *b, const gpsat_cv *cv);
+
+/* largest fold of gpsat_fit_predict_batch_cv (256 for GPSAT_F64, D = 1..4); 0 for GPSAT_F32 and unsupported arguments */
+int gpsat_max_cv_fold(int dtype, int D);
+
 /* library / ABI version (GPSAT_ABI_VERSION) */
 int gpsat_version(void);
 
