@@ -312,8 +312,33 @@ constexpr int SHARED_FLOATS = (int)((sizeof(Shared) + 15) / 16) * 4;
 
 __device__ __forceinline__ Shared* shared_state() { return reinterpret_cast<Shared*>(lds_f); }
 
-// float offsets into lds_f
-struct Lay { int xs, xsc, y, z, alpha, Ad, LT, U01, Wh, tmp, piv; };
+// float offsets into lds_f; end: the first float behind the last region
+struct Lay { int xs, xsc, y, z, alpha, Ad, LT, U01, Wh, tmp, piv, end; };
+
+// THE layout of a workgroup's LDS, for the kernel and for the host's allocation (shared_bytes): a region added here is
+// allocated.  Every region holds the largest tile of the launch (NBmax block columns).
+__host__ __device__ constexpr Lay lds_layout(int D, int NBmax) {
+    const int NPmax = NBmax * 32;
+    Lay L{};
+    int off = SHARED_FLOATS;
+    L.xs = off; off += D * NPmax;
+    L.xsc = off; off += D * NPmax;
+    L.y = off; off += NPmax;
+    L.z = off; off += NPmax;
+    L.alpha = off; off += NPmax;
+    L.LT = off; off += 4 * BLK;
+    L.U01 = off; off += 2 * BLK;
+    L.Wh = off; off += 4 * BLK;          // column wave: finished k-loop of the next group 0, parked for the chain wave
+    L.Ad = off; off += 32 * 33 + 3;       // 1059 -> keep the next offsets 16-B aligned
+    off = (off + 3) & ~3;
+    L.tmp = off; off += 32;
+    L.piv = off; off += 64;
+    L.end = off;
+    return L;
+}
+// floats allocated behind Lay::end, read by nobody: the allocation's size is part of the launch plan, which picks the build by
+// it and is pinned in tests/test_abi.py
+constexpr int LDS_SLACK_FLOATS = 3;
 
 template <int D, int KN>
 struct Ctx {
@@ -1997,21 +2022,8 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     c.w = c.tid >> 6;
     c.h = c.lane >> 5;
     c.g = c.lane & 31;
-    const int NPmax = A.NBmax * 32;
     Shared* sh = shared_state();
-    int off = SHARED_FLOATS;
-    c.L.xs = off; off += D * NPmax;
-    c.L.xsc = off; off += D * NPmax;
-    c.L.y = off; off += NPmax;
-    c.L.z = off; off += NPmax;
-    c.L.alpha = off; off += NPmax;
-    c.L.LT = off; off += 4 * BLK;
-    c.L.U01 = off; off += 2 * BLK;
-    c.L.Wh = off; off += 4 * BLK;          // column wave: finished k-loop of the next group 0, parked for the chain wave
-    c.L.Ad = off; off += 32 * 33 + 3;       // 1059 -> keep the next offsets 16-B aligned
-    off = (off + 3) & ~3;
-    c.L.tmp = off; off += 32;
-    c.L.piv = off; off += 64;
+    c.L = lds_layout(D, A.NBmax);
     float* const ws_own = A.ws + (size_t)blockIdx.x * A.ws_stride;
     c.ws = ws_own;
     c.zb = (int)(A.ws_stride / BLK) - 1;            // last block of the workgroup's workspace: zeros
@@ -2035,9 +2047,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
     if (c.tid < NW * 16) sh->prof[c.tid] = 0ull;
     const unsigned long long prof_k0 = __builtin_amdgcn_s_memtime(), prof_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    OptCfg o;
-    o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
-    o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    OptCfg o = opt_cfg(A);
     o.ms_S = A.ms_S; o.ms_starts = A.ms_starts; o.ms_state = A.ms_state; o.ms_fout = A.ms_fout;
 
     const bool sliced = A.seg_cost > 0;
@@ -2149,19 +2159,8 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
         c.cv0 = c.vs0 + NW * 2 * NB;
         c.gp0 = c.vs0 * (BLK * 4);
         if (c.N == 0) {
-            if (c.tid == 0) {
-                A.status[t] = 4; A.n_eval[t] = 0; A.nll[t] = 0.0;
-                if (A.n_iter) A.n_iter[t] = 0;
-                for (int i = 0; i < H; ++i) {
-                    A.theta[(size_t)t * H + i] = A.theta0[(size_t)t * H + i];
-                    if (A.grad) A.grad[(size_t)t * H + i] = 0.0;
-                }
-            }
-            // prior prediction for an empty tile
-            for (long long q = p0 + c.tid; q < p1; q += NT) {
-                const float sf2 = (float)A.theta0[(size_t)t * H + D], sn2 = (float)A.theta0[(size_t)t * H + D + 1];
-                A.f_mean[q] = 0.f; A.f_var[q] = sf2; A.y_var[q] = sf2 + sn2;
-            }
+            if (c.tid == 0) tile_out_empty(A, H, t);
+            tile_predict_prior(A, H, t, c.tid, p0, p1, A.f_mean, A.f_var, A.y_var);
             if (A.f_cov) {
                 // prior covariance K_** of an empty tile
                 const int Pn = (int)(p1 - p0);
@@ -2205,36 +2204,8 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
             lds_f[c.L.z + idx] = 0.f;
             lds_f[c.L.alpha + idx] = 0.f;
         }
-        if (resumed) {
-            // The state was written by another workgroup, possibly on another XCD (whose L2 is not coherent with this one).
-            // It travels through agent-scope atomic word accesses, which go to memory past the caches: no cache-wide
-            // write-back / invalidate (an agent-scope fence costs every workgroup of the XCD its L2 contents).  Every wave of
-            // the writer had drained its stores (s_waitcnt vmcnt(0)) and met the workgroup barrier before one lane published
-            // the ring entry that this workgroup's thread 0 has polled (sc1 load) ahead of the barrier above; every load of
-            // the state is an sc1 load to registers (MI355X_MICROARCH.md, inter-workgroup visibility: valid forms).
-            const unsigned* src = A.state + (size_t)t * A.state_words;
-            unsigned* dst = reinterpret_cast<unsigned*>(sh);
-            for (int i = c.tid; i < A.state_words; i += NT)
-                dst[i] = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (c.tid == 0) {
-            sh->n_eval = 0; sh->n_eval_opt = 0; sh->status = 5; sh->iter = 0; sh->hist_n = 0; sh->hist_pos = 0;
-            sh->last_dec = 1e300;
-            sh->fail = 0;
-            for (int i = 0; i < H; ++i) {
-                const double lo = A.lo[(size_t)t * H + i], hi = A.hi[(size_t)t * H + i];
-                const bool box = (lo == lo) && (hi == hi) && (fabs(lo) < 1e300) && (fabs(hi) < 1e300);
-                sh->box[i] = box ? 1 : 0;
-                sh->lo[i] = lo; sh->hi[i] = hi;
-                sh->shift[i] = (!box && i == D + 1) ? 1e-6 : 0.0;   // GPflow likelihood-variance lower bound
-                sh->trainable[i] = A.trainable[i] ? 1 : 0;
-                sh->theta[i] = A.theta0[(size_t)t * H + i];
-                sh->u[i] = u_of_theta(sh, i, sh->theta[i]);
-                sh->m1[i] = 0.0; sh->m2[i] = 0.0;
-            }
-            const bool optim = (o.optimiser != 0 && o.max_iter > 0);
-            sh->phase = optim ? PH_INIT : PH_FINAL;
-            sh->want_grad = optim ? 1 : o.want_grad_out;
-        }
+        if (resumed) state_load(sh, A, t, c.tid);
+        else if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
         const bool helpable = coop_on && NB >= A.coop_min_nb;
         if (c.tid == 0) {
             sh->hp[2] = -1;                        // the coordinates in LDS are this tile's, not a helped one's
@@ -2283,14 +2254,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
             __hip_atomic_store(&ctl_own->pa, PA_MAKE(sh->coop_seq, COOP_RELEASED), RLX_AGENT);
         }
         if (suspended) {
-            unsigned* dst = A.state + (size_t)t * A.state_words;
-            const unsigned* src = reinterpret_cast<const unsigned*>(sh);
-            for (int i = c.tid; i < A.state_words; i += NT)
-                __hip_atomic_store(&dst[i], src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // EVERY storing wave drains its own stores (a workgroup-scope fence emits no vmcnt wait on gfx950; inline asm
-            // so that no compiler pass can drop or move it), THEN the barrier, THEN one lane publishes the ring entry
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
+            state_save(sh, A, t, c.tid);
             if (c.tid == 0) {
                 if (defer_on) __hip_atomic_fetch_add(&A.cu_busy[my_cu], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 ring_push(A, t);
@@ -2317,18 +2281,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
         }
 #endif
         // ================= outputs + prediction from the factorisation at the accepted parameters
-        if (c.tid == 0) {
-            int st = sh->status;
-            if (sh->fail) st = (sh->nll == sh->nll) ? 2 : 3;
-            A.status[t] = st;
-            A.n_eval[t] = sh->n_eval_opt;
-            if (A.n_iter) A.n_iter[t] = sh->iter;
-            A.nll[t] = sh->fail ? __builtin_nan("") : sh->nll;
-            for (int i = 0; i < H; ++i) {
-                A.theta[(size_t)t * H + i] = sh->theta[i];
-                if (A.grad) A.grad[(size_t)t * H + i] = sh->fail ? __builtin_nan("") : sh->gth[i];
-            }
-        }
+        if (c.tid == 0) tile_out_finished(A, sh, H, t);
         bool deferred = false;
         if (c.P > 0) {
             if (!sh->fail) {
@@ -2347,11 +2300,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
                     predict_tile<D, KN>(c, A.Xs + (size_t)p0 * D, A.f_mean + p0, A.f_var + p0, A.y_var + p0, invl,
                                         A.f_cov ? A.f_cov + A.cov_off[t] : nullptr);
             } else {
-                for (long long q = p0 + c.tid; q < p1; q += NT) {
-                    A.f_mean[q] = __builtin_nanf(""); A.f_var[q] = __builtin_nanf(""); A.y_var[q] = __builtin_nanf("");
-                }
-                if (A.f_cov)
-                    for (long long q = A.cov_off[t] + c.tid; q < A.cov_off[t + 1]; q += NT) A.f_cov[q] = __builtin_nanf("");
+                tile_predict_nan(c.tid, p0, p1, A.f_mean, A.f_var, A.y_var, A.f_cov, A.cov_off, t);
             }
         }
         // a deferred tile stays unfinished until its prediction is written (pq_predict)
@@ -2377,8 +2326,7 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
 }
 
 size_t shared_bytes(int D, int NBmax) {
-    const size_t NP = (size_t)NBmax * 32;
-    size_t fl = (size_t)SHARED_FLOATS + 2 * D * NP + 3 * NP + 10 * BLK + 32 * 33 + 3 + 4 + 32 + 64;
+    const size_t fl = (size_t)lds_layout(D, NBmax).end + LDS_SLACK_FLOATS;
     return (fl * sizeof(float) + 15) & ~size_t(15);
 }
 

@@ -1,5 +1,11 @@
-// gpsat_opt.h -- per-workgroup optimiser state and the on-device L-BFGS / Adam driver shared by the fp32 and fp64
-// tile kernels (device code, thread 0 of a workgroup, fp64 arithmetic).  Included inside namespace gpsat.
+// gpsat_opt.h -- what the persistent kernels (fp32 tiles, fp64 tiles and teams, sparse experts) share, device code:
+//   * the per-workgroup optimiser state (Shared) and the on-device L-BFGS / L-BFGS-B / Adam driver (thread 0, fp64
+//     arithmetic), advanced once per evaluation by opt_advance;
+//   * the per-tile driver pieces around the evaluate / opt_advance loop (at the end of the file): OptCfg from the kernel
+//     arguments, a fresh tile's optimiser state, the outputs of an empty and of a finished tile, prior and NaN predictions,
+//     and the save / load of a suspended tile's state (time slicing).
+// The numerics -- evaluate, predict, the prior covariance of an empty tile -- stay with each kernel.
+// Included inside each kernel's namespace (under namespace gpsat), after GPSAT_NW is set.
 #ifndef GPSAT_OPT_H
 #define GPSAT_OPT_H
 
@@ -687,6 +693,118 @@ static __device__ __noinline__ void opt_advance(Shared* sh, int H, const OptCfg&
             sh->phase = PH_EXIT;
             return;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// per-tile driver pieces of the persistent kernels: what every kernel does around its evaluate / opt_advance loop.  `Args` is
+// KernelArgs or SgprArgs (the same field names for everything read here); H = D + 2 as for opt_advance.
+// ---------------------------------------------------------------------------------------------
+// the multi-start fields exist in KernelArgs only: those kernels copy them at the call site
+template <class Args>
+static __device__ __forceinline__ OptCfg opt_cfg(const Args& A) {
+    OptCfg o;
+    o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
+    o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    return o;
+}
+
+// thread 0: outputs of a tile without observations (its predictions are the prior: tile_predict_prior)
+template <class Args>
+static __device__ __forceinline__ void tile_out_empty(const Args& A, int H, int t) {
+    A.status[t] = 4; A.n_eval[t] = 0; A.nll[t] = 0.0;
+    if (A.n_iter) A.n_iter[t] = 0;
+    for (int i = 0; i < H; ++i) {
+        A.theta[(size_t)t * H + i] = A.theta0[(size_t)t * H + i];
+        if (A.grad) A.grad[(size_t)t * H + i] = 0.0;
+    }
+}
+
+// thread 0: optimiser state of a tile that starts (a resumed one loads its state: state_load)
+template <class Args>
+static __device__ __forceinline__ void opt_fresh_tile(Shared* sh, const Args& A, int H, int t, const OptCfg& o) {
+    sh->n_eval = 0; sh->n_eval_opt = 0; sh->status = 5; sh->iter = 0; sh->hist_n = 0; sh->hist_pos = 0;
+    sh->last_dec = 1e300;
+    sh->fail = 0;
+    for (int i = 0; i < H; ++i) {
+        const double lo = A.lo[(size_t)t * H + i], hi = A.hi[(size_t)t * H + i];
+        const bool box = (lo == lo) && (hi == hi) && (fabs(lo) < 1e300) && (fabs(hi) < 1e300);
+        sh->box[i] = box ? 1 : 0;
+        sh->lo[i] = lo; sh->hi[i] = hi;
+        sh->shift[i] = (!box && i == H - 1) ? 1e-6 : 0.0;   // GPflow likelihood-variance lower bound
+        sh->trainable[i] = A.trainable[i] ? 1 : 0;
+        sh->theta[i] = A.theta0[(size_t)t * H + i];
+        sh->u[i] = u_of_theta(sh, i, sh->theta[i]);
+        sh->m1[i] = 0.0; sh->m2[i] = 0.0;
+    }
+    const bool optim = (o.optimiser != 0 && o.max_iter > 0);
+    sh->phase = optim ? PH_INIT : PH_FINAL;
+    sh->want_grad = optim ? 1 : o.want_grad_out;
+}
+
+// thread 0: outputs of a tile whose optimiser has reached PH_EXIT; a failed last evaluation gives status 2 (not positive
+// definite) or 3 (NaN objective) and NaN objective / gradient
+template <class Args>
+static __device__ __forceinline__ void tile_out_finished(const Args& A, const Shared* sh, int H, int t) {
+    int st = sh->status;
+    if (sh->fail) st = (sh->nll == sh->nll) ? 2 : 3;
+    A.status[t] = st;
+    A.n_eval[t] = sh->n_eval_opt;
+    if (A.n_iter) A.n_iter[t] = sh->iter;
+    A.nll[t] = sh->fail ? __builtin_nan("") : sh->nll;
+    for (int i = 0; i < H; ++i) {
+        A.theta[(size_t)t * H + i] = sh->theta[i];
+        if (A.grad) A.grad[(size_t)t * H + i] = sh->fail ? __builtin_nan("") : sh->gth[i];
+    }
+}
+
+// all threads: predictions [p0, p1) of a tile without observations are the prior at theta0 (T: the kernel's output scalar).
+// The prior covariance K_** needs the covariance function: it stays with the kernels.
+template <class T, class Args>
+static __device__ __forceinline__ void tile_predict_prior(const Args& A, int H, int t, int tid, long long p0, long long p1,
+                                                          T* f_mean, T* f_var, T* y_var) {
+    for (long long q = p0 + tid; q < p1; q += NT) {
+        const T sf2 = (T)A.theta0[(size_t)t * H + H - 2], sn2 = (T)A.theta0[(size_t)t * H + H - 1];
+        f_mean[q] = (T)0; f_var[q] = sf2; y_var[q] = sf2 + sn2;
+    }
+}
+
+// all threads: NaN predictions [p0, p1) of a tile whose last evaluation failed; kernels with a full covariance output pass
+// it (or nullptr) and the tiles' offsets into it, and tile t's elements become NaN too
+template <class T>
+static __device__ __forceinline__ void tile_predict_nan(int tid, long long p0, long long p1, T* f_mean, T* f_var, T* y_var,
+                                                        T* f_cov = nullptr, const long long* cov_off = nullptr, int t = 0) {
+    const T qnan = (T)__builtin_nan("");
+    for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = qnan; f_var[q] = qnan; y_var[q] = qnan; }
+    if (f_cov)
+        for (long long q = cov_off[t] + tid; q < cov_off[t + 1]; q += NT) f_cov[q] = qnan;
+}
+
+// Time slicing (KernelArgs::seg_cost > 0): a suspended tile's optimiser state, the first A.state_words words of Shared, waits
+// in A.state until any workgroup pops the tile's ring entry again.
+//
+// The state was written by another workgroup, possibly on another XCD (whose L2 is not coherent with this one).
+// It travels through agent-scope atomic word accesses, which go to memory past the caches: no cache-wide
+// write-back / invalidate (an agent-scope fence costs every workgroup of the XCD its L2 contents).  Every wave of
+// the writer had drained its stores (s_waitcnt vmcnt(0)) and met the workgroup barrier before one lane published
+// the ring entry that this workgroup's thread 0 has polled (sc1 load) ahead of the barrier behind the pop; every load of
+// the state is an sc1 load to registers (MI355X_MICROARCH.md, inter-workgroup visibility: valid forms).
+static __device__ __forceinline__ void state_load(Shared* sh, const KernelArgs& A, int t, int tid) {
+    const unsigned* src = A.state + (size_t)t * A.state_words;
+    unsigned* dst = reinterpret_cast<unsigned*>(sh);
+    for (int i = tid; i < A.state_words; i += NT)
+        dst[i] = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// all threads; behind it ONE lane publishes the ring entry (ring_push, at the call site)
+static __device__ __forceinline__ void state_save(const Shared* sh, const KernelArgs& A, int t, int tid) {
+    unsigned* dst = A.state + (size_t)t * A.state_words;
+    const unsigned* src = reinterpret_cast<const unsigned*>(sh);
+    for (int i = tid; i < A.state_words; i += NT)
+        __hip_atomic_store(&dst[i], src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // EVERY storing wave drains its own stores (a workgroup-scope fence emits no vmcnt wait on gfx950; inline asm
+    // so that no compiler pass can drop or move it), THEN the barrier, THEN the publish
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
 }
 
 

@@ -524,9 +524,7 @@ __global__ void __launch_bounds__(NT, 1) sgpr_kernel(const SgprArgs A) {
     c.Mmax = A.Mmax;
     c.MS = mat_stride(A.Mmax);
     c.ws = A.ws + (size_t)blockIdx.x * A.ws_stride;
-    OptCfg o;
-    o.optimiser = A.optimiser; o.max_iter = A.max_iter; o.max_ls = A.max_ls; o.want_grad_out = A.grad != nullptr;
-    o.ftol = A.ftol; o.gtol = A.gtol; o.adam_lr = A.adam_lr; o.noise_rel = A.noise_rel;
+    const OptCfg o = opt_cfg(A);
     for (;;) {
         __syncthreads();
         if (c.tid == 0) {
@@ -542,40 +540,12 @@ __global__ void __launch_bounds__(NT, 1) sgpr_kernel(const SgprArgs A) {
         c.N = (int)(o1 - o0); c.P = (int)(p1 - p0); c.M = (int)(z1 - z0);
         c.X = A.X + (size_t)o0 * D; c.y = A.y + o0;
         if (c.N == 0) {
-            if (c.tid == 0) {
-                A.status[t] = 4; A.n_eval[t] = 0; A.nll[t] = 0.0;
-                if (A.n_iter) A.n_iter[t] = 0;
-                for (int i = 0; i < H; ++i) {
-                    A.theta[(size_t)t * H + i] = A.theta0[(size_t)t * H + i];
-                    if (A.grad) A.grad[(size_t)t * H + i] = 0.0;
-                }
-            }
-            for (long long qq = p0 + c.tid; qq < p1; qq += NT) {
-                const double sf2 = A.theta0[(size_t)t * H + D], sn2 = A.theta0[(size_t)t * H + D + 1];
-                A.f_mean[qq] = 0.0; A.f_var[qq] = sf2; A.y_var[qq] = sf2 + sn2;
-            }
+            if (c.tid == 0) tile_out_empty(A, H, t);
+            tile_predict_prior(A, H, t, c.tid, p0, p1, A.f_mean, A.f_var, A.y_var);
             continue;
         }
         for (int i = c.tid; i < c.M * D; i += NT) c.zl[i] = A.Z[(size_t)z0 * D + i];
-        if (c.tid == 0) {
-            sh->n_eval = 0; sh->n_eval_opt = 0; sh->status = 5; sh->iter = 0; sh->hist_n = 0; sh->hist_pos = 0;
-            sh->last_dec = 1e300;
-            sh->fail = 0;
-            for (int i = 0; i < H; ++i) {
-                const double lo = A.lo[(size_t)t * H + i], hi = A.hi[(size_t)t * H + i];
-                const bool box = (lo == lo) && (hi == hi) && (fabs(lo) < 1e300) && (fabs(hi) < 1e300);
-                sh->box[i] = box ? 1 : 0;
-                sh->lo[i] = lo; sh->hi[i] = hi;
-                sh->shift[i] = (!box && i == D + 1) ? 1e-6 : 0.0;
-                sh->trainable[i] = A.trainable[i] ? 1 : 0;
-                sh->theta[i] = A.theta0[(size_t)t * H + i];
-                sh->u[i] = u_of_theta(sh, i, sh->theta[i]);
-                sh->m1[i] = 0.0; sh->m2[i] = 0.0;
-            }
-            const bool optim = (o.optimiser != 0 && o.max_iter > 0);
-            sh->phase = optim ? PH_INIT : PH_FINAL;
-            sh->want_grad = optim ? 1 : o.want_grad_out;
-        }
+        if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
         __syncthreads();
         for (;;) {
             evaluate<D, KN>(c, sh, sh->want_grad != 0, A.jitter, flag);
@@ -583,25 +553,12 @@ __global__ void __launch_bounds__(NT, 1) sgpr_kernel(const SgprArgs A) {
             __syncthreads();
             if (sh->phase == PH_EXIT) break;
         }
-        if (c.tid == 0) {
-            int st = sh->status;
-            if (sh->fail) st = (sh->nll == sh->nll) ? 2 : 3;
-            A.status[t] = st;
-            A.n_eval[t] = sh->n_eval_opt;
-            if (A.n_iter) A.n_iter[t] = sh->iter;
-            A.nll[t] = sh->fail ? __builtin_nan("") : sh->nll;
-            for (int i = 0; i < H; ++i) {
-                A.theta[(size_t)t * H + i] = sh->theta[i];
-                if (A.grad) A.grad[(size_t)t * H + i] = sh->fail ? __builtin_nan("") : sh->gth[i];
-            }
-        }
+        if (c.tid == 0) tile_out_finished(A, sh, H, t);
         if (c.P > 0) {
             if (!sh->fail) {
                 predict<D, KN>(c, sh, A.Xs + (size_t)p0 * D, A.f_mean + p0, A.f_var + p0, A.y_var + p0);
             } else {
-                for (long long qq = p0 + c.tid; qq < p1; qq += NT) {
-                    A.f_mean[qq] = __builtin_nan(""); A.f_var[qq] = __builtin_nan(""); A.y_var[qq] = __builtin_nan("");
-                }
+                tile_predict_nan(c.tid, p0, p1, A.f_mean, A.f_var, A.y_var);
             }
         }
     }

@@ -48,6 +48,7 @@ def _same(a, b):
     ("Matern32", [1500, 1100, 2047, 0, 1793], dict(optimiser="lbfgs", max_iter=2)),
     ("Matern52", [1601], dict(optimiser="none", want_grad=True, full_cov=True)),
     ("Matern12", [1280], dict(optimiser="adam", max_iter=3, adam_lr=0.05)),
+    ("Matern52", [1100, 0], dict(optimiser="none", full_cov=True)),       # an empty tile's K_** is the prior under a team too
 ])
 def test_team_returns_the_bits_of_one_workgroup(eng, kernel, Ns, extra):
     kid = {"RBF": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3}[kernel]
