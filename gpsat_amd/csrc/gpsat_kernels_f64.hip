@@ -159,27 +159,7 @@ __device__ __forceinline__ void wave_lds_sync() {
     asm volatile("" ::: "memory");
 }
 
-template <int KERN>
-__device__ __forceinline__ void kfun(double r2, double& kf, double& gg) {
-    if (KERN == 0) {
-        kf = exp(-0.5 * r2);
-        gg = kf;
-    } else {
-        const double r = sqrt(fmax(r2, 1e-36));
-        if (KERN == 1) {
-            kf = exp(-r);
-            gg = kf / r;
-        } else if (KERN == 2) {
-            const double s = 1.7320508075688772 * r, e = exp(-s);
-            kf = (1.0 + s) * e;
-            gg = 3.0 * e;
-        } else {
-            const double s = 2.23606797749979 * r, e = exp(-s);
-            kf = (1.0 + s + s * s * (1.0 / 3.0)) * e;
-            gg = (5.0 / 3.0) * (1.0 + s) * e;
-        }
-    }
-}
+#include "gpsat_kfun_f64.h"
 
 struct Lay { int xsc, y, z, alpha, Ad, LT, tmp, Pn, tp4, PnLA, tpLA, end; };   // double offsets into lds_d; end: behind the last region
 

@@ -42,27 +42,7 @@ __host__ __device__ inline size_t mat_stride(int Mmax) { return (size_t)Mmax * M
 __host__ __device__ inline int n_mats(int D) { return 7 + D; }
 
 // covariance function of r^2 (r = scaled distance): kf = k / s and gg with dk/dl_d = s gg (x_d - z_d)^2 / l_d^3
-template <int KERN>
-__device__ __forceinline__ void kfun(double r2, double& kf, double& gg) {
-    if (KERN == 0) {
-        kf = exp(-0.5 * r2);
-        gg = kf;
-    } else {
-        const double r = sqrt(fmax(r2, 1e-36));
-        if (KERN == 1) {
-            kf = exp(-r);
-            gg = kf / r;
-        } else if (KERN == 2) {
-            const double s = 1.7320508075688772 * r, e = exp(-s);
-            kf = (1.0 + s) * e;
-            gg = 3.0 * e;
-        } else {
-            const double s = 2.23606797749979 * r, e = exp(-s);
-            kf = (1.0 + s + s * s * (1.0 / 3.0)) * e;
-            gg = (5.0 / 3.0) * (1.0 + s) * e;
-        }
-    }
-}
+#include "gpsat_kfun_f64.h"
 
 // k(z, x) = s kf and dk/dl_d = s gg t_d^2 / l_d with t_d = (z_d - x_d) / l_d
 template <int D, int KN, bool G>

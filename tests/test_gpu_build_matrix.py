@@ -152,6 +152,35 @@ def test_four_wave_build_every_instantiation_matches_oracle(eng, eng8, n_cu, D, 
     _same(r, _run(eng8, big, thb, kid), "4-wave vs 8-wave build")
 
 
+def _kloop_batch(D, kid):
+    """every block count from 1 to 9, with the last block holding one observation and full"""
+    Ns = [n for nb in range(1, 10) for n in (32 * nb - 31, 32 * nb)]
+    Pv = [0, 1, 31, 32, 33, 64, 65, 96]
+    Ps = [Pv[i % len(Pv)] for i in range(len(Ns))]
+    b = syn.make_batch(len(Ns), Ns, Ps, D, kid, base_seed=6000 + 100 * D + 10 * kid)
+    return b, _theta(np.random.default_rng(60 + 10 * D + kid), len(Ns), D)
+
+
+@pytest.mark.parametrize("D,kid", [(3, 0), (2, 2)], ids=["D3-RBF", "D2-Matern32"])
+def test_four_wave_build_every_small_block_count_matches_oracle(eng, eng8, n_cu, D, kid):
+    """The k-loops are software pipelines of depth 2, 3 and 4 over n = 2 x (block rows) half steps: prologue, rotation and
+    tail depend on n modulo the depth and on n < depth - 1, and an odd block count leaves the last panel without its second
+    column.  18 tiles, NB = 1 .. 9 with the last block holding one observation or full, P across the chunk boundaries
+    (and none), replicated to at least one tile per CU (the 4-wave build).  Every distinct tile against the oracle, every
+    copy bit-identical to the first, the same bits from the 8-wave build."""
+    b, th = _kloop_batch(D, kid)
+    T = b["T"]
+    assert T == 18 and sorted({-(-int(n) // 32) for n in np.diff(b["obs_off"])}) == list(range(1, 10))
+    rep = -(-n_cu // T)
+    big, thb = _replicate(b, th, rep)
+    r = _run(eng, big, thb, kid)
+    assert (r.status == 5).all() and (r.theta == thb).all()
+    for t in range(T):
+        _check_eval(r, b, t, th[t], kid)
+    _replicas_identical(r, T, int(b["pred_off"][-1]), rep)
+    _same(r, _run(eng8, big, thb, kid), "4-wave vs 8-wave build")
+
+
 def test_four_wave_build_full_covariance_matches_oracle(eng, n_cu):
     D, kid = 3, 0
     b, th = _w4_batch(D, kid)
