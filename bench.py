@@ -26,9 +26,16 @@ on the arguments only, so two builds run with the same arguments can be compared
 ``python bench.py --gpus N`` without a torch.distributed environment starts the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py``, before this process touches the GPU) and relays the line.
 
-Prints ONE JSON line on rank 0.  ``value`` = whole-job tiles/s with inputs resident in HBM; ``host_to_host_ms`` is the
-same step timed from packed host arrays to outputs on the host (SURVEY.md 8(d)'s definition, PCIe included) -- context,
-never ``value``.
+Prints ONE JSON line on rank 0.  ``value`` = whole-job tiles/s with inputs resident in HBM.
+
+A plain run sets up, warms up, times the steps, writes ``--dump-outputs`` and prints the line (the roofline block comes
+from the timed steps' own kernel times).  ``--full`` adds, outside the timed region and with the same headline, what takes
+runs of its own: ``cpu_baseline`` (the fp64 oracle and scikit-learn on a sample of the same tiles, before the GPU is
+initialised), ``host_to_host_ms`` (the same step timed from packed host arrays to outputs on the host, SURVEY.md 8(d)'s
+definition, PCIe included -- context, never ``value``; null in a plain run), ``quality`` (the same tiles run to
+convergence by the fp64 kernels) and ``other_workloads`` (two steps each of configs2, configs4 and f64fit).  Each of these
+has a switch that takes it out of a full run again (``--cpu-tiles 0``, ``--no-host-leg``, ``--no-quality``,
+``--no-other-workloads``).
 """
 import argparse
 import json
@@ -391,7 +398,9 @@ def dump_outputs(out_dir, r, pred_off, budget=DUMP_BYTES):
     return {k: list(v.shape) for k, v in arrays.items()}
 
 
-def main():
+def parse_args(argv=None):
+    """A plain run does what the headline needs and nothing else; the other legs run with --full, each unless its own
+    switch takes it out again.  Without --full those switches change nothing."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -405,22 +414,31 @@ def main():
     ap.add_argument("--optimiser", default="lbfgs")
     ap.add_argument("--max-iter", type=int, default=20)
     ap.add_argument("--exact-iters", action="store_true", help="early stopping off: exactly max_iter iterations per tile")
-    ap.add_argument("--cpu-tiles", type=int, default=-1, help="tiles in the CPU baseline sample (0 = skip, -1 = auto)")
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the host-to-host timing")
+    ap.add_argument("--cpu-tiles", type=int, default=-1, help="with --full: tiles in the CPU baseline sample (0 = skip, -1 = auto)")
+    ap.add_argument("--no-host-leg", action="store_true", help="with --full: skip the host-to-host timing")
     ap.add_argument("--wg-per-cu", type=int, default=0)
     ap.add_argument("--workers", type=int, default=0, help="host processes for data generation / CPU baseline "
                     "(0 = auto; use 1 under rocprofv3 --pmc: no fork beside the profiler)")
     ap.add_argument("--workload", default="configs1", choices=["configs1", "configs2", "configs4", "f64fit"])
-    ap.add_argument("--no-sklearn", action="store_true", help="skip the scikit-learn line of the CPU baseline")
-    ap.add_argument("--no-quality", action="store_true", help="skip the result-quality block (fp64 converged reference run)")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the two-step runs of configs[2], configs[4] per GPU and the "
+    ap.add_argument("--no-sklearn", action="store_true", help="with --full: skip the scikit-learn line of the CPU baseline")
+    ap.add_argument("--no-quality", action="store_true", help="with --full: skip the result-quality block (fp64 converged reference run)")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the two-step runs of configs[2], configs[4] per GPU and the "
                     "fp64 fit that follow the headline's timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0's tiles) as DIR/<name>.npy, "
                     f"at most {DUMP_BYTES // 10 ** 6} MB (a fixed sample of tiles beyond that)")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline's timed steps also measure everything else: the CPU "
+                    "baseline, the host-to-host step, the result-quality block and the other workloads (off by default)")
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:
+        a.cpu_tiles, a.no_host_leg, a.no_quality, a.no_other_workloads = 0, True, True, True
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: start the N ranks as a CHILD torch.distributed.run (this process has not touched the

@@ -78,3 +78,23 @@ def test_bench_inputs_do_not_depend_on_the_blas_thread_count():
 def test_steps_below_one_are_refused_before_the_gpu_is_touched():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and "--steps" in p.stderr
+
+
+LEGS = ("cpu_tiles", "no_host_leg", "no_quality", "no_other_workloads")
+
+
+def test_a_plain_run_has_no_leg_beyond_the_headline_and_full_has_them_all():
+    """Every leg of the benchmark outside setting up, warming up, the timed steps, --dump-outputs and the result line is
+    decided by these four arguments (bench.main reads nothing else for them)."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and [getattr(plain, k) for k in LEGS] == [0, True, True, True]
+    # the legs' own switches and sizes change nothing without --full
+    same = bench.parse_args(["--cpu-tiles", "64", "--no-sklearn"])
+    assert [getattr(same, k) for k in LEGS] == [0, True, True, True]
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and [getattr(full, k) for k in LEGS] == [-1, False, False, False] and not full.no_sklearn
+    # ... and take their leg out of a full run as before
+    part = bench.parse_args(["--full", "--cpu-tiles", "0", "--no-host-leg", "--no-other-workloads"])
+    assert [getattr(part, k) for k in LEGS] == [0, True, False, True]
+    for k in ("steps", "warmup", "tiles", "nobs", "npred", "dim", "kernel", "optimiser", "max_iter", "workload", "dump_outputs"):
+        assert getattr(plain, k) == getattr(full, k)                # the timed workload is the same one
