@@ -25,9 +25,10 @@ EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_cre
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
            "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
-           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold"]
+           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
-OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold"]
+OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold",
+                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit"]
 
 
 class GpsatOpts(C.Structure):
@@ -64,6 +65,16 @@ class GpsatCv(C.Structure):
     _fields_ = [("fold", C.c_void_p), ("cv_mean", C.c_void_p), ("cv_f_var", C.c_void_p), ("cv_y_var", C.c_void_p),
                 ("reserved", C.c_int32 * 8)]
 
+
+class GpsatCvRefit(C.Structure):
+    _fields_ = [("fold", C.c_void_p), ("start", C.c_int32), ("recentre", C.c_int32), ("min_obs", C.c_int32),
+                ("fold_off", C.c_void_p), ("cv_mean", C.c_void_p), ("cv_f_var", C.c_void_p), ("cv_y_var", C.c_void_p),
+                ("fold_theta", C.c_void_p), ("fold_nll", C.c_void_p), ("fold_shift", C.c_void_p),
+                ("fold_status", C.c_void_p), ("fold_n_eval", C.c_void_p), ("fold_n_iter", C.c_void_p),
+                ("fold_n_obs", C.c_void_p), ("fold_label", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
+CV_START_IDS = {"theta0": 0, "full": 1}
 
 SEL_MAXCRIT = 4
 COMP_IDS = {">=": 0, ">": 1, "==": 2, "<": 3, "<=": 4}
@@ -170,6 +181,11 @@ def load():
         lib.gpsat_fit_predict_batch_cv.restype = C.c_int
         lib.gpsat_max_cv_fold.argtypes = [C.c_int, C.c_int]
         lib.gpsat_max_cv_fold.restype = C.c_int
+    if hasattr(lib, "gpsat_fit_predict_batch_cv_refit"):
+        lib.gpsat_cv_refit_count.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.gpsat_cv_refit_count.restype = C.c_int
+        lib.gpsat_fit_predict_batch_cv_refit.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatCvRefit)]
+        lib.gpsat_fit_predict_batch_cv_refit.restype = C.c_int
     if hasattr(lib, "gpsat_bin_batch"):
         lib.gpsat_bin_batch.restype = C.c_int
         lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,

@@ -2,7 +2,8 @@
 // reference interfaces each entry point replaces).  Host-side responsibilities only: argument
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
 // gpsat_fit_predict_batch in steps: check_batch / check_multistart / check_cv, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
-// setup_*, launch, fetch_batch / fetch_cv, record_timing.
+// setup_*, launch, fetch_batch / fetch_cv, record_timing.  gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice:
+// for the batch, and for the batch of its folds that gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -17,6 +18,7 @@
 #include "gpsat_hip.h"
 #include "gpsat_kernels.h"
 #include "gpsat_plan.h"
+#include "gpsat_cvfold.h"
 
 namespace {
 
@@ -128,6 +130,7 @@ struct gpsat_handle : HandleQueue {
     // device buffers (grown lazily, owned by the handle, freed by its destructor)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
+    DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
     DevBuf bin_in, bin_keys, bin_rows, bin_vals, bin_runs, bin_tmp, bin_out;     // gpsat_bin_batch
@@ -695,6 +698,162 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
     }
 }
 
+// ---- refitted cross-validation (gpsat_fit_predict_batch_cv_refit): the plain batch, then every fitted fold as a tile of a
+// second, device-resident batch through fit_predict itself; gpsat_cvfold.hip builds that batch and puts its predictions back.
+int check_cv_refit(const gpsat_batch* b, const gpsat_cv_refit* cv, gpsat::CvFoldTables& tb) {
+    const char* who = "gpsat_cv_refit: ";
+    if (!cv->fold) return fail(GPSAT_EINVAL, std::string(who) + "fold is NULL");
+    if (!cv->fold_off) return fail(GPSAT_EINVAL, std::string(who) + "fold_off is NULL");
+    if (!cv->cv_mean) return fail(GPSAT_EINVAL, std::string(who) + "cv_mean is NULL");
+    if (!cv->cv_f_var) return fail(GPSAT_EINVAL, std::string(who) + "cv_f_var is NULL");
+    if (cv->start != 0 && cv->start != 1) return fail(GPSAT_EINVAL, std::string(who) + "start must be 0 (theta0) or 1 (the tile's full-data theta)");
+    if (cv->recentre != 0 && cv->recentre != 1) return fail(GPSAT_EINVAL, std::string(who) + "recentre must be 0 or 1");
+    if (b->cov_off || b->f_cov)
+        return fail(GPSAT_EINVAL, std::string(who) + "refitted held-out predictions and the full covariance cannot be asked for in the same call: cov_off / f_cov must be NULL");
+    const std::string err = gpsat::cvfold_tables(b->T, b->obs_off, cv->fold, true, tb);
+    if (!err.empty()) return fail(GPSAT_EINVAL, who + err);
+    for (int t = 0; t <= b->T; ++t)
+        if (cv->fold_off[t] != tb.fold_off[t])
+            return fail(GPSAT_EINVAL, std::string(who) + "fold_off[" + std::to_string(t) + "] = " + std::to_string(cv->fold_off[t]) +
+                                          " differs from gpsat_cv_refit_count's " + std::to_string(tb.fold_off[t]));
+    if (tb.fold_off[b->T] > 0) {
+        const std::pair<const void*, const char*> outs[] = {{cv->fold_theta, "fold_theta"}, {cv->fold_nll, "fold_nll"}, {cv->fold_shift, "fold_shift"},
+            {cv->fold_status, "fold_status"}, {cv->fold_n_eval, "fold_n_eval"}, {cv->fold_n_obs, "fold_n_obs"}, {cv->fold_label, "fold_label"}};
+        for (const auto& o : outs)
+            if (!o.first) return fail(GPSAT_EINVAL, std::string(who) + o.second + " is NULL");
+    }
+    return GPSAT_OK;
+}
+
+int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
+    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL handle or batch");
+    if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL gpsat_cv_refit");
+    if (b->T == 0) return GPSAT_OK;
+    BatchDims d;
+    int rc;
+    if ((rc = check_batch(b, false, d))) return rc;
+    gpsat::CvFoldTables tb;
+    if ((rc = check_cv_refit(b, cv, tb))) return rc;
+    // ---- 1. the batch itself
+    if ((rc = fit_predict(h, b, nullptr))) return rc;
+    double kernel_ms = h->last_kernel_ms, total_ms = h->last_total_ms;
+    const int T = b->T, D = b->D, H = D + 2;
+    const bool f64 = b->dtype == GPSAT_F64, host = b->memory == GPSAT_MEM_HOST;
+    const size_t esz = f64 ? sizeof(double) : sizeof(float), sumN = (size_t)d.sumN;
+    const size_t F = (size_t)tb.fold_off[T];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    // ---- 2. the derived batch: its tables here, its rows on the device
+    gpsat::CvFoldDerived dv;
+    gpsat::cvfold_derive(tb, b->obs_off, cv->min_obs, dv);
+    const size_t F2 = dv.d_fold.size(), E = (size_t)dv.d_obs_off[F2], P2 = (size_t)dv.d_pred_off[F2];
+    for (size_t f = 0; f < F; ++f) {
+        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = nan;
+        cv->fold_nll[f] = nan; cv->fold_shift[f] = nan;
+        cv->fold_status[f] = GPSAT_STATUS_SKIPPED; cv->fold_n_eval[f] = 0;
+        if (cv->fold_n_iter) cv->fold_n_iter[f] = 0;
+        cv->fold_n_obs[f] = tb.fold_n_obs[f]; cv->fold_label[f] = tb.fold_label[f];
+    }
+    if (sumN == 0) return GPSAT_OK;
+    // one int64 / double block and one int32 block, laid out once for the host copy and the device
+    std::vector<long long> t64;                     // d_obs_off [F2+1], d_pred_off [F2+1], d_src_off [F2], then delta [F2] (doubles)
+    t64.insert(t64.end(), dv.d_obs_off.begin(), dv.d_obs_off.end());
+    t64.insert(t64.end(), dv.d_pred_off.begin(), dv.d_pred_off.end());
+    t64.insert(t64.end(), dv.d_src_off.begin(), dv.d_src_off.end());
+    const size_t n64 = t64.size() + F2;
+    std::vector<int> t32;
+    size_t o_src_n, o_fold, o_fold_ptr, o_fold_rows, o_fold_derived, o_row_fold, o_row_pos, o_status;
+    auto put = [&](const std::vector<int>& v, size_t& off) { off = t32.size(); t32.insert(t32.end(), v.begin(), v.end()); };
+    put(dv.d_src_n, o_src_n); put(dv.d_fold, o_fold); put(tb.fold_ptr, o_fold_ptr); put(tb.fold_rows, o_fold_rows);
+    put(dv.fold_derived, o_fold_derived); put(tb.row_fold, o_row_fold); put(tb.row_pos, o_row_pos);
+    o_status = t32.size();
+    if ((rc = h->cvr_tab.reserve(n64 * 8 + (t32.size() + F2) * sizeof(int)))) return rc;
+    if ((rc = h->cvr_in.reserve(std::max<size_t>(E * (D + 1) + P2 * D, 1) * esz))) return rc;
+    if ((rc = h->cvr_out.reserve(std::max<size_t>(3 * P2 + (host ? 3 * sumN : 0), 1) * esz))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    long long* d64 = static_cast<long long*>(h->cvr_tab.p);
+    int* d32 = reinterpret_cast<int*>(d64 + n64);
+    HIP_TRY(hipMemcpyAsync(d64, t64.data(), t64.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d32, t32.data(), t32.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    gpsat::CvFoldArgs a;
+    a.F2 = (int)F2; a.D = D; a.f64 = f64; a.recentre = cv->recentre; a.sumN = d.sumN;
+    a.d_obs_off = d64; a.d_pred_off = d64 + (F2 + 1); a.d_src_off = d64 + 2 * (F2 + 1);
+    a.delta = reinterpret_cast<double*>(d64 + 2 * (F2 + 1) + F2);
+    a.d_src_n = d32 + o_src_n; a.d_fold = d32 + o_fold; a.d_status = d32 + o_status;
+    a.fold_ptr = d32 + o_fold_ptr; a.fold_rows = d32 + o_fold_rows; a.fold_derived = d32 + o_fold_derived;
+    a.row_fold = d32 + o_row_fold; a.row_pos = d32 + o_row_pos;
+    // the source rows: the caller's device arrays, or where stage_batch left them for the first launch (X, then y)
+    a.X = host ? h->bulk_in.p : b->X;
+    a.y = host ? static_cast<const void*>(static_cast<const char*>(h->bulk_in.p) + sumN * D * esz) : b->y;
+    char* in = static_cast<char*>(h->cvr_in.p);
+    a.Xd = in; a.yd = in + E * D * esz; a.Xsd = in + E * (D + 1) * esz;
+    char* out = static_cast<char*>(h->cvr_out.p);
+    a.fm = out; a.fv = out + P2 * esz; a.yv = out + 2 * P2 * esz;
+    a.cv_mean = host ? out + 3 * P2 * esz : cv->cv_mean;
+    a.cv_f_var = host ? out + (3 * P2 + sumN) * esz : cv->cv_f_var;
+    a.cv_y_var = host ? out + (3 * P2 + 2 * sumN) * esz : cv->cv_y_var;
+    std::vector<double> delta(F2, 0.0);
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::launch_cvfold_expand(a, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    if (F2) HIP_TRY(hipMemcpyAsync(delta.data(), a.delta, F2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // t64, t32 are local host memory
+    if ((rc = record_timing(h))) return rc;
+    const double expand_ms = h->last_kernel_ms;
+    kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+    // ---- 3. all fitted folds as one batch
+    std::vector<double> th0(F2 * H), lo(F2 * H), hi(F2 * H), theta(F2 * H), nll(F2);
+    std::vector<int> status(F2, GPSAT_STATUS_SKIPPED), n_eval(F2), n_iter(F2);
+    for (size_t j = 0; j < F2; ++j) {
+        const size_t t = (size_t)tb.fold_tile[dv.d_fold[j]];
+        bool full = cv->start == 1;
+        for (int i = 0; i < H && full; ++i) full = b->theta[t * H + i] > 0.0 && std::isfinite(b->theta[t * H + i]);
+        for (int i = 0; i < H; ++i) {
+            th0[j * H + i] = full ? b->theta[t * H + i] : b->theta0[t * H + i];
+            lo[j * H + i] = b->lo[t * H + i]; hi[j * H + i] = b->hi[t * H + i];
+        }
+    }
+    if (F2) {
+        gpsat_batch b2 = *b;
+        b2.T = (int)F2; b2.memory = GPSAT_MEM_DEVICE;
+        b2.obs_off = dv.d_obs_off.data(); b2.pred_off = dv.d_pred_off.data();
+        b2.theta0 = th0.data(); b2.lo = lo.data(); b2.hi = hi.data();
+        b2.X = a.Xd; b2.y = a.yd; b2.Xs = a.Xsd;
+        b2.theta = theta.data(); b2.nll = nll.data(); b2.grad = nullptr; b2.status = status.data(); b2.n_eval = n_eval.data(); b2.n_iter = n_iter.data();
+        b2.f_mean = const_cast<void*>(a.fm); b2.f_var = const_cast<void*>(a.fv); b2.y_var = const_cast<void*>(a.yv);
+        b2.cov_off = nullptr; b2.f_cov = nullptr;
+        if ((rc = fit_predict(h, &b2, nullptr))) return rc;
+        kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+    }
+    for (size_t j = 0; j < F2; ++j) {
+        const size_t f = (size_t)dv.d_fold[j];
+        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = theta[j * H + i];
+        cv->fold_nll[f] = nll[j]; cv->fold_shift[f] = delta[j];
+        cv->fold_status[f] = status[j]; cv->fold_n_eval[f] = n_eval[j];
+        if (cv->fold_n_iter) cv->fold_n_iter[f] = n_iter[j];
+    }
+    // ---- 4. the predictions back at their rows
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (F2) HIP_TRY(hipMemcpyAsync(const_cast<int*>(a.d_status), status.data(), F2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::launch_cvfold_scatter(a, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    if (host) {
+        void* const hp[3] = {cv->cv_mean, cv->cv_f_var, cv->cv_y_var};
+        void* const dp[3] = {a.cv_mean, a.cv_f_var, a.cv_y_var};
+        for (int i = 0; i < 3; ++i)
+            if (hp[i]) HIP_TRY(hipMemcpyAsync(hp[i], dp[i], sumN * esz, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = record_timing(h))) return rc;
+    if (dev_env("GPSAT_DEBUG_CVFOLD_STATS"))      // developer / scripts/cv_bench.py: the two streaming kernels on their own
+        std::fprintf(stderr, "gpsat cvfold: %zu derived tiles, %zu expanded rows, %zu held-out rows: expand %.4f ms, scatter %.4f ms\n",
+                     F2, E, P2, expand_ms, h->last_kernel_ms);
+    h->last_kernel_ms += kernel_ms; h->last_total_ms += total_ms;
+    return GPSAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -787,6 +946,20 @@ int gpsat_fit_predict_batch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsa
     if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv: NULL gpsat_cv");
     if (b && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "held-out predictions are built for GPSAT_F64 only");
     return fit_predict(h, b, nullptr, cv);
+}
+
+int gpsat_cv_refit_count(int32_t T, const int64_t* obs_off, const int32_t* fold, int64_t* fold_off, int64_t* expanded_rows) {
+    if (!fold_off || !expanded_rows) return fail(GPSAT_EINVAL, "gpsat_cv_refit_count: fold_off / expanded_rows is NULL");
+    gpsat::CvFoldTables tb;
+    const std::string err = gpsat::cvfold_tables(T, obs_off, fold, false, tb);
+    if (!err.empty()) return fail(GPSAT_EINVAL, "gpsat_cv_refit_count: " + err);
+    std::copy(tb.fold_off.begin(), tb.fold_off.end(), fold_off);
+    *expanded_rows = tb.expanded_rows;
+    return GPSAT_OK;
+}
+
+int gpsat_fit_predict_batch_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
+    return fit_predict_cv_refit(h, b, cv);
 }
 
 #ifdef GPSAT_DUMP

@@ -207,6 +207,27 @@ hipError_t bin_sort_rows(const BinArgs& a, void* temp, size_t& temp_bytes, hipSt
 hipError_t bin_cell_stats(const BinArgs& a, long long n_cells, long long n_valid, void* temp, size_t& temp_bytes, hipStream_t stream);
 int bin_long_rows();                  // rows from which a cell's sums are walked by a wave instead of a lane
 
+// refitted cross-validation (gpsat_cvfold.hip); device pointers, tables as gpsat_cvfold.h builds them.  Bulk arrays are float
+// or double according to `f64`.
+struct CvFoldArgs {
+    int F2, D, f64, recentre;         // derived tiles (fitted folds), input dimension, element type, de-mean the remaining rows
+    long long sumN;                   // rows of the source batch
+    const long long *d_obs_off, *d_pred_off;      // [F2+1] CSR offsets of the derived batch
+    const long long* d_src_off;       // [F2] first row of the derived tile's source tile
+    const int *d_src_n, *d_fold;      // [F2] rows of the source tile, fold of the derived tile
+    const int* d_status;              // [F2] status of the derived tile's fit (scatter only)
+    const int *fold_ptr, *fold_rows;  // [F+1], [R] a fold's tile-local rows, ascending
+    const int* fold_derived;          // [F] derived tile of a fold, -1: not fitted
+    const int *row_fold, *row_pos;    // [sumN] fold of a source row (-1: never held out), position in it
+    const void *X, *y;                // source batch [sumN, D], [sumN]
+    void *Xd, *yd, *Xsd;              // derived batch [E, D], [E], [P2, D]
+    double* delta;                    // [F2] mean of the remaining rows (0 without recentre)
+    const void *fm, *fv, *yv;         // [P2] predictions of the derived batch (scatter)
+    void *cv_mean, *cv_f_var, *cv_y_var;          // [sumN]; cv_y_var may be nullptr
+};
+hipError_t launch_cvfold_expand(const CvFoldArgs& a, hipStream_t stream);
+hipError_t launch_cvfold_scatter(const CvFoldArgs& a, hipStream_t stream);
+
 #define GPSAT_GLUE_MAXVARS 4
 // post-processing (gpsat_post.hip); device pointers
 hipError_t launch_smooth(int T, const double* x, const double* y, const double* vals, double lx, double ly, double* out,

@@ -35,6 +35,16 @@ class BatchResult:
     cv_mean: object = None  # [sum N] held-out predictions (cv_fold given): "f*" of every row from the other folds of its tile
     cv_f_var: object = None
     cv_y_var: object = None
+    # cv_refit: one entry per fold, folds of a tile numbered by ascending label; fold k of tile t is entry cv_fold_off[t] + k
+    cv_fold_off: np.ndarray | None = None   # [T+1]
+    cv_theta: np.ndarray | None = None      # [F, H] parameters fitted without the fold (NaN: the fold was not fitted)
+    cv_nll: np.ndarray | None = None        # [F]
+    cv_status: np.ndarray | None = None     # [F] see _lib.STATUS; 4 = too few rows left (min_obs)
+    cv_n_eval: np.ndarray | None = None     # [F]
+    cv_n_iter: np.ndarray | None = None     # [F]
+    cv_n_obs: np.ndarray | None = None      # [F] rows the fold leaves
+    cv_shift: np.ndarray | None = None      # [F] mean of those rows, in the units of y (0 without recentre)
+    cv_label: np.ndarray | None = None      # [F]
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -89,6 +99,29 @@ def factorise_folds(fold, N=None):
     if (codes >= 0).any():                       # dense again after the never-held-out labels left
         codes[codes >= 0] = pd.factorize(codes[codes >= 0])[0]
     return codes.astype(np.int32)
+
+
+# cv_refit: the default budget of one library call, in expanded rows (the sum over all folds of the rows each fold leaves).
+# A call holds (D + 1) elements per expanded row on the device: at D = 3, 2^25 rows are 0.5 GiB in fp32 and 1 GiB in fp64.
+CV_REFIT_MAX_EXPANDED_ROWS = 1 << 25
+
+
+def cv_refit_options(cv_refit) -> dict:
+    """``cv_refit`` of Engine.fit_predict_batch (True, or a dict) as a dict with every key set."""
+    opts = {"start": "theta0", "recentre": True, "min_obs": 1, "max_expanded_rows": CV_REFIT_MAX_EXPANDED_ROWS}
+    if cv_refit is True:
+        return opts
+    if not isinstance(cv_refit, dict):
+        raise GpsatError(f"cv_refit must be True or a dict with keys out of {sorted(opts)}, got {cv_refit!r}")
+    unknown = sorted(set(cv_refit) - set(opts))
+    if unknown:
+        raise GpsatError(f"cv_refit: unknown keys {unknown}; known: {sorted(opts)}")
+    opts.update(cv_refit)
+    if opts["start"] not in L.CV_START_IDS:
+        raise GpsatError(f"cv_refit: start must be 'theta0' or 'full', got {opts['start']!r}")
+    if int(opts["max_expanded_rows"]) < 1:
+        raise GpsatError("cv_refit: max_expanded_rows must be at least 1")
+    return opts
 
 
 def _ptr(a):
@@ -196,7 +229,8 @@ class Engine:
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
-                          out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None) -> BatchResult:
+                          out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
+                          cv_refit=None) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -211,7 +245,29 @@ class Engine:
         together, a negative label is never held out): also return, per row, the prediction from the other folds of its
         tile at the returned parameters (gpsat_fit_predict_batch_cv, fp64 only) as ``cv_mean``, ``cv_f_var``, ``cv_y_var``.
         None: gpsat_fit_predict_batch, as ever.
+        ``cv_refit`` (with integer ``cv_fold`` labels; both dtypes, a fold of any size): True, or a dict with keys out of
+        ``start`` ("theta0": every fold starts from the tile's theta0, a fresh run as the reference makes; "full": from the
+        tile's fitted parameters), ``recentre`` (True: the rows a fold leaves are de-meaned again by their own mean),
+        ``min_obs`` (a fold that leaves fewer rows is not fitted: status 4, NaN rows) and ``max_expanded_rows``.  Every
+        fold is then FITTED AGAIN without its rows (gpsat_fit_predict_batch_cv_refit): ``cv_mean`` (in the units of the
+        tile's y), ``cv_f_var`` and ``cv_y_var`` are the refitted model's predictions at the held-out rows, and
+        ``cv_fold_off``, ``cv_theta``, ``cv_nll``, ``cv_status``, ``cv_n_eval``, ``cv_n_iter``, ``cv_n_obs``, ``cv_shift``
+        and ``cv_label`` describe every fold.  When the folds' remaining rows sum to more than ``max_expanded_rows``
+        (default CV_REFIT_MAX_EXPANDED_ROWS = 2^25 rows: (D + 1) elements each on the device, 0.5 GiB in fp32 and 1 GiB
+        in fp64 at D = 3), consecutive ranges of tiles are run by one library call each and the results concatenated; a
+        single tile above the budget is an error.  Refused with cv_fold="loo", ``n_starts`` and ``full_cov``.
         """
+        refit = None
+        if cv_refit is not None and cv_refit is not False:
+            refit = cv_refit_options(cv_refit)
+            if cv_fold is None:
+                raise GpsatError("cv_refit needs the fold labels: cv_fold is None")
+            if isinstance(cv_fold, str):
+                raise GpsatError(f"cv_refit is not built for cv_fold={cv_fold!r}: give integer fold labels")
+            if n_starts is not None:
+                raise GpsatError("cv_refit and n_starts cannot be combined")
+            if full_cov:
+                raise GpsatError("cv_refit and full_cov cannot be combined")
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable)
         obs_off, pred_off = meta[0]
         T, H = len(obs_off) - 1, D + 2
@@ -246,7 +302,7 @@ class Engine:
         f_start = None
         name = "gpsat_fit_predict_batch"
         if cv_fold is not None:
-            name = "gpsat_fit_predict_batch_cv"
+            name = "gpsat_fit_predict_batch_cv_refit" if refit else "gpsat_fit_predict_batch_cv"
             if not hasattr(self._lib, name):
                 raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_cv (held-out predictions)")
             if n_starts is not None:
@@ -261,6 +317,9 @@ class Engine:
                 labels = np.ascontiguousarray(raw, dtype=np.int32)
                 if labels.shape != (sumN,):
                     raise GpsatError(f"cv_fold: {labels.size} labels for {sumN} rows")
+            if refit:
+                return self._cv_refit(D, dtype, device_mode, meta, (X, y, Xs), preds, labels, refit,
+                                      (kernel, optimiser, max_iter, max_ls, ftol, gtol, adam_lr, want_grad))
             if device_mode:
                 import torch
                 cvo = tuple(torch.empty(max(sumN, 1), dtype=t_dt, device=X.device) for _ in range(3))
@@ -289,6 +348,68 @@ class Engine:
             rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
         return self._result(rc, name, res, preds, sumP, f_start=f_start,
                             f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
+
+    def _cv_refit(self, D, dtype, device_mode, meta, data, preds, labels, opts, run) -> BatchResult:
+        """gpsat_fit_predict_batch_cv_refit over consecutive ranges of tiles, each within ``max_expanded_rows``."""
+        (obs_off, pred_off), theta0, lo, hi, trainable = meta
+        X, y, Xs = data
+        T, H = len(obs_off) - 1, D + 2
+        sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
+        fold_off = np.zeros(T + 1, dtype=np.int64)
+        rows = C.c_int64(0)
+        rc = self._lib.gpsat_cv_refit_count(T, _ptr(obs_off), _ptr(labels), _ptr(fold_off), C.byref(rows))
+        if rc != 0:
+            raise GpsatError(f"gpsat_cv_refit_count failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        # expanded rows per tile: every fold leaves N - g rows, so F N - (rows that are held out at all)
+        held = np.bincount(np.repeat(np.arange(T), np.diff(obs_off))[labels >= 0], minlength=T)
+        per_tile = np.diff(fold_off) * np.diff(obs_off) - held
+        assert int(per_tile.sum()) == rows.value
+        budget = int(opts["max_expanded_rows"])
+        ranges, t0, acc = [], 0, 0
+        for t in range(T):
+            if per_tile[t] > budget:
+                raise GpsatError(f"cv_refit: tile {t} alone expands to {int(per_tile[t])} rows, above max_expanded_rows = {budget}")
+            if acc + per_tile[t] > budget:
+                ranges.append((t0, t))
+                t0, acc = t, 0
+            acc += int(per_tile[t])
+        ranges.append((t0, T))
+        F = int(fold_off[-1])
+        np_dt = np.float32 if dtype == "f32" else np.float64
+        if device_mode:
+            import torch
+            cvo = tuple(torch.empty(max(sumN, 1), dtype=X.dtype, device=X.device) for _ in range(3))
+        else:
+            cvo = tuple(np.empty(sumN, dtype=np_dt) for _ in range(3))
+        fo = dict(cv_theta=np.full((F, H), np.nan), cv_nll=np.full(F, np.nan), cv_shift=np.full(F, np.nan),
+                  cv_status=np.full(F, 4, dtype=np.int32), cv_n_eval=np.zeros(F, dtype=np.int32), cv_n_iter=np.zeros(F, dtype=np.int32),
+                  cv_n_obs=np.zeros(F, dtype=np.int32), cv_label=np.zeros(F, dtype=np.int32))
+        ptr = (lambda a_: a_.data_ptr()) if device_mode else _ptr
+        parts, km, tm = [], 0.0, 0.0
+        for t0, t1 in ranges:
+            a, e, pa, pe, f0, f1 = (int(v) for v in (obs_off[t0], obs_off[t1], pred_off[t0], pred_off[t1], fold_off[t0], fold_off[t1]))
+            sub_meta = ((np.ascontiguousarray(obs_off[t0:t1 + 1] - a), np.ascontiguousarray(pred_off[t0:t1 + 1] - pa)),
+                        np.ascontiguousarray(theta0[t0:t1]), np.ascontiguousarray(lo[t0:t1]), np.ascontiguousarray(hi[t0:t1]), trainable)
+            sub_preds = tuple(p_[pa:pe] if pe > pa else p_[:1] for p_ in preds) if device_mode else tuple(p_[pa:pe] for p_ in preds)
+            b, res = self._fill_batch(D, dtype, device_mode, sub_meta, (X[a:e], y[a:e], Xs[pa:pe]), sub_preds, *run)
+            sub_off = np.ascontiguousarray(fold_off[t0:t1 + 1] - f0)
+            sub_lab = np.ascontiguousarray(labels[a:e])
+            cv = L.GpsatCvRefit()
+            cv.fold, cv.fold_off = _ptr(sub_lab), _ptr(sub_off)
+            cv.start, cv.recentre, cv.min_obs = L.CV_START_IDS[opts["start"]], int(bool(opts["recentre"])), int(opts["min_obs"])
+            cv.cv_mean, cv.cv_f_var, cv.cv_y_var = (ptr(c_[a:e] if e > a else c_[:1]) for c_ in cvo)
+            sub_fo = {k: v[f0:f1] for k, v in fo.items()}          # views: the library writes into the whole arrays
+            cv.fold_theta, cv.fold_nll, cv.fold_shift = _ptr(sub_fo["cv_theta"]), _ptr(sub_fo["cv_nll"]), _ptr(sub_fo["cv_shift"])
+            cv.fold_status, cv.fold_n_eval, cv.fold_n_iter = _ptr(sub_fo["cv_status"]), _ptr(sub_fo["cv_n_eval"]), _ptr(sub_fo["cv_n_iter"])
+            cv.fold_n_obs, cv.fold_label = _ptr(sub_fo["cv_n_obs"]), _ptr(sub_fo["cv_label"])
+            rc = self._lib.gpsat_fit_predict_batch_cv_refit(self._h, C.byref(b), C.byref(cv))
+            r = self._result(rc, "gpsat_fit_predict_batch_cv_refit", res, sub_preds, pe - pa)
+            parts.append(res)
+            km, tm = km + r.kernel_ms, tm + r.total_ms
+        res = {k: (None if parts[0][k] is None else np.concatenate([p_[k] for p_ in parts])) for k in parts[0]}
+        fm, fv, yv = (p_[:sumP] for p_ in preds)
+        return BatchResult(f_mean=fm, f_var=fv, y_var=yv, kernel_ms=km, total_ms=tm, **res, cv_mean=cvo[0][:sumN], cv_f_var=cvo[1][:sumN],
+                           cv_y_var=cvo[2][:sumN], cv_fold_off=fold_off, **fo)
 
     def sgpr_fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, z_off, Z, theta0, lo=None, hi=None,
                                trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000, max_ls=0,

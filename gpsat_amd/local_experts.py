@@ -74,6 +74,16 @@ the observation under ``obs_col`` (raw), ``f*``, ``f*_var``, ``y_var`` and ``f_b
 prediction of the raw observation is ``f_bar + obs_scale * f*`` with variance ``obs_scale**2 * y_var``.  A fold above
 ``gpsat_max_cv_fold`` rows, and a row with a missing value in a ``by`` column, is not held out (NaN rows, counted in
 ``run_details.cv_rows_skipped``).
+``cv={"by": [...], "refit": True, "start": "theta0" | "full"}`` (``dtype`` fp32 or fp64): every fold is FITTED AGAIN without
+its rows, as the reference's cross-validation runs do (Engine.fit_predict_batch ``cv_refit``): the rows
+a fold leaves are de-meaned again when the model's ``obs_mean`` is "local", a fold that leaves fewer than the run's
+``min_obs`` rows is not fitted (its rows are NaN and counted in ``cv_rows_skipped``), and a fold has no size limit.
+``cv_preds`` keeps its columns, ``f*`` still in the units of the tile's ``f_bar``.  Table ``cv_params``, committed with the
+waves like ``cv_preds``, has one row per fold: expert index; the ``by`` columns' values; ``num_obs`` (rows fitted);
+``lengthscales_<k>``, ``kernel_variance``, ``likelihood_variance`` in the units of the parameter tables;
+``objective_value``; ``optimise_success``; and ``f_bar``, the de-meaning constant of the fold's own fit (the tile's plus
+``obs_scale`` times the mean of the remaining rows).  What still differs from the reference: a row is predicted by every
+expert that selects it and the predictions are not glued, and ``max_dist`` of the prediction locations is not applied.
 """
 from __future__ import annotations
 
@@ -838,13 +848,26 @@ class BatchedLocalExpertOI:
             raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
         self.dtype = dtype
         # held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with equal
-        # values in those columns are held out together.  None: nothing of a run differs.
+        # values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
+        # fitted again without its rows (tables cv_preds and cv_params; fp32 or fp64), from "start": "theta0" (default) | "full".
+        self.cv_refit = None
         if cv is not None:
-            if not (cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
+            if isinstance(cv, dict) and "refit" in cv:
+                if not set(cv) <= {"by", "refit", "start"}:
+                    raise ValueError("cv must be None, 'loo', {'by': [column, ...]} or {'by': [...], 'refit': True, 'start': 'theta0' | 'full'}")
+                if cv.get("by") in (None, "loo") or len(_as_list(cv["by"])) == 0:
+                    raise NotImplementedError("cv: refit is not built for leave-one-out through the orchestrator: give {'by': [column, ...]}")
+                if cv.get("start", "theta0") not in ("theta0", "full"):
+                    raise ValueError(f"cv: start must be 'theta0' or 'full', got {cv.get('start')!r}")
+                if cv["refit"]:
+                    self.cv_refit = {"start": cv.get("start", "theta0")}
+                elif "start" in cv:
+                    raise ValueError("cv: start is an option of refit=True")
+            elif not (cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
                 raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
             if self.sgpr:
                 raise NotImplementedError("cv: held-out predictions are not built for SGPR experts (exact GP experts only)")
-            if dtype != "f64":
+            if dtype != "f64" and self.cv_refit is None:
                 raise NotImplementedError(f"cv: held-out predictions are built in fp64 only: dtype must be 'f64', not {dtype!r}")
             pks = [model_config.get("pred_kwargs"), model_config.get("replacement_pred_kwargs")]
             if any((pk or {}).get("full_cov", False) for pk in pks):
@@ -1056,6 +1079,7 @@ class BatchedLocalExpertOI:
         in_group = (not logical) and world_size > 1 and d_world == world_size
         if self.cv is not None and world_size > 1:
             raise NotImplementedError("cv: held-out predictions are not built for sharded runs (world_size > 1, real or logical)")
+        self._cv_min_obs = int(min_obs)
         if world_size > 1 and not logical and not in_group and gather:
             # explicit rank / world_size without a process group of that size: the caller synchronises the ranks itself
             # (nothing here can separate reading the resume state from rank 0's writes, and nothing can gather)
@@ -1099,7 +1123,7 @@ class BatchedLocalExpertOI:
                 sh = shards[0]
                 out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
                 if self.cv is not None and sh.tables is None:
-                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped)
+                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped, sh.cvp_frames)
         finally:
             tf = time.perf_counter()                               # also after a fault: what was committed is on disk
             for sh in reversed(shards):
@@ -1324,7 +1348,7 @@ class BatchedLocalExpertOI:
         labels = np.full(len(rows), -1, dtype=np.int32)
         labels[known] = inv
         big = np.zeros(len(rows), dtype=bool)
-        if len(inv):
+        if len(inv) and self.cv_refit is None:       # a refitted fold is a prediction set: no limit
             big[known] = cnt[inv] > L.max_cv_fold("f64", len(self.coords_col))
         labels[big] = -1
         skip = big | ~known
@@ -1351,10 +1375,34 @@ class BatchedLocalExpertOI:
         fr.update({"f*": vals[:, 0], "f*_var": vals[:, 1], "y_var": vals[:, 2], "f_bar": np.repeat(np.asarray(f_bar, dtype=np.float64), cnt)})
         return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
 
-    def _cv_tables(self, plan, tables, items, frames, skipped):
-        """``cv_preds`` and the run_details column ``cv_rows_skipped`` into a run's (or a wave's) tables."""
+    def _cv_params_frame(self, plan, items, folds, f_bar):
+        """Table ``cv_params`` of the tiles among ``items`` (``folds``: per item [F, H + 5]: theta, objective, status, rows
+        fitted, shift, position in the tile of the fold's first row; ``f_bar``: per item the tile's de-meaning constant)."""
+        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
+        H = len(cc) + 2
+        cnt = np.array([len(c) for c in folds], dtype=np.int64)
+        v = _cat([c for c in folds if len(c)], H + 5)
+        rows = np.concatenate([plan.idx[plan.off[i] + c[:, H + 4].astype(np.int64)] for i, c in zip(items, folds) if len(c)]).astype(np.int64) \
+            if cnt.sum() else np.zeros(0, dtype=np.int64)
+        fr = {c_: self.df[c_].values[rows] for c_ in self.cv_by}
+        fr["num_obs"] = v[:, H + 2].astype(np.int64)
+        for k in range(H - 2):
+            fr[f"lengthscales_{k}"] = v[:, k]
+        fr["kernel_variance"], fr["likelihood_variance"] = v[:, H - 2], v[:, H - 1]
+        fr["objective_value"] = v[:, H]
+        fr["optimise_success"] = bool(plan.optimise) & (v[:, H + 1] == 0)
+        osc = np.array([plan.profiles[p].obs_scale for p in plan.prof_id[items]], dtype=np.float64)
+        fr["f_bar"] = np.repeat(np.asarray(f_bar, dtype=np.float64), cnt) + np.repeat(osc, cnt) * v[:, H + 3]
+        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
+
+    def _cv_tables(self, plan, tables, items, frames, skipped, param_frames=()):
+        """``cv_preds`` (with refit: and ``cv_params``) and the run_details column ``cv_rows_skipped`` into a run's (or a
+        wave's) tables."""
         frames = [f_ for f_ in frames if len(f_)]
         tables[f"cv_preds{plan.table_suffix}"] = pd.concat(frames) if len(frames) > 1 else (frames[0] if frames else pd.DataFrame())
+        if self.cv_refit is not None:
+            pf_ = [f_ for f_ in param_frames if len(f_)]
+            tables[f"cv_params{plan.table_suffix}"] = pd.concat(pf_) if len(pf_) > 1 else (pf_[0] if pf_ else pd.DataFrame())
         rd = tables[f"run_details{plan.table_suffix}"]
         assert len(rd) == len(items) == len(skipped)
         rd["cv_rows_skipped"] = np.asarray(skipped, dtype=np.int64)
@@ -1505,6 +1553,7 @@ class _ShardRunner:
         self.rows = ([], [], [])               # fixed, preds, cov of the closed waves
         self.tables, self.flush = None, []     # the only wave's tables; the flush queued last
         self.open_cv, self.cv_frames, self.cv_skipped = {}, [], np.zeros(0, dtype=np.int64)   # held-out rows of the open waves; closed waves' frames
+        self.open_cvp, self.cvp_frames = {}, []     # cv refit: per-fold rows of the open waves; closed waves' cv_params frames
         self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
         self.counts = np.where(plan.kind[items] == 2, plan.n_pred[items] if plan.predict else 0, 0).astype(np.int64)
 
@@ -1595,6 +1644,8 @@ class _ShardRunner:
             else:
                 if self.oi.cv is not None:
                     kw["cv_fold"] = pk["cv_fold"]
+                if self.oi.cv_refit is not None:
+                    kw["cv_refit"] = dict(self.oi.cv_refit, recentre=bool(pf.local_mean), min_obs=self.oi._cv_min_obs)
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
                                            **kw, **({"full_cov": True} if pf.full_cov else {}))
             t1 = time.perf_counter()
@@ -1629,6 +1680,17 @@ class _ShardRunner:
             for kk, j in enumerate(loc_ids):
                 cvr[j] = cv3[o_off[kk]:o_off[kk + 1]]
             skp[loc_ids] = pk["cv_skipped"]
+            if self.oi.cv_refit is not None:
+                cvp, lab, f_off = self.open_cvp[wi], pk["cv_fold"], r.cv_fold_off
+                per_fold = np.column_stack([r.cv_theta, r.cv_nll, r.cv_status, r.cv_n_obs, r.cv_shift, np.zeros(len(r.cv_nll))])
+                for kk, j in enumerate(loc_ids):
+                    lt = lab[o_off[kk]:o_off[kk + 1]]
+                    rows_f = per_fold[f_off[kk]:f_off[kk + 1]]
+                    # folds ascend with the label: np.unique's order; the first row of each names the fold's `by` values
+                    rows_f[:, H + 4] = np.unique(np.where(lt >= 0, lt, np.iinfo(np.int32).max), return_index=True)[1][:len(rows_f)]
+                    cvp[j] = rows_f
+                    not_fitted = rows_f[:, H + 1] == 4
+                    skp[j] += int((len(lt) - rows_f[not_fitted, H + 2]).sum())
         if p.predict:
             pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
                            np.asarray(r.y_var, dtype=np.float64)], axis=1)
@@ -1657,6 +1719,7 @@ class _ShardRunner:
             n = len(self.waves[wi])
             self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
             self.open_cv[wi] = ([np.zeros((0, 3))] * n, np.zeros(n, dtype=np.int64))
+            self.open_cvp[wi] = [np.zeros((0, self.H + 5))] * n
         return self.open[wi]
 
     def _close_waves_to(self, w):
@@ -1677,10 +1740,13 @@ class _ShardRunner:
         lazy = bool(pieces) and not p.want_cov
         tables = oi._tables(p, items, fixed, pred_cat, cov_cat, with_preds=not lazy)
         cvr, skp = self.open_cv.pop(wi)
+        cvp = self.open_cvp.pop(wi)
         if oi.cv is not None:
             self.cv_frames.append(oi._cv_frame(p, items, cvr, fixed[:, self.H + _OBS_MEAN]))
+            if oi.cv_refit is not None:
+                self.cvp_frames.append(oi._cv_params_frame(p, items, cvp, fixed[:, self.H + _OBS_MEAN]))
             self.cv_skipped = np.concatenate([self.cv_skipped, skp])
-            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp)
+            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp, self.cvp_frames[-1:])
         oi.timings["tables_s"] += time.perf_counter() - tt
         tf = time.perf_counter()
         # commit: these experts are done.  The parts are written by the writer thread while the next wave runs (one writer,

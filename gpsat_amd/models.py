@@ -342,16 +342,27 @@ class HipGPRModel:
             out["f_bar"] = f_bar
         return out
 
-    def cross_validate(self, fold=None, apply_scale=True) -> Dict[str, np.ndarray]:
-        """Held-out predictions at the model's current parameters (no optimisation, nothing is fitted again without the
-        fold): every row predicted from the rows of all OTHER folds, from the tile's own factor (gpsat_fit_predict_batch_cv).
+    def cross_validate(self, fold=None, apply_scale=True, refit=False, **refit_kwargs) -> Dict[str, np.ndarray]:
+        """Held-out predictions.  ``refit=False``: at the model's current parameters (no optimisation, nothing is fitted
+        again without the fold; for that see ``refit`` below): every row predicted from the rows of all OTHER folds, from the tile's own factor (gpsat_fit_predict_batch_cv).
         ``fold``: None = leave-one-out; an array-like of N labels of any hashable kind, or a 2-D array whose equal rows form
         a fold; integer labels < 0 and None / NaN labels are never held out (NaN results).  Returns "f*", "f*_var" and
         "y_var", each [N] in the order of the model's rows, in the units ``predict`` returns its own (with "f_bar", the
         tile's own de-meaning constant: it is not recomputed per fold).  Always computed in fp64, whatever ``dtype``.
-        ``apply_scale`` is accepted for symmetry with ``predict``: the model's coordinates are already scaled."""
+        ``apply_scale`` is accepted for symmetry with ``predict``: the model's coordinates are already scaled.
+        ``refit=True``: every fold is fitted again without its rows (gpsat_fit_predict_batch_cv_refit), in the model's
+        ``dtype``, from the model's current parameters ("start": "theta0") or from the tile's fitted ones ("full"); the
+        model itself is not changed.  ``refit_kwargs``: ``start``, ``recentre``, ``min_obs``, ``max_expanded_rows`` as
+        Engine.fit_predict_batch takes them in ``cv_refit``, and ``max_iter`` / ``optimiser`` / ``max_ls`` / ``ftol`` /
+        ``gtol`` as ``optimise_parameters`` does.  "f*" is in the units of the tile's own "f_bar"; the result also holds,
+        per fold in ascending order of the factorised label, "fold" (the code of factorise_folds), "theta" [F, H],
+        "objective_value", "status", "num_obs" and "shift" (the mean of the rows the fold leaves, in the units of "f*")."""
         from .engine import factorise_folds
         N, D = self.coords.shape
+        if refit:
+            return self._cross_validate_refit(fold, **refit_kwargs)
+        if refit_kwargs:
+            raise TypeError(f"cross_validate: {sorted(refit_kwargs)} are options of refit=True")
         nmax = L.max_tile_obs("f64", D)
         if N > nmax:
             raise ValueError(f"tile of {N} observations: held-out predictions take at most {nmax} (gpsat_max_tile_obs, fp64, D={D})")
@@ -370,6 +381,22 @@ class HipGPRModel:
             raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
         return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
                 "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N)}
+
+
+    def _cross_validate_refit(self, fold, max_iter=10_000, optimiser="lbfgs", **kw):
+        from .engine import factorise_folds
+        N, D = self.coords.shape
+        labels = np.arange(N, dtype=np.int32) if fold is None else factorise_folds(fold, N)
+        run = {k: kw.pop(k) for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in kw}
+        r = self._engine.fit_predict_batch(
+            dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, 0]),
+            Xs=np.zeros((0, D)), theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
+            trainable=self._trainable, kernel=self.kernel, optimiser=optimiser, max_iter=max_iter, cv_fold=labels,
+            cv_refit=kw or True, **run)
+        return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
+                "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N),
+                "fold": r.cv_label, "theta": r.cv_theta, "objective_value": r.cv_nll, "status": r.cv_status,
+                "num_obs": r.cv_n_obs, "shift": r.cv_shift}
 
 
 def select_inducing_points(coords: np.ndarray, num_inducing_points: int, seed: int = 0, expert_index: int = 0) -> np.ndarray:
@@ -415,7 +442,7 @@ class HipSGPRModel(HipGPRModel):
     def param_names(self) -> List[str]:
         return ["lengthscales", "kernel_variance", "likelihood_variance", "inducing_points"]
 
-    def cross_validate(self, fold=None, apply_scale=True):
+    def cross_validate(self, fold=None, apply_scale=True, **kwargs):
         raise NotImplementedError("held-out predictions are built for exact experts (HipGPRModel) only, not for SGPR")
 
     def get_inducing_points(self) -> np.ndarray:
@@ -565,7 +592,7 @@ class HipSklearnGPRModel(HipGPRModel):
         """No effect: alpha is fixed, never trained."""
 
     # -- fit / objective / predict
-    def cross_validate(self, fold=None, apply_scale=True):
+    def cross_validate(self, fold=None, apply_scale=True, **kwargs):
         raise NotImplementedError("held-out predictions are built for HipGPRModel only, not for sklearn experts")
 
     def restart_starts(self, rng=None):

@@ -213,6 +213,60 @@ int gpsat_fit_predict_batch_cv(gpsat_handle *h, const gpsat_batch *b, const gpsa
 /* largest fold of gpsat_fit_predict_batch_cv (256 for GPSAT_F64, D = 1..4); 0 for GPSAT_F32 and unsupported arguments */
 int gpsat_max_cv_fold(int dtype, int D);
 
+/*
+ * Cross-validation that fits every held-out fold again: the extension of gpsat_fit_predict_batch_cv_refit (both dtypes).
+ * Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ * Replaces the reference's cross-validation runs (examples/create_xval_config.py: one LocalExpertOI run per held-out track,
+ * which removes the track, fits every expert's parameters on what is left, de-means what is left again and predicts at the
+ * held-out rows).
+ *
+ * 1. The batch is run exactly as gpsat_fit_predict_batch runs it: every plain output has that call's bits.
+ * 2. For every fold G of every tile (rows with the same label >= 0; folds of a tile are numbered by ascending label,
+ *    fold_off[t] + k is fold k of tile t) that leaves at least max(min_obs, 1) rows, a derived tile is formed on the device:
+ *    observations = the tile's other rows in source order, y' = dtype(double(y) - delta) with delta = their fp64 mean
+ *    (recentre = 1) or 0, prediction points = the fold's rows in source order, theta0 = the batch's theta0 of the tile
+ *    (start = 0) or the tile's returned theta (start = 1; the batch's theta0 where that theta is not finite and positive),
+ *    the tile's lo / hi and the batch's trainable, optimiser and tolerances.
+ * 3. All derived tiles, in fold order, are run as ONE batch through gpsat_fit_predict_batch's own path (device-resident
+ *    inputs in buffers of the handle): a fold's outputs have the bits that batch has from any caller.
+ * 4. cv_mean of a fold's rows = dtype(double(f*) + delta), i.e. in the units of the tile's y; cv_f_var / cv_y_var are the
+ *    derived tile's.  Rows of label < 0, of a fold that was not fitted and of a fold whose derived tile ended NOT_PD or NAN
+ *    are NaN.
+ * 5. Per fold: theta, objective, status, evaluations, iterations, rows fitted, delta and the label.  A fold that was not
+ *    fitted has status GPSAT_STATUS_SKIPPED, NaN theta / nll / shift and 0 evaluations.
+ * delta is one fp64 sum in a fixed order: a second call returns the same bits.  There is no limit on the size of a fold (it
+ * is a prediction set).  GPSAT_OPT_NONE evaluates every fold at theta0.  gpsat_last_timing covers both launches and the two
+ * kernels around the second.
+ * Memory: the handle keeps, until gpsat_destroy, the derived inputs (expanded_rows (D + 1) + R D elements, R <= sum N the
+ * held-out rows), three outputs of R elements, in host mode the three cv outputs (3 sum N elements), and the fold tables
+ * (about 3 int32 per row, 40 bytes per fold).  The call does NOT split itself: size it with gpsat_cv_refit_count, which
+ * returns expanded_rows -- at D = 3 about 16 (fp32) or 32 (fp64) bytes per expanded row -- and hand over consecutive ranges
+ * of tiles whose expanded_rows fit the device.  A failed allocation is GPSAT_ENOMEM.
+ */
+typedef struct gpsat_cv_refit {
+    const int32_t *fold;      /* [sum N] host, labels as in gpsat_cv (>= 0 held out together, < 0 never held out); must not be NULL */
+    int32_t start;            /* 0: every fold starts from b->theta0 (the reference: a fresh run); 1: from the tile's full-data theta */
+    int32_t recentre;         /* 1: the remaining rows are de-meaned by their own mean (obs_mean="local" without the fold) */
+    int32_t min_obs;          /* a fold that leaves fewer than max(min_obs, 1) rows is not fitted (fold_status SKIPPED, rows NaN) */
+    const int64_t *fold_off;  /* [T+1] host: from gpsat_cv_refit_count; sizes the per-fold outputs */
+    void    *cv_mean, *cv_f_var, *cv_y_var;   /* [sum N] host|device as b->memory, element type b->dtype; cv_y_var may be NULL */
+    double  *fold_theta;      /* [F*H] host */
+    double  *fold_nll;        /* [F] host */
+    double  *fold_shift;      /* [F] host: delta */
+    int32_t *fold_status, *fold_n_eval, *fold_n_iter, *fold_n_obs, *fold_label;   /* [F] host; n_iter may be NULL */
+    int32_t reserved[8];
+} gpsat_cv_refit;
+
+/* Folds per tile as CSR offsets fold_off [T+1] (F = fold_off[T]) and expanded_rows = the sum over all folds of N_t - g, the
+ * observation rows gpsat_fit_predict_batch_cv_refit will hold on the device.  Host code only: works without a GPU.
+ * GPSAT_EINVAL for a NULL argument, bad offsets, or more than 2^31 - 1 rows. */
+int gpsat_cv_refit_count(int32_t T, const int64_t *obs_off, const int32_t *fold, int64_t *fold_off, int64_t *expanded_rows);
+
+/* as gpsat_fit_predict_batch, with the refitted held-out predictions above.  GPSAT_EINVAL (with a message that names the
+ * argument) for a NULL cv, fold, fold_off, cv_mean, cv_f_var or required per-fold output, a fold_off that differs from
+ * gpsat_cv_refit_count's, start or recentre outside {0, 1}, and cov_off / f_cov in the same call. */
+int gpsat_fit_predict_batch_cv_refit(gpsat_handle *h, const gpsat_batch *b, const gpsat_cv_refit *cv);
+
 /* library / ABI version (GPSAT_ABI_VERSION) */
 int gpsat_version(void);
 
