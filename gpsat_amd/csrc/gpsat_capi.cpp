@@ -1,9 +1,16 @@
 // gpsat_capi.cpp -- C ABI of libgpsat_hip.so (see include/gpsat_hip.h for the contract and the
 // reference interfaces each entry point replaces).  Host-side responsibilities only: argument
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
-// gpsat_fit_predict_batch in steps: check_batch / check_multistart / check_cv, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
-// setup_*, launch, fetch_batch / fetch_cv, record_timing.  gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice:
-// for the batch, and for the batch of its folds that gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h.
+// Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
+// translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
+//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+//     setup_*, launch, fetch_batch / fetch_cv, record_timing.
+//   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
+//     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
+//     cvr_stage_expand, cvr_derived_batch, cvr_unpack, cvr_scatter_fetch.
+//   gpsat_select_batch_ex (gpsat_select_plan.h): check -> cache hit? -> chunks -> stage -> bin (select_bin_table, optional) ->
+//     boxes -> count -> scan -> fill -> unbin (select_unbin_indices, optional) -> fetch -> remember.
+//   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -19,6 +26,8 @@
 #include "gpsat_kernels.h"
 #include "gpsat_plan.h"
 #include "gpsat_cvfold.h"
+#include "gpsat_select_plan.h"
+#include "gpsat_bin_plan.h"
 
 namespace {
 
@@ -92,48 +101,25 @@ struct HandleQueue {
 
 }  // namespace
 
-// FNV-1a over all of `refs` and `bounds` and a sample of at most 65 536 evenly spaced elements of `points` (plus both ends): a
-// caller who refills the same host buffers between the sizes call and the fill call gets a fresh selection, not the cached one
-static unsigned long long sel_fingerprint(const double* points, long long nP, const double* refs, long long nR,
-                                          const double* bounds, long long nB) {
-    unsigned long long h = 1469598103934665603ull;
-    auto mix = [&](const double* p) {
-        unsigned long long v;
-        std::memcpy(&v, p, 8);
-        h = (h ^ v) * 1099511628211ull;
-    };
-    for (long long i = 0; i < nR; ++i) mix(refs + i);
-    for (long long i = 0; i < nB; ++i) mix(bounds + i);
-    const long long step = std::max<long long>(1, nP / 65536);
-    for (long long i = 0; i < nP; i += step) mix(points + i);
-    for (long long i = std::max<long long>(0, nP - 64); i < nP; ++i) mix(points + i);
-    return h;
-}
-
 struct gpsat_handle : HandleQueue {
     int device = 0;
     int num_cu = 0;
     int wg_per_cu = 2;
     char name[256] = {0};
     double last_kernel_ms = 0.0, last_total_ms = 0.0;
-    // gpsat_select_batch is called twice per selection (sizes, then indices): the first call already leaves the indices on
-    // the device; the second, when it repeats the first call's arguments, only copies them out
-    struct {
-        const void *pts = nullptr, *refs = nullptr, *bounds = nullptr;
-        int64_t M = 0, total = -1;
-        int C = 0, T = 0, n_bounds = 0;
-        gpsat_select_spec sp;
-        unsigned long long fp = 0;     // fingerprint of the tables' CONTENTS at the sizes call
-        const int* d_result = nullptr;
-        std::vector<int64_t> off;
-    } selc;
+    // The two-call selection (gpsat_select_plan.h).  Its d_result points into sel.idx or sel.keys, buffers that a later call may
+    // grow (and so free): that is safe only because begin_call, where every entry point starts its device work, ends the cache.
+    gpsat::SelectCache selc;
     // device buffers (grown lazily, owned by the handle, freed by its destructor)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
-    DevBuf sel_pts, sel_refs, sel_cnt, sel_idx, sel_box, sel_perm, sel_keys, sel_tmp, sel_ord, sel_bnd;
-    DevBuf bin_in, bin_keys, bin_rows, bin_vals, bin_runs, bin_tmp, bin_out;     // gpsat_bin_batch
+    // gpsat_select_batch_ex.  gpsat_smooth_batch and gpsat_glue_batch stage their inputs in sel.pts (glue: its segments in
+    // sel.cnt) instead of buffers of their own: the post-processing follows the selection, whose tables are no longer needed
+    // then, and no call leaves anything in the two for a later one (the selection cache holds neither).
+    struct SelectBufs { DevBuf pts, refs, cnt, idx, box, perm, keys, tmp, ord, bnd; } sel;
+    struct BinBufs { DevBuf in, keys, rows, vals, runs, tmp, out; } bin;     // gpsat_bin_batch (layout: gpsat_bin_plan.h)
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
@@ -144,7 +130,7 @@ namespace {
 // Every entry point that uses the device starts its device work here.  Any call on the handle ends a pending two-call
 // selection (the selection's own sizes call sets it up again at its end).
 int begin_call(gpsat_handle* h) {
-    h->selc.total = -1;
+    h->selc.forget();
     HIP_TRY(hipSetDevice(h->device));
     return GPSAT_OK;
 }
@@ -157,6 +143,21 @@ int record_timing(gpsat_handle* h, int t0 = 0, int t1 = 3) {
     h->last_kernel_ms = km;
     h->last_total_ms = tm;
     return GPSAT_OK;
+}
+
+// The two-pass idiom of the sort-based steps (select_bin_rows, select_unbin, bin_sort_rows, bin_cell_stats): step(nullptr, bytes)
+// only reports the scratch it needs, step(scratch, bytes) runs.  `mark`, when given, is recorded between the two: after the
+// reservation, so that an allocation is not timed as kernel time.
+template <class Step>
+int run_with_temp(gpsat_handle* h, DevBuf& tmp, const char* what, hipEvent_t mark, Step step) {
+    auto failed = [&](hipError_t e) { return fail(e == hipErrorOutOfMemory ? GPSAT_ENOMEM : GPSAT_EHIP, std::string(what) + ": " + hipGetErrorString(e)); };
+    size_t bytes = 0;
+    hipError_t e = step(nullptr, bytes);
+    if (e != hipSuccess) return failed(e);
+    if (int rc = tmp.reserve(std::max<size_t>(bytes, 16))) return rc;
+    if (mark) HIP_TRY(hipEventRecord(mark, h->stream));
+    e = step(tmp.p, bytes);
+    return e != hipSuccess ? failed(e) : GPSAT_OK;
 }
 
 struct BatchDims { long long sumN = 0, sumP = 0, sumC = 0, sumM = 0, maxN = 0, maxP = 0; bool want_cov = false; };
@@ -725,62 +726,29 @@ int check_cv_refit(const gpsat_batch* b, const gpsat_cv_refit* cv, gpsat::CvFold
     return GPSAT_OK;
 }
 
-int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
-    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL handle or batch");
-    if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL gpsat_cv_refit");
-    if (b->T == 0) return GPSAT_OK;
-    BatchDims d;
-    int rc;
-    if ((rc = check_batch(b, false, d))) return rc;
-    gpsat::CvFoldTables tb;
-    if ((rc = check_cv_refit(b, cv, tb))) return rc;
-    // ---- 1. the batch itself
-    if ((rc = fit_predict(h, b, nullptr))) return rc;
-    double kernel_ms = h->last_kernel_ms, total_ms = h->last_total_ms;
-    const int T = b->T, D = b->D, H = D + 2;
+// Stage and expand: the packed tables to the device, CvFoldArgs laid out over the handle's three cvr buffers, the rows of every
+// derived tile written by the device, `delta` (the mean each tile was shifted by) read back.  Synchronises and records the timing.
+int cvr_stage_expand(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv, size_t sumN, const gpsat::CvFoldDerived& dv,
+                     const gpsat::CvFoldPacked& pk, gpsat::CvFoldArgs& a, std::vector<double>& delta) {
+    const int D = b->D;
     const bool f64 = b->dtype == GPSAT_F64, host = b->memory == GPSAT_MEM_HOST;
-    const size_t esz = f64 ? sizeof(double) : sizeof(float), sumN = (size_t)d.sumN;
-    const size_t F = (size_t)tb.fold_off[T];
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    // ---- 2. the derived batch: its tables here, its rows on the device
-    gpsat::CvFoldDerived dv;
-    gpsat::cvfold_derive(tb, b->obs_off, cv->min_obs, dv);
+    const size_t esz = f64 ? sizeof(double) : sizeof(float);
     const size_t F2 = dv.d_fold.size(), E = (size_t)dv.d_obs_off[F2], P2 = (size_t)dv.d_pred_off[F2];
-    for (size_t f = 0; f < F; ++f) {
-        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = nan;
-        cv->fold_nll[f] = nan; cv->fold_shift[f] = nan;
-        cv->fold_status[f] = GPSAT_STATUS_SKIPPED; cv->fold_n_eval[f] = 0;
-        if (cv->fold_n_iter) cv->fold_n_iter[f] = 0;
-        cv->fold_n_obs[f] = tb.fold_n_obs[f]; cv->fold_label[f] = tb.fold_label[f];
-    }
-    if (sumN == 0) return GPSAT_OK;
-    // one int64 / double block and one int32 block, laid out once for the host copy and the device
-    std::vector<long long> t64;                     // d_obs_off [F2+1], d_pred_off [F2+1], d_src_off [F2], then delta [F2] (doubles)
-    t64.insert(t64.end(), dv.d_obs_off.begin(), dv.d_obs_off.end());
-    t64.insert(t64.end(), dv.d_pred_off.begin(), dv.d_pred_off.end());
-    t64.insert(t64.end(), dv.d_src_off.begin(), dv.d_src_off.end());
-    const size_t n64 = t64.size() + F2;
-    std::vector<int> t32;
-    size_t o_src_n, o_fold, o_fold_ptr, o_fold_rows, o_fold_derived, o_row_fold, o_row_pos, o_status;
-    auto put = [&](const std::vector<int>& v, size_t& off) { off = t32.size(); t32.insert(t32.end(), v.begin(), v.end()); };
-    put(dv.d_src_n, o_src_n); put(dv.d_fold, o_fold); put(tb.fold_ptr, o_fold_ptr); put(tb.fold_rows, o_fold_rows);
-    put(dv.fold_derived, o_fold_derived); put(tb.row_fold, o_row_fold); put(tb.row_pos, o_row_pos);
-    o_status = t32.size();
-    if ((rc = h->cvr_tab.reserve(n64 * 8 + (t32.size() + F2) * sizeof(int)))) return rc;
+    int rc;
+    if ((rc = h->cvr_tab.reserve(pk.n64 * 8 + pk.n32 * sizeof(int)))) return rc;
     if ((rc = h->cvr_in.reserve(std::max<size_t>(E * (D + 1) + P2 * D, 1) * esz))) return rc;
     if ((rc = h->cvr_out.reserve(std::max<size_t>(3 * P2 + (host ? 3 * sumN : 0), 1) * esz))) return rc;
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     long long* d64 = static_cast<long long*>(h->cvr_tab.p);
-    int* d32 = reinterpret_cast<int*>(d64 + n64);
-    HIP_TRY(hipMemcpyAsync(d64, t64.data(), t64.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d32, t32.data(), t32.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    gpsat::CvFoldArgs a;
-    a.F2 = (int)F2; a.D = D; a.f64 = f64; a.recentre = cv->recentre; a.sumN = d.sumN;
-    a.d_obs_off = d64; a.d_pred_off = d64 + (F2 + 1); a.d_src_off = d64 + 2 * (F2 + 1);
-    a.delta = reinterpret_cast<double*>(d64 + 2 * (F2 + 1) + F2);
-    a.d_src_n = d32 + o_src_n; a.d_fold = d32 + o_fold; a.d_status = d32 + o_status;
-    a.fold_ptr = d32 + o_fold_ptr; a.fold_rows = d32 + o_fold_rows; a.fold_derived = d32 + o_fold_derived;
-    a.row_fold = d32 + o_row_fold; a.row_pos = d32 + o_row_pos;
+    int* d32 = reinterpret_cast<int*>(d64 + pk.n64);
+    HIP_TRY(hipMemcpyAsync(d64, pk.t64.data(), pk.t64.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d32, pk.t32.data(), pk.t32.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    a.F2 = (int)F2; a.D = D; a.f64 = f64; a.recentre = cv->recentre; a.sumN = (long long)sumN;
+    a.d_obs_off = d64 + pk.o_obs_off; a.d_pred_off = d64 + pk.o_pred_off; a.d_src_off = d64 + pk.o_src_off;
+    a.delta = reinterpret_cast<double*>(d64 + pk.o_delta);
+    a.d_src_n = d32 + pk.o_src_n; a.d_fold = d32 + pk.o_fold; a.d_status = d32 + pk.o_status;
+    a.fold_ptr = d32 + pk.o_fold_ptr; a.fold_rows = d32 + pk.o_fold_rows; a.fold_derived = d32 + pk.o_fold_derived;
+    a.row_fold = d32 + pk.o_row_fold; a.row_pos = d32 + pk.o_row_pos;
     // the source rows: the caller's device arrays, or where stage_batch left them for the first launch (X, then y)
     a.X = host ? h->bulk_in.p : b->X;
     a.y = host ? static_cast<const void*>(static_cast<const char*>(h->bulk_in.p) + sumN * D * esz) : b->y;
@@ -791,54 +759,87 @@ int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_r
     a.cv_mean = host ? out + 3 * P2 * esz : cv->cv_mean;
     a.cv_f_var = host ? out + (3 * P2 + sumN) * esz : cv->cv_f_var;
     a.cv_y_var = host ? out + (3 * P2 + 2 * sumN) * esz : cv->cv_y_var;
-    std::vector<double> delta(F2, 0.0);
+    delta.assign(F2, 0.0);
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     HIP_TRY(gpsat::launch_cvfold_expand(a, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if (F2) HIP_TRY(hipMemcpyAsync(delta.data(), a.delta, F2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // t64, t32 are local host memory
-    if ((rc = record_timing(h))) return rc;
-    const double expand_ms = h->last_kernel_ms;
-    kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
-    // ---- 3. all fitted folds as one batch
-    std::vector<double> th0(F2 * H), lo(F2 * H), hi(F2 * H), theta(F2 * H), nll(F2);
-    std::vector<int> status(F2, GPSAT_STATUS_SKIPPED), n_eval(F2), n_iter(F2);
+    HIP_TRY(hipStreamSynchronize(h->stream));          // pk's tables are host memory of the caller
+    return record_timing(h);
+}
+
+// The derived batch: every fitted fold a tile of a device-resident batch, its rows where the expansion left them.  A fold
+// starts from its tile's full-data theta (cv->start == 1, where that is finite and positive) or from theta0, in its tile's bounds.
+struct DerivedBatch {
+    std::vector<double> th0, lo, hi, theta, nll;
+    std::vector<int> status, n_eval, n_iter;
+    gpsat_batch b2;
+};
+
+void cvr_derived_batch(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldTables& tb, const gpsat::CvFoldDerived& dv,
+                       const gpsat::CvFoldArgs& a, DerivedBatch& db) {
+    const int H = b->D + 2;
+    const size_t F2 = dv.d_fold.size();
+    db.th0.resize(F2 * H); db.lo.resize(F2 * H); db.hi.resize(F2 * H); db.theta.resize(F2 * H); db.nll.resize(F2);
+    db.status.assign(F2, GPSAT_STATUS_SKIPPED); db.n_eval.resize(F2); db.n_iter.resize(F2);
     for (size_t j = 0; j < F2; ++j) {
         const size_t t = (size_t)tb.fold_tile[dv.d_fold[j]];
         bool full = cv->start == 1;
         for (int i = 0; i < H && full; ++i) full = b->theta[t * H + i] > 0.0 && std::isfinite(b->theta[t * H + i]);
         for (int i = 0; i < H; ++i) {
-            th0[j * H + i] = full ? b->theta[t * H + i] : b->theta0[t * H + i];
-            lo[j * H + i] = b->lo[t * H + i]; hi[j * H + i] = b->hi[t * H + i];
+            db.th0[j * H + i] = full ? b->theta[t * H + i] : b->theta0[t * H + i];
+            db.lo[j * H + i] = b->lo[t * H + i]; db.hi[j * H + i] = b->hi[t * H + i];
         }
     }
-    if (F2) {
-        gpsat_batch b2 = *b;
-        b2.T = (int)F2; b2.memory = GPSAT_MEM_DEVICE;
-        b2.obs_off = dv.d_obs_off.data(); b2.pred_off = dv.d_pred_off.data();
-        b2.theta0 = th0.data(); b2.lo = lo.data(); b2.hi = hi.data();
-        b2.X = a.Xd; b2.y = a.yd; b2.Xs = a.Xsd;
-        b2.theta = theta.data(); b2.nll = nll.data(); b2.grad = nullptr; b2.status = status.data(); b2.n_eval = n_eval.data(); b2.n_iter = n_iter.data();
-        b2.f_mean = const_cast<void*>(a.fm); b2.f_var = const_cast<void*>(a.fv); b2.y_var = const_cast<void*>(a.yv);
-        b2.cov_off = nullptr; b2.f_cov = nullptr;
-        if ((rc = fit_predict(h, &b2, nullptr))) return rc;
-        kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+    gpsat_batch& b2 = db.b2;
+    b2 = *b;
+    b2.T = (int)F2; b2.memory = GPSAT_MEM_DEVICE;
+    b2.obs_off = dv.d_obs_off.data(); b2.pred_off = dv.d_pred_off.data();
+    b2.theta0 = db.th0.data(); b2.lo = db.lo.data(); b2.hi = db.hi.data();
+    b2.X = a.Xd; b2.y = a.yd; b2.Xs = a.Xsd;
+    b2.theta = db.theta.data(); b2.nll = db.nll.data(); b2.grad = nullptr;
+    b2.status = db.status.data(); b2.n_eval = db.n_eval.data(); b2.n_iter = db.n_iter.data();
+    b2.f_mean = const_cast<void*>(a.fm); b2.f_var = const_cast<void*>(a.fv); b2.y_var = const_cast<void*>(a.yv);
+    b2.cov_off = nullptr; b2.f_cov = nullptr;
+}
+
+// The caller's per-fold outputs: `skipped` for every fold (before anything runs), then what the derived batch returned
+void cvr_folds_skipped(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldTables& tb) {
+    const int H = b->D + 2;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t f = 0; f < (size_t)tb.fold_off[b->T]; ++f) {
+        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = nan;
+        cv->fold_nll[f] = nan; cv->fold_shift[f] = nan;
+        cv->fold_status[f] = GPSAT_STATUS_SKIPPED; cv->fold_n_eval[f] = 0;
+        if (cv->fold_n_iter) cv->fold_n_iter[f] = 0;
+        cv->fold_n_obs[f] = tb.fold_n_obs[f]; cv->fold_label[f] = tb.fold_label[f];
     }
-    for (size_t j = 0; j < F2; ++j) {
+}
+
+void cvr_unpack(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldDerived& dv, const DerivedBatch& db,
+                const std::vector<double>& delta) {
+    const int H = b->D + 2;
+    for (size_t j = 0; j < dv.d_fold.size(); ++j) {
         const size_t f = (size_t)dv.d_fold[j];
-        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = theta[j * H + i];
-        cv->fold_nll[f] = nll[j]; cv->fold_shift[f] = delta[j];
-        cv->fold_status[f] = status[j]; cv->fold_n_eval[f] = n_eval[j];
-        if (cv->fold_n_iter) cv->fold_n_iter[f] = n_iter[j];
+        for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = db.theta[j * H + i];
+        cv->fold_nll[f] = db.nll[j]; cv->fold_shift[f] = delta[j];
+        cv->fold_status[f] = db.status[j]; cv->fold_n_eval[f] = db.n_eval[j];
+        if (cv->fold_n_iter) cv->fold_n_iter[f] = db.n_iter[j];
     }
-    // ---- 4. the predictions back at their rows
+}
+
+// Scatter and fetch: the status of every derived tile to the device, its predictions back at the rows they were held out
+// from, and (host mode) those to the caller.  Synchronises and records the timing.
+int cvr_scatter_fetch(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv, size_t sumN, const gpsat::CvFoldArgs& a,
+                      const std::vector<int>& status) {
+    const size_t esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float), F2 = status.size();
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     if (F2) HIP_TRY(hipMemcpyAsync(const_cast<int*>(a.d_status), status.data(), F2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     HIP_TRY(gpsat::launch_cvfold_scatter(a, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    if (host) {
+    if (b->memory == GPSAT_MEM_HOST) {
         void* const hp[3] = {cv->cv_mean, cv->cv_f_var, cv->cv_y_var};
         void* const dp[3] = {a.cv_mean, a.cv_f_var, a.cv_y_var};
         for (int i = 0; i < 3; ++i)
@@ -846,11 +847,106 @@ int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_r
     }
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if ((rc = record_timing(h))) return rc;
+    return record_timing(h);
+}
+
+// The batch itself, then its fitted folds as a second batch through fit_predict; the timing is the sum of the four steps.
+int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
+    if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL handle or batch");
+    if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL gpsat_cv_refit");
+    if (b->T == 0) return GPSAT_OK;
+    BatchDims d;
+    int rc;
+    if ((rc = check_batch(b, false, d))) return rc;
+    gpsat::CvFoldTables tb;
+    if ((rc = check_cv_refit(b, cv, tb))) return rc;
+    if ((rc = fit_predict(h, b, nullptr))) return rc;
+    double kernel_ms = h->last_kernel_ms, total_ms = h->last_total_ms;
+    gpsat::CvFoldDerived dv;
+    gpsat::cvfold_derive(tb, b->obs_off, cv->min_obs, dv);
+    cvr_folds_skipped(b, cv, tb);
+    const size_t sumN = (size_t)d.sumN, F2 = dv.d_fold.size();
+    if (sumN == 0) return GPSAT_OK;
+    const gpsat::CvFoldPacked pk = gpsat::cvfold_pack(tb, dv);
+    gpsat::CvFoldArgs a;
+    std::vector<double> delta;
+    if ((rc = cvr_stage_expand(h, b, cv, sumN, dv, pk, a, delta))) return rc;
+    const double expand_ms = h->last_kernel_ms;
+    kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+    DerivedBatch db;
+    cvr_derived_batch(b, cv, tb, dv, a, db);
+    if (F2) {
+        if ((rc = fit_predict(h, &db.b2, nullptr))) return rc;
+        kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+    }
+    cvr_unpack(b, cv, dv, db, delta);
+    if ((rc = cvr_scatter_fetch(h, b, cv, sumN, a, db.status))) return rc;
     if (dev_env("GPSAT_DEBUG_CVFOLD_STATS"))      // developer / scripts/cv_bench.py: the two streaming kernels on their own
         std::fprintf(stderr, "gpsat cvfold: %zu derived tiles, %zu expanded rows, %zu held-out rows: expand %.4f ms, scatter %.4f ms\n",
-                     F2, E, P2, expand_ms, h->last_kernel_ms);
+                     F2, (size_t)dv.d_obs_off[F2], (size_t)dv.d_pred_off[F2], expand_ms, h->last_kernel_ms);
     h->last_kernel_ms += kernel_ms; h->last_total_ms += total_ms;
+    return GPSAT_OK;
+}
+
+// ---- the steps of gpsat_select_batch_ex that are more than a call
+
+// The fill call of a two-call selection that the cache answers: the offsets from the host, the indices from the device.
+int select_from_cache(gpsat_handle* h, int32_t T, int64_t* off, int32_t* idx, int64_t capacity) {
+    const int64_t total = h->selc.total;
+    h->selc.forget();
+    std::memcpy(off, h->selc.off.data(), (size_t)(T + 1) * sizeof(int64_t));
+    if (capacity < total) return fail(GPSAT_EINVAL, "gpsat_select_batch: idx capacity too small (see off[T])");
+    if (int rc = begin_call(h)) return rc;
+    if (total > 0) HIP_TRY(hipMemcpy(idx, h->selc.d_result, (size_t)total * sizeof(int), hipMemcpyDeviceToHost));
+    return GPSAT_OK;
+}
+
+// The staged table sorted by the cells of `bin` (a.pts: the sorted copy, d_perm: the source row of every position), and the
+// order of the experts on the device (a.eorder).
+int select_bin_table(gpsat_handle* h, const gpsat::BinSpec& bin, const double* refs, gpsat::SelectArgs& a, const int*& d_perm) {
+    gpsat_handle::SelectBufs& sb = h->sel;
+    const long long M = a.M;
+    const int C = a.C, T = a.T;
+    int rc;
+    const size_t perm_bytes = ((size_t)M * 2 * sizeof(int) + 255) & ~size_t(255);
+    if ((rc = sb.perm.reserve(perm_bytes + (size_t)M * C * sizeof(double)))) return rc;
+    if ((rc = sb.keys.reserve((size_t)M * 2 * sizeof(unsigned)))) return rc;
+    int* d_rows = static_cast<int*>(sb.perm.p);
+    int* d_p = d_rows + M;
+    double* d_pp = reinterpret_cast<double*>(static_cast<char*>(sb.perm.p) + perm_bytes);
+    unsigned* d_k = static_cast<unsigned*>(sb.keys.p);
+    const double* pts = a.pts;
+    if ((rc = run_with_temp(h, sb.tmp, "select_bin_rows", nullptr, [&](void* temp, size_t& tb) {
+             return gpsat::select_bin_rows(M, C, pts, bin, d_k, d_k + M, d_rows, d_p, d_pp, temp, tb, h->stream);
+         })))
+        return rc;
+    a.pts = d_pp;
+    d_perm = d_p;
+    const std::vector<int> eord = gpsat::select_expert_order(bin, refs, T, C);
+    if ((rc = sb.ord.reserve((size_t)T * sizeof(int) + (size_t)(T + 1) * sizeof(unsigned)))) return rc;
+    HIP_TRY(hipMemcpyAsync(sb.ord.p, eord.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // `eord` is local host memory
+    a.eorder = static_cast<const int*>(sb.ord.p);
+    return GPSAT_OK;
+}
+
+// Positions of the binned table -> source rows, every expert's list ascending (source row order); d_result: where they are.
+int select_unbin_indices(gpsat_handle* h, int64_t M, int32_t T, const int64_t* off, const int* d_perm, int* d_idx, const int*& d_result) {
+    gpsat_handle::SelectBufs& sb = h->sel;
+    int rc;
+    if (off[T] > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_select_batch: more than 2^31-1 selected rows");
+    std::vector<unsigned> off32(T + 1);
+    for (int t = 0; t <= T; ++t) off32[t] = (unsigned)off[t];
+    unsigned* d_off32 = reinterpret_cast<unsigned*>(static_cast<char*>(sb.ord.p) + (size_t)T * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(d_off32, off32.data(), (size_t)(T + 1) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = sb.keys.reserve(std::max((size_t)M * 2 * sizeof(unsigned), (size_t)off[T] * sizeof(int))))) return rc;
+    int* d_sorted = static_cast<int*>(sb.keys.p);            // the row keys are no longer needed
+    if ((rc = run_with_temp(h, sb.tmp, "select_unbin", nullptr, [&](void* temp, size_t& tb) {
+             return gpsat::select_unbin(T, off[T], d_off32, d_perm, d_idx, d_sorted, temp, tb, h->stream);
+         })))
+        return rc;
+    d_result = d_sorted;
     return GPSAT_OK;
 }
 
@@ -1049,184 +1145,76 @@ int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t 
     if (!h || !sp || !off) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL argument");
     if (T < 0 || M < 0 || C < 1 || n_bounds < 0) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad sizes");
     if (M > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_select_batch: more than 2^31-1 rows");
-    if (sp->n_crit < 1 || sp->n_crit > GPSAT_SEL_MAXCRIT) return fail(GPSAT_EINVAL, "gpsat_select_batch: n_crit out of range");
     gpsat::SelectArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.n_crit = sp->n_crit;
-    for (int k = 0; k < sp->n_crit; ++k) {
-        // kind 2 (per-expert interval) only through gpsat_select_batch_ex, which passes the bounds
-        if (sp->kind[k] != 0 && sp->kind[k] != 1 && !(sp->kind[k] == 2 && n_bounds > 0))
-            return fail(GPSAT_EINVAL, "gpsat_select_batch: bad criterion kind");
-        if (sp->comp[k] < 0 || sp->comp[k] > 4) return fail(GPSAT_EINVAL, "gpsat_select_batch: bad comparison");
-        if (sp->kind[k] == 2) {
-            if (sp->cols[k][0] < 0 || sp->cols[k][0] >= C) return fail(GPSAT_EINVAL, "gpsat_select_batch: column index out of range");
-            if (sp->cols[k][1] < 0 || sp->cols[k][1] >= n_bounds) return fail(GPSAT_EINVAL, "gpsat_select_batch: bound index out of range");
-            a.kind[k] = 2; a.comp[k] = sp->comp[k]; a.ncols[k] = 1;
-            a.cols[k][0] = sp->cols[k][0]; a.cols[k][1] = sp->cols[k][1];
-            continue;
-        }
-        const int nc = sp->kind[k] == 0 ? 1 : sp->ncols[k];
-        if (nc < 1 || nc > 3) return fail(GPSAT_EINVAL, "gpsat_select_batch: ball criteria take 1..3 columns");
-        if (sp->kind[k] == 1 && sp->comp[k] != 3 && sp->comp[k] != 4) return fail(GPSAT_EINVAL, "gpsat_select_batch: ball criteria are < or <=");
-        a.kind[k] = sp->kind[k]; a.comp[k] = sp->comp[k]; a.ncols[k] = nc; a.val[k] = sp->val[k];
-        for (int m = 0; m < nc; ++m) {
-            if (sp->cols[k][m] < 0 || sp->cols[k][m] >= C) return fail(GPSAT_EINVAL, "gpsat_select_batch: column index out of range");
-            a.cols[k][m] = sp->cols[k][m];
-        }
-    }
+    const std::string bad = gpsat::select_check_spec(sp, C, n_bounds, a);
+    if (!bad.empty()) return fail(GPSAT_EINVAL, bad);
     off[0] = 0;
     if (T == 0) return GPSAT_OK;
     if ((M > 0 && !points) || !refs || (n_bounds > 0 && !bounds)) return fail(GPSAT_EINVAL, "gpsat_select_batch: NULL table");
-    const long long nB = (long long)T * n_bounds * 2;
-    if (idx && h->selc.total >= 0 && h->selc.pts == points && h->selc.refs == refs && h->selc.M == M && h->selc.C == C &&
-        h->selc.T == T && h->selc.n_bounds == n_bounds && h->selc.bounds == bounds && std::memcmp(&h->selc.sp, sp, sizeof(*sp)) == 0 &&
-        h->selc.fp == sel_fingerprint(points, (long long)M * C, refs, (long long)T * C, bounds, nB)) {
-        const int64_t total = h->selc.total;
-        h->selc.total = -1;
-        std::memcpy(off, h->selc.off.data(), (size_t)(T + 1) * sizeof(int64_t));
-        if (capacity < total) return fail(GPSAT_EINVAL, "gpsat_select_batch: idx capacity too small (see off[T])");
-        if (int rc0 = begin_call(h)) return rc0;
-        if (total > 0) HIP_TRY(hipMemcpy(idx, h->selc.d_result, (size_t)total * sizeof(int), hipMemcpyDeviceToHost));
-        return GPSAT_OK;
-    }
+    const gpsat::SelectCache::Call call = {sp, M, C, points, T, refs, n_bounds, bounds};
+    if (idx && h->selc.matches(call)) return select_from_cache(h, T, off, idx, capacity);
     int rc;
     if ((rc = begin_call(h))) return rc;
-    if ((rc = h->sel_pts.reserve(std::max<size_t>((size_t)M * C, 1) * sizeof(double)))) return rc;
-    if ((rc = h->sel_refs.reserve((size_t)T * C * sizeof(double)))) return rc;
-    // row chunks: enough workgroups to fill the chip (T/32 workgroups per chunk), chunk a multiple of 64 rows
-    const int wgs_per_chunk = std::max(1, (T + 31) / 32);
-    int n_chunks = (int)std::min<long long>(std::max<long long>(1, (4096 + wgs_per_chunk - 1) / wgs_per_chunk), std::max<long long>(1, (M + 4095) / 4096));
+    gpsat_handle::SelectBufs& sb = h->sel;
+    // ---- stage: the tables to the device, one count per (expert, row chunk) cell
+    if ((rc = sb.pts.reserve(std::max<size_t>((size_t)M * C, 1) * sizeof(double)))) return rc;
+    if ((rc = sb.refs.reserve((size_t)T * C * sizeof(double)))) return rc;
     const long long sub = gpsat::select_sub_rows();             // rows per bounding box: chunks are whole numbers of them
-    long long chunk_rows = ((M + n_chunks - 1) / n_chunks + sub - 1) / sub * sub;
-    if (chunk_rows < sub) chunk_rows = sub;
-    n_chunks = (int)std::max<long long>(1, (M + chunk_rows - 1) / chunk_rows);
-    const size_t ncell = (size_t)T * n_chunks;
-    if ((rc = h->sel_cnt.reserve(2 * ncell * sizeof(long long)))) return rc;
-    if (M > 0) HIP_TRY(hipMemcpyAsync(h->sel_pts.p, points, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->sel_refs.p, refs, (size_t)T * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const gpsat::SelectChunks ch = gpsat::select_chunks(M, T, sub);
+    const size_t ncell = (size_t)T * ch.n_chunks;
+    if ((rc = sb.cnt.reserve(2 * ncell * sizeof(long long)))) return rc;
+    if (M > 0) HIP_TRY(hipMemcpyAsync(sb.pts.p, points, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(sb.refs.p, refs, (size_t)T * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
     a.n_bounds = n_bounds;
     a.bounds = nullptr;
     if (n_bounds > 0) {
-        if ((rc = h->sel_bnd.reserve((size_t)nB * sizeof(double)))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->sel_bnd.p, bounds, (size_t)nB * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        a.bounds = static_cast<const double*>(h->sel_bnd.p);
+        const size_t nB = (size_t)T * n_bounds * 2;
+        if ((rc = sb.bnd.reserve(nB * sizeof(double)))) return rc;
+        HIP_TRY(hipMemcpyAsync(sb.bnd.p, bounds, nB * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        a.bounds = static_cast<const double*>(sb.bnd.p);
     }
     a.M = M; a.C = C; a.T = T;
-    a.n_chunks = n_chunks; a.chunk_rows = chunk_rows;
+    a.n_chunks = ch.n_chunks; a.chunk_rows = ch.chunk_rows;
     a.eorder = nullptr;
-    a.pts = static_cast<const double*>(h->sel_pts.p);
-    // ---- spatial binning (gpsat_select.hip): large tables are sorted on the device by the grid cell of the criteria's
-    // columns -- a ball criterion's columns with cells of its radius, a two-sided 1-D window's column with cells of half its
-    // width, at most three columns -- and the experts are dealt to the waves in the order of their own cells
+    a.pts = static_cast<const double*>(sb.pts.p);
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    gpsat::BinSpec bin;
-    bin.ndim = 0;
+    // ---- bin (gpsat_select.hip): large tables are sorted on the device by the grid cell of the criteria's columns, and the
+    // experts are dealt to the waves in the order of their own cells
+    gpsat::BinSpec bin = {};
+    if (M >= 65536 && !dev_env("GPSAT_DEBUG_NO_BINNING")) bin = gpsat::select_bin_dims(a, points, M, C);
     const int* d_perm = nullptr;
-    if (M >= 65536 && !dev_env("GPSAT_DEBUG_NO_BINNING")) {
-        auto add_dim = [&](int col, double cell) {
-            if (bin.ndim >= 3 || !(cell > 0.0) || !std::isfinite(cell)) return;
-            for (int d = 0; d < bin.ndim; ++d) if (bin.col[d] == col) return;
-            double mn = INFINITY, mx = -INFINITY;
-            const double* x = points + (size_t)col * M;
-            for (int64_t i = 0; i < M; ++i) { const double v = x[i]; if (v < mn) mn = v; if (v > mx) mx = v; }
-            if (!(mn <= mx) || !std::isfinite(mn) || !std::isfinite(mx)) return;
-            const double nc = std::min(1024.0, std::max(1.0, std::ceil((mx - mn) / cell)));
-            bin.col[bin.ndim] = col; bin.origin[bin.ndim] = mn; bin.ncell[bin.ndim] = (int)nc;
-            bin.inv_cell[bin.ndim] = (mx > mn) ? nc / (mx - mn) : 0.0;
-            ++bin.ndim;
-        };
-        for (int k = 0; k < a.n_crit; ++k) {              // two-sided windows first (GPSat: the time column)
-            if (a.kind[k] != 0 || !(a.comp[k] == 3 || a.comp[k] == 4)) continue;
-            for (int k2 = 0; k2 < a.n_crit; ++k2)
-                if (a.kind[k2] == 0 && (a.comp[k2] == 0 || a.comp[k2] == 1) && a.cols[k2][0] == a.cols[k][0] && a.val[k] > a.val[k2])
-                    add_dim(a.cols[k][0], 0.5 * (a.val[k] - a.val[k2]));
-        }
-        for (int k = 0; k < a.n_crit; ++k)
-            if (a.kind[k] == 1) for (int m = 0; m < a.ncols[k]; ++m) add_dim(a.cols[k][m], a.val[k]);
-    }
-    if (bin.ndim > 0) {
-        const size_t perm_bytes = ((size_t)M * 2 * sizeof(int) + 255) & ~size_t(255);
-        if ((rc = h->sel_perm.reserve(perm_bytes + (size_t)M * C * sizeof(double)))) return rc;
-        if ((rc = h->sel_keys.reserve((size_t)M * 2 * sizeof(unsigned)))) return rc;
-        int* d_rows = static_cast<int*>(h->sel_perm.p);
-        int* d_p = d_rows + M;
-        double* d_pp = reinterpret_cast<double*>(static_cast<char*>(h->sel_perm.p) + perm_bytes);
-        unsigned* d_k = static_cast<unsigned*>(h->sel_keys.p);
-        size_t tb = 0;
-        HIP_TRY(gpsat::select_bin_rows(M, C, a.pts, bin, d_k, d_k + M, d_rows, d_p, d_pp, nullptr, tb, h->stream));
-        if ((rc = h->sel_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
-        HIP_TRY(gpsat::select_bin_rows(M, C, a.pts, bin, d_k, d_k + M, d_rows, d_p, d_pp, h->sel_tmp.p, tb, h->stream));
-        a.pts = d_pp;
-        d_perm = d_p;
-        // experts by their own cell
-        std::vector<unsigned> ekey(T);
-        for (int t = 0; t < T; ++t) {
-            unsigned key = 0;
-            for (int d = 0; d < bin.ndim; ++d) {
-                const double cf = (refs[(size_t)t * C + bin.col[d]] - bin.origin[d]) * bin.inv_cell[d];
-                const int cell = (cf >= 0.0) ? (int)std::min(cf, (double)(bin.ncell[d] - 1)) : 0;
-                key = key * (unsigned)bin.ncell[d] + (unsigned)cell;
-            }
-            ekey[t] = key;
-        }
-        std::vector<int> eord(T);
-        std::iota(eord.begin(), eord.end(), 0);
-        std::stable_sort(eord.begin(), eord.end(), [&](int x, int y) { return ekey[x] < ekey[y]; });
-        if ((rc = h->sel_ord.reserve((size_t)T * sizeof(int) + (size_t)(T + 1) * sizeof(unsigned)))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->sel_ord.p, eord.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));          // `eord` is local host memory
-        a.eorder = static_cast<const int*>(h->sel_ord.p);
-    }
-    a.refs = static_cast<const double*>(h->sel_refs.p);
-    a.counts = static_cast<long long*>(h->sel_cnt.p);
+    if (bin.ndim > 0 && (rc = select_bin_table(h, bin, refs, a, d_perm))) return rc;
+    a.refs = static_cast<const double*>(sb.refs.p);
+    a.counts = static_cast<long long*>(sb.cnt.p);
+    // ---- boxes: per-column [min, max] of every `sub` rows, which let a wave skip sub-chunks none of its experts can select from
     a.box = nullptr;
     if (M > 0) {
-        // per-column [min, max] of every `sub` rows: lets a wave skip sub-chunks none of its experts can select from
         const size_t nsub = (size_t)((M + sub - 1) / sub);
-        if ((rc = h->sel_box.reserve(nsub * C * 2 * sizeof(double)))) return rc;
-        HIP_TRY(gpsat::launch_select_boxes(M, C, a.pts, static_cast<double*>(h->sel_box.p), h->stream));
-        a.box = static_cast<const double*>(h->sel_box.p);
+        if ((rc = sb.box.reserve(nsub * C * 2 * sizeof(double)))) return rc;
+        HIP_TRY(gpsat::launch_select_boxes(M, C, a.pts, static_cast<double*>(sb.box.p), h->stream));
+        a.box = static_cast<const double*>(sb.box.p);
     }
+    // ---- count, scan on the host (cnt becomes the start offset of every cell)
     HIP_TRY(gpsat::launch_select(a, false, h->stream));
     std::vector<long long> cnt(ncell);
     HIP_TRY(hipMemcpyAsync(cnt.data(), a.counts, ncell * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    // exclusive scan over (expert, chunk) cells, expert-major: cnt becomes the start offset of every cell
-    long long run = 0;
-    for (int t = 0; t < T; ++t) {
-        off[t] = run;
-        for (int cc = 0; cc < n_chunks; ++cc) { const long long v = cnt[(size_t)t * n_chunks + cc]; cnt[(size_t)t * n_chunks + cc] = run; run += v; }
-    }
-    off[T] = run;
+    gpsat::select_scan(cnt.data(), T, ch.n_chunks, off);
     if (idx && capacity < off[T]) return fail(GPSAT_EINVAL, "gpsat_select_batch: idx capacity too small (see off[T])");
-    const int* d_final = nullptr;
+    // ---- fill, unbin, fetch
+    const int* d_result = nullptr;
     if (off[T] > 0) {
-        if ((rc = h->sel_idx.reserve((size_t)off[T] * sizeof(int)))) return rc;
-        long long* d_off = static_cast<long long*>(h->sel_cnt.p) + ncell;
+        if ((rc = sb.idx.reserve((size_t)off[T] * sizeof(int)))) return rc;
+        long long* d_off = static_cast<long long*>(sb.cnt.p) + ncell;
         HIP_TRY(hipMemcpyAsync(d_off, cnt.data(), ncell * sizeof(long long), hipMemcpyHostToDevice, h->stream));
         a.off = d_off;
-        a.idx = static_cast<int*>(h->sel_idx.p);
+        a.idx = static_cast<int*>(sb.idx.p);
         HIP_TRY(gpsat::launch_select(a, true, h->stream));
-        const int* d_result = a.idx;
-        if (d_perm) {
-            // positions of the binned table -> source rows, every expert's list ascending (source row order)
-            if (off[T] > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_select_batch: more than 2^31-1 selected rows");
-            std::vector<unsigned> off32(T + 1);
-            for (int t = 0; t <= T; ++t) off32[t] = (unsigned)off[t];
-            unsigned* d_off32 = reinterpret_cast<unsigned*>(static_cast<char*>(h->sel_ord.p) + (size_t)T * sizeof(int));
-            HIP_TRY(hipMemcpyAsync(d_off32, off32.data(), (size_t)(T + 1) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if ((rc = h->sel_keys.reserve(std::max((size_t)M * 2 * sizeof(unsigned), (size_t)off[T] * sizeof(int))))) return rc;
-            int* d_sorted = static_cast<int*>(h->sel_keys.p);            // the row keys are no longer needed
-            size_t tb = 0;
-            HIP_TRY(gpsat::select_unbin(T, off[T], d_off32, d_perm, a.idx, d_sorted, nullptr, tb, h->stream));
-            if ((rc = h->sel_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
-            HIP_TRY(gpsat::select_unbin(T, off[T], d_off32, d_perm, a.idx, d_sorted, h->sel_tmp.p, tb, h->stream));
-            d_result = d_sorted;
-        }
+        d_result = a.idx;
+        if (d_perm && (rc = select_unbin_indices(h, M, T, off, d_perm, a.idx, d_result))) return rc;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-        d_final = d_result;
         if (idx) HIP_TRY(hipMemcpyAsync(idx, d_result, (size_t)off[T] * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     } else {
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1234,14 +1222,8 @@ int gpsat_select_batch_ex(gpsat_handle* h, const gpsat_select_spec* sp, int64_t 
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if ((rc = record_timing(h))) return rc;                     // kernel time: count + scan round trip + fill
-    if (!idx) {
-        // sizes asked for: the indices stay on the device for the call that follows with the same arguments
-        h->selc.pts = points; h->selc.refs = refs; h->selc.M = M; h->selc.C = C; h->selc.T = T; h->selc.sp = *sp;
-        h->selc.bounds = bounds; h->selc.n_bounds = n_bounds;
-        h->selc.d_result = d_final; h->selc.total = off[T];
-        h->selc.fp = sel_fingerprint(points, (long long)M * C, refs, (long long)T * C, bounds, nB);
-        h->selc.off.assign(off, off + T + 1);
-    }
+    // sizes asked for: the indices stay on the device for the call that follows with the same arguments
+    if (!idx) h->selc.remember(call, off, d_result);
     return GPSAT_OK;
 }
 
@@ -1250,51 +1232,27 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
                     uint32_t stats, int64_t capacity, int64_t* n_cells, int64_t* keys, double* out) {
     if (!h || !n_cells) return fail(GPSAT_EINVAL, "gpsat_bin_batch: NULL handle or n_cells");
     *n_cells = 0;
-    if (R < 0 || G < 0 || capacity < 0) return fail(GPSAT_EINVAL, "gpsat_bin_batch: bad sizes");
-    if (R > 2147483647LL) return fail(GPSAT_EINVAL, "gpsat_bin_batch: more than 2^31-1 rows in one call");
-    const uint32_t all = GPSAT_BIN_COUNT | GPSAT_BIN_SUM | GPSAT_BIN_MEAN | GPSAT_BIN_STD | GPSAT_BIN_MIN | GPSAT_BIN_MAX | GPSAT_BIN_MEDIAN;
-    if (stats == 0 || (stats & ~all)) return fail(GPSAT_EINVAL, "gpsat_bin_batch: stats must be a non-empty OR of GPSAT_BIN_*");
-    const bool two_d = y != nullptr;
-    auto check_axis = [](const char* name, int n, const double* e, double hi) -> std::string {
-        if (n < 2 || !e) return std::string("gpsat_bin_batch: ") + name + " needs at least 2 edges";
-        for (int i = 0; i < n; ++i) {
-            if (!std::isfinite(e[i])) return std::string("gpsat_bin_batch: ") + name + " edges must be finite";
-            if (i > 0 && !(e[i] > e[i - 1])) return std::string("gpsat_bin_batch: ") + name + " edges must be strictly increasing";
-        }
-        if (!(hi >= e[n - 1])) return std::string("gpsat_bin_batch: the upper limit of the last ") + name + " bin is below the last edge";
-        return std::string();
-    };
-    std::string msg = check_axis("x", nx, ex, x_hi);
-    if (msg.empty() && two_d) msg = check_axis("y", ny, ey, y_hi);
-    if (!msg.empty()) return fail(GPSAT_EINVAL, msg);
-    const unsigned long long cells = (unsigned long long)(nx - 1) * (unsigned long long)(two_d ? ny - 1 : 1);
-    if (cells >= (1ull << 31)) return fail(GPSAT_EINVAL, "gpsat_bin_batch: 2^31 or more cells per group");
-    if (G > 0 && cells > ((1ull << 63) - 1) / (unsigned long long)G) return fail(GPSAT_EINVAL, "gpsat_bin_batch: G * cells must stay below 2^63");
+    const std::string bad = gpsat::bin_check(R, x, y, v, gid, G, nx, ex, x_hi, ny, ey, y_hi, stats, capacity);
+    if (!bad.empty()) return fail(GPSAT_EINVAL, bad);
     if (R == 0 || G == 0) return GPSAT_OK;
-    if (!x || !v) return fail(GPSAT_EINVAL, "gpsat_bin_batch: x / v is NULL");
-    if (gid)
-        for (int64_t i = 0; i < R; ++i)
-            if (gid[i] < 0 || gid[i] >= G)
-                return fail(GPSAT_EINVAL, "gpsat_bin_batch: gid[" + std::to_string(i) + "] = " + std::to_string(gid[i]) + " is not in 0.." + std::to_string(G - 1));
-    int n_stat = 0;
-    for (uint32_t b = 1; b <= GPSAT_BIN_MEDIAN; b <<= 1) n_stat += (stats & b) ? 1 : 0;
+    const bool two_d = y != nullptr, median = (stats & GPSAT_BIN_MEDIAN) != 0;
+    const gpsat::BinLayout l = gpsat::bin_layout(R, nx, ny, two_d, gid != nullptr, median, gpsat::bin_long_rows());
+    const gpsat::BinScales sc = gpsat::bin_scales(nx, ex, ny, ey, two_d, G, stats);
     int rc;
     if ((rc = begin_call(h))) return rc;
+    gpsat_handle::BinBufs& bb = h->bin;
+    if ((rc = bb.in.reserve(l.in_bytes))) return rc;
+    if ((rc = bb.keys.reserve(l.keys_bytes))) return rc;
+    if ((rc = bb.rows.reserve(l.rows_bytes))) return rc;
+    if ((rc = bb.vals.reserve(l.vals_bytes))) return rc;
+    if ((rc = bb.runs.reserve(l.runs_bytes))) return rc;
+    // ---- stage: edges and columns to the device
     const size_t nR = (size_t)R;
-    const size_t edge_bytes = ((size_t)(nx + (two_d ? ny : 0)) * sizeof(double) + 255) & ~size_t(255);
-    if ((rc = h->bin_in.reserve(edge_bytes + (two_d ? 3 : 2) * nR * sizeof(double) + nR * sizeof(int)))) return rc;
-    if ((rc = h->bin_keys.reserve(2 * nR * sizeof(unsigned long long)))) return rc;
-    if ((rc = h->bin_rows.reserve(2 * nR * sizeof(unsigned)))) return rc;
-    const bool median = (stats & GPSAT_BIN_MEDIAN) != 0;
-    if ((rc = h->bin_vals.reserve((median ? 3 : 1) * nR * sizeof(double)))) return rc;
-    const size_t starts_bytes = ((nR + 1) * sizeof(unsigned) + 255) & ~size_t(255);
-    const size_t flag_bytes = (nR + 255) & ~size_t(255);
-    if ((rc = h->bin_runs.reserve(starts_bytes + 256 + flag_bytes + (nR / gpsat::bin_long_rows() + 1) * sizeof(unsigned)))) return rc;
     gpsat::BinArgs a;
     std::memset(&a, 0, sizeof(a));
     a.R = R; a.nx = nx; a.ny = two_d ? ny : 2;
-    double* d_e = static_cast<double*>(h->bin_in.p);
-    double* d_col = reinterpret_cast<double*>(static_cast<char*>(h->bin_in.p) + edge_bytes);
+    char* d_in = static_cast<char*>(bb.in.p);
+    double* d_e = reinterpret_cast<double*>(d_in);
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     HIP_TRY(hipMemcpyAsync(d_e, ex, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     a.ex = d_e;
@@ -1302,57 +1260,52 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
         HIP_TRY(hipMemcpyAsync(d_e + nx, ey, (size_t)ny * sizeof(double), hipMemcpyHostToDevice, h->stream));
         a.ey = d_e + nx;
     }
-    HIP_TRY(hipMemcpyAsync(d_col, x, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    a.x = d_col; d_col += nR;
-    HIP_TRY(hipMemcpyAsync(d_col, v, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    a.v = d_col; d_col += nR;
+    HIP_TRY(hipMemcpyAsync(d_in + l.in_x, x, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.x = reinterpret_cast<const double*>(d_in + l.in_x);
+    HIP_TRY(hipMemcpyAsync(d_in + l.in_v, v, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.v = reinterpret_cast<const double*>(d_in + l.in_v);
     if (two_d) {
-        HIP_TRY(hipMemcpyAsync(d_col, y, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        a.y = d_col; d_col += nR;
+        HIP_TRY(hipMemcpyAsync(d_in + l.in_y, y, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        a.y = reinterpret_cast<const double*>(d_in + l.in_y);
     }
     if (gid) {
-        HIP_TRY(hipMemcpyAsync(d_col, gid, nR * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        a.gid = reinterpret_cast<const int*>(d_col);
+        HIP_TRY(hipMemcpyAsync(d_in + l.in_gid, gid, nR * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        a.gid = reinterpret_cast<const int*>(d_in + l.in_gid);
     }
     a.x_hi = x_hi; a.y_hi = y_hi;
-    a.inv_x = (double)(nx - 1) / (ex[nx - 1] - ex[0]);
-    a.inv_y = two_d ? (double)(ny - 1) / (ey[ny - 1] - ey[0]) : 0.0;
-    if (!std::isfinite(a.inv_x)) a.inv_x = 0.0;           // the range overflowed: the guess is bin 0, the correction does the rest
-    if (!std::isfinite(a.inv_y)) a.inv_y = 0.0;
-    a.sentinel = cells * (unsigned long long)G;
-    a.keys = static_cast<unsigned long long*>(h->bin_keys.p); a.keys_sorted = a.keys + nR;
-    a.rows = static_cast<unsigned*>(h->bin_rows.p); a.perm = a.rows + nR;
-    a.vs = static_cast<double*>(h->bin_vals.p);
+    a.inv_x = sc.inv_x; a.inv_y = sc.inv_y; a.sentinel = sc.sentinel;
+    a.keys = static_cast<unsigned long long*>(bb.keys.p); a.keys_sorted = a.keys + nR;
+    a.rows = static_cast<unsigned*>(bb.rows.p); a.perm = a.rows + nR;
+    a.vs = static_cast<double*>(bb.vals.p);
     if (median) { a.vcanon = a.vs + nR; a.vsorted = a.vs + 2 * nR; }
-    a.starts = static_cast<unsigned*>(h->bin_runs.p);
-    char* d_info = static_cast<char*>(h->bin_runs.p) + starts_bytes;
-    a.n_cells = reinterpret_cast<long long*>(d_info);
-    a.n_runs = reinterpret_cast<unsigned*>(d_info + 16);
-    a.n_long = reinterpret_cast<unsigned*>(d_info + 32);
-    a.flags = reinterpret_cast<unsigned char*>(d_info + 256);
-    a.long_list = reinterpret_cast<unsigned*>(d_info + 256 + flag_bytes);
+    char* d_runs = static_cast<char*>(bb.runs.p);
+    a.starts = reinterpret_cast<unsigned*>(d_runs);
+    a.n_cells = reinterpret_cast<long long*>(d_runs + l.runs_n_cells);
+    a.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
+    a.n_long = reinterpret_cast<unsigned*>(d_runs + l.runs_n_long);
+    a.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+    a.long_list = reinterpret_cast<unsigned*>(d_runs + l.runs_long_list);
     a.mask = stats;
-    size_t tb = 0;
-    HIP_TRY(gpsat::bin_sort_rows(a, nullptr, tb, h->stream));
-    if ((rc = h->bin_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(gpsat::bin_sort_rows(a, h->bin_tmp.p, tb, h->stream));
+    // ---- sort (the kernel time starts once its scratch is there), read the counts
+    if ((rc = run_with_temp(h, bb.tmp, "bin_sort_rows", h->ev[1], [&](void* temp, size_t& tb) { return gpsat::bin_sort_rows(a, temp, tb, h->stream); })))
+        return rc;
     long long info[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(info, a.n_cells, sizeof(info), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const long long nc = info[0], n_valid = info[1];
     *n_cells = nc;
+    // ---- stats, fetch
     if (nc > 0 && capacity >= nc) {
         if (!keys || !out) return fail(GPSAT_EINVAL, "gpsat_bin_batch: keys / out is NULL");
-        if ((rc = h->bin_out.reserve((size_t)nc * (n_stat + 1) * sizeof(double)))) return rc;
-        a.out_keys = static_cast<long long*>(h->bin_out.p);
+        if ((rc = bb.out.reserve((size_t)nc * (sc.n_stat + 1) * sizeof(double)))) return rc;
+        a.out_keys = static_cast<long long*>(bb.out.p);
         a.out = reinterpret_cast<double*>(a.out_keys + nc);
-        HIP_TRY(gpsat::bin_cell_stats(a, nc, n_valid, nullptr, tb, h->stream));
-        if ((rc = h->bin_tmp.reserve(std::max<size_t>(tb, 16)))) return rc;
-        HIP_TRY(gpsat::bin_cell_stats(a, nc, n_valid, h->bin_tmp.p, tb, h->stream));
+        if ((rc = run_with_temp(h, bb.tmp, "bin_cell_stats", nullptr,
+                                [&](void* temp, size_t& tb) { return gpsat::bin_cell_stats(a, nc, n_valid, temp, tb, h->stream); })))
+            return rc;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         HIP_TRY(hipMemcpyAsync(keys, a.out_keys, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        for (int s = 0; s < n_stat; ++s)
+        for (int s = 0; s < sc.n_stat; ++s)
             HIP_TRY(hipMemcpyAsync(out + (size_t)s * capacity, a.out + (size_t)s * nc, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     } else {
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1371,8 +1324,8 @@ int gpsat_smooth_batch(gpsat_handle* h, int32_t T, const double* x, const double
     if (T == 0) return GPSAT_OK;
     int rc;
     if ((rc = begin_call(h))) return rc;
-    if ((rc = h->sel_pts.reserve((size_t)4 * T * sizeof(double)))) return rc;
-    double* d = static_cast<double*>(h->sel_pts.p);
+    if ((rc = h->sel.pts.reserve((size_t)4 * T * sizeof(double)))) return rc;
+    double* d = static_cast<double*>(h->sel.pts.p);
     HIP_TRY(hipMemcpyAsync(d, x, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d + T, y, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d + 2 * (size_t)T, vals, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1396,17 +1349,17 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     int rc;
     if ((rc = begin_call(h))) return rc;
     const size_t nd = (size_t)(2 * ndim + nvars + 1) * R + (size_t)nvars * G;
-    if ((rc = h->sel_pts.reserve(std::max<size_t>(nd, 1) * sizeof(double)))) return rc;
-    if ((rc = h->sel_cnt.reserve((size_t)(G + 1) * sizeof(long long)))) return rc;
-    double* d = static_cast<double*>(h->sel_pts.p);
+    if ((rc = h->sel.pts.reserve(std::max<size_t>(nd, 1) * sizeof(double)))) return rc;
+    if ((rc = h->sel.cnt.reserve((size_t)(G + 1) * sizeof(long long)))) return rc;
+    double* d = static_cast<double*>(h->sel.pts.p);
     double* dp = d; double* dx = d + (size_t)ndim * R; double* dv = dx + (size_t)ndim * R; double* dsig = dv + (size_t)nvars * R; double* dout = dsig + R;
     HIP_TRY(hipMemcpyAsync(dp, pred, (size_t)ndim * R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(dx, xprt, (size_t)ndim * R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(dv, vals, (size_t)nvars * R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sigma_rows) HIP_TRY(hipMemcpyAsync(dsig, sigma_rows, (size_t)R * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->sel_cnt.p, seg, (size_t)(G + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->sel.cnt.p, seg, (size_t)(G + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(gpsat::launch_glue(G, ndim, nvars, R, static_cast<const long long*>(h->sel_cnt.p), dp, dx, dv, sigma, sigma_rows ? dsig : nullptr, dout, h->stream));
+    HIP_TRY(gpsat::launch_glue(G, ndim, nvars, R, static_cast<const long long*>(h->sel.cnt.p), dp, dx, dv, sigma, sigma_rows ? dsig : nullptr, dout, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)nvars * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

@@ -93,5 +93,29 @@ inline void cvfold_derive(const CvFoldTables& tb, const int64_t* obs_off, int mi
     }
 }
 
+// The tables the two kernels read, packed for one copy each: a block of 64-bit words and a block of int32, laid out once for the
+// host copy and the device.  Each block ends with F2 words that only the device holds (delta as doubles; d_status).
+struct CvFoldPacked {
+    std::vector<long long> t64;        // d_obs_off [F2+1], d_pred_off [F2+1], d_src_off [F2]
+    size_t o_obs_off = 0, o_pred_off = 0, o_src_off = 0, o_delta = 0, n64 = 0;     // offsets into the 64-bit block, and its words
+    std::vector<int> t32;              // d_src_n, d_fold [F2]; fold_ptr [F+1]; fold_rows [R]; fold_derived [F]; row_fold, row_pos [sumN]
+    size_t o_src_n = 0, o_fold = 0, o_fold_ptr = 0, o_fold_rows = 0, o_fold_derived = 0, o_row_fold = 0, o_row_pos = 0, o_status = 0, n32 = 0;
+};
+
+inline CvFoldPacked cvfold_pack(const CvFoldTables& tb, const CvFoldDerived& dv) {
+    CvFoldPacked p;
+    const size_t F2 = dv.d_fold.size();
+    auto put64 = [&](const std::vector<int64_t>& v, size_t& off) { off = p.t64.size(); p.t64.insert(p.t64.end(), v.begin(), v.end()); };
+    put64(dv.d_obs_off, p.o_obs_off); put64(dv.d_pred_off, p.o_pred_off); put64(dv.d_src_off, p.o_src_off);
+    p.o_delta = p.t64.size();
+    p.n64 = p.t64.size() + F2;
+    auto put = [&](const std::vector<int>& v, size_t& off) { off = p.t32.size(); p.t32.insert(p.t32.end(), v.begin(), v.end()); };
+    put(dv.d_src_n, p.o_src_n); put(dv.d_fold, p.o_fold); put(tb.fold_ptr, p.o_fold_ptr); put(tb.fold_rows, p.o_fold_rows);
+    put(dv.fold_derived, p.o_fold_derived); put(tb.row_fold, p.o_row_fold); put(tb.row_pos, p.o_row_pos);
+    p.o_status = p.t32.size();
+    p.n32 = p.t32.size() + F2;
+    return p;
+}
+
 }  // namespace gpsat
 #endif

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "gpsat_select_types.h"
+
 // Largest tile the C ABI accepts in any dtype (gpsat_max_tile_obs searches down from here), and the block columns (32
 // observations each) of the largest fp32 tile: the words of the fp32 sweep flags colrow[] in the workgroup state
 // (gpsat_opt.h Shared) and in each cooperative control block (gpsat_coop.h CoopCtl).  phase_pt writes colrow[0 .. NB-1].
@@ -125,16 +127,8 @@ size_t workspace_floats_per_wg_w8(int NBmax, int PCcov);
 hipError_t launch_tiles_w8(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 int state_words_w8();
 
-#define GPSAT_SEL_MAXCRIT 4
-
-// tile selection (gpsat_select.hip); all pointers are device pointers
-struct SelectArgs {
-    int n_crit;
-    int kind[GPSAT_SEL_MAXCRIT];      // 0: 1-D compare, 1: Euclidean ball, 2: per-expert interval on cols[k][0], bounds cols[k][1]
-    int comp[GPSAT_SEL_MAXCRIT];      // 0 >=, 1 >, 2 ==, 3 <, 4 <=
-    int ncols[GPSAT_SEL_MAXCRIT];
-    int cols[GPSAT_SEL_MAXCRIT][3];
-    double val[GPSAT_SEL_MAXCRIT];
+// tile selection (gpsat_select.hip); all pointers are device pointers.  The criteria come first (gpsat_select_types.h).
+struct SelectArgs : SelectCriteria {
     long long M;                      // rows of the point table
     int C;                            // columns of the point table / reference table
     int T;                            // experts
@@ -155,14 +149,7 @@ hipError_t launch_select(const SelectArgs& a, bool fill, hipStream_t stream);
 hipError_t launch_select_boxes(long long M, int C, const double* pts, double* box, hipStream_t stream);
 int select_sub_rows();      // rows per box; chunk_rows must be a multiple of it
 
-// Spatial binning of the point table (gpsat_select.hip): rows sorted by the cell of up to 3 columns, so that the boxes of
-// consecutive rows are tight whatever order the table came in.
-struct BinSpec {
-    int ndim;                         // binned columns (1..3)
-    int col[3];
-    double origin[3], inv_cell[3];
-    int ncell[3];
-};
+// Spatial binning of the point table (gpsat_select.hip) by a BinSpec (gpsat_select_types.h).
 hipError_t select_bin_rows(long long M, int C, const double* pts, const BinSpec& b, unsigned* keys, unsigned* keys_out, int* rows,
                            int* perm, double* pts_perm, void* temp, size_t& temp_bytes, hipStream_t stream);
 // selected positions of the binned table -> source rows, every expert's list ascending (the reference's source row order)

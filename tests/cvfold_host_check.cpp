@@ -1,9 +1,10 @@
 // Stand-alone driver of the host side of gpsat_fit_predict_batch_cv_refit (gpsat_amd/csrc/gpsat_cvfold.h: what
-// gpsat_cv_refit_count returns, the fold tables and the derived batch), for a build with the host sanitizers:
+// gpsat_cv_refit_count returns, the fold tables, the derived batch and its packing), for a build with the host sanitizers:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I gpsat_amd/csrc tests/cvfold_host_check.cpp
 // usage: cvfold_host_check MIN_OBS T off_0 .. off_T label_0 .. label_{sumN-1}
 // prints "fold_off ...", "expanded_rows n", "fold_n_obs ...", "fold_label ...", "derived ..." (derived tile of every fold),
-// "d_obs_off ..." and "d_pred_off ...", after checking the tables against each other.  tests/test_cv_refit_cpu.py runs it.
+// "d_obs_off ..." and "d_pred_off ...", after checking the tables against each other and the packed blocks (cvfold_pack) against
+// the tables.  tests/test_cv_refit_cpu.py runs it.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -63,6 +64,29 @@ int main(int argc, char** argv) {
         CHECK(dv.d_obs_off[j + 1] - dv.d_obs_off[j] + dv.d_pred_off[j + 1] - dv.d_pred_off[j] == dv.d_src_n[j]);
         CHECK(dv.d_src_off[j] == off[tb.fold_tile[f]]);
     }
+    // the packed blocks hold every table, whole and in its own place, at the offset they report; F2 words follow each
+    const gpsat::CvFoldPacked pk = gpsat::cvfold_pack(tb, dv);
+    const size_t F2 = dv.d_fold.size();
+    size_t words64 = 0, words32 = 0;
+    auto holds = [](const auto& block, size_t off, const auto& v, size_t& words) {
+        words += v.size();
+        if (off + v.size() > block.size()) return false;
+        for (size_t i = 0; i < v.size(); ++i) if ((long long)block[off + i] != (long long)v[i]) return false;
+        return true;
+    };
+    CHECK(holds(pk.t64, pk.o_obs_off, dv.d_obs_off, words64) && holds(pk.t64, pk.o_pred_off, dv.d_pred_off, words64));
+    CHECK(holds(pk.t64, pk.o_src_off, dv.d_src_off, words64));
+    CHECK(pk.o_obs_off == 0 && pk.o_pred_off == F2 + 1 && pk.o_src_off == 2 * (F2 + 1));      // in this order, nothing between
+    CHECK(words64 == pk.t64.size() && pk.o_delta == pk.t64.size() && pk.n64 == pk.o_delta + F2);
+    CHECK(holds(pk.t32, pk.o_src_n, dv.d_src_n, words32) && holds(pk.t32, pk.o_fold, dv.d_fold, words32));
+    CHECK(holds(pk.t32, pk.o_fold_ptr, tb.fold_ptr, words32) && holds(pk.t32, pk.o_fold_rows, tb.fold_rows, words32));
+    CHECK(holds(pk.t32, pk.o_fold_derived, dv.fold_derived, words32));
+    CHECK(holds(pk.t32, pk.o_row_fold, tb.row_fold, words32) && holds(pk.t32, pk.o_row_pos, tb.row_pos, words32));
+    CHECK(words32 == pk.t32.size() && pk.o_status == pk.t32.size() && pk.n32 == pk.o_status + F2);
+    const size_t starts[] = {pk.o_src_n, pk.o_fold, pk.o_fold_ptr, pk.o_fold_rows, pk.o_fold_derived, pk.o_row_fold, pk.o_row_pos, pk.o_status};
+    const size_t sizes[] = {F2, F2, F + 1, tb.fold_rows.size(), F, (size_t)sumN, (size_t)sumN};
+    CHECK(starts[0] == 0);
+    for (int i = 0; i < 7; ++i) CHECK(starts[i + 1] == starts[i] + sizes[i]);      // no table overlaps the next
     show("fold_off", tb.fold_off);
     std::printf("expanded_rows %lld\n", (long long)tb.expanded_rows);
     show("fold_n_obs", tb.fold_n_obs);
