@@ -114,6 +114,7 @@ struct gpsat_handle : HandleQueue {
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
+    DevBuf memo;                      // 64 bytes of developer statistics, then the evaluation memo [T][MEMO_WORDS] (fp32 L-BFGS batches)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     // gpsat_select_batch_ex.  gpsat_smooth_batch and gpsat_glue_batch stage their inputs in sel.pts (glue: its segments in
     // sel.cnt) instead of buffers of their own: the post-processing follows the selection, whose tables are no longer needed
@@ -505,6 +506,24 @@ int setup_multistart(gpsat_handle* h, const gpsat_batch* b, int S, const double*
     return GPSAT_OK;
 }
 
+// ---- the memo of evaluations (gpsat_plan.h eval_cache_bytes): the tiles clear their own headers, nothing to preset
+int setup_eval_cache(gpsat_handle* h, const gpsat_batch* b, bool ms_on, gpsat::KernelArgs& a) {
+    a.memo = nullptr; a.memo_stats = nullptr;
+    const char* knob = dev_env("GPSAT_DEBUG_EVAL_CACHE");
+    const bool f64 = b->dtype == GPSAT_F64;
+    const size_t bytes = gpsat::eval_cache_bytes(b->T, f64, b->optimiser, b->max_iter, ms_on, knob && std::atoi(knob) == 0);
+    const bool stats = !f64 && dev_env("GPSAT_DEBUG_EVAL_CACHE_STATS");
+    if (bytes == 0 && !stats) return GPSAT_OK;
+    int rc;
+    if ((rc = h->memo.reserve(64 + bytes))) return rc;
+    if (stats) {
+        HIP_TRY(hipMemsetAsync(h->memo.p, 0, 64, h->stream));
+        a.memo_stats = static_cast<unsigned*>(h->memo.p);
+    }
+    if (bytes) a.memo = static_cast<unsigned*>(h->memo.p) + 16;
+    return GPSAT_OK;
+}
+
 // ---- deferred predictions: the snapshot pool the plan asked for (gpsat_ring.h), or none when there is no memory for it
 int setup_deferred(gpsat_handle* h, const gpsat::TilePlan& p, gpsat::KernelArgs& a) {
     a.pq = nullptr; a.pq_ctl = nullptr; a.cu_busy = nullptr; a.pq_snap = nullptr; a.pq_stride = 0; a.pq_slots = 0;
@@ -532,6 +551,7 @@ int setup_deferred(gpsat_handle* h, const gpsat::TilePlan& p, gpsat::KernelArgs&
 struct LaunchReport {
     std::vector<int> team, coop;      // TeamCtl / CoopCtl blocks
     int pq_taken = -1, unfinished = 0;
+    unsigned memo[9] = {0};               // KernelArgs::memo_stats
     bool team_gave_up = false;
 };
 
@@ -547,6 +567,7 @@ int queue_report(gpsat_handle* h, const gpsat::TilePlan& p, const gpsat::KernelA
     }
     if (a.pq_ctl && dev_env("GPSAT_DEBUG_DEFER_STATS"))
         HIP_TRY(hipMemcpyAsync(&r.pq_taken, a.pq_ctl, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (a.memo_stats) HIP_TRY(hipMemcpyAsync(r.memo, a.memo_stats, sizeof(r.memo), hipMemcpyDeviceToHost, h->stream));
     if (p.seg_cost > 0) HIP_TRY(hipMemcpyAsync(&r.unfinished, a.ring_ctl + 32, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return GPSAT_OK;
 }
@@ -564,6 +585,11 @@ void read_report(const gpsat::TilePlan& p, const gpsat::KernelArgs& a, LaunchRep
     if (dev_env("GPSAT_DEBUG_DEFER_STATS"))       // developer / tests: how many predictions were deferred
         std::fprintf(stderr, "gpsat defer: T %d: deferred predictions %d of %d snapshot slots\n", T,
                      r.pq_taken < 0 ? 0 : std::min(r.pq_taken, a.pq_slots), a.pq_slots);
+    if (a.memo_stats)                             // developer / tests: what the memo of evaluations answered
+        std::fprintf(stderr, "gpsat eval cache: T %d: memo %s, evaluations %u, answered from the memo %u, of those the previous key again %u, "
+                             "tiles with such an evaluation %u, tiles that finished on one %u; tiles with 30 evaluations or more %u, answered "
+                             "from the memo in those %u; most evaluations of a tile %u, most computed evaluations of a tile %u\n",
+                     T, a.memo ? "on" : "off", r.memo[0], r.memo[1], r.memo[2], r.memo[3], r.memo[4], r.memo[6], r.memo[5], r.memo[7], r.memo[8]);
     if (!r.team.empty() && dev_env("GPSAT_DEBUG_TEAM_STATS"))
         std::fprintf(stderr, "gpsat team 0 (size %d), factorisation, owner thread 0, s_memtime ticks: own work of (A) %d, (A) wait + barrier %d, (B) + barrier %d, "
                              "(C) + barrier %d\n", p.team, r.team[24], r.team[25], r.team[26], r.team[27]);
@@ -611,6 +637,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if ((rc = setup_coop_and_team(h, p, &b->T, a))) return rc;
     if (j.ms_on && (rc = setup_multistart(h, b, j.ms->n_starts, j.theta0, j.starts_clipped, a))) return rc;
     if ((rc = setup_deferred(h, p, a))) return rc;
+    if ((rc = setup_eval_cache(h, b, j.ms_on, a))) return rc;
     gpsat::CvArgs ca;
     if (j.cv) {
         if (!gpsat::builds[p.build].launch_cv) return fail(GPSAT_EINVAL, "held-out predictions: no kernel in this build");

@@ -18,6 +18,14 @@ namespace gpsat {
 // All pointers are DEVICE pointers.
 // per-tile words of multi-start state (gpsat_opt.h ms_end_start)
 constexpr int MS_WORDS = 16;
+// Per-tile memo of recent evaluations (fp32 tile kernels, KernelArgs::memo), 32-bit words.  Header: [0] entries stored so far,
+// [1] entry (+ 1) whose factor, z and scaled coordinates are in the running workgroup's workspace and LDS (0: none), [2] entry
+// (+ 1) of the previous evaluation (0: none), [3] evaluations answered from the memo, [4] those that repeated the previous
+// evaluation's key, [5] the last line-search evaluation was answered from the memo.  Then MEMO_K entries, replaced round-robin:
+// the key (6 floats: scaled inverse length scales, sf2, sn2, as the evaluation forms them), nll (fp64) and the 6 summed
+// gradient values in front of the chain to theta (fp64).
+constexpr int MEMO_K = 4, MEMO_HDR = 8, MEMO_ENTRY = 6 + 2 + 12;
+constexpr int MEMO_WORDS = MEMO_HDR + MEMO_K * MEMO_ENTRY;
 
 struct KernelArgs {
     int T, kernel, optimiser, max_iter, max_ls, NBmax;
@@ -85,6 +93,13 @@ struct KernelArgs {
     const double* ms_starts = nullptr;   // [T][ms_S - 1][H]
     double* ms_state = nullptr;   // [T][MS_WORDS]
     double* ms_fout = nullptr;    // [T][ms_S] or nullptr
+    // evaluation memo of the fp32 tile kernels (nullptr: every evaluation is computed): a line-search evaluation whose D + 2
+    // parameter floats equal those of one of the tile's last MEMO_K distinct evaluations is answered from it (gpsat_kernels.hip)
+    unsigned* memo = nullptr;         // [T][MEMO_WORDS]; a tile's header is cleared where the tile starts
+    unsigned* memo_stats = nullptr;   // developer, zeroed: [0] evaluations, [1] answered from the memo, [2] of those: the previous key
+                                      // again, [3] tiles with such an evaluation, [4] tiles whose last line-search evaluation was one,
+                                      // [5] as [1] and [6] tiles, of the tiles with >= 30 evaluations, [7] most evaluations of a tile,
+                                      // [8] most computed evaluations of a tile
 };
 
 // Held-out predictions of the fp64 tile kernels (gpsat_fit_predict_batch_cv); device pointers.  Folds are numbered through the

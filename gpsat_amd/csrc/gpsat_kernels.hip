@@ -1521,6 +1521,27 @@ __device__ __forceinline__ void grad_loop(const Ctx<D, KN>& c) {
     }
 }
 
+// thread 0: the gradient sum of parameter i over the eight virtual waves, in their order (left in sh->red by phase_grad until
+// the next evaluation's finish_nll, which writes column 7 only)
+static __device__ __forceinline__ double grad_sum(const Shared* sh, int i) {
+    double s = 0.0;
+    for (int ww = 0; ww < 8; ++ww) s += sh->red[ww][i];
+    return s;
+}
+
+// ... and its chain to dNLL/dtheta_i at the fp64 theta_i.  The one place it is written: a computed evaluation and one answered
+// from the memo (memo_lookup) run these statements.
+template <int D, int KN>
+static __device__ __forceinline__ double grad_chain(int i, double s, float sf2, double theta_i) {
+    // scaled diff^2 already carries 1/l^2 (dk/dl = g diff^2 / l^3); kf, g are without sf2
+    if (i < D) return 0.5 * (double)sf2 * (s / (double)KScale<KN>::c2) / theta_i;
+    return 0.5 * s;
+}
+
+// the float an evaluation makes of length scale theta_d: all it sees of it
+template <int KN>
+static __device__ __forceinline__ float inv_len(double theta_d) { return (float)((double)KScale<KN>::c / theta_d); }
+
 template <int D, int KN, bool COOP>
 __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     Shared* sh = shared_state();
@@ -1577,13 +1598,7 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     }
     __syncthreads();
     if (c.tid == 0) {
-        for (int i = 0; i < D + 2; ++i) {
-            double s = 0.0;
-            for (int ww = 0; ww < 8; ++ww) s += sh->red[ww][i];
-            // scaled diff^2 already carries 1/l^2 (dk/dl = g diff^2 / l^3); kf, g are without sf2
-            if (i < D) sh->gth[i] = 0.5 * (double)c.sf2 * (s / (double)KScale<KN>::c2) / sh->theta[i];
-            else sh->gth[i] = 0.5 * s;
-        }
+        for (int i = 0; i < D + 2; ++i) sh->gth[i] = grad_chain<D, KN>(i, grad_sum(sh, i), c.sf2, sh->theta[i]);
     }
     __syncthreads();
 }
@@ -1620,7 +1635,7 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad) {
     PROF_BEGIN();
     float invl[D];
 #pragma unroll
-    for (int d = 0; d < D; ++d) invl[d] = (float)((double)KScale<KN>::c / sh->theta[d]);
+    for (int d = 0; d < D; ++d) invl[d] = inv_len<KN>(sh->theta[d]);
     c.sf2 = (float)sh->theta[D];
     c.sn2 = (float)sh->theta[D + 1];
     for (int idx = c.tid; idx < c.Npad; idx += NT) {
@@ -2011,6 +2026,126 @@ __device__ void pq_predict(Ctx<D, KN>& c, const KernelArgs& A, int s, int t, flo
 }
 
 // ---------------------------------------------------------------------------------------------
+// The memo of evaluations (KernelArgs::memo; layout: MEMO_* in gpsat_kernels.h).  evaluate() reads the trial point only through
+// D + 2 floats -- inv_len of the length scales, (float) sf2, (float) sn2 -- and is deterministic, so two trial points with the
+// same floats give the same nll, the same gradient sums and the same factor, bit for bit.  A More-Thuente search that cannot
+// meet the Wolfe conditions at the fp32 noise floor bisects its bracket until the trial points differ by less than one fp32
+// ulp and then evaluates the same floats up to max_ls times (and once more after the steepest-descent restart).  Thread 0
+// keeps the tile's last MEMO_K distinct evaluations and answers such a repeat from them; the chain to theta- and u-space is
+// run at the new fp64 theta as after a computed evaluation.  The optimiser sees what it saw before: n_eval counts the repeat.
+//
+// The memo lives in device memory, per tile, so that a suspended tile finds it on whichever workgroup resumes it.  Thread 0
+// alone reads and writes it, with agent-scope word accesses (memory, not this XCD's L2), as ms_ld / ms_st and the saved state;
+// state_save's drain of every wave's stores, ahead of the barrier and the ring entry, covers thread 0's stores to it.
+// ---------------------------------------------------------------------------------------------
+static __device__ __forceinline__ unsigned memo_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+static __device__ __forceinline__ void memo_st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+static __device__ __forceinline__ double memo_ld64(const unsigned* p) {
+    const unsigned long long lo = memo_ld(p), hi = memo_ld(p + 1);
+    return __longlong_as_double((long long)(lo | (hi << 32)));
+}
+static __device__ __forceinline__ void memo_st64(unsigned* p, double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    memo_st(p, (unsigned)u);
+    memo_st(p + 1, (unsigned)(u >> 32));
+}
+
+// the bit patterns of the floats evaluate() forms from sh->theta
+template <int D, int KN>
+static __device__ __forceinline__ void memo_key(const Shared* sh, unsigned (&key)[D + 2]) {
+    for (int d = 0; d < D; ++d) key[d] = __float_as_uint(inv_len<KN>(sh->theta[d]));
+    key[D] = __float_as_uint((float)sh->theta[D]);
+    key[D + 1] = __float_as_uint((float)sh->theta[D + 1]);
+}
+
+// thread 0, where a tile starts (fresh: an empty memo) or is resumed (the factor in this workgroup's memory is not the tile's)
+static __device__ __forceinline__ void memo_begin_tile(unsigned* m, bool resumed) {
+    if (resumed) memo_st(m + 1, 0u);
+    else for (int i = 0; i < 6; ++i) memo_st(m + i, 0u);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // in memory before this thread loads the words again
+}
+
+enum { MEMO_MISS = 0, MEMO_HIT = 1, MEMO_HIT_STALE = 2 };
+
+// thread 0, in front of a line-search evaluation with gradient: MEMO_MISS, or sh->nll, sh->gth, sh->fail and sh->n_eval are what
+// evaluate() would leave.  MEMO_HIT: the factorisation in memory is the one of these floats; MEMO_HIT_STALE: of others.
+template <int D, int KN>
+static __device__ __noinline__ int memo_lookup(Shared* sh, unsigned* m) {
+    unsigned key[D + 2];
+    memo_key<D, KN>(sh, key);
+    // every stored key in one round of independent loads (a compare that stops at the first difference would wait for
+    // memory once per word)
+    unsigned stored[MEMO_K][D + 2];
+    const int n = min((int)memo_ld(m), MEMO_K);
+#pragma unroll
+    for (int e = 0; e < MEMO_K; ++e) {
+#pragma unroll
+        for (int i = 0; i < D + 2; ++i) stored[e][i] = memo_ld(m + MEMO_HDR + e * MEMO_ENTRY + i);
+    }
+    int hit = -1;
+#pragma unroll
+    for (int e = 0; e < MEMO_K; ++e) {            // the stored keys differ: one match at most
+        bool same = e < n;
+#pragma unroll
+        for (int i = 0; i < D + 2; ++i) same = same & (stored[e][i] == key[i]);
+        if (same) hit = e;
+    }
+    if (hit < 0) return MEMO_MISS;
+    const unsigned* q = m + MEMO_HDR + hit * MEMO_ENTRY;
+    sh->nll = memo_ld64(q + 6);
+    sh->fail = 0;                                 // failed evaluations are not stored
+    const float sf2 = __uint_as_float(key[D]);
+    for (int i = 0; i < D + 2; ++i) sh->gth[i] = grad_chain<D, KN>(i, memo_ld64(q + 8 + 2 * i), sf2, sh->theta[i]);
+    sh->n_eval += 1;
+    const unsigned slot = (unsigned)hit + 1u;
+    memo_st(m + 3, memo_ld(m + 3) + 1u);
+    if (memo_ld(m + 2) == slot) memo_st(m + 4, memo_ld(m + 4) + 1u);
+    memo_st(m + 2, slot);
+    memo_st(m + 5, 1u);
+    const bool current = memo_ld(m + 1) == slot;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return current ? MEMO_HIT : MEMO_HIT_STALE;
+}
+
+// thread 0, behind a computed evaluation with gradient of the optimiser (not the final one): store it.  Its factor is the one in
+// memory now; a failed evaluation is not stored and leaves no factor.  (A computed line-search evaluation missed every stored
+// key, and the memo is empty at a tile's first evaluation: the stored keys stay distinct.)
+template <int D, int KN>
+static __device__ __noinline__ void memo_insert(const Shared* sh, unsigned* m) {
+    memo_st(m + 5, 0u);
+    if (sh->fail) { memo_st(m + 1, 0u); memo_st(m + 2, 0u); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
+    unsigned key[D + 2];
+    memo_key<D, KN>(sh, key);
+    const unsigned n = memo_ld(m), e = n % (unsigned)MEMO_K;
+    unsigned* q = m + MEMO_HDR + e * MEMO_ENTRY;
+    for (int i = 0; i < D + 2; ++i) memo_st(q + i, key[i]);
+    memo_st64(q + 6, sh->nll);
+    for (int i = 0; i < D + 2; ++i) memo_st64(q + 8 + 2 * i, grad_sum(sh, i));
+    memo_st(m, n + 1u);
+    memo_st(m + 1, e + 1u);
+    memo_st(m + 2, e + 1u);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// thread 0, developer statistics of a finished tile (KernelArgs::memo_stats)
+static __device__ __forceinline__ void memo_count_tile(const KernelArgs& A, const Shared* sh, const unsigned* m) {
+    auto add = [&](int i, unsigned v) { __hip_atomic_fetch_add(&A.memo_stats[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto top = [&](int i, unsigned v) { __hip_atomic_fetch_max(&A.memo_stats[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const unsigned n = (unsigned)sh->n_eval_opt, hits = m ? memo_ld(m + 3) : 0u;
+    const bool long_tile = n >= 30u;
+    add(0, n);
+    if (long_tile) add(6, 1u);
+    top(7, n);
+    top(8, n - hits);
+    if (hits == 0) return;
+    add(1, hits);
+    add(2, memo_ld(m + 4));
+    add(3, 1u);
+    if (memo_ld(m + 5)) add(4, 1u);
+    if (long_tile) add(5, hits);
+}
+
+// ---------------------------------------------------------------------------------------------
 // the persistent kernel
 // ---------------------------------------------------------------------------------------------
 template <int D, int KN>
@@ -2206,6 +2341,8 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
         }
         if (resumed) state_load(sh, A, t, c.tid);
         else if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
+        unsigned* const memo = A.memo ? A.memo + (size_t)t * MEMO_WORDS : nullptr;
+        if (memo && c.tid == 0) memo_begin_tile(memo, resumed);
         const bool helpable = coop_on && NB >= A.coop_min_nb;
         if (c.tid == 0) {
             sh->hp[2] = -1;                        // the coordinates in LDS are this tile's, not a helped one's
@@ -2223,24 +2360,42 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
         // ================= evaluate / advance loop (one inlined evaluate call site per mode) =================
         const int seg_evals = sliced ? max(1, A.seg_cost / (NB * NB * NB)) : 0x7fffffff;
         bool suspended = false;
-        for (int nseg = 1;; ++nseg) {
-            if (helpable) {
-                // cooperative evaluation when helpers are attached (they may still leave: nothing waits for them)
-                if (c.tid == 0) sh->coop_now = ((A.coop_force & 1) || __hip_atomic_load(&ctl_own->helpers, RLX_AGENT) > 0) ? 1 : 0;
+        for (int nseg = 0;;) {
+            // a line-search evaluation whose floats the tile has evaluated before is answered from its memo: thread 0 leaves
+            // what evaluate() would, every wave skips it (and it is not counted against the time slice)
+            int known = MEMO_MISS;
+            if (memo) {
+                if (c.tid == 0) {
+                    // (a search's first two trial points are computed without a look: a repeat needs a bracket bisected down
+                    // to one fp32 ulp, and most searches end before their third evaluation)
+                    const int r = (sh->phase == PH_LS && sh->want_grad && sh->ls_iter >= 2) ? memo_lookup<D, KN>(sh, memo) : MEMO_MISS;
+                    sh->hp[4] = r;
+                    o.factor_stale = r == MEMO_HIT_STALE;
+                }
                 __syncthreads();
+                known = __builtin_amdgcn_readfirstlane(sh->hp[4]);
             }
-            if (helpable && sh->coop_now) {
-                const f32x2 sv = evaluate_coop<D, KN>(c, sh->want_grad != 0);
-                c.sf2 = sv[0]; c.sn2 = sv[1];
-            } else {
-                evaluate<D, KN, false>(c, sh->want_grad != 0);
+            if (known == MEMO_MISS) {
+                ++nseg;
+                if (helpable) {
+                    // cooperative evaluation when helpers are attached (they may still leave: nothing waits for them)
+                    if (c.tid == 0) sh->coop_now = ((A.coop_force & 1) || __hip_atomic_load(&ctl_own->helpers, RLX_AGENT) > 0) ? 1 : 0;
+                    __syncthreads();
+                }
+                if (helpable && sh->coop_now) {
+                    const f32x2 sv = evaluate_coop<D, KN>(c, sh->want_grad != 0);
+                    c.sf2 = sv[0]; c.sn2 = sv[1];
+                } else {
+                    evaluate<D, KN, false>(c, sh->want_grad != 0);
+                }
+                if (memo && c.tid == 0 && sh->phase != PH_FINAL && sh->want_grad) memo_insert<D, KN>(sh, memo);
             }
             if (c.tid == 0) opt_advance(sh, H, o);
             __syncthreads();
             if (sh->phase == PH_EXIT) break;
             // time slice used up while the optimiser goes on (the final evaluation + prediction are never split off:
             // prediction needs this workgroup's factorisation)
-            if (nseg >= seg_evals && sh->phase != PH_FINAL) {
+            if (known == MEMO_MISS && nseg >= seg_evals && sh->phase != PH_FINAL) {
                 // ... unless no other tile is waiting in the ring: the slice would only hand this tile to a workgroup that
                 // waits for work (state through device memory for nothing) and shake off the tile's helpers
                 if (c.tid == 0) sh->hp[6] = ring_waiting_tiles(A);
@@ -2282,12 +2437,13 @@ __global__ void __launch_bounds__(NT, GPSAT_MIN_WG) gp_tile_kernel(const KernelA
 #endif
         // ================= outputs + prediction from the factorisation at the accepted parameters
         if (c.tid == 0) tile_out_finished(A, sh, H, t);
+        if (A.memo_stats && c.tid == 0) memo_count_tile(A, sh, memo);
         bool deferred = false;
         if (c.P > 0) {
             if (!sh->fail) {
                 float invl[D];
 #pragma unroll
-                for (int d = 0; d < D; ++d) invl[d] = (float)((double)KScale<KN>::c / sh->theta[d]);
+                for (int d = 0; d < D; ++d) invl[d] = inv_len<KN>(sh->theta[d]);
                 if (defer_on && !A.f_cov) {
                     // other tiles wait for a workgroup: leave the prediction to the end of the launch, where workgroups idle
                     if (c.tid == 0) sh->hp[6] = ring_waiting_tiles(A) > 0 ? pq_take_slot(A) : -1;

@@ -254,6 +254,9 @@ struct OptCfg {
     const double* ms_starts = nullptr;   // [T][ms_S - 1][H] further starts, constrained space, inside the bounds
     double* ms_state = nullptr;          // [T][MS_WORDS] (see ms_end_start), preset by the host
     double* ms_fout = nullptr;           // [T][ms_S] final objective of every start, or nullptr
+    // The last evaluation was answered from the tile's memo of evaluations (fp32 tile kernels), and the factorisation in this
+    // workgroup's memory belongs to other parameter floats: thread 0 sets it before opt_advance; ms_S = 0 only.
+    int factor_stale = 0;
 };
 
 // per-tile multi-start state, MS_WORDS (gpsat_kernels.h) doubles: [0] index of the running start, [1] best f, [2] its
@@ -518,7 +521,7 @@ static __device__ __noinline__ void ms_end_start(Shared* sh, int H, const OptCfg
 static __device__ __noinline__ void opt_finish(Shared* sh, int H, const OptCfg& o, bool factor_is_current) {
     if (o.ms_S > 0) { ms_end_start(sh, H, o, factor_is_current); return; }
     sh->n_eval_opt = sh->n_eval;
-    if (factor_is_current && !sh->fail) { sh->phase = PH_EXIT; return; }
+    if (factor_is_current && !sh->fail && !o.factor_stale) { sh->phase = PH_EXIT; return; }
     set_trial(sh, H, sh->u);
     sh->want_grad = o.want_grad_out;
     sh->phase = PH_FINAL;

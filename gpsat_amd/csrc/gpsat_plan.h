@@ -154,5 +154,14 @@ bool plan_tiles(const PlanInput& in, TilePlan& p) {
     return true;
 }
 
+// The memo of evaluations of the fp32 tile kernels (KernelArgs::memo, gpsat_kernels.hip): bytes of device memory a batch of T
+// tiles needs for it, 0 when the batch runs without one.  It serves the unbounded L-BFGS driver's line search only: no fp64
+// batch (the key would be the fp64 theta), no Adam, no multi-start, nothing without an optimisation; `off`: the developer
+// switched it off (GPSAT_DEBUG_EVAL_CACHE=0).  Kept apart from TilePlan, whose layout tests/test_abi.py mirrors.
+size_t eval_cache_bytes(int T, int f64, int optimiser, int max_iter, int multistart, int off) {
+    if (T <= 0 || f64 || optimiser != GPSAT_OPT_LBFGS || max_iter <= 0 || multistart || off) return 0;
+    return (size_t)T * MEMO_WORDS * sizeof(unsigned);
+}
+
 }  // namespace gpsat
 #endif
