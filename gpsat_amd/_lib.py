@@ -15,7 +15,9 @@ LIB_PATH = os.environ.get("GPSAT_LIB") or os.path.join(_HERE, "csrc", "libgpsat_
 # constants mirrored from include/gpsat_hip.h
 ABI_VERSION = 4
 F32, F64 = 0, 1
-KERNEL_IDS = {"RBF": 0, "SquaredExponential": 0, "Matern12": 1, "Exponential": 1, "Matern32": 2, "Matern52": 3}
+KERNEL_IDS = {"RBF": 0, "SquaredExponential": 0, "Matern12": 1, "Exponential": 1, "Matern32": 2, "Matern52": 3,
+              "RationalQuadratic": 4}
+KERNEL_RQ = 4      # GPSAT_KERNEL_RQ: one more hyper-parameter (alpha, last), fp64 and D <= 3 only
 OPT_NONE, OPT_LBFGS, OPT_ADAM = 0, 1, 2
 OPT_IDS = {"none": OPT_NONE, None: OPT_NONE, "lbfgs": OPT_LBFGS, "L-BFGS-B": OPT_LBFGS, "adam": OPT_ADAM}
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -25,10 +27,11 @@ EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_cre
            "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
            "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
-           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit"]
+           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit",
+           "gpsat_n_hyper"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
 OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold",
-                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit"]
+                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit", "gpsat_n_hyper"]
 
 
 class GpsatOpts(C.Structure):
@@ -186,6 +189,9 @@ def load():
         lib.gpsat_cv_refit_count.restype = C.c_int
         lib.gpsat_fit_predict_batch_cv_refit.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatCvRefit)]
         lib.gpsat_fit_predict_batch_cv_refit.restype = C.c_int
+    if hasattr(lib, "gpsat_n_hyper"):
+        lib.gpsat_n_hyper.argtypes = [C.c_int, C.c_int]
+        lib.gpsat_n_hyper.restype = C.c_int
     if hasattr(lib, "gpsat_bin_batch"):
         lib.gpsat_bin_batch.restype = C.c_int
         lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -196,6 +202,14 @@ def load():
     if lib.gpsat_version() != ABI_VERSION:
         raise LibraryMissing(f"ABI version mismatch: library {lib.gpsat_version()} != binding {ABI_VERSION}")
     return lib
+
+
+def n_hyper(kernel, D: int) -> int:
+    """Hyper-parameters per tile (gpsat_n_hyper): D + 3 for "RationalQuadratic" (lengthscales, kernel variance, likelihood
+    variance, alpha), D + 2 for the other kernels.  Host arithmetic, the same rule as the library's: shapes can be laid out
+    without loading it."""
+    kid = KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+    return int(D) + (3 if kid == KERNEL_RQ else 2)
 
 
 def max_tile_obs(dtype: str, D: int) -> int:

@@ -161,6 +161,10 @@ int run_with_temp(gpsat_handle* h, DevBuf& tmp, const char* what, hipEvent_t mar
     return e != hipSuccess ? failed(e) : GPSAT_OK;
 }
 
+// Hyper-parameters per tile: D + 2, or D + 3 with the RationalQuadratic kernel's alpha behind them (gpsat_n_hyper).  Read
+// behind check_batch only, which refuses the arguments it answers with 0.
+int n_hyper(const gpsat_batch* b) { return gpsat_n_hyper(b->kernel, b->D); }
+
 struct BatchDims { long long sumN = 0, sumP = 0, sumC = 0, sumM = 0, maxN = 0, maxP = 0; bool want_cov = false; };
 
 // The argument checks the dense and the sparse entry point share, in the order of the dense one, up to the CSR offsets
@@ -170,7 +174,7 @@ int check_batch(const gpsat_batch* b, bool f64_only, BatchDims& d) {
     if (b->D < 1 || b->D > 4) return fail(GPSAT_EINVAL, "D must be 1..4 in this build");
     if (f64_only && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "sparse GP experts are built for GPSAT_F64 only");
     if (b->dtype != GPSAT_F32 && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "unknown dtype");
-    if (b->kernel < 0 || b->kernel > 3) return fail(GPSAT_EINVAL, "unknown kernel id");
+    if (b->kernel < 0 || b->kernel > GPSAT_KERNEL_RQ) return fail(GPSAT_EINVAL, "unknown kernel id");
     if (b->optimiser < 0 || b->optimiser > 2) return fail(GPSAT_EINVAL, "unknown optimiser id");
     if (b->memory != GPSAT_MEM_HOST && b->memory != GPSAT_MEM_DEVICE) return fail(GPSAT_EINVAL, "bad memory flag");
     if (!b->obs_off || !b->pred_off || !b->theta0 || !b->lo || !b->hi || !b->trainable)
@@ -187,11 +191,22 @@ int check_batch(const gpsat_batch* b, bool f64_only, BatchDims& d) {
     return GPSAT_OK;
 }
 
+// GPSAT_KERNEL_RQ is built into gpsat_fit_predict_batch alone, in fp64 and for D <= 3 (H = D + 3 <= 6, the optimiser state's
+// HMAX).  `entry`: nullptr for that call, else the name of the entry point that refuses the kernel.
+int check_rq(const gpsat_batch* b, const char* entry) {
+    if (b->kernel != GPSAT_KERNEL_RQ) return GPSAT_OK;
+    const std::string who = "RationalQuadratic (GPSAT_KERNEL_RQ) ";
+    if (entry) return fail(GPSAT_EINVAL, who + "is built for gpsat_fit_predict_batch only, not for " + entry);
+    if (b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, who + "is built for GPSAT_F64 only");
+    if (b->D > 3) return fail(GPSAT_EINVAL, who + "is built for D <= 3: H = D + 3 parameters, at most 6");
+    return GPSAT_OK;
+}
+
 // ... and the checks that follow the offsets in both: data pointers against the sums, theta0
 int check_batch_data(const gpsat_batch* b, const BatchDims& d) {
     if (d.sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
     if (d.sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
-    for (size_t e = 0; e < (size_t)b->T * (b->D + 2); ++e)
+    for (size_t e = 0; e < (size_t)b->T * n_hyper(b); ++e)
         if (!(b->theta0[e] > 0.0) || !std::isfinite(b->theta0[e])) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
     return GPSAT_OK;
 }
@@ -199,7 +214,7 @@ int check_batch_data(const gpsat_batch* b, const BatchDims& d) {
 // x clipped into the bounds of the trainable parameters, n rows of H per tile (SciPy clips x0 into the bounds,
 // _minimize_lbfgsb; the further starts likewise: L-BFGS-B works inside the box only)
 std::vector<double> clip_to_bounds(const gpsat_batch* b, const double* x, int n) {
-    const int T = b->T, H = b->D + 2;
+    const int T = b->T, H = n_hyper(b);
     std::vector<double> out(x, x + (size_t)T * n * H);
     for (int t = 0; t < T; ++t)
         for (int k = 0; k < n; ++k)
@@ -215,7 +230,7 @@ std::vector<double> clip_to_bounds(const gpsat_batch* b, const double* x, int n)
 // when the optimiser runs at all (`ms_on`)
 int check_multistart(const gpsat_batch* b, const gpsat_multistart* ms, bool ms_on, std::vector<double>& theta0_clipped,
                      std::vector<double>& starts_clipped) {
-    const int T = b->T, H = b->D + 2, S = ms->n_starts;
+    const int T = b->T, H = n_hyper(b), S = ms->n_starts;
     if (S < 1) return fail(GPSAT_EINVAL, "multistart: n_starts must be >= 1");
     if (ms->transform != GPSAT_TRANSFORM_LOG) return fail(GPSAT_EINVAL, "multistart: unknown transform (GPSAT_TRANSFORM_LOG only)");
     if (S > 1 && !ms->starts) return fail(GPSAT_EINVAL, "multistart: starts is NULL with n_starts > 1");
@@ -339,7 +354,7 @@ struct Staged {
 // `order` is pageable host memory of the caller and must outlive the launch.
 int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const double* theta0, const std::vector<int>& order,
                 const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s) {
-    const int T = b->T, D = b->D, H = D + 2;
+    const int T = b->T, D = b->D, H = n_hyper(b);
     const size_t esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
     const size_t sumN = (size_t)d.sumN, sumP = (size_t)d.sumP, sumM = (size_t)d.sumM;
     int rc;
@@ -393,7 +408,7 @@ int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const
 // The fields KernelArgs and SgprArgs have in common: sizes, optimiser settings with their defaults, staged pointers.
 template <class Args>
 void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s) {
-    const int T = b->T, H = b->D + 2;
+    const int T = b->T, H = n_hyper(b);
     const bool f64 = b->dtype == GPSAT_F64;
     a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
     a.max_ls = b->max_ls > 0 ? b->max_ls : 20;                                 // SciPy L-BFGS-B maxls
@@ -418,7 +433,7 @@ void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s) {
 
 // Device-to-host copies of the results (host mode: the predictions and the covariance too).
 int fetch_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const Staged& s) {
-    const size_t T = (size_t)b->T, H = (size_t)b->D + 2, esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
+    const size_t T = (size_t)b->T, H = (size_t)n_hyper(b), esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
     HIP_TRY(hipMemcpyAsync(b->theta, s.out_f64, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(b->nll, s.out_f64 + T * H, T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, s.out_f64 + T * H + T, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -484,7 +499,7 @@ int setup_coop_and_team(gpsat_handle* h, const gpsat::TilePlan& p, const int* T_
 // ---- multi-start: per-tile state (log theta0, best so far), the clipped further starts, the objectives of every start
 int setup_multistart(gpsat_handle* h, const gpsat_batch* b, int S, const double* theta0, const std::vector<double>& starts,
                      gpsat::KernelArgs& a) {
-    const int T = b->T, H = b->D + 2;
+    const int T = b->T, H = n_hyper(b);
     const size_t n_state = (size_t)T * gpsat::MS_WORDS, n_starts = (size_t)T * (S - 1) * H, n_f = (size_t)T * S;
     int rc;
     if ((rc = h->ms.reserve((n_state + n_starts + n_f) * sizeof(double)))) return rc;
@@ -614,9 +629,9 @@ struct DenseJob {
 int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, LaunchReport& r) {
     const gpsat_batch* b = j.b;
     const BatchDims& d = j.dims;
-    const bool f64 = b->dtype == GPSAT_F64;
+    const bool f64 = b->dtype == GPSAT_F64, rq = b->kernel == GPSAT_KERNEL_RQ;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
-                           h->num_cu, h->wg_per_cu, solo || j.cv, unsliced, read_dev_knobs()};     // held-out: one workgroup per tile
+                           h->num_cu, h->wg_per_cu, solo || j.cv || rq, unsliced, read_dev_knobs()};     // held-out, RQ: one workgroup per tile
     gpsat::TilePlan p;
     if (!gpsat::plan_tiles(in, p)) return fail(GPSAT_EINVAL, "tile too large for LDS");
     Staged s;
@@ -657,6 +672,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     if (j.cv) HIP_TRY(gpsat::builds[p.build].launch_cv(b->D, a, ca, p.grid, p.smem, h->stream));
+    else if (rq) HIP_TRY((p.build == gpsat::BUILD_F64_W4 ? gpsat::launch_tiles_rq_f64_w4 : gpsat::launch_tiles_rq_f64)(b->D, a, p.grid, p.smem, h->stream));
     else HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s))) return rc;
@@ -680,6 +696,7 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
     j.b = b; j.ms = ms; j.cv = cv;
     int rc;
     if ((rc = check_batch(b, false, j.dims))) return rc;
+    if ((rc = check_rq(b, ms ? "gpsat_fit_predict_batch_ms" : cv ? "gpsat_fit_predict_batch_cv" : nullptr))) return rc;
     BatchDims& d = j.dims;
     d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
     if (d.want_cov) {
@@ -806,7 +823,7 @@ struct DerivedBatch {
 
 void cvr_derived_batch(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldTables& tb, const gpsat::CvFoldDerived& dv,
                        const gpsat::CvFoldArgs& a, DerivedBatch& db) {
-    const int H = b->D + 2;
+    const int H = n_hyper(b);
     const size_t F2 = dv.d_fold.size();
     db.th0.resize(F2 * H); db.lo.resize(F2 * H); db.hi.resize(F2 * H); db.theta.resize(F2 * H); db.nll.resize(F2);
     db.status.assign(F2, GPSAT_STATUS_SKIPPED); db.n_eval.resize(F2); db.n_iter.resize(F2);
@@ -833,7 +850,7 @@ void cvr_derived_batch(const gpsat_batch* b, const gpsat_cv_refit* cv, const gps
 
 // The caller's per-fold outputs: `skipped` for every fold (before anything runs), then what the derived batch returned
 void cvr_folds_skipped(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldTables& tb) {
-    const int H = b->D + 2;
+    const int H = n_hyper(b);
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (size_t f = 0; f < (size_t)tb.fold_off[b->T]; ++f) {
         for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = nan;
@@ -846,7 +863,7 @@ void cvr_folds_skipped(const gpsat_batch* b, const gpsat_cv_refit* cv, const gps
 
 void cvr_unpack(const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat::CvFoldDerived& dv, const DerivedBatch& db,
                 const std::vector<double>& delta) {
-    const int H = b->D + 2;
+    const int H = n_hyper(b);
     for (size_t j = 0; j < dv.d_fold.size(); ++j) {
         const size_t f = (size_t)dv.d_fold[j];
         for (int i = 0; i < H; ++i) cv->fold_theta[f * H + i] = db.theta[j * H + i];
@@ -885,6 +902,7 @@ int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_r
     BatchDims d;
     int rc;
     if ((rc = check_batch(b, false, d))) return rc;
+    if ((rc = check_rq(b, "gpsat_fit_predict_batch_cv_refit"))) return rc;
     gpsat::CvFoldTables tb;
     if ((rc = check_cv_refit(b, cv, tb))) return rc;
     if ((rc = fit_predict(h, b, nullptr))) return rc;
@@ -1007,6 +1025,12 @@ int gpsat_max_tile_obs(int dtype, int D) {
     return 0;
 }
 
+int gpsat_n_hyper(int kernel, int D) {
+    if (D < 1 || D > 4 || kernel < 0 || kernel > GPSAT_KERNEL_RQ) return 0;
+    if (kernel == GPSAT_KERNEL_RQ) return D <= 3 ? D + 3 : 0;
+    return D + 2;
+}
+
 int gpsat_create(int device_id, const gpsat_opts* opts, gpsat_handle** out) {
     if (!out) return fail(GPSAT_EINVAL, "gpsat_create: out is NULL");
     *out = nullptr;
@@ -1106,6 +1130,7 @@ int gpsat_sgpr_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b, const gp
     BatchDims d;
     int rc;
     if ((rc = check_batch(b, true, d))) return rc;
+    if ((rc = check_rq(b, "gpsat_sgpr_fit_predict_batch"))) return rc;
     if (b->cov_off || b->f_cov) return fail(GPSAT_EINVAL, "sparse GP experts do not return the full covariance: cov_off / f_cov must be NULL");
     if (!(sp->jitter >= 0.0) || !std::isfinite(sp->jitter)) return fail(GPSAT_EINVAL, "jitter must be finite and >= 0");
     const int T = b->T, D = b->D;

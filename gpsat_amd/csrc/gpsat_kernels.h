@@ -33,7 +33,7 @@ struct KernelArgs {
     double noise_rel;             // relative objective resolution of the arithmetic (line-search failure at the noise floor)
     const long long* obs_off;     // [T+1]
     const long long* pred_off;    // [T+1]
-    const double* theta0;         // [T*H]
+    const double* theta0;         // [T*H], H = gpsat_n_hyper(kernel, D)
     const double* lo;             // [T*H]
     const double* hi;             // [T*H]
     const unsigned char* trainable;  // [H]
@@ -132,6 +132,10 @@ size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
 hipError_t launch_tiles_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 hipError_t launch_tiles_cv_f64_w4(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
+// the same tile loop for the RationalQuadratic covariance function (-DGPSAT_F64_RQ: kernel 4, D = 1..3, H = D + 3), one
+// workgroup per tile; LDS, workspace and state words are those of the build of the same wave count
+hipError_t launch_tiles_rq_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+hipError_t launch_tiles_rq_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

@@ -47,6 +47,33 @@ namespace gpsat {
 #define CV_KERNEL_PARAM
 #define CV_FINAL_WANTS_M(sh_)
 #endif
+// -DGPSAT_F64_RQ compiles the one-workgroup-per-tile kernel of either build once more for the RationalQuadratic covariance
+// function (GPSAT_KERNEL_RQ), whose shape parameter alpha is one more trainable hyper-parameter: H = D + 3, theta =
+// (l_0 .. l_{D-1}, kernel variance, likelihood variance, alpha), D = 1..3.  Objects of their own that export
+// launch_tiles_rq_f64[_w4] only.  As with GPSAT_F64_CV, everything the flag adds stands behind these macros: without it the
+// translation unit is, token for token, what it was before.
+#ifdef GPSAT_F64_RQ
+#ifdef GPSAT_F64_CV
+#error "GPSAT_F64_RQ and GPSAT_F64_CV are builds of their own"
+#endif
+#undef F64NS
+#ifdef GPSAT_F64_W4
+#define F64NS f64k4rq
+#else
+#define F64NS f64krq
+#endif
+#define F64_NHYP D + 3                                    /* hyper-parameters of a tile, in expressions of the templates */
+#define RQ_ARG(x_) , x_
+#define KFUN_C(c_, r2_, kf_, gg_) double ga; kfun_rq((c_).rqa, (c_).rqh, r2_, kf_, gg_, ga)
+#define KFUN_T(th_, r2_, kf_, gg_) double ga; kfun_rq((th_)[D + 2], 0.5 / (th_)[D + 2], r2_, kf_, gg_, ga)
+#define TILE_PREDICT_PRIOR rq_predict_prior<D>
+#else
+#define F64_NHYP D + 2
+#define RQ_ARG(x_)
+#define KFUN_C(c_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
+#define KFUN_T(th_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
+#define TILE_PREDICT_PRIOR tile_predict_prior
+#endif
 namespace F64NS {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -160,6 +187,9 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 #include "gpsat_kfun_f64.h"
+#ifdef GPSAT_F64_RQ
+#include "gpsat_kfun_rq_f64.h"
+#endif
 
 struct Lay { int xsc, y, z, alpha, Ad, LT, tmp, Pn, tp4, PnLA, tpLA, end; };   // double offsets into lds_d; end: behind the last region
 
@@ -236,6 +266,9 @@ struct Ctx {
     int pn0;                     // block index of the exchanged diagonal region
     gdouble *tpg, *zg, *ag;
     int gp0;                     // byte offset of the gradient phase's per-item partial sums (aliases the prediction scratch)
+#ifdef GPSAT_F64_RQ
+    double rqa, rqh;             // alpha of the running evaluation, and 1 / (2 alpha)
+#endif
 };
 
 // who this thread is, and the launch's LDS layout
@@ -275,7 +308,7 @@ __device__ __forceinline__ void prior_cov_empty(const double* theta0, const doub
             r2 = fma(df, df, r2);
         }
         double kf, gg;
-        kfun<KN>(r2, kf, gg);
+        KFUN_T(theta0, r2, kf, gg);
         cov[e] = sf2 * kf;
     }
 }
@@ -320,7 +353,7 @@ __device__ __forceinline__ f64x4 kblock(const Ctx<D, KN>& c, int bi, int bj) {
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; r2 = fma(df, df, r2); }
         double kf, gg;
-        kfun<KN>(r2, kf, gg);
+        KFUN_C(c, r2, kf, gg);
         double v = ((p < c.N) && (qc < c.N)) ? c.sf2 * kf : 0.0;
         if (p == qc) v = (p < c.N) ? (v + c.sn2) : 1.0;
         out[r] = v;
@@ -338,7 +371,7 @@ __device__ __forceinline__ f64x4 ksblock(const Ctx<D, KN>& c, int bj, const doub
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; r2 = fma(df, df, r2); }
         double kf, gg;
-        kfun<KN>(r2, kf, gg);
+        KFUN_C(c, r2, kf, gg);
         out[r] = ((p < c.N) && qvalid) ? c.sf2 * kf : 0.0;
     }
     return out;
@@ -346,7 +379,7 @@ __device__ __forceinline__ f64x4 ksblock(const Ctx<D, KN>& c, int bj, const doub
 
 template <int D, int KN>
 __device__ __forceinline__ void contract(const Ctx<D, KN>& c, const f64x4& kinv, int ba, int bb, double wgt,
-                                         double (&accl)[D], double& accsf, double& accsn) {
+                                         double (&accl)[D], double& accsf, double& accsn RQ_ARG(double& accal)) {
     const int qc = BS * bb + c.g;
     double xq[D];
 #pragma unroll
@@ -360,11 +393,14 @@ __device__ __forceinline__ void contract(const Ctx<D, KN>& c, const f64x4& kinv,
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; d2[d] = df * df; r2 += d2[d]; }
         double kf, gg;
-        kfun<KN>(r2, kf, gg);
+        KFUN_C(c, r2, kf, gg);
         double Q = kinv[r] - lds_d[c.L.alpha + p] * aq;
         Q = (qv && p < c.N) ? Q : 0.0;
         const double wq = wgt * Q;
         accsf = fma(wq, kf, accsf);
+#ifdef GPSAT_F64_RQ
+        accal = fma(wq, ga, accal);
+#endif
         const double wg = wq * gg;
 #pragma unroll
         for (int d = 0; d < D; ++d) accl[d] = fma(wg, d2[d], accl[d]);
@@ -1004,27 +1040,36 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
 #pragma unroll
             for (int d = 0; d < D; ++d) accl[d] = 0.0;
             double accsf = 0.0, accsn = 0.0;
+#ifdef GPSAT_F64_RQ
+            double accal = 0.0;
+#endif
 #pragma unroll
             for (int r = 0; r < PR; ++r) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const int a = a0 + r, b = b0 + n;
                     if (r < na && b < NB && a >= b)
-                        contract<D, KN>(c, acc[r][n], a, b, (a == b) ? 1.0 : 2.0, accl, accsf, accsn);
+                        contract<D, KN>(c, acc[r][n], a, b, (a == b) ? 1.0 : 2.0, accl, accsf, accsn RQ_ARG(accal));
                 }
             }
-            double* gp = gpart + (size_t)item * (D + 2) * 64 + lane;
+            double* gp = gpart + (size_t)item * (F64_NHYP) * 64 + lane;
             if (TEAM) {
                 gdouble* gg = (gdouble*)gp;
 #pragma unroll
                 for (int d = 0; d < D; ++d) gst_d(gg + d * 64, accl[d]);
                 gst_d(gg + D * 64, accsf);
                 gst_d(gg + (D + 1) * 64, accsn);
+#ifdef GPSAT_F64_RQ
+                gst_d(gg + (D + 2) * 64, accal);
+#endif
             } else {
 #pragma unroll
                 for (int d = 0; d < D; ++d) gp[d * 64] = accl[d];
                 gp[D * 64] = accsf;
                 gp[(D + 1) * 64] = accsn;
+#ifdef GPSAT_F64_RQ
+                gp[(D + 2) * 64] = accal;
+#endif
             }
             PROF_END(c, 13);
         }
@@ -1035,29 +1080,32 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     PROF_END(c, 11);
     if (c.member != 0) return;
     // fixed-order sum: wave w adds the items w, w + NW, ... per lane, then across lanes, then across waves
-    double v[D + 2];
+    double v[F64_NHYP];
 #pragma unroll
-    for (int i = 0; i < D + 2; ++i) v[i] = 0.0;
+    for (int i = 0; i < F64_NHYP; ++i) v[i] = 0.0;
     for (int it = c.w; it < nitems; it += NW) {
-        const double* gp = gpart + (size_t)it * (D + 2) * 64 + lane;
+        const double* gp = gpart + (size_t)it * (F64_NHYP) * 64 + lane;
 #pragma unroll
-        for (int i = 0; i < D + 2; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
+        for (int i = 0; i < F64_NHYP; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
     }
 #pragma unroll
-    for (int i = 0; i < D + 2; ++i) {
+    for (int i = 0; i < F64_NHYP; ++i) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
     }
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < D + 2; ++i) sh->red[c.w][i] = v[i];
+        for (int i = 0; i < F64_NHYP; ++i) sh->red[c.w][i] = v[i];
     }
     __syncthreads();
     if (c.tid == 0) {
-        for (int i = 0; i < D + 2; ++i) {
+        for (int i = 0; i < F64_NHYP; ++i) {
             double s = 0.0;
             for (int ww = 0; ww < NW; ++ww) s += sh->red[ww][i];
             if (i < D) sh->gth[i] = 0.5 * c.sf2 * s / sh->theta[i];
+#ifdef GPSAT_F64_RQ
+            else if (i == D + 2) sh->gth[i] = 0.5 * c.sf2 * s;      // dNLL/dalpha = 1/2 sum Q_ab dK_ab/dalpha
+#endif
             else sh->gth[i] = 0.5 * s;
         }
     }
@@ -1071,6 +1119,10 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
     PROF_BEGIN();
     c.sf2 = sh->theta[D];
     c.sn2 = sh->theta[D + 1];
+#ifdef GPSAT_F64_RQ
+    c.rqa = sh->theta[D + 2];
+    c.rqh = 0.5 / c.rqa;
+#endif
     for (int idx = c.tid; idx < c.Npad; idx += NT) {
 #pragma unroll
         for (int d = 0; d < D; ++d) lds_d[c.L.xsc + d * c.Npad + idx] = (idx < c.N) ? Xg[(size_t)idx * D + d] / sh->theta[d] : 0.0;
@@ -1078,7 +1130,7 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
     __syncthreads();
     phase_potrf<D, KN, TEAM>(c, want_grad CV_FINAL_WANTS_M(sh));
     if (sh->fail) {
-        if (c.tid == 0) { sh->nll = __builtin_inf(); for (int i = 0; i < D + 2; ++i) sh->gth[i] = 0.0; }
+        if (c.tid == 0) { sh->nll = __builtin_inf(); for (int i = 0; i < F64_NHYP; ++i) sh->gth[i] = 0.0; }
         __syncthreads();
         return;
     }
@@ -1227,7 +1279,7 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
                             r2 = fma(df, df, r2);
                         }
                         double kf, gg;
-                        kfun<KN>(r2, kf, gg);
+                        KFUN_C(c, r2, kf, gg);
                         const double v = c.sf2 * kf - Cb[r];
                         fcov[(size_t)pi * c.P + qj] = v;
                         if (p != q) fcov[(size_t)qj * c.P + pi] = v;
@@ -1378,9 +1430,32 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
 
 #endif
 
+#ifdef GPSAT_F64_RQ
+// thread 0, behind opt_fresh_tile: that gives the LAST parameter GPflow's lower bound of the likelihood variance (a shift of
+// the softplus); here the last parameter is alpha (softplus without a shift, GPflow's positive()) and the likelihood
+// variance stands in front of it
+template <int D>
+__device__ __forceinline__ void rq_fresh_tile(Shared* sh) {
+    constexpr int iv = D + 1, ia = D + 2;
+    sh->shift[ia] = 0.0;
+    sh->shift[iv] = sh->box[iv] ? 0.0 : 1e-6;
+    sh->u[ia] = u_of_theta(sh, ia, sh->theta[ia]);
+    sh->u[iv] = u_of_theta(sh, iv, sh->theta[iv]);
+}
+
+// all threads: the prior at theta0 as the predictions of a tile without observations (tile_predict_prior reads the two
+// variances at the end of theta0)
+template <int D>
+__device__ __forceinline__ void rq_predict_prior(const KernelArgs& A, int H, int t, int tid, long long p0, long long p1,
+                                                 double* f_mean, double* f_var, double* y_var) {
+    const double sf2 = A.theta0[(size_t)t * H + D], sn2 = A.theta0[(size_t)t * H + D + 1];
+    for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = 0.0; f_var[q] = sf2; y_var[q] = sf2 + sn2; }
+}
+#endif
+
 template <int D, int KN>
 __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const KernelArgs A CV_KERNEL_PARAM) {
-    constexpr int H = D + 2;
+    constexpr int H = F64_NHYP;
     Ctx<D, KN> c;
     ctx_init(c, A.NBmax);
     Shared* sh = reinterpret_cast<Shared*>(lds_d);
@@ -1426,7 +1501,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
         const int NB = c.NB;
         if (c.N == 0) {
             if (c.tid == 0) tile_out_empty(A, H, t);
-            tile_predict_prior(A, H, t, c.tid, p0, p1, f_mean, f_var, y_var);
+            TILE_PREDICT_PRIOR(A, H, t, c.tid, p0, p1, f_mean, f_var, y_var);
             if (f_cov) prior_cov_empty<D, KN>(A.theta0 + (size_t)t * H, Xs + (size_t)p0 * D, c.P, c.tid, f_cov + A.cov_off[t]);
             if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
@@ -1438,6 +1513,9 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
         }
         if (resumed) state_load(sh, A, t, c.tid);
         else if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
+#ifdef GPSAT_F64_RQ
+        if (!resumed && c.tid == 0) rq_fresh_tile<D>(sh);
+#endif
         __syncthreads();
         const int seg_evals = sliced ? max(1, A.seg_cost / (NB * NB * NB)) : 0x7fffffff;
         bool suspended = false;
@@ -1474,7 +1552,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
 #endif
 }
 
-#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV)
+#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV) && !defined(GPSAT_F64_RQ)
 // ---------------------------------------------------------------------------------------------
 // the team kernel: KernelArgs::team_size workgroups per tile (see "Teams" above).  Workgroup b is member b % G of team
 // b / G; the team's workspace is the slab of its member 0.  The owner pops tiles, runs the optimiser and, before every
@@ -1619,6 +1697,16 @@ static hipError_t launch_d_cv(const KernelArgs& a, const CvArgs& cv, int grid, s
         default: return hipErrorInvalidValue;
     }
 }
+#elif defined(GPSAT_F64_RQ)
+template <int D>
+static hipError_t launch_d_rq(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
+    if (a.team_size > 1 || a.kernel != 4) return hipErrorInvalidValue;          // one workgroup per tile only
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, 4>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gp_tile_kernel_f64<D, 4>), dim3(grid), dim3(NT), smem, stream, a);
+    return hipGetLastError();
+}
 #else
 template <int D, int KN>
 static hipError_t launch_one(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
@@ -1660,6 +1748,15 @@ hipError_t F64FN(launch_tiles_cv_f64)(int D, const KernelArgs& a, const CvArgs& 
         case 2: return F64NS::launch_d_cv<2>(a, cv, grid, smem, stream);
         case 3: return F64NS::launch_d_cv<3>(a, cv, grid, smem, stream);
         case 4: return F64NS::launch_d_cv<4>(a, cv, grid, smem, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+#elif defined(GPSAT_F64_RQ)
+hipError_t F64FN(launch_tiles_rq_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
+    switch (D) {
+        case 1: return F64NS::launch_d_rq<1>(a, grid, smem, stream);
+        case 2: return F64NS::launch_d_rq<2>(a, grid, smem, stream);
+        case 3: return F64NS::launch_d_rq<3>(a, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -20,7 +20,7 @@ class GpsatError(RuntimeError):
 
 @dataclass
 class BatchResult:
-    theta: np.ndarray      # [T, H] learned parameters (l_1..l_D, kernel_variance, likelihood_variance)
+    theta: np.ndarray      # [T, H] learned parameters (l_1..l_D, kernel_variance, likelihood_variance[, alpha: RationalQuadratic])
     nll: np.ndarray        # [T] objective = negative log marginal likelihood
     status: np.ndarray     # [T] see _lib.STATUS
     n_eval: np.ndarray     # [T] objective+gradient evaluations used by the optimiser
@@ -128,10 +128,11 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-def _host_meta(D, offs, theta0, lo, hi, trainable):
-    """The CSR offset tables as contiguous int64, theta0 / lo / hi as [T, H] fp64 (no bounds: NaN) and trainable as [H] uint8."""
+def _host_meta(D, offs, theta0, lo, hi, trainable, H=None):
+    """The CSR offset tables as contiguous int64, theta0 / lo / hi as [T, H] fp64 (no bounds: NaN) and trainable as [H] uint8.
+    ``H``: hyper-parameters per tile (_lib.n_hyper), D + 2 by default."""
     offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
-    T, H = len(offs[0]) - 1, D + 2
+    T, H = len(offs[0]) - 1, (D + 2 if H is None else int(H))
     assert all(len(o) == T + 1 for o in offs)
 
     def per_tile(a):
@@ -196,7 +197,7 @@ class Engine:
         (f_mean, f_var, y_var), with fresh per-tile result arrays.  Returns (batch, results): ``results`` are BatchResult
         fields; the caller keeps ``meta``, ``data`` and ``preds`` alive until the library call has returned."""
         (obs_off, pred_off, *_), theta0, lo, hi, trainable = meta
-        T, H = len(obs_off) - 1, D + 2
+        T, H = len(obs_off) - 1, theta0.shape[1]
         res = dict(theta=np.empty((T, H), dtype=np.float64), nll=np.empty(T, dtype=np.float64),
                    grad=np.empty((T, H), dtype=np.float64) if want_grad else None, status=np.empty(T, dtype=np.int32),
                    n_eval=np.empty(T, dtype=np.int32), n_iter=np.zeros(T, dtype=np.int32))
@@ -256,6 +257,9 @@ class Engine:
         (default CV_REFIT_MAX_EXPANDED_ROWS = 2^25 rows: (D + 1) elements each on the device, 0.5 GiB in fp32 and 1 GiB
         in fp64 at D = 3), consecutive ranges of tiles are run by one library call each and the results concatenated; a
         single tile above the budget is an error.  Refused with cv_fold="loo", ``n_starts`` and ``full_cov``.
+        ``kernel="RationalQuadratic"``: one more hyper-parameter per tile, H = D + 3 with alpha last, so theta0 / lo / hi are
+        (H,) or (T, H) and trainable is (H,); fp64 and D <= 3 only, with ``full_cov`` but without ``n_starts``, ``cv_fold``
+        and ``cv_refit`` (the library refuses those with its own message).
         """
         refit = None
         if cv_refit is not None and cv_refit is not False:
@@ -268,9 +272,17 @@ class Engine:
                 raise GpsatError("cv_refit and n_starts cannot be combined")
             if full_cov:
                 raise GpsatError("cv_refit and full_cov cannot be combined")
-        meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable)
+        H = L.n_hyper(kernel, D)
+        if H == D + 3:
+            for pname, a in (("theta0", theta0), ("lo", lo), ("hi", hi), ("trainable", trainable)):
+                shp = None if a is None else np.shape(a)
+                if shp is not None and (len(shp) not in ((1,) if pname == "trainable" else (1, 2)) or shp[-1] != H):
+                    raise GpsatError(f"{pname} has shape {shp}: kernel {kernel!r} with D = {D} has H = D + 3 = {H} parameters per "
+                                     f"tile (lengthscales, kernel_variance, likelihood_variance, alpha), so (H,)"
+                                     + ("" if pname == "trainable" else " or (T, H)") + " is expected")
+        meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, H)
         obs_off, pred_off = meta[0]
-        T, H = len(obs_off) - 1, D + 2
+        T = len(obs_off) - 1
         sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
         if dtype not in ("f32", "f64"):
             raise GpsatError(f"dtype {dtype!r}: use 'f32' or 'f64'")
@@ -353,7 +365,7 @@ class Engine:
         """gpsat_fit_predict_batch_cv_refit over consecutive ranges of tiles, each within ``max_expanded_rows``."""
         (obs_off, pred_off), theta0, lo, hi, trainable = meta
         X, y, Xs = data
-        T, H = len(obs_off) - 1, D + 2
+        T, H = len(obs_off) - 1, theta0.shape[1]
         sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
         fold_off = np.zeros(T + 1, dtype=np.int64)
         rows = C.c_int64(0)

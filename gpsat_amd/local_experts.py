@@ -55,6 +55,10 @@ Sparse experts (``oi_model`` GPflowSGPRModel / HipSGPRModel, fp64): the main pro
 (``select_inducing_points`` with the expert's position in the expert locations), stored in the table ``inducing_points``
 (``_dim_0`` inducing index, ``_dim_1`` coordinate, scaled coordinates); ``objective_value`` is the ELBO.  The replacement
 profile stays an exact GP.
+RationalQuadratic experts (``init_params.kernel == "RationalQuadratic"``, exact GP, fp64: ``dtype`` None or "f64", at most 3
+coordinate columns): a fourth parameter, ``kernel_alpha`` (``init_params.kernel_kwargs.alpha``, default 1), with a table of its
+own that is stored by default, read by ``load_params`` (file or direct value), carried in the ``previous`` running mean and
+accepted by ``constraints``.  Not combined with a replacement model, ``cv`` or SGPR.
 ``replacement_*`` model settings for tiles below ``replacement_threshold`` observations are honoured (one engine call
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
@@ -108,6 +112,7 @@ from .models import (HipGPRModel, HipSGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND,
 
 _COMPS = {">=": np.greater_equal, ">": np.greater, "==": np.equal, "<": np.less, "<=": np.less_equal}
 PARAM_NAMES = ["lengthscales", "kernel_variance", "likelihood_variance"]
+RQ_KERNEL = "RationalQuadratic"                 # its experts have a fourth parameter table, kernel_alpha (H = D + 3)
 MODEL_NAME = f"{HipGPRModel.__module__}.{HipGPRModel.__name__}"[:64]
 SGPR_MODEL_NAME = f"{HipSGPRModel.__module__}.{HipSGPRModel.__name__}"[:64]
 SGPR_INIT_KEYS = ("num_inducing_points", "inducing_seed")
@@ -807,7 +812,7 @@ def _adjust_func(spec):
     raise NotImplementedError("load_params.index_adjust takes {col: {'func': callable or 'lambda x: ...'}}")
 
 
-# The per-tile result matrix ``fixed`` [n, H + _N_RES] (H = D + 2 parameters) holds, after the parameters, these columns at
+# The per-tile result matrix ``fixed`` [n, H + _N_RES] (H = D + 2 parameters, D + 3 with RationalQuadratic's alpha) holds, after the parameters, these columns at
 # ``H + <name>``.  It stays one float64 matrix so that ``sharding.gather_arrays`` carries it in one piece.
 _NLL, _STATUS, _N_EVAL, _N_ITER, _SECONDS, _OBS_MEAN = range(6)
 _N_RES = 6
@@ -839,13 +844,27 @@ class BatchedLocalExpertOI:
         if name not in ("HipGPRModel", "GPflowGPRModel") + SGPR_MODEL_NAMES:
             raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP and SGPR experts only")
         self.sgpr = name in SGPR_MODEL_NAMES
-        # dtype None: fp32 for exact-GP experts, fp64 for sparse ones (built in fp64 only -- an explicit fp32 is refused)
+        # RationalQuadratic experts: one more parameter per tile (kernel_alpha, last), exact GP in fp64 and D <= 3 only
+        self.rq = (model_config.get("init_params") or {}).get("kernel") == RQ_KERNEL
+        self.param_names = PARAM_NAMES + ["kernel_alpha"] if self.rq else PARAM_NAMES
+        self.H = len(data_config["coords_col"]) + len(self.param_names) - 1
+        if self.rq and self.sgpr:
+            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built for exact-GP experts only, not for SGPR")
+        # dtype None: fp32 for exact-GP experts, fp64 for sparse and RationalQuadratic ones (built in fp64 only -- an explicit
+        # fp32 is refused)
         if dtype is None:
-            dtype = "f64" if self.sgpr else "f32"
+            dtype = "f64" if (self.sgpr or self.rq) else "f32"
         if dtype not in DTYPES:
             raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
         if self.sgpr and dtype != "f64":
             raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
+        if self.rq and dtype != "f64":
+            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built in fp64 only: dtype must be None or 'f64'")
+        if self.rq and len(data_config["coords_col"]) > 3:
+            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built for 1..3 coordinate columns (D + 3 <= 6 parameters), "
+                                      f"got {len(data_config['coords_col'])}")
+        if self.rq and cv is not None:
+            raise NotImplementedError(f"cv: held-out predictions are not built for kernel '{RQ_KERNEL}'")
         self.dtype = dtype
         # held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with equal
         # values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
@@ -939,6 +958,9 @@ class BatchedLocalExpertOI:
                 raise NotImplementedError(f"replacement_model '{rname}': the batched backend builds the exact-GP expert only")
             rip = model_config.get("replacement_init_params")
             rco = model_config.get("replacement_constraints")
+            if self.rq or (rip or {}).get("kernel") == RQ_KERNEL:
+                raise NotImplementedError(f"kernel '{RQ_KERNEL}' and a replacement model cannot be combined: the two profiles of "
+                                          f"a run share one parameter layout, and this kernel has a parameter more")
             main_ip = {k: v for k, v in self.init_params.items() if k not in SGPR_INIT_KEYS}
             self.profiles["replacement"] = dict(
                 sgpr=False,
@@ -947,8 +969,8 @@ class BatchedLocalExpertOI:
                 optim_kwargs=dict(model_config.get("replacement_optim_kwargs") or {}),
                 pred_kwargs=dict(model_config.get("replacement_pred_kwargs") or {}))
         self.params_to_store = model_config.get("params_to_store") or (PARAM_NAMES + ["inducing_points"] if self.sgpr
-                                                                        else PARAM_NAMES)
-        bad = [p_ for p_ in self.params_to_store if p_ not in PARAM_NAMES + (["inducing_points"] if self.sgpr else [])]
+                                                                        else self.param_names)
+        bad = [p_ for p_ in self.params_to_store if p_ not in self.param_names + (["inducing_points"] if self.sgpr else [])]
         if bad:
             raise NotImplementedError(f"params_to_store {bad}: not a parameter of this model")
         self._set_load_params(model_config.get("load_params"))
@@ -988,6 +1010,14 @@ class BatchedLocalExpertOI:
             self.load_params = None
         elif lp is not None and "previous" in lp:
             self.load_params = {k: v for k, v in lp.items() if k not in ("previous", "previous_params")}
+
+    def _slots(self):
+        """(first column, width) of every named parameter in a tile's theta."""
+        D = len(self.coords_col)
+        slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
+        if self.rq:
+            slots["kernel_alpha"] = (D + 2, 1)
+        return slots
 
     def _template(self, pf, optimise, predict) -> _Profile:
         """The profile's record: HipGPRModel's defaults, scales, box and trainable mask from one throw-away model on a
@@ -1033,7 +1063,7 @@ class BatchedLocalExpertOI:
             j, f = cc.index(col), _adjust_func(spec)
             look[:, j] = [f(v) for v in look[:, j]]
         key = _index_for(cc, look)
-        slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
+        slots = self._slots()
         for pn, tab in tabs.items():
             start, width = slots[pn]
             colvals = np.full((len(locs), width), np.nan)
@@ -1241,8 +1271,8 @@ class BatchedLocalExpertOI:
             # the tables, read ONCE per run and indexed by expert coordinates (local_experts.py:553-689)
             src, tsuf = lp.get("file"), lp.get("table_suffix", "")   # load_params(table_suffix="") default, :561
             reader, tabs = None if isinstance(src, dict) else ResultStore(src), {}
-            for pn in lp.get("param_names") or PARAM_NAMES:
-                assert pn in PARAM_NAMES, f"provide param name:{pn}\nis not in param_names:{PARAM_NAMES}"
+            for pn in lp.get("param_names") or self.param_names:
+                assert pn in self.param_names, f"provide param name:{pn}\nis not in param_names:{self.param_names}"
                 tab = src.get(f"{pn}{tsuf}") if isinstance(src, dict) else reader.read(f"{pn}{tsuf}")
                 if tab is not None and len(tab):
                     tabs[pn] = tab
@@ -1257,7 +1287,7 @@ class BatchedLocalExpertOI:
             save_params[:] = not (same and not optimise)        # local_experts.py:1090-1097
         elif lp is not None:
             # parameters given directly (load_params(**param_dict), local_experts.py:553-604)
-            direct = {k: v for k, v in lp.items() if k in PARAM_NAMES}
+            direct = {k: v for k, v in lp.items() if k in self.param_names}
             if not direct:
                 raise NotImplementedError("load_params needs 'file' or parameter values")
             for pn, v in direct.items():
@@ -1265,7 +1295,7 @@ class BatchedLocalExpertOI:
                 if pn == "lengthscales":
                     theta0[:, :D] = v
                 else:
-                    theta0[:, D + PARAM_NAMES.index(pn) - 1] = v[0]
+                    theta0[:, D + self.param_names.index(pn) - 1] = v[0]
         for pi, pf in enumerate(profiles):                      # move within tol of the box (gpflow_models.py:471-479)
             m_ = prof_id == pi
             for sl, tol in pf.clamp:
@@ -1467,7 +1497,7 @@ class BatchedLocalExpertOI:
         tiles' predictions / covariance blocks back to back), pure array assembly (GPSat/local_experts.py:691-747).
         ``with_preds=False``: the caller has written the preds rows as pieces and builds that frame itself."""
         cc = self.coords_col
-        D, H = len(cc), len(cc) + 2
+        D, H = len(cc), self.H
         items = np.asarray(items, dtype=np.int64)
         n, locs, tile = len(items), plan.locs[items], plan.kind[items] == 2
         profs = [plan.profiles[p] for p in plan.prof_id[items]]
@@ -1481,7 +1511,7 @@ class BatchedLocalExpertOI:
             "device": np.array([pf.device if t else "" for pf, t in zip(profs, tile)], dtype=object),
             "config_id": np.full(n, plan.config_id, dtype=np.int64)}, index=_index_for(cc, locs))}
         sp = tile & plan.save_params[items]
-        slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
+        slots = self._slots()
         for pn in self.params_to_store:
             if pn == "inducing_points":
                 # [M, D] per expert: _dim_0 inducing index, _dim_1 coordinate (dict_of_array_to_table of a 2-D array)
@@ -1533,7 +1563,7 @@ class _ShardRunner:
 
     def __init__(self, oi: BatchedLocalExpertOI, plan: _Plan, items, store: ResultStore, wave_n, chunk_n, t_start):
         self.oi, self.plan, self.items, self.store, self.t_start = oi, plan, items, store, t_start
-        self.H = len(oi.coords_col) + 2
+        self.H = oi.H
         self.waves = [items[w0:w0 + wave_n] for w0 in range(0, len(items), wave_n)]
         self.jobs, self.jobs_of_wave = [], {}          # jobs: (wave, profile, positions within the wave, items)
         for wi, w in enumerate(self.waves):
@@ -1633,7 +1663,7 @@ class _ShardRunner:
         """Job k on a free engine: (packed arrays, engine result, seconds of the call)."""
         p, pf, ids = self.plan, self.plan.profiles[self.jobs[k][1]], self.jobs[k][3]
         pk = self.packs.pop(k).result()
-        kw = dict(D=self.H - 2, obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"], Xs=pk["Xs"], lo=p.lo[ids],
+        kw = dict(D=len(self.oi.coords_col), obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"], Xs=pk["Xs"], lo=p.lo[ids],
                   hi=p.hi[ids], trainable=pf.trainable, kernel=pf.kernel, optimiser=pf.optimiser, max_iter=pf.max_iter,
                   **pf.eng_kw)
         eng_ = self.free_engines.get()

@@ -132,13 +132,21 @@ class HipGPRModel:
         if D > 4:
             raise NotImplementedError("HIP backend is built for 1..4 input dimensions")
         self.D = D
+        # RationalQuadratic: a fourth trainable parameter, alpha, last in the device's vector (H = D + 3)
+        self._rq = L.KERNEL_IDS[kernel] == L.KERNEL_RQ
+        if self._rq and dtype != "f64":
+            raise NotImplementedError(f"kernel {kernel!r} is built in fp64 only: pass dtype='f64'")
+        if self._rq and D > 3:
+            raise NotImplementedError(f"kernel {kernel!r} is built for 1..3 input dimensions (D + 3 <= 6 parameters), got D = {D}")
         kk = dict(kernel_kwargs or {})
         ls = np.broadcast_to(np.asarray(kk.get("lengthscales", np.ones(D)), dtype=np.float64), (D,)).copy()
         self._theta = np.concatenate([ls, [float(kk.get("variance", 1.0))],
-                                      [1.0 if noise_variance is None else float(noise_variance)]])
-        self._lo = np.full(D + 2, np.nan)
-        self._hi = np.full(D + 2, np.nan)
-        self._trainable = np.ones(D + 2, dtype=bool)
+                                      [1.0 if noise_variance is None else float(noise_variance)],
+                                      [float(kk.get("alpha", 1.0))] if self._rq else []])       # GPflow: alpha = 1
+        H = L.n_hyper(kernel, D)
+        self._lo = np.full(H, np.nan)
+        self._hi = np.full(H, np.nan)
+        self._trainable = np.ones(H, dtype=bool)
 
         # ---- device info: base_model.py:259 (attributes the orchestrator reads at local_experts.py:1180)
         from .engine import default_engine
@@ -157,7 +165,9 @@ class HipGPRModel:
     # ------------------------------------------------------------------ interface
     @property
     def param_names(self) -> List[str]:
-        return ["lengthscales", "kernel_variance", "likelihood_variance"]
+        # the reference's three names (gpflow_models.py:179-184) would lose alpha in params_to_store and load_params
+        names = ["lengthscales", "kernel_variance", "likelihood_variance"]
+        return names + ["kernel_alpha"] if self._rq else names
 
     def get_parameters(self, *args, return_dict=True):
         # base_model.py:370-403
@@ -191,6 +201,20 @@ class HipGPRModel:
     def get_likelihood_variance(self) -> float:
         return float(self._theta[self.D + 1])
 
+    def _need_rq(self):
+        if not self._rq:
+            raise AttributeError(f"kernel_alpha is a parameter of the 'RationalQuadratic' kernel, this model's is {self.kernel!r}")
+
+    def get_kernel_alpha(self) -> float:
+        self._need_rq()
+        return float(self._theta[self.D + 2])
+
+    def set_kernel_alpha(self, kernel_alpha):
+        self._need_rq()
+        v = np.asarray(kernel_alpha, dtype=np.float64).reshape(-1)
+        assert len(v) == 1, f"set_kernel_alpha expected a float or an array of one element, got {len(v)}"
+        self._theta[self.D + 2] = float(v[0])
+
     def set_lengthscales(self, lengthscales):
         v = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
         assert len(v) in (1, self.D), f"lengthscales must have length 1 or {self.D}"
@@ -221,7 +245,7 @@ class HipGPRModel:
     def _slice(self, name):
         D = self.D
         return {"lengthscales": slice(0, D), "kernel_variance": slice(D, D + 1),
-                "likelihood_variance": slice(D + 1, D + 2)}[name]
+                "likelihood_variance": slice(D + 1, D + 2), "kernel_alpha": slice(D + 2, D + 3)}[name]
 
     def _set_param_constraints(self, name, low, high, move_within_tol=True, tol=1e-8, scale=False,
                                scale_magnitude=None):
@@ -257,6 +281,10 @@ class HipGPRModel:
 
     def set_likelihood_variance_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
         self._set_param_constraints("likelihood_variance", low, high, move_within_tol, tol, scale, scale_magnitude)
+
+    def set_kernel_alpha_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
+        self._need_rq()
+        self._set_param_constraints("kernel_alpha", low, high, move_within_tol, tol, scale, scale_magnitude)
 
     # -- the three device calls
     def _run(self, *, optimiser, max_iter=0, pred_coords=None, **opt_kwargs):
@@ -359,6 +387,8 @@ class HipGPRModel:
         "objective_value", "status", "num_obs" and "shift" (the mean of the rows the fold leaves, in the units of "f*")."""
         from .engine import factorise_folds
         N, D = self.coords.shape
+        if self._rq:
+            raise NotImplementedError(f"held-out predictions are not built for kernel {self.kernel!r}")
         if refit:
             return self._cross_validate_refit(fold, **refit_kwargs)
         if refit_kwargs:
@@ -427,6 +457,8 @@ class HipSGPRModel(HipGPRModel):
                  inducing_seed=0, expert_index=0, **kwargs):
         if dtype != "f64":
             raise NotImplementedError("HipSGPRModel is built in fp64 only (dtype='f64')")
+        if kernel == "RationalQuadratic":
+            raise NotImplementedError("kernel 'RationalQuadratic' is built for exact experts (HipGPRModel) only, not for SGPR")
         super().__init__(data=data, coords_col=coords_col, obs_col=obs_col, coords=coords, obs=obs,
                          coords_scale=coords_scale, obs_scale=obs_scale, obs_mean=obs_mean, verbose=verbose,
                          kernel=kernel, kernel_kwargs=kernel_kwargs, mean_function=mean_function,

@@ -20,6 +20,9 @@
  *     theta = (lengthscale_0 .. lengthscale_{D-1}, kernel_variance, likelihood_variance)
  * i.e. the reference's param_names ["lengthscales","kernel_variance","likelihood_variance"]
  * (GPSat/models/gpflow_models.py:179-184) flattened.
+ * GPSAT_KERNEL_RQ has one more, its shape parameter alpha, behind them (H = D + 3, no other index moves):
+ *     theta = (lengthscale_0 .. lengthscale_{D-1}, kernel_variance, likelihood_variance, alpha)
+ * H of any kernel is gpsat_n_hyper(kernel, D).
  */
 #ifndef GPSAT_HIP_H
 #define GPSAT_HIP_H
@@ -48,6 +51,13 @@ extern "C" {
 #define GPSAT_KERNEL_MATERN12 1   /* "Matern12" / "Exponential"   */
 #define GPSAT_KERNEL_MATERN32 2   /* "Matern32" (reference default, gpflow_models.py:44) */
 #define GPSAT_KERNEL_MATERN52 3   /* "Matern52" */
+#define GPSAT_KERNEL_RQ       4   /* "RationalQuadratic": k = s (1 + r^2 / (2 alpha))^-alpha, r^2 = sum_d ((x_d - x'_d) / l_d)^2,  */
+                                  /*   as GPflow's and scikit-learn's; H = D + 3 with alpha last.  Built into                     */
+                                  /*   gpsat_fit_predict_batch (f_cov included) for GPSAT_F64 and D <= 3, one workgroup per tile; */
+                                  /*   GPSAT_F32, D = 4 and every other entry point return GPSAT_EINVAL with a message.  alpha's  */
+                                  /*   transform follows lo / hi like every parameter's: NaN bounds = softplus without a shift    */
+                                  /*   (GPflow's positive()), finite bounds = the sigmoid box.  Callers detect the kernel by the  */
+                                  /*   presence of gpsat_n_hyper; GPSAT_ABI_VERSION stays 4.                                      */
 
 /* optimisers */
 #define GPSAT_OPT_NONE  0   /* optimise=False in LocalExpertOI.run (local_experts.py:1126-1132) */
@@ -73,6 +83,10 @@ extern "C" {
                                    /*   the best sufficient-decrease point seen                   */
 
 typedef struct gpsat_handle gpsat_handle;
+
+/* Hyper-parameters per tile, the H of every [T*H] and [H] array of gpsat_batch: D + 3 for GPSAT_KERNEL_RQ (D = 1..3),
+ * D + 2 for the other kernels (D = 1..4); 0 for unsupported arguments. */
+int gpsat_n_hyper(int kernel, int D);
 
 typedef struct gpsat_opts {
     int32_t workgroups_per_cu;   /* persistent workgroups per CU (0 = default 2)            */
