@@ -20,11 +20,10 @@ import numpy as np
 import pytest
 
 import sgpr_numpy as sn
-from oracle import gp_oracle as go
+from sgpr_edge_cases import check_fixed as _check_fixed, cond_kuu as _cond, pack as _pack
 
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(np.float64).eps
 M_MAX = 1024
 
 
@@ -36,45 +35,12 @@ def eng():
     e.close()
 
 
-def _cond(kid, Z, th):
-    D = Z.shape[1]
-    return np.linalg.cond(go.kernel_matrix(kid, Z, Z, th[:D], th[D]) + sn.JITTER * np.eye(len(Z)))
-
-
 def _make_tile(rng, N, M, D, P=5):
     side = 0.5 * M ** (1.0 / D)          # inducing points about half a length scale apart
     X = rng.uniform(0, side, (N, D))
     y = np.sin(X.sum(1)) + 0.3 * rng.normal(size=N)
     Z = X[:M].copy() if N >= M else rng.uniform(0, side, (M, D))
     return X, y, Z, rng.uniform(0, side, (P, D))
-
-
-def _pack(tiles):
-    off = lambda k: np.concatenate([[0], np.cumsum([len(t[k]) for t in tiles])]).astype(np.int64)
-    cat = lambda k: np.concatenate([t[k] for t in tiles])
-    return dict(obs_off=off(0), X=cat(0), y=cat(1), z_off=off(2), Z=cat(2), pred_off=off(3), Xs=cat(3))
-
-
-def _check_fixed(eng, kid, D, tiles, th):
-    pk = _pack(tiles)
-    r = eng.sgpr_fit_predict_batch(D=D, kernel=kid, theta0=th, optimiser="none", want_grad=True, **pk)
-    assert (r.status == 5).all(), r.status
-    for t, (X, y, Z, P) in enumerate(tiles):
-        c = X.mean(0)
-        Xc, Zc, Pc = X - c, Z - c, P - c
-        el = sn.elbo(kid, Xc, y, Zc, th)
-        g = sn.elbo_grad(kid, Xc, y, Zc, th)
-        f, fv, yv = sn.predict(kid, Xc, y, Zc, Pc, th)
-        cnd = 64 * EPS * _cond(kid, Zc, th)
-        a, b = pk["pred_off"][t], pk["pred_off"][t + 1]
-        what = f"kernel {kid} D {D} N {len(X)} M {len(Z)}"
-        assert abs(-r.nll[t] - el) <= (1e-9 + cnd) * abs(el), what
-        gtol = 1e-7 * np.max(np.abs(g)) + cnd * sn.grad_rounding_scale(kid, Xc, y, Zc, th)
-        assert np.all(np.abs(-r.grad[t] - g) <= gtol), (what, -r.grad[t] - g, gtol)
-        assert np.max(np.abs(r.f_mean[a:b] - f)) <= (1e-9 + cnd) * max(1.0, np.max(np.abs(f))), what
-        assert np.max(np.abs(r.f_var[a:b] - fv)) <= (1e-9 + cnd) * th[D], what
-        assert np.max(np.abs(r.y_var[a:b] - yv)) <= (1e-9 + cnd) * th[D], what
-    return r
 
 
 def test_reference_sgpr_known_answer(eng, golden_dir):
