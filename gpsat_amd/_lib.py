@@ -18,6 +18,8 @@ F32, F64 = 0, 1
 KERNEL_IDS = {"RBF": 0, "SquaredExponential": 0, "Matern12": 1, "Exponential": 1, "Matern32": 2, "Matern52": 3,
               "RationalQuadratic": 4}
 KERNEL_RQ = 4      # GPSAT_KERNEL_RQ: one more hyper-parameter (alpha, last), fp64 and D <= 3 only
+MEAN_ZERO, MEAN_CONSTANT = 0, 1      # GPSAT_MEAN_*: a trainable constant mean is one more hyper-parameter (c, last)
+MEAN_IDS = {None: MEAN_ZERO, "zero": MEAN_ZERO, "constant": MEAN_CONSTANT}
 OPT_NONE, OPT_LBFGS, OPT_ADAM = 0, 1, 2
 OPT_IDS = {"none": OPT_NONE, None: OPT_NONE, "lbfgs": OPT_LBFGS, "L-BFGS-B": OPT_LBFGS, "adam": OPT_ADAM}
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -28,10 +30,11 @@ EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_cre
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
            "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
            "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit",
-           "gpsat_n_hyper"]
+           "gpsat_n_hyper", "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
 OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold",
-                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit", "gpsat_n_hyper"]
+                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit", "gpsat_n_hyper",
+                    "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean"]
 
 
 class GpsatOpts(C.Structure):
@@ -62,6 +65,10 @@ TRANSFORM_LOG = 1
 class GpsatMultistart(C.Structure):
     _fields_ = [("n_starts", C.c_int32), ("transform", C.c_int32), ("starts", C.c_void_p), ("f_start", C.c_void_p),
                 ("reserved", C.c_int32 * 8)]
+
+
+class GpsatMean(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class GpsatCv(C.Structure):
@@ -192,6 +199,11 @@ def load():
     if hasattr(lib, "gpsat_n_hyper"):
         lib.gpsat_n_hyper.argtypes = [C.c_int, C.c_int]
         lib.gpsat_n_hyper.restype = C.c_int
+    if hasattr(lib, "gpsat_fit_predict_batch_mean"):
+        lib.gpsat_n_hyper_mean.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.gpsat_n_hyper_mean.restype = C.c_int
+        lib.gpsat_fit_predict_batch_mean.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMean)]
+        lib.gpsat_fit_predict_batch_mean.restype = C.c_int
     if hasattr(lib, "gpsat_bin_batch"):
         lib.gpsat_bin_batch.restype = C.c_int
         lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -204,12 +216,13 @@ def load():
     return lib
 
 
-def n_hyper(kernel, D: int) -> int:
-    """Hyper-parameters per tile (gpsat_n_hyper): D + 3 for "RationalQuadratic" (lengthscales, kernel variance, likelihood
-    variance, alpha), D + 2 for the other kernels.  Host arithmetic, the same rule as the library's: shapes can be laid out
-    without loading it."""
+def n_hyper(kernel, D: int, mean=None) -> int:
+    """Hyper-parameters per tile (gpsat_n_hyper, gpsat_n_hyper_mean): D + 3 for "RationalQuadratic" (lengthscales, kernel
+    variance, likelihood variance, alpha) and for ``mean="constant"`` with another kernel (..., likelihood variance, c), D + 2
+    otherwise.  Host arithmetic, the same rule as the library's for the arguments it supports: shapes can be laid out without
+    loading it."""
     kid = KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-    return int(D) + (3 if kid == KERNEL_RQ else 2)
+    return int(D) + (3 if kid == KERNEL_RQ or MEAN_IDS[mean] == MEAN_CONSTANT else 2)
 
 
 def max_tile_obs(dtype: str, D: int) -> int:

@@ -3,7 +3,7 @@
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
 // Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
 // translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
-//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
 //     setup_*, launch, fetch_batch / fetch_cv, record_timing.
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
@@ -162,8 +162,9 @@ int run_with_temp(gpsat_handle* h, DevBuf& tmp, const char* what, hipEvent_t mar
 }
 
 // Hyper-parameters per tile: D + 2, or D + 3 with the RationalQuadratic kernel's alpha behind them (gpsat_n_hyper).  Read
-// behind check_batch only, which refuses the arguments it answers with 0.
-int n_hyper(const gpsat_batch* b) { return gpsat_n_hyper(b->kernel, b->D); }
+// behind check_batch only, which refuses the arguments it answers with 0.  `mean`: GPSAT_MEAN_* of the call
+// (gpsat_fit_predict_batch_mean; a constant mean is one more parameter, last), behind gpsat::check_mean.
+int n_hyper(const gpsat_batch* b, int mean = GPSAT_MEAN_ZERO) { return gpsat_n_hyper_mean(b->kernel, b->D, mean); }
 
 struct BatchDims { long long sumN = 0, sumP = 0, sumC = 0, sumM = 0, maxN = 0, maxP = 0; bool want_cov = false; };
 
@@ -203,11 +204,15 @@ int check_rq(const gpsat_batch* b, const char* entry) {
 }
 
 // ... and the checks that follow the offsets in both: data pointers against the sums, theta0
-int check_batch_data(const gpsat_batch* b, const BatchDims& d) {
+// (a constant mean, the last parameter, may be any finite value: gpsat::check_mean has looked at it)
+int check_batch_data(const gpsat_batch* b, const BatchDims& d, int mean = GPSAT_MEAN_ZERO) {
     if (d.sumN > 0 && (!b->X || !b->y)) return fail(GPSAT_EINVAL, "X / y is NULL");
     if (d.sumP > 0 && (!b->Xs || !b->f_mean || !b->f_var || !b->y_var)) return fail(GPSAT_EINVAL, "prediction pointer is NULL");
-    for (size_t e = 0; e < (size_t)b->T * n_hyper(b); ++e)
+    const size_t H = (size_t)n_hyper(b, mean);
+    for (size_t e = 0; e < (size_t)b->T * H; ++e) {
+        if (mean == GPSAT_MEAN_CONSTANT && e % H == H - 1) continue;
         if (!(b->theta0[e] > 0.0) || !std::isfinite(b->theta0[e])) return fail(GPSAT_EINVAL, "theta0 must be finite and positive");
+    }
     return GPSAT_OK;
 }
 
@@ -353,8 +358,8 @@ struct Staged {
 // copies.  `off3`: the third offset table or nullptr; `Z`: the sparse path's inducing points (d.sumM rows) or nullptr.
 // `order` is pageable host memory of the caller and must outlive the launch.
 int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const double* theta0, const std::vector<int>& order,
-                const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s) {
-    const int T = b->T, D = b->D, H = n_hyper(b);
+                const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s, int mean = GPSAT_MEAN_ZERO) {
+    const int T = b->T, D = b->D, H = n_hyper(b, mean);
     const size_t esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
     const size_t sumN = (size_t)d.sumN, sumP = (size_t)d.sumP, sumM = (size_t)d.sumM;
     int rc;
@@ -407,8 +412,8 @@ int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const
 
 // The fields KernelArgs and SgprArgs have in common: sizes, optimiser settings with their defaults, staged pointers.
 template <class Args>
-void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s) {
-    const int T = b->T, H = n_hyper(b);
+void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s, int mean = GPSAT_MEAN_ZERO) {
+    const int T = b->T, H = n_hyper(b, mean);
     const bool f64 = b->dtype == GPSAT_F64;
     a.T = T; a.kernel = b->kernel; a.optimiser = b->optimiser; a.max_iter = b->max_iter;
     a.max_ls = b->max_ls > 0 ? b->max_ls : 20;                                 // SciPy L-BFGS-B maxls
@@ -432,8 +437,8 @@ void fill_common_args(Args& a, const gpsat_batch* b, const Staged& s) {
 }
 
 // Device-to-host copies of the results (host mode: the predictions and the covariance too).
-int fetch_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const Staged& s) {
-    const size_t T = (size_t)b->T, H = (size_t)n_hyper(b), esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
+int fetch_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const Staged& s, int mean = GPSAT_MEAN_ZERO) {
+    const size_t T = (size_t)b->T, H = (size_t)n_hyper(b, mean), esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
     HIP_TRY(hipMemcpyAsync(b->theta, s.out_f64, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(b->nll, s.out_f64 + T * H, T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (b->grad) HIP_TRY(hipMemcpyAsync(b->grad, s.out_f64 + T * H + T, T * H * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -618,6 +623,7 @@ struct DenseJob {
     const gpsat_multistart* ms;       // nullptr: gpsat_fit_predict_batch
     const gpsat_cv* cv = nullptr;     // held-out predictions (gpsat_fit_predict_batch_cv), with their fold tables
     CvTables cv_tables;
+    int mean = GPSAT_MEAN_ZERO;       // GPSAT_MEAN_CONSTANT: gpsat_fit_predict_batch_mean with a trainable constant mean
     bool ms_on;                       // ms given and the optimiser runs
     BatchDims dims;
     const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
@@ -629,18 +635,18 @@ struct DenseJob {
 int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, LaunchReport& r) {
     const gpsat_batch* b = j.b;
     const BatchDims& d = j.dims;
-    const bool f64 = b->dtype == GPSAT_F64, rq = b->kernel == GPSAT_KERNEL_RQ;
+    const bool f64 = b->dtype == GPSAT_F64, rq = b->kernel == GPSAT_KERNEL_RQ, mean = j.mean == GPSAT_MEAN_CONSTANT;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
-                           h->num_cu, h->wg_per_cu, solo || j.cv || rq, unsliced, read_dev_knobs()};     // held-out, RQ: one workgroup per tile
+                           h->num_cu, h->wg_per_cu, solo || j.cv || rq || mean, unsliced, read_dev_knobs()};     // held-out, RQ, mean: one workgroup per tile
     gpsat::TilePlan p;
     if (!gpsat::plan_tiles(in, p)) return fail(GPSAT_EINVAL, "tile too large for LDS");
     Staged s;
     int rc;
     // one workspace per workgroup, or per team
     const size_t ws_bytes = (size_t)(p.grid / p.team) * p.ws_stride * (f64 ? sizeof(double) : sizeof(float));
-    if ((rc = stage_batch(h, b, d, j.theta0, j.order, d.want_cov ? b->cov_off : nullptr, nullptr, ws_bytes, s))) return rc;
+    if ((rc = stage_batch(h, b, d, j.theta0, j.order, d.want_cov ? b->cov_off : nullptr, nullptr, ws_bytes, s, j.mean))) return rc;
     gpsat::KernelArgs a;
-    fill_common_args(a, b, s);
+    fill_common_args(a, b, s, j.mean);
     a.NBmax = p.NBmax;
     a.ws = static_cast<float*>(h->ws.p); a.ws_stride = p.ws_stride;     // fp64: the kernel reinterprets ws as doubles
     a.prof = nullptr;
@@ -673,9 +679,10 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     if (j.cv) HIP_TRY(gpsat::builds[p.build].launch_cv(b->D, a, ca, p.grid, p.smem, h->stream));
     else if (rq) HIP_TRY((p.build == gpsat::BUILD_F64_W4 ? gpsat::launch_tiles_rq_f64_w4 : gpsat::launch_tiles_rq_f64)(b->D, a, p.grid, p.smem, h->stream));
+    else if (mean) HIP_TRY((p.build == gpsat::BUILD_F64_W4 ? gpsat::launch_tiles_mean_f64_w4 : gpsat::launch_tiles_mean_f64)(b->D, a, p.grid, p.smem, h->stream));
     else HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    if ((rc = fetch_batch(h, b, d, s))) return rc;
+    if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, d, ca))) return rc;
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -689,7 +696,8 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     return GPSAT_OK;
 }
 
-int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr) {
+int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr,
+                const gpsat_mean* mn = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
@@ -697,6 +705,11 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
     int rc;
     if ((rc = check_batch(b, false, j.dims))) return rc;
     if ((rc = check_rq(b, ms ? "gpsat_fit_predict_batch_ms" : cv ? "gpsat_fit_predict_batch_cv" : nullptr))) return rc;
+    if (mn) {
+        const char* why = nullptr;
+        if ((rc = gpsat::check_mean(b, mn, &why))) return fail(rc, why);
+        j.mean = mn->kind;
+    }
     BatchDims& d = j.dims;
     d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
     if (d.want_cov) {
@@ -712,7 +725,7 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
     if (d.maxN > gpsat_max_tile_obs(b->dtype, b->D))
         return fail(GPSAT_EINVAL, "tile too large for the LDS of a CU: at most " + std::to_string(gpsat_max_tile_obs(b->dtype, b->D)) +
                                       " observations per tile for this dtype and D (gpsat_max_tile_obs)");
-    if ((rc = check_batch_data(b, d))) return rc;
+    if ((rc = check_batch_data(b, d, j.mean))) return rc;
     if (cv && (rc = check_cv(b, cv, d, j.cv_tables))) return rc;
     j.ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
     if (ms && (rc = check_multistart(b, ms, j.ms_on, j.theta0_clipped, j.starts_clipped))) return rc;
@@ -1031,6 +1044,12 @@ int gpsat_n_hyper(int kernel, int D) {
     return D + 2;
 }
 
+int gpsat_n_hyper_mean(int kernel, int D, int mean_kind) {
+    if (mean_kind == GPSAT_MEAN_ZERO) return gpsat_n_hyper(kernel, D);
+    if (mean_kind != GPSAT_MEAN_CONSTANT || D < 1 || D > 3 || kernel < 0 || kernel >= GPSAT_KERNEL_RQ) return 0;
+    return D + 3;
+}
+
 int gpsat_create(int device_id, const gpsat_opts* opts, gpsat_handle** out) {
     if (!out) return fail(GPSAT_EINVAL, "gpsat_create: out is NULL");
     *out = nullptr;
@@ -1078,6 +1097,11 @@ int gpsat_last_timing(gpsat_handle* h, double* kernel_ms, double* total_ms) {
 }
 
 int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_predict(h, b, nullptr); }
+
+int gpsat_fit_predict_batch_mean(gpsat_handle* h, const gpsat_batch* b, const gpsat_mean* m) {
+    if (!m) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_mean: mean is NULL");
+    return fit_predict(h, b, nullptr, nullptr, m);
+}
 
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {
     if (!ms) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_ms: NULL multistart");

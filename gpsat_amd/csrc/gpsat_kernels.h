@@ -136,6 +136,9 @@ hipError_t launch_tiles_cv_f64_w4(int D, const KernelArgs& a, const CvArgs& cv, 
 // workgroup per tile; LDS, workspace and state words are those of the build of the same wave count
 hipError_t launch_tiles_rq_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 hipError_t launch_tiles_rq_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+// ... and for a trainable constant mean (-DGPSAT_F64_MEAN: kernels 0..3, D = 1..3, H = D + 3 with c last), by the same rules
+hipError_t launch_tiles_mean_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+hipError_t launch_tiles_mean_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

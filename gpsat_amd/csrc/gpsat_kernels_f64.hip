@@ -63,16 +63,43 @@ namespace gpsat {
 #define F64NS f64krq
 #endif
 #define F64_NHYP D + 3                                    /* hyper-parameters of a tile, in expressions of the templates */
+#define F64_NSUM D + 3                                    /* partial sums per lane an item of the gradient phase leaves */
 #define RQ_ARG(x_) , x_
 #define KFUN_C(c_, r2_, kf_, gg_) double ga; kfun_rq((c_).rqa, (c_).rqh, r2_, kf_, gg_, ga)
 #define KFUN_T(th_, r2_, kf_, gg_) double ga; kfun_rq((th_)[D + 2], 0.5 / (th_)[D + 2], r2_, kf_, gg_, ga)
 #define TILE_PREDICT_PRIOR rq_predict_prior<D>
 #else
-#define F64_NHYP D + 2
 #define RQ_ARG(x_)
 #define KFUN_C(c_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
 #define KFUN_T(th_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
+#define F64_NSUM D + 2
+#endif
+// -DGPSAT_F64_MEAN compiles the one-workgroup-per-tile kernel of either build once more for a trainable constant mean
+// (GPflow's mean_functions.Constant, gpsat_fit_predict_batch_mean): y ~ N(c 1, K + sn2 I) with the four stationary kernels,
+// H = D + 3, theta = (l_0 .. l_{D-1}, kernel variance, likelihood variance, c), D = 1..3.  Every evaluation works on the
+// residual y - c of ITS c; dNLL/dc = -sum(alpha); c is added to the predicted mean.  c has the identity transform unless it
+// is boxed (GPSAT_OPT_IDENTITY in gpsat_opt.h, defined for these builds only).  Objects of their own that export
+// launch_tiles_mean_f64[_w4] only; without the flag the translation unit is, token for token, what it was before.
+#ifdef GPSAT_F64_MEAN
+#if defined(GPSAT_F64_CV) || defined(GPSAT_F64_RQ)
+#error "GPSAT_F64_MEAN, GPSAT_F64_RQ and GPSAT_F64_CV are builds of their own"
+#endif
+#undef F64NS
+#ifdef GPSAT_F64_W4
+#define F64NS f64k4mn
+#else
+#define F64NS f64kmn
+#endif
+#define GPSAT_OPT_IDENTITY
+#define F64_NHYP D + 3
+#define TILE_PREDICT_PRIOR mean_predict_prior<D>
+#define MEAN_ADD(x_) + (x_)
+#elif !defined(GPSAT_F64_RQ)
+#define F64_NHYP D + 2
 #define TILE_PREDICT_PRIOR tile_predict_prior
+#endif
+#ifndef GPSAT_F64_MEAN
+#define MEAN_ADD(x_)
 #endif
 namespace F64NS {
 
@@ -268,6 +295,9 @@ struct Ctx {
     int gp0;                     // byte offset of the gradient phase's per-item partial sums (aliases the prediction scratch)
 #ifdef GPSAT_F64_RQ
     double rqa, rqh;             // alpha of the running evaluation, and 1 / (2 alpha)
+#endif
+#ifdef GPSAT_F64_MEAN
+    const double* yg;            // the tile's observations in memory: every evaluation forms y - c in LDS from them
 #endif
 };
 
@@ -1052,7 +1082,7 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
                         contract<D, KN>(c, acc[r][n], a, b, (a == b) ? 1.0 : 2.0, accl, accsf, accsn RQ_ARG(accal));
                 }
             }
-            double* gp = gpart + (size_t)item * (F64_NHYP) * 64 + lane;
+            double* gp = gpart + (size_t)item * (F64_NSUM) * 64 + lane;
             if (TEAM) {
                 gdouble* gg = (gdouble*)gp;
 #pragma unroll
@@ -1080,26 +1110,37 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     PROF_END(c, 11);
     if (c.member != 0) return;
     // fixed-order sum: wave w adds the items w, w + NW, ... per lane, then across lanes, then across waves
-    double v[F64_NHYP];
+    double v[F64_NSUM];
 #pragma unroll
-    for (int i = 0; i < F64_NHYP; ++i) v[i] = 0.0;
+    for (int i = 0; i < F64_NSUM; ++i) v[i] = 0.0;
     for (int it = c.w; it < nitems; it += NW) {
-        const double* gp = gpart + (size_t)it * (F64_NHYP) * 64 + lane;
+        const double* gp = gpart + (size_t)it * (F64_NSUM) * 64 + lane;
 #pragma unroll
-        for (int i = 0; i < F64_NHYP; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
+        for (int i = 0; i < F64_NSUM; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
     }
 #pragma unroll
-    for (int i = 0; i < F64_NHYP; ++i) {
+    for (int i = 0; i < F64_NSUM; ++i) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
     }
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < F64_NHYP; ++i) sh->red[c.w][i] = v[i];
+        for (int i = 0; i < F64_NSUM; ++i) sh->red[c.w][i] = v[i];
     }
+#ifdef GPSAT_F64_MEAN
+    // dNLL/dc = -sum_p alpha_p in the order of EIGHT virtual waves (the 4-wave build runs two each): virtual lane v adds the
+    // rows v, v + 512, ..., then across the lanes of its wave, then thread 0 across the eight -- one order in both builds
+    for (int vw = c.w; vw < 8; vw += NW) {
+        double s = 0.0;
+        for (int p = 64 * vw + lane; p < c.N; p += 512) s += lds_d[c.L.alpha + p];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        if (lane == 0) sh->red[vw][D + 2] = s;
+    }
+#endif
     __syncthreads();
     if (c.tid == 0) {
-        for (int i = 0; i < F64_NHYP; ++i) {
+        for (int i = 0; i < F64_NSUM; ++i) {
             double s = 0.0;
             for (int ww = 0; ww < NW; ++ww) s += sh->red[ww][i];
             if (i < D) sh->gth[i] = 0.5 * c.sf2 * s / sh->theta[i];
@@ -1108,6 +1149,11 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
 #endif
             else sh->gth[i] = 0.5 * s;
         }
+#ifdef GPSAT_F64_MEAN
+        double sa = 0.0;
+        for (int ww = 0; ww < 8; ++ww) sa += sh->red[ww][D + 2];
+        sh->gth[D + 2] = -sa;
+#endif
     }
     __syncthreads();
 }
@@ -1126,6 +1172,11 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
     for (int idx = c.tid; idx < c.Npad; idx += NT) {
 #pragma unroll
         for (int d = 0; d < D; ++d) lds_d[c.L.xsc + d * c.Npad + idx] = (idx < c.N) ? Xg[(size_t)idx * D + d] / sh->theta[d] : 0.0;
+#ifdef GPSAT_F64_MEAN
+        // the residual of THIS evaluation's c, from the observations in memory: nothing of an earlier c (or of the workgroup
+        // that ran the tile before a suspension) is read
+        lds_d[c.L.y + idx] = (idx < c.N) ? c.yg[idx] - sh->theta[D + 2] : 0.0;
+#endif
     }
     __syncthreads();
     phase_potrf<D, KN, TEAM>(c, want_grad CV_FINAL_WANTS_M(sh));
@@ -1240,7 +1291,7 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
             const int qa = BS * (pc0 + n) + c.g;
             if (c.q == 0 && va[n]) {
                 const double var = c.sf2 - vsum;
-                fm[qa] = msum; fv[qa] = var; yv[qa] = var + c.sn2;
+                fm[qa] = msum MEAN_ADD(theta[D + 2]); fv[qa] = var; yv[qa] = var + c.sn2;
             }
         }
     }
@@ -1453,6 +1504,29 @@ __device__ __forceinline__ void rq_predict_prior(const KernelArgs& A, int H, int
 }
 #endif
 
+#ifdef GPSAT_F64_MEAN
+// thread 0, behind opt_fresh_tile: that gives the LAST parameter GPflow's lower bound of the likelihood variance; here the
+// last parameter is c and the likelihood variance stands in front of it.  c is GPflow's unconstrained Parameter: without a
+// box it has the identity transform (box code 3: theta = u, any finite real value), with finite bounds the sigmoid box
+template <int D>
+__device__ __forceinline__ void mean_fresh_tile(Shared* sh) {
+    constexpr int iv = D + 1, ic = D + 2;
+    sh->shift[ic] = 0.0;
+    sh->shift[iv] = sh->box[iv] ? 0.0 : 1e-6;
+    if (!sh->box[ic]) sh->box[ic] = 3;
+    sh->u[ic] = u_of_theta(sh, ic, sh->theta[ic]);
+    sh->u[iv] = u_of_theta(sh, iv, sh->theta[iv]);
+}
+
+// all threads: the prior at theta0 as the predictions of a tile without observations: the mean is c
+template <int D>
+__device__ __forceinline__ void mean_predict_prior(const KernelArgs& A, int H, int t, int tid, long long p0, long long p1,
+                                                   double* f_mean, double* f_var, double* y_var) {
+    const double sf2 = A.theta0[(size_t)t * H + D], sn2 = A.theta0[(size_t)t * H + D + 1], cm = A.theta0[(size_t)t * H + D + 2];
+    for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = cm; f_var[q] = sf2; y_var[q] = sf2 + sn2; }
+}
+#endif
+
 template <int D, int KN>
 __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const KernelArgs A CV_KERNEL_PARAM) {
     constexpr int H = F64_NHYP;
@@ -1516,6 +1590,10 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
 #ifdef GPSAT_F64_RQ
         if (!resumed && c.tid == 0) rq_fresh_tile<D>(sh);
 #endif
+#ifdef GPSAT_F64_MEAN
+        if (!resumed && c.tid == 0) mean_fresh_tile<D>(sh);
+        c.yg = y + o0;
+#endif
         __syncthreads();
         const int seg_evals = sliced ? max(1, A.seg_cost / (NB * NB * NB)) : 0x7fffffff;
         bool suspended = false;
@@ -1552,7 +1630,7 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
 #endif
 }
 
-#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV) && !defined(GPSAT_F64_RQ)
+#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV) && !defined(GPSAT_F64_RQ) && !defined(GPSAT_F64_MEAN)
 // ---------------------------------------------------------------------------------------------
 // the team kernel: KernelArgs::team_size workgroups per tile (see "Teams" above).  Workgroup b is member b % G of team
 // b / G; the team's workspace is the slab of its member 0.  The owner pops tiles, runs the optimiser and, before every
@@ -1707,6 +1785,27 @@ static hipError_t launch_d_rq(const KernelArgs& a, int grid, size_t smem, hipStr
     hipLaunchKernelGGL((gp_tile_kernel_f64<D, 4>), dim3(grid), dim3(NT), smem, stream, a);
     return hipGetLastError();
 }
+#elif defined(GPSAT_F64_MEAN)
+template <int D, int KN>
+static hipError_t launch_one_mean(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
+    if (a.team_size > 1) return hipErrorInvalidValue;          // one workgroup per tile only
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, KN>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gp_tile_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a);
+    return hipGetLastError();
+}
+
+template <int D>
+static hipError_t launch_d_mean(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
+    switch (a.kernel) {
+        case 0: return launch_one_mean<D, 0>(a, grid, smem, stream);
+        case 1: return launch_one_mean<D, 1>(a, grid, smem, stream);
+        case 2: return launch_one_mean<D, 2>(a, grid, smem, stream);
+        case 3: return launch_one_mean<D, 3>(a, grid, smem, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
 #else
 template <int D, int KN>
 static hipError_t launch_one(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
@@ -1757,6 +1856,15 @@ hipError_t F64FN(launch_tiles_rq_f64)(int D, const KernelArgs& a, int grid, size
         case 1: return F64NS::launch_d_rq<1>(a, grid, smem, stream);
         case 2: return F64NS::launch_d_rq<2>(a, grid, smem, stream);
         case 3: return F64NS::launch_d_rq<3>(a, grid, smem, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+#elif defined(GPSAT_F64_MEAN)
+hipError_t F64FN(launch_tiles_mean_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
+    switch (D) {
+        case 1: return F64NS::launch_d_mean<1>(a, grid, smem, stream);
+        case 2: return F64NS::launch_d_mean<2>(a, grid, smem, stream);
+        case 3: return F64NS::launch_d_mean<3>(a, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -71,13 +71,22 @@ struct Shared {
 // ---------------------------------------------------------------------------------------------
 static __device__ inline double softplus_d(double x) { return log1p(exp(-fabs(x))) + fmax(x, 0.0); }
 
+// A build that defines GPSAT_OPT_IDENTITY has a third code, box 3: the identity, theta = u, for a parameter that may take any
+// finite real value (the constant mean of the fp64 tile kernel's -DGPSAT_F64_MEAN builds, which set the code themselves
+// behind opt_fresh_tile).  Without the define these functions are what they were.
 static __device__ __noinline__ double theta_of_u(const Shared* sh, int i, double u) {
+#ifdef GPSAT_OPT_IDENTITY
+    if (sh->box[i] == 3) return u;
+#endif
     if (sh->box[i] == 2) return exp(u);          // log transform (bounded L-BFGS-B in log space, gpsat_fit_predict_batch_ms)
     if (sh->box[i]) return sh->lo[i] + (sh->hi[i] - sh->lo[i]) / (1.0 + exp(-u));
     return softplus_d(u) + sh->shift[i];
 }
 
 static __device__ __noinline__ double u_of_theta(const Shared* sh, int i, double th) {
+#ifdef GPSAT_OPT_IDENTITY
+    if (sh->box[i] == 3) return th;
+#endif
     if (sh->box[i] == 2) return log(th);
     if (sh->box[i]) {
         const double lo = sh->lo[i], hi = sh->hi[i];
@@ -93,6 +102,9 @@ static __device__ __noinline__ double u_of_theta(const Shared* sh, int i, double
 }
 
 static __device__ inline double dtheta_du(const Shared* sh, int i, double th) {
+#ifdef GPSAT_OPT_IDENTITY
+    if (sh->box[i] == 3) return 1.0;
+#endif
     if (sh->box[i] == 2) return th;
     if (sh->box[i]) return (th - sh->lo[i]) * (sh->hi[i] - th) / (sh->hi[i] - sh->lo[i]);
     return -expm1(-(th - sh->shift[i]));

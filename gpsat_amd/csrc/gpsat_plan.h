@@ -154,6 +154,26 @@ bool plan_tiles(const PlanInput& in, TilePlan& p) {
     return true;
 }
 
+// gpsat_fit_predict_batch_mean's own checks (behind check_batch, which has seen T, D, dtype, kernel and the metadata pointers): a
+// pure function of host data like plan_tiles, reached by tests through its exported symbol.  GPSAT_OK, or GPSAT_EINVAL with the
+// reason in *why (a string literal).  GPSAT_MEAN_ZERO asks nothing of the batch: it is gpsat_fit_predict_batch.
+int check_mean(const gpsat_batch* b, const gpsat_mean* m, const char** why) {
+    *why = nullptr;
+    if (m->kind != GPSAT_MEAN_ZERO && m->kind != GPSAT_MEAN_CONSTANT) { *why = "mean: unknown kind (GPSAT_MEAN_ZERO or GPSAT_MEAN_CONSTANT)"; return GPSAT_EINVAL; }
+    for (int i = 0; i < 7; ++i)
+        if (m->reserved[i] != 0) { *why = "mean: reserved words must be 0"; return GPSAT_EINVAL; }
+    if (m->kind == GPSAT_MEAN_ZERO) return GPSAT_OK;
+    if (b->dtype != GPSAT_F64) { *why = "a constant mean (GPSAT_MEAN_CONSTANT) is built for GPSAT_F64 only"; return GPSAT_EINVAL; }
+    if (b->kernel == GPSAT_KERNEL_RQ) { *why = "a constant mean (GPSAT_MEAN_CONSTANT) is not built for GPSAT_KERNEL_RQ: H would be D + 4"; return GPSAT_EINVAL; }
+    if (b->D > 3) { *why = "a constant mean (GPSAT_MEAN_CONSTANT) is built for D <= 3: H = D + 3 parameters, at most 6"; return GPSAT_EINVAL; }
+    const int H = b->D + 3;
+    for (int t = 0; t < b->T; ++t) {
+        const double c0 = b->theta0[(size_t)t * H + H - 1];
+        if (!(c0 - c0 == 0.0)) { *why = "theta0 of the constant mean (the last parameter) must be finite"; return GPSAT_EINVAL; }
+    }
+    return GPSAT_OK;
+}
+
 // The memo of evaluations of the fp32 tile kernels (KernelArgs::memo, gpsat_kernels.hip): bytes of device memory a batch of T
 // tiles needs for it, 0 when the batch runs without one.  It serves the unbounded L-BFGS driver's line search only: no fp64
 // batch (the key would be the fp64 theta), no Adam, no multi-start, nothing without an optimisation; `off`: the developer

@@ -20,7 +20,7 @@ class GpsatError(RuntimeError):
 
 @dataclass
 class BatchResult:
-    theta: np.ndarray      # [T, H] learned parameters (l_1..l_D, kernel_variance, likelihood_variance[, alpha: RationalQuadratic])
+    theta: np.ndarray      # [T, H] learned parameters (l_1..l_D, kernel_variance, likelihood_variance[, alpha: RationalQuadratic | c: mean="constant"])
     nll: np.ndarray        # [T] objective = negative log marginal likelihood
     status: np.ndarray     # [T] see _lib.STATUS
     n_eval: np.ndarray     # [T] objective+gradient evaluations used by the optimiser
@@ -231,7 +231,7 @@ class Engine:
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
                           out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
-                          cv_refit=None) -> BatchResult:
+                          cv_refit=None, mean=None) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -260,7 +260,23 @@ class Engine:
         ``kernel="RationalQuadratic"``: one more hyper-parameter per tile, H = D + 3 with alpha last, so theta0 / lo / hi are
         (H,) or (T, H) and trainable is (H,); fp64 and D <= 3 only, with ``full_cov`` but without ``n_starts``, ``cv_fold``
         and ``cv_refit`` (the library refuses those with its own message).
+        ``mean="constant"`` (gpsat_fit_predict_batch_mean): a trainable constant mean c, GPflow's mean_functions.Constant --
+        y ~ N(c 1, K + sn2 I).  One more hyper-parameter per tile, H = D + 3 with c last and in the units of y, so theta0 / lo /
+        hi are (H,) or (T, H) and trainable is (H,); c is unconstrained with NaN bounds (any finite value) and boxed with finite
+        ones, ``f_mean`` includes it and a tile without observations predicts c of theta0.  fp64 and D <= 3 only, with
+        ``full_cov`` and either optimiser, but without ``n_starts``, ``cv_fold``, ``cv_refit`` and "RationalQuadratic".  None:
+        the zero-mean model, as ever.
         """
+        if mean not in L.MEAN_IDS:
+            raise GpsatError(f"mean {mean!r}: use None or 'constant'")
+        const_mean = L.MEAN_IDS[mean] == L.MEAN_CONSTANT
+        if const_mean:
+            for what, on in (("n_starts", n_starts is not None), ("cv_fold", cv_fold is not None),
+                             ("cv_refit", cv_refit is not None and cv_refit is not False),
+                             ("kernel='RationalQuadratic'", L.KERNEL_IDS.get(kernel, kernel) == L.KERNEL_RQ)):
+                if on:
+                    raise GpsatError(f"mean='constant' and {what} cannot be combined: the constant mean is built for the plain "
+                                     f"fit / predict call with a stationary kernel")
         refit = None
         if cv_refit is not None and cv_refit is not False:
             refit = cv_refit_options(cv_refit)
@@ -272,13 +288,15 @@ class Engine:
                 raise GpsatError("cv_refit and n_starts cannot be combined")
             if full_cov:
                 raise GpsatError("cv_refit and full_cov cannot be combined")
-        H = L.n_hyper(kernel, D)
+        H = L.n_hyper(kernel, D, mean)
+        last = "c: the constant mean" if const_mean else "alpha"
         if H == D + 3:
             for pname, a in (("theta0", theta0), ("lo", lo), ("hi", hi), ("trainable", trainable)):
                 shp = None if a is None else np.shape(a)
                 if shp is not None and (len(shp) not in ((1,) if pname == "trainable" else (1, 2)) or shp[-1] != H):
-                    raise GpsatError(f"{pname} has shape {shp}: kernel {kernel!r} with D = {D} has H = D + 3 = {H} parameters per "
-                                     f"tile (lengthscales, kernel_variance, likelihood_variance, alpha), so (H,)"
+                    raise GpsatError(f"{pname} has shape {shp}: kernel {kernel!r}" + (" with mean='constant'" if const_mean else "")
+                                     + f" with D = {D} has H = D + 3 = {H} parameters per "
+                                     f"tile (lengthscales, kernel_variance, likelihood_variance, {last}), so (H,)"
                                      + ("" if pname == "trainable" else " or (T, H)") + " is expected")
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, H)
         obs_off, pred_off = meta[0]
@@ -356,6 +374,13 @@ class Engine:
             f_start = np.full((T, max(int(n_starts), 1)), np.nan)
             ms.starts, ms.f_start = _ptr(st), _ptr(f_start)
             rc = self._lib.gpsat_fit_predict_batch_ms(self._h, C.byref(b), C.byref(ms))
+        elif const_mean:
+            name = "gpsat_fit_predict_batch_mean"
+            if not hasattr(self._lib, name):
+                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_mean (trainable constant mean)")
+            mn = L.GpsatMean()
+            mn.kind = L.MEAN_CONSTANT
+            rc = self._lib.gpsat_fit_predict_batch_mean(self._h, C.byref(b), C.byref(mn))
         else:
             rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
         return self._result(rc, name, res, preds, sumP, f_start=f_start,

@@ -59,6 +59,11 @@ RationalQuadratic experts (``init_params.kernel == "RationalQuadratic"``, exact 
 coordinate columns): a fourth parameter, ``kernel_alpha`` (``init_params.kernel_kwargs.alpha``, default 1), with a table of its
 own that is stored by default, read by ``load_params`` (file or direct value), carried in the ``previous`` running mean and
 accepted by ``constraints``.  Not combined with a replacement model, ``cv`` or SGPR.
+Experts with a trainable constant mean (``init_params.mean_function == "Constant"``, ``init_params.mean_func_kwargs.c``,
+default 0; GPflow's mean_functions.Constant) are the same kind of profile -- one extra named parameter, here the table
+``mean_constant`` (in scaled observation units), under the same rules: fp64, at most 3 coordinate columns, stored, loaded,
+averaged and constrained like the others; not combined with a replacement model, ``cv``, SGPR or RationalQuadratic
+(DESIGN.md section 15).  ``mean_function`` None and "Zero" are the zero mean; other names are not built.
 ``replacement_*`` model settings for tiles below ``replacement_threshold`` observations are honoured (one engine call
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
@@ -113,6 +118,19 @@ from .models import (HipGPRModel, HipSGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND,
 _COMPS = {">=": np.greater_equal, ">": np.greater, "==": np.equal, "<": np.less, "<=": np.less_equal}
 PARAM_NAMES = ["lengthscales", "kernel_variance", "likelihood_variance"]
 RQ_KERNEL = "RationalQuadratic"                 # its experts have a fourth parameter table, kernel_alpha (H = D + 3)
+
+
+def _extra_param(init_params):
+    """A profile with ONE extra named parameter behind the reference's three (H = D + 3): (table name, what asks for it in
+    a message), or None.  RationalQuadratic's alpha, or the constant of mean_function "Constant"."""
+    ip = init_params or {}
+    mf = ip.get("mean_function")
+    if mf is not None and (not isinstance(mf, str) or mf not in ("Zero", "Constant")):
+        raise NotImplementedError(f"init_params.mean_function {mf!r}: None, 'Zero' and 'Constant' are built")
+    rq, const = ip.get("kernel") == RQ_KERNEL, mf == "Constant"
+    if rq and const:
+        raise NotImplementedError(f"kernel '{RQ_KERNEL}' and mean_function 'Constant' cannot be combined: D + 4 parameters")
+    return ("kernel_alpha", f"kernel '{RQ_KERNEL}'") if rq else ("mean_constant", "mean_function 'Constant'") if const else None
 MODEL_NAME = f"{HipGPRModel.__module__}.{HipGPRModel.__name__}"[:64]
 SGPR_MODEL_NAME = f"{HipSGPRModel.__module__}.{HipSGPRModel.__name__}"[:64]
 SGPR_INIT_KEYS = ("num_inducing_points", "inducing_seed")
@@ -844,27 +862,30 @@ class BatchedLocalExpertOI:
         if name not in ("HipGPRModel", "GPflowGPRModel") + SGPR_MODEL_NAMES:
             raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP and SGPR experts only")
         self.sgpr = name in SGPR_MODEL_NAMES
-        # RationalQuadratic experts: one more parameter per tile (kernel_alpha, last), exact GP in fp64 and D <= 3 only
-        self.rq = (model_config.get("init_params") or {}).get("kernel") == RQ_KERNEL
-        self.param_names = PARAM_NAMES + ["kernel_alpha"] if self.rq else PARAM_NAMES
+        # RationalQuadratic experts and experts with a constant mean: one more parameter per tile (kernel_alpha /
+        # mean_constant, last), exact GP in fp64 and D <= 3 only
+        self.extra = _extra_param(model_config.get("init_params"))
+        extra, who = self.extra or (None, None)
+        self.rq = extra == "kernel_alpha"
+        self.param_names = PARAM_NAMES + [extra] if extra else PARAM_NAMES
         self.H = len(data_config["coords_col"]) + len(self.param_names) - 1
-        if self.rq and self.sgpr:
-            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built for exact-GP experts only, not for SGPR")
-        # dtype None: fp32 for exact-GP experts, fp64 for sparse and RationalQuadratic ones (built in fp64 only -- an explicit
-        # fp32 is refused)
+        if extra and self.sgpr:
+            raise NotImplementedError(f"{who} is built for exact-GP experts only, not for SGPR")
+        # dtype None: fp32 for exact-GP experts, fp64 for sparse ones and those with an extra parameter (built in fp64 only --
+        # an explicit fp32 is refused)
         if dtype is None:
-            dtype = "f64" if (self.sgpr or self.rq) else "f32"
+            dtype = "f64" if (self.sgpr or extra) else "f32"
         if dtype not in DTYPES:
             raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
         if self.sgpr and dtype != "f64":
             raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
-        if self.rq and dtype != "f64":
-            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built in fp64 only: dtype must be None or 'f64'")
-        if self.rq and len(data_config["coords_col"]) > 3:
-            raise NotImplementedError(f"kernel '{RQ_KERNEL}' is built for 1..3 coordinate columns (D + 3 <= 6 parameters), "
+        if extra and dtype != "f64":
+            raise NotImplementedError(f"{who} is built in fp64 only: dtype must be None or 'f64'")
+        if extra and len(data_config["coords_col"]) > 3:
+            raise NotImplementedError(f"{who} is built for 1..3 coordinate columns (D + 3 <= 6 parameters), "
                                       f"got {len(data_config['coords_col'])}")
-        if self.rq and cv is not None:
-            raise NotImplementedError(f"cv: held-out predictions are not built for kernel '{RQ_KERNEL}'")
+        if extra and cv is not None:
+            raise NotImplementedError(f"cv: held-out predictions are not built for {who}")
         self.dtype = dtype
         # held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with equal
         # values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
@@ -958,9 +979,10 @@ class BatchedLocalExpertOI:
                 raise NotImplementedError(f"replacement_model '{rname}': the batched backend builds the exact-GP expert only")
             rip = model_config.get("replacement_init_params")
             rco = model_config.get("replacement_constraints")
-            if self.rq or (rip or {}).get("kernel") == RQ_KERNEL:
-                raise NotImplementedError(f"kernel '{RQ_KERNEL}' and a replacement model cannot be combined: the two profiles of "
-                                          f"a run share one parameter layout, and this kernel has a parameter more")
+            for ex in (self.extra, _extra_param(rip)):
+                if ex:
+                    raise NotImplementedError(f"{ex[1]} and a replacement model cannot be combined: the two profiles of "
+                                              f"a run share one parameter layout, and this one has a parameter more")
             main_ip = {k: v for k, v in self.init_params.items() if k not in SGPR_INIT_KEYS}
             self.profiles["replacement"] = dict(
                 sgpr=False,
@@ -1015,8 +1037,8 @@ class BatchedLocalExpertOI:
         """(first column, width) of every named parameter in a tile's theta."""
         D = len(self.coords_col)
         slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
-        if self.rq:
-            slots["kernel_alpha"] = (D + 2, 1)
+        if self.extra:
+            slots[self.extra[0]] = (D + 2, 1)
         return slots
 
     def _template(self, pf, optimise, predict) -> _Profile:
@@ -1666,6 +1688,8 @@ class _ShardRunner:
         kw = dict(D=len(self.oi.coords_col), obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"], Xs=pk["Xs"], lo=p.lo[ids],
                   hi=p.hi[ids], trainable=pf.trainable, kernel=pf.kernel, optimiser=pf.optimiser, max_iter=pf.max_iter,
                   **pf.eng_kw)
+        if self.oi.extra and self.oi.extra[0] == "mean_constant":
+            kw["mean"] = "constant"
         eng_ = self.free_engines.get()
         try:
             te = time.perf_counter()

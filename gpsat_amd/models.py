@@ -10,7 +10,11 @@ kernels through the C ABI (include/gpsat_hip.h).  There is no CPU fallback.
 Differences that are deliberate and documented in DESIGN.md:
   * compute dtype is fp32 on the GPU by default, ``dtype="f64"`` selects the fp64 kernels (host-side scaling /
     constraints are always fp64 like the reference);
-  * ``mean_function`` and custom likelihoods are not built (NotImplementedError);
+  * of the mean functions, ``mean_function="Constant"`` is built (a trainable constant c, GPflow's
+    mean_functions.Constant, ``mean_func_kwargs={"c": ...}``; fp64, at most 3 input dimensions, not with
+    "RationalQuadratic"): one more parameter, ``mean_constant``, with its getter, setter and constraints, in the model's
+    scaled observation units.  Other mean functions and custom likelihoods are not built
+    (NotImplementedError);
   * no TensorFlow import, no per-construction device probe (the engine knows its device).
 """
 from __future__ import annotations
@@ -122,8 +126,13 @@ class HipGPRModel:
         assert kernel is not None, "kernel was not provided"
         if not isinstance(kernel, str) or kernel not in L.KERNEL_IDS:
             raise NotImplementedError(f"kernel {kernel!r}: this backend builds {sorted(L.KERNEL_IDS)}")
-        if mean_function is not None or likelihood is not None:
+        if likelihood is not None:
             raise NotImplementedError("mean_function / custom likelihood are not built in the HIP backend")
+        if mean_function is not None and (not isinstance(mean_function, str) or mean_function not in ("Zero", "Constant")):
+            raise NotImplementedError(f"mean_function {mean_function!r}: the HIP backend builds None, 'Zero' and 'Constant' "
+                                      f"(Linear and the others would need 2 D + 3 > 6 parameters)")
+        # a trainable constant mean (gpflow.mean_functions.Constant): one more parameter, c, last in the device's vector
+        self._mean = mean_function == "Constant"
         self.kernel = kernel
         if dtype not in ("f32", "f64"):
             raise ValueError("dtype must be 'f32' or 'f64'")
@@ -138,12 +147,24 @@ class HipGPRModel:
             raise NotImplementedError(f"kernel {kernel!r} is built in fp64 only: pass dtype='f64'")
         if self._rq and D > 3:
             raise NotImplementedError(f"kernel {kernel!r} is built for 1..3 input dimensions (D + 3 <= 6 parameters), got D = {D}")
+        if self._mean:
+            why = ("is built in fp64 only: pass dtype='f64'" if dtype != "f64" else
+                   f"is built for 1..3 input dimensions (D + 3 <= 6 parameters), got D = {D}" if D > 3 else
+                   f"is not built for kernel {kernel!r} (D + 4 parameters)" if self._rq else None)
+            if why:
+                raise NotImplementedError(f"mean_function 'Constant' {why}")
+            mk = dict(mean_func_kwargs or {})
+            if set(mk) - {"c"}:
+                raise NotImplementedError(f"mean_func_kwargs {sorted(set(mk) - {'c'})}: 'Constant' takes 'c' only")
+            c0 = np.asarray(0.0 if mk.get("c") is None else mk["c"], dtype=np.float64).reshape(-1)   # GPflow: c=None is 0
+            assert len(c0) == 1, f"mean_func_kwargs['c'] must be a number or a sequence of one element, got {len(c0)}"
         kk = dict(kernel_kwargs or {})
         ls = np.broadcast_to(np.asarray(kk.get("lengthscales", np.ones(D)), dtype=np.float64), (D,)).copy()
         self._theta = np.concatenate([ls, [float(kk.get("variance", 1.0))],
                                       [1.0 if noise_variance is None else float(noise_variance)],
-                                      [float(kk.get("alpha", 1.0))] if self._rq else []])       # GPflow: alpha = 1
-        H = L.n_hyper(kernel, D)
+                                      [float(kk.get("alpha", 1.0))] if self._rq else [],        # GPflow: alpha = 1
+                                      [float(c0[0])] if self._mean else []])
+        H = L.n_hyper(kernel, D, "constant" if self._mean else None)
         self._lo = np.full(H, np.nan)
         self._hi = np.full(H, np.nan)
         self._trainable = np.ones(H, dtype=bool)
@@ -166,8 +187,9 @@ class HipGPRModel:
     @property
     def param_names(self) -> List[str]:
         # the reference's three names (gpflow_models.py:179-184) would lose alpha in params_to_store and load_params
+        # ... and likewise the constant of mean_function="Constant"
         names = ["lengthscales", "kernel_variance", "likelihood_variance"]
-        return names + ["kernel_alpha"] if self._rq else names
+        return names + (["kernel_alpha"] if self._rq else []) + (["mean_constant"] if self._mean else [])
 
     def get_parameters(self, *args, return_dict=True):
         # base_model.py:370-403
@@ -200,6 +222,22 @@ class HipGPRModel:
 
     def get_likelihood_variance(self) -> float:
         return float(self._theta[self.D + 1])
+
+    def _need_mean(self):
+        if not self._mean:
+            raise AttributeError("mean_constant is the parameter of mean_function='Constant', this model has a zero mean")
+
+    def get_mean_constant(self) -> float:
+        """c of the constant mean, in the model's scaled observation units, (y - obs_mean) / obs_scale."""
+        self._need_mean()
+        return float(self._theta[self.D + 2])
+
+    def set_mean_constant(self, mean_constant):
+        self._need_mean()
+        v = np.asarray(mean_constant, dtype=np.float64).reshape(-1)
+        assert len(v) == 1, f"set_mean_constant expected a float or an array of one element, got {len(v)}"
+        assert np.isfinite(v[0]), "mean_constant must be finite"
+        self._theta[self.D + 2] = float(v[0])
 
     def _need_rq(self):
         if not self._rq:
@@ -245,7 +283,8 @@ class HipGPRModel:
     def _slice(self, name):
         D = self.D
         return {"lengthscales": slice(0, D), "kernel_variance": slice(D, D + 1),
-                "likelihood_variance": slice(D + 1, D + 2), "kernel_alpha": slice(D + 2, D + 3)}[name]
+                "likelihood_variance": slice(D + 1, D + 2), "kernel_alpha": slice(D + 2, D + 3),
+                "mean_constant": slice(D + 2, D + 3)}[name]
 
     def _set_param_constraints(self, name, low, high, move_within_tol=True, tol=1e-8, scale=False,
                                scale_magnitude=None):
@@ -286,6 +325,15 @@ class HipGPRModel:
         self._need_rq()
         self._set_param_constraints("kernel_alpha", low, high, move_within_tol, tol, scale, scale_magnitude)
 
+    def set_mean_constant_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
+        """A box for c (without one it is unconstrained, as GPflow's Constant.c).  ``scale`` divides bounds by the COORDINATE
+        scale, which means nothing for a level of the observations: refused."""
+        self._need_mean()
+        if scale:
+            raise NotImplementedError("set_mean_constant_constraints: scale=True divides by the coordinate scale, which "
+                                      "does not apply to mean_constant; give the bounds in scaled observation units")
+        self._set_param_constraints("mean_constant", low, high, move_within_tol, tol, False, None)
+
     # -- the three device calls
     def _run(self, *, optimiser, max_iter=0, pred_coords=None, **opt_kwargs):
         N, D = self.coords.shape
@@ -295,7 +343,7 @@ class HipGPRModel:
             dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0],
             pred_off=np.array([0, P]), Xs=Xs, theta0=self._theta[None, :], lo=self._lo[None, :],
             hi=self._hi[None, :], trainable=self._trainable, kernel=self.kernel, optimiser=optimiser,
-            max_iter=max_iter, **opt_kwargs)
+            max_iter=max_iter, **({"mean": "constant"} if self._mean else {}), **opt_kwargs)
 
     def _fix_hyperparameters(self, params_list):
         # gpflow_models.py:275-288
@@ -389,6 +437,8 @@ class HipGPRModel:
         N, D = self.coords.shape
         if self._rq:
             raise NotImplementedError(f"held-out predictions are not built for kernel {self.kernel!r}")
+        if self._mean:
+            raise NotImplementedError("held-out predictions are not built for mean_function='Constant'")
         if refit:
             return self._cross_validate_refit(fold, **refit_kwargs)
         if refit_kwargs:
@@ -459,6 +509,8 @@ class HipSGPRModel(HipGPRModel):
             raise NotImplementedError("HipSGPRModel is built in fp64 only (dtype='f64')")
         if kernel == "RationalQuadratic":
             raise NotImplementedError("kernel 'RationalQuadratic' is built for exact experts (HipGPRModel) only, not for SGPR")
+        if mean_function is not None:
+            raise NotImplementedError("mean_function is not built for sparse experts (HipSGPRModel)")
         super().__init__(data=data, coords_col=coords_col, obs_col=obs_col, coords=coords, obs=obs,
                          coords_scale=coords_scale, obs_scale=obs_scale, obs_mean=obs_mean, verbose=verbose,
                          kernel=kernel, kernel_kwargs=kernel_kwargs, mean_function=mean_function,

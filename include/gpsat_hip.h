@@ -191,6 +191,38 @@ typedef struct gpsat_multistart {
 int gpsat_fit_predict_batch_ms(gpsat_handle *h, const gpsat_batch *b, const gpsat_multistart *ms);
 
 /*
+ * A trainable constant mean (GPflow's gpflow.mean_functions.Constant, the reference's mean_function="Constant",
+ * GPSat/models/gpflow_models.py:143-157): the extension of gpsat_fit_predict_batch_mean.  Callers detect it by the presence
+ * of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ *
+ *     y ~ N(c 1, K_theta + sn2 I),   nll(theta, c; y) = nll_zero-mean(theta; y - c 1),   dnll/dc = -sum(K_y^-1 (y - c 1)),
+ *     f*(x) = c + k*(x)^T K_y^-1 (y - c 1);  f_var, y_var and f_cov are those of the zero-mean model.
+ *
+ * GPSAT_MEAN_CONSTANT: one more parameter per tile, behind the others (H = D + 3 = gpsat_n_hyper_mean, no other index moves):
+ *     theta = (lengthscale_0 .. lengthscale_{D-1}, kernel_variance, likelihood_variance, c)
+ * in theta0, lo, hi, trainable, theta and grad.  c is unconstrained -- any finite value, zero and negatives included --
+ * when its bounds are NaN (the identity transform, GPflow's plain Parameter), and boxed like every parameter when lo / hi
+ * are finite.  A tile without observations predicts the prior: f_mean = c of theta0.  Built for GPSAT_F64, the kernels
+ * GPSAT_KERNEL_RBF .. GPSAT_KERNEL_MATERN52 and D <= 3, one workgroup per tile, with both optimisers and f_cov.
+ * GPSAT_MEAN_ZERO is gpsat_fit_predict_batch itself and returns the same bits.
+ */
+#define GPSAT_MEAN_ZERO     0
+#define GPSAT_MEAN_CONSTANT 1
+typedef struct gpsat_mean {
+    int32_t kind;              /* GPSAT_MEAN_*                                                */
+    int32_t reserved[7];       /* must be 0                                                   */
+} gpsat_mean;                  /* 32 bytes */
+
+/* Hyper-parameters per tile with a mean: D + 3 for GPSAT_MEAN_CONSTANT with a stationary kernel (not GPSAT_KERNEL_RQ) and
+ * D <= 3; gpsat_n_hyper(kernel, D) for GPSAT_MEAN_ZERO; 0 for everything else. */
+int gpsat_n_hyper_mean(int kernel, int D, int mean_kind);
+
+/* as gpsat_fit_predict_batch, with the mean above.  GPSAT_EINVAL (with a message that names the reason; the handle stays
+ * usable) for GPSAT_MEAN_CONSTANT with GPSAT_F32, D = 4 or GPSAT_KERNEL_RQ, for an unknown kind, non-zero reserved words
+ * and a non-finite theta0 of c. */
+int gpsat_fit_predict_batch_mean(gpsat_handle *h, const gpsat_batch *b, const gpsat_mean *m);
+
+/*
  * Held-out (cross-validation) predictions from every tile's own factor: the extension of gpsat_fit_predict_batch_cv
  * (fp64 only).  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
  *
