@@ -635,9 +635,11 @@ struct DenseJob {
 int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, LaunchReport& r) {
     const gpsat_batch* b = j.b;
     const BatchDims& d = j.dims;
-    const bool f64 = b->dtype == GPSAT_F64, rq = b->kernel == GPSAT_KERNEL_RQ, mean = j.mean == GPSAT_MEAN_CONSTANT;
+    const bool f64 = b->dtype == GPSAT_F64;
+    const gpsat::F64Variant variant = j.cv ? gpsat::CV : b->kernel == GPSAT_KERNEL_RQ ? gpsat::RQ
+                                      : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : gpsat::PLAIN;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
-                           h->num_cu, h->wg_per_cu, solo || j.cv || rq || mean, unsliced, read_dev_knobs()};     // held-out, RQ, mean: one workgroup per tile
+                           h->num_cu, h->wg_per_cu, solo || variant != gpsat::PLAIN, unsliced, read_dev_knobs()};     // a variant: one workgroup per tile
     gpsat::TilePlan p;
     if (!gpsat::plan_tiles(in, p)) return fail(GPSAT_EINVAL, "tile too large for LDS");
     Staged s;
@@ -659,11 +661,10 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if (j.ms_on && (rc = setup_multistart(h, b, j.ms->n_starts, j.theta0, j.starts_clipped, a))) return rc;
     if ((rc = setup_deferred(h, p, a))) return rc;
     if ((rc = setup_eval_cache(h, b, j.ms_on, a))) return rc;
+    const auto launch = gpsat::builds[p.build].launch_variant[variant];
+    if (!launch) return fail(GPSAT_EINVAL, variant == gpsat::CV ? "held-out predictions: no kernel in this build" : "no kernel for this model in this build");
     gpsat::CvArgs ca;
-    if (j.cv) {
-        if (!gpsat::builds[p.build].launch_cv) return fail(GPSAT_EINVAL, "held-out predictions: no kernel in this build");
-        if ((rc = stage_cv(h, b, j.cv, d, j.cv_tables, ca))) return rc;
-    }
+    if (j.cv && (rc = stage_cv(h, b, j.cv, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
     if (h->dump_dev && !f64) {
         const size_t need = ((size_t)p.NBmax * p.NBmax + p.NBmax) * 1024 + 2 * (size_t)p.NBmax * 32 + 16 + 8 * 1024;
@@ -677,10 +678,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     a.prof = static_cast<unsigned long long*>(h->prof.p);
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    if (j.cv) HIP_TRY(gpsat::builds[p.build].launch_cv(b->D, a, ca, p.grid, p.smem, h->stream));
-    else if (rq) HIP_TRY((p.build == gpsat::BUILD_F64_W4 ? gpsat::launch_tiles_rq_f64_w4 : gpsat::launch_tiles_rq_f64)(b->D, a, p.grid, p.smem, h->stream));
-    else if (mean) HIP_TRY((p.build == gpsat::BUILD_F64_W4 ? gpsat::launch_tiles_mean_f64_w4 : gpsat::launch_tiles_mean_f64)(b->D, a, p.grid, p.smem, h->stream));
-    else HIP_TRY(gpsat::builds[p.build].launch(b->D, a, p.grid, p.smem, h->stream));
+    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, d, ca))) return rc;

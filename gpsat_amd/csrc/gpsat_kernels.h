@@ -124,21 +124,20 @@ size_t shared_bytes(int D, int NBmax);
 size_t shared_bytes_f64(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64(int NBmax, int PCcov);
 int state_words_f64();
-hipError_t launch_tiles_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
-hipError_t launch_tiles_cv_f64(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
 // 4-wave build (gpsat_kernels_f64.hip -DGPSAT_F64_W4): two workgroups per CU for tiles whose LDS fits twice
 size_t shared_bytes_f64_w4(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
-hipError_t launch_tiles_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
-hipError_t launch_tiles_cv_f64_w4(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
-// the same tile loop for the RationalQuadratic covariance function (-DGPSAT_F64_RQ: kernel 4, D = 1..3, H = D + 3), one
-// workgroup per tile; LDS, workspace and state words are those of the build of the same wave count
-hipError_t launch_tiles_rq_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
-hipError_t launch_tiles_rq_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
-// ... and for a trainable constant mean (-DGPSAT_F64_MEAN: kernels 0..3, D = 1..3, H = D + 3 with c last), by the same rules
-hipError_t launch_tiles_mean_f64(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
-hipError_t launch_tiles_mean_f64_w4(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
+// The variants of the fp64 tile loop (the table at the top of gpsat_kernels_f64.hip), launch_tiles_f64[_variant][_w4], one
+// signature: `cv` is null unless the variant is cv.  A (D, a.kernel, a.team_size) a variant does not have: hipErrorInvalidValue.
+//   plain  kernels 0..3, D = 1..4, H = D + 2; teams in the 8-wave build
+//   cv     the same with the held-out phase (gpsat_fit_predict_batch_cv), one workgroup per tile
+//   rq     the RationalQuadratic covariance function: kernel 4, D = 1..3, H = D + 3, one workgroup per tile
+//   mean   a trainable constant mean: kernels 0..3, D = 1..3, H = D + 3 with c last, one workgroup per tile
+// LDS, workspace and state words of every variant are those of the build of the same wave count.
+typedef hipError_t F64Launch(int D, const KernelArgs& a, const CvArgs* cv, int grid, size_t smem, hipStream_t stream);
+F64Launch launch_tiles_f64, launch_tiles_f64_w4, launch_tiles_f64_cv, launch_tiles_f64_cv_w4;
+F64Launch launch_tiles_f64_rq, launch_tiles_f64_rq_w4, launch_tiles_f64_mean, launch_tiles_f64_mean_w4;
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

@@ -17,100 +17,93 @@
 #include "gpsat_ring.h"
 
 namespace gpsat {
-// Two builds are linked (as for the fp32 kernels): the default, 8 waves per workgroup and one workgroup per CU, and
-// -DGPSAT_F64_W4, 4 waves and two workgroups per CU for tiles whose LDS fits twice (a second TILE per CU overlaps the
-// serial diagonal work of the first).
-#ifdef GPSAT_F64_W4
-#define GPSAT_F64_NW 4
-#define F64NS f64k4
-#define F64FN(name) name##_w4
-#define F64_MIN_WG 2
-#else
-#define F64NS f64k
-#define F64FN(name) name
-#define F64_MIN_WG 1
+// ---- which object this is ---------------------------------------------------------------------
+// The file is compiled eight times: with 8 waves per workgroup and one workgroup per CU (the default) or, -DGPSAT_F64_W4,
+// with 4 waves and two workgroups per CU for tiles whose LDS fits twice (a second TILE per CU overlaps the serial diagonal
+// work of the first) -- and each of the two as one VARIANT of the one-workgroup-per-tile kernel: plain, or with one of
+// -DGPSAT_F64_CV, -DGPSAT_F64_RQ, -DGPSAT_F64_MEAN.  A variant is one row of the table below: the row becomes the constants
+// CV, MEAN, KN_SET and D_MAX, the templates ask them with `if constexpr`, and an object instantiates
+// gp_tile_kernel_f64<D, KN> for the row's D and KN only, in the row's namespace, behind the row's one exported entry point.
+// A new variant is a new row and the `if constexpr` that reads its constant.  Beyond this block the preprocessor sees a
+// variant in three places: the kernel's parameter list (cv), the host's sizing functions at the end of the file (plain),
+// and GPSAT_OPT_IDENTITY below (mean), which gpsat_opt.h asks with #ifdef.
+//   plain  gpsat_fit_predict_batch: the four stationary kernels, H = D + 2, theta = (l_0 .. l_{D-1}, kernel variance,
+//          likelihood variance).  The only variant with the team kernel (8 waves) and the host's sizing functions.
+//   cv     held-out predictions (gpsat_fit_predict_batch_cv): phase_cv behind every tile's prediction; the final evaluation
+//          leaves L^-1 and alpha behind for it.  The kernel has one more parameter, CvArgs.
+//   rq     the RationalQuadratic covariance function (GPSAT_KERNEL_RQ = KN 4, gpsat_kfun_rq_f64.h), whose shape parameter
+//          alpha is one more trainable hyper-parameter: H = D + 3, theta = (.., likelihood variance, alpha).  Needs no
+//          constant: the templates ask `KN == 4`.
+//   mean   a trainable constant mean (GPflow's mean_functions.Constant, gpsat_fit_predict_batch_mean): y ~ N(c 1, K + sn2 I),
+//          H = D + 3, theta = (.., likelihood variance, c).  Every evaluation works on the residual y - c of ITS c;
+//          dNLL/dc = -sum(alpha); c is added to the predicted mean.  c has the identity transform unless it is boxed
+//          (GPSAT_OPT_IDENTITY in gpsat_opt.h, defined for this variant only).
+//                         namespace         entry point             sizing,                  kernels   D up
+//                         8 / 4 waves       (+ _w4)                 teams   CV     MEAN      (bit KN)  to
+#define F64_VARIANT_plain  f64k,   f64k4,    launch_tiles_f64,       true,   false, false,    0x0f,     4
+#define F64_VARIANT_cv     f64kcv, f64k4cv,  launch_tiles_f64_cv,    false,  true,  false,    0x0f,     4
+#define F64_VARIANT_rq     f64krq, f64k4rq,  launch_tiles_f64_rq,    false,  false, false,    0x10,     3
+#define F64_VARIANT_mean   f64kmn, f64k4mn,  launch_tiles_f64_mean,  false,  false, true,     0x0f,     3
+#ifndef GPSAT_F64_CV
+#define GPSAT_F64_CV 0
 #endif
-// -DGPSAT_F64_CV compiles the one-workgroup-per-tile kernel of either build once more, with the held-out phase (phase_cv)
-// behind every tile's prediction, into objects of their own that export launch_tiles_cv_f64[_w4] only.  Everything the flag
-// adds stands behind these macros, so that without it the translation unit is, token for token, what it was before the
-// held-out phase existed: the kernels of gpsat_fit_predict_batch are compiled from unchanged source.
-#ifdef GPSAT_F64_CV
-#undef F64NS
-#ifdef GPSAT_F64_W4
-#define F64NS f64k4cv
-#else
-#define F64NS f64kcv
-#endif
-#define CV_KERNEL_PARAM , const CvArgs cvA
-#define CV_FINAL_WANTS_M(sh_) || ((sh_)->phase == PH_FINAL)      /* the final evaluation leaves L^-1 and alpha behind */
-#else
-#define CV_KERNEL_PARAM
-#define CV_FINAL_WANTS_M(sh_)
-#endif
-// -DGPSAT_F64_RQ compiles the one-workgroup-per-tile kernel of either build once more for the RationalQuadratic covariance
-// function (GPSAT_KERNEL_RQ), whose shape parameter alpha is one more trainable hyper-parameter: H = D + 3, theta =
-// (l_0 .. l_{D-1}, kernel variance, likelihood variance, alpha), D = 1..3.  Objects of their own that export
-// launch_tiles_rq_f64[_w4] only.  As with GPSAT_F64_CV, everything the flag adds stands behind these macros: without it the
-// translation unit is, token for token, what it was before.
-#ifdef GPSAT_F64_RQ
-#ifdef GPSAT_F64_CV
-#error "GPSAT_F64_RQ and GPSAT_F64_CV are builds of their own"
-#endif
-#undef F64NS
-#ifdef GPSAT_F64_W4
-#define F64NS f64k4rq
-#else
-#define F64NS f64krq
-#endif
-#define F64_NHYP D + 3                                    /* hyper-parameters of a tile, in expressions of the templates */
-#define F64_NSUM D + 3                                    /* partial sums per lane an item of the gradient phase leaves */
-#define RQ_ARG(x_) , x_
-#define KFUN_C(c_, r2_, kf_, gg_) double ga; kfun_rq((c_).rqa, (c_).rqh, r2_, kf_, gg_, ga)
-#define KFUN_T(th_, r2_, kf_, gg_) double ga; kfun_rq((th_)[D + 2], 0.5 / (th_)[D + 2], r2_, kf_, gg_, ga)
-#define TILE_PREDICT_PRIOR rq_predict_prior<D>
-#else
-#define RQ_ARG(x_)
-#define KFUN_C(c_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
-#define KFUN_T(th_, r2_, kf_, gg_) kfun<KN>(r2_, kf_, gg_)
-#define F64_NSUM D + 2
-#endif
-// -DGPSAT_F64_MEAN compiles the one-workgroup-per-tile kernel of either build once more for a trainable constant mean
-// (GPflow's mean_functions.Constant, gpsat_fit_predict_batch_mean): y ~ N(c 1, K + sn2 I) with the four stationary kernels,
-// H = D + 3, theta = (l_0 .. l_{D-1}, kernel variance, likelihood variance, c), D = 1..3.  Every evaluation works on the
-// residual y - c of ITS c; dNLL/dc = -sum(alpha); c is added to the predicted mean.  c has the identity transform unless it
-// is boxed (GPSAT_OPT_IDENTITY in gpsat_opt.h, defined for these builds only).  Objects of their own that export
-// launch_tiles_mean_f64[_w4] only; without the flag the translation unit is, token for token, what it was before.
-#ifdef GPSAT_F64_MEAN
-#if defined(GPSAT_F64_CV) || defined(GPSAT_F64_RQ)
-#error "GPSAT_F64_MEAN, GPSAT_F64_RQ and GPSAT_F64_CV are builds of their own"
-#endif
-#undef F64NS
-#ifdef GPSAT_F64_W4
-#define F64NS f64k4mn
-#else
-#define F64NS f64kmn
-#endif
-#define GPSAT_OPT_IDENTITY
-#define F64_NHYP D + 3
-#define TILE_PREDICT_PRIOR mean_predict_prior<D>
-#define MEAN_ADD(x_) + (x_)
-#elif !defined(GPSAT_F64_RQ)
-#define F64_NHYP D + 2
-#define TILE_PREDICT_PRIOR tile_predict_prior
+#ifndef GPSAT_F64_RQ
+#define GPSAT_F64_RQ 0
 #endif
 #ifndef GPSAT_F64_MEAN
-#define MEAN_ADD(x_)
+#define GPSAT_F64_MEAN 0
+#endif
+// A variant adds ONE thing to the plain kernel; no combination is built, dispatched or tested.
+static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN <= 1, "GPSAT_F64_CV, GPSAT_F64_RQ and GPSAT_F64_MEAN are builds of their own");
+#if GPSAT_F64_CV
+#define F64_VARIANT F64_VARIANT_cv
+#elif GPSAT_F64_RQ
+#define F64_VARIANT F64_VARIANT_rq
+#elif GPSAT_F64_MEAN
+#define F64_VARIANT F64_VARIANT_mean
+#else
+#define F64_VARIANT F64_VARIANT_plain
+#endif
+// F64_ROW(m): m(the columns of this object's row)
+#define F64_ROW_(m_, ...) m_(__VA_ARGS__)
+#define F64_ROW(m_) F64_ROW_(m_, F64_VARIANT)
+#ifdef GPSAT_F64_W4
+#define GPSAT_F64_NW 4
+#define F64FN(name) name##_w4
+#define F64_COL_NS(ns8_, ns4_, ...) ns4_
+#else
+#define GPSAT_F64_NW 8
+#define F64FN(name) name
+#define F64_COL_NS(ns8_, ns4_, ...) ns8_
+#endif
+#define F64_COL_ENTRY(ns8_, ns4_, fn_, ...) F64FN(fn_)
+#define F64_COL_BASE(ns8_, ns4_, fn_, base_, ...) base_
+#define F64_COL_CV(ns8_, ns4_, fn_, base_, cv_, ...) cv_
+#define F64_COL_MEAN(ns8_, ns4_, fn_, base_, cv_, mean_, ...) mean_
+#define F64_CONSTANTS(ns8_, ns4_, fn_, base_, cv_, mean_, kn_, dmax_) \
+    constexpr bool BASE = base_, CV = cv_, MEAN = mean_;              \
+    constexpr unsigned KN_SET = kn_;                                  \
+    constexpr int D_MAX = dmax_;
+#define F64NS F64_ROW(F64_COL_NS)
+#if F64_ROW(F64_COL_MEAN)
+#define GPSAT_OPT_IDENTITY
 #endif
 namespace F64NS {
+
+F64_ROW(F64_CONSTANTS)
+static_assert(int(BASE) + int(CV) + int(MEAN) + int(KN_SET == 0x10u) == 1, "a row of the variant table is plain, or adds one thing");
+constexpr int MIN_WG = GPSAT_F64_NW == 4 ? 2 : 1;       // workgroups per CU the kernel is compiled for
+constexpr bool TEAMS = BASE && GPSAT_F64_NW == 8;       // the object with the team kernel
+
+// hyper-parameters of a tile, and partial sums per lane an item of the gradient phase leaves (dNLL/dc needs none)
+template <int D, int KN> constexpr int nhyp() { return D + 2 + ((KN == 4 || MEAN) ? 1 : 0); }
+template <int D, int KN> constexpr int nsum() { return D + 2 + (KN == 4 ? 1 : 0); }
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 extern __shared__ __attribute__((aligned(16))) double lds_d[];
 
-#ifndef GPSAT_F64_NW
-#define GPSAT_F64_NW 8
-#endif
 #define GPSAT_NW GPSAT_F64_NW     // one workgroup per CU (LDS): 8 waves = 2 per SIMD hide the operand latency
 #include "gpsat_opt.h"
 #undef GPSAT_NW
@@ -214,9 +207,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 #include "gpsat_kfun_f64.h"
-#ifdef GPSAT_F64_RQ
 #include "gpsat_kfun_rq_f64.h"
-#endif
 
 struct Lay { int xsc, y, z, alpha, Ad, LT, tmp, Pn, tp4, PnLA, tpLA, end; };   // double offsets into lds_d; end: behind the last region
 
@@ -293,13 +284,24 @@ struct Ctx {
     int pn0;                     // block index of the exchanged diagonal region
     gdouble *tpg, *zg, *ag;
     int gp0;                     // byte offset of the gradient phase's per-item partial sums (aliases the prediction scratch)
-#ifdef GPSAT_F64_RQ
-    double rqa, rqh;             // alpha of the running evaluation, and 1 / (2 alpha)
-#endif
-#ifdef GPSAT_F64_MEAN
-    const double* yg;            // the tile's observations in memory: every evaluation forms y - c in LDS from them
-#endif
+    double rqa, rqh;             // KN == 4: alpha of the running evaluation, and 1 / (2 alpha)
+    const double* yg;            // MEAN: the tile's observations in memory: every evaluation forms y - c in LDS from them
 };
+
+// The covariance function KN at squared scaled distance r2, without the variance factor: kf = k, gg and ga its derivative
+// factors (gpsat_kfun_f64.h, gpsat_kfun_rq_f64.h; ga, dk/dalpha, is written for KN == 4 only).  kfun_c takes the shape
+// parameter from the running evaluation, kfun_t from a parameter vector.
+template <int D, int KN>
+__device__ __forceinline__ void kfun_c(const Ctx<D, KN>& c, double r2, double& kf, double& gg, double& ga) {
+    if constexpr (KN == 4) kfun_rq(c.rqa, c.rqh, r2, kf, gg, ga);
+    else kfun<KN>(r2, kf, gg);
+}
+
+template <int D, int KN>
+__device__ __forceinline__ void kfun_t(const double* theta, double r2, double& kf, double& gg, double& ga) {
+    if constexpr (KN == 4) kfun_rq(theta[D + 2], 0.5 / theta[D + 2], r2, kf, gg, ga);
+    else kfun<KN>(r2, kf, gg);
+}
 
 // who this thread is, and the launch's LDS layout
 template <int D, int KN>
@@ -337,8 +339,8 @@ __device__ __forceinline__ void prior_cov_empty(const double* theta0, const doub
             const double df = (Xs[(size_t)i * D + d] - Xs[(size_t)j * D + d]) / theta0[d];
             r2 = fma(df, df, r2);
         }
-        double kf, gg;
-        KFUN_T(theta0, r2, kf, gg);
+        [[maybe_unused]] double kf, gg, ga;
+        kfun_t<D, KN>(theta0, r2, kf, gg, ga);
         cov[e] = sf2 * kf;
     }
 }
@@ -382,8 +384,8 @@ __device__ __forceinline__ f64x4 kblock(const Ctx<D, KN>& c, int bi, int bj) {
         double r2 = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; r2 = fma(df, df, r2); }
-        double kf, gg;
-        KFUN_C(c, r2, kf, gg);
+        [[maybe_unused]] double kf, gg, ga;
+        kfun_c(c, r2, kf, gg, ga);
         double v = ((p < c.N) && (qc < c.N)) ? c.sf2 * kf : 0.0;
         if (p == qc) v = (p < c.N) ? (v + c.sn2) : 1.0;
         out[r] = v;
@@ -400,16 +402,18 @@ __device__ __forceinline__ f64x4 ksblock(const Ctx<D, KN>& c, int bj, const doub
         double r2 = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; r2 = fma(df, df, r2); }
-        double kf, gg;
-        KFUN_C(c, r2, kf, gg);
+        [[maybe_unused]] double kf, gg, ga;
+        kfun_c(c, r2, kf, gg, ga);
         out[r] = ((p < c.N) && qvalid) ? c.sf2 * kf : 0.0;
     }
     return out;
 }
 
+// accal: the sum for dK/dalpha, null unless KN == 4 (a pointer: with a reference to a sum nobody forms, the registers of the
+// gradient phase's k-loop come out differently in every object)
 template <int D, int KN>
 __device__ __forceinline__ void contract(const Ctx<D, KN>& c, const f64x4& kinv, int ba, int bb, double wgt,
-                                         double (&accl)[D], double& accsf, double& accsn RQ_ARG(double& accal)) {
+                                         double (&accl)[D], double& accsf, double& accsn, double* accal) {
     const int qc = BS * bb + c.g;
     double xq[D];
 #pragma unroll
@@ -422,15 +426,13 @@ __device__ __forceinline__ void contract(const Ctx<D, KN>& c, const f64x4& kinv,
         double d2[D], r2 = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) { const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d]; d2[d] = df * df; r2 += d2[d]; }
-        double kf, gg;
-        KFUN_C(c, r2, kf, gg);
+        [[maybe_unused]] double kf, gg, ga;
+        kfun_c(c, r2, kf, gg, ga);
         double Q = kinv[r] - lds_d[c.L.alpha + p] * aq;
         Q = (qv && p < c.N) ? Q : 0.0;
         const double wq = wgt * Q;
         accsf = fma(wq, kf, accsf);
-#ifdef GPSAT_F64_RQ
-        accal = fma(wq, ga, accal);
-#endif
+        if constexpr (KN == 4) *accal = fma(wq, ga, *accal);
         const double wg = wq * gg;
 #pragma unroll
         for (int d = 0; d < D; ++d) accl[d] = fma(wg, d2[d], accl[d]);
@@ -1014,6 +1016,7 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     Shared* sh = reinterpret_cast<Shared*>(lds_d);
     const int NB = c.NB, lane = c.lane;
     double* gpart = reinterpret_cast<double*>(reinterpret_cast<char*>(c.ws) + c.gp0);
+    constexpr int NS = nsum<D, KN>();
     // one workgroup: the items (longest first: their k-loops run from a0 to NB) are pulled from a queue; a team deals them
     int mine = TEAM ? c.vw : -1;
     PROF_BEGIN();
@@ -1070,36 +1073,30 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
 #pragma unroll
             for (int d = 0; d < D; ++d) accl[d] = 0.0;
             double accsf = 0.0, accsn = 0.0;
-#ifdef GPSAT_F64_RQ
-            double accal = 0.0;
-#endif
+            [[maybe_unused]] double accal = 0.0;
 #pragma unroll
             for (int r = 0; r < PR; ++r) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const int a = a0 + r, b = b0 + n;
                     if (r < na && b < NB && a >= b)
-                        contract<D, KN>(c, acc[r][n], a, b, (a == b) ? 1.0 : 2.0, accl, accsf, accsn RQ_ARG(accal));
+                        contract<D, KN>(c, acc[r][n], a, b, (a == b) ? 1.0 : 2.0, accl, accsf, accsn, KN == 4 ? &accal : nullptr);
                 }
             }
-            double* gp = gpart + (size_t)item * (F64_NSUM) * 64 + lane;
+            double* gp = gpart + (size_t)item * NS * 64 + lane;
             if (TEAM) {
                 gdouble* gg = (gdouble*)gp;
 #pragma unroll
                 for (int d = 0; d < D; ++d) gst_d(gg + d * 64, accl[d]);
                 gst_d(gg + D * 64, accsf);
                 gst_d(gg + (D + 1) * 64, accsn);
-#ifdef GPSAT_F64_RQ
-                gst_d(gg + (D + 2) * 64, accal);
-#endif
+                if constexpr (KN == 4) gst_d(gg + (D + 2) * 64, accal);
             } else {
 #pragma unroll
                 for (int d = 0; d < D; ++d) gp[d * 64] = accl[d];
                 gp[D * 64] = accsf;
                 gp[(D + 1) * 64] = accsn;
-#ifdef GPSAT_F64_RQ
-                gp[(D + 2) * 64] = accal;
-#endif
+                if constexpr (KN == 4) gp[(D + 2) * 64] = accal;
             }
             PROF_END(c, 13);
         }
@@ -1110,50 +1107,48 @@ __device__ __forceinline__ void phase_grad(Ctx<D, KN>& c) {
     PROF_END(c, 11);
     if (c.member != 0) return;
     // fixed-order sum: wave w adds the items w, w + NW, ... per lane, then across lanes, then across waves
-    double v[F64_NSUM];
+    double v[NS];
 #pragma unroll
-    for (int i = 0; i < F64_NSUM; ++i) v[i] = 0.0;
+    for (int i = 0; i < NS; ++i) v[i] = 0.0;
     for (int it = c.w; it < nitems; it += NW) {
-        const double* gp = gpart + (size_t)it * (F64_NSUM) * 64 + lane;
+        const double* gp = gpart + (size_t)it * NS * 64 + lane;
 #pragma unroll
-        for (int i = 0; i < F64_NSUM; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
+        for (int i = 0; i < NS; ++i) v[i] += TEAM ? gld_d((const gdouble*)(gp + i * 64)) : gp[i * 64];
     }
 #pragma unroll
-    for (int i = 0; i < F64_NSUM; ++i) {
+    for (int i = 0; i < NS; ++i) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
     }
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < F64_NSUM; ++i) sh->red[c.w][i] = v[i];
+        for (int i = 0; i < NS; ++i) sh->red[c.w][i] = v[i];
     }
-#ifdef GPSAT_F64_MEAN
-    // dNLL/dc = -sum_p alpha_p in the order of EIGHT virtual waves (the 4-wave build runs two each): virtual lane v adds the
-    // rows v, v + 512, ..., then across the lanes of its wave, then thread 0 across the eight -- one order in both builds
-    for (int vw = c.w; vw < 8; vw += NW) {
-        double s = 0.0;
-        for (int p = 64 * vw + lane; p < c.N; p += 512) s += lds_d[c.L.alpha + p];
+    if constexpr (MEAN) {
+        // dNLL/dc = -sum_p alpha_p in the order of EIGHT virtual waves (the 4-wave build runs two each): virtual lane v adds the
+        // rows v, v + 512, ..., then across the lanes of its wave, then thread 0 across the eight -- one order in both builds
+        for (int vw = c.w; vw < 8; vw += NW) {
+            double s = 0.0;
+            for (int p = 64 * vw + lane; p < c.N; p += 512) s += lds_d[c.L.alpha + p];
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) sh->red[vw][D + 2] = s;
+            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) sh->red[vw][D + 2] = s;
+        }
     }
-#endif
     __syncthreads();
     if (c.tid == 0) {
-        for (int i = 0; i < F64_NSUM; ++i) {
+        for (int i = 0; i < NS; ++i) {
             double s = 0.0;
             for (int ww = 0; ww < NW; ++ww) s += sh->red[ww][i];
             if (i < D) sh->gth[i] = 0.5 * c.sf2 * s / sh->theta[i];
-#ifdef GPSAT_F64_RQ
-            else if (i == D + 2) sh->gth[i] = 0.5 * c.sf2 * s;      // dNLL/dalpha = 1/2 sum Q_ab dK_ab/dalpha
-#endif
+            else if (KN == 4 && i == D + 2) sh->gth[i] = 0.5 * c.sf2 * s;      // dNLL/dalpha = 1/2 sum Q_ab dK_ab/dalpha
             else sh->gth[i] = 0.5 * s;
         }
-#ifdef GPSAT_F64_MEAN
-        double sa = 0.0;
-        for (int ww = 0; ww < 8; ++ww) sa += sh->red[ww][D + 2];
-        sh->gth[D + 2] = -sa;
-#endif
+        if constexpr (MEAN) {
+            double sa = 0.0;
+            for (int ww = 0; ww < 8; ++ww) sa += sh->red[ww][D + 2];
+            sh->gth[D + 2] = -sa;
+        }
     }
     __syncthreads();
 }
@@ -1165,23 +1160,23 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
     PROF_BEGIN();
     c.sf2 = sh->theta[D];
     c.sn2 = sh->theta[D + 1];
-#ifdef GPSAT_F64_RQ
-    c.rqa = sh->theta[D + 2];
-    c.rqh = 0.5 / c.rqa;
-#endif
+    if constexpr (KN == 4) {
+        c.rqa = sh->theta[D + 2];
+        c.rqh = 0.5 / c.rqa;
+    }
     for (int idx = c.tid; idx < c.Npad; idx += NT) {
 #pragma unroll
         for (int d = 0; d < D; ++d) lds_d[c.L.xsc + d * c.Npad + idx] = (idx < c.N) ? Xg[(size_t)idx * D + d] / sh->theta[d] : 0.0;
-#ifdef GPSAT_F64_MEAN
         // the residual of THIS evaluation's c, from the observations in memory: nothing of an earlier c (or of the workgroup
         // that ran the tile before a suspension) is read
-        lds_d[c.L.y + idx] = (idx < c.N) ? c.yg[idx] - sh->theta[D + 2] : 0.0;
-#endif
+        if constexpr (MEAN) lds_d[c.L.y + idx] = (idx < c.N) ? c.yg[idx] - sh->theta[D + 2] : 0.0;
     }
     __syncthreads();
-    phase_potrf<D, KN, TEAM>(c, want_grad CV_FINAL_WANTS_M(sh));
+    bool want_m = want_grad;
+    if constexpr (CV) want_m = want_m || sh->phase == PH_FINAL;      // the final evaluation leaves L^-1 and alpha behind
+    phase_potrf<D, KN, TEAM>(c, want_m);
     if (sh->fail) {
-        if (c.tid == 0) { sh->nll = __builtin_inf(); for (int i = 0; i < F64_NHYP; ++i) sh->gth[i] = 0.0; }
+        if (c.tid == 0) { sh->nll = __builtin_inf(); for (int i = 0; i < nhyp<D, KN>(); ++i) sh->gth[i] = 0.0; }
         __syncthreads();
         return;
     }
@@ -1291,7 +1286,9 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
             const int qa = BS * (pc0 + n) + c.g;
             if (c.q == 0 && va[n]) {
                 const double var = c.sf2 - vsum;
-                fm[qa] = msum MEAN_ADD(theta[D + 2]); fv[qa] = var; yv[qa] = var + c.sn2;
+                if constexpr (MEAN) fm[qa] = msum + theta[D + 2];
+                else fm[qa] = msum;
+                fv[qa] = var; yv[qa] = var + c.sn2;
             }
         }
     }
@@ -1329,8 +1326,8 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
                             const double df = Xs[(size_t)pi * D + d] / theta[d] - xq[d];
                             r2 = fma(df, df, r2);
                         }
-                        double kf, gg;
-                        KFUN_C(c, r2, kf, gg);
+                        [[maybe_unused]] double kf, gg, ga;
+                        kfun_c(c, r2, kf, gg, ga);
                         const double v = c.sf2 * kf - Cb[r];
                         fcov[(size_t)pi * c.P + qj] = v;
                         if (p != q) fcov[(size_t)qj * c.P + pi] = v;
@@ -1341,7 +1338,6 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
     }
 }
 
-#ifdef GPSAT_F64_CV
 // ---- held-out predictions (gpsat_fit_predict_batch_cv): the rows G of a fold predicted from all other rows of the tile at
 // the returned parameters, from what the last evaluation left behind -- M = L^-1 in the lower slots and alpha = K_y^-1 y in
 // LDS.  With A = K_y^-1 = M^T M:   A_GG = M[:, G]^T M[:, G],   mean = y_G - A_GG^-1 alpha_G,   cov(y_G) = A_GG^-1
@@ -1479,57 +1475,46 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
     }
 }
 
-#endif
-
-#ifdef GPSAT_F64_RQ
-// thread 0, behind opt_fresh_tile: that gives the LAST parameter GPflow's lower bound of the likelihood variance (a shift of
-// the softplus); here the last parameter is alpha (softplus without a shift, GPflow's positive()) and the likelihood
-// variance stands in front of it
-template <int D>
-__device__ __forceinline__ void rq_fresh_tile(Shared* sh) {
-    constexpr int iv = D + 1, ia = D + 2;
-    sh->shift[ia] = 0.0;
+// thread 0, behind opt_fresh_tile, variants with a third parameter behind the two variances: opt_fresh_tile gives the LAST
+// parameter GPflow's lower bound of the likelihood variance (a shift of the softplus); here the likelihood variance stands
+// in front of the last one.  That is alpha (KN == 4: softplus without a shift, GPflow's positive()) or c (MEAN: GPflow's
+// unconstrained Parameter -- without a box the identity transform, box code 3: theta = u, any finite real value; with finite
+// bounds the sigmoid box)
+template <int D, int KN>
+__device__ __forceinline__ void fresh_tile_extra(Shared* sh) {
+    constexpr int iv = D + 1, ix = D + 2;
+    sh->shift[ix] = 0.0;
     sh->shift[iv] = sh->box[iv] ? 0.0 : 1e-6;
-    sh->u[ia] = u_of_theta(sh, ia, sh->theta[ia]);
+    if constexpr (MEAN) { if (!sh->box[ix]) sh->box[ix] = 3; }
+    sh->u[ix] = u_of_theta(sh, ix, sh->theta[ix]);
     sh->u[iv] = u_of_theta(sh, iv, sh->theta[iv]);
 }
 
-// all threads: the prior at theta0 as the predictions of a tile without observations (tile_predict_prior reads the two
-// variances at the end of theta0)
-template <int D>
-__device__ __forceinline__ void rq_predict_prior(const KernelArgs& A, int H, int t, int tid, long long p0, long long p1,
-                                                 double* f_mean, double* f_var, double* y_var) {
+// all threads, H = D + 3: the prior at theta0 as the predictions of a tile without observations; the mean is 0 or c
+// (tile_predict_prior of gpsat_opt.h, for H = D + 2, reads the two variances at the END of theta0)
+template <int D, int KN>
+__device__ __forceinline__ void predict_prior(const KernelArgs& A, int t, int tid, long long p0, long long p1,
+                                              double* f_mean, double* f_var, double* y_var) {
+    constexpr int H = nhyp<D, KN>();
     const double sf2 = A.theta0[(size_t)t * H + D], sn2 = A.theta0[(size_t)t * H + D + 1];
-    for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = 0.0; f_var[q] = sf2; y_var[q] = sf2 + sn2; }
-}
-#endif
-
-#ifdef GPSAT_F64_MEAN
-// thread 0, behind opt_fresh_tile: that gives the LAST parameter GPflow's lower bound of the likelihood variance; here the
-// last parameter is c and the likelihood variance stands in front of it.  c is GPflow's unconstrained Parameter: without a
-// box it has the identity transform (box code 3: theta = u, any finite real value), with finite bounds the sigmoid box
-template <int D>
-__device__ __forceinline__ void mean_fresh_tile(Shared* sh) {
-    constexpr int iv = D + 1, ic = D + 2;
-    sh->shift[ic] = 0.0;
-    sh->shift[iv] = sh->box[iv] ? 0.0 : 1e-6;
-    if (!sh->box[ic]) sh->box[ic] = 3;
-    sh->u[ic] = u_of_theta(sh, ic, sh->theta[ic]);
-    sh->u[iv] = u_of_theta(sh, iv, sh->theta[iv]);
-}
-
-// all threads: the prior at theta0 as the predictions of a tile without observations: the mean is c
-template <int D>
-__device__ __forceinline__ void mean_predict_prior(const KernelArgs& A, int H, int t, int tid, long long p0, long long p1,
-                                                   double* f_mean, double* f_var, double* y_var) {
-    const double sf2 = A.theta0[(size_t)t * H + D], sn2 = A.theta0[(size_t)t * H + D + 1], cm = A.theta0[(size_t)t * H + D + 2];
+    double cm = 0.0;
+    if constexpr (MEAN) cm = A.theta0[(size_t)t * H + D + 2];
     for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = cm; f_var[q] = sf2; y_var[q] = sf2 + sn2; }
 }
-#endif
 
+// The kernel of every variant.  `cvA` is a parameter of the held-out variant only -- the one place a variant's row reaches
+// the preprocessor inside the device code: the other variants keep their kernel-argument layout and their mangled names.
+// There the name stands for this, in the discarded `if constexpr (CV)`.
+#if !F64_ROW(F64_COL_CV)
+constexpr CvArgs cvA{};
+#endif
 template <int D, int KN>
-__global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const KernelArgs A CV_KERNEL_PARAM) {
-    constexpr int H = F64_NHYP;
+__global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArgs A
+#if F64_ROW(F64_COL_CV)
+                                                                 , const CvArgs cvA
+#endif
+) {
+    constexpr int H = nhyp<D, KN>();
     Ctx<D, KN> c;
     ctx_init(c, A.NBmax);
     Shared* sh = reinterpret_cast<Shared*>(lds_d);
@@ -1575,7 +1560,10 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
         const int NB = c.NB;
         if (c.N == 0) {
             if (c.tid == 0) tile_out_empty(A, H, t);
-            TILE_PREDICT_PRIOR(A, H, t, c.tid, p0, p1, f_mean, f_var, y_var);
+            // (H = D + 2: the shared function, called from here as it always was -- through predict_prior the address arithmetic
+            // of its loads comes out in another order)
+            if constexpr (H == D + 2) tile_predict_prior(A, H, t, c.tid, p0, p1, f_mean, f_var, y_var);
+            else predict_prior<D, KN>(A, t, c.tid, p0, p1, f_mean, f_var, y_var);
             if (f_cov) prior_cov_empty<D, KN>(A.theta0 + (size_t)t * H, Xs + (size_t)p0 * D, c.P, c.tid, f_cov + A.cov_off[t]);
             if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
@@ -1587,13 +1575,8 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
         }
         if (resumed) state_load(sh, A, t, c.tid);
         else if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
-#ifdef GPSAT_F64_RQ
-        if (!resumed && c.tid == 0) rq_fresh_tile<D>(sh);
-#endif
-#ifdef GPSAT_F64_MEAN
-        if (!resumed && c.tid == 0) mean_fresh_tile<D>(sh);
-        c.yg = y + o0;
-#endif
+        if constexpr (H == D + 3) { if (!resumed && c.tid == 0) fresh_tile_extra<D, KN>(sh); }
+        if constexpr (MEAN) c.yg = y + o0;
         __syncthreads();
         const int seg_evals = sliced ? max(1, A.seg_cost / (NB * NB * NB)) : 0x7fffffff;
         bool suspended = false;
@@ -1618,10 +1601,10 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
                 tile_predict_nan(c.tid, p0, p1, f_mean, f_var, y_var, f_cov, A.cov_off, t);
             }
         }
-#ifdef GPSAT_F64_CV
-        __syncthreads();                             // the prediction scratch of every wave is free
-        phase_cv<D, KN>(c, cvA, t, o0, sh->fail != 0);
-#endif
+        if constexpr (CV) {
+            __syncthreads();                         // the prediction scratch of every wave is free
+            phase_cv<D, KN>(c, cvA, t, o0, sh->fail != 0);
+        }
         if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #ifdef GPSAT_PROFILE
@@ -1630,7 +1613,6 @@ __global__ void __launch_bounds__(NT, F64_MIN_WG) gp_tile_kernel_f64(const Kerne
 #endif
 }
 
-#if !defined(GPSAT_F64_W4) && !defined(GPSAT_F64_CV) && !defined(GPSAT_F64_RQ) && !defined(GPSAT_F64_MEAN)
 // ---------------------------------------------------------------------------------------------
 // the team kernel: KernelArgs::team_size workgroups per tile (see "Teams" above).  Workgroup b is member b % G of team
 // b / G; the team's workspace is the slab of its member 0.  The owner pops tiles, runs the optimiser and, before every
@@ -1752,123 +1734,57 @@ __global__ void __launch_bounds__(NT, 1) gp_team_kernel_f64(const KernelArgs A) 
         }
     }
 }
-#endif
 
-#ifdef GPSAT_F64_CV
-template <int D, int KN>
-static hipError_t launch_one_cv(const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
-    if (a.team_size > 1) return hipErrorInvalidValue;          // one workgroup per tile only
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, KN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+// ---- the launch ladder: run-time D and KernelArgs::kernel to the instantiation, within what the variant's row allows
+template <class... Args>
+static hipError_t launch_kernel(void (*kernel)(Args...), int grid, size_t smem, hipStream_t stream, const Args&... args) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gp_tile_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a, cv);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), smem, stream, args...);
     return hipGetLastError();
 }
 
+template <int D, int KN>
+static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
+    if constexpr (D > D_MAX || !((KN_SET >> KN) & 1u)) {
+        return hipErrorInvalidValue;
+    } else {
+        if (a.team_size > 1) {                                     // elsewhere: one workgroup per tile only
+            if constexpr (TEAMS) return launch_kernel(gp_team_kernel_f64<D, KN>, grid, smem, stream, a);
+            else return hipErrorInvalidValue;
+        }
+        if constexpr (CV) return cv ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *cv) : hipErrorInvalidValue;
+        else return launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a);
+    }
+}
+
 template <int D>
-static hipError_t launch_d_cv(const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
+static hipError_t launch_d(const KernelArgs& a, const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
     switch (a.kernel) {
-        case 0: return launch_one_cv<D, 0>(a, cv, grid, smem, stream);
-        case 1: return launch_one_cv<D, 1>(a, cv, grid, smem, stream);
-        case 2: return launch_one_cv<D, 2>(a, cv, grid, smem, stream);
-        case 3: return launch_one_cv<D, 3>(a, cv, grid, smem, stream);
+        case 0: return launch_one<D, 0>(a, cv, grid, smem, stream);
+        case 1: return launch_one<D, 1>(a, cv, grid, smem, stream);
+        case 2: return launch_one<D, 2>(a, cv, grid, smem, stream);
+        case 3: return launch_one<D, 3>(a, cv, grid, smem, stream);
+        case 4: return launch_one<D, 4>(a, cv, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }
-#elif defined(GPSAT_F64_RQ)
-template <int D>
-static hipError_t launch_d_rq(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    if (a.team_size > 1 || a.kernel != 4) return hipErrorInvalidValue;          // one workgroup per tile only
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gp_tile_kernel_f64<D, 4>), dim3(grid), dim3(NT), smem, stream, a);
-    return hipGetLastError();
-}
-#elif defined(GPSAT_F64_MEAN)
-template <int D, int KN>
-static hipError_t launch_one_mean(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    if (a.team_size > 1) return hipErrorInvalidValue;          // one workgroup per tile only
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, KN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gp_tile_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a);
-    return hipGetLastError();
-}
-
-template <int D>
-static hipError_t launch_d_mean(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    switch (a.kernel) {
-        case 0: return launch_one_mean<D, 0>(a, grid, smem, stream);
-        case 1: return launch_one_mean<D, 1>(a, grid, smem, stream);
-        case 2: return launch_one_mean<D, 2>(a, grid, smem, stream);
-        case 3: return launch_one_mean<D, 3>(a, grid, smem, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-#else
-template <int D, int KN>
-static hipError_t launch_one(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-#ifndef GPSAT_F64_W4
-    if (a.team_size > 1) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_team_kernel_f64<D, KN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gp_team_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a);
-        return hipGetLastError();
-    }
-#endif
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gp_tile_kernel_f64<D, KN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gp_tile_kernel_f64<D, KN>), dim3(grid), dim3(NT), smem, stream, a);
-    return hipGetLastError();
-}
-
-template <int D>
-static hipError_t launch_d(const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    switch (a.kernel) {
-        case 0: return launch_one<D, 0>(a, grid, smem, stream);
-        case 1: return launch_one<D, 1>(a, grid, smem, stream);
-        case 2: return launch_one<D, 2>(a, grid, smem, stream);
-        case 3: return launch_one<D, 3>(a, grid, smem, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-#endif
 
 }  // namespace F64NS
 
-#ifdef GPSAT_F64_CV
-hipError_t F64FN(launch_tiles_cv_f64)(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream) {
+// `cv`: the held-out variant's arguments, null for every other
+hipError_t F64_ROW(F64_COL_ENTRY)(int D, const KernelArgs& a, const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
     switch (D) {
-        case 1: return F64NS::launch_d_cv<1>(a, cv, grid, smem, stream);
-        case 2: return F64NS::launch_d_cv<2>(a, cv, grid, smem, stream);
-        case 3: return F64NS::launch_d_cv<3>(a, cv, grid, smem, stream);
-        case 4: return F64NS::launch_d_cv<4>(a, cv, grid, smem, stream);
+        case 1: return F64NS::launch_d<1>(a, cv, grid, smem, stream);
+        case 2: return F64NS::launch_d<2>(a, cv, grid, smem, stream);
+        case 3: return F64NS::launch_d<3>(a, cv, grid, smem, stream);
+        case 4: return F64NS::launch_d<4>(a, cv, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }
-#elif defined(GPSAT_F64_RQ)
-hipError_t F64FN(launch_tiles_rq_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    switch (D) {
-        case 1: return F64NS::launch_d_rq<1>(a, grid, smem, stream);
-        case 2: return F64NS::launch_d_rq<2>(a, grid, smem, stream);
-        case 3: return F64NS::launch_d_rq<3>(a, grid, smem, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-#elif defined(GPSAT_F64_MEAN)
-hipError_t F64FN(launch_tiles_mean_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    switch (D) {
-        case 1: return F64NS::launch_d_mean<1>(a, grid, smem, stream);
-        case 2: return F64NS::launch_d_mean<2>(a, grid, smem, stream);
-        case 3: return F64NS::launch_d_mean<3>(a, grid, smem, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-#else
+
+#if F64_ROW(F64_COL_BASE)
+// what the host sizes a launch of either wave count by, for every variant
 size_t F64FN(shared_bytes_f64)(int D, int NBmax) {
     // doubles allocated behind Lay::end, read by nobody: the allocation's size is part of the launch plan, which picks the build
     // by it and is pinned in tests/test_abi.py
@@ -1885,16 +1801,6 @@ size_t F64FN(workspace_doubles_per_wg_f64)(int NBmax, int PCcov) {
     // ... the exchange area of teams (diagonal region of a panel, z, alpha), and the zero block
     return (size_t)F64NS::BLK * ((size_t)NBmax * NBmax + (size_t)NBmax + (size_t)F64NS::NW * 4 * NBmax + cov +
                                  F64NS::xchg_blocks(NBmax) + 1);
-}
-
-hipError_t F64FN(launch_tiles_f64)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream) {
-    switch (D) {
-        case 1: return F64NS::launch_d<1>(a, grid, smem, stream);
-        case 2: return F64NS::launch_d<2>(a, grid, smem, stream);
-        case 3: return F64NS::launch_d<3>(a, grid, smem, stream);
-        case 4: return F64NS::launch_d<4>(a, grid, smem, stream);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 #endif

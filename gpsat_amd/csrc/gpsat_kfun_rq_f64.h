@@ -1,5 +1,5 @@
-// gpsat_kfun_rq_f64.h -- the RationalQuadratic covariance function in fp64, for the -DGPSAT_F64_RQ builds of the fp64 tile
-// kernel.  Included inside the kernel file's namespace (under namespace gpsat), like gpsat_kfun_f64.h.
+// gpsat_kfun_rq_f64.h -- the RationalQuadratic covariance function in fp64, KN == 4 of the fp64 tile kernel (instantiated in
+// its rq variant only).  Included inside the kernel file's namespace (under namespace gpsat), like gpsat_kfun_f64.h.
 //   k = s b^-alpha,  b = 1 + r2 / (2 alpha),  r2 the squared scaled distance   (GPflow's and scikit-learn's RationalQuadratic)
 // a = alpha, ha = 1 / (2 alpha).  Out, all without the variance factor s: kf = k, gg with dk/dl_d = gg (x_d - x'_d)^2 / l_d^3
 // (gg = kf / b), and ga = dk/dalpha = kf (-log b + (b - 1) / b).  r2 = 0 gives kf = 1 and ga = 0 exactly.

@@ -16,17 +16,24 @@ struct Build {
     size_t (*shared_bytes)(int D, int NBmax);
     size_t (*workspace_per_wg)(int NBmax, int PCcov);         // floats (fp32 builds) or doubles (fp64 builds)
     int (*state_words)();
-    hipError_t (*launch)(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);
     size_t (*pq_floats_per_slot)(int D, int NBmax);           // nullptr: the build has no deferred predictions
-    // the same tile loop with the held-out phase (gpsat_fit_predict_batch_cv); nullptr: the build has none
-    hipError_t (*launch_cv)(int D, const KernelArgs& a, const CvArgs& cv, int grid, size_t smem, hipStream_t stream);
+    // the tile loop per F64Variant (`cv`: the held-out variant's arguments, else null); nullptr: the build has no such variant
+    F64Launch* launch_variant[4];
 };
 enum { BUILD_F32_W4 = 0, BUILD_F32_W8 = 1, BUILD_F64_W8 = 2, BUILD_F64_W4 = 3 };
+// The variants of the fp64 tile loop (gpsat_kernels_f64.hip): held-out predictions, the RationalQuadratic covariance function,
+// a trainable constant mean.  A job is one of them; every one but PLAIN runs one workgroup per tile.
+enum F64Variant { PLAIN = 0, CV = 1, RQ = 2, MEAN = 3 };
+// the fp32 builds (no variants) behind the same signature
+inline hipError_t launch_f32_w4(int D, const KernelArgs& a, const CvArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles(D, a, grid, smem, stream); }
+inline hipError_t launch_f32_w8(int D, const KernelArgs& a, const CvArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles_w8(D, a, grid, smem, stream); }
 const Build builds[4] = {
-    {shared_bytes, workspace_floats_per_wg, state_words, launch_tiles, pq_floats_per_slot, nullptr},
-    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, launch_tiles_w8, nullptr, nullptr},
-    {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, launch_tiles_f64, nullptr, launch_tiles_cv_f64},
-    {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, launch_tiles_f64_w4, nullptr, launch_tiles_cv_f64_w4},
+    {shared_bytes, workspace_floats_per_wg, state_words, pq_floats_per_slot, {launch_f32_w4, nullptr, nullptr, nullptr}},
+    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, nullptr, {launch_f32_w8, nullptr, nullptr, nullptr}},
+    {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, nullptr,
+     {launch_tiles_f64, launch_tiles_f64_cv, launch_tiles_f64_rq, launch_tiles_f64_mean}},
+    {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, nullptr,
+     {launch_tiles_f64_w4, launch_tiles_f64_cv_w4, launch_tiles_f64_rq_w4, launch_tiles_f64_mean_w4}},
 };
 
 // One developer knob (GPSAT_DEBUG_*, read through dev_env() only): whether it is set, and atoi of its text.
