@@ -30,11 +30,11 @@ EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_cre
            "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
            "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
            "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit",
-           "gpsat_n_hyper", "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean"]
+           "gpsat_n_hyper", "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean", "gpsat_fit_predict_batch_noise"]
 # ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
 OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold",
                     "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit", "gpsat_n_hyper",
-                    "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean"]
+                    "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean", "gpsat_fit_predict_batch_noise"]
 
 
 class GpsatOpts(C.Structure):
@@ -69,6 +69,10 @@ class GpsatMultistart(C.Structure):
 
 class GpsatMean(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class GpsatNoise(C.Structure):
+    _fields_ = [("obs_var", C.c_void_p), ("reserved", C.c_int32 * 8)]
 
 
 class GpsatCv(C.Structure):
@@ -204,6 +208,9 @@ def load():
         lib.gpsat_n_hyper_mean.restype = C.c_int
         lib.gpsat_fit_predict_batch_mean.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMean)]
         lib.gpsat_fit_predict_batch_mean.restype = C.c_int
+    if hasattr(lib, "gpsat_fit_predict_batch_noise"):
+        lib.gpsat_fit_predict_batch_noise.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatNoise)]
+        lib.gpsat_fit_predict_batch_noise.restype = C.c_int
     if hasattr(lib, "gpsat_bin_batch"):
         lib.gpsat_bin_batch.restype = C.c_int
         lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,

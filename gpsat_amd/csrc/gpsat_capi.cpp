@@ -3,7 +3,7 @@
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
 // Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
 // translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
-//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
 //     setup_*, launch, fetch_batch / fetch_cv, record_timing.
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
@@ -347,6 +347,7 @@ int fetch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const Ba
 // Device pointers of a staged batch.
 struct Staged {
     const char *X = nullptr, *y = nullptr, *Xs = nullptr, *Z = nullptr;
+    const double* obs_var = nullptr;  // [sumN] noise variances per observation (gpsat_fit_predict_batch_noise), or nullptr
     char *fm = nullptr, *fv = nullptr, *yv = nullptr, *cov = nullptr;
     long long* i64 = nullptr;         // [3][T+1]: obs_off, pred_off, then cov_off (dense) or z_off (sparse)
     double *f64 = nullptr, *out_f64 = nullptr;    // [3][T*H]: theta0, lo, hi; theta [T*H], nll [T], grad [T*H]
@@ -355,10 +356,12 @@ struct Staged {
 };
 
 // Reserve the metadata, output, workspace and (host mode) bulk buffers, lay them out, record ev[0] and issue the host-to-device
-// copies.  `off3`: the third offset table or nullptr; `Z`: the sparse path's inducing points (d.sumM rows) or nullptr.
+// copies.  `off3`: the third offset table or nullptr; `Z`: the sparse path's inducing points (d.sumM rows) or nullptr;
+// `obs_var`: the caller's noise variances per observation (d.sumN doubles, host or device as the bulk arrays) or nullptr.
 // `order` is pageable host memory of the caller and must outlive the launch.
 int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const double* theta0, const std::vector<int>& order,
-                const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s, int mean = GPSAT_MEAN_ZERO) {
+                const int64_t* off3, const void* Z, size_t ws_bytes, Staged& s, int mean = GPSAT_MEAN_ZERO,
+                const void* obs_var = nullptr) {
     const int T = b->T, D = b->D, H = n_hyper(b, mean);
     const size_t esz = b->dtype == GPSAT_F64 ? sizeof(double) : sizeof(float);
     const size_t sumN = (size_t)d.sumN, sumP = (size_t)d.sumP, sumM = (size_t)d.sumM;
@@ -371,7 +374,7 @@ int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const
     if ((rc = h->ws.reserve(ws_bytes))) return rc;
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     if (b->memory == GPSAT_MEM_HOST) {
-        const size_t in_e = sumN * D + sumN + sumP * D + sumM * D;
+        const size_t in_e = sumN * D + sumN + sumP * D + sumM * D + (obs_var ? sumN : 0);     // (obs_var: fp64 only, esz = 8)
         if ((rc = h->bulk_in.reserve(std::max<size_t>(in_e, 1) * esz))) return rc;
         if ((rc = h->bulk_out.reserve(std::max<size_t>(sumP * 3 + (size_t)d.sumC, 1) * esz))) return rc;
         char* base = static_cast<char*>(h->bulk_in.p);
@@ -382,12 +385,18 @@ int stage_batch(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const
         }
         if (sumP > 0) HIP_TRY(hipMemcpyAsync(const_cast<char*>(s.Xs), b->Xs, sumP * D * esz, hipMemcpyHostToDevice, h->stream));
         if (Z) HIP_TRY(hipMemcpyAsync(const_cast<char*>(s.Z), Z, sumM * D * esz, hipMemcpyHostToDevice, h->stream));
+        if (obs_var) {
+            double* dv = reinterpret_cast<double*>(const_cast<char*>(s.Z) + sumM * D * esz);
+            if (sumN > 0) HIP_TRY(hipMemcpyAsync(dv, obs_var, sumN * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            s.obs_var = dv;
+        }
         s.fm = static_cast<char*>(h->bulk_out.p); s.fv = s.fm + sumP * esz; s.yv = s.fv + sumP * esz;
         if (d.want_cov) s.cov = s.yv + sumP * esz;
     } else {
         s.cov = static_cast<char*>(b->f_cov);
         s.X = static_cast<const char*>(b->X); s.y = static_cast<const char*>(b->y); s.Xs = static_cast<const char*>(b->Xs);
         s.Z = static_cast<const char*>(Z);
+        s.obs_var = static_cast<const double*>(obs_var);
         s.fm = static_cast<char*>(b->f_mean); s.fv = static_cast<char*>(b->f_var); s.yv = static_cast<char*>(b->y_var);
     }
     s.i64 = static_cast<long long*>(h->meta_i64.p);
@@ -624,6 +633,7 @@ struct DenseJob {
     const gpsat_cv* cv = nullptr;     // held-out predictions (gpsat_fit_predict_batch_cv), with their fold tables
     CvTables cv_tables;
     int mean = GPSAT_MEAN_ZERO;       // GPSAT_MEAN_CONSTANT: gpsat_fit_predict_batch_mean with a trainable constant mean
+    const void* obs_var = nullptr;    // gpsat_fit_predict_batch_noise: noise variances per observation, behind gpsat::check_noise
     bool ms_on;                       // ms given and the optimiser runs
     BatchDims dims;
     const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
@@ -637,7 +647,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     const BatchDims& d = j.dims;
     const bool f64 = b->dtype == GPSAT_F64;
     const gpsat::F64Variant variant = j.cv ? gpsat::CV : b->kernel == GPSAT_KERNEL_RQ ? gpsat::RQ
-                                      : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : gpsat::PLAIN;
+                                      : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : j.obs_var ? gpsat::NOISE : gpsat::PLAIN;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
                            h->num_cu, h->wg_per_cu, solo || variant != gpsat::PLAIN, unsliced, read_dev_knobs()};     // a variant: one workgroup per tile
     gpsat::TilePlan p;
@@ -646,7 +656,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     int rc;
     // one workspace per workgroup, or per team
     const size_t ws_bytes = (size_t)(p.grid / p.team) * p.ws_stride * (f64 ? sizeof(double) : sizeof(float));
-    if ((rc = stage_batch(h, b, d, j.theta0, j.order, d.want_cov ? b->cov_off : nullptr, nullptr, ws_bytes, s, j.mean))) return rc;
+    if ((rc = stage_batch(h, b, d, j.theta0, j.order, d.want_cov ? b->cov_off : nullptr, nullptr, ws_bytes, s, j.mean, j.obs_var))) return rc;
     gpsat::KernelArgs a;
     fill_common_args(a, b, s, j.mean);
     a.NBmax = p.NBmax;
@@ -663,6 +673,8 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if ((rc = setup_eval_cache(h, b, j.ms_on, a))) return rc;
     const auto launch = gpsat::builds[p.build].launch_variant[variant];
     if (!launch) return fail(GPSAT_EINVAL, variant == gpsat::CV ? "held-out predictions: no kernel in this build" : "no kernel for this model in this build");
+    gpsat::NoiseArgs na;
+    na.obs_var = s.obs_var;
     gpsat::CvArgs ca;
     if (j.cv && (rc = stage_cv(h, b, j.cv, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
@@ -678,7 +690,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     a.prof = static_cast<unsigned long long*>(h->prof.p);
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, p.grid, p.smem, h->stream));
+    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, d, ca))) return rc;
@@ -695,7 +707,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
 }
 
 int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr,
-                const gpsat_mean* mn = nullptr) {
+                const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
@@ -707,6 +719,11 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
         const char* why = nullptr;
         if ((rc = gpsat::check_mean(b, mn, &why))) return fail(rc, why);
         j.mean = mn->kind;
+    }
+    if (nz) {
+        char why[160];
+        if ((rc = gpsat::check_noise(b, nz, why, sizeof(why)))) return fail(rc, why);
+        j.obs_var = nz->obs_var;
     }
     BatchDims& d = j.dims;
     d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
@@ -1099,6 +1116,11 @@ int gpsat_fit_predict_batch(gpsat_handle* h, const gpsat_batch* b) { return fit_
 int gpsat_fit_predict_batch_mean(gpsat_handle* h, const gpsat_batch* b, const gpsat_mean* m) {
     if (!m) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_mean: mean is NULL");
     return fit_predict(h, b, nullptr, nullptr, m);
+}
+
+int gpsat_fit_predict_batch_noise(gpsat_handle* h, const gpsat_batch* b, const gpsat_noise* nz) {
+    if (!nz) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_noise: noise is NULL");
+    return fit_predict(h, b, nullptr, nullptr, nullptr, nz);
 }
 
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {

@@ -18,14 +18,14 @@
 
 namespace gpsat {
 // ---- which object this is ---------------------------------------------------------------------
-// The file is compiled eight times: with 8 waves per workgroup and one workgroup per CU (the default) or, -DGPSAT_F64_W4,
+// The file is compiled ten times: with 8 waves per workgroup and one workgroup per CU (the default) or, -DGPSAT_F64_W4,
 // with 4 waves and two workgroups per CU for tiles whose LDS fits twice (a second TILE per CU overlaps the serial diagonal
 // work of the first) -- and each of the two as one VARIANT of the one-workgroup-per-tile kernel: plain, or with one of
-// -DGPSAT_F64_CV, -DGPSAT_F64_RQ, -DGPSAT_F64_MEAN.  A variant is one row of the table below: the row becomes the constants
-// CV, MEAN, KN_SET and D_MAX, the templates ask them with `if constexpr`, and an object instantiates
+// -DGPSAT_F64_CV, -DGPSAT_F64_RQ, -DGPSAT_F64_MEAN, -DGPSAT_F64_NOISE.  A variant is one row of the table below: the row becomes
+// the constants CV, MEAN, NOISE, KN_SET and D_MAX, the templates ask them with `if constexpr`, and an object instantiates
 // gp_tile_kernel_f64<D, KN> for the row's D and KN only, in the row's namespace, behind the row's one exported entry point.
 // A new variant is a new row and the `if constexpr` that reads its constant.  Beyond this block the preprocessor sees a
-// variant in three places: the kernel's parameter list (cv), the host's sizing functions at the end of the file (plain),
+// variant in three places: the kernel's parameter list (cv, noise), the host's sizing functions at the end of the file (plain),
 // and GPSAT_OPT_IDENTITY below (mean), which gpsat_opt.h asks with #ifdef.
 //   plain  gpsat_fit_predict_batch: the four stationary kernels, H = D + 2, theta = (l_0 .. l_{D-1}, kernel variance,
 //          likelihood variance).  The only variant with the team kernel (8 waves) and the host's sizing functions.
@@ -38,12 +38,16 @@ namespace gpsat {
 //          H = D + 3, theta = (.., likelihood variance, c).  Every evaluation works on the residual y - c of ITS c;
 //          dNLL/dc = -sum(alpha); c is added to the predicted mean.  c has the identity transform unless it is boxed
 //          (GPSAT_OPT_IDENTITY in gpsat_opt.h, defined for this variant only).
-//                         namespace         entry point             sizing,                  kernels   D up
-//                         8 / 4 waves       (+ _w4)                 teams   CV     MEAN      (bit KN)  to
-#define F64_VARIANT_plain  f64k,   f64k4,    launch_tiles_f64,       true,   false, false,    0x0f,     4
-#define F64_VARIANT_cv     f64kcv, f64k4cv,  launch_tiles_f64_cv,    false,  true,  false,    0x0f,     4
-#define F64_VARIANT_rq     f64krq, f64k4rq,  launch_tiles_f64_rq,    false,  false, false,    0x10,     3
-#define F64_VARIANT_mean   f64kmn, f64k4mn,  launch_tiles_f64_mean,  false,  false, true,     0x0f,     3
+//   noise  known noise variances per observation (gpsat_fit_predict_batch_noise): y ~ N(0, K + sn2 I + diag(v)), v given and
+//          not trained, H = D + 2.  v_p is added to the diagonal element of K in kblock, read from memory by every K build;
+//          nothing else knows of it.  The kernel has one more parameter, NoiseArgs.
+//                         namespace         entry point             sizing,                         kernels   D up
+//                         8 / 4 waves       (+ _w4)                 teams   CV     MEAN   NOISE     (bit KN)  to
+#define F64_VARIANT_plain  f64k,   f64k4,    launch_tiles_f64,       true,   false, false, false,    0x0f,     4
+#define F64_VARIANT_cv     f64kcv, f64k4cv,  launch_tiles_f64_cv,    false,  true,  false, false,    0x0f,     4
+#define F64_VARIANT_rq     f64krq, f64k4rq,  launch_tiles_f64_rq,    false,  false, false, false,    0x10,     3
+#define F64_VARIANT_mean   f64kmn, f64k4mn,  launch_tiles_f64_mean,  false,  false, true,  false,    0x0f,     3
+#define F64_VARIANT_noise  f64knz, f64k4nz,  launch_tiles_f64_noise, false,  false, false, true,     0x0f,     4
 #ifndef GPSAT_F64_CV
 #define GPSAT_F64_CV 0
 #endif
@@ -53,14 +57,20 @@ namespace gpsat {
 #ifndef GPSAT_F64_MEAN
 #define GPSAT_F64_MEAN 0
 #endif
+#ifndef GPSAT_F64_NOISE
+#define GPSAT_F64_NOISE 0
+#endif
 // A variant adds ONE thing to the plain kernel; no combination is built, dispatched or tested.
-static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN <= 1, "GPSAT_F64_CV, GPSAT_F64_RQ and GPSAT_F64_MEAN are builds of their own");
+static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE <= 1,
+              "GPSAT_F64_CV, GPSAT_F64_RQ, GPSAT_F64_MEAN and GPSAT_F64_NOISE are builds of their own");
 #if GPSAT_F64_CV
 #define F64_VARIANT F64_VARIANT_cv
 #elif GPSAT_F64_RQ
 #define F64_VARIANT F64_VARIANT_rq
 #elif GPSAT_F64_MEAN
 #define F64_VARIANT F64_VARIANT_mean
+#elif GPSAT_F64_NOISE
+#define F64_VARIANT F64_VARIANT_noise
 #else
 #define F64_VARIANT F64_VARIANT_plain
 #endif
@@ -80,9 +90,10 @@ static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN <= 1, "GPSAT_F64_CV, 
 #define F64_COL_BASE(ns8_, ns4_, fn_, base_, ...) base_
 #define F64_COL_CV(ns8_, ns4_, fn_, base_, cv_, ...) cv_
 #define F64_COL_MEAN(ns8_, ns4_, fn_, base_, cv_, mean_, ...) mean_
-#define F64_CONSTANTS(ns8_, ns4_, fn_, base_, cv_, mean_, kn_, dmax_) \
-    constexpr bool BASE = base_, CV = cv_, MEAN = mean_;              \
-    constexpr unsigned KN_SET = kn_;                                  \
+#define F64_COL_NOISE(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, ...) noise_
+#define F64_CONSTANTS(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, kn_, dmax_) \
+    constexpr bool BASE = base_, CV = cv_, MEAN = mean_, NOISE = noise_;      \
+    constexpr unsigned KN_SET = kn_;                                          \
     constexpr int D_MAX = dmax_;
 #define F64NS F64_ROW(F64_COL_NS)
 #if F64_ROW(F64_COL_MEAN)
@@ -91,7 +102,7 @@ static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN <= 1, "GPSAT_F64_CV, 
 namespace F64NS {
 
 F64_ROW(F64_CONSTANTS)
-static_assert(int(BASE) + int(CV) + int(MEAN) + int(KN_SET == 0x10u) == 1, "a row of the variant table is plain, or adds one thing");
+static_assert(int(BASE) + int(CV) + int(MEAN) + int(NOISE) + int(KN_SET == 0x10u) == 1, "a row of the variant table is plain, or adds one thing");
 constexpr int MIN_WG = GPSAT_F64_NW == 4 ? 2 : 1;       // workgroups per CU the kernel is compiled for
 constexpr bool TEAMS = BASE && GPSAT_F64_NW == 8;       // the object with the team kernel
 
@@ -286,6 +297,7 @@ struct Ctx {
     int gp0;                     // byte offset of the gradient phase's per-item partial sums (aliases the prediction scratch)
     double rqa, rqh;             // KN == 4: alpha of the running evaluation, and 1 / (2 alpha)
     const double* yg;            // MEAN: the tile's observations in memory: every evaluation forms y - c in LDS from them
+    const double* vg;            // NOISE: the tile's N noise variances in memory: every K build reads its diagonal's from them
 };
 
 // The covariance function KN at squared scaled distance r2, without the variance factor: kf = k, gg and ga its derivative
@@ -371,8 +383,19 @@ __device__ __forceinline__ void team_barrier(Ctx<D, KN>& c, bool long_wait = fal
     __syncthreads();
 }
 
+// NOISE: v_p of this lane's diagonal element of the diagonal block bi (the lane with rowof(r, q) == g, r = g / 4), 0 in the
+// other lanes and beyond the tile's N rows.  One load in 16 lanes of the wave, from memory at every K build: a resumed tile
+// and a tile on another workgroup read what the first evaluation read.  The caller issues it ahead of the block's chain of
+// products, whose latency hides the load's.
 template <int D, int KN>
-__device__ __forceinline__ f64x4 kblock(const Ctx<D, KN>& c, int bi, int bj) {
+__device__ __forceinline__ double noise_diag(const Ctx<D, KN>& c, int bi) {
+    const int p = BS * bi + c.g;
+    return ((c.g & 3) == c.q && p < c.N) ? c.vg[p] : 0.0;
+}
+
+// vd: noise_diag of a diagonal block (NOISE), 0 for every other
+template <int D, int KN>
+__device__ __forceinline__ f64x4 kblock(const Ctx<D, KN>& c, int bi, int bj, [[maybe_unused]] double vd = 0.0) {
     const int qc = BS * bj + c.g;
     double xq[D];
 #pragma unroll
@@ -388,6 +411,8 @@ __device__ __forceinline__ f64x4 kblock(const Ctx<D, KN>& c, int bi, int bj) {
         kfun_c(c, r2, kf, gg, ga);
         double v = ((p < c.N) && (qc < c.N)) ? c.sf2 * kf : 0.0;
         if (p == qc) v = (p < c.N) ? (v + c.sn2) : 1.0;
+        // the row's own variance, (sf2 k + sn2) + v_p in this order: v_p = 0 changes no bit (p == qc in diagonal blocks only)
+        if constexpr (NOISE) { if (p == qc) v = v + vd; }
         out[r] = v;
     }
     return out;
@@ -801,6 +826,8 @@ __device__ __forceinline__ void phase_potrf(Ctx<D, KN>& c, const bool want_m) {
             diag_item(bb, r, r2);
             if (r2 >= nr) continue;
             const bool dg = (r == r2);
+            [[maybe_unused]] double vd = 0.0;
+            if constexpr (NOISE) { if (dg) vd = noise_diag(c, j0 + r); }       // one wave-uniform test, N loads per K build
             f64x4 acc = zero4();
             double tp = 0.0;
             if (LA && j0 > 0) {
@@ -816,7 +843,7 @@ __device__ __forceinline__ void phase_potrf(Ctx<D, KN>& c, const bool want_m) {
             } else {
                 diag_chain<D, KN, TEAM>(c, j0, r, r2, 0, j0, dg, acc, tp);
             }
-            acc = kblock<D, KN>(c, j0 + r, j0 + r2) - acc;
+            acc = kblock<D, KN>(c, j0 + r, j0 + r2, vd) - acc;
             if (TEAM) stg(c.ws, c.pn0 + bb, lane, acc);
             else stl(c.L.Pn + bb * BLK, lane, acc);
             if (dg) {
@@ -1502,16 +1529,21 @@ __device__ __forceinline__ void predict_prior(const KernelArgs& A, int t, int ti
     for (long long q = p0 + tid; q < p1; q += NT) { f_mean[q] = cm; f_var[q] = sf2; y_var[q] = sf2 + sn2; }
 }
 
-// The kernel of every variant.  `cvA` is a parameter of the held-out variant only -- the one place a variant's row reaches
-// the preprocessor inside the device code: the other variants keep their kernel-argument layout and their mangled names.
-// There the name stands for this, in the discarded `if constexpr (CV)`.
+// The kernel of every variant.  `cvA` is a parameter of the held-out variant only, `nzA` of the noise variant only -- the one
+// place a variant's row reaches the preprocessor inside the device code: the other variants keep their kernel-argument layout
+// and their mangled names.  There the names stand for these, in the discarded `if constexpr (CV)` / `(NOISE)`.
 #if !F64_ROW(F64_COL_CV)
 constexpr CvArgs cvA{};
+#endif
+#if !F64_ROW(F64_COL_NOISE)
+constexpr NoiseArgs nzA{};
 #endif
 template <int D, int KN>
 __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArgs A
 #if F64_ROW(F64_COL_CV)
                                                                  , const CvArgs cvA
+#elif F64_ROW(F64_COL_NOISE)
+                                                                 , const NoiseArgs nzA
 #endif
 ) {
     constexpr int H = nhyp<D, KN>();
@@ -1577,6 +1609,7 @@ __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArg
         else if (c.tid == 0) opt_fresh_tile(sh, A, H, t, o);
         if constexpr (H == D + 3) { if (!resumed && c.tid == 0) fresh_tile_extra<D, KN>(sh); }
         if constexpr (MEAN) c.yg = y + o0;
+        if constexpr (NOISE) c.vg = nzA.obs_var + o0;
         __syncthreads();
         const int seg_evals = sliced ? max(1, A.seg_cost / (NB * NB * NB)) : 0x7fffffff;
         bool suspended = false;
@@ -1745,7 +1778,7 @@ static hipError_t launch_kernel(void (*kernel)(Args...), int grid, size_t smem, 
 }
 
 template <int D, int KN>
-static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
+static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs* cv, [[maybe_unused]] const NoiseArgs* nz, int grid, size_t smem, hipStream_t stream) {
     if constexpr (D > D_MAX || !((KN_SET >> KN) & 1u)) {
         return hipErrorInvalidValue;
     } else {
@@ -1754,31 +1787,32 @@ static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs*
             else return hipErrorInvalidValue;
         }
         if constexpr (CV) return cv ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *cv) : hipErrorInvalidValue;
+        else if constexpr (NOISE) return nz && nz->obs_var ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *nz) : hipErrorInvalidValue;
         else return launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a);
     }
 }
 
 template <int D>
-static hipError_t launch_d(const KernelArgs& a, const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
+static hipError_t launch_d(const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, int grid, size_t smem, hipStream_t stream) {
     switch (a.kernel) {
-        case 0: return launch_one<D, 0>(a, cv, grid, smem, stream);
-        case 1: return launch_one<D, 1>(a, cv, grid, smem, stream);
-        case 2: return launch_one<D, 2>(a, cv, grid, smem, stream);
-        case 3: return launch_one<D, 3>(a, cv, grid, smem, stream);
-        case 4: return launch_one<D, 4>(a, cv, grid, smem, stream);
+        case 0: return launch_one<D, 0>(a, cv, nz, grid, smem, stream);
+        case 1: return launch_one<D, 1>(a, cv, nz, grid, smem, stream);
+        case 2: return launch_one<D, 2>(a, cv, nz, grid, smem, stream);
+        case 3: return launch_one<D, 3>(a, cv, nz, grid, smem, stream);
+        case 4: return launch_one<D, 4>(a, cv, nz, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace F64NS
 
-// `cv`: the held-out variant's arguments, null for every other
-hipError_t F64_ROW(F64_COL_ENTRY)(int D, const KernelArgs& a, const CvArgs* cv, int grid, size_t smem, hipStream_t stream) {
+// `cv`: the held-out variant's arguments, `nz`: the noise variant's; null for every other
+hipError_t F64_ROW(F64_COL_ENTRY)(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, int grid, size_t smem, hipStream_t stream) {
     switch (D) {
-        case 1: return F64NS::launch_d<1>(a, cv, grid, smem, stream);
-        case 2: return F64NS::launch_d<2>(a, cv, grid, smem, stream);
-        case 3: return F64NS::launch_d<3>(a, cv, grid, smem, stream);
-        case 4: return F64NS::launch_d<4>(a, cv, grid, smem, stream);
+        case 1: return F64NS::launch_d<1>(a, cv, nz, grid, smem, stream);
+        case 2: return F64NS::launch_d<2>(a, cv, nz, grid, smem, stream);
+        case 3: return F64NS::launch_d<3>(a, cv, nz, grid, smem, stream);
+        case 4: return F64NS::launch_d<4>(a, cv, nz, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -231,7 +231,7 @@ class Engine:
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
                           out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
-                          cv_refit=None, mean=None) -> BatchResult:
+                          cv_refit=None, mean=None, obs_var=None) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -266,7 +266,20 @@ class Engine:
         ones, ``f_mean`` includes it and a tile without observations predicts c of theta0.  fp64 and D <= 3 only, with
         ``full_cov`` and either optimiser, but without ``n_starts``, ``cv_fold``, ``cv_refit`` and "RationalQuadratic".  None:
         the zero-mean model, as ever.
+        ``obs_var`` [sumN] (gpsat_fit_predict_batch_noise): known noise variances per observation, float64, numpy or a device
+        tensor as the other bulk inputs are -- y ~ N(0, K + sn2 I + diag(obs_var)), finite and >= 0, not trained.  theta and H
+        are those of the plain call; likelihood_variance is what obs_var does not explain (fix it through ``trainable`` to
+        trust obs_var alone) and ``y_var`` = ``f_var`` + likelihood_variance.  fp64 only, D <= 4, with ``full_cov`` and either
+        optimiser, but without ``n_starts``, ``cv_fold``, ``cv_refit``, ``mean="constant"`` and "RationalQuadratic".  All
+        zeros return the bits of the plain call; None is the plain call.
         """
+        if obs_var is not None:
+            for what, on in (("dtype='f32'", dtype != "f64"), ("n_starts", n_starts is not None), ("cv_fold", cv_fold is not None),
+                             ("cv_refit", cv_refit is not None and cv_refit is not False), ("mean='constant'", mean == "constant"),
+                             ("kernel='RationalQuadratic'", L.KERNEL_IDS.get(kernel, kernel) == L.KERNEL_RQ)):
+                if on:
+                    raise GpsatError(f"obs_var and {what} cannot be combined: noise variances per observation are built for the "
+                                     f"plain fp64 fit / predict call with a stationary kernel")
         if mean not in L.MEAN_IDS:
             raise GpsatError(f"mean {mean!r}: use None or 'constant'")
         const_mean = L.MEAN_IDS[mean] == L.MEAN_CONSTANT
@@ -307,8 +320,13 @@ class Engine:
         np_dt = np.float32 if dtype == "f32" else np.float64
         device_mode = not isinstance(X, np.ndarray)
         if device_mode:
-            t_dt, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D)}, dtype, sumP, out)
+            t_dt, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D),
+                                           **({} if obs_var is None else {"obs_var": (obs_var, sumN)})}, dtype, sumP, out)
         else:
+            if obs_var is not None:
+                if np.size(obs_var) != sumN:
+                    raise GpsatError(f"obs_var: {np.size(obs_var)} variances for {sumN} rows")
+                obs_var = np.ascontiguousarray(obs_var, dtype=np.float64).reshape(sumN)
             if dtype == "f32" and sumN > 0 and np.asarray(X).dtype == np.float64:
                 # fp64 coordinates handed to the fp32 kernels: centre per tile before the cast (see centre_tiles)
                 X, Xs = centre_tiles(np.asarray(X, dtype=np.float64).reshape(sumN, D),
@@ -374,6 +392,13 @@ class Engine:
             f_start = np.full((T, max(int(n_starts), 1)), np.nan)
             ms.starts, ms.f_start = _ptr(st), _ptr(f_start)
             rc = self._lib.gpsat_fit_predict_batch_ms(self._h, C.byref(b), C.byref(ms))
+        elif obs_var is not None:
+            name = "gpsat_fit_predict_batch_noise"
+            if not hasattr(self._lib, name):
+                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_noise (noise variances per observation)")
+            nz = L.GpsatNoise()
+            nz.obs_var = obs_var.data_ptr() if device_mode else _ptr(obs_var)
+            rc = self._lib.gpsat_fit_predict_batch_noise(self._h, C.byref(b), C.byref(nz))
         elif const_mean:
             name = "gpsat_fit_predict_batch_mean"
             if not hasattr(self._lib, name):
@@ -451,11 +476,13 @@ class Engine:
     def sgpr_fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, z_off, Z, theta0, lo=None, hi=None,
                                trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000, max_ls=0,
                                ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False, jitter=0.0, out=None,
-                               dtype="f64", full_cov=False) -> BatchResult:
+                               dtype="f64", full_cov=False, obs_var=None) -> BatchResult:
         """Sparse GP experts (gpsat_sgpr_fit_predict_batch): GPflow SGPR with fixed inducing points Z [sumM, D] per tile
         (CSR ``z_off`` [T+1]).  Arguments and result as ``fit_predict_batch``, except: fp64 only, no ``full_cov``, no
         per-tile observation limit, ``nll`` is the negative ELBO.  Host coordinates are centred per tile (X, Xs and Z by
         the tile's mean observation coordinate) before the call; device tensors are taken as they are."""
+        if obs_var is not None:
+            raise NotImplementedError("sparse GP experts take no noise variances per observation (obs_var)")
         if dtype != "f64":
             raise NotImplementedError("sparse GP experts are built in fp64 only (dtype='f64')")
         if full_cov:

@@ -64,6 +64,11 @@ default 0; GPflow's mean_functions.Constant) are the same kind of profile -- one
 ``mean_constant`` (in scaled observation units), under the same rules: fp64, at most 3 coordinate columns, stored, loaded,
 averaged and constrained like the others; not combined with a replacement model, ``cv``, SGPR or RationalQuadratic
 (DESIGN.md section 15).  ``mean_function`` None and "Zero" are the zero mean; other names are not built.
+Known noise variances per observation (``data_config["obs_var_col"]``, a column of the data source with every row's noise
+variance in raw observation units, e.g. ``std**2 / count`` of binned data): the column travels with the observations into
+every tile, is divided by ``obs_scale**2`` and is added to the diagonal of K beside ``likelihood_variance``; it is not
+trained and no table changes.  Exact-GP experts in fp64 (``dtype`` None then means fp64); not combined with SGPR, ``cv``, a
+replacement model, RationalQuadratic or a constant mean.
 ``replacement_*`` model settings for tiles below ``replacement_threshold`` observations are honoured (one engine call
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
@@ -846,7 +851,8 @@ _Profile = make_dataclass("_Profile", [
 # row; prof_id indexes profiles; theta0, lo, hi [T, H] its start parameters and box.
 _Plan = make_dataclass("_Plan", [
     "ex", "locs", "off", "idx", "n_obs", "pcs", "n_pred", "kind", "prof_id", "profiles", "theta0", "lo", "hi", "save_params",
-    "want_cov", "coords_all", "obs_all", "config_id", "table_suffix", "optimise", "predict"])
+    "want_cov", "coords_all", "obs_all", "config_id", "table_suffix", "optimise", "predict", "var_all"])
+# var_all: the noise variance of every row of obs_all (data_config["obs_var_col"], raw observation units), or None
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -871,6 +877,25 @@ class BatchedLocalExpertOI:
         self.H = len(data_config["coords_col"]) + len(self.param_names) - 1
         if extra and self.sgpr:
             raise NotImplementedError(f"{who} is built for exact-GP experts only, not for SGPR")
+        # known noise variances per observation: a column of the data source that travels with the observations; exact GP in
+        # fp64 with a stationary kernel and a zero mean only
+        self.obs_var_col = data_config.get("obs_var_col")
+        if self.obs_var_col is not None:
+            nv = f"data_config.obs_var_col ({self.obs_var_col!r}: noise variances per observation)"
+            if not isinstance(self.obs_var_col, str):
+                raise ValueError(f"data_config.obs_var_col must be one column name, got {self.obs_var_col!r}")
+            if self.sgpr:
+                raise NotImplementedError(f"{nv} is built for exact-GP experts only, not for SGPR")
+            if extra:
+                raise NotImplementedError(f"{nv} and {who} cannot be combined")
+            if cv is not None:
+                raise NotImplementedError(f"cv: held-out predictions are not built for {nv}")
+            if model_config.get("replacement_threshold") is not None:
+                raise NotImplementedError(f"{nv} and a replacement model cannot be combined")
+            if dtype is None:
+                dtype = "f64"
+            if dtype == "f32":
+                raise NotImplementedError(f"{nv} is built in fp64 only: dtype must be None or 'f64'")
         # dtype None: fp32 for exact-GP experts, fp64 for sparse ones and those with an extra parameter (built in fp64 only --
         # an explicit fp32 is refused)
         if dtype is None:
@@ -925,6 +950,8 @@ class BatchedLocalExpertOI:
         static_gs, dynamic_gs = split_global_select(data_config.get("global_select"))
         df = data_select(_load_frame(data_config["data_source"]), static_gs)
         self.df = df
+        if self.obs_var_col is not None and self.obs_var_col not in df.columns:
+            raise KeyError(f"obs_var_col: column {self.obs_var_col!r} is not in the data source")
         missing = [c for c in self.cv_by if c not in df.columns]
         if missing:
             raise KeyError(f"cv: columns {missing} are not in the data source")
@@ -1229,10 +1256,15 @@ class BatchedLocalExpertOI:
         coords_all, obs_all = self.df.loc[:, cc].values.astype(np.float64), self.df[self.obs_col].values.astype(np.float64)
         assert not np.isnan(coords_all).any(), "nans found in coords"
         assert not np.isnan(obs_all).any(), "nans found in obs"
+        var_all = None
+        if self.obs_var_col is not None:
+            var_all = self.df[self.obs_var_col].values.astype(np.float64)
+            assert not np.isnan(var_all).any(), "nans found in obs_var"
+            assert np.isfinite(var_all).all() and not (var_all < 0).any(), "obs_var must be finite and not negative"
         return _Plan(ex=ex, locs=locs, off=off, idx=idx, n_obs=n_obs, pcs=pcs, n_pred=n_pred, kind=kind, prof_id=prof_id,
                      profiles=profiles, theta0=theta0, lo=lo, hi=hi, save_params=save_params, coords_all=coords_all,
                      want_cov=any(pf.full_cov for pf in profiles), obs_all=obs_all, config_id=config_id,
-                     table_suffix=table_suffix, optimise=optimise, predict=predict)
+                     table_suffix=table_suffix, optimise=optimise, predict=predict, var_all=var_all)
 
     def _select(self, refs, locs):
         """Membership CSR (off, idx) of every expert in ``refs`` and its prediction coordinates; with ``device_select`` the
@@ -1336,6 +1368,7 @@ class BatchedLocalExpertOI:
         out_dt = np.float32 if self.dtype == "f32" else np.float64
         X, y = np.empty((int(o_off[-1]), D), dtype=out_dt), np.empty(int(o_off[-1]), dtype=out_dt)
         Xs, mean = np.empty((int(p_off[-1]), D), dtype=out_dt), np.zeros(len(ids))
+        var = np.empty(int(o_off[-1]), dtype=np.float64) if plan.var_all is not None else None
         consecutive = len(ids) > 0 and bool(np.all(np.diff(ids) == 1))
         idx, off = plan.idx, plan.off
 
@@ -1364,6 +1397,8 @@ class BatchedLocalExpertOI:
                 Xd, Xsd = centre_tiles(Xd, Xsd, oo, p_off[a:b + 1] - p_off[a])
             X[o_off[a]:o_off[b]] = Xd
             y[o_off[a]:o_off[b]] = yd
+            if var is not None:
+                var[o_off[a]:o_off[b]] = plan.var_all[rows] / pf.obs_scale ** 2      # the rows of y, in y's scaled units
             Xs[p_off[a]:p_off[b]] = Xsd
 
         nsub = max(1, min(self.pack_threads, len(ids) // 128))
@@ -1374,6 +1409,8 @@ class BatchedLocalExpertOI:
             for f_ in [self._sub_pool().submit(sub, int(bounds[j]), int(bounds[j + 1])) for j in range(nsub)]:
                 f_.result()
         out = dict(o_off=o_off, X=X, y=y, p_off=p_off, Xs=Xs, mean=mean)
+        if var is not None:
+            out["obs_var"] = var
         if self.cv is not None:
             out["cv_fold"], out["cv_skipped"] = self._cv_labels(plan, ids, Ns)
         if pf.sgpr:
@@ -1690,6 +1727,8 @@ class _ShardRunner:
                   **pf.eng_kw)
         if self.oi.extra and self.oi.extra[0] == "mean_constant":
             kw["mean"] = "constant"
+        if "obs_var" in pk:
+            kw["obs_var"] = pk["obs_var"]
         eng_ = self.free_engines.get()
         try:
             te = time.perf_counter()

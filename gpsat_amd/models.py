@@ -15,6 +15,10 @@ Differences that are deliberate and documented in DESIGN.md:
     "RationalQuadratic"): one more parameter, ``mean_constant``, with its getter, setter and constraints, in the model's
     scaled observation units.  Other mean functions and custom likelihoods are not built
     (NotImplementedError);
+  * of the likelihoods, a Gaussian one whose variance is a known function of the row is built: ``obs_var`` (an array beside
+    ``obs``) or ``obs_var_col`` (a column of ``data``) gives every observation's noise variance in raw observation units,
+    added to the diagonal of K beside ``likelihood_variance`` and not trained (fp64; not with "RationalQuadratic",
+    ``mean_function="Constant"`` or ``cross_validate``; DESIGN.md section 17).  ``likelihood=`` itself stays refused;
   * no TensorFlow import, no per-construction device probe (the engine knows its device).
 """
 from __future__ import annotations
@@ -87,7 +91,16 @@ class HipGPRModel:
     def __init__(self, data=None, coords_col=None, obs_col=None, coords=None, obs=None,
                  coords_scale=None, obs_scale=None, obs_mean=None, verbose=True, *,
                  kernel="Matern32", kernel_kwargs=None, mean_function=None, mean_func_kwargs=None,
-                 noise_variance=None, likelihood=None, engine=None, dtype="f32", **kwargs):
+                 noise_variance=None, likelihood=None, engine=None, dtype="f32", obs_var=None, obs_var_col=None, **kwargs):
+        # ---- known noise variances per observation: an array beside coords / obs, or a column of data
+        if obs_var is not None and obs_var_col is not None:
+            raise AssertionError("obs_var and obs_var_col were both provided, give one")
+        if obs_var_col is not None:
+            if data is None:
+                raise AssertionError("obs_var_col names a column of data, but data was not provided")
+            if not isinstance(obs_var_col, str):
+                raise AssertionError(f"obs_var_col must be one column name, got {obs_var_col!r}")
+            obs_var = data.loc[:, obs_var_col].to_numpy()
         # ---- data intake (behaviour of GPSat/models/base_model.py:134-189): a frame + column names, or bare arrays
         if data is not None:
             if coords_col is None or obs_col is None:
@@ -121,6 +134,17 @@ class HipGPRModel:
         self.coords_scale = _as_scale_row(coords_scale)
         self.coords = np.array(raw_coords, dtype=np.float64) / self.coords_scale
         self.obs = (np.array(raw_obs, dtype=np.float64) - self.obs_mean) / self.obs_scale
+        # variances in raw observation units -> the model's scaled units
+        self.obs_var = None
+        if obs_var is not None:
+            raw_var = np.asarray(obs_var, dtype=np.float64).reshape(-1)
+            if len(raw_var) != len(raw_obs):
+                raise AssertionError(f"obs_var has {len(raw_var)} entries for {len(raw_obs)} observations")
+            if np.isnan(raw_var).any():
+                raise AssertionError("nans found in obs_var")
+            if not np.isfinite(raw_var).all() or (raw_var < 0).any():
+                raise AssertionError("obs_var must be finite and not negative")
+            self.obs_var = raw_var / float(self.obs_scale[0, 0]) ** 2
 
         # ---- kernel / defaults: gpflow_models.py:113-157
         assert kernel is not None, "kernel was not provided"
@@ -158,6 +182,12 @@ class HipGPRModel:
                 raise NotImplementedError(f"mean_func_kwargs {sorted(set(mk) - {'c'})}: 'Constant' takes 'c' only")
             c0 = np.asarray(0.0 if mk.get("c") is None else mk["c"], dtype=np.float64).reshape(-1)   # GPflow: c=None is 0
             assert len(c0) == 1, f"mean_func_kwargs['c'] must be a number or a sequence of one element, got {len(c0)}"
+        if self.obs_var is not None:
+            why = ("are built in fp64 only: pass dtype='f64'" if dtype != "f64" else
+                   f"are not built for kernel {kernel!r}" if self._rq else
+                   "are not built for mean_function='Constant'" if self._mean else None)
+            if why:
+                raise NotImplementedError(f"noise variances per observation (obs_var) {why}")
         kk = dict(kernel_kwargs or {})
         ls = np.broadcast_to(np.asarray(kk.get("lengthscales", np.ones(D)), dtype=np.float64), (D,)).copy()
         self._theta = np.concatenate([ls, [float(kk.get("variance", 1.0))],
@@ -343,7 +373,8 @@ class HipGPRModel:
             dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0],
             pred_off=np.array([0, P]), Xs=Xs, theta0=self._theta[None, :], lo=self._lo[None, :],
             hi=self._hi[None, :], trainable=self._trainable, kernel=self.kernel, optimiser=optimiser,
-            max_iter=max_iter, **({"mean": "constant"} if self._mean else {}), **opt_kwargs)
+            max_iter=max_iter, **({"mean": "constant"} if self._mean else {}),
+            **({} if self.obs_var is None else {"obs_var": self.obs_var}), **opt_kwargs)
 
     def _fix_hyperparameters(self, params_list):
         # gpflow_models.py:275-288
@@ -439,6 +470,8 @@ class HipGPRModel:
             raise NotImplementedError(f"held-out predictions are not built for kernel {self.kernel!r}")
         if self._mean:
             raise NotImplementedError("held-out predictions are not built for mean_function='Constant'")
+        if self.obs_var is not None:
+            raise NotImplementedError("held-out predictions are not built for noise variances per observation (obs_var)")
         if refit:
             return self._cross_validate_refit(fold, **refit_kwargs)
         if refit_kwargs:
@@ -504,7 +537,10 @@ class HipSGPRModel(HipGPRModel):
                  coords_scale=None, obs_scale=None, obs_mean=None, verbose=True, *,
                  kernel="Matern32", num_inducing_points=500, kernel_kwargs=None, mean_function=None,
                  mean_func_kwargs=None, noise_variance=None, likelihood=None, engine=None, dtype="f64",
-                 inducing_seed=0, expert_index=0, **kwargs):
+                 inducing_seed=0, expert_index=0, obs_var=None, obs_var_col=None, **kwargs):
+        if obs_var is not None or obs_var_col is not None:
+            raise NotImplementedError("noise variances per observation (obs_var, obs_var_col) are built for exact experts "
+                                      "(HipGPRModel) only, not for SGPR")
         if dtype != "f64":
             raise NotImplementedError("HipSGPRModel is built in fp64 only (dtype='f64')")
         if kernel == "RationalQuadratic":
@@ -596,7 +632,11 @@ class HipSklearnGPRModel(HipGPRModel):
     def __init__(self, data=None, coords_col=None, obs_col=None, coords=None, obs=None,
                  coords_scale=None, obs_scale=None, obs_mean=None, verbose=True, *,
                  kernel="Matern", kernel_kwargs=None, mean_value=None, kernel_variance=1., likelihood_variance=None,
-                 param_bounds=None, n_restarts_optimizer=2, random_state=None, engine=None, dtype="f64", **kwargs):
+                 param_bounds=None, n_restarts_optimizer=2, random_state=None, engine=None, dtype="f64",
+                 obs_var=None, obs_var_col=None, **kwargs):
+        if obs_var is not None or obs_var_col is not None:
+            raise NotImplementedError("noise variances per observation (obs_var, obs_var_col) are built for HipGPRModel only, "
+                                      "not for the sklearn model")
         kk = dict(kernel_kwargs or {})
         if kernel == "Matern":
             nu = float(kk.pop("nu", 1.5))

@@ -223,6 +223,31 @@ int gpsat_n_hyper_mean(int kernel, int D, int mean_kind);
 int gpsat_fit_predict_batch_mean(gpsat_handle *h, const gpsat_batch *b, const gpsat_mean *m);
 
 /*
+ * Known noise variances per observation (a Gaussian likelihood whose variance is a fixed function of the row; optimal
+ * interpolation's observation-error variance): the extension of gpsat_fit_predict_batch_noise.  Callers detect it by the
+ * presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ *
+ *     y ~ N(0, K_theta + sn2 I + diag(v)),   v_i >= 0 finite, given per row of y and not trained.
+ *
+ * theta, H = D + 2, the transforms, the lower bound of likelihood_variance, the optimisers and the status codes are those of
+ * gpsat_fit_predict_batch; likelihood_variance is the variance that v does not explain (fix it through `trainable` to trust
+ * v alone).  Objective and gradient are the plain formulas with K_y as above (dK_y/dtheta does not involve v).  Predictions:
+ * f* = k*^T K_y^-1 y, f_var = k** - k*^T K_y^-1 k*, y_var = f_var + sn2 (a new point carries the homogeneous part only);
+ * f_cov uses the same K_y; a tile without observations predicts the prior.  Built for GPSAT_F64, the kernels
+ * GPSAT_KERNEL_RBF .. GPSAT_KERNEL_MATERN52 and D <= 4, one workgroup per tile, with both optimisers and f_cov.
+ * v == 0 everywhere, and obs_var == NULL, return the bits of gpsat_fit_predict_batch in every output.
+ */
+typedef struct gpsat_noise {
+    const void *obs_var;       /* [sum N] doubles, host|device as b->memory; NULL = the plain call */
+    int32_t reserved[8];       /* must be 0                                                   */
+} gpsat_noise;                 /* 40 bytes */
+
+/* as gpsat_fit_predict_batch, with the noise variances above.  GPSAT_EINVAL (with a message that names the reason; the
+ * handle stays usable) for GPSAT_F32, GPSAT_KERNEL_RQ, a NULL nz, non-zero reserved words and, in host mode, a negative or
+ * non-finite entry of obs_var (the message names the tile and the row).  Device mode: obs_var is not inspected, as y is not. */
+int gpsat_fit_predict_batch_noise(gpsat_handle *h, const gpsat_batch *b, const gpsat_noise *nz);
+
+/*
  * Held-out (cross-validation) predictions from every tile's own factor: the extension of gpsat_fit_predict_batch_cv
  * (fp64 only).  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
  *
