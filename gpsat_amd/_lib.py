@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from . import variants
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPSAT_LIB: developer override to load the diagnostic build (scripts/phase_profile.py); never a fallback
 LIB_PATH = os.environ.get("GPSAT_LIB") or os.path.join(_HERE, "csrc", "libgpsat_hip.so")
@@ -24,18 +26,6 @@ OPT_NONE, OPT_LBFGS, OPT_ADAM = 0, 1, 2
 OPT_IDS = {"none": OPT_NONE, None: OPT_NONE, "lbfgs": OPT_LBFGS, "L-BFGS-B": OPT_LBFGS, "adam": OPT_ADAM}
 MEM_HOST, MEM_DEVICE = 0, 1
 STATUS = {0: "converged", 1: "max_iter", 2: "not_pd", 3: "nan", 4: "skipped", 5: "not_optimised", 6: "ls_failed"}
-
-EXPORTS = ["gpsat_version", "gpsat_last_error", "gpsat_device_count", "gpsat_create", "gpsat_device_name",
-           "gpsat_destroy", "gpsat_fit_predict_batch", "gpsat_last_timing", "gpsat_select_batch",
-           "gpsat_smooth_batch", "gpsat_glue_batch", "gpsat_max_tile_obs", "gpsat_sgpr_fit_predict_batch",
-           "gpsat_max_inducing", "gpsat_select_batch_ex", "gpsat_fit_predict_batch_ms", "gpsat_bin_batch",
-           "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold", "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit",
-           "gpsat_n_hyper", "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean", "gpsat_fit_predict_batch_noise"]
-# ABI additions that keep GPSAT_ABI_VERSION: callers detect them by their presence (engine: a clear error if absent)
-OPTIONAL_EXPORTS = ["gpsat_fit_predict_batch_ms", "gpsat_bin_batch", "gpsat_fit_predict_batch_cv", "gpsat_max_cv_fold",
-                    "gpsat_cv_refit_count", "gpsat_fit_predict_batch_cv_refit", "gpsat_n_hyper",
-                    "gpsat_n_hyper_mean", "gpsat_fit_predict_batch_mean", "gpsat_fit_predict_batch_noise"]
-
 
 class GpsatOpts(C.Structure):
     _fields_ = [("workgroups_per_cu", C.c_int32), ("reserved", C.c_int32 * 7)]
@@ -148,6 +138,38 @@ def _check_one_hip_runtime():
                       "the ROCm release PyTorch was built for (INTEGRATION.md, 'One HIP runtime per process').")
 
 
+_I, _I32, _I64, _U32, _D, _P, _S = C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_double, C.c_void_p, C.c_char_p
+_EXT = {v.entry: globals()[v.struct] for v in variants.VARIANTS.values() if v.entry}       # entry point -> its extension struct
+_SELECT = [_P, C.POINTER(GpsatSelectSpec), _I64, _I32, _P, _I32, _P]
+# name -> (restype, argtypes or None, required).  Not required: an ABI addition that keeps GPSAT_ABI_VERSION; callers detect
+# it by its presence (engine: a clear error if absent).
+SIGNATURES = {
+    "gpsat_version": (_I, None, True),
+    "gpsat_last_error": (_S, None, True),
+    "gpsat_device_count": (_I, None, True),
+    "gpsat_create": (_I, [_I, C.POINTER(GpsatOpts), C.POINTER(_P)], True),
+    "gpsat_device_name": (_I, [_P, _S, _I], True),
+    "gpsat_destroy": (_I, [_P], True),
+    "gpsat_fit_predict_batch": (_I, [_P, C.POINTER(GpsatBatch)], True),
+    "gpsat_last_timing": (_I, [_P, C.POINTER(_D), C.POINTER(_D)], True),
+    "gpsat_select_batch": (_I, _SELECT + [_P, _P, _I64], True),
+    "gpsat_select_batch_ex": (_I, _SELECT + [_I32, _P, _P, _P, _I64], True),
+    "gpsat_smooth_batch": (_I, [_P, _I32, _P, _P, _P, _D, _D, _P], True),
+    "gpsat_glue_batch": (_I, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _D, _P, _P], True),
+    "gpsat_max_tile_obs": (_I, [_I, _I], True),
+    "gpsat_max_inducing": (_I, [_I, _I], True),
+    "gpsat_max_cv_fold": (_I, [_I, _I], False),
+    "gpsat_cv_refit_count": (_I, [_I32, _P, _P, _P, C.POINTER(_I64)], False),
+    "gpsat_n_hyper": (_I, [_I, _I], False),
+    "gpsat_n_hyper_mean": (_I, [_I, _I, _I], False),
+    "gpsat_bin_batch": (_I, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _D, _I32, _P, _D, _U32, _I64, _P, _P, _P], False),
+    # the entry points of the variant table: (handle, batch, extension struct); the sparse one has been there since ABI 4
+    **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(st)], name == "gpsat_sgpr_fit_predict_batch") for name, st in _EXT.items()},
+}
+EXPORTS = list(SIGNATURES)
+OPTIONAL_EXPORTS = [name for name, (_, _, required) in SIGNATURES.items() if not required]
+
+
 def load():
     if not os.path.exists(LIB_PATH):
         raise LibraryMissing(
@@ -156,80 +178,31 @@ def load():
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     _check_one_hip_runtime()
-    for name in EXPORTS:
-        if name not in OPTIONAL_EXPORTS and not hasattr(lib, name):
+    for name, (_, _, required) in SIGNATURES.items():
+        if required and not hasattr(lib, name):
             raise LibraryMissing(f"{LIB_PATH} does not export {name}")
-    lib.gpsat_version.restype = C.c_int
-    lib.gpsat_last_error.restype = C.c_char_p
-    lib.gpsat_device_count.restype = C.c_int
-    lib.gpsat_create.restype = C.c_int
-    lib.gpsat_create.argtypes = [C.c_int, C.POINTER(GpsatOpts), C.POINTER(C.c_void_p)]
-    lib.gpsat_device_name.restype = C.c_int
-    lib.gpsat_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.gpsat_destroy.restype = C.c_int
-    lib.gpsat_destroy.argtypes = [C.c_void_p]
-    lib.gpsat_fit_predict_batch.restype = C.c_int
-    lib.gpsat_fit_predict_batch.argtypes = [C.c_void_p, C.POINTER(GpsatBatch)]
-    lib.gpsat_select_batch.restype = C.c_int
-    lib.gpsat_select_batch.argtypes = [C.c_void_p, C.POINTER(GpsatSelectSpec), C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    lib.gpsat_select_batch_ex.restype = C.c_int
-    lib.gpsat_select_batch_ex.argtypes = [C.c_void_p, C.POINTER(GpsatSelectSpec), C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    lib.gpsat_smooth_batch.restype = C.c_int
-    lib.gpsat_smooth_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
-    lib.gpsat_glue_batch.restype = C.c_int
-    lib.gpsat_glue_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
-    lib.gpsat_max_tile_obs.restype = C.c_int
-    lib.gpsat_max_tile_obs.argtypes = [C.c_int, C.c_int]
-    lib.gpsat_sgpr_fit_predict_batch.restype = C.c_int
-    lib.gpsat_sgpr_fit_predict_batch.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatSparse)]
-    lib.gpsat_max_inducing.restype = C.c_int
-    lib.gpsat_max_inducing.argtypes = [C.c_int, C.c_int]
-    if hasattr(lib, "gpsat_fit_predict_batch_ms"):
-        lib.gpsat_fit_predict_batch_ms.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMultistart)]
-        lib.gpsat_fit_predict_batch_ms.restype = C.c_int
-    if hasattr(lib, "gpsat_fit_predict_batch_cv"):
-        lib.gpsat_fit_predict_batch_cv.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatCv)]
-        lib.gpsat_fit_predict_batch_cv.restype = C.c_int
-        lib.gpsat_max_cv_fold.argtypes = [C.c_int, C.c_int]
-        lib.gpsat_max_cv_fold.restype = C.c_int
-    if hasattr(lib, "gpsat_fit_predict_batch_cv_refit"):
-        lib.gpsat_cv_refit_count.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
-        lib.gpsat_cv_refit_count.restype = C.c_int
-        lib.gpsat_fit_predict_batch_cv_refit.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatCvRefit)]
-        lib.gpsat_fit_predict_batch_cv_refit.restype = C.c_int
-    if hasattr(lib, "gpsat_n_hyper"):
-        lib.gpsat_n_hyper.argtypes = [C.c_int, C.c_int]
-        lib.gpsat_n_hyper.restype = C.c_int
-    if hasattr(lib, "gpsat_fit_predict_batch_mean"):
-        lib.gpsat_n_hyper_mean.argtypes = [C.c_int, C.c_int, C.c_int]
-        lib.gpsat_n_hyper_mean.restype = C.c_int
-        lib.gpsat_fit_predict_batch_mean.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatMean)]
-        lib.gpsat_fit_predict_batch_mean.restype = C.c_int
-    if hasattr(lib, "gpsat_fit_predict_batch_noise"):
-        lib.gpsat_fit_predict_batch_noise.argtypes = [C.c_void_p, C.POINTER(GpsatBatch), C.POINTER(GpsatNoise)]
-        lib.gpsat_fit_predict_batch_noise.restype = C.c_int
-    if hasattr(lib, "gpsat_bin_batch"):
-        lib.gpsat_bin_batch.restype = C.c_int
-        lib.gpsat_bin_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                        C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_double, C.c_uint32,
-                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.gpsat_last_timing.restype = C.c_int
-    lib.gpsat_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    for name, (restype, argtypes, _) in SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     if lib.gpsat_version() != ABI_VERSION:
         raise LibraryMissing(f"ABI version mismatch: library {lib.gpsat_version()} != binding {ABI_VERSION}")
     return lib
 
 
 def n_hyper(kernel, D: int, mean=None) -> int:
-    """Hyper-parameters per tile (gpsat_n_hyper, gpsat_n_hyper_mean): D + 3 for "RationalQuadratic" (lengthscales, kernel
-    variance, likelihood variance, alpha) and for ``mean="constant"`` with another kernel (..., likelihood variance, c), D + 2
-    otherwise.  Host arithmetic, the same rule as the library's for the arguments it supports: shapes can be laid out without
-    loading it."""
+    """Hyper-parameters per tile (gpsat_n_hyper, gpsat_n_hyper_mean) of a kernel (name or id) and a mean: the layout of
+    variants.n_hyper.  Host arithmetic, the same rule as the library's for the arguments it supports: shapes can be laid out
+    without loading it."""
+    return variants.n_hyper(D, theta_variants(kernel, mean))
+
+
+def theta_variants(kernel, mean=None) -> list:
+    """The rows of variants.VARIANTS that a kernel (name or id) and a mean ask for: those that change the layout of theta."""
     kid = KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-    return int(D) + (3 if kid == KERNEL_RQ or MEAN_IDS[mean] == MEAN_CONSTANT else 2)
+    return ["rq"] * (kid == KERNEL_RQ) + ["mean"] * (MEAN_IDS[mean] == MEAN_CONSTANT)
 
 
 def max_tile_obs(dtype: str, D: int) -> int:

@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from . import variants as V
 
 
 class GpsatError(RuntimeError):
@@ -124,15 +125,47 @@ def cv_refit_options(cv_refit) -> dict:
     return opts
 
 
+NP_DTYPES = {"f32": np.float32, "f64": np.float64}
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _bulk_ptr(a):
+    """Pointer to a bulk input or output: host numpy, or a device tensor."""
+    return _ptr(a) if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def _alloc(n, dtype, beside=None, at_least=0):
+    """An output of ``n`` elements (at least ``at_least``) of ``dtype``: numpy on the host, or a torch tensor beside the
+    device tensor ``beside`` -- there of one element at least, so that its pointer is valid.  Callers hand out ``[:n]``."""
+    if beside is None:
+        return np.empty(max(n, at_least), dtype=NP_DTYPES[dtype])
+    import torch
+    return torch.empty(max(n, 1), dtype=beside.dtype, device=beside.device)
+
+
+def _fold_labels(cv_fold, sumN):
+    """``cv_fold`` as the C ABI takes it: None for "loo", else contiguous int32 labels [sumN]."""
+    if isinstance(cv_fold, str) and cv_fold == "loo":
+        return None
+    raw = np.asarray(cv_fold).reshape(-1)
+    if not np.issubdtype(raw.dtype, np.integer):
+        raise GpsatError(f"cv_fold: integer labels wanted, got dtype {raw.dtype} (factorise_folds makes them)")
+    if raw.size and (int(raw.max()) > 2 ** 31 - 1 or int(raw.min()) < -2 ** 31):
+        raise GpsatError("cv_fold: labels must fit int32 (the C ABI's label type); factorise_folds makes dense codes")
+    labels = np.ascontiguousarray(raw, dtype=np.int32)
+    if labels.shape != (sumN,):
+        raise GpsatError(f"cv_fold: {labels.size} labels for {sumN} rows")
+    return labels
+
+
 def _host_meta(D, offs, theta0, lo, hi, trainable, H=None):
     """The CSR offset tables as contiguous int64, theta0 / lo / hi as [T, H] fp64 (no bounds: NaN) and trainable as [H] uint8.
-    ``H``: hyper-parameters per tile (_lib.n_hyper), D + 2 by default."""
+    ``H``: hyper-parameters per tile (variants.n_hyper), by default those of the plain call."""
     offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
-    T, H = len(offs[0]) - 1, (D + 2 if H is None else int(H))
+    T, H = len(offs[0]) - 1, (V.n_hyper(D) if H is None else int(H))
     assert all(len(o) == T + 1 for o in offs)
 
     def per_tile(a):
@@ -175,7 +208,7 @@ class Engine:
 
     def _device_io(self, inputs, dtype, sumP, out):
         """Device mode: check the input tensors (name -> (tensor, elements)), take or allocate the three prediction outputs
-        and wait for the caller's stream.  Returns (torch dtype, (f_mean, f_var, y_var))."""
+        and wait for the caller's stream.  Returns (f_mean, f_var, y_var)."""
         import torch
         t_dt = torch.float32 if dtype == "f32" else torch.float64
         for tname, (t_, _) in inputs.items():
@@ -186,10 +219,21 @@ class Engine:
             raise GpsatError(f"tensors live on cuda:{dev.index}, engine on device {self.device_id}")
         assert all(t_.numel() == n for t_, n in inputs.values())
         if out is None:
-            fm = torch.empty(max(sumP, 1), dtype=t_dt, device=dev)
-            out = fm, torch.empty_like(fm), torch.empty_like(fm)
+            out = tuple(_alloc(sumP, dtype, inputs["X"][0]) for _ in range(3))
         torch.cuda.current_stream(dev).synchronize()   # inputs must be complete before our stream reads them
-        return t_dt, tuple(out)
+        return tuple(out)
+
+    def _stage(self, D, dtype, sumN, sumP, X, y, Xs, out, more=None):
+        """The bulk inputs and the three prediction outputs as the library takes them: (device_mode, (X, y, Xs), preds).
+        Device mode (``X`` is not a numpy array): the tensors, and those of ``more`` (name -> (tensor, elements)), are
+        checked and taken as they are.  Host mode: X, y and Xs are cast to ``dtype`` and laid out contiguously."""
+        if not isinstance(X, np.ndarray):
+            return True, (X, y, Xs), self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D), **(more or {})},
+                                                     dtype, sumP, out)
+        np_dt = NP_DTYPES[dtype]
+        data = (np.ascontiguousarray(X, dtype=np_dt).reshape(sumN, D), np.ascontiguousarray(y, dtype=np_dt).reshape(sumN),
+                np.ascontiguousarray(Xs, dtype=np_dt).reshape(sumP, D))
+        return False, data, tuple(_alloc(sumP, dtype) for _ in range(3))
 
     @staticmethod
     def _fill_batch(D, dtype, device_mode, meta, data, preds, kernel, optimiser, max_iter, max_ls, ftol, gtol, adam_lr, want_grad):
@@ -201,7 +245,6 @@ class Engine:
         res = dict(theta=np.empty((T, H), dtype=np.float64), nll=np.empty(T, dtype=np.float64),
                    grad=np.empty((T, H), dtype=np.float64) if want_grad else None, status=np.empty(T, dtype=np.int32),
                    n_eval=np.empty(T, dtype=np.int32), n_iter=np.zeros(T, dtype=np.int32))
-        ptr = (lambda a: a.data_ptr()) if device_mode else _ptr
         b = L.GpsatBatch()
         b.T, b.D, b.dtype = T, D, (L.F32 if dtype == "f32" else L.F64)
         b.kernel = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
@@ -211,10 +254,10 @@ class Engine:
         b.ftol, b.gtol, b.adam_lr = float(ftol), float(gtol), float(adam_lr)
         b.obs_off, b.pred_off = _ptr(obs_off), _ptr(pred_off)
         b.theta0, b.lo, b.hi, b.trainable = _ptr(theta0), _ptr(lo), _ptr(hi), _ptr(trainable)
-        b.X, b.y, b.Xs = (ptr(a) for a in data)
+        b.X, b.y, b.Xs = (_bulk_ptr(a) for a in data)
         b.theta, b.nll, b.grad = _ptr(res["theta"]), _ptr(res["nll"]), _ptr(res["grad"])
         b.status, b.n_eval, b.n_iter = _ptr(res["status"]), _ptr(res["n_eval"]), _ptr(res["n_iter"])
-        b.f_mean, b.f_var, b.y_var = (ptr(a) for a in preds)
+        b.f_mean, b.f_var, b.y_var = (_bulk_ptr(a) for a in preds)
         b.cov_off, b.f_cov = None, None
         return b, res
 
@@ -226,6 +269,73 @@ class Engine:
         self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
         fm, fv, yv = preds if len(preds[0]) == sumP else (a[:sumP] for a in preds)     # device outputs hold at least one element
         return BatchResult(f_mean=fm, f_var=fv, y_var=yv, kernel_ms=km.value, total_ms=tm.value, **res, **more)
+
+    @staticmethod
+    def _check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov):
+        """The rows of variants.VARIANTS the call asks for, and the options of ``cv_refit`` (None without it).  Raises for
+        what the wrapper refuses itself; what one library call can express is left to the library's own message."""
+        if dtype not in NP_DTYPES:
+            raise GpsatError(f"dtype {dtype!r}: use 'f32' or 'f64'")
+        if mean not in L.MEAN_IDS:
+            raise GpsatError(f"mean {mean!r}: use None or 'constant'")
+        refit = None if cv_refit is None or cv_refit is False else cv_refit_options(cv_refit)
+        on = {"noise": obs_var is not None, "cv": cv_fold is not None and refit is None, "cv_refit": refit is not None,
+              "multistart": n_starts is not None, "full_cov": bool(full_cov)}
+        asked = L.theta_variants(kernel, mean) + [k for k in on if on[k]]
+        why = V.why_refused(asked, dtype, None, host_only=True)
+        if why:
+            raise GpsatError(why)
+        if refit is not None and cv_fold is None:
+            raise GpsatError("cv_refit needs the fold labels: cv_fold is None")
+        if refit is not None and isinstance(cv_fold, str):
+            raise GpsatError(f"cv_refit is not built for cv_fold={cv_fold!r}: give integer fold labels")
+        return asked, refit
+
+    @staticmethod
+    def _check_widths(asked, kernel, D, **arrays):
+        """theta0 / lo / hi / trainable of a variant with a parameter of its own: say which width is expected, by name."""
+        names = V.param_names(asked)
+        if len(names) == len(V.BASE_PARAMS):
+            return
+        H = V.n_hyper(D, asked)
+        for pname, a in arrays.items():
+            shp = None if a is None else np.shape(a)
+            if shp is not None and (len(shp) not in ((1,) if pname == "trainable" else (1, 2)) or shp[-1] != H):
+                raise GpsatError(f"{pname} has shape {shp}: kernel {kernel!r}" + (" with mean='constant'" if "mean" in asked else "")
+                                 + f" with D = {D} has H = D + {H - D} = {H} parameters per tile ({', '.join(names)}), so (H,)"
+                                 + ("" if pname == "trainable" else " or (T, H)") + " is expected")
+
+    def _entry(self, asked):
+        """(row key, name) of the library call that carries ``asked``: the one row with an entry point of its own, else
+        the plain call."""
+        key = next((k for k in asked if V.VARIANTS[k].entry), None)
+        name = V.VARIANTS[key].entry if key else V.PLAIN_ENTRY
+        if not hasattr(self._lib, name):
+            raise GpsatError(f"this libgpsat_hip.so has no {name} ({V.VARIANTS[key].label})")
+        return key, name
+
+    @staticmethod
+    def _extension(key, T, H, sumN, dtype, beside, n_starts, starts, obs_var, labels):
+        """The extension struct of row ``key``, the BatchResult fields it fills and what else the struct points to (the
+        caller holds all three until the library call has returned)."""
+        ext, fields, keep = getattr(L, V.VARIANTS[key].struct)(), {}, None
+        if key == "multistart":
+            S = int(n_starts)
+            ext.n_starts, ext.transform = S, L.TRANSFORM_LOG
+            if starts is not None and S > 1:
+                keep = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(T, S - 1, H))
+            fields["f_start"] = np.full((T, max(S, 1)), np.nan)
+            ext.starts, ext.f_start = _ptr(keep), _ptr(fields["f_start"])
+        elif key == "noise":
+            ext.obs_var = _bulk_ptr(obs_var)
+        elif key == "mean":
+            ext.kind = L.MEAN_CONSTANT
+        elif key == "cv":
+            cvo = tuple(_alloc(sumN, dtype, beside) for _ in range(3))
+            ext.fold = _ptr(labels)
+            ext.cv_mean, ext.cv_f_var, ext.cv_y_var = (_bulk_ptr(a) for a in cvo)
+            fields.update(cv_mean=cvo[0][:sumN], cv_f_var=cvo[1][:sumN], cv_y_var=cvo[2][:sumN])
+        return ext, fields, keep
 
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
@@ -256,73 +366,28 @@ class Engine:
         and ``cv_label`` describe every fold.  When the folds' remaining rows sum to more than ``max_expanded_rows``
         (default CV_REFIT_MAX_EXPANDED_ROWS = 2^25 rows: (D + 1) elements each on the device, 0.5 GiB in fp32 and 1 GiB
         in fp64 at D = 3), consecutive ranges of tiles are run by one library call each and the results concatenated; a
-        single tile above the budget is an error.  Refused with cv_fold="loo", ``n_starts`` and ``full_cov``.
+        single tile above the budget is an error.  Refused with cv_fold="loo".
         ``kernel="RationalQuadratic"``: one more hyper-parameter per tile, H = D + 3 with alpha last, so theta0 / lo / hi are
-        (H,) or (T, H) and trainable is (H,); fp64 and D <= 3 only, with ``full_cov`` but without ``n_starts``, ``cv_fold``
-        and ``cv_refit`` (the library refuses those with its own message).
+        (H,) or (T, H) and trainable is (H,); fp64 and D <= 3 only.
         ``mean="constant"`` (gpsat_fit_predict_batch_mean): a trainable constant mean c, GPflow's mean_functions.Constant --
         y ~ N(c 1, K + sn2 I).  One more hyper-parameter per tile, H = D + 3 with c last and in the units of y, so theta0 / lo /
         hi are (H,) or (T, H) and trainable is (H,); c is unconstrained with NaN bounds (any finite value) and boxed with finite
         ones, ``f_mean`` includes it and a tile without observations predicts c of theta0.  fp64 and D <= 3 only, with
-        ``full_cov`` and either optimiser, but without ``n_starts``, ``cv_fold``, ``cv_refit`` and "RationalQuadratic".  None:
-        the zero-mean model, as ever.
+        either optimiser.  None: the zero-mean model, as ever.
         ``obs_var`` [sumN] (gpsat_fit_predict_batch_noise): known noise variances per observation, float64, numpy or a device
         tensor as the other bulk inputs are -- y ~ N(0, K + sn2 I + diag(obs_var)), finite and >= 0, not trained.  theta and H
         are those of the plain call; likelihood_variance is what obs_var does not explain (fix it through ``trainable`` to
-        trust obs_var alone) and ``y_var`` = ``f_var`` + likelihood_variance.  fp64 only, D <= 4, with ``full_cov`` and either
-        optimiser, but without ``n_starts``, ``cv_fold``, ``cv_refit``, ``mean="constant"`` and "RationalQuadratic".  All
+        trust obs_var alone) and ``y_var`` = ``f_var`` + likelihood_variance.  fp64 only, D <= 4, with either optimiser.  All
         zeros return the bits of the plain call; None is the plain call.
+        Which of these arguments cannot be combined is the table of gpsat_amd/variants.py: a pairing
+        that one library call cannot express is refused here, any other by the library with its own message.
         """
-        if obs_var is not None:
-            for what, on in (("dtype='f32'", dtype != "f64"), ("n_starts", n_starts is not None), ("cv_fold", cv_fold is not None),
-                             ("cv_refit", cv_refit is not None and cv_refit is not False), ("mean='constant'", mean == "constant"),
-                             ("kernel='RationalQuadratic'", L.KERNEL_IDS.get(kernel, kernel) == L.KERNEL_RQ)):
-                if on:
-                    raise GpsatError(f"obs_var and {what} cannot be combined: noise variances per observation are built for the "
-                                     f"plain fp64 fit / predict call with a stationary kernel")
-        if mean not in L.MEAN_IDS:
-            raise GpsatError(f"mean {mean!r}: use None or 'constant'")
-        const_mean = L.MEAN_IDS[mean] == L.MEAN_CONSTANT
-        if const_mean:
-            for what, on in (("n_starts", n_starts is not None), ("cv_fold", cv_fold is not None),
-                             ("cv_refit", cv_refit is not None and cv_refit is not False),
-                             ("kernel='RationalQuadratic'", L.KERNEL_IDS.get(kernel, kernel) == L.KERNEL_RQ)):
-                if on:
-                    raise GpsatError(f"mean='constant' and {what} cannot be combined: the constant mean is built for the plain "
-                                     f"fit / predict call with a stationary kernel")
-        refit = None
-        if cv_refit is not None and cv_refit is not False:
-            refit = cv_refit_options(cv_refit)
-            if cv_fold is None:
-                raise GpsatError("cv_refit needs the fold labels: cv_fold is None")
-            if isinstance(cv_fold, str):
-                raise GpsatError(f"cv_refit is not built for cv_fold={cv_fold!r}: give integer fold labels")
-            if n_starts is not None:
-                raise GpsatError("cv_refit and n_starts cannot be combined")
-            if full_cov:
-                raise GpsatError("cv_refit and full_cov cannot be combined")
-        H = L.n_hyper(kernel, D, mean)
-        last = "c: the constant mean" if const_mean else "alpha"
-        if H == D + 3:
-            for pname, a in (("theta0", theta0), ("lo", lo), ("hi", hi), ("trainable", trainable)):
-                shp = None if a is None else np.shape(a)
-                if shp is not None and (len(shp) not in ((1,) if pname == "trainable" else (1, 2)) or shp[-1] != H):
-                    raise GpsatError(f"{pname} has shape {shp}: kernel {kernel!r}" + (" with mean='constant'" if const_mean else "")
-                                     + f" with D = {D} has H = D + 3 = {H} parameters per "
-                                     f"tile (lengthscales, kernel_variance, likelihood_variance, {last}), so (H,)"
-                                     + ("" if pname == "trainable" else " or (T, H)") + " is expected")
-        meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, H)
+        asked, refit = self._check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov)
+        self._check_widths(asked, kernel, D, theta0=theta0, lo=lo, hi=hi, trainable=trainable)
+        meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, V.n_hyper(D, asked))
         obs_off, pred_off = meta[0]
-        T = len(obs_off) - 1
-        sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
-        if dtype not in ("f32", "f64"):
-            raise GpsatError(f"dtype {dtype!r}: use 'f32' or 'f64'")
-        np_dt = np.float32 if dtype == "f32" else np.float64
-        device_mode = not isinstance(X, np.ndarray)
-        if device_mode:
-            t_dt, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D),
-                                           **({} if obs_var is None else {"obs_var": (obs_var, sumN)})}, dtype, sumP, out)
-        else:
+        T, H, sumN, sumP = len(obs_off) - 1, meta[1].shape[1], int(obs_off[-1]), int(pred_off[-1])
+        if isinstance(X, np.ndarray):
             if obs_var is not None:
                 if np.size(obs_var) != sumN:
                     raise GpsatError(f"obs_var: {np.size(obs_var)} variances for {sumN} rows")
@@ -331,85 +396,29 @@ class Engine:
                 # fp64 coordinates handed to the fp32 kernels: centre per tile before the cast (see centre_tiles)
                 X, Xs = centre_tiles(np.asarray(X, dtype=np.float64).reshape(sumN, D),
                                      np.asarray(Xs, dtype=np.float64).reshape(sumP, D), obs_off, pred_off)
-            X = np.ascontiguousarray(X, dtype=np_dt).reshape(sumN, D)
-            y = np.ascontiguousarray(y, dtype=np_dt).reshape(sumN)
-            Xs = np.ascontiguousarray(Xs, dtype=np_dt).reshape(sumP, D)
-            preds = tuple(np.empty(sumP, dtype=np_dt) for _ in range(3))
-        b, res = self._fill_batch(D, dtype, device_mode, meta, (X, y, Xs), preds, kernel, optimiser, max_iter, max_ls, ftol, gtol,
-                                  adam_lr, want_grad)
-        cov_off = fc = None
+        device_mode, data, preds = self._stage(D, dtype, sumN, sumP, X, y, Xs, out,
+                                               None if obs_var is None else {"obs_var": (obs_var, sumN)})
+        beside = data[0] if device_mode else None
+        run = (kernel, optimiser, max_iter, max_ls, ftol, gtol, adam_lr, want_grad)
+        b, res = self._fill_batch(D, dtype, device_mode, meta, data, preds, *run)
+        fields = {}
         if full_cov:
             Pt = np.diff(pred_off)
             cov_off = np.concatenate([[0], np.cumsum(Pt * Pt)]).astype(np.int64)
-            if device_mode:
-                import torch
-                fc = torch.empty(max(int(cov_off[-1]), 1), dtype=t_dt, device=X.device)
-            else:
-                fc = np.empty(max(int(cov_off[-1]), 1), dtype=np_dt)
-            b.cov_off, b.f_cov = _ptr(cov_off), (fc.data_ptr() if device_mode else _ptr(fc))
-        f_start = None
-        name = "gpsat_fit_predict_batch"
-        if cv_fold is not None:
-            name = "gpsat_fit_predict_batch_cv_refit" if refit else "gpsat_fit_predict_batch_cv"
-            if not hasattr(self._lib, name):
-                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_cv (held-out predictions)")
-            if n_starts is not None:
-                raise GpsatError("cv_fold and n_starts cannot be combined")
-            labels = None
-            if not (isinstance(cv_fold, str) and cv_fold == "loo"):
-                raw = np.asarray(cv_fold).reshape(-1)
-                if not np.issubdtype(raw.dtype, np.integer):
-                    raise GpsatError(f"cv_fold: integer labels wanted, got dtype {raw.dtype} (factorise_folds makes them)")
-                if raw.size and (int(raw.max()) > 2 ** 31 - 1 or int(raw.min()) < -2 ** 31):
-                    raise GpsatError("cv_fold: labels must fit int32 (the C ABI's label type); factorise_folds makes dense codes")
-                labels = np.ascontiguousarray(raw, dtype=np.int32)
-                if labels.shape != (sumN,):
-                    raise GpsatError(f"cv_fold: {labels.size} labels for {sumN} rows")
-            if refit:
-                return self._cv_refit(D, dtype, device_mode, meta, (X, y, Xs), preds, labels, refit,
-                                      (kernel, optimiser, max_iter, max_ls, ftol, gtol, adam_lr, want_grad))
-            if device_mode:
-                import torch
-                cvo = tuple(torch.empty(max(sumN, 1), dtype=t_dt, device=X.device) for _ in range(3))
-            else:
-                cvo = tuple(np.empty(sumN, dtype=np_dt) for _ in range(3))
-            cv = L.GpsatCv()
-            cv.fold = _ptr(labels)
-            cv.cv_mean, cv.cv_f_var, cv.cv_y_var = ((a.data_ptr() if device_mode else _ptr(a)) for a in cvo)
-            rc = self._lib.gpsat_fit_predict_batch_cv(self._h, C.byref(b), C.byref(cv))
-            cvo = tuple(a[:sumN] for a in cvo)
-            return self._result(rc, name, res, preds, sumP, f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off,
-                                cv_mean=cvo[0], cv_f_var=cvo[1], cv_y_var=cvo[2])
-        if n_starts is not None:
-            name = "gpsat_fit_predict_batch_ms"
-            if not hasattr(self._lib, name):
-                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_ms (multi-start L-BFGS-B)")
-            ms = L.GpsatMultistart()
-            ms.n_starts, ms.transform = int(n_starts), L.TRANSFORM_LOG
-            st = None
-            if starts is not None and int(n_starts) > 1:
-                st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(T, max(int(n_starts) - 1, 0), H))
-            f_start = np.full((T, max(int(n_starts), 1)), np.nan)
-            ms.starts, ms.f_start = _ptr(st), _ptr(f_start)
-            rc = self._lib.gpsat_fit_predict_batch_ms(self._h, C.byref(b), C.byref(ms))
-        elif obs_var is not None:
-            name = "gpsat_fit_predict_batch_noise"
-            if not hasattr(self._lib, name):
-                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_noise (noise variances per observation)")
-            nz = L.GpsatNoise()
-            nz.obs_var = obs_var.data_ptr() if device_mode else _ptr(obs_var)
-            rc = self._lib.gpsat_fit_predict_batch_noise(self._h, C.byref(b), C.byref(nz))
-        elif const_mean:
-            name = "gpsat_fit_predict_batch_mean"
-            if not hasattr(self._lib, name):
-                raise GpsatError("this libgpsat_hip.so has no gpsat_fit_predict_batch_mean (trainable constant mean)")
-            mn = L.GpsatMean()
-            mn.kind = L.MEAN_CONSTANT
-            rc = self._lib.gpsat_fit_predict_batch_mean(self._h, C.byref(b), C.byref(mn))
-        else:
-            rc = self._lib.gpsat_fit_predict_batch(self._h, C.byref(b))
-        return self._result(rc, name, res, preds, sumP, f_start=f_start,
-                            f_cov=(fc[:int(cov_off[-1])] if full_cov else None), cov_off=cov_off)
+            fc = _alloc(int(cov_off[-1]), dtype, beside, at_least=1)
+            b.cov_off, b.f_cov = _ptr(cov_off), _bulk_ptr(fc)
+            fields.update(cov_off=cov_off, f_cov=fc[:int(cov_off[-1])])
+        key, name = self._entry(asked)
+        labels = None if cv_fold is None else _fold_labels(cv_fold, sumN)
+        if refit:
+            return self._cv_refit(D, dtype, device_mode, meta, data, preds, labels, refit, run)
+        args = [self._h, C.byref(b)]
+        if key:
+            ext, more, keep = self._extension(key, T, H, sumN, dtype, beside, n_starts, starts, obs_var, labels)
+            fields.update(more)
+            args.append(C.byref(ext))
+        rc = getattr(self._lib, name)(*args)
+        return self._result(rc, name, res, preds, sumP, **fields)
 
     def _cv_refit(self, D, dtype, device_mode, meta, data, preds, labels, opts, run) -> BatchResult:
         """gpsat_fit_predict_batch_cv_refit over consecutive ranges of tiles, each within ``max_expanded_rows``."""
@@ -437,16 +446,10 @@ class Engine:
             acc += int(per_tile[t])
         ranges.append((t0, T))
         F = int(fold_off[-1])
-        np_dt = np.float32 if dtype == "f32" else np.float64
-        if device_mode:
-            import torch
-            cvo = tuple(torch.empty(max(sumN, 1), dtype=X.dtype, device=X.device) for _ in range(3))
-        else:
-            cvo = tuple(np.empty(sumN, dtype=np_dt) for _ in range(3))
+        cvo = tuple(_alloc(sumN, dtype, X if device_mode else None) for _ in range(3))
         fo = dict(cv_theta=np.full((F, H), np.nan), cv_nll=np.full(F, np.nan), cv_shift=np.full(F, np.nan),
                   cv_status=np.full(F, 4, dtype=np.int32), cv_n_eval=np.zeros(F, dtype=np.int32), cv_n_iter=np.zeros(F, dtype=np.int32),
                   cv_n_obs=np.zeros(F, dtype=np.int32), cv_label=np.zeros(F, dtype=np.int32))
-        ptr = (lambda a_: a_.data_ptr()) if device_mode else _ptr
         parts, km, tm = [], 0.0, 0.0
         for t0, t1 in ranges:
             a, e, pa, pe, f0, f1 = (int(v) for v in (obs_off[t0], obs_off[t1], pred_off[t0], pred_off[t1], fold_off[t0], fold_off[t1]))
@@ -459,7 +462,7 @@ class Engine:
             cv = L.GpsatCvRefit()
             cv.fold, cv.fold_off = _ptr(sub_lab), _ptr(sub_off)
             cv.start, cv.recentre, cv.min_obs = L.CV_START_IDS[opts["start"]], int(bool(opts["recentre"])), int(opts["min_obs"])
-            cv.cv_mean, cv.cv_f_var, cv.cv_y_var = (ptr(c_[a:e] if e > a else c_[:1]) for c_ in cvo)
+            cv.cv_mean, cv.cv_f_var, cv.cv_y_var = (_bulk_ptr(c_[a:e] if e > a else c_[:1]) for c_ in cvo)
             sub_fo = {k: v[f0:f1] for k, v in fo.items()}          # views: the library writes into the whole arrays
             cv.fold_theta, cv.fold_nll, cv.fold_shift = _ptr(sub_fo["cv_theta"]), _ptr(sub_fo["cv_nll"]), _ptr(sub_fo["cv_shift"])
             cv.fold_status, cv.fold_n_eval, cv.fold_n_iter = _ptr(sub_fo["cv_status"]), _ptr(sub_fo["cv_n_eval"]), _ptr(sub_fo["cv_n_iter"])
@@ -481,30 +484,21 @@ class Engine:
         (CSR ``z_off`` [T+1]).  Arguments and result as ``fit_predict_batch``, except: fp64 only, no ``full_cov``, no
         per-tile observation limit, ``nll`` is the negative ELBO.  Host coordinates are centred per tile (X, Xs and Z by
         the tile's mean observation coordinate) before the call; device tensors are taken as they are."""
-        if obs_var is not None:
-            raise NotImplementedError("sparse GP experts take no noise variances per observation (obs_var)")
-        if dtype != "f64":
-            raise NotImplementedError("sparse GP experts are built in fp64 only (dtype='f64')")
-        if full_cov:
-            raise NotImplementedError("sparse GP experts do not return the full covariance")
+        why = V.why_refused(["sgpr"] + ["noise"] * (obs_var is not None) + ["full_cov"] * bool(full_cov), dtype, None)
+        if why:
+            raise NotImplementedError(why)
         meta = _host_meta(D, (obs_off, pred_off, z_off), theta0, lo, hi, trainable)
         obs_off, pred_off, z_off = meta[0]
         sumN, sumP, sumM = int(obs_off[-1]), int(pred_off[-1]), int(z_off[-1])
-        device_mode = not isinstance(X, np.ndarray)
-        if device_mode:
-            _, preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D), "Z": (Z, sumM * D)}, dtype, sumP, out)
-            pZ = Z.data_ptr()
-        else:
+        if isinstance(X, np.ndarray):
             X, Xs, Z = centre_tiles(np.asarray(X, dtype=np.float64).reshape(sumN, D), np.asarray(Xs, dtype=np.float64).reshape(sumP, D),
                                     obs_off, pred_off, np.asarray(Z, dtype=np.float64).reshape(sumM, D), z_off)
-            X, Xs, Z = np.ascontiguousarray(X), np.ascontiguousarray(Xs), np.ascontiguousarray(Z)
-            y = np.ascontiguousarray(y, dtype=np.float64).reshape(sumN)
-            preds = tuple(np.empty(sumP, dtype=np.float64) for _ in range(3))
-            pZ = _ptr(Z)
-        b, res = self._fill_batch(D, dtype, device_mode, meta, (X, y, Xs), preds, kernel, optimiser, max_iter, max_ls, ftol, gtol,
+            Z = np.ascontiguousarray(Z)
+        device_mode, data, preds = self._stage(D, dtype, sumN, sumP, X, y, Xs, out, {"Z": (Z, sumM * D)})
+        b, res = self._fill_batch(D, dtype, device_mode, meta, data, preds, kernel, optimiser, max_iter, max_ls, ftol, gtol,
                                   adam_lr, want_grad)
         sp = L.GpsatSparse()
-        sp.z_off, sp.Z, sp.jitter = _ptr(z_off), pZ, float(jitter)
+        sp.z_off, sp.Z, sp.jitter = _ptr(z_off), _bulk_ptr(Z), float(jitter)
         rc = self._lib.gpsat_sgpr_fit_predict_batch(self._h, C.byref(b), C.byref(sp))
         return self._result(rc, "gpsat_sgpr_fit_predict_batch", res, preds, sumP)
 

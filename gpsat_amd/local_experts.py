@@ -58,17 +58,17 @@ profile stays an exact GP.
 RationalQuadratic experts (``init_params.kernel == "RationalQuadratic"``, exact GP, fp64: ``dtype`` None or "f64", at most 3
 coordinate columns): a fourth parameter, ``kernel_alpha`` (``init_params.kernel_kwargs.alpha``, default 1), with a table of its
 own that is stored by default, read by ``load_params`` (file or direct value), carried in the ``previous`` running mean and
-accepted by ``constraints``.  Not combined with a replacement model, ``cv`` or SGPR.
+accepted by ``constraints``.
 Experts with a trainable constant mean (``init_params.mean_function == "Constant"``, ``init_params.mean_func_kwargs.c``,
 default 0; GPflow's mean_functions.Constant) are the same kind of profile -- one extra named parameter, here the table
 ``mean_constant`` (in scaled observation units), under the same rules: fp64, at most 3 coordinate columns, stored, loaded,
-averaged and constrained like the others; not combined with a replacement model, ``cv``, SGPR or RationalQuadratic
-(DESIGN.md section 15).  ``mean_function`` None and "Zero" are the zero mean; other names are not built.
+averaged and constrained like the others.  ``mean_function`` None and "Zero" are the zero mean; other names are not built.
 Known noise variances per observation (``data_config["obs_var_col"]``, a column of the data source with every row's noise
 variance in raw observation units, e.g. ``std**2 / count`` of binned data): the column travels with the observations into
 every tile, is divided by ``obs_scale**2`` and is added to the diagonal of K beside ``likelihood_variance``; it is not
-trained and no table changes.  Exact-GP experts in fp64 (``dtype`` None then means fp64); not combined with SGPR, ``cv``, a
-replacement model, RationalQuadratic or a constant mean.
+trained and no table changes.  Exact-GP experts in fp64 (``dtype`` None then means fp64).
+What each of these kinds of expert, ``cv`` and ``pred_kwargs.full_cov`` cannot be combined with is the table of
+gpsat_amd/variants.py; the constructor refuses such a config with the table's reason.
 ``replacement_*`` model settings for tiles below ``replacement_threshold`` observations are honoured (one engine call
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
@@ -117,25 +117,23 @@ from scipy.spatial import cKDTree
 
 from . import _lib as L
 from . import sharding
+from . import variants as V
 from .models import (HipGPRModel, HipSGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND, SGPR_MODEL_NAMES, clamp_within,
                      select_inducing_points)
 
 _COMPS = {">=": np.greater_equal, ">": np.greater, "==": np.equal, "<": np.less, "<=": np.less_equal}
-PARAM_NAMES = ["lengthscales", "kernel_variance", "likelihood_variance"]
-RQ_KERNEL = "RationalQuadratic"                 # its experts have a fourth parameter table, kernel_alpha (H = D + 3)
 
 
-def _extra_param(init_params):
-    """A profile with ONE extra named parameter behind the reference's three (H = D + 3): (table name, what asks for it in
-    a message), or None.  RationalQuadratic's alpha, or the constant of mean_function "Constant"."""
+def _profile_variants(init_params):
+    """The rows of variants.VARIANTS that a model profile's ``init_params`` ask for: RationalQuadratic's alpha, or the constant
+    of mean_function "Constant" -- ONE extra named parameter behind the reference's three."""
     ip = init_params or {}
     mf = ip.get("mean_function")
     if mf is not None and (not isinstance(mf, str) or mf not in ("Zero", "Constant")):
         raise NotImplementedError(f"init_params.mean_function {mf!r}: None, 'Zero' and 'Constant' are built")
-    rq, const = ip.get("kernel") == RQ_KERNEL, mf == "Constant"
-    if rq and const:
-        raise NotImplementedError(f"kernel '{RQ_KERNEL}' and mean_function 'Constant' cannot be combined: D + 4 parameters")
-    return ("kernel_alpha", f"kernel '{RQ_KERNEL}'") if rq else ("mean_constant", "mean_function 'Constant'") if const else None
+    return ["rq"] * (ip.get("kernel") == "RationalQuadratic") + ["mean"] * (mf == "Constant")
+
+
 MODEL_NAME = f"{HipGPRModel.__module__}.{HipGPRModel.__name__}"[:64]
 SGPR_MODEL_NAME = f"{HipSGPRModel.__module__}.{HipSGPRModel.__name__}"[:64]
 SGPR_INIT_KEYS = ("num_inducing_points", "inducing_seed")
@@ -835,7 +833,7 @@ def _adjust_func(spec):
     raise NotImplementedError("load_params.index_adjust takes {col: {'func': callable or 'lambda x: ...'}}")
 
 
-# The per-tile result matrix ``fixed`` [n, H + _N_RES] (H = D + 2 parameters, D + 3 with RationalQuadratic's alpha) holds, after the parameters, these columns at
+# The per-tile result matrix ``fixed`` [n, H + _N_RES] (H = variants.n_hyper parameters) holds, after the parameters, these columns at
 # ``H + <name>``.  It stays one float64 matrix so that ``sharding.gather_arrays`` carries it in one piece.
 _NLL, _STATUS, _N_EVAL, _N_ITER, _SECONDS, _OBS_MEAN = range(6)
 _N_RES = 6
@@ -863,165 +861,11 @@ class BatchedLocalExpertOI:
                  engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None):
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
-        om = model_config.get("oi_model", "HipGPRModel")
-        name = om["model_name"] if isinstance(om, dict) else om
-        if name not in ("HipGPRModel", "GPflowGPRModel") + SGPR_MODEL_NAMES:
-            raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP and SGPR experts only")
-        self.sgpr = name in SGPR_MODEL_NAMES
-        # RationalQuadratic experts and experts with a constant mean: one more parameter per tile (kernel_alpha /
-        # mean_constant, last), exact GP in fp64 and D <= 3 only
-        self.extra = _extra_param(model_config.get("init_params"))
-        extra, who = self.extra or (None, None)
-        self.rq = extra == "kernel_alpha"
-        self.param_names = PARAM_NAMES + [extra] if extra else PARAM_NAMES
-        self.H = len(data_config["coords_col"]) + len(self.param_names) - 1
-        if extra and self.sgpr:
-            raise NotImplementedError(f"{who} is built for exact-GP experts only, not for SGPR")
-        # known noise variances per observation: a column of the data source that travels with the observations; exact GP in
-        # fp64 with a stationary kernel and a zero mean only
-        self.obs_var_col = data_config.get("obs_var_col")
-        if self.obs_var_col is not None:
-            nv = f"data_config.obs_var_col ({self.obs_var_col!r}: noise variances per observation)"
-            if not isinstance(self.obs_var_col, str):
-                raise ValueError(f"data_config.obs_var_col must be one column name, got {self.obs_var_col!r}")
-            if self.sgpr:
-                raise NotImplementedError(f"{nv} is built for exact-GP experts only, not for SGPR")
-            if extra:
-                raise NotImplementedError(f"{nv} and {who} cannot be combined")
-            if cv is not None:
-                raise NotImplementedError(f"cv: held-out predictions are not built for {nv}")
-            if model_config.get("replacement_threshold") is not None:
-                raise NotImplementedError(f"{nv} and a replacement model cannot be combined")
-            if dtype is None:
-                dtype = "f64"
-            if dtype == "f32":
-                raise NotImplementedError(f"{nv} is built in fp64 only: dtype must be None or 'f64'")
-        # dtype None: fp32 for exact-GP experts, fp64 for sparse ones and those with an extra parameter (built in fp64 only --
-        # an explicit fp32 is refused)
-        if dtype is None:
-            dtype = "f64" if (self.sgpr or extra) else "f32"
-        if dtype not in DTYPES:
-            raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
-        if self.sgpr and dtype != "f64":
-            raise NotImplementedError("sparse (SGPR) experts are built in fp64 only: dtype must be None or 'f64'")
-        if extra and dtype != "f64":
-            raise NotImplementedError(f"{who} is built in fp64 only: dtype must be None or 'f64'")
-        if extra and len(data_config["coords_col"]) > 3:
-            raise NotImplementedError(f"{who} is built for 1..3 coordinate columns (D + 3 <= 6 parameters), "
-                                      f"got {len(data_config['coords_col'])}")
-        if extra and cv is not None:
-            raise NotImplementedError(f"cv: held-out predictions are not built for {who}")
-        self.dtype = dtype
-        # held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with equal
-        # values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
-        # fitted again without its rows (tables cv_preds and cv_params; fp32 or fp64), from "start": "theta0" (default) | "full".
-        self.cv_refit = None
-        if cv is not None:
-            if isinstance(cv, dict) and "refit" in cv:
-                if not set(cv) <= {"by", "refit", "start"}:
-                    raise ValueError("cv must be None, 'loo', {'by': [column, ...]} or {'by': [...], 'refit': True, 'start': 'theta0' | 'full'}")
-                if cv.get("by") in (None, "loo") or len(_as_list(cv["by"])) == 0:
-                    raise NotImplementedError("cv: refit is not built for leave-one-out through the orchestrator: give {'by': [column, ...]}")
-                if cv.get("start", "theta0") not in ("theta0", "full"):
-                    raise ValueError(f"cv: start must be 'theta0' or 'full', got {cv.get('start')!r}")
-                if cv["refit"]:
-                    self.cv_refit = {"start": cv.get("start", "theta0")}
-                elif "start" in cv:
-                    raise ValueError("cv: start is an option of refit=True")
-            elif not (cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
-                raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
-            if self.sgpr:
-                raise NotImplementedError("cv: held-out predictions are not built for SGPR experts (exact GP experts only)")
-            if dtype != "f64" and self.cv_refit is None:
-                raise NotImplementedError(f"cv: held-out predictions are built in fp64 only: dtype must be 'f64', not {dtype!r}")
-            pks = [model_config.get("pred_kwargs"), model_config.get("replacement_pred_kwargs")]
-            if any((pk or {}).get("full_cov", False) for pk in pks):
-                raise NotImplementedError("cv: held-out predictions and pred_kwargs.full_cov cannot be combined "
-                                          "(the kernel returns one or the other in a call)")
-        self.cv = cv
-        self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
-        # ---- data (local_experts.py:266-290)
-        self.obs_col = data_config["obs_col"]
-        self.coords_col = list(data_config["coords_col"])
-        if isinstance(self.obs_col, (list, tuple)):
-            assert len(self.obs_col) == 1
-            self.obs_col = self.obs_col[0]
-        self.local_select = data_config.get("local_select", [])
-        static_gs, dynamic_gs = split_global_select(data_config.get("global_select"))
-        df = data_select(_load_frame(data_config["data_source"]), static_gs)
-        self.df = df
-        if self.obs_var_col is not None and self.obs_var_col not in df.columns:
-            raise KeyError(f"obs_var_col: column {self.obs_var_col!r} is not in the data source")
-        missing = [c for c in self.cv_by if c not in df.columns]
-        if missing:
-            raise KeyError(f"cv: columns {missing} are not in the data source")
-        # one code per distinct combination of the `by` columns over the whole frame: equal codes inside a tile = one fold;
-        # -1: a missing value in a `by` column, such a row is never held out
-        self._cv_codes = pd.factorize(pd.MultiIndex.from_frame(df[self.cv_by]) if len(self.cv_by) > 1 else df[self.cv_by[0]])[0] \
-            .astype(np.int64) if self.cv_by else None
-        if self.cv_by:
-            self._cv_codes[df[self.cv_by].isna().any(axis=1).values] = -1
-        # ---- expert locations (local_experts.py:349-422)
-        xl = _load_frame(expert_loc_config["source"])
-        if expert_loc_config.get("sort_by") is not None:
-            xl = xl.sort_values(expert_loc_config["sort_by"])
-        for k in expert_loc_config:
-            if k not in ("source", "sort_by"):
-                raise NotImplementedError(f"expert_loc_config key '{k}' is not supported by the batched backend")
-        self.expert_locs = xl.reset_index(drop=True)
-        # dynamic global_select entries: per-expert rank intervals (DynamicSelect)
-        self.dynamic = DynamicSelect(dynamic_gs, data_config.get("local_select"), df, self.expert_locs.columns) \
-            if dynamic_gs else None
-        if self.dynamic is not None and not self.dynamic.items:
-            self.dynamic = None                   # no local_select entry on its loc_col: it adds nothing
-        if device_select and self.dynamic is not None and len(self.local_select) + len(self.dynamic.src_cols) > L.SEL_MAXCRIT:
-            raise NotImplementedError(f"device_select=True takes at most {L.SEL_MAXCRIT} selection criteria (GPSAT_SEL_MAXCRIT); "
-                                      f"this config needs {len(self.local_select) + len(self.dynamic.src_cols)}: "
-                                      f"{len(self.local_select)} local_select entries and {len(self.dynamic.src_cols)} "
-                                      f"dynamic global_select interval(s), one per src_col")
-        # ---- model (local_experts.py:292-346)
-        self.init_params = dict(model_config.get("init_params") or {})
-        self.constraints = model_config.get("constraints")
-        self.optim_kwargs = dict(model_config.get("optim_kwargs") or {})
-        self.pred_kwargs = dict(model_config.get("pred_kwargs") or {})
-        # replacement model for tiles with fewer than `replacement_threshold` observations (local_experts.py:339-346,
-        # 1021-1041): same defaults as the reference -- init_params / constraints fall back to the main ones,
-        # optim_kwargs / pred_kwargs to {}
-        self.replacement_threshold = model_config.get("replacement_threshold")
-        self.profiles = {"main": dict(init_params=self.init_params, constraints=self.constraints,
-                                      optim_kwargs=self.optim_kwargs, pred_kwargs=self.pred_kwargs, sgpr=self.sgpr)}
-        if self.sgpr:
-            if self.pred_kwargs.get("full_cov", False):
-                raise NotImplementedError("sparse (SGPR) experts do not return the full covariance (pred_kwargs.full_cov)")
-            if self.optim_kwargs.get("train_inducing_points", False):
-                raise NotImplementedError("train_inducing_points=True is not built: the inducing points stay fixed")
-            M = int(self.init_params.get("num_inducing_points", 500))
-            if not 1 <= M <= L.max_inducing("f64", len(data_config["coords_col"])):
-                raise ValueError(f"num_inducing_points={M}: 1..{L.max_inducing('f64', len(data_config['coords_col']))} "
-                                 f"are built (gpsat_max_inducing)")
-        if self.replacement_threshold is not None:
-            rm = model_config.get("replacement_model")
-            rname = rm["model_name"] if isinstance(rm, dict) else rm
-            if rname not in (None, "HipGPRModel", "GPflowGPRModel"):
-                raise NotImplementedError(f"replacement_model '{rname}': the batched backend builds the exact-GP expert only")
-            rip = model_config.get("replacement_init_params")
-            rco = model_config.get("replacement_constraints")
-            for ex in (self.extra, _extra_param(rip)):
-                if ex:
-                    raise NotImplementedError(f"{ex[1]} and a replacement model cannot be combined: the two profiles of "
-                                              f"a run share one parameter layout, and this one has a parameter more")
-            main_ip = {k: v for k, v in self.init_params.items() if k not in SGPR_INIT_KEYS}
-            self.profiles["replacement"] = dict(
-                sgpr=False,
-                init_params=main_ip if rip is None else dict(rip),
-                constraints=self.constraints if rco is None else rco,
-                optim_kwargs=dict(model_config.get("replacement_optim_kwargs") or {}),
-                pred_kwargs=dict(model_config.get("replacement_pred_kwargs") or {}))
-        self.params_to_store = model_config.get("params_to_store") or (PARAM_NAMES + ["inducing_points"] if self.sgpr
-                                                                        else self.param_names)
-        bad = [p_ for p_ in self.params_to_store if p_ not in self.param_names + (["inducing_points"] if self.sgpr else [])]
-        if bad:
-            raise NotImplementedError(f"params_to_store {bad}: not a parameter of this model")
+        self.dtype = self._ask_variants(data_config, model_config, dtype, cv)
+        self._parse_cv(cv)
+        self._load_data(data_config)
+        self._load_expert_locs(expert_loc_config, data_config, device_select)
+        self._set_profiles(model_config)
         self._set_load_params(model_config.get("load_params"))
         # ---- prediction locations (local_experts.py:254-264)
         plc = dict(pred_loc_config or {"method": "expert_loc"})
@@ -1035,6 +879,148 @@ class BatchedLocalExpertOI:
         # tile membership for all experts in one GPU call (bit-identical to the host selector)
         self.device_select = device_select
         self.timings = {}
+
+    def _ask_variants(self, data_config, model_config, dtype, cv):
+        """Which rows of variants.VARIANTS the four configs ask for, and whether the table allows them together at this
+        dtype and number of coordinate columns.  Sets ``sgpr``, ``rq``, ``extra``, ``param_names``, ``H`` and ``obs_var_col``;
+        returns the run's dtype."""
+        om = model_config.get("oi_model", "HipGPRModel")
+        name = om["model_name"] if isinstance(om, dict) else om
+        if name not in ("HipGPRModel", "GPflowGPRModel") + SGPR_MODEL_NAMES:
+            raise NotImplementedError(f"oi_model '{name}': the batched backend builds the exact-GP and SGPR experts only")
+        self.sgpr = name in SGPR_MODEL_NAMES
+        # known noise variances per observation: a column of the data source that travels with the observations
+        self.obs_var_col = data_config.get("obs_var_col")
+        if self.obs_var_col is not None and not isinstance(self.obs_var_col, str):
+            raise ValueError(f"data_config.obs_var_col must be one column name, got {self.obs_var_col!r}")
+        self._variants = _profile_variants(model_config.get("init_params"))
+        kind = self._variants + ["noise"] * (self.obs_var_col is not None) + ["sgpr"] * self.sgpr
+        # dtype None: fp32 for exact-GP experts, fp64 for the kinds of expert that are built in fp64 only (an explicit fp32
+        # is refused below)
+        if dtype is None:
+            dtype = "f32" if all("f32" in V.VARIANTS[k].dtypes for k in kind) else "f64"
+        if dtype not in DTYPES:
+            raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
+        # one check per model profile: the main one carries the kind of expert; the replacement stays a plain exact GP
+        held_out = [] if cv is None else ["cv_refit" if isinstance(cv, dict) and cv.get("refit") else "cv"]
+        replaced = ["replacement"] * (model_config.get("replacement_threshold") is not None)
+        profiles = [(kind, model_config.get("pred_kwargs"))]
+        if replaced:
+            profiles.append((_profile_variants(model_config.get("replacement_init_params")), model_config.get("replacement_pred_kwargs")))
+        D = len(data_config["coords_col"])
+        for asked, pk in profiles:
+            why = V.why_refused(asked + held_out + replaced + ["full_cov"] * bool((pk or {}).get("full_cov", False)), dtype, D,
+                                dims="coordinate columns")
+            if why:
+                raise NotImplementedError(why)
+        row = next((V.VARIANTS[k] for k in self._variants if V.VARIANTS[k].param), None)
+        self.extra = (row.param, row.arg) if row else None          # the ONE extra named parameter and what asks for it
+        self.rq = "rq" in self._variants
+        self.param_names = V.param_names(self._variants)
+        self.H = V.n_hyper(D, self._variants)
+        return dtype
+
+    def _parse_cv(self, cv):
+        """``cv``: held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with
+        equal values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
+        fitted again without its rows (tables cv_preds and cv_params; fp32 or fp64), from "start": "theta0" (default) | "full".
+        Sets ``cv``, ``cv_by`` and ``cv_refit``."""
+        self.cv_refit = None
+        if isinstance(cv, dict) and "refit" in cv:
+            if not set(cv) <= {"by", "refit", "start"}:
+                raise ValueError("cv must be None, 'loo', {'by': [column, ...]} or {'by': [...], 'refit': True, 'start': 'theta0' | 'full'}")
+            if cv.get("by") in (None, "loo") or len(_as_list(cv["by"])) == 0:
+                raise NotImplementedError("cv: refit is not built for leave-one-out through the orchestrator: give {'by': [column, ...]}")
+            if cv.get("start", "theta0") not in ("theta0", "full"):
+                raise ValueError(f"cv: start must be 'theta0' or 'full', got {cv.get('start')!r}")
+            if cv["refit"]:
+                self.cv_refit = {"start": cv.get("start", "theta0")}
+            elif "start" in cv:
+                raise ValueError("cv: start is an option of refit=True")
+        elif not (cv is None or cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
+            raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
+        self.cv = cv
+        self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
+
+    def _load_data(self, data_config):
+        """The globally selected frame (local_experts.py:266-290) and, with ``cv_by``, the fold code of every row."""
+        self.obs_col = data_config["obs_col"]
+        self.coords_col = list(data_config["coords_col"])
+        if isinstance(self.obs_col, (list, tuple)):
+            assert len(self.obs_col) == 1
+            self.obs_col = self.obs_col[0]
+        self.local_select = data_config.get("local_select", [])
+        static_gs, self._dynamic_gs = split_global_select(data_config.get("global_select"))
+        df = data_select(_load_frame(data_config["data_source"]), static_gs)
+        self.df = df
+        if self.obs_var_col is not None and self.obs_var_col not in df.columns:
+            raise KeyError(f"obs_var_col: column {self.obs_var_col!r} is not in the data source")
+        missing = [c for c in self.cv_by if c not in df.columns]
+        if missing:
+            raise KeyError(f"cv: columns {missing} are not in the data source")
+        # one code per distinct combination of the `by` columns over the whole frame: equal codes inside a tile = one fold;
+        # -1: a missing value in a `by` column, such a row is never held out
+        self._cv_codes = pd.factorize(pd.MultiIndex.from_frame(df[self.cv_by]) if len(self.cv_by) > 1 else df[self.cv_by[0]])[0] \
+            .astype(np.int64) if self.cv_by else None
+        if self.cv_by:
+            self._cv_codes[df[self.cv_by].isna().any(axis=1).values] = -1
+
+    def _load_expert_locs(self, expert_loc_config, data_config, device_select):
+        """Expert locations (local_experts.py:349-422) and the dynamic global_select entries as per-expert rank intervals."""
+        xl = _load_frame(expert_loc_config["source"])
+        if expert_loc_config.get("sort_by") is not None:
+            xl = xl.sort_values(expert_loc_config["sort_by"])
+        for k in expert_loc_config:
+            if k not in ("source", "sort_by"):
+                raise NotImplementedError(f"expert_loc_config key '{k}' is not supported by the batched backend")
+        self.expert_locs = xl.reset_index(drop=True)
+        self.dynamic = DynamicSelect(self._dynamic_gs, data_config.get("local_select"), self.df, self.expert_locs.columns) \
+            if self._dynamic_gs else None
+        if self.dynamic is not None and not self.dynamic.items:
+            self.dynamic = None                   # no local_select entry on its loc_col: it adds nothing
+        if device_select and self.dynamic is not None and len(self.local_select) + len(self.dynamic.src_cols) > L.SEL_MAXCRIT:
+            raise NotImplementedError(f"device_select=True takes at most {L.SEL_MAXCRIT} selection criteria (GPSAT_SEL_MAXCRIT); "
+                                      f"this config needs {len(self.local_select) + len(self.dynamic.src_cols)}: "
+                                      f"{len(self.local_select)} local_select entries and {len(self.dynamic.src_cols)} "
+                                      f"dynamic global_select interval(s), one per src_col")
+
+    def _set_profiles(self, model_config):
+        """The model profiles of a run (local_experts.py:292-346) and the parameter tables it stores."""
+        self.init_params = dict(model_config.get("init_params") or {})
+        self.constraints = model_config.get("constraints")
+        self.optim_kwargs = dict(model_config.get("optim_kwargs") or {})
+        self.pred_kwargs = dict(model_config.get("pred_kwargs") or {})
+        # replacement model for tiles with fewer than `replacement_threshold` observations (local_experts.py:339-346,
+        # 1021-1041): same defaults as the reference -- init_params / constraints fall back to the main ones,
+        # optim_kwargs / pred_kwargs to {}
+        self.replacement_threshold = model_config.get("replacement_threshold")
+        self.profiles = {"main": dict(init_params=self.init_params, constraints=self.constraints,
+                                      optim_kwargs=self.optim_kwargs, pred_kwargs=self.pred_kwargs, sgpr=self.sgpr)}
+        if self.sgpr:
+            if self.optim_kwargs.get("train_inducing_points", False):
+                raise NotImplementedError("train_inducing_points=True is not built: the inducing points stay fixed")
+            M, Mmax = int(self.init_params.get("num_inducing_points", 500)), L.max_inducing("f64", len(self.coords_col))
+            if not 1 <= M <= Mmax:
+                raise ValueError(f"num_inducing_points={M}: 1..{Mmax} are built (gpsat_max_inducing)")
+        if self.replacement_threshold is not None:
+            rm = model_config.get("replacement_model")
+            rname = rm["model_name"] if isinstance(rm, dict) else rm
+            if rname not in (None, "HipGPRModel", "GPflowGPRModel"):
+                raise NotImplementedError(f"replacement_model '{rname}': the batched backend builds the exact-GP expert only")
+            rip = model_config.get("replacement_init_params")
+            rco = model_config.get("replacement_constraints")
+            main_ip = {k: v for k, v in self.init_params.items() if k not in SGPR_INIT_KEYS}
+            self.profiles["replacement"] = dict(
+                sgpr=False,
+                init_params=main_ip if rip is None else dict(rip),
+                constraints=self.constraints if rco is None else rco,
+                optim_kwargs=dict(model_config.get("replacement_optim_kwargs") or {}),
+                pred_kwargs=dict(model_config.get("replacement_pred_kwargs") or {}))
+        stored = self.param_names + ["inducing_points"] * self.sgpr
+        self.params_to_store = model_config.get("params_to_store") or stored
+        bad = [p_ for p_ in self.params_to_store if p_ not in stored]
+        if bad:
+            raise NotImplementedError(f"params_to_store {bad}: not a parameter of this model")
 
     def _set_load_params(self, lp):
         """``load_params`` as the run reads it: ``use_previous``, and the file / direct values without ``previous``."""
@@ -1059,14 +1045,6 @@ class BatchedLocalExpertOI:
             self.load_params = None
         elif lp is not None and "previous" in lp:
             self.load_params = {k: v for k, v in lp.items() if k not in ("previous", "previous_params")}
-
-    def _slots(self):
-        """(first column, width) of every named parameter in a tile's theta."""
-        D = len(self.coords_col)
-        slots = {"lengthscales": (0, D), "kernel_variance": (D, 1), "likelihood_variance": (D + 1, 1)}
-        if self.extra:
-            slots[self.extra[0]] = (D + 2, 1)
-        return slots
 
     def _template(self, pf, optimise, predict) -> _Profile:
         """The profile's record: HipGPRModel's defaults, scales, box and trainable mask from one throw-away model on a
@@ -1095,10 +1073,10 @@ class BatchedLocalExpertOI:
             coords_scale=np.broadcast_to(m.coords_scale, (1, D)).astype(np.float64),
             obs_scale=float(m.obs_scale.reshape(-1)[0]),
             local_mean=isinstance(pf["init_params"].get("obs_mean"), str) and pf["init_params"]["obs_mean"] == "local",
-            unconstrained_noise=not np.isfinite(m._lo[D + 1]), device=str(m.gpu_name)[:64], sgpr=bool(pf.get("sgpr")),
+            unconstrained_noise=not np.isfinite(m._lo[m._slice("likelihood_variance")]).any(), device=str(m.gpu_name)[:64], sgpr=bool(pf.get("sgpr")),
             n_inducing=int(pf["init_params"].get("num_inducing_points", 500)),
             inducing_seed=int(pf["init_params"].get("inducing_seed", 0)), kernel=kernel, max_iter=int(ok.get("max_iter", 10_000)),
-            eng_kw={k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok},
+            eng_kw={**{k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok}, **m._variant_args()},
             optimiser=ok.get("optimiser", "lbfgs") if optimise else "none", apply_scale=pf["pred_kwargs"].get("apply_scale", True),
             full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict)
 
@@ -1112,7 +1090,7 @@ class BatchedLocalExpertOI:
             j, f = cc.index(col), _adjust_func(spec)
             look[:, j] = [f(v) for v in look[:, j]]
         key = _index_for(cc, look)
-        slots = self._slots()
+        slots = V.slots(D, self._variants)
         for pn, tab in tabs.items():
             start, width = slots[pn]
             colvals = np.full((len(locs), width), np.nan)
@@ -1346,10 +1324,8 @@ class BatchedLocalExpertOI:
                 raise NotImplementedError("load_params needs 'file' or parameter values")
             for pn, v in direct.items():
                 v = np.asarray(v, dtype=np.float64).reshape(-1)
-                if pn == "lengthscales":
-                    theta0[:, :D] = v
-                else:
-                    theta0[:, D + self.param_names.index(pn) - 1] = v[0]
+                start, width = V.slots(D, self._variants)[pn]
+                theta0[:, start:start + width] = v if pn == "lengthscales" else v[0]
         for pi, pf in enumerate(profiles):                      # move within tol of the box (gpflow_models.py:471-479)
             m_ = prof_id == pi
             for sl, tol in pf.clamp:
@@ -1467,17 +1443,16 @@ class BatchedLocalExpertOI:
     def _cv_params_frame(self, plan, items, folds, f_bar):
         """Table ``cv_params`` of the tiles among ``items`` (``folds``: per item [F, H + 5]: theta, objective, status, rows
         fitted, shift, position in the tile of the fold's first row; ``f_bar``: per item the tile's de-meaning constant)."""
-        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
-        H = len(cc) + 2
+        cc, items, H = self.coords_col, np.asarray(items, dtype=np.int64), self.H
         cnt = np.array([len(c) for c in folds], dtype=np.int64)
         v = _cat([c for c in folds if len(c)], H + 5)
         rows = np.concatenate([plan.idx[plan.off[i] + c[:, H + 4].astype(np.int64)] for i, c in zip(items, folds) if len(c)]).astype(np.int64) \
             if cnt.sum() else np.zeros(0, dtype=np.int64)
         fr = {c_: self.df[c_].values[rows] for c_ in self.cv_by}
         fr["num_obs"] = v[:, H + 2].astype(np.int64)
-        for k in range(H - 2):
-            fr[f"lengthscales_{k}"] = v[:, k]
-        fr["kernel_variance"], fr["likelihood_variance"] = v[:, H - 2], v[:, H - 1]
+        for pn, (start, width) in V.slots(len(cc), self._variants).items():
+            for k in range(width):
+                fr[f"{pn}_{k}" if pn == "lengthscales" else pn] = v[:, start + k]
         fr["objective_value"] = v[:, H]
         fr["optimise_success"] = bool(plan.optimise) & (v[:, H + 1] == 0)
         osc = np.array([plan.profiles[p].obs_scale for p in plan.prof_id[items]], dtype=np.float64)
@@ -1570,7 +1545,7 @@ class BatchedLocalExpertOI:
             "device": np.array([pf.device if t else "" for pf, t in zip(profs, tile)], dtype=object),
             "config_id": np.full(n, plan.config_id, dtype=np.int64)}, index=_index_for(cc, locs))}
         sp = tile & plan.save_params[items]
-        slots = self._slots()
+        slots = V.slots(D, self._variants)
         for pn in self.params_to_store:
             if pn == "inducing_points":
                 # [M, D] per expert: _dim_0 inducing index, _dim_1 coordinate (dict_of_array_to_table of a 2-D array)
@@ -1725,8 +1700,6 @@ class _ShardRunner:
         kw = dict(D=len(self.oi.coords_col), obs_off=pk["o_off"], X=pk["X"], y=pk["y"], pred_off=pk["p_off"], Xs=pk["Xs"], lo=p.lo[ids],
                   hi=p.hi[ids], trainable=pf.trainable, kernel=pf.kernel, optimiser=pf.optimiser, max_iter=pf.max_iter,
                   **pf.eng_kw)
-        if self.oi.extra and self.oi.extra[0] == "mean_constant":
-            kw["mean"] = "constant"
         if "obs_var" in pk:
             kw["obs_var"] = pk["obs_var"]
         eng_ = self.free_engines.get()

@@ -36,6 +36,7 @@ except Exception:  # pragma: no cover
     pd = None
 
 from . import _lib as L
+from . import variants as V
 
 LIKELIHOOD_VARIANCE_LOWER_BOUND = 1e-6   # GPflow Gaussian likelihood default (gpflow_models.py:404-409)
 
@@ -155,46 +156,34 @@ class HipGPRModel:
         if mean_function is not None and (not isinstance(mean_function, str) or mean_function not in ("Zero", "Constant")):
             raise NotImplementedError(f"mean_function {mean_function!r}: the HIP backend builds None, 'Zero' and 'Constant' "
                                       f"(Linear and the others would need 2 D + 3 > 6 parameters)")
-        # a trainable constant mean (gpflow.mean_functions.Constant): one more parameter, c, last in the device's vector
-        self._mean = mean_function == "Constant"
         self.kernel = kernel
         if dtype not in ("f32", "f64"):
             raise ValueError("dtype must be 'f32' or 'f64'")
         self.dtype = dtype                                # device compute precision (the reference computes in fp64)
         D = self.coords.shape[1]
-        if D > 4:
-            raise NotImplementedError("HIP backend is built for 1..4 input dimensions")
+        if D > V.MAX_D:
+            raise NotImplementedError(f"HIP backend is built for 1..{V.MAX_D} input dimensions")
         self.D = D
-        # RationalQuadratic: a fourth trainable parameter, alpha, last in the device's vector (H = D + 3)
-        self._rq = L.KERNEL_IDS[kernel] == L.KERNEL_RQ
-        if self._rq and dtype != "f64":
-            raise NotImplementedError(f"kernel {kernel!r} is built in fp64 only: pass dtype='f64'")
-        if self._rq and D > 3:
-            raise NotImplementedError(f"kernel {kernel!r} is built for 1..3 input dimensions (D + 3 <= 6 parameters), got D = {D}")
-        if self._mean:
-            why = ("is built in fp64 only: pass dtype='f64'" if dtype != "f64" else
-                   f"is built for 1..3 input dimensions (D + 3 <= 6 parameters), got D = {D}" if D > 3 else
-                   f"is not built for kernel {kernel!r} (D + 4 parameters)" if self._rq else None)
-            if why:
-                raise NotImplementedError(f"mean_function 'Constant' {why}")
+        # the rows of variants.VARIANTS this model asks for: RationalQuadratic's alpha and the constant of a trainable
+        # constant mean (gpflow.mean_functions.Constant) are one more parameter each, last in the device's vector
+        self._variants = L.theta_variants(kernel, "constant" if mean_function == "Constant" else None) \
+            + ["noise"] * (self.obs_var is not None)
+        why = V.why_refused(self._variants, dtype, D)
+        if why:
+            raise NotImplementedError(why)
+        if "mean" in self._variants:
             mk = dict(mean_func_kwargs or {})
             if set(mk) - {"c"}:
                 raise NotImplementedError(f"mean_func_kwargs {sorted(set(mk) - {'c'})}: 'Constant' takes 'c' only")
             c0 = np.asarray(0.0 if mk.get("c") is None else mk["c"], dtype=np.float64).reshape(-1)   # GPflow: c=None is 0
             assert len(c0) == 1, f"mean_func_kwargs['c'] must be a number or a sequence of one element, got {len(c0)}"
-        if self.obs_var is not None:
-            why = ("are built in fp64 only: pass dtype='f64'" if dtype != "f64" else
-                   f"are not built for kernel {kernel!r}" if self._rq else
-                   "are not built for mean_function='Constant'" if self._mean else None)
-            if why:
-                raise NotImplementedError(f"noise variances per observation (obs_var) {why}")
         kk = dict(kernel_kwargs or {})
         ls = np.broadcast_to(np.asarray(kk.get("lengthscales", np.ones(D)), dtype=np.float64), (D,)).copy()
         self._theta = np.concatenate([ls, [float(kk.get("variance", 1.0))],
                                       [1.0 if noise_variance is None else float(noise_variance)],
-                                      [float(kk.get("alpha", 1.0))] if self._rq else [],        # GPflow: alpha = 1
-                                      [float(c0[0])] if self._mean else []])
-        H = L.n_hyper(kernel, D, "constant" if self._mean else None)
+                                      [float(kk.get("alpha", 1.0))] if "rq" in self._variants else [],        # GPflow: alpha = 1
+                                      [float(c0[0])] if "mean" in self._variants else []])
+        H = V.n_hyper(D, self._variants)
         self._lo = np.full(H, np.nan)
         self._hi = np.full(H, np.nan)
         self._trainable = np.ones(H, dtype=bool)
@@ -218,8 +207,7 @@ class HipGPRModel:
     def param_names(self) -> List[str]:
         # the reference's three names (gpflow_models.py:179-184) would lose alpha in params_to_store and load_params
         # ... and likewise the constant of mean_function="Constant"
-        names = ["lengthscales", "kernel_variance", "likelihood_variance"]
-        return names + (["kernel_alpha"] if self._rq else []) + (["mean_constant"] if self._mean else [])
+        return V.param_names(self._variants)
 
     def get_parameters(self, *args, return_dict=True):
         # base_model.py:370-403
@@ -245,48 +233,47 @@ class HipGPRModel:
 
     # -- getters / setters: gpflow_models.py:339-411
     def get_lengthscales(self) -> np.ndarray:
-        return self._theta[:self.D].copy()
+        return self._theta[self._slice("lengthscales")].copy()
 
     def get_kernel_variance(self) -> float:
-        return float(self._theta[self.D])
+        return float(self._theta[self._column("kernel_variance")])
 
     def get_likelihood_variance(self) -> float:
-        return float(self._theta[self.D + 1])
+        return float(self._theta[self._column("likelihood_variance")])
 
-    def _need_mean(self):
-        if not self._mean:
-            raise AttributeError("mean_constant is the parameter of mean_function='Constant', this model has a zero mean")
+    def _column(self, name):
+        """The first column of theta with the parameter ``name``; AttributeError for a variant's parameter in a model without
+        that variant."""
+        if name not in self.param_names:
+            row = next(v for v in V.VARIANTS.values() if v.param == name)
+            raise AttributeError(f"{name} is the parameter of {row.label}, which this model (kernel {self.kernel!r}) does not have")
+        return self._slice(name).start
+
+    def _set_variant_param(self, name, value):
+        col = self._column(name)
+        v = np.asarray(value, dtype=np.float64).reshape(-1)
+        assert len(v) == 1, f"set_{name} expected a float or an array of one element, got {len(v)}"
+        self._theta[col] = float(v[0])
 
     def get_mean_constant(self) -> float:
         """c of the constant mean, in the model's scaled observation units, (y - obs_mean) / obs_scale."""
-        self._need_mean()
-        return float(self._theta[self.D + 2])
+        return float(self._theta[self._column("mean_constant")])
 
     def set_mean_constant(self, mean_constant):
-        self._need_mean()
-        v = np.asarray(mean_constant, dtype=np.float64).reshape(-1)
-        assert len(v) == 1, f"set_mean_constant expected a float or an array of one element, got {len(v)}"
-        assert np.isfinite(v[0]), "mean_constant must be finite"
-        self._theta[self.D + 2] = float(v[0])
-
-    def _need_rq(self):
-        if not self._rq:
-            raise AttributeError(f"kernel_alpha is a parameter of the 'RationalQuadratic' kernel, this model's is {self.kernel!r}")
+        self._column("mean_constant")
+        assert np.isfinite(np.asarray(mean_constant, dtype=np.float64)).all(), "mean_constant must be finite"
+        self._set_variant_param("mean_constant", mean_constant)
 
     def get_kernel_alpha(self) -> float:
-        self._need_rq()
-        return float(self._theta[self.D + 2])
+        return float(self._theta[self._column("kernel_alpha")])
 
     def set_kernel_alpha(self, kernel_alpha):
-        self._need_rq()
-        v = np.asarray(kernel_alpha, dtype=np.float64).reshape(-1)
-        assert len(v) == 1, f"set_kernel_alpha expected a float or an array of one element, got {len(v)}"
-        self._theta[self.D + 2] = float(v[0])
+        self._set_variant_param("kernel_alpha", kernel_alpha)
 
     def set_lengthscales(self, lengthscales):
         v = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
         assert len(v) in (1, self.D), f"lengthscales must have length 1 or {self.D}"
-        self._theta[:self.D] = v
+        self._theta[self._slice("lengthscales")] = v
 
     def set_kernel_variance(self, kernel_variance):
         if isinstance(kernel_variance, np.ndarray):
@@ -294,7 +281,7 @@ class HipGPRModel:
                 f"set_kernel_variance expected to receive float, or np.array with len(1), shape:(1,), got" \
                 f"len: {len(kernel_variance)}, shape: {kernel_variance.shape}"
             kernel_variance = kernel_variance[0]
-        self._theta[self.D] = float(kernel_variance)
+        self._theta[self._column("kernel_variance")] = float(kernel_variance)
 
     def set_likelihood_variance(self, likelihood_variance):
         if isinstance(likelihood_variance, np.ndarray):
@@ -302,19 +289,17 @@ class HipGPRModel:
                 f"set_likelihood_variance expected to receive float, or np.array with len(1), shape:(1,), got" \
                 f"len: {len(likelihood_variance)}, shape: {likelihood_variance.shape}"
             likelihood_variance = likelihood_variance[0]
-        unconstrained = not np.isfinite(self._lo[self.D + 1])
+        unconstrained = not np.isfinite(self._lo[self._column("likelihood_variance")])
         if unconstrained and likelihood_variance < LIKELIHOOD_VARIANCE_LOWER_BOUND:
             warnings.warn("\n***\ntrying to set likelihood_variance to value less than "
                           "model.likelihood.variance_lower_bound\nwill set to variance_lower_bound\n***\n")
             likelihood_variance = LIKELIHOOD_VARIANCE_LOWER_BOUND
-        self._theta[self.D + 1] = float(likelihood_variance)
+        self._theta[self._column("likelihood_variance")] = float(likelihood_variance)
 
     # -- constraints: gpflow_models.py:416-590
     def _slice(self, name):
-        D = self.D
-        return {"lengthscales": slice(0, D), "kernel_variance": slice(D, D + 1),
-                "likelihood_variance": slice(D + 1, D + 2), "kernel_alpha": slice(D + 2, D + 3),
-                "mean_constant": slice(D + 2, D + 3)}[name]
+        start, width = V.slots(self.D, self._variants)[name]
+        return slice(start, start + width)
 
     def _set_param_constraints(self, name, low, high, move_within_tol=True, tol=1e-8, scale=False,
                                scale_magnitude=None):
@@ -352,29 +337,38 @@ class HipGPRModel:
         self._set_param_constraints("likelihood_variance", low, high, move_within_tol, tol, scale, scale_magnitude)
 
     def set_kernel_alpha_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
-        self._need_rq()
+        self._column("kernel_alpha")
         self._set_param_constraints("kernel_alpha", low, high, move_within_tol, tol, scale, scale_magnitude)
 
     def set_mean_constant_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
         """A box for c (without one it is unconstrained, as GPflow's Constant.c).  ``scale`` divides bounds by the COORDINATE
         scale, which means nothing for a level of the observations: refused."""
-        self._need_mean()
+        self._column("mean_constant")
         if scale:
             raise NotImplementedError("set_mean_constant_constraints: scale=True divides by the coordinate scale, which "
                                       "does not apply to mean_constant; give the bounds in scaled observation units")
         self._set_param_constraints("mean_constant", low, high, move_within_tol, tol, False, None)
 
     # -- the three device calls
-    def _run(self, *, optimiser, max_iter=0, pred_coords=None, **opt_kwargs):
+    def _tile_args(self, pred_coords=None) -> dict:
+        """The engine arguments of this model's one tile: offsets, X, y, the prediction coordinates, theta0, the box, the
+        trainable mask, the kernel and what the model's variants add."""
         N, D = self.coords.shape
-        P = 0 if pred_coords is None else len(pred_coords)
         Xs = np.zeros((0, D)) if pred_coords is None else pred_coords
-        return self._engine.fit_predict_batch(
-            dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0],
-            pred_off=np.array([0, P]), Xs=Xs, theta0=self._theta[None, :], lo=self._lo[None, :],
-            hi=self._hi[None, :], trainable=self._trainable, kernel=self.kernel, optimiser=optimiser,
-            max_iter=max_iter, **({"mean": "constant"} if self._mean else {}),
-            **({} if self.obs_var is None else {"obs_var": self.obs_var}), **opt_kwargs)
+        return dict(D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, len(Xs)]), Xs=Xs,
+                    theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :], trainable=self._trainable,
+                    kernel=self.kernel, **self._variant_args())
+
+    def _variant_args(self) -> dict:
+        """The engine keywords that this model's variants add to a call."""
+        kw = {"mean": "constant"} if "mean" in self._variants else {}
+        if self.obs_var is not None:
+            kw["obs_var"] = self.obs_var
+        return kw
+
+    def _run(self, *, optimiser, max_iter=0, pred_coords=None, **opt_kwargs):
+        return self._engine.fit_predict_batch(dtype=self.dtype, optimiser=optimiser, max_iter=max_iter,
+                                              **self._tile_args(pred_coords), **opt_kwargs)
 
     def _fix_hyperparameters(self, params_list):
         # gpflow_models.py:275-288
@@ -466,12 +460,9 @@ class HipGPRModel:
         "objective_value", "status", "num_obs" and "shift" (the mean of the rows the fold leaves, in the units of "f*")."""
         from .engine import factorise_folds
         N, D = self.coords.shape
-        if self._rq:
-            raise NotImplementedError(f"held-out predictions are not built for kernel {self.kernel!r}")
-        if self._mean:
-            raise NotImplementedError("held-out predictions are not built for mean_function='Constant'")
-        if self.obs_var is not None:
-            raise NotImplementedError("held-out predictions are not built for noise variances per observation (obs_var)")
+        why = V.why_refused(self._variants + ["cv_refit" if refit else "cv"], None, None)
+        if why:
+            raise NotImplementedError(why)
         if refit:
             return self._cross_validate_refit(fold, **refit_kwargs)
         if refit_kwargs:
@@ -486,10 +477,7 @@ class HipGPRModel:
             counts = np.bincount(labels[labels >= 0]) if (labels >= 0).any() else np.zeros(1, dtype=int)
             if counts.max() > gmax:
                 raise ValueError(f"a fold of {int(counts.max())} rows: at most {gmax} rows are held out together (gpsat_max_cv_fold)")
-        r = self._engine.fit_predict_batch(
-            dtype="f64", D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, 0]),
-            Xs=np.zeros((0, D)), theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
-            trainable=self._trainable, kernel=self.kernel, optimiser="none", max_iter=0, cv_fold=labels)
+        r = self._engine.fit_predict_batch(dtype="f64", optimiser="none", max_iter=0, cv_fold=labels, **self._tile_args())
         if r.status[0] in (2, 3):
             raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
         return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
@@ -498,14 +486,11 @@ class HipGPRModel:
 
     def _cross_validate_refit(self, fold, max_iter=10_000, optimiser="lbfgs", **kw):
         from .engine import factorise_folds
-        N, D = self.coords.shape
+        N = len(self.coords)
         labels = np.arange(N, dtype=np.int32) if fold is None else factorise_folds(fold, N)
         run = {k: kw.pop(k) for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in kw}
-        r = self._engine.fit_predict_batch(
-            dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, 0]),
-            Xs=np.zeros((0, D)), theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
-            trainable=self._trainable, kernel=self.kernel, optimiser=optimiser, max_iter=max_iter, cv_fold=labels,
-            cv_refit=kw or True, **run)
+        r = self._engine.fit_predict_batch(dtype=self.dtype, optimiser=optimiser, max_iter=max_iter, cv_fold=labels,
+                                           cv_refit=kw or True, **self._tile_args(), **run)
         return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
                 "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N),
                 "fold": r.cv_label, "theta": r.cv_theta, "objective_value": r.cv_nll, "status": r.cv_status,
@@ -538,13 +523,10 @@ class HipSGPRModel(HipGPRModel):
                  kernel="Matern32", num_inducing_points=500, kernel_kwargs=None, mean_function=None,
                  mean_func_kwargs=None, noise_variance=None, likelihood=None, engine=None, dtype="f64",
                  inducing_seed=0, expert_index=0, obs_var=None, obs_var_col=None, **kwargs):
-        if obs_var is not None or obs_var_col is not None:
-            raise NotImplementedError("noise variances per observation (obs_var, obs_var_col) are built for exact experts "
-                                      "(HipGPRModel) only, not for SGPR")
-        if dtype != "f64":
-            raise NotImplementedError("HipSGPRModel is built in fp64 only (dtype='f64')")
-        if kernel == "RationalQuadratic":
-            raise NotImplementedError("kernel 'RationalQuadratic' is built for exact experts (HipGPRModel) only, not for SGPR")
+        why = V.why_refused(["sgpr"] + ["noise"] * (obs_var is not None or obs_var_col is not None)
+                            + ["rq"] * (kernel == "RationalQuadratic"), dtype, None)
+        if why:
+            raise NotImplementedError(why)
         if mean_function is not None:
             raise NotImplementedError("mean_function is not built for sparse experts (HipSGPRModel)")
         super().__init__(data=data, coords_col=coords_col, obs_col=obs_col, coords=coords, obs=obs,
@@ -563,7 +545,7 @@ class HipSGPRModel(HipGPRModel):
         return ["lengthscales", "kernel_variance", "likelihood_variance", "inducing_points"]
 
     def cross_validate(self, fold=None, apply_scale=True, **kwargs):
-        raise NotImplementedError("held-out predictions are built for exact experts (HipGPRModel) only, not for SGPR")
+        raise NotImplementedError(V.why_refused(["sgpr", "cv"], None, None))
 
     def get_inducing_points(self) -> np.ndarray:
         """Inducing points [M, D] in the model's (scaled) coordinates."""
@@ -583,14 +565,9 @@ class HipSGPRModel(HipGPRModel):
     def _run(self, *, optimiser, max_iter=0, pred_coords=None, full_cov=False, **opt_kwargs):
         if full_cov:
             raise NotImplementedError("HipSGPRModel.predict(full_cov=True) is not built")
-        N, D = self.coords.shape
-        P = 0 if pred_coords is None else len(pred_coords)
-        Xs = np.zeros((0, D)) if pred_coords is None else pred_coords
         Z = self.inducing_points
-        return self._engine.sgpr_fit_predict_batch(
-            D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0], pred_off=np.array([0, P]), Xs=Xs,
-            z_off=np.array([0, len(Z)]), Z=Z, theta0=self._theta[None, :], lo=self._lo[None, :], hi=self._hi[None, :],
-            trainable=self._trainable, kernel=self.kernel, optimiser=optimiser, max_iter=max_iter, **opt_kwargs)
+        return self._engine.sgpr_fit_predict_batch(z_off=np.array([0, len(Z)]), Z=Z, optimiser=optimiser, max_iter=max_iter,
+                                                   **self._tile_args(pred_coords), **opt_kwargs)
 
     def optimise_parameters(self, train_inducing_points=False, max_iter=10_000, fixed_params=None, **opt_kwargs):
         """L-BFGS on the three hyper-parameters with Z fixed (gpflow_models.py:865-901)."""
@@ -635,8 +612,7 @@ class HipSklearnGPRModel(HipGPRModel):
                  param_bounds=None, n_restarts_optimizer=2, random_state=None, engine=None, dtype="f64",
                  obs_var=None, obs_var_col=None, **kwargs):
         if obs_var is not None or obs_var_col is not None:
-            raise NotImplementedError("noise variances per observation (obs_var, obs_var_col) are built for HipGPRModel only, "
-                                      "not for the sklearn model")
+            raise NotImplementedError(V.why_refused(["multistart", "noise"], None, None))
         kk = dict(kernel_kwargs or {})
         if kernel == "Matern":
             nu = float(kk.pop("nu", 1.5))
@@ -682,19 +658,19 @@ class HipSklearnGPRModel(HipGPRModel):
 
     # -- getters / setters (sklearn_models.py:186-240)
     def get_kernel_variance(self) -> float:
-        return float(self._theta[self.D]) ** 2 if self._has_constant else 1.0
+        return float(self._theta[self._column("kernel_variance")]) ** 2 if self._has_constant else 1.0
 
     def set_kernel_variance(self, kernel_variance):
         if self._has_constant:
-            self._theta[self.D] = float(np.sqrt(np.asarray(kernel_variance, dtype=np.float64).reshape(-1)[0]))
+            self._theta[self._column("kernel_variance")] = float(np.sqrt(np.asarray(kernel_variance, dtype=np.float64).reshape(-1)[0]))
 
     def set_likelihood_variance(self, likelihood_variance):
-        self._theta[self.D + 1] = float(np.asarray(likelihood_variance, dtype=np.float64).reshape(-1)[0])
+        self._theta[self._column("likelihood_variance")] = float(np.asarray(likelihood_variance, dtype=np.float64).reshape(-1)[0])
 
     def set_lengthscales(self, lengthscales):
         v = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
         assert len(v) == self.D, f"lengthscales must have length {self.D}"
-        self._theta[:self.D] = v
+        self._theta[self._slice("lengthscales")] = v
 
     # -- constraints (sklearn_models.py:282-360): only the length-scale bounds reach the kernel
     def set_lengthscales_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
@@ -707,7 +683,8 @@ class HipSklearnGPRModel(HipGPRModel):
             div = self.coords_scale[0, :] if scale_magnitude is None else scale_magnitude
             lo, hi = lo / div, hi / div
         # move_within_tol edits a copy in the reference: the current values stay
-        self._lo[:self.D], self._hi[:self.D] = lo, hi
+        ls = self._slice("lengthscales")
+        self._lo[ls], self._hi[ls] = lo, hi
 
     def set_kernel_variance_constraints(self, low, high, move_within_tol=True, tol=1e-8, scale=False, scale_magnitude=None):
         """No effect, as in the reference: it sets an attribute of the Product kernel that sklearn never reads."""
@@ -717,7 +694,7 @@ class HipSklearnGPRModel(HipGPRModel):
 
     # -- fit / objective / predict
     def cross_validate(self, fold=None, apply_scale=True, **kwargs):
-        raise NotImplementedError("held-out predictions are built for HipGPRModel only, not for sklearn experts")
+        raise NotImplementedError(V.why_refused(["multistart", "cv"], None, None))
 
     def restart_starts(self, rng=None):
         """The n_restarts_optimizer further starts, constrained space [n, D + 2], drawn as sklearn draws them from
@@ -732,15 +709,9 @@ class HipSklearnGPRModel(HipGPRModel):
         return out
 
     def _run(self, *, optimiser, max_iter=0, pred_coords=None, starts=None, **opt_kwargs):
-        N, D = self.coords.shape
-        P = 0 if pred_coords is None else len(pred_coords)
-        Xs = np.zeros((0, D)) if pred_coords is None else pred_coords
         S = 1 if starts is None else 1 + len(starts)
-        return self._engine.fit_predict_batch(
-            dtype=self.dtype, D=D, obs_off=np.array([0, N]), X=self.coords, y=self.obs[:, 0],
-            pred_off=np.array([0, P]), Xs=Xs, theta0=self._theta[None, :], lo=self._lo[None, :],
-            hi=self._hi[None, :], trainable=self._trainable, kernel=self.kernel, optimiser=optimiser,
-            max_iter=max_iter, n_starts=S, starts=starts, **opt_kwargs)
+        return self._engine.fit_predict_batch(dtype=self.dtype, optimiser=optimiser, max_iter=max_iter, n_starts=S, starts=starts,
+                                              **self._tile_args(pred_coords), **opt_kwargs)
 
     def optimise_parameters(self, opt=None, **kwargs):
         """sklearn's fit: L-BFGS-B from the current parameters and from n_restarts_optimizer random starts, the best
