@@ -163,6 +163,8 @@ SIGNATURES = {
     "gpsat_n_hyper": (_I, [_I, _I], False),
     "gpsat_n_hyper_mean": (_I, [_I, _I, _I], False),
     "gpsat_bin_batch": (_I, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _D, _I32, _P, _D, _U32, _I64, _P, _P, _P], False),
+    "gpsat_glue_keyed_batch": (_I, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _D, _P, _D, _I64, C.POINTER(_I64), _P, _P, _P], False),
+    "gpsat_glue_keyed_timing": (_I, [_P, _P], False),
     # the entry points of the variant table: (handle, batch, extension struct); the sparse one has been there since ABI 4
     **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(st)], name == "gpsat_sgpr_fit_predict_batch") for name, st in _EXT.items()},
 }

@@ -11,6 +11,8 @@
 //   gpsat_select_batch_ex (gpsat_select_plan.h): check -> cache hit? -> chunks -> stage -> bin (select_bin_table, optional) ->
 //     boxes -> count -> scan -> fill -> unbin (select_unbin_indices, optional) -> fetch -> remember.
 //   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
+//   gpsat_glue_keyed_batch (gpsat_glue_plan.h): check -> key range, layout -> stage -> sort, run heads -> read the group count ->
+//     reduce -> fetch.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -28,6 +30,7 @@
 #include "gpsat_cvfold.h"
 #include "gpsat_select_plan.h"
 #include "gpsat_bin_plan.h"
+#include "gpsat_glue_plan.h"
 
 namespace {
 
@@ -121,6 +124,14 @@ struct gpsat_handle : HandleQueue {
     // then, and no call leaves anything in the two for a later one (the selection cache holds neither).
     struct SelectBufs { DevBuf pts, refs, cnt, idx, box, perm, keys, tmp, ord, bnd; } sel;
     struct BinBufs { DevBuf in, keys, rows, vals, runs, tmp, out; } bin;     // gpsat_bin_batch (layout: gpsat_bin_plan.h)
+    // gpsat_glue_keyed_batch (layout: gpsat_glue_plan.h); ev: after the sort, after the run heads, in front of the reduce
+    // kernel; ms: the last call's sort, run detection and reduce (gpsat_glue_keyed_timing)
+    struct GlueBufs {
+        DevBuf in, keys, rows, runs, tmp, out;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        double ms[3] = {0.0, 0.0, 0.0};
+        ~GlueBufs() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } glue;
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
@@ -1460,6 +1471,104 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)nvars * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return record_timing(h, 1, 2);                              // no ev[0] / ev[3] here: the total is the kernel time
+}
+
+// check (gpsat_glue_plan.h) -> key range -> stage -> sort, run heads -> read the group count -> reduce -> fetch
+int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
+                           const double* xprt, const double* vals, double sigma, const double* sigma_rows, double max_dist,
+                           int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_batch: handle is NULL");
+    char why[160];
+    int rc;
+    if ((rc = gpsat::check_glue_keyed(R, ndim, nvars, key, pred, xprt, vals, sigma, sigma_rows, max_dist, capacity, G, out_key,
+                                      out_count, out, why, sizeof(why))))
+        return fail(rc, why);
+    *G = 0;
+    h->glue.ms[0] = h->glue.ms[1] = h->glue.ms[2] = 0.0;
+    const unsigned long long sentinel = gpsat::glue_keyed_sentinel(R, key);
+    if (sentinel == 0) return GPSAT_OK;                         // no row, or no key >= 0
+    int team = gpsat::glue_keyed_team();
+    if (const char* e = dev_env("GPSAT_DEBUG_GLUE_TEAM")) team = std::atoi(e);       // scripts/cv_glue_bench.py
+    if (team != 1 && team != 4 && team != 8 && team != 16 && team != 32 && team != 64)
+        return fail(GPSAT_EINVAL, "GPSAT_DEBUG_GLUE_TEAM must be 1, 4, 8, 16, 32 or 64");
+    const gpsat::GlueKeyedLayout l = gpsat::glue_keyed_layout(R, ndim, nvars);
+    if ((rc = begin_call(h))) return rc;
+    gpsat_handle::GlueBufs& gb = h->glue;
+    for (hipEvent_t& ev : gb.ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    if ((rc = gb.in.reserve(l.in_bytes))) return rc;
+    if ((rc = gb.keys.reserve(l.keys_bytes))) return rc;
+    if ((rc = gb.rows.reserve(l.rows_bytes))) return rc;
+    if ((rc = gb.runs.reserve(l.runs_bytes))) return rc;
+    // ---- stage
+    const size_t nR = (size_t)R;
+    gpsat::GlueKeyedArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.R = R; a.ndim = ndim; a.nvars = nvars; a.sentinel = sentinel;
+    a.sigma = sigma; a.md2 = gpsat::glue_keyed_md2(max_dist);
+    char* d_in = static_cast<char*>(gb.in.p);
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    HIP_TRY(hipMemcpyAsync(d_in, key, nR * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + l.in_pred, pred, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + l.in_xprt, xprt, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + l.in_vals, vals, (size_t)nvars * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (sigma_rows) HIP_TRY(hipMemcpyAsync(d_in + l.in_sigma, sigma_rows, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.key = reinterpret_cast<const long long*>(d_in);
+    a.pred = reinterpret_cast<const double*>(d_in + l.in_pred);
+    a.xprt = reinterpret_cast<const double*>(d_in + l.in_xprt);
+    a.vals = reinterpret_cast<const double*>(d_in + l.in_vals);
+    a.sigma_rows = sigma_rows ? reinterpret_cast<const double*>(d_in + l.in_sigma) : nullptr;
+    a.keys = static_cast<unsigned long long*>(gb.keys.p); a.keys_sorted = a.keys + nR;
+    a.rows = static_cast<unsigned*>(gb.rows.p); a.perm = a.rows + nR;
+    char* d_runs = static_cast<char*>(gb.runs.p);
+    a.starts = reinterpret_cast<unsigned*>(d_runs);
+    a.n_groups = reinterpret_cast<long long*>(d_runs + l.runs_n_groups);
+    a.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
+    a.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+    // ---- sort and run heads (the kernel time starts once the scratch is there), read the counts
+    if ((rc = run_with_temp(h, gb.tmp, "glue_keyed_sort", h->ev[1],
+                            [&](void* temp, size_t& tb) { return gpsat::glue_keyed_sort(a, temp, tb, gb.ev[0], h->stream); })))
+        return rc;
+    HIP_TRY(hipEventRecord(gb.ev[1], h->stream));
+    long long info[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(info, a.n_groups, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const long long ng = info[0];
+    *G = ng;
+    // ---- reduce, fetch
+    if (ng > 0 && capacity >= ng) {
+        const size_t nG = (size_t)ng;
+        if ((rc = gb.out.reserve(nG * ((size_t)nvars + 1) * sizeof(double) + nG * sizeof(int)))) return rc;
+        a.out_key = static_cast<long long*>(gb.out.p);
+        a.out = reinterpret_cast<double*>(a.out_key + nG);
+        a.out_count = reinterpret_cast<int*>(a.out + (size_t)nvars * nG);
+        HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // behind the reservation
+        HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, h->stream));
+        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        HIP_TRY(hipMemcpyAsync(out_key, a.out_key, nG * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(out_count, a.out_count, nG * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        for (int v = 0; v < nvars; ++v)
+            HIP_TRY(hipMemcpyAsync(out + (size_t)v * capacity, a.out + (size_t)v * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    } else {
+        HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // no reduction: an empty interval
+        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = record_timing(h))) return rc;                     // kernel time: keys, sort, run heads, count round trip, reduce
+    float ms[3] = {0.f, 0.f, 0.f};
+    HIP_TRY(hipEventElapsedTime(&ms[0], h->ev[1], gb.ev[0]));
+    HIP_TRY(hipEventElapsedTime(&ms[1], gb.ev[0], gb.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms[2], gb.ev[2], h->ev[2]));
+    for (int i = 0; i < 3; ++i) gb.ms[i] = ms[i];
+    if ((rc = gpsat::check_glue_capacity(capacity, ng, why, sizeof(why)))) return fail(rc, why);
+    return GPSAT_OK;
+}
+
+int gpsat_glue_keyed_timing(gpsat_handle* h, double* ms) {
+    if (!h || !ms) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_timing: NULL argument");
+    for (int i = 0; i < 3; ++i) ms[i] = h->glue.ms[i];
+    return GPSAT_OK;
 }
 
 #ifdef GPSAT_PROFILE

@@ -1,0 +1,92 @@
+// gpsat_glue_plan.h -- host side of gpsat_glue_keyed_batch: the argument checks, the key range of a call and the layout of the
+// handle's buffers.  Plain C++ without a HIP call, in the manner of gpsat_bin_plan.h; the two checks are exported like
+// gpsat::check_noise (gpsat_plan.h), so that tests drive every refusal without a device.  Part of gpsat_capi.cpp's
+// translation unit.
+#ifndef GPSAT_GLUE_PLAN_H
+#define GPSAT_GLUE_PLAN_H
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+#include "gpsat_hip.h"
+
+#ifndef GPSAT_GLUE_MAXVARS
+#define GPSAT_GLUE_MAXVARS 4
+#endif
+
+namespace gpsat {
+
+// Everything gpsat_glue_keyed_batch can refuse before it has counted the keys (the handle is the entry point's to check).
+// GPSAT_OK, or GPSAT_EINVAL with the reason in why[why_len].  G is required whatever R is; the inputs with R > 0; the outputs
+// with capacity > 0.
+int check_glue_keyed(int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred, const double* xprt,
+                     const double* vals, double sigma, const double* sigma_rows, double max_dist, int64_t capacity,
+                     const int64_t* G, const int64_t* out_key, const int32_t* out_count, const double* out, char* why,
+                     size_t why_len) {
+    if (why_len > 0) why[0] = 0;
+    auto bad = [&](const char* msg) { std::snprintf(why, why_len, "gpsat_glue_keyed_batch: %s", msg); return GPSAT_EINVAL; };
+    if (!G) return bad("G is NULL");
+    if (R < 0 || capacity < 0) return bad("R and capacity must not be negative");
+    if (R > 2147483647LL) return bad("more than 2^31-1 rows in one call");
+    if (ndim < 1 || ndim > 2) return bad("ndim must be 1 or 2");
+    if (nvars < 1 || nvars > GPSAT_GLUE_MAXVARS) return bad("nvars must be 1..4 (GPSAT_GLUE_MAXVARS)");
+    if (!sigma_rows && (!(sigma > 0.0) || !std::isfinite(sigma))) return bad("sigma must be finite and positive when sigma_rows is NULL");
+    if (max_dist != max_dist) return bad("max_dist is NaN (+inf or a value <= 0 switches the limit off)");
+    if (R > 0 && (!key || !pred || !xprt || !vals)) return bad("key / pred / xprt / vals is NULL");
+    if (capacity > 0 && (!out_key || !out_count || !out)) return bad("out_key / out_count / out is NULL");
+    return GPSAT_OK;
+}
+
+// After the keys are counted: the outputs must hold one record per distinct key.
+int check_glue_capacity(int64_t capacity, int64_t G, char* why, size_t why_len) {
+    if (why_len > 0) why[0] = 0;
+    if (capacity >= G) return GPSAT_OK;
+    std::snprintf(why, why_len, "gpsat_glue_keyed_batch: capacity %lld < G %lld", (long long)capacity, (long long)G);
+    return GPSAT_EINVAL;
+}
+
+// The key that rows with a negative key are given on the device: one above the largest key of the call, so that they sort
+// behind every group and the sort runs over the bits of the largest key only.  0: no row has a key >= 0.
+inline unsigned long long glue_keyed_sentinel(int64_t R, const int64_t* key) {
+    int64_t mx = -1;
+    for (int64_t i = 0; i < R; ++i) mx = key[i] > mx ? key[i] : mx;
+    return (unsigned long long)(mx + 1);       // mx <= 2^63 - 1: no overflow in 64 unsigned bits
+}
+
+// max_dist as the kernel takes it: the square, or a negative value when there is no limit (+inf, <= 0)
+inline double glue_keyed_md2(double max_dist) {
+    return (max_dist > 0.0 && std::isfinite(max_dist)) ? max_dist * max_dist : -1.0;
+}
+
+// Bytes of the handle's buffers and the offsets of what lies in them.
+struct GlueKeyedLayout {
+    // `in`: key [R] (int64), pred and xprt [ndim][R], vals [nvars][R], sigma_rows [R] (room reserved either way)
+    size_t in_bytes, in_pred, in_xprt, in_vals, in_sigma;
+    size_t keys_bytes;                // [2][R] 64-bit keys: as given (negative ones replaced), sorted
+    size_t rows_bytes;                // [2][R] 32-bit rows: source, sorted
+    // `runs`: starts [R + 1] rounded to 256 B, a 256-B block with n_groups [2] and n_runs, the head flags [R]
+    size_t runs_bytes, runs_n_groups, runs_n_runs, runs_flags;
+};
+
+inline GlueKeyedLayout glue_keyed_layout(int64_t R, int ndim, int nvars) {
+    const size_t nR = (size_t)R;
+    GlueKeyedLayout l = {};
+    l.in_pred = nR * sizeof(int64_t);
+    l.in_xprt = l.in_pred + (size_t)ndim * nR * sizeof(double);
+    l.in_vals = l.in_xprt + (size_t)ndim * nR * sizeof(double);
+    l.in_sigma = l.in_vals + (size_t)nvars * nR * sizeof(double);
+    l.in_bytes = l.in_sigma + nR * sizeof(double);
+    l.keys_bytes = 2 * nR * sizeof(unsigned long long);
+    l.rows_bytes = 2 * nR * sizeof(unsigned);
+    const size_t starts_bytes = ((nR + 1) * sizeof(unsigned) + 255) & ~size_t(255);
+    l.runs_n_groups = starts_bytes;
+    l.runs_n_runs = starts_bytes + 16;
+    l.runs_flags = starts_bytes + 256;
+    l.runs_bytes = l.runs_flags + nR;
+    return l;
+}
+
+}  // namespace gpsat
+#endif

@@ -248,6 +248,31 @@ hipError_t launch_smooth(int T, const double* x, const double* y, const double* 
                          hipStream_t stream);
 hipError_t launch_glue(int G, int ndim, int nvars, long long R, const long long* seg, const double* pred, const double* xprt,
                        const double* vals, double sigma, const double* sigma_rows, double* out, hipStream_t stream);
+// keyed glue (gpsat_glue_keyed_batch): rows in any order, grouped by an integer key on the device
+struct GlueKeyedArgs {
+    long long R;                      // rows (< 2^31)
+    int ndim, nvars;
+    const long long* key;             // [R] as the caller gave them; < 0: the row is ignored
+    unsigned long long sentinel;      // largest key + 1: the key of ignored rows, they sort behind every group
+    unsigned long long *keys, *keys_sorted;   // [R]
+    unsigned *rows, *perm;            // [R] source rows, and the same in sorted order
+    unsigned char* flags;             // [R] 1 at the first row of every run of equal keys
+    unsigned* starts;                 // [R + 1] first sorted row of every run; starts[n_groups] = rows with a key >= 0
+    unsigned* n_runs;                 // [1]
+    long long* n_groups;              // [2] distinct keys >= 0, rows that have one
+    const double *pred, *xprt, *vals, *sigma_rows;   // [ndim][R], [ndim][R], [nvars][R], [R] or nullptr; in SOURCE order
+    double sigma;
+    double md2;                       // max_dist^2; < 0: no limit
+    long long* out_key;               // [G] ascending
+    int* out_count;                   // [G] rows that took part
+    double* out;                      // [nvars][G]
+};
+// key per row, stable sort of (key, row), run heads; leaves n_groups[0..1] on the device.  temp == nullptr: only the size
+// of the temporary storage is returned.  `after_sort`, when given, is recorded between the sort and the run detection.
+hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream);
+// one team of `team` lanes per group, gathering through the permutation; team in {1, 4, 8, 16, 32, 64}
+hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream);
+int glue_keyed_team();                // the team width of the product
 
 // sparse GP experts (gpsat_sgpr.hip, fp64 only); device pointers.  One workgroup per tile from an atomic queue.
 struct SgprArgs {

@@ -11,8 +11,18 @@
 // out of L1 / L2): the LDS-tiled form (one thread per output, inputs staged in tiles of 256 and read by broadcast;
 // scripts/experiments/r4_smooth_kernel_lds_tiled.patch) measured 390 G pairs/s at 131 072 locations and 17 instead of 229 at
 // 4 096 (a quarter of the waves in flight, one dependent accumulation chain per thread) -- not adopted.
+//   glue_keyed_kernel : the same average over rows that arrive in ANY order with an integer key per row (held-out
+//                   predictions keyed by observation: groups of 3..20 rows, millions of them).  A stable rocPRIM radix sort
+//                   of (key, source row) over the bits of the largest key, run heads by flag + select (as gpsat_bin.hip),
+//                   then one TEAM of lanes per group that gathers its rows through the permutation: lane l of the team adds
+//                   the group's rows l, l + W, l + 2W, ... in that order and a fixed xor tree over the team's W lanes joins
+//                   them.  A group's bits are a function of its own rows in source order (the sort is stable) and of W, a
+//                   compile-time constant of the product: not of the other keys, the grid or the capacity.  No float atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 #include "gpsat_kernels.h"
 
 namespace gpsat {
@@ -94,6 +104,131 @@ hipError_t launch_smooth(int T, const double* x, const double* y, const double* 
 hipError_t launch_glue(int G, int ndim, int nvars, long long R, const long long* seg, const double* pred, const double* xprt,
                        const double* vals, double sigma, const double* sigma_rows, double* out, hipStream_t stream) {
     hipLaunchKernelGGL(glue_kernel, dim3((G + 3) / 4), dim3(256), 0, stream, G, ndim, nvars, R, seg, pred, xprt, vals, sigma, sigma_rows, out);
+    return hipGetLastError();
+}
+
+// ---- keyed glue
+__global__ void __launch_bounds__(256) glue_key_kernel(const GlueKeyedArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.R) return;
+    const long long k = a.key[i];
+    a.keys[i] = k < 0 ? a.sentinel : (unsigned long long)k;
+    a.rows[i] = (unsigned)i;
+}
+
+__global__ void __launch_bounds__(256) glue_flag_kernel(const GlueKeyedArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.R) return;
+    a.flags[i] = (i == 0 || a.keys_sorted[i] != a.keys_sorted[i - 1]) ? 1 : 0;
+}
+
+// runs -> groups: the run of ignored rows, when there is one, is the last; starts[n_groups] = first row past the groups
+__global__ void glue_finish_kernel(const GlueKeyedArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    long long n = *a.n_runs;
+    long long valid = a.R;
+    if (n > 0 && a.keys_sorted[a.starts[n - 1]] == a.sentinel) { valid = a.starts[n - 1]; --n; }
+    a.starts[n] = (unsigned)valid;
+    a.n_groups[0] = n;
+    a.n_groups[1] = valid;
+}
+
+// W lanes per group, 256 / W groups per workgroup.  No lane leaves before the shuffles: a team past the last group walks an
+// empty range and stores nothing.
+template <int W>
+__global__ void __launch_bounds__(256) glue_keyed_kernel(const GlueKeyedArgs a, long long G) {
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) / W;
+    const int tl = threadIdx.x & (W - 1);
+    const bool live = g < G;
+    const unsigned s = live ? a.starts[g] : 0u, e = live ? a.starts[g + 1] : 0u;
+    const size_t R = (size_t)a.R;
+    const int ndim = a.ndim, nvars = a.nvars;
+    double ws = 0.0;
+    int cnt = 0;
+    double acc[GPSAT_GLUE_MAXVARS];
+#pragma unroll
+    for (int v = 0; v < GPSAT_GLUE_MAXVARS; ++v) acc[v] = 0.0;
+    for (unsigned i = s + tl; i < e; i += W) {
+        const size_t r = a.perm[i];
+        const double sg = a.sigma_rows ? a.sigma_rows[r] : a.sigma;
+        const double cnorm = 1.0 / (sg * 2.5066282746310002);       // 1 / (sigma sqrt(2 pi))
+        double w = 1.0, d2 = 0.0;
+        for (int d = 0; d < ndim; ++d) {
+            const double df = a.pred[(size_t)d * R + r] - a.xprt[(size_t)d * R + r];
+            const double zz = df / sg;
+            d2 += df * df;
+            w *= exp(-zz * zz / 2) * cnorm;
+        }
+        if (a.md2 >= 0.0 && !(d2 < a.md2)) continue;                // strict, and a NaN distance is outside
+        ++cnt;
+        ws += w;
+#pragma unroll
+        for (int v = 0; v < GPSAT_GLUE_MAXVARS; ++v)
+            if (v < nvars) {
+                const double x = a.vals[(size_t)v * R + r];          // NaN: out of the sum, its weight stays (glue_kernel)
+                if (x == x) acc[v] += w * x;
+            }
+    }
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) {
+        ws += __shfl_xor(ws, off);
+        cnt += __shfl_xor(cnt, off);
+#pragma unroll
+        for (int v = 0; v < GPSAT_GLUE_MAXVARS; ++v) acc[v] += __shfl_xor(acc[v], off);
+    }
+    if (live && tl == 0) {
+        a.out_key[g] = (long long)a.keys_sorted[s];
+        a.out_count[g] = cnt;
+#pragma unroll
+        for (int v = 0; v < GPSAT_GLUE_MAXVARS; ++v)
+            if (v < nvars) a.out[(size_t)v * (size_t)G + (size_t)g] = cnt ? acc[v] / ws : __builtin_nan("");
+    }
+}
+
+static inline int glue_key_bits(unsigned long long sentinel) {
+    int bits = 1;
+    while (bits < 64 && (sentinel >> bits) != 0) ++bits;
+    return bits;
+}
+
+hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream) {
+    const int bits = glue_key_bits(a.sentinel);
+    rocprim::counting_iterator<unsigned> rows0(0);
+    if (!temp) {
+        size_t t1 = 0, t2 = 0;
+        hipError_t e = rocprim::radix_sort_pairs(nullptr, t1, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);
+        if (e != hipSuccess) return e;
+        e = rocprim::select(nullptr, t2, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
+        temp_bytes = t1 > t2 ? t1 : t2;
+        return e;
+    }
+    const unsigned grid = (unsigned)((a.R + 255) / 256);
+    hipLaunchKernelGGL(glue_key_kernel, dim3(grid), dim3(256), 0, stream, a);
+    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);   // stable
+    if (e != hipSuccess) return e;
+    if (after_sort && (e = hipEventRecord(after_sort, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(glue_flag_kernel, dim3(grid), dim3(256), 0, stream, a);
+    e = rocprim::select(temp, temp_bytes, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(glue_finish_kernel, dim3(1), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+constexpr int GLUE_KEYED_TEAM = 8;
+int glue_keyed_team() { return GLUE_KEYED_TEAM; }
+
+hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream) {
+    if (G <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
+    switch (team) {
+        case 1: hipLaunchKernelGGL(glue_keyed_kernel<1>, grid, block, 0, stream, a, G); break;
+        case 4: hipLaunchKernelGGL(glue_keyed_kernel<4>, grid, block, 0, stream, a, G); break;
+        case 8: hipLaunchKernelGGL(glue_keyed_kernel<8>, grid, block, 0, stream, a, G); break;
+        case 16: hipLaunchKernelGGL(glue_keyed_kernel<16>, grid, block, 0, stream, a, G); break;
+        case 32: hipLaunchKernelGGL(glue_keyed_kernel<32>, grid, block, 0, stream, a, G); break;
+        case 64: hipLaunchKernelGGL(glue_keyed_kernel<64>, grid, block, 0, stream, a, G); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -597,6 +597,49 @@ class Engine:
             raise GpsatError(f"gpsat_glue_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         return out
 
+    def glue_keyed_batch(self, key, pred, xprt, vals, sigma, max_dist=None):
+        """Weighted combination of overlapping predictions grouped by an integer key on the device
+        (gpsat_glue_keyed_batch): rows in any order; key [R] (negative: the row is ignored); pred, xprt [ndim, R];
+        vals [nvars, R]; sigma scalar or per row [R]; max_dist: rows at that distance from their expert or beyond stay
+        out (None: no limit).  Returns (keys [G] ascending, counts [G] rows that took part, out [nvars, G])."""
+        if not hasattr(self._lib, "gpsat_glue_keyed_batch"):
+            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_batch: rebuild the library (there is no host fallback)")
+        key = np.ascontiguousarray(key, dtype=np.int64)
+        pred = np.ascontiguousarray(pred, dtype=np.float64)
+        xprt = np.ascontiguousarray(xprt, dtype=np.float64)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        ndim, R = pred.shape
+        nvars = vals.shape[0]
+        assert key.shape == (R,) and xprt.shape == pred.shape and vals.shape[1] == R
+        srow = None
+        if np.ndim(sigma) > 0:
+            srow = np.ascontiguousarray(sigma, dtype=np.float64)
+            assert srow.shape == (R,)
+        md = float("inf") if max_dist is None else float(max_dist)
+
+        def call(cap):
+            keys, counts = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int32)
+            out = np.empty((nvars, cap), dtype=np.float64)
+            n = C.c_int64(0)
+            rc = self._lib.gpsat_glue_keyed_batch(self._h, R, ndim, nvars, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(vals),
+                                                  0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
+                                                  md, cap, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out))
+            return rc, int(n.value), keys, counts, out
+
+        # capacity R always suffices; only the first G records of the outputs are ever written (untouched pages cost nothing)
+        rc, n, keys, counts, out = call(R)
+        if rc != 0:
+            raise GpsatError(f"gpsat_glue_keyed_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        return keys[:n].copy(), counts[:n].copy(), np.ascontiguousarray(out[:, :n])
+
+    def glue_keyed_timing(self):
+        """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch on this engine."""
+        ms = np.zeros(3)
+        rc = self._lib.gpsat_glue_keyed_timing(self._h, _ptr(ms))
+        if rc != 0:
+            raise GpsatError(f"gpsat_glue_keyed_timing failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        return tuple(ms)
+
     def bin_batch(self, x, y, v, gid, n_groups, x_edges, y_edges, statistics, x_hi=None, y_hi=None) -> BinResult:
         """Binned statistics of raw observations, all groups in one call (gpsat_bin_batch; scipy.stats.binned_statistic_2d
         per group, bit for bit).  x, y, v: [R] (y None: one dimension, y_edges is not read); gid: [R] groups 0..n_groups-1 or

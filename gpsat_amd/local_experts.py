@@ -96,8 +96,16 @@ a fold leaves are de-meaned again when the model's ``obs_mean`` is "local", a fo
 waves like ``cv_preds``, has one row per fold: expert index; the ``by`` columns' values; ``num_obs`` (rows fitted);
 ``lengthscales_<k>``, ``kernel_variance``, ``likelihood_variance`` in the units of the parameter tables;
 ``objective_value``; ``optimise_success``; and ``f_bar``, the de-meaning constant of the fold's own fit (the tile's plus
-``obs_scale`` times the mean of the remaining rows).  What still differs from the reference: a row is predicted by every
-expert that selects it and the predictions are not glued, and ``max_dist`` of the prediction locations is not applied.
+``obs_scale`` times the mean of the remaining rows).
+``cv_glue={"inference_radius": r, "R": 3, "max_dist": d | None, "xprt_loc_cols": [...] | None}`` (constructor; needs ``cv``,
+either kind): a row is predicted by every expert that selects it, and after the run these rows are glued into ONE held-out
+prediction per observation, as the reference glues the overlapping predictions of its cross-validation runs (DESIGN.md
+section 19; ``postprocessing.glue_cv_predictions``, the grouping and the weighted sums on the device): table ``cv_glued``
+(``obs_index``, the ``by`` columns, ``pred_loc_<c>``, the raw observation, ``f*``, ``f*_var``, ``y_var`` in RAW units,
+``n_experts``, ``z``), keyed on the observation's positional row in the selected frame, and table ``cv_scores``
+(``postprocessing.score_cv_predictions``: overall and per combination of the ``by`` columns).  ``max_dist`` leaves out the
+experts at that distance or beyond in ``xprt_loc_cols`` (default: the first two coordinate columns).  Both tables are of
+the experts THIS run fitted: a resumed run glues what it ran, ``glue_cv_predictions`` on the store glues everything.
 """
 from __future__ import annotations
 
@@ -858,11 +866,12 @@ _Plan = make_dataclass("_Plan", [
 # ----------------------------------------------------------------------------------------------------------
 class BatchedLocalExpertOI:
     def __init__(self, expert_loc_config: dict, data_config: dict, model_config: dict, pred_loc_config: dict,
-                 engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None):
+                 engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None, cv_glue=None):
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
         self.dtype = self._ask_variants(data_config, model_config, dtype, cv)
         self._parse_cv(cv)
+        self._parse_cv_glue(cv_glue, data_config)
         self._load_data(data_config)
         self._load_expert_locs(expert_loc_config, data_config, device_select)
         self._set_profiles(model_config)
@@ -941,6 +950,33 @@ class BatchedLocalExpertOI:
             raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
         self.cv = cv
         self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
+
+    def _parse_cv_glue(self, cv_glue, data_config):
+        """``cv_glue``: glue the held-out predictions per observation and score them after the run (tables cv_glued and
+        cv_scores): {"inference_radius": r, "R": 3, "max_dist": d | None, "xprt_loc_cols": [...] | None}.  None: nothing of a
+        run differs.  Sets ``cv_glue`` (the option with its defaults filled in) and records it in the run's configuration."""
+        self.cv_glue = None
+        if cv_glue is None:
+            return
+        if self.cv is None:
+            raise ValueError("cv_glue glues the held-out predictions of a run with cv: give cv='loo' or cv={'by': [...]} too")
+        if not isinstance(cv_glue, dict) or "inference_radius" not in cv_glue or \
+                not set(cv_glue) <= {"inference_radius", "R", "max_dist", "xprt_loc_cols"}:
+            raise ValueError("cv_glue must be None or {'inference_radius': r, 'R': 3, 'max_dist': d | None, 'xprt_loc_cols': [...] | None}")
+        r = cv_glue["inference_radius"]
+        if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not (r > 0 and np.isfinite(r)):
+            raise ValueError(f"cv_glue: inference_radius must be one finite positive number, got {r!r}")
+        coords = list(data_config["coords_col"])
+        cols = cv_glue.get("xprt_loc_cols")
+        cols = coords[:2] if cols is None else _as_list(cols)
+        if not 1 <= len(cols) <= 2 or any(c not in coords for c in cols):
+            raise ValueError(f"cv_glue: xprt_loc_cols must be 1 or 2 of the coordinate columns {coords}, got {cols}")
+        md = cv_glue.get("max_dist")
+        if md is not None and not (md == md):
+            raise ValueError("cv_glue: max_dist is NaN")
+        self.cv_glue = {"inference_radius": float(r), "R": float(cv_glue.get("R", 3)), "max_dist": None if md is None else float(md),
+                        "xprt_loc_cols": list(cols)}
+        self.config["cv_glue"] = dict(self.cv_glue)
 
     def _load_data(self, data_config):
         """The globally selected frame (local_experts.py:266-290) and, with ``cv_by``, the fold code of every row."""
@@ -1181,12 +1217,17 @@ class BatchedLocalExpertOI:
                 out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
                 if self.cv is not None and sh.tables is None:
                     self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped, sh.cvp_frames)
+                if self.cv_glue is not None:
+                    self._cv_glue_tables(plan, out, sh.cv_pos)
         finally:
             tf = time.perf_counter()                               # also after a fault: what was committed is on disk
             for sh in reversed(shards):
                 while sh.flush:
                     sh.flush.pop().result()
             self.timings["flush_wait_s"] += time.perf_counter() - tf
+        if self.cv_glue is not None and len(out.get(f"cv_glued{table_suffix}", ())):
+            for name in (f"cv_glued{table_suffix}", f"cv_scores{table_suffix}"):      # whole tables, behind the waves' commits
+                store.put(name, out[name])
         self.run_seconds = time.perf_counter() - t_start
         self.timings["total_s"] = self.run_seconds
         return out
@@ -1420,14 +1461,36 @@ class BatchedLocalExpertOI:
         np.add.at(skipped, tile[skip], 1)
         return labels, skipped
 
+    def _cv_positions(self, plan, items, cv_rows):
+        """The positional row in the selected frame of every row of ``_cv_frame(plan, items, cv_rows, ...)``."""
+        parts = [plan.idx[plan.off[i]:plan.off[i + 1]] for i, c in zip(np.asarray(items, dtype=np.int64), cv_rows) if len(c)]
+        return np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
+
+    def _cv_glue_tables(self, plan, tables, positions):
+        """``cv_glued`` and ``cv_scores`` of a run's ``cv_preds`` into its tables: one glued held-out prediction per
+        observation, keyed on the observation's positional row in the selected frame (``positions``: per wave, the rows of
+        the wave's cv_preds frame), in raw units by the profile's ``obs_scale`` (postprocessing.glue_cv_predictions)."""
+        from . import postprocessing as post
+        cvp = tables[f"cv_preds{plan.table_suffix}"]
+        g = self.cv_glue
+        if len(cvp):
+            key = np.concatenate(positions) if len(positions) else np.zeros(0, dtype=np.int64)
+            assert len(key) == len(cvp)
+            glued = post._glue_cv_frame(cvp, key, g["xprt_loc_cols"], g["inference_radius"], g["R"], g["max_dist"],
+                                        plan.profiles[0].obs_scale, self.engine)
+            scores = post.score_cv_predictions(glued, by=self.cv_by or None)
+        else:
+            glued, scores = pd.DataFrame(), pd.DataFrame()
+        tables[f"cv_glued{plan.table_suffix}"] = glued
+        tables[f"cv_scores{plan.table_suffix}"] = scores
+
     def _cv_frame(self, plan, items, cv_rows, f_bar):
         """Table ``cv_preds`` of the tiles among ``items`` (``cv_rows``: per item the [N, 3] held-out f*, f*_var, y_var of its
         rows, in the order of the tile; ``f_bar``: per item the tile's de-meaning constant): expert coordinates as the index,
         like ``preds``, and the values in the units of ``preds`` -- the observation is ``f_bar + obs_scale f*`` plus noise."""
         cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
         cnt = np.array([len(c) for c in cv_rows], dtype=np.int64)
-        rows = np.concatenate([plan.idx[plan.off[i]:plan.off[i + 1]] for i, n in zip(items, cnt) if n]).astype(np.int64) \
-            if cnt.sum() else np.zeros(0, dtype=np.int64)
+        rows = self._cv_positions(plan, items, cv_rows)
         vals = _cat([c for c in cv_rows if len(c)], 3)
         tot = int(cnt.sum())
         fr = {"_dim_0": np.arange(tot) - np.repeat(np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt),
@@ -1616,6 +1679,7 @@ class _ShardRunner:
         self.piece_futs, self.packs = {}, {}   # wave -> writes of its preds pieces; job -> its packed arrays (future)
         self.rows = ([], [], [])               # fixed, preds, cov of the closed waves
         self.tables, self.flush = None, []     # the only wave's tables; the flush queued last
+        self.cv_pos = []                            # per closed wave: the positional rows of its cv_preds frame (cv_glue keys on them)
         self.open_cv, self.cv_frames, self.cv_skipped = {}, [], np.zeros(0, dtype=np.int64)   # held-out rows of the open waves; closed waves' frames
         self.open_cvp, self.cvp_frames = {}, []     # cv refit: per-fold rows of the open waves; closed waves' cv_params frames
         self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
@@ -1809,6 +1873,7 @@ class _ShardRunner:
         cvp = self.open_cvp.pop(wi)
         if oi.cv is not None:
             self.cv_frames.append(oi._cv_frame(p, items, cvr, fixed[:, self.H + _OBS_MEAN]))
+            self.cv_pos.append(oi._cv_positions(p, items, cvr))
             if oi.cv_refit is not None:
                 self.cvp_frames.append(oi._cv_params_frame(p, items, cvp, fixed[:, self.H + _OBS_MEAN]))
             self.cv_skipped = np.concatenate([self.cv_skipped, skp])

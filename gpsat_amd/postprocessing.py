@@ -1,7 +1,9 @@
 """Post-processing of local-expert results on the MI355X: hyper-parameter smoothing and gluing of overlapping
 predictions.  Host-side mirror of GPSat/postprocessing.py (``smooth_hyperparameters`` :117-375,
 ``glue_local_predictions`` / ``_1d`` / ``_2d`` :447-577): same argument names and meaning, tables in / tables out; the
-arithmetic runs in gpsat_post.hip through the C ABI (``gpsat_smooth_batch`` / ``gpsat_glue_batch``).  No CPU fallback:
+arithmetic runs in gpsat_post.hip through the C ABI (``gpsat_smooth_batch`` / ``gpsat_glue_batch``).  Beside them, for the
+held-out predictions of a run with ``cv``: ``glue_cv_predictions`` (one glued prediction per observation, grouped by an
+integer key on the device, ``gpsat_glue_keyed_batch``) and ``score_cv_predictions``.  No CPU fallback:
 without the HIP library these functions raise."""
 import copy
 import json
@@ -126,6 +128,106 @@ def _glue(preds_df, pred_loc_cols, xprt_loc_cols, vars_to_glue, inference_radius
     for i, v in enumerate(vars_to_glue):
         out[v] = glued[i]
     return out
+
+
+def _cv_layout(columns):
+    """(by columns, pred_loc columns, observation column) of a ``cv_preds`` / ``cv_glued`` table, from the order in which the
+    orchestrator lays them out: ..., obs_index, <by>, pred_loc_<c>..., <obs>, f*, ..."""
+    cols = list(columns)
+    ploc = [c for c in cols if c.startswith("pred_loc_")]
+    if "obs_index" not in cols or "f*" not in cols or not ploc:
+        raise ValueError(f"not a table of held-out predictions: columns {cols}")
+    by = cols[cols.index("obs_index") + 1:cols.index(ploc[0])]
+    return by, ploc, cols[cols.index("f*") - 1]
+
+
+def _glue_cv_frame(cvp, key, xprt_loc_cols, inference_radius, R, max_dist, obs_scale, engine):
+    """``cv_glued`` of one ``cv_preds`` table.  ``key``: the group of every row (int64; None: from ``obs_index``)."""
+    eng = engine or default_engine()
+    if isinstance(inference_radius, bool) or not isinstance(inference_radius, (int, float, np.integer, np.floating)):
+        raise TypeError("inference_radius must be one number: per-expert radii are not built for held-out predictions")
+    by, ploc, obs_col = _cv_layout(cvp.columns)
+    coords = [c[len("pred_loc_"):] for c in ploc]
+    xcols = list(coords[:2]) if xprt_loc_cols is None else ([xprt_loc_cols] if isinstance(xprt_loc_cols, str) else list(xprt_loc_cols))
+    if not 1 <= len(xcols) <= 2 or any(c not in coords or c not in cvp.index.names for c in xcols):
+        raise ValueError(f"xprt_loc_cols must be 1 or 2 of the coordinate columns {coords}, got {xcols}")
+    n = len(cvp)
+    f, fv, yv, fbar = (cvp[c].values.astype(np.float64) for c in ("f*", "f*_var", "y_var", "f_bar"))
+    osc = float(obs_scale)
+    vals = np.stack([fbar + osc * f, osc * osc * fv, osc * osc * yv])      # raw units
+    oi = cvp["obs_index"].values
+    if key is None:
+        if np.issubdtype(oi.dtype, np.integer) and (n == 0 or oi.min() >= 0):
+            key = oi.astype(np.int64)
+        else:
+            key = pd.factorize(oi)[0].astype(np.int64)
+    key = np.where(np.isnan(f), -1, np.asarray(key, dtype=np.int64))      # not held out, skipped fold, failed tile
+    pred = np.stack([cvp[f"pred_loc_{c}"].values.astype(np.float64) for c in xcols])
+    xprt = np.stack([cvp.index.get_level_values(c).values.astype(np.float64) for c in xcols])
+    keys, counts, out = eng.glue_keyed_batch(key, pred, xprt, vals, float(inference_radius) / R, max_dist)
+    # carried columns: the value of the key's first row
+    rows = np.nonzero(key >= 0)[0]
+    first = np.zeros(len(keys), dtype=np.int64)
+    first[np.searchsorted(keys, key[rows])[::-1]] = rows[::-1]           # repeated positions: the last assignment stays
+    fr = {c: cvp[c].values[first] for c in ["obs_index"] + by + ploc + [obs_col]}
+    fr.update({"f*": out[0], "f*_var": out[1], "y_var": out[2], "n_experts": counts.astype(np.int64)})
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fr["z" if obs_col != "z" else "z_score"] = (fr[obs_col].astype(np.float64) - out[0]) / np.sqrt(out[2])
+    return pd.DataFrame(fr)
+
+
+def glue_cv_predictions(result: Union[str, Dict[str, pd.DataFrame]], xprt_loc_cols: Optional[List[str]], inference_radius: float,
+                        R=3, max_dist: Optional[float] = None, obs_scale: float = 1.0, table_suffix: str = "",
+                        engine=None) -> pd.DataFrame:
+    """One held-out prediction per observation: table ``cv_preds<table_suffix>`` of a run with ``cv`` (a dict of tables or
+    a store path) holds one row per expert that selected the observation; they are glued as the reference glues the
+    overlapping predictions of its cross-validation runs (``glue_local_predictions_1d`` / ``_2d``,
+    GPSat/postprocessing.py:447-577) -- weights ``normpdf(pred_loc; expert_loc, inference_radius / R)`` in
+    ``xprt_loc_cols``, 1 or 2 of the coordinate columns (None: the first two) -- with the grouping on the device
+    (``Engine.glue_keyed_batch``).  Every row is first converted to raw units with the model's ``obs_scale``: mean
+    ``f_bar + obs_scale f*``, variances times ``obs_scale**2``.  Rows whose ``f*`` is NaN (not held out, skipped fold,
+    failed tile) take no part.  ``max_dist``: a row takes part only if its expert lies nearer than that in
+    ``xprt_loc_cols`` (strictly).  The group is ``obs_index``, used as it is when its dtype is a non-negative integer and
+    factorised otherwise.  Returns ``cv_glued``, a row per held-out observation in ascending key order: ``obs_index``, the
+    ``by`` columns, ``pred_loc_<c>``, the raw observation, ``f*``, ``f*_var``, ``y_var`` (raw units), ``n_experts`` (rows
+    that took part; 0: all of them beyond ``max_dist``, the values are NaN) and ``z = (obs - f*) / sqrt(y_var)`` (named
+    ``z_score`` when the observation column itself is called ``z``)."""
+    tables = result if isinstance(result, dict) else ResultStore(result).tables()
+    name = f"cv_preds{table_suffix}"
+    if name not in tables:
+        raise KeyError(f"table {name} is not in {list(tables.keys())}: run with cv=...")
+    return _glue_cv_frame(tables[name], None, xprt_loc_cols, inference_radius, R, max_dist, obs_scale, engine)
+
+
+def score_cv_predictions(cv_glued: pd.DataFrame, by: Optional[List[str]] = None) -> pd.DataFrame:
+    """``cv_scores`` of a ``cv_glued`` table: one row overall (the ``by`` columns NaN / None) and, with ``by``, one per
+    combination of those columns.  ``n`` rows scored, ``n_missing`` rows left out (no expert took part, or a NaN among
+    observation, mean and variance), ``bias`` = mean(f* - obs), ``rmse`` and ``nll`` as the reference's ``utils.rmse`` and
+    ``utils.nll`` with ``sig = sqrt(y_var)`` (the nll as the mean per row instead of the total), ``mean_z2``.  Host NumPy."""
+    by = [] if by is None else ([by] if isinstance(by, str) else list(by))
+    _, _, obs_col = _cv_layout(cv_glued.columns)
+    y, mu, var = (cv_glued[c].values.astype(np.float64) for c in (obs_col, "f*", "y_var"))
+    ok = (cv_glued["n_experts"].values > 0) & ~(np.isnan(y) | np.isnan(mu) | np.isnan(var))
+
+    def score(rows):
+        use = rows[ok[rows]]
+        rec = {"n": len(use), "n_missing": len(rows) - len(use)}
+        if len(use) == 0:
+            rec.update(bias=np.nan, rmse=np.nan, nll=np.nan, mean_z2=np.nan)
+            return rec
+        yy, mm, sig = y[use], mu[use], np.sqrt(var[use])
+        rec["bias"] = float(np.mean(mm - yy))
+        rec["rmse"] = float(np.sqrt(np.mean((yy - mm) ** 2)))
+        rec["nll"] = float(np.mean(np.log(sig * np.sqrt(2 * np.pi)) + (yy - mm) ** 2 / (2 * sig ** 2)))
+        rec["mean_z2"] = float(np.mean(((yy - mm) / sig) ** 2))
+        return rec
+
+    recs = [dict({c: None for c in by}, **score(np.arange(len(cv_glued))))]
+    if by:
+        for kv, sub in cv_glued.reset_index(drop=True).groupby(by, sort=True):
+            kv = kv if isinstance(kv, tuple) else (kv,)
+            recs.append(dict(zip(by, kv), **score(sub.index.values)))
+    return pd.DataFrame(recs, columns=by + ["n", "n_missing", "bias", "rmse", "nll", "mean_z2"])
 
 
 def glue_local_predictions_1d(preds_df: pd.DataFrame, pred_loc_col: str, xprt_loc_col: str,

@@ -438,6 +438,42 @@ int gpsat_glue_batch(gpsat_handle *h, int64_t R, int32_t G, int32_t ndim, int32_
                      const double *sigma_rows, double *out);
 
 /*
+ * Gluing by an integer key, rows in ANY order (added within ABI 4, check for the symbol): what gpsat_glue_batch computes,
+ * for callers whose groups are named by an integer instead of a pre-sorted segment table -- held-out predictions keyed by
+ * the observation they predict: millions of groups of a few rows each.  The grouping runs on the device (a stable radix
+ * sort of (key, row) over the bits of the largest key, run heads, one team of 8 lanes per group).
+ *
+ * key        : host [R]; every distinct key >= 0 yields one output record, in ascending key order; key < 0: the row is
+ *              ignored altogether.
+ * pred, xprt : host fp64 [ndim][R], ndim 1 or 2;  vals: host fp64 [nvars][R], nvars <= 4 (GPSAT_GLUE_MAXVARS).
+ * sigma, sigma_rows: as gpsat_glue_batch (sigma finite and > 0 unless sigma_rows [R] is given).
+ * max_dist   : finite and > 0: a row takes part only if sum_d (pred_d - xprt_d)^2 < max_dist^2 (strict: a row exactly on
+ *              the limit is out, as is one whose distance is NaN); +inf or <= 0: every row takes part.
+ * Within a key, out = sum w v / sum w over the rows that take part, w = prod_d normpdf(pred_d; xprt_d, sigma).  A NaN value
+ * is left out of the numerator and its weight stays in the denominator (the rule of gpsat_glue_batch).  A key whose rows
+ * all fall outside max_dist has count 0 and NaN outputs.
+ *   G        : host out [1], the number of distinct keys >= 0; written whenever the arguments pass the checks;
+ *   out_key  : host out [capacity], ascending;  out_count: host out [capacity], the rows that took part;
+ *   out      : host out fp64, variable v of record j at out[v * capacity + j].
+ * capacity = R always suffices.  GPSAT_EINVAL (the handle stays usable) for a NULL required pointer, ndim outside {1, 2},
+ * nvars outside 1..4, a sigma that is not finite and positive with sigma_rows == NULL, a NaN max_dist, R > 2^31 - 1, and
+ * capacity < G (G is valid then: call again).  R = 0 returns G = 0.
+ * A group's bits depend on its own rows in their source order only -- not on the other keys of the call, nor on the grid
+ * or the capacity -- and a second call returns the same bytes: the sort is stable, lane l of a team adds the group's rows
+ * l, l + 8, ... in order, a fixed tree joins the 8 lanes, and there are no atomics.  They are not the bits of
+ * gpsat_glue_batch, whose tree is 64 lanes wide.  A group is walked by its one team: a call whose rows all share a few
+ * keys is slow next to gpsat_glue_batch.
+ * The device workspace (about 32 + 8 (2 ndim + nvars + 2) bytes per row) is owned by the handle.  gpsat_last_timing covers
+ * the call: kernel_ms = keys, sort, run heads, reduction; gpsat_glue_keyed_timing splits it: ms[0] sort, ms[1] run heads,
+ * ms[2] reduction, of the last call on the handle.
+ */
+int gpsat_glue_keyed_batch(gpsat_handle *h, int64_t R, int32_t ndim, int32_t nvars, const int64_t *key,
+                           const double *pred, const double *xprt, const double *vals, double sigma,
+                           const double *sigma_rows, double max_dist, int64_t capacity, int64_t *G, int64_t *out_key,
+                           int32_t *out_count, double *out);
+int gpsat_glue_keyed_timing(gpsat_handle *h, double *ms);
+
+/*
  * Binning of raw observations on a regular grid, all groups in one call (added within ABI 4, check for the symbol).
  * Replaces DataPrep.bin_data_by / DataPrep.bin_data (GPSat/dataprepper.py:21-401): per group (day, satellite, ...) a
  * scipy.stats.binned_statistic_2d (1-D: binned_statistic) of `v` over the bins of `ex` x `ey`.  Every statistic of every
