@@ -1,183 +1,51 @@
 """GPU: experts with a trainable constant mean in fp64 (gpsat_fit_predict_batch_mean, GPSAT_MEAN_CONSTANT: H = D + 3 with c
-last) against the fp64 restatement tests/mean_numpy.py.
+last): fixed parameters and the full covariance on the bodies this variant shares with the others (tests/variant_cases.py,
+which states the bounds), GPSAT_MEAN_ZERO, the converged fit and c through the generalised-least-squares identity
+(variant_numpy.gls_sides, to rtol 1e-6), Adam, c fixed or boxed, the refusals, the model and the orchestrator.  The large tile,
+the ragged batch and bit identity are in tests/test_gpu_variants.py.
 
-Bounds are those of tests/test_gpu_rq.py::_check_tile: objective 1e-9 max(1, |nll|) N, gradient rtol 1e-7 with atol
-1e-8 (max|g| + 1), mean 1e-9 max(|y|max, 1), variance 1e-10; the full covariance at the fp64 bound of
-test_full_cov_ragged_batch_matches_oracle; the converged fit at the bounds of test_fp64_learned_hyperparameters_match_scipy,
-and c through the generalised-least-squares identity (mean_numpy.gls_sides) to rtol 1e-6.
+The converged fit is held to the bounds of tests/test_gpu_parity.py::test_fp64_learned_hyperparameters_match_scipy.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pandas as pd
 import pytest
 
-import mean_numpy as mn
+import variant_numpy as vn
 from gpsat_amd import _lib as L
-from gpsat_amd import sharding, synthetic as syn
+from gpsat_amd import synthetic as syn
 from gpsat_amd.engine import GpsatError
+from variant_cases import check_fixed_parameters, check_full_cov, eng, eng8, FIELDS, KERNELS, MEAN as CASE, ragged_inputs, run, same as _same  # noqa: F401 (eng, eng8: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["RBF", "Matern12", "Matern32", "Matern52"]
-FIELDS = ("theta", "nll", "grad", "status", "n_eval", "n_iter", "f_mean", "f_var", "y_var")
-SHIFT = 0.3                                        # the level added to synthetic's de-meaned y
+SHIFT = CASE.SHIFT                                 # the level added to synthetic's de-meaned y
+_run, _batch, _theta = functools.partial(run, CASE), CASE.batch, CASE.theta
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from gpsat_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng8():
-    """One workgroup per CU: the 8-wave build whatever the batch."""
-    from gpsat_amd.engine import Engine
-    e = Engine(0, workgroups_per_cu=1)
-    yield e
-    e.close()
-
-
-def _batch(T, N, P, D, kernel, base_seed):
-    b = syn.make_batch(T, N, P, D, L.KERNEL_IDS[kernel], base_seed=base_seed, dtype=np.float64)
-    b["y"] = b["y"] + SHIFT
-    b["kernel"] = kernel
-    return b
-
-
-def _theta(rng, T, D, c):
-    return np.column_stack([rng.uniform(1.5, 6.0, (T, D)), rng.uniform(0.05, 1.0, T), rng.uniform(0.01, 0.5, T),
-                            np.broadcast_to(c, (T,))])
-
-
-def _check_tile(r, b, t, theta, what=""):
-    D, kernel = b["D"], b["kernel"]
-    a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-    N = int(e - a)
-    X, y, Xs = b["X"][a:e], b["y"][a:e], b["Xs"][pa:pe]
-    if N == 0:                                             # no observations: the prior at theta0, whose mean is c
-        assert r.status[t] == 4 and r.nll[t] == 0.0, what
-        np.testing.assert_array_equal(r.f_mean[pa:pe], theta[D + 2])
-        np.testing.assert_array_equal(r.f_var[pa:pe], theta[D])
-        np.testing.assert_array_equal(r.y_var[pa:pe], theta[D] + theta[D + 1])
-        np.testing.assert_array_equal(r.theta[t], theta)
-        return
-    nll, g = mn.nll_and_grad(kernel, X, y, theta)
-    ymax = np.abs(y).max()
-    assert abs(r.nll[t] - nll) <= 1e-9 * max(1.0, abs(nll)) * max(N, 1), (what, t, N, r.nll[t], nll)
-    np.testing.assert_allclose(r.grad[t], g, rtol=1e-7, atol=1e-8 * (np.abs(g).max() + 1), err_msg=f"{what} tile {t} N {N}")
-    if pe > pa:
-        f, fv, yv = mn.predict(kernel, X, y, Xs, theta)
-        np.testing.assert_allclose(r.f_mean[pa:pe], f, rtol=0, atol=1e-9 * max(ymax, 1.0), err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.f_var[pa:pe], fv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.y_var[pa:pe], yv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-
-
-def _run(e, b, theta0, **kw):
-    kw = {"optimiser": "none", "want_grad": True, "mean": "constant", **kw}
-    return e.fit_predict_batch(D=b["D"], obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"],
-                               theta0=theta0, kernel=b["kernel"], dtype="f64", **kw)
-
-
-# ---- 1. fixed theta against mean_numpy
-SHAPES = [(1, 2, 1), (15, 5, 2), (16, 16, 3), (17, 3, 3), (100, 33, 3), (500, 40, 3)]
-CS = (-0.7, 0.0, 2.5)
-
-
-@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(SHAPES)])
+# ---- 1. fixed theta against variant_numpy, and the full covariance: the shared bodies of tests/variant_cases.py
+@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(CASE.SHAPES)])
 def test_objective_gradient_predict_at_fixed_parameters(eng, i, N, P, D):
     """Three tiles, one per value of c; the kernels take turns over the shapes (each at least once)."""
-    T, kernel = 3, KERNELS[i % 4]
-    b = _batch(T, N, P, D, kernel, 7000 + N)
-    th = _theta(np.random.default_rng(N), T, D, CS)
-    r = _run(eng, b, th)
-    assert r.theta.shape == (T, D + 3) and r.grad.shape == (T, D + 3) and r.f_mean.dtype == np.float64
-    assert (r.status == 5).all() and (r.n_eval == 0).all()
-    np.testing.assert_array_equal(r.theta, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], f"4-wave {kernel} c {CS[t]}")
+    check_fixed_parameters(CASE, eng, KERNELS[i % 4], N, P, D, N, CASE.CS, f"4-wave {KERNELS[i % 4]} c {CASE.CS}")
 
 
-@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(SHAPES)])
+@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(CASE.SHAPES)])
 def test_fixed_parameters_on_the_eight_wave_build(eng8, i, N, P, D):
-    T, kernel = 3, KERNELS[(i + 2) % 4]
-    b = _batch(T, N, P, D, kernel, 7000 + N)
-    th = _theta(np.random.default_rng(N), T, D, CS)
-    r = _run(eng8, b, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], f"8-wave, one workgroup per CU, {kernel} c {CS[t]}")
+    check_fixed_parameters(CASE, eng8, KERNELS[(i + 2) % 4], N, P, D, N, CASE.CS, f"8-wave, one workgroup per CU, {KERNELS[(i + 2) % 4]}",
+                           eight_wave=True)
 
 
-def test_large_tile_takes_the_eight_wave_build(eng):
-    """A tile whose LDS does not fit twice into a CU runs on the 8-wave build (gpsat_plan.h), next to a small one."""
-    b = _batch(2, [1200, 90], [24, 9], 3, "Matern32", 7300)
-    th = _theta(np.random.default_rng(12), 2, 3, (2.5, -0.7))
-    r = _run(eng, b, th)
-    for t in range(2):
-        _check_tile(r, b, t, th[t], "8-wave build by LDS")
-
-
-# ---- 2. a ragged batch
-RAGGED_T = 60
-
-
-@pytest.fixture(scope="module")
-def ragged(eng):
-    """One ragged batch of 60 tiles, N <= 200 (an empty tile, a tile without prediction points): the batch, theta0, the result."""
-    rng = np.random.default_rng(5)
-    Ns = rng.integers(1, 201, size=RAGGED_T)
-    Ps = rng.integers(1, 40, size=RAGGED_T)
-    Ns[3], Ns[17], Ps[5] = 0, 200, 0
-    D = 3
-    b = _batch(RAGGED_T, Ns.tolist(), Ps.tolist(), D, "Matern32", 8000)
-    th = _theta(rng, RAGGED_T, D, rng.choice([-0.7, 0.0, 0.3, 2.5], size=RAGGED_T))
-    th[3, D + 2] = 2.5
-    return b, th, _run(eng, b, th)
-
-
-def test_ragged_batch(ragged):
-    b, th, r = ragged
-    assert r.status[3] == 4 and (r.f_mean[b["pred_off"][3]:b["pred_off"][4]] == 2.5).all() and b["pred_off"][4] > b["pred_off"][3]
-    for t in range(RAGGED_T):
-        _check_tile(r, b, t, th[t], "ragged")
-
-
-# ---- 3. the full covariance
-@pytest.mark.parametrize("D", [1, 2, 3])
+@pytest.mark.parametrize("D", CASE.cov_D)
 def test_full_cov_at_fixed_parameters(eng, D):
-    from oracle import gp_oracle as go
-    Ns, Ps = [40, 0, 100, 33, 257, 64], [5, 3, 0, 32, 70, 1]
-    T, kernel = len(Ns), KERNELS[D]
-    b = _batch(T, Ns, Ps, D, kernel, 321)
-    th0 = np.tile(np.concatenate([np.full(D, 2.0), [0.8, 0.05, -0.7]]), (T, 1))
-    r = _run(eng, b, th0, full_cov=True, want_grad=False)
-    r0 = _run(eng, b, th0, want_grad=False)
-    np.testing.assert_array_equal(r.f_mean, r0.f_mean)
-    np.testing.assert_array_equal(r.f_var, r0.f_var)
-    assert r0.f_cov is None and len(r.f_cov) == sum(p * p for p in Ps)
-    tol = 1e-9
-    for t in range(T):
-        a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-        P = pe - pa
-        if P == 0:
-            continue
-        Cv = np.asarray(r.f_cov[r.cov_off[t]:r.cov_off[t + 1]]).reshape(P, P)
-        Xs = b["Xs"][pa:pe]
-        ref = go.kernel_matrix(L.KERNEL_IDS[kernel], Xs, Xs, th0[t, :D], th0[t, D]) if Ns[t] == 0 else \
-            mn.predict_cov(kernel, b["X"][a:e], b["y"][a:e], Xs, th0[t])
-        np.testing.assert_allclose(Cv, ref, rtol=0, atol=tol * th0[t, D] / 0.8 * 1.0)
-        np.testing.assert_array_equal(Cv, Cv.T)
-        np.testing.assert_allclose(np.diag(Cv), r.f_var[pa:pe], rtol=0, atol=tol)
-        if Ns[t] == 0:
-            np.testing.assert_array_equal(r.f_mean[pa:pe], -0.7)
+    check_full_cov(CASE, eng, D)
 
 
-# ---- 4. GPSAT_MEAN_ZERO is gpsat_fit_predict_batch
-def test_kind_zero_returns_the_bytes_of_the_plain_call(eng, ragged, monkeypatch):
-    b, th, _ = ragged
+# ---- 2. GPSAT_MEAN_ZERO is gpsat_fit_predict_batch
+def test_kind_zero_returns_the_bytes_of_the_plain_call(eng, monkeypatch):
+    b, th = ragged_inputs(CASE)
     th2 = th[:, :b["D"] + 2].copy()
     kw = dict(D=b["D"], obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"], theta0=th2,
               kernel=b["kernel"], dtype="f64", optimiser="lbfgs", max_iter=5, want_grad=True)
@@ -204,7 +72,7 @@ def test_kind_zero_returns_the_bytes_of_the_plain_call(eng, ragged, monkeypatch)
         assert np.asarray(getattr(routed, name)).tobytes() == np.asarray(getattr(plain, name)).tobytes(), name
 
 
-# ---- 5. a converged fit
+# ---- 3. a converged fit
 FIT_SEEDS = (900, 902, 905)          # SciPy reports success on each (checked on the CPU)
 
 
@@ -219,7 +87,7 @@ def fit_case(eng):
     lo, hi = np.column_stack([lo2, np.full(T, np.nan)]), np.column_stack([hi2, np.full(T, np.nan)])
     th0 = np.ones((T, D + 3))
     th0[:, D + 2] = 0.0
-    ref = [mn.fit(kernel, b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)], th0[t], lo[t], hi[t], max_iter=1000)
+    ref = [vn.fit(vn.MEAN, kernel, b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)], th0[t], lo[t], hi[t], max_iter=1000)
            for t in range(T)]
     return b, th0, lo, hi, ref
 
@@ -238,11 +106,11 @@ def test_learned_hyperparameters_match_scipy(eng, fit_case):
     for t in range(T):
         X, y = b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)]
         # c: the returned c, the returned dnll/dc and a numpy K_y at the returned theta satisfy the GLS identity
-        left, right = mn.gls_sides(kernel, X, y, r.theta[t], r.grad[t, D + 2])
+        left, right = vn.gls_sides(kernel, X, y, r.theta[t], r.grad[t, D + 2])
         print("tile", t, "c", r.theta[t, D + 2], "scipy c", o_theta[t, D + 2], "GLS sides", left, right)
         np.testing.assert_allclose(left, right, rtol=1e-6)
         # the returned objective is the objective at the returned parameters
-        assert abs(mn.nll_and_grad(kernel, X, y, r.theta[t], False)[0] - r.nll[t]) <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
+        assert abs(vn.nll_and_grad(vn.MEAN, kernel, X, y, r.theta[t], want_grad=False)[0] - r.nll[t]) <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
         # c is really trained: away from its start, and not the sample mean
         assert abs(r.theta[t, D + 2] - SHIFT) > 1e-3 and abs(r.theta[t, D + 2] - y.mean()) > 1e-3
 
@@ -257,7 +125,7 @@ def test_adam_trains_the_constant_through_the_identity_transform(eng, fit_case):
     assert (r.theta[:, D + 2] > 0.05).all() and (r.theta[:, D + 2] < 1.6).all()           # at most 30 steps of 0.05 from 0
 
 
-# ---- 6. c fixed, and c in a box
+# ---- 4. c fixed, and c in a box
 def test_constant_fixed_and_constant_in_a_box(eng, fit_case):
     b, th0, lo, hi, ref = fit_case
     D, T = b["D"], len(FIT_SEEDS)
@@ -270,7 +138,7 @@ def test_constant_fixed_and_constant_in_a_box(eng, fit_case):
     assert (r.status == 0).all() and (r.theta[:, :D + 2] != 1.0).all()
     for t in range(T):                                     # the others are fitted: the zero-mean fit of y - c
         X, y = b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)]
-        th, f, res = mn.fit(b["kernel"], X, y, th1[t], lo[t], hi[t], trainable=tr, max_iter=1000)
+        th, f, res = vn.fit(vn.MEAN, b["kernel"], X, y, th1[t], lo[t], hi[t], trainable=tr, max_iter=1000)
         print("fixed c", th1[t, D + 2], "device", r.theta[t], r.nll[t], "scipy", th, f)
         assert res.success and abs(r.nll[t] - f) <= 5e-5
     # a box that excludes the unconstrained optimum (about 0.3): c stays inside and goes to its upper end
@@ -289,57 +157,7 @@ def test_constant_fixed_and_constant_in_a_box(eng, fit_case):
     np.testing.assert_allclose(rc.nll, [f for _, f, _ in ref], rtol=0, atol=5e-5)
 
 
-# ---- 7. the same bits alone, inside the batch, on a second call and with the time-sliced queue
-def _same(a, e, what):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(e, name)
-        assert np.asarray(x).tobytes() == np.asarray(y).tobytes(), (what, name)
-
-
-def _one(b, t):
-    s = sharding.pack_subset(b, np.array([t]))
-    return dict(D=b["D"], kernel=b["kernel"], obs_off=s["obs_off"], pred_off=s["pred_off"], X=s["X"], y=s["y"], Xs=s["Xs"])
-
-
-def test_same_bits_alone_in_the_batch_and_again(eng, ragged):
-    b, th, r = ragged
-    _same(_run(eng, b, th), r, "second call")
-    for t in (17, 40):
-        r1 = _run(eng, _one(b, t), th[[t]])
-        pa, pe = b["pred_off"][t], b["pred_off"][t + 1]
-        for name in FIELDS:
-            whole = getattr(r, name)
-            part = whole[pa:pe] if name in ("f_mean", "f_var", "y_var") else whole[[t]]
-            assert np.asarray(getattr(r1, name)).tobytes() == np.asarray(part).tobytes(), (t, name)
-
-
-def test_time_sliced_optimisation_is_bit_identical(eng, ragged, monkeypatch):
-    """As tests/test_gpu_rq.py::test_time_sliced_optimisation_is_bit_identical forces the queue: suspended after every
-    evaluation, after every third of a 200-point tile, or never.  A resumed tile forms its residual from the restored c:
-    one formed from the c of the tile the workgroup ran in between would change the bits."""
-    b, th, _ = ragged
-    T, D = RAGGED_T, b["D"]
-    lo2, hi2 = syn.default_bounds(T, D)
-    lo, hi = np.column_stack([lo2, np.full(T, np.nan)]), np.column_stack([hi2, np.full(T, np.nan)])
-    th0 = np.ones((T, D + 3))
-    th0[:, D + 2] = th[:, D + 2]                           # a different start of c in every tile
-    kw = dict(lo=lo, hi=hi, optimiser="lbfgs", max_iter=12)
-    monkeypatch.setenv("GPSAT_DEVELOPER", "1")
-    monkeypatch.setenv("GPSAT_DEBUG_SEG", "0")
-    r0 = _run(eng, b, th0, **kw)
-    moved = r0.status <= 1
-    assert r0.n_eval.max() > 6 and moved.sum() > 40 and (r0.theta[moved, D + 2] != th0[moved, D + 2]).all()      # c moved
-    for seg in ("1", str(3 * 14 ** 3)):
-        monkeypatch.setenv("GPSAT_DEBUG_SEG", seg)
-        _same(_run(eng, b, th0, **kw), r0, f"slice {seg}")
-    monkeypatch.delenv("GPSAT_DEBUG_SEG")
-    t = 17
-    r1 = _run(eng, _one(b, t), th0[[t]], lo=lo[[t]], hi=hi[[t]], optimiser="lbfgs", max_iter=12)
-    assert r1.theta.tobytes() == r0.theta[[t]].tobytes() and r1.nll.tobytes() == r0.nll[[t]].tobytes()
-    assert r1.f_mean.tobytes() == r0.f_mean[b["pred_off"][t]:b["pred_off"][t + 1]].tobytes()
-
-
-# ---- 8. what the C ABI refuses, and that the handle works afterwards
+# ---- 5. what the C ABI refuses, and that the handle works afterwards
 def test_refusals_leave_the_handle_usable(eng):
     b = _batch(2, 40, 5, 3, "Matern32", 1)
     th = _theta(np.random.default_rng(0), 2, 3, (0.3, -0.7))
@@ -389,7 +207,7 @@ def test_refusals_leave_the_handle_usable(eng):
     assert lib.gpsat_n_hyper_mean(2, 3, L.MEAN_CONSTANT) == 6 and lib.gpsat_n_hyper_mean(L.KERNEL_RQ, 3, L.MEAN_CONSTANT) == 0
 
 
-# ---- 9. the model and the orchestrator end to end
+# ---- 6. the model and the orchestrator end to end
 def test_model_agrees_with_the_engine_call(eng):
     from gpsat_amd.models import HipGPRModel
     X, y, Xs, _ = syn.make_tile(900, 150, 16, 3, kid=2)

@@ -1,211 +1,52 @@
-"""GPU: known noise variances per observation in fp64 (gpsat_fit_predict_batch_noise: K_y = K + sn2 I + diag(v)) against the
-fp64 restatement tests/noise_numpy.py.
+"""GPU: known noise variances per observation in fp64 (gpsat_fit_predict_batch_noise: K_y = K + sn2 I + diag(v)): fixed
+parameters and the full covariance on the bodies this variant shares with the others (tests/variant_cases.py, which states the
+bounds), zero and NULL obs_var, a constant and a huge variance, the converged fit, Adam, scikit-learn's fixture, the refusals,
+device tensors and the orchestrator.  The large tile, the ragged batch and bit identity are in tests/test_gpu_variants.py.
 
-Bounds are those of tests/test_gpu_mean.py::_check_tile: objective 1e-9 max(1, |nll|) N, gradient rtol 1e-7 with atol
-1e-8 (max|g| + 1), mean 1e-9 max(|y|max, 1), variance 1e-10; the full covariance at 1e-9; the converged fit at nll 5e-5 and
-theta rtol 2e-3 (tests/test_noise_cpu.py shows SciPy reproducing itself to a tenth of that on the same inputs); the
-scikit-learn fixture at the reference's 1e-6.
+The converged fit is held to nll 5e-5 and theta rtol 2e-3 (tests/test_noise_cpu.py shows SciPy reproducing itself to a
+tenth of that on the same inputs); the scikit-learn fixture to the reference's 1e-6.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pandas as pd
 import pytest
 
-import noise_numpy as nn
+import variant_numpy as vn
 from gpsat_amd import _lib as L
-from gpsat_amd import sharding, synthetic as syn
+from gpsat_amd import synthetic as syn
 from gpsat_amd.engine import GpsatError
+from variant_cases import check_fixed_parameters, check_full_cov, eng, eng8, FIELDS, KERNELS, NOISE as CASE, ragged_inputs, run, same as _same  # noqa: F401 (eng, eng8: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ["RBF", "Matern12", "Matern32", "Matern52"]
-FIELDS = ("theta", "nll", "grad", "status", "n_eval", "n_iter", "f_mean", "f_var", "y_var")
+_run, _batch, _theta = functools.partial(run, CASE), CASE.batch, CASE.theta
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from gpsat_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng8():
-    """One workgroup per CU: the 8-wave build whatever the batch."""
-    from gpsat_amd.engine import Engine
-    e = Engine(0, workgroups_per_cu=1)
-    yield e
-    e.close()
-
-
-def _batch(T, N, P, D, kernel, base_seed, vmax=0.3):
-    """synthetic's batch with v ~ U(0, vmax) per row, about one row in five exactly 0."""
-    b = syn.make_batch(T, N, P, D, L.KERNEL_IDS[kernel], base_seed=base_seed, dtype=np.float64)
-    rng = np.random.default_rng(base_seed + 1)
-    v = rng.uniform(0.0, vmax, int(b["obs_off"][-1]))
-    v[rng.uniform(size=len(v)) < 0.2] = 0.0
-    b["obs_var"], b["kernel"] = v, kernel
-    return b
-
-
-def _theta(rng, T, D):
-    return np.column_stack([rng.uniform(1.5, 6.0, (T, D)), rng.uniform(0.05, 1.0, T), rng.uniform(0.01, 0.5, T)])
-
-
-def _check_tile(r, b, t, theta, what=""):
-    D, kernel = b["D"], b["kernel"]
-    a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-    N = int(e - a)
-    X, y, v, Xs = b["X"][a:e], b["y"][a:e], b["obs_var"][a:e], b["Xs"][pa:pe]
-    if N == 0:                                             # no observations: the prior at theta0
-        assert r.status[t] == 4 and r.nll[t] == 0.0, what
-        np.testing.assert_array_equal(r.f_mean[pa:pe], 0.0)
-        np.testing.assert_array_equal(r.f_var[pa:pe], theta[D])
-        np.testing.assert_array_equal(r.y_var[pa:pe], theta[D] + theta[D + 1])
-        np.testing.assert_array_equal(r.theta[t], theta)
-        return
-    nll, g = nn.nll_and_grad(kernel, X, y, v, theta)
-    ymax = np.abs(y).max()
-    assert abs(r.nll[t] - nll) <= 1e-9 * max(1.0, abs(nll)) * max(N, 1), (what, t, N, r.nll[t], nll)
-    np.testing.assert_allclose(r.grad[t], g, rtol=1e-7, atol=1e-8 * (np.abs(g).max() + 1), err_msg=f"{what} tile {t} N {N}")
-    if pe > pa:
-        f, fv, yv = nn.predict(kernel, X, y, v, Xs, theta)
-        np.testing.assert_allclose(r.f_mean[pa:pe], f, rtol=0, atol=1e-9 * max(ymax, 1.0), err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.f_var[pa:pe], fv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.y_var[pa:pe], yv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-
-
-def _run(e, b, theta0, **kw):
-    kw = {"optimiser": "none", "want_grad": True, "obs_var": b.get("obs_var"), **kw}
-    return e.fit_predict_batch(D=b["D"], obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"],
-                               theta0=theta0, kernel=b["kernel"], dtype="f64", **kw)
-
-
-def _same(a, e, what, fields=FIELDS):
-    for name in fields:
-        assert np.asarray(getattr(a, name)).tobytes() == np.asarray(getattr(e, name)).tobytes(), (what, name)
-
-
-# ---- 1. fixed theta against noise_numpy
-SHAPES = [(1, 2, 1), (15, 5, 2), (16, 16, 3), (17, 3, 4), (100, 33, 3), (500, 40, 4)]
-
-
-@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(SHAPES)])
+# ---- 1. fixed theta against variant_numpy, and the full covariance: the shared bodies of tests/variant_cases.py
+@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(CASE.SHAPES)])
 def test_objective_gradient_predict_at_fixed_parameters(eng, i, N, P, D):
     """Three tiles; the kernels take turns over the shapes (each at least once)."""
-    T, kernel = 3, KERNELS[i % 4]
-    b = _batch(T, N, P, D, kernel, 7000 + N)
-    th = _theta(np.random.default_rng(N), T, D)
-    r = _run(eng, b, th)
-    assert r.theta.shape == (T, D + 2) and r.grad.shape == (T, D + 2) and r.f_mean.dtype == np.float64
-    assert (r.status == 5).all() and (r.n_eval == 0).all()
-    np.testing.assert_array_equal(r.theta, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], f"4-wave {kernel}")
-    # and v is really read: the plain call answers something else
-    r0 = _run(eng, b, th, obs_var=None)
-    has_v = np.array([b["obs_var"][b["obs_off"][t]:b["obs_off"][t + 1]].any() for t in range(T)])
-    assert has_v.any() and (r0.nll[has_v] != r.nll[has_v]).all() and (r0.nll[~has_v] == r.nll[~has_v]).all()
+    check_fixed_parameters(CASE, eng, KERNELS[i % 4], N, P, D, N, None, f"4-wave {KERNELS[i % 4]}")
 
 
-@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(SHAPES)])
+@pytest.mark.parametrize("i,N,P,D", [(i, *s) for i, s in enumerate(CASE.SHAPES)])
 def test_fixed_parameters_on_the_eight_wave_build(eng8, i, N, P, D):
-    T, kernel = 3, KERNELS[(i + 2) % 4]
-    b = _batch(T, N, P, D, kernel, 7000 + N)
-    th = _theta(np.random.default_rng(N), T, D)
-    r = _run(eng8, b, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], f"8-wave, one workgroup per CU, {kernel}")
+    check_fixed_parameters(CASE, eng8, KERNELS[(i + 2) % 4], N, P, D, N, None, f"8-wave, one workgroup per CU, {KERNELS[(i + 2) % 4]}",
+                           eight_wave=True)
 
 
-def test_large_tile_takes_the_eight_wave_build(eng):
-    """A tile whose LDS does not fit twice into a CU runs on the 8-wave build (gpsat_plan.h), next to a small one."""
-    b = _batch(2, [1200, 90], [24, 9], 3, "Matern32", 7300)
-    th = _theta(np.random.default_rng(12), 2, 3)
-    r = _run(eng, b, th)
-    for t in range(2):
-        _check_tile(r, b, t, th[t], "8-wave build by LDS")
+@pytest.mark.parametrize("D", CASE.cov_D)
+def test_full_cov_at_fixed_parameters(eng, D):
+    check_full_cov(CASE, eng, D)
 
 
-# ---- 2. a ragged, unsorted batch
-RAGGED_T = 60
-
-
-@pytest.fixture(scope="module")
-def ragged(eng):
-    """One ragged batch of 60 tiles in no order of size, N <= 200, a different v in every tile (an empty tile, a tile without
-    prediction points): the batch, theta0, the result."""
-    rng = np.random.default_rng(5)
-    Ns = rng.integers(1, 201, size=RAGGED_T)
-    Ps = rng.integers(1, 40, size=RAGGED_T)
-    Ns[3], Ns[17], Ps[5] = 0, 200, 0
-    D = 3
-    b = _batch(RAGGED_T, Ns.tolist(), Ps.tolist(), D, "Matern32", 8000)
-    b["obs_var"] = b["obs_var"] * np.repeat(rng.uniform(0.01, 3.0, RAGGED_T), Ns)      # a scale of its own per tile
-    th = _theta(rng, RAGGED_T, D)
-    return b, th, _run(eng, b, th)
-
-
-def test_ragged_batch(ragged):
-    b, th, r = ragged
-    assert r.status[3] == 4 and b["pred_off"][4] > b["pred_off"][3]
-    for t in range(RAGGED_T):
-        _check_tile(r, b, t, th[t], "ragged")
-
-
-def _one(b, t):
-    s = sharding.pack_subset(b, np.array([t]))
-    a, e = b["obs_off"][t], b["obs_off"][t + 1]
-    return dict(D=b["D"], kernel=b["kernel"], obs_off=s["obs_off"], pred_off=s["pred_off"], X=s["X"], y=s["y"], Xs=s["Xs"],
-                obs_var=b["obs_var"][a:e].copy())
-
-
-def test_same_bits_alone_in_the_batch_and_again(eng, ragged):
-    b, th, r = ragged
-    _same(_run(eng, b, th), r, "second call")
-    for t in (17, 40):
-        r1 = _run(eng, _one(b, t), th[[t]])
-        pa, pe = b["pred_off"][t], b["pred_off"][t + 1]
-        for name in FIELDS:
-            whole = getattr(r, name)
-            part = whole[pa:pe] if name in ("f_mean", "f_var", "y_var") else whole[[t]]
-            assert np.asarray(getattr(r1, name)).tobytes() == np.asarray(part).tobytes(), (t, name)
-
-
-def test_time_sliced_optimisation_is_bit_identical(eng, ragged, monkeypatch):
-    """As tests/test_gpu_mean.py forces the queue: suspended after every evaluation, after every third of a 200-point tile,
-    or never.  A resumed tile reads its own v again, on whatever workgroup: the v of the tile that workgroup ran in between
-    would change the bits."""
-    b, th, _ = ragged
-    T, D = RAGGED_T, b["D"]
-    lo, hi = syn.default_bounds(T, D)
-    th0 = np.ones((T, D + 2))
-    kw = dict(lo=lo, hi=hi, optimiser="lbfgs", max_iter=12)
-    monkeypatch.setenv("GPSAT_DEVELOPER", "1")
-    monkeypatch.setenv("GPSAT_DEBUG_SEG", "0")
-    r0 = _run(eng, b, th0, **kw)
-    assert r0.n_eval.max() > 6 and (r0.status <= 1).sum() > 40
-    for seg in ("1", str(3 * 14 ** 3)):
-        monkeypatch.setenv("GPSAT_DEBUG_SEG", seg)
-        _same(_run(eng, b, th0, **kw), r0, f"slice {seg}")
-    monkeypatch.delenv("GPSAT_DEBUG_SEG")
-    t = 17
-    r1 = _run(eng, _one(b, t), th0[[t]], lo=lo[[t]], hi=hi[[t]], optimiser="lbfgs", max_iter=12)
-    assert r1.theta.tobytes() == r0.theta[[t]].tobytes() and r1.nll.tobytes() == r0.nll[[t]].tobytes()
-    assert r1.f_mean.tobytes() == r0.f_mean[b["pred_off"][t]:b["pred_off"][t + 1]].tobytes()
-    # the fit is the noise model's: not the plain call's
-    rp = _run(eng, b, th0, obs_var=None, **kw)
-    big = (r0.status <= 1) & (np.diff(b["obs_off"]) >= 20)
-    assert big.sum() > 30 and (rp.theta[big] != r0.theta[big]).any(axis=1).all()
-
-
-# ---- 3. v = 0 and a NULL obs_var are gpsat_fit_predict_batch
+# ---- 2. v = 0 and a NULL obs_var are gpsat_fit_predict_batch
 @pytest.mark.parametrize("optimiser,max_iter", [("lbfgs", 5), ("none", 0)])
-def test_zero_variances_and_null_return_the_bytes_of_the_plain_call(eng, ragged, monkeypatch, optimiser, max_iter):
-    b, th, _ = ragged
+def test_zero_variances_and_null_return_the_bytes_of_the_plain_call(eng, monkeypatch, optimiser, max_iter):
+    b, th = ragged_inputs(CASE)
     kw = dict(D=b["D"], obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"], theta0=th,
               kernel=b["kernel"], dtype="f64", optimiser=optimiser, max_iter=max_iter, want_grad=True)
     plain = eng.fit_predict_batch(**kw)
@@ -234,7 +75,7 @@ def test_zero_variances_and_null_return_the_bytes_of_the_plain_call(eng, ragged,
     _same(routed, plain, "NULL obs_var")
 
 
-# ---- 4. a constant v is a larger likelihood variance
+# ---- 3. a constant v is a larger likelihood variance
 def test_constant_variance_is_the_plain_call_at_a_larger_likelihood_variance(eng):
     """v = 0.2 everywhere at a given sn2: objective, gradient and predictions of the plain call at sn2 + 0.2, at the bounds
     (not bitwise: (k + sn2) + 0.2 and k + (sn2 + 0.2) round differently)."""
@@ -254,7 +95,7 @@ def test_constant_variance_is_the_plain_call_at_a_larger_likelihood_variance(eng
     np.testing.assert_allclose(r.y_var, r0.y_var - 0.2, rtol=0, atol=1e-10)       # a new point carries sn2 only
 
 
-# ---- 5. each row meets its own variance
+# ---- 4. each row meets its own variance
 @pytest.mark.parametrize("N,D", [(17, 1), (100, 3), (500, 4)])
 def test_a_huge_variance_deletes_the_row(eng, N, D):
     """v = 1e12 on every fifth row: f* and f*_var of the tile with these rows deleted, to 1e-9 and 1e-10 (on the CPU the two
@@ -271,45 +112,17 @@ def test_a_huge_variance_deletes_the_row(eng, N, D):
     np.testing.assert_allclose(r.f_mean, r0.f_mean, rtol=0, atol=1e-9)
     np.testing.assert_allclose(r.f_var, r0.f_var, rtol=0, atol=1e-10)
     # and against the restatement of the reduced tile
-    f, fv, _ = nn.predict("Matern32", X[keep], y[keep], np.zeros(int(keep.sum())), Xs, theta)
+    f, fv, _ = vn.predict(vn.NOISE, "Matern32", X[keep], y[keep], Xs, theta, np.zeros(int(keep.sum())))
     np.testing.assert_allclose(r.f_mean, f, rtol=0, atol=1e-9)
     np.testing.assert_allclose(r.f_var, fv, rtol=0, atol=1e-10)
 
 
-# ---- 6. the full covariance
-@pytest.mark.parametrize("D", [1, 2, 3])
-def test_full_cov_at_fixed_parameters(eng, D):
-    from oracle import gp_oracle as go
-    Ns, Ps = [40, 0, 100, 33, 257, 64], [5, 3, 0, 32, 70, 1]
-    T, kernel = len(Ns), KERNELS[D]
-    b = _batch(T, Ns, Ps, D, kernel, 321)
-    th0 = np.tile(np.concatenate([np.full(D, 2.0), [0.8, 0.05]]), (T, 1))
-    r = _run(eng, b, th0, full_cov=True, want_grad=False)
-    r0 = _run(eng, b, th0, want_grad=False)
-    np.testing.assert_array_equal(r.f_mean, r0.f_mean)
-    np.testing.assert_array_equal(r.f_var, r0.f_var)
-    assert r0.f_cov is None and len(r.f_cov) == sum(p * p for p in Ps)
-    tol = 1e-9
-    for t in range(T):
-        a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-        P = pe - pa
-        if P == 0:
-            continue
-        Cv = np.asarray(r.f_cov[r.cov_off[t]:r.cov_off[t + 1]]).reshape(P, P)
-        Xs = b["Xs"][pa:pe]
-        ref = go.kernel_matrix(L.KERNEL_IDS[kernel], Xs, Xs, th0[t, :D], th0[t, D]) if Ns[t] == 0 else \
-            nn.predict_cov(kernel, b["X"][a:e], b["y"][a:e], b["obs_var"][a:e], Xs, th0[t])
-        np.testing.assert_allclose(Cv, ref, rtol=0, atol=tol)
-        np.testing.assert_array_equal(Cv, Cv.T)
-        np.testing.assert_allclose(np.diag(Cv), r.f_var[pa:pe], rtol=0, atol=tol)
-
-
-# ---- 7. a converged fit
+# ---- 5. a converged fit
 @pytest.fixture(scope="module")
 def fit_case():
-    b, th0, lo, hi = nn.fit_case()
-    ref = [nn.fit("Matern32", b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)], b["obs_var"][150 * t:150 * (t + 1)],
-                  th0[t], lo[t], hi[t], max_iter=1000) for t in range(3)]
+    b, th0, lo, hi = vn.fit_case()
+    ref = [vn.fit(vn.NOISE, "Matern32", b["X"][150 * t:150 * (t + 1)], b["y"][150 * t:150 * (t + 1)], th0[t], lo[t], hi[t], max_iter=1000,
+                  obs_var=b["obs_var"][150 * t:150 * (t + 1)]) for t in range(3)]
     return b, th0, lo, hi, ref
 
 
@@ -327,7 +140,7 @@ def test_learned_hyperparameters_match_scipy(eng, fit_case):
     for t in range(T):
         sl = slice(150 * t, 150 * (t + 1))
         # the returned objective is the objective at the returned parameters
-        assert abs(nn.nll_and_grad("Matern32", b["X"][sl], b["y"][sl], b["obs_var"][sl], r.theta[t], False)[0] - r.nll[t]) \
+        assert abs(vn.nll_and_grad(vn.NOISE, "Matern32", b["X"][sl], b["y"][sl], r.theta[t], b["obs_var"][sl], want_grad=False)[0] - r.nll[t]) \
             <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
     # v is part of the fit: without it the likelihood variance comes out larger
     rp = _run(eng, b, th0, lo=lo, hi=hi, optimiser="lbfgs", max_iter=1000, obs_var=None)
@@ -342,11 +155,11 @@ def test_adam(eng, fit_case):
     assert (r.status == 1).all() and (r.nll < r0.nll).all()
     for t in range(3):
         sl = slice(150 * t, 150 * (t + 1))
-        assert abs(nn.nll_and_grad("Matern32", b["X"][sl], b["y"][sl], b["obs_var"][sl], r.theta[t], False)[0] - r.nll[t]) \
+        assert abs(vn.nll_and_grad(vn.NOISE, "Matern32", b["X"][sl], b["y"][sl], r.theta[t], b["obs_var"][sl], want_grad=False)[0] - r.nll[t]) \
             <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
 
 
-# ---- 8. the scikit-learn fixture through the model
+# ---- 6. the scikit-learn fixture through the model
 def _fixture_model(eng, golden_dir):
     from gpsat_amd.models import HipGPRModel
     g = np.load(os.path.join(golden_dir, "kat_sklearn_noise.npz"))
@@ -379,7 +192,7 @@ def test_sklearn_fixture_optimised_on_the_device(eng, golden_dir):
     assert abs(lml - float(g["ml"])) < 1e-6
 
 
-# ---- 9. what the C ABI refuses, and that the handle works afterwards
+# ---- 7. what the C ABI refuses, and that the handle works afterwards
 def test_refusals_leave_the_handle_usable(eng):
     b = _batch(2, 40, 5, 3, "Matern32", 1)
     th = _theta(np.random.default_rng(0), 2, 3)
@@ -447,7 +260,7 @@ def test_device_tensors(eng):
     assert r.f_mean.cpu().numpy().tobytes() == host.f_mean.tobytes() and r.f_var.cpu().numpy().tobytes() == host.f_var.tobytes()
 
 
-# ---- 10. the model and the orchestrator end to end
+# ---- 8. the model and the orchestrator end to end
 def test_orchestrator_tables_equal_the_per_tile_model(eng):
     """Six experts in waves of four, sharing rows: the tables are those of HipGPRModel(obs_var_col=...) run tile by tile."""
     from gpsat_amd.local_experts import BatchedLocalExpertOI

@@ -1,165 +1,48 @@
-"""GPU: RationalQuadratic experts in fp64 (GPSAT_KERNEL_RQ, H = D + 3 with alpha last) against the fp64 restatement
-tests/rq_numpy.py and scikit-learn's fixture.
+"""GPU: RationalQuadratic experts in fp64 (GPSAT_KERNEL_RQ, H = D + 3 with alpha last): fixed parameters and the full covariance
+on the bodies this variant shares with the others (tests/variant_cases.py, which states the bounds), scikit-learn's fixture, the
+converged fit, the refusals and the orchestrator.  The large tile, the ragged batch and bit identity are in
+tests/test_gpu_variants.py.
 
-Bounds are those of tests/test_gpu_parity.py::test_fp64_objective_gradient_predict: objective 1e-9 max(1, |nll|) N, gradient
-rtol 1e-7 with atol 1e-8 (max|g| + 1), mean 1e-9 max(|y|max, 1), variance 1e-10; the full covariance at the fp64 bound of
-test_full_cov_ragged_batch_matches_oracle; the converged fit at the bounds of test_fp64_learned_hyperparameters_match_scipy.
+The converged fit is held to the bounds of tests/test_gpu_parity.py::test_fp64_learned_hyperparameters_match_scipy.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pandas as pd
 import pytest
 
-import rq_numpy as rq
+import variant_numpy as vn
 from gpsat_amd import _lib as L
-from gpsat_amd import sharding, synthetic as syn
+from gpsat_amd import synthetic as syn
 from gpsat_amd.engine import GpsatError
+from variant_cases import check_fixed_parameters, check_full_cov, eng, eng8, RQ as CASE, run, same as _same  # noqa: F401 (eng, eng8: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
-KERNEL = "RationalQuadratic"
-FIELDS = ("theta", "nll", "grad", "status", "n_eval", "n_iter", "f_mean", "f_var", "y_var")
+KERNEL = vn.RQ_KERNEL
+_run = functools.partial(run, CASE)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from gpsat_amd.engine import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng8():
-    """One workgroup per CU: the 8-wave build whatever the batch."""
-    from gpsat_amd.engine import Engine
-    e = Engine(0, workgroups_per_cu=1)
-    yield e
-    e.close()
-
-
-def _theta(rng, T, D, alpha):
-    return np.column_stack([rng.uniform(1.5, 6.0, (T, D)), rng.uniform(0.05, 1.0, T), rng.uniform(0.01, 0.5, T), np.full(T, alpha)])
-
-
-def _check_tile(r, b, t, theta, what=""):
-    D = b["D"]
-    a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-    N = int(e - a)
-    X, y, Xs = b["X"][a:e], b["y"][a:e], b["Xs"][pa:pe]
-    if N == 0:                                             # no observations: the prior at theta0
-        assert r.status[t] == 4 and r.nll[t] == 0.0, what
-        np.testing.assert_array_equal(r.f_mean[pa:pe], 0.0)
-        np.testing.assert_array_equal(r.f_var[pa:pe], theta[D])
-        np.testing.assert_array_equal(r.y_var[pa:pe], theta[D] + theta[D + 1])
-        return
-    nll, g = rq.nll_and_grad(X, y, theta)
-    ymax = np.abs(y).max()
-    assert abs(r.nll[t] - nll) <= 1e-9 * max(1.0, abs(nll)) * max(N, 1), (what, t, N, r.nll[t], nll)
-    np.testing.assert_allclose(r.grad[t], g, rtol=1e-7, atol=1e-8 * (np.abs(g).max() + 1), err_msg=f"{what} tile {t} N {N}")
-    if pe > pa:
-        f, fv, yv = rq.predict(X, y, Xs, theta)
-        np.testing.assert_allclose(r.f_mean[pa:pe], f, rtol=0, atol=1e-9 * max(ymax, 1.0), err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.f_var[pa:pe], fv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-        np.testing.assert_allclose(r.y_var[pa:pe], yv, rtol=0, atol=1e-10, err_msg=f"{what} tile {t}")
-
-
-def _run(e, b, theta0, **kw):
-    kw = {"optimiser": "none", "want_grad": True, **kw}
-    return e.fit_predict_batch(D=b["D"], obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"],
-                               theta0=theta0, kernel=KERNEL, dtype="f64", **kw)
-
-
-# ---- 1. fixed theta against rq_numpy
-SHAPES = [(1, 2, 1), (15, 5, 2), (16, 16, 3), (17, 3, 3), (100, 33, 3), (500, 40, 3)]
-
-
-@pytest.mark.parametrize("alpha", [0.3, 1.0, 30.0])
-@pytest.mark.parametrize("N,P,D", SHAPES)
+# ---- 1. fixed theta against variant_numpy, and the full covariance: the shared bodies of tests/variant_cases.py
+@pytest.mark.parametrize("alpha", CASE.ALPHAS)
+@pytest.mark.parametrize("N,P,D", CASE.SHAPES)
 def test_objective_gradient_predict_at_fixed_parameters(eng, N, P, D, alpha):
-    T = 2
-    b = syn.make_batch(T, N, P, D, 0, base_seed=7000 + N, dtype=np.float64)
-    th = _theta(np.random.default_rng(N + int(10 * alpha)), T, D, alpha)
-    r = _run(eng, b, th)
-    assert r.theta.shape == (T, D + 3) and r.grad.shape == (T, D + 3) and r.f_mean.dtype == np.float64
-    assert (r.status == 5).all() and (r.n_eval == 0).all()
-    np.testing.assert_array_equal(r.theta, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], f"4-wave alpha {alpha}")
+    check_fixed_parameters(CASE, eng, KERNEL, N, P, D, N + int(10 * alpha), alpha, f"4-wave alpha {alpha}")
 
 
-@pytest.mark.parametrize("N,P,D", SHAPES)
+@pytest.mark.parametrize("N,P,D", CASE.SHAPES)
 def test_fixed_parameters_on_the_eight_wave_build(eng8, N, P, D):
-    T, alpha = 2, 1.0
-    b = syn.make_batch(T, N, P, D, 0, base_seed=7000 + N, dtype=np.float64)
-    th = _theta(np.random.default_rng(N + 10), T, D, alpha)
-    r = _run(eng8, b, th)
-    for t in range(T):
-        _check_tile(r, b, t, th[t], "8-wave, one workgroup per CU")
+    check_fixed_parameters(CASE, eng8, KERNEL, N, P, D, N + 10, 1.0, "8-wave, one workgroup per CU", eight_wave=True)
 
 
-def test_large_tile_takes_the_eight_wave_build(eng):
-    """A tile whose LDS does not fit twice into a CU runs on the 8-wave build (gpsat_plan.h), next to a small one."""
-    b = syn.make_batch(2, [1200, 90], [24, 9], 3, 0, base_seed=7300, dtype=np.float64)
-    th = _theta(np.random.default_rng(12), 2, 3, 2.0)
-    r = _run(eng, b, th)
-    for t in range(2):
-        _check_tile(r, b, t, th[t], "8-wave build by LDS")
-
-
-RAGGED_T = 300
-
-
-@pytest.fixture(scope="module")
-def ragged(eng):
-    """One ragged batch of 300 tiles, N <= 200 (an empty tile, tiles without prediction points): the batch, theta0, the result."""
-    rng = np.random.default_rng(5)
-    Ns = rng.integers(1, 201, size=RAGGED_T)
-    Ps = rng.integers(0, 40, size=RAGGED_T)
-    Ns[3], Ns[17], Ps[5] = 0, 200, 0
-    D = 3
-    b = syn.make_batch(RAGGED_T, Ns.tolist(), Ps.tolist(), D, 0, base_seed=8000, dtype=np.float64)
-    th = _theta(rng, RAGGED_T, D, 1.0)
-    th[:, D + 2] = rng.choice([0.3, 1.0, 4.0, 30.0], size=RAGGED_T)
-    return b, th, _run(eng, b, th)
-
-
-def test_ragged_batch_of_300_tiles(ragged):
-    b, th, r = ragged
-    for t in range(RAGGED_T):
-        _check_tile(r, b, t, th[t], "ragged")
-
-
-# ---- 2. the full covariance
-@pytest.mark.parametrize("D", [3, 1])
+@pytest.mark.parametrize("D", CASE.cov_D)
 def test_full_cov_at_fixed_parameters(eng, D):
-    Ns, Ps = [40, 0, 100, 33, 257, 64], [5, 3, 0, 32, 70, 1]
-    T = len(Ns)
-    b = syn.make_batch(T, Ns, Ps, D, 0, base_seed=321, dtype=np.float64)
-    th0 = np.tile(np.concatenate([np.full(D, 2.0), [0.8, 0.05, 1.5]]), (T, 1))
-    r = _run(eng, b, th0, full_cov=True, want_grad=False)
-    r0 = _run(eng, b, th0, want_grad=False)
-    np.testing.assert_array_equal(r.f_mean, r0.f_mean)
-    np.testing.assert_array_equal(r.f_var, r0.f_var)
-    assert r0.f_cov is None and len(r.f_cov) == sum(p * p for p in Ps)
-    tol = 1e-9
-    for t in range(T):
-        a, e, pa, pe = b["obs_off"][t], b["obs_off"][t + 1], b["pred_off"][t], b["pred_off"][t + 1]
-        P = pe - pa
-        if P == 0:
-            continue
-        Cv = np.asarray(r.f_cov[r.cov_off[t]:r.cov_off[t + 1]]).reshape(P, P)
-        Xs = b["Xs"][pa:pe]
-        ref = rq.kernel_matrix(Xs, Xs, th0[t, :D], th0[t, D], th0[t, D + 2]) if Ns[t] == 0 else \
-            rq.predict_cov(b["X"][a:e], b["y"][a:e], Xs, th0[t])
-        np.testing.assert_allclose(Cv, ref, rtol=0, atol=tol * th0[t, D] / 0.8 * 1.0)
-        np.testing.assert_array_equal(Cv, Cv.T)
-        np.testing.assert_allclose(np.diag(Cv), r.f_var[pa:pe], rtol=0, atol=tol)
+    check_full_cov(CASE, eng, D)
 
 
-# ---- 3. scikit-learn's fixture through HipGPRModel
+# ---- 2. scikit-learn's fixture through HipGPRModel
 def _fixture_model(eng, golden_dir, **kernel_kwargs):
     from gpsat_amd.models import HipGPRModel
     g = np.load(os.path.join(golden_dir, "kat_sklearn_rq.npz"))
@@ -193,27 +76,26 @@ def test_sklearn_fixture_optimised_on_the_device(eng, golden_dir):
     assert abs(lml - float(g["ml"])) < 1e-6
 
 
-# ---- 4. a converged fit
+# ---- 3. a converged fit
 FIT_SEEDS = (900, 902, 911)          # SciPy reports success on each, at an alpha inside its box (checked on the CPU)
 
 
 def _fit_tile(seed, N=150, D=3, P=16):
     """Coordinates, prediction points and generating parameters of synthetic.make_tile; y drawn from the RQ prior, alpha = 1."""
     X, _, Xs, tr = syn.make_tile(seed, N, P, D, 0)
-    y = rq.rq_prior_draw(np.random.default_rng(1000 + seed), X, tr[:D], tr[D], tr[D + 1], 1.0)
+    y = vn.rq_prior_draw(np.random.default_rng(1000 + seed), X, tr[:D], tr[D], tr[D + 1], 1.0)
     return X, y - y.mean(), Xs
 
 
 def test_learned_hyperparameters_match_scipy(eng):
     T, D = len(FIT_SEEDS), 3
     tiles = [_fit_tile(s) for s in FIT_SEEDS]
-    b = dict(D=D, obs_off=np.arange(T + 1) * 150, pred_off=np.arange(T + 1) * 16, X=np.concatenate([t[0] for t in tiles]),
+    b = dict(D=D, kernel=KERNEL, obs_off=np.arange(T + 1) * 150, pred_off=np.arange(T + 1) * 16, X=np.concatenate([t[0] for t in tiles]),
              y=np.concatenate([t[1] for t in tiles]), Xs=np.concatenate([t[2] for t in tiles]))
-    lo2, hi2 = syn.default_bounds(T, D)
-    lo, hi = np.column_stack([lo2, np.full(T, 0.1)]), np.column_stack([hi2, np.full(T, 20.0)])
+    lo, hi = CASE.bounds(T, D)                             # alpha in [0.1, 20]
     th0 = np.ones((T, D + 3))
     r = _run(eng, b, th0, lo=lo, hi=hi, optimiser="lbfgs", max_iter=1000, want_grad=False)
-    ref = [rq.fit(X, y, th0[t], lo[t], hi[t], max_iter=1000) for t, (X, y, _) in enumerate(tiles)]
+    ref = [vn.fit(vn.RQ, KERNEL, X, y, th0[t], lo[t], hi[t], max_iter=1000) for t, (X, y, _) in enumerate(tiles)]
     assert all(res.success for _, _, res in ref)
     o_theta, o_nll = np.array([th for th, _, _ in ref]), np.array([f for _, f, _ in ref])
     print("device theta", r.theta, "nll", r.nll, "status", r.status, "n_eval", r.n_eval)
@@ -224,61 +106,13 @@ def test_learned_hyperparameters_match_scipy(eng):
     np.testing.assert_allclose(r.theta[:, :D + 2], o_theta[:, :D + 2], rtol=2e-3, atol=1e-5)
     assert ((r.theta[:, D + 2] >= 0.1) & (r.theta[:, D + 2] <= 20.0)).all()
     for t, (X, y, _) in enumerate(tiles):                  # the returned objective is the objective at the returned theta
-        assert abs(rq.nll_and_grad(X, y, r.theta[t], False)[0] - r.nll[t]) <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
+        assert abs(vn.nll_and_grad(vn.RQ, KERNEL, X, y, r.theta[t], want_grad=False)[0] - r.nll[t]) <= 1e-9 * max(1.0, abs(r.nll[t])) * 150
 
 
-# ---- 5. the same bits alone, inside the batch, on a second call and with the time-sliced queue
-def _same(a, e, what):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(e, name)
-        assert np.asarray(x).tobytes() == np.asarray(y).tobytes(), (what, name)
-
-
-def _one(b, t):
-    s = sharding.pack_subset(b, np.array([t]))
-    return dict(D=b["D"], obs_off=s["obs_off"], pred_off=s["pred_off"], X=s["X"], y=s["y"], Xs=s["Xs"])
-
-
-def test_same_bits_alone_in_the_batch_and_again(eng, ragged):
-    b, th, r = ragged
-    _same(_run(eng, b, th), r, "second call")
-    for t in (17, 100):
-        r1 = _run(eng, _one(b, t), th[[t]])
-        pa, pe = b["pred_off"][t], b["pred_off"][t + 1]
-        for name in FIELDS:
-            whole = getattr(r, name)
-            part = whole[pa:pe] if name in ("f_mean", "f_var", "y_var") else whole[[t]]
-            assert np.asarray(getattr(r1, name)).tobytes() == np.asarray(part).tobytes(), (t, name)
-
-
-def test_time_sliced_optimisation_is_bit_identical(eng, ragged, monkeypatch):
-    """As tests/test_gpu_parity.py::test_time_sliced_optimisation_is_bit_identical forces the queue: suspended after every
-    evaluation, after every third of a 200-point tile, or never -- the H = D + 3 optimiser state travels intact.  One tile of
-    the batch run alone returns the bits it has inside it."""
-    b, th, _ = ragged
-    T, D = RAGGED_T, b["D"]
-    lo2, hi2 = syn.default_bounds(T, D)
-    lo, hi = np.column_stack([lo2, np.full(T, 0.1)]), np.column_stack([hi2, np.full(T, 20.0)])
-    th0 = np.ones((T, D + 3))
-    kw = dict(lo=lo, hi=hi, optimiser="lbfgs", max_iter=12)
-    monkeypatch.setenv("GPSAT_DEVELOPER", "1")
-    monkeypatch.setenv("GPSAT_DEBUG_SEG", "0")
-    r0 = _run(eng, b, th0, **kw)
-    assert r0.n_eval.max() > 6 and (r0.theta[r0.status <= 1, D + 2] != 1.0).all()      # alpha moved
-    for seg in ("1", str(3 * 14 ** 3)):
-        monkeypatch.setenv("GPSAT_DEBUG_SEG", seg)
-        _same(_run(eng, b, th0, **kw), r0, f"slice {seg}")
-    monkeypatch.delenv("GPSAT_DEBUG_SEG")
-    t = 17
-    r1 = _run(eng, _one(b, t), th0[[t]], lo=lo[[t]], hi=hi[[t]], optimiser="lbfgs", max_iter=12)
-    assert r1.theta.tobytes() == r0.theta[[t]].tobytes() and r1.nll.tobytes() == r0.nll[[t]].tobytes()
-    assert r1.f_mean.tobytes() == r0.f_mean[b["pred_off"][t]:b["pred_off"][t + 1]].tobytes()
-
-
-# ---- 6. what the C ABI refuses for this kernel, and that the handle works afterwards
+# ---- 4. what the C ABI refuses for this kernel, and that the handle works afterwards
 def test_refusals_leave_the_handle_usable(eng):
-    b = syn.make_batch(2, 40, 5, 3, 0, base_seed=1, dtype=np.float64)
-    th = _theta(np.random.default_rng(0), 2, 3, 1.0)
+    b = CASE.batch(2, 40, 5, 3, KERNEL, 1)
+    th = CASE.theta(np.random.default_rng(0), 2, 3, 1.0)
     good = _run(eng, b, th)
 
     def refused(match, e=eng, bb=b, tt=th, **kw):
@@ -323,7 +157,7 @@ def test_refusals_leave_the_handle_usable(eng):
     assert lib.gpsat_n_hyper(L.KERNEL_RQ, 3) == 6 and lib.gpsat_n_hyper(L.KERNEL_RQ, 4) == 0
 
 
-# ---- 7. the orchestrator end to end
+# ---- 5. the orchestrator end to end
 def test_orchestrator_tables_equal_the_per_tile_model(eng, tmp_path):
     """12 experts in waves of 5, the run killed after the first wave and resumed: the tables are those of HipGPRModel run
     tile by tile, kernel_alpha among them."""
@@ -331,7 +165,7 @@ def test_orchestrator_tables_equal_the_per_tile_model(eng, tmp_path):
     from gpsat_amd.models import HipGPRModel
     rng = np.random.default_rng(3)
     x = np.sort(rng.uniform(0.0, 14.0, 420))
-    df = pd.DataFrame({"x": x, "y": rq.rq_prior_draw(rng, x[:, None], np.array([0.6]), 1.0, 0.05 ** 2, 0.4)})
+    df = pd.DataFrame({"x": x, "y": vn.rq_prior_draw(rng, x[:, None], np.array([0.6]), 1.0, 0.05 ** 2, 0.4)})
     locs, radius = np.linspace(1.0, 13.0, 12), 1.5
     cons = {"kernel_alpha": {"low": 0.1, "high": 20.0}, "lengthscales": {"low": 1e-3, "high": 10.0}}
     optim = {"fixed_params": ["likelihood_variance"], "max_iter": 60}

@@ -1,8 +1,8 @@
-"""CPU: experts with a trainable constant mean (mean_function="Constant") without a GPU -- the fp64 restatement (mean_numpy)
-against central differences and the generalised-least-squares identity, the ABI's struct, constants and gpsat_n_hyper_mean
-through a compiled C program, the host checks of gpsat_fit_predict_batch_mean, and the host logic of HipGPRModel / Engine /
-BatchedLocalExpertOI with a device-free engine."""
+"""CPU: experts with a trainable constant mean (mean_function="Constant") without a GPU -- the ABI's struct, constants and
+gpsat_n_hyper_mean through a compiled C program, the host checks of gpsat_fit_predict_batch_mean, and the host logic of
+HipGPRModel / Engine / BatchedLocalExpertOI with a device-free engine (variant_numpy's stand-in), and the restatement itself on the checks of tests/variant_cases.py."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -10,67 +10,48 @@ import numpy as np
 import pandas as pd
 import pytest
 
-import mean_numpy as mn
+import variant_numpy as vn
 from gpsat_amd import _lib as L
 from gpsat_amd.engine import Engine, GpsatError
 from gpsat_amd.local_experts import BatchedLocalExpertOI, get_results
 from gpsat_amd.models import HipGPRModel, HipSGPRModel
+from oracle import gp_oracle as go
+from variant_cases import KERNELS, check_gradient, cpu_tile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["RBF", "Matern12", "Matern32", "Matern52"]
-
-
-def _tile(seed, N, D, P=7):
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(0.0, 4.0, (N, D))
-    y = 0.3 + np.sin(X.sum(axis=1)) + 0.1 * rng.standard_normal(N)
-    return X, y, rng.uniform(0.0, 4.0, (P, D))
+_tile, MeanNumpyEngine = functools.partial(cpu_tile, vn.MEAN), functools.partial(vn.NumpyEngine, vn.MEAN)
 
 
 # ---- the restatement
 @pytest.mark.parametrize("D", [1, 2, 3])
 def test_mean_numpy_gradient_matches_central_differences(D):
-    X, y, _ = _tile(10 + D, 30, D)
-    rng = np.random.default_rng(D)
-    kernel = KERNELS[D]
-    for c in (-0.7, 0.0, 2.5):
-        theta = np.concatenate([rng.uniform(0.8, 2.0, D), [0.9, 0.07, c]])
-        _, g = mn.nll_and_grad(kernel, X, y, theta)
-        fd = np.empty_like(g)
-        for i in range(D + 3):
-            h = 1e-5 * max(abs(theta[i]), 1.0)
-            tp, tm = theta.copy(), theta.copy()
-            tp[i] += h
-            tm[i] -= h
-            fd[i] = (mn.nll_and_grad(kernel, X, y, tp, False)[0] - mn.nll_and_grad(kernel, X, y, tm, False)[0]) / (2 * h)
-        np.testing.assert_allclose(g, fd, rtol=1e-7, atol=1e-7 * np.abs(g).max())
+    check_gradient(vn.MEAN, D)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_gls_identity(kernel):
     """c - 1^T K_y^-1 y / 1^T K_y^-1 1 = (dnll/dc) / (1^T K_y^-1 1) at any theta: the stationary c is the generalised
     least-squares level.  Independent of how the gradient was computed."""
-    X, y, _ = _tile(3, 40, 2)
+    X, y, _, _ = _tile(3, 40, 2)
     for c in (-0.7, 0.0, 0.3, 2.5):
         theta = np.array([1.3, 0.9, 0.6, 0.05, c])
-        _, g = mn.nll_and_grad(kernel, X, y, theta)
-        left, right = mn.gls_sides(kernel, X, y, theta, g[-1])
+        _, g = vn.nll_and_grad(vn.MEAN, kernel, X, y, theta)
+        left, right = vn.gls_sides(kernel, X, y, theta, g[-1])
         assert left == pytest.approx(right, rel=1e-9, abs=1e-12 * max(abs(c), 1.0)), (kernel, c)
 
 
 def test_predictions_are_the_zero_mean_models_on_the_residual():
-    from oracle import gp_oracle as go
-    X, y, Xs = _tile(5, 25, 2)
+    X, y, _, Xs = _tile(5, 25, 2)
     theta = np.array([1.1, 2.0, 0.7, 0.03, 0.4])
-    f, fv, yv = mn.predict("Matern32", X, y, Xs, theta)
+    f, fv, yv = vn.predict(vn.MEAN, "Matern32", X, y, Xs, theta)
     f0, fv0, yv0 = go.predict(2, X, y - 0.4, Xs, theta[:4])
     np.testing.assert_array_equal(f, f0 + 0.4)
     np.testing.assert_array_equal(fv, fv0)
-    np.testing.assert_allclose(np.diag(mn.predict_cov("Matern32", X, y, Xs, theta)), fv, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(np.diag(vn.predict_cov(vn.MEAN, "Matern32", X, y, Xs, theta)), fv, rtol=0, atol=1e-12)
     # the fit moves c off its start towards the GLS level, where dnll/dc vanishes
-    th, nll, res = mn.fit("Matern32", X, y, np.array([1.0, 1.0, 1.0, 1.0, 0.0]))
+    th, nll, res = vn.fit(vn.MEAN, "Matern32", X, y, np.array([1.0, 1.0, 1.0, 1.0, 0.0]))
     assert res.success and th[-1] != 0.0
-    left, right = mn.gls_sides("Matern32", X, y, th, mn.nll_and_grad("Matern32", X, y, th)[1][-1])
+    left, right = vn.gls_sides("Matern32", X, y, th, vn.nll_and_grad(vn.MEAN, "Matern32", X, y, th)[1][-1])
     assert abs(left) < 1e-3 and left == pytest.approx(right, rel=1e-9, abs=1e-12)
 
 
@@ -176,7 +157,7 @@ class _NoDevice:
 
 
 def test_model_param_names_accessors_and_fixed_params():
-    X, y, _ = _tile(3, 12, 2)
+    X, y, _, _ = _tile(3, 12, 2)
     kw = dict(coords=X, obs=y, engine=_NoDevice(), dtype="f64", mean_function="Constant")
     m = HipGPRModel(kernel_kwargs={"lengthscales": [2.0, 3.0], "variance": 0.5}, **kw)
     assert m.param_names == ["lengthscales", "kernel_variance", "likelihood_variance", "mean_constant"]
@@ -219,19 +200,19 @@ def test_model_param_names_accessors_and_fixed_params():
 
 
 def test_model_hands_the_mean_to_the_engine():
-    X, y, Xs = _tile(4, 12, 2)
-    eng = mn.MeanNumpyEngine()
+    X, y, _, Xs = _tile(4, 12, 2)
+    eng = MeanNumpyEngine()
     m = HipGPRModel(coords=X, obs=y, engine=eng, dtype="f64", mean_function="Constant", mean_func_kwargs={"c": 0.3},
                     kernel_kwargs={"lengthscales": 1.5}, noise_variance=0.05)
     theta = np.array([1.5, 1.5, 1.0, 0.05, 0.3])
-    assert m.get_objective_function_value() == mn.nll_and_grad("Matern32", X, y, theta, False)[0]
-    np.testing.assert_array_equal(m.predict(Xs)["f*"], mn.predict("Matern32", X, y, Xs, theta)[0])
+    assert m.get_objective_function_value() == vn.nll_and_grad(vn.MEAN, "Matern32", X, y, theta, want_grad=False)[0]
+    np.testing.assert_array_equal(m.predict(Xs)["f*"], vn.predict(vn.MEAN, "Matern32", X, y, Xs, theta)[0])
     assert m.optimise_parameters(fixed_params=["likelihood_variance"]) and m.get_mean_constant() != 0.3
     assert m.get_likelihood_variance() == 0.05
 
 
 def test_model_refusals():
-    X, y, _ = _tile(4, 12, 2)
+    X, y, _, _ = _tile(4, 12, 2)
     kw = dict(coords=X, obs=y, engine=_NoDevice(), mean_function="Constant")
     with pytest.raises(NotImplementedError, match="dtype='f64'"):
         HipGPRModel(dtype="f32", **kw)
@@ -256,7 +237,7 @@ def test_model_refusals():
 
 def test_engine_refuses_before_any_library_call():
     eng = object.__new__(Engine)                                         # no handle, no library: a call would fail otherwise
-    X, y, Xs = _tile(5, 10, 2)
+    X, y, _, Xs = _tile(5, 10, 2)
     kw = dict(D=2, obs_off=[0, 10], X=X, y=y, pred_off=[0, 7], Xs=Xs, dtype="f64", optimiser="none", mean="constant")
     with pytest.raises(GpsatError, match=r"H = D \+ 3 = 5"):
         eng.fit_predict_batch(theta0=np.ones((1, 4)), **kw)
@@ -293,7 +274,7 @@ def _mean_case(n_locs=6, seed=3):
 
 def test_orchestrator_stores_mean_constant_and_reads_it_back(tmp_path):
     cfg, locs = _mean_case()
-    eng = mn.MeanNumpyEngine()
+    eng = MeanNumpyEngine()
     oi = BatchedLocalExpertOI(engine=eng, **cfg)
     assert oi.dtype == "f64" and oi.H == 4 and oi.params_to_store[-1] == "mean_constant" and not oi.rq
     store = str(tmp_path / "store")
@@ -309,7 +290,7 @@ def test_orchestrator_stores_mean_constant_and_reads_it_back(tmp_path):
     np.testing.assert_array_equal(eng.calls[0]["lo"][:, 3], -2.0)
     np.testing.assert_array_equal(eng.calls[0]["hi"][:, 3], 2.0)
     # second run: parameters from the store, no optimisation -> the same predictions
-    eng2 = mn.MeanNumpyEngine()
+    eng2 = MeanNumpyEngine()
     cfg2 = {**cfg, "model_config": {**cfg["model_config"], "load_params": {"file": store, "table_suffix": ""}}}
     tabs2 = BatchedLocalExpertOI(engine=eng2, **cfg2).run(store_path=str(tmp_path / "store2"), optimise=False, table_suffix="_P")
     assert all(c["optimiser"] == "none" for c in eng2.calls)
@@ -319,7 +300,7 @@ def test_orchestrator_stores_mean_constant_and_reads_it_back(tmp_path):
     np.testing.assert_array_equal(tabs2["preds_P"]["f*"].values, tabs["preds"]["f*"].values)
     np.testing.assert_array_equal(tabs2["mean_constant_P"]["mean_constant"].values, mc["mean_constant"].values)
     # direct values, a negative c among them; and without a box
-    eng3 = mn.MeanNumpyEngine()
+    eng3 = MeanNumpyEngine()
     cfg3 = {**cfg, "model_config": {**cfg["model_config"], "constraints": None,
                                     "load_params": {"mean_constant": -0.4, "lengthscales": [0.8]}}}
     BatchedLocalExpertOI(engine=eng3, **cfg3).run(store_path=None, optimise=False)
@@ -329,7 +310,7 @@ def test_orchestrator_stores_mean_constant_and_reads_it_back(tmp_path):
 
 def test_orchestrator_previous_running_mean_includes_the_constant():
     cfg, locs = _mean_case(n_locs=4)
-    eng = mn.MeanNumpyEngine()
+    eng = MeanNumpyEngine()
     cfgp = {**cfg, "model_config": {**cfg["model_config"], "load_params": {"previous": True}}}
     tabs = BatchedLocalExpertOI(engine=eng, **cfgp).run(store_path=None, engine_chunk=1)
     th0 = np.concatenate([c["theta0"] for c in eng.calls])
@@ -346,7 +327,7 @@ def test_orchestrator_previous_running_mean_includes_the_constant():
 def test_orchestrator_refusals():
     cfg, _ = _mean_case()
     mc = cfg["model_config"]
-    E = mn.MeanNumpyEngine
+    E = MeanNumpyEngine
     with pytest.raises(NotImplementedError, match="fp64 only"):
         BatchedLocalExpertOI(engine=E(), dtype="f32", **cfg)
     with pytest.raises(NotImplementedError, match="replacement"):

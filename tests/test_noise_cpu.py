@@ -1,8 +1,8 @@
-"""CPU: known noise variances per observation (obs_var) without a GPU -- the fp64 restatement (noise_numpy) against
-scikit-learn, central differences and the oracle, a scikit-learn fixture, the ABI's struct through a compiled C program, the
+"""CPU: known noise variances per observation (obs_var) without a GPU -- the ABI's struct through a compiled C program, the
 host checks of gpsat_fit_predict_batch_noise (gpsat::check_noise), and the host logic of HipGPRModel / Engine /
-BatchedLocalExpertOI with a device-free engine."""
+BatchedLocalExpertOI with a device-free engine (variant_numpy's stand-in), and the restatement itself on the checks of tests/variant_cases.py."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -10,66 +10,30 @@ import numpy as np
 import pandas as pd
 import pytest
 
-import noise_numpy as nn
+import variant_numpy as vn
 from gpsat_amd import _lib as L
 from gpsat_amd import synthetic as syn
 from gpsat_amd.engine import Engine, GpsatError
 from gpsat_amd.local_experts import BatchedLocalExpertOI
 from gpsat_amd.models import HipGPRModel, HipSGPRModel, HipSklearnGPRModel
 from oracle import gp_oracle as go
+from variant_cases import KERNELS, check_gradient, check_matches_sklearn, check_sklearn_fixture, cpu_tile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["RBF", "Matern12", "Matern32", "Matern52"]
-
-
-def _tile(seed, N, D, P=7):
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(0.0, 4.0, (N, D))
-    y = np.sin(X.sum(axis=1)) + 0.1 * rng.standard_normal(N)
-    v = rng.uniform(0.0, 0.3, N)
-    v[::7] = 0.0                                           # every seventh entry exactly 0
-    return X, y, v, rng.uniform(0.0, 4.0, (P, D))
+_tile, NoiseNumpyEngine = functools.partial(cpu_tile, vn.NOISE), functools.partial(vn.NumpyEngine, vn.NOISE)
 
 
 # ---- the restatement
 @pytest.mark.parametrize("D", [1, 2, 3, 4])
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_noise_numpy_matches_sklearn(kernel, D):
-    """LML, predictive mean and variance of GaussianProcessRegressor(ConstantKernel(s) * {RBF, Matern nu}, alpha=sn2 + v,
-    optimizer=None) -- sklearn adds alpha to the diagonal of K -- to 1e-10, the bound of tests/test_rq_cpu.py."""
-    from sklearn.gaussian_process import GaussianProcessRegressor
-    from sklearn.gaussian_process.kernels import RBF, ConstantKernel, Matern
-    X, y, v, Xs = _tile(D, 60, D)
-    ell = np.random.default_rng(D).uniform(0.7, 2.5, D)
-    s, sn2 = 1.3, 0.05
-    k = RBF(length_scale=ell) if kernel == "RBF" else Matern(length_scale=ell, nu={"Matern12": 0.5, "Matern32": 1.5, "Matern52": 2.5}[kernel])
-    gp = GaussianProcessRegressor(ConstantKernel(s) * k, alpha=sn2 + v, optimizer=None).fit(X, y)
-    theta = np.concatenate([ell, [s, sn2]])
-    nll, _ = nn.nll_and_grad(kernel, X, y, v, theta)
-    f, fv, yv = nn.predict(kernel, X, y, v, Xs, theta)
-    mu, sd = gp.predict(Xs, return_std=True)
-    print("lml", abs(-nll - gp.log_marginal_likelihood_value_), "mean", np.abs(f - mu).max(), "var", np.abs(fv - sd ** 2).max())
-    assert abs(-nll - gp.log_marginal_likelihood_value_) < 1e-10
-    np.testing.assert_allclose(f, mu, rtol=0, atol=1e-10)
-    np.testing.assert_allclose(fv, sd ** 2, rtol=0, atol=1e-10)
-    np.testing.assert_array_equal(yv, fv + sn2)           # a new point carries the homogeneous part only
-    np.testing.assert_allclose(np.diag(nn.predict_cov(kernel, X, y, v, Xs, theta)), fv, rtol=0, atol=1e-12)
+    """GaussianProcessRegressor(ConstantKernel(s) * {RBF, Matern nu}, alpha=sn2 + v, optimizer=None)."""
+    check_matches_sklearn(vn.NOISE, kernel, D, D, 60, np.random.default_rng(D).uniform(0.7, 2.5, D), 1.3, 0.05)
 
 
 @pytest.mark.parametrize("D", [1, 2, 3, 4])
 def test_noise_numpy_gradient_matches_central_differences(D):
-    X, y, v, _ = _tile(10 + D, 30, D)
-    kernel = KERNELS[D % 4]
-    theta = np.concatenate([np.random.default_rng(D).uniform(0.8, 2.0, D), [0.9, 0.07]])
-    _, g = nn.nll_and_grad(kernel, X, y, v, theta)
-    fd = np.empty_like(g)
-    for i in range(D + 2):
-        h = 1e-5 * theta[i]
-        tp, tm = theta.copy(), theta.copy()
-        tp[i] += h
-        tm[i] -= h
-        fd[i] = (nn.nll_and_grad(kernel, X, y, v, tp, False)[0] - nn.nll_and_grad(kernel, X, y, v, tm, False)[0]) / (2 * h)
-    np.testing.assert_allclose(g, fd, rtol=1e-7, atol=1e-7 * np.abs(g).max())
+    check_gradient(vn.NOISE, D)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -79,17 +43,17 @@ def test_constant_variance_is_the_oracle_at_a_larger_likelihood_variance(kernel)
     theta = np.array([1.1, 2.0, 0.7, 0.9, 0.05])
     th2 = theta.copy()
     th2[4] += 0.2
-    nll, g = nn.nll_and_grad(kernel, X, y, np.full(60, 0.2), theta)
+    nll, g = vn.nll_and_grad(vn.NOISE, kernel, X, y, theta, np.full(60, 0.2))
     nll0, g0 = go.nll_and_grad(go.KERNEL_IDS[kernel], X, y, th2)
     print("relative difference", abs(nll - nll0) / abs(nll0))
     assert abs(nll - nll0) <= 1e-12 * abs(nll0)
     np.testing.assert_allclose(g, g0, rtol=1e-10, atol=1e-12)
-    f, fv, yv = nn.predict(kernel, X, y, np.full(60, 0.2), Xs, theta)
+    f, fv, yv = vn.predict(vn.NOISE, kernel, X, y, Xs, theta, np.full(60, 0.2))
     f0, fv0, yv0 = go.predict(go.KERNEL_IDS[kernel], X, y, Xs, th2)
     np.testing.assert_allclose(f, f0, rtol=0, atol=1e-12)
     np.testing.assert_allclose(fv, fv0, rtol=0, atol=1e-12)
     np.testing.assert_allclose(yv, yv0 - 0.2, rtol=0, atol=1e-12)          # y_var leaves v out
-    assert nn.nll_and_grad(kernel, X, y, np.zeros(60), theta)[0] == go.nll_and_grad(go.KERNEL_IDS[kernel], X, y, theta)[0]
+    assert vn.nll_and_grad(vn.NOISE, kernel, X, y, theta, np.zeros(60))[0] == go.nll_and_grad(go.KERNEL_IDS[kernel], X, y, theta)[0]
 
 
 @pytest.mark.parametrize("N,D", [(17, 1), (100, 3), (500, 4)])
@@ -100,7 +64,7 @@ def test_a_huge_variance_deletes_the_row(N, D):
     v = np.zeros(N)
     v[::5] = 1e12
     keep = v == 0.0
-    f, fv, _ = nn.predict("Matern32", X, y, v, Xs, theta)
+    f, fv, _ = vn.predict(vn.NOISE, "Matern32", X, y, Xs, theta, v)
     f0, fv0, _ = go.predict(2, X[keep], y[keep], Xs, theta)
     print("N", N, "D", D, "mean", np.abs(f - f0).max(), "var", np.abs(fv - fv0).max())
     np.testing.assert_allclose(f, f0, rtol=0, atol=1e-11)
@@ -108,33 +72,18 @@ def test_a_huge_variance_deletes_the_row(N, D):
 
 
 def test_sklearn_fixture(golden_dir):
-    """tests/golden/kat_sklearn_noise.npz (tests/golden/make_noise_golden.py, scikit-learn only): noise_numpy at the stored
-    optimum."""
-    g = np.load(os.path.join(golden_dir, "kat_sklearn_noise.npz"))
-    m = np.load(os.path.join(golden_dir, "kat_sklearn_matern32.npz"))
-    np.testing.assert_array_equal(g["x_train"], m["x_train"])
-    np.testing.assert_array_equal(g["y_train"], m["y_train"])
-    v = g["obs_var"]
-    assert float(g["x_test"]) == float(m["x_test"]) and v.shape == (50,) and (v[::7] == 0.0).all() and (v >= 0).all() and v.max() > 0.04
-    X, y = g["x_train"][:, None], g["y_train"]
-    theta = np.array([float(g["ls"]), 1.0, float(g["eps"]) ** 2])
-    nll, grad = nn.nll_and_grad("Matern32", X, y, v, theta)
-    f, fv, _ = nn.predict("Matern32", X, y, v, np.array([[float(g["x_test"])]]), theta)
-    assert abs(-nll - float(g["ml"])) < 1e-8
-    assert abs(f[0] - float(g["pred_mean"])) < 1e-8 and abs(fv[0] - float(g["pred_std"]) ** 2) < 1e-8
-    assert abs(grad[0] * theta[0]) < 1e-3                  # stationary in sklearn's log space
-    assert abs(float(g["ls"]) - float(m["ls"])) > 1e-2    # and v matters: not the optimum of the fixture without it
+    check_sklearn_fixture(golden_dir, vn.NOISE)
 
 
-# ---- the converged-fit case of tests/test_gpu_noise.py: what SciPy itself reproduces
 def test_scipy_agrees_with_itself_from_two_starts_on_the_fit_case():
-    """The GPU test holds the device's fit to SciPy's at nll 5e-5 and theta rtol 2e-3 (tests/test_gpu_mean.py); on these
+    """The GPU test holds the device's fit to SciPy's at nll 5e-5 and theta rtol 2e-3 (tests/test_gpu_noise.py); on these
     inputs SciPy from two starts agrees with itself to a tenth of that."""
-    b, th0, lo, hi = nn.fit_case()
+    b, th0, lo, hi = vn.fit_case()
     for t in range(3):
         sl = slice(150 * t, 150 * (t + 1))
-        a = nn.fit("Matern32", b["X"][sl], b["y"][sl], b["obs_var"][sl], th0[t], lo[t], hi[t], max_iter=1000)
-        c = nn.fit("Matern32", b["X"][sl], b["y"][sl], b["obs_var"][sl], np.array([2.5, 0.6, 1.7, 0.3, 0.05]), lo[t], hi[t], max_iter=1000)
+        a = vn.fit(vn.NOISE, "Matern32", b["X"][sl], b["y"][sl], th0[t], lo[t], hi[t], max_iter=1000, obs_var=b["obs_var"][sl])
+        c = vn.fit(vn.NOISE, "Matern32", b["X"][sl], b["y"][sl], np.array([2.5, 0.6, 1.7, 0.3, 0.05]), lo[t], hi[t], max_iter=1000,
+                   obs_var=b["obs_var"][sl])
         print("tile", t, "theta", a[0], c[0], "nll", a[1], c[1])
         assert a[2].success and c[2].success
         assert abs(a[1] - c[1]) <= 5e-6
@@ -245,16 +194,16 @@ class _NoDevice:
 
 def test_model_scales_the_variances_and_hands_them_to_the_engine():
     X, y, v, Xs = _tile(4, 12, 2)
-    eng = nn.NoiseNumpyEngine()
+    eng = NoiseNumpyEngine()
     m = HipGPRModel(coords=X, obs=y, obs_var=v, engine=eng, dtype="f64", obs_scale=2.0, obs_mean="local",
                     kernel_kwargs={"lengthscales": 1.5}, noise_variance=0.05)
     assert m.param_names == ["lengthscales", "kernel_variance", "likelihood_variance"] and m._theta.shape == (4,)
     np.testing.assert_array_equal(m.obs_var, v / 4.0)                    # variances: divided by obs_scale squared
     theta = np.array([1.5, 1.5, 1.0, 0.05])
     ys = (y - y.mean()) / 2.0
-    assert m.get_objective_function_value() == nn.nll_and_grad("Matern32", X, ys, v / 4.0, theta, False)[0]
+    assert m.get_objective_function_value() == vn.nll_and_grad(vn.NOISE, "Matern32", X, ys, theta, v / 4.0, want_grad=False)[0]
     np.testing.assert_array_equal(eng.calls[-1]["obs_var"], v / 4.0)
-    np.testing.assert_array_equal(m.predict(Xs)["f*"], nn.predict("Matern32", X, ys, v / 4.0, Xs, theta)[0])
+    np.testing.assert_array_equal(m.predict(Xs)["f*"], vn.predict(vn.NOISE, "Matern32", X, ys, Xs, theta, v / 4.0)[0])
     assert m.optimise_parameters(fixed_params=["likelihood_variance"]) and m.get_likelihood_variance() == 0.05
     assert m.get_lengthscales()[0] != 1.5 and eng.calls[-1]["optimiser"] == "lbfgs"
     # the column form, beside data=
@@ -337,7 +286,7 @@ def _noise_case(n_locs=6, seed=3):
 
 def test_orchestrator_carries_the_column_to_the_right_rows(tmp_path):
     cfg, locs, df, radius = _noise_case()
-    eng = nn.NoiseNumpyEngine()
+    eng = NoiseNumpyEngine()
     oi = BatchedLocalExpertOI(engine=eng, **cfg)
     assert oi.dtype == "f64" and oi.H == 3 and oi.extra is None and oi.obs_var_col == "var"
     assert oi.config["data"]["obs_var_col"] == "var"                      # recorded in oi_config
@@ -364,14 +313,14 @@ def test_orchestrator_carries_the_column_to_the_right_rows(tmp_path):
     # the tables are those of the per-tile model with obs_var_col
     for k, loc in enumerate(locs):
         d = df[(df["x"] <= loc + radius) & (df["x"] >= loc - radius)]
-        m = HipGPRModel(data=d, obs_col="y", coords_col=["x"], obs_var_col="var", engine=nn.NoiseNumpyEngine(), dtype="f64",
+        m = HipGPRModel(data=d, obs_col="y", coords_col=["x"], obs_var_col="var", engine=NoiseNumpyEngine(), dtype="f64",
                         **cfg["model_config"]["init_params"])
         m.set_parameter_constraints(cfg["model_config"]["constraints"], move_within_tol=True, tol=1e-2)
         m.optimise_parameters(**cfg["model_config"]["optim_kwargs"])
         assert tabs["lengthscales"]["lengthscales"].values[k] == m.get_lengthscales()[0] != 1.0
         assert tabs["likelihood_variance"]["likelihood_variance"].values[k] == 0.03 ** 2
     # one expert per engine call: the chunks carry their own rows
-    eng2 = nn.NoiseNumpyEngine()
+    eng2 = NoiseNumpyEngine()
     tabs2 = BatchedLocalExpertOI(engine=eng2, **cfg).run(store_path=None, engine_chunk=1)
     assert len(eng2.calls) == len(locs)
     np.testing.assert_array_equal(tabs2["preds"]["f*"].values, tabs["preds"]["f*"].values)
@@ -381,7 +330,7 @@ def test_orchestrator_carries_the_column_to_the_right_rows(tmp_path):
 def test_orchestrator_refusals():
     cfg, _, df, _ = _noise_case()
     mc, dc = cfg["model_config"], cfg["data_config"]
-    E = nn.NoiseNumpyEngine
+    E = NoiseNumpyEngine
     with pytest.raises(NotImplementedError, match="fp64 only"):
         BatchedLocalExpertOI(engine=E(), dtype="f32", **cfg)
     with pytest.raises(NotImplementedError, match="replacement"):

@@ -1,6 +1,6 @@
-"""CPU: RationalQuadratic experts without a GPU -- the fp64 restatement (rq_numpy) against scikit-learn and central
-differences, the scikit-learn fixture, the ABI's constant and gpsat_n_hyper through a compiled C program, and the host logic
-of HipGPRModel / Engine / BatchedLocalExpertOI with a device-free engine."""
+"""CPU: RationalQuadratic experts without a GPU -- the ABI's constant and gpsat_n_hyper through a compiled C program, and the host
+logic of HipGPRModel / Engine / BatchedLocalExpertOI with a device-free engine (variant_numpy's stand-in), and the restatement itself on the checks of tests/variant_cases.py."""
+import functools
 import os
 import subprocess
 
@@ -8,76 +8,32 @@ import numpy as np
 import pandas as pd
 import pytest
 
-import rq_numpy as rq
+import variant_numpy as vn
 from gpsat_amd import _lib as L
 from gpsat_amd.engine import Engine, GpsatError
 from gpsat_amd.local_experts import BatchedLocalExpertOI, get_results
 from gpsat_amd.models import HipGPRModel, HipSGPRModel
+from variant_cases import check_gradient, check_matches_sklearn, check_sklearn_fixture, cpu_tile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_tile, RqNumpyEngine = functools.partial(cpu_tile, vn.RQ), functools.partial(vn.NumpyEngine, vn.RQ)
 
 
-def _tile(seed, N, D, P=7):
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(0.0, 4.0, (N, D))
-    y = np.sin(X.sum(axis=1)) + 0.1 * rng.standard_normal(N)
-    return X, y, rng.uniform(0.0, 4.0, (P, D))
-
-
-# ---- rq_numpy against scikit-learn
+# ---- the restatement: the shared checks of tests/variant_cases.py
 @pytest.mark.parametrize("ell,s,sn2,alpha", [(0.7, 1.3, 0.05, 0.3), (1.5, 0.4, 0.2, 1.0), (2.5, 2.0, 0.01, 30.0)])
 def test_rq_numpy_matches_sklearn(ell, s, sn2, alpha):
-    """LML, predictive mean and variance of GaussianProcessRegressor(ConstantKernel(s) * RationalQuadratic(l, alpha),
-    alpha=sn2, optimizer=None) at three theta with equal length scales, to 1e-10."""
-    from sklearn.gaussian_process import GaussianProcessRegressor
-    from sklearn.gaussian_process.kernels import ConstantKernel, RationalQuadratic
-    D = 2
-    X, y, Xs = _tile(1, 40, D)
-    gp = GaussianProcessRegressor(ConstantKernel(s) * RationalQuadratic(length_scale=ell, alpha=alpha), alpha=sn2, optimizer=None).fit(X, y)
-    theta = np.array([ell] * D + [s, sn2, alpha])
-    nll, _ = rq.nll_and_grad(X, y, theta)
-    f, fv, _ = rq.predict(X, y, Xs, theta)
-    mu, sd = gp.predict(Xs, return_std=True)
-    assert abs(-nll - gp.log_marginal_likelihood_value_) < 1e-10
-    np.testing.assert_allclose(f, mu, rtol=0, atol=1e-10)
-    np.testing.assert_allclose(fv, sd ** 2, rtol=0, atol=1e-10)
-    np.testing.assert_allclose(np.diag(rq.predict_cov(X, y, Xs, theta)), fv, rtol=0, atol=1e-12)
+    """GaussianProcessRegressor(ConstantKernel(s) * RationalQuadratic(l, alpha), alpha=sn2, optimizer=None) at three theta with
+    equal length scales."""
+    check_matches_sklearn(vn.RQ, vn.RQ_KERNEL, 2, 1, 40, ell, s, sn2, alpha)
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
 def test_rq_numpy_gradient_matches_central_differences(D):
-    X, y, _ = _tile(10 + D, 30, D)
-    rng = np.random.default_rng(D)
-    theta = np.concatenate([rng.uniform(0.8, 2.0, D), [0.9, 0.07, 1.7]])
-    _, g = rq.nll_and_grad(X, y, theta)
-    fd = np.empty_like(g)
-    for i in range(D + 3):
-        h = 1e-5 * theta[i]
-        tp, tm = theta.copy(), theta.copy()
-        tp[i] += h
-        tm[i] -= h
-        fd[i] = (rq.nll_and_grad(X, y, tp, False)[0] - rq.nll_and_grad(X, y, tm, False)[0]) / (2 * h)
-    np.testing.assert_allclose(g, fd, rtol=1e-7, atol=1e-7 * np.abs(g).max())
-    # on the diagonal the covariance does not depend on alpha or the length scales
-    K = rq.kernel_matrix(X, X, theta[:D], theta[D], theta[D + 2])
-    np.testing.assert_array_equal(np.diag(K), np.full(len(X), theta[D]))
+    check_gradient(vn.RQ, D)
 
 
 def test_sklearn_fixture(golden_dir):
-    """tests/golden/kat_sklearn_rq.npz (tests/golden/make_rq_golden.py, scikit-learn only): rq_numpy at the stored optimum."""
-    g = np.load(os.path.join(golden_dir, "kat_sklearn_rq.npz"))
-    m = np.load(os.path.join(golden_dir, "kat_sklearn_matern32.npz"))
-    np.testing.assert_array_equal(g["x_train"], m["x_train"])
-    np.testing.assert_array_equal(g["y_train"], m["y_train"])
-    assert float(g["x_test"]) == float(m["x_test"]) and float(g["eps"]) ** 2 == pytest.approx(1e-4)
-    X, y = g["x_train"][:, None], g["y_train"]
-    theta = np.array([float(g["ls"]), 1.0, float(g["eps"]) ** 2, float(g["alpha"])])
-    nll, grad = rq.nll_and_grad(X, y, theta)
-    f, fv, _ = rq.predict(X, y, np.array([[float(g["x_test"])]]), theta)
-    assert abs(-nll - float(g["ml"])) < 1e-8
-    assert abs(f[0] - float(g["pred_mean"])) < 1e-8 and abs(fv[0] - float(g["pred_std"]) ** 2) < 1e-8
-    # a stationary point of the objective in sklearn's log space: dNLL/dlog(theta) = theta dNLL/dtheta
-    assert np.abs(grad[[0, 3]] * theta[[0, 3]]).max() < 1e-3
+    check_sklearn_fixture(golden_dir, vn.RQ)
 
 
 # ---- ABI
@@ -124,7 +80,7 @@ class _NoDevice:
 
 
 def test_model_param_names_accessors_and_fixed_params():
-    X, y, _ = _tile(3, 12, 2)
+    X, y, _, _ = _tile(3, 12, 2)
     m = HipGPRModel(coords=X, obs=y, engine=_NoDevice(), kernel="RationalQuadratic", dtype="f64",
                     kernel_kwargs={"lengthscales": [2.0, 3.0], "variance": 0.5})
     assert m.param_names == ["lengthscales", "kernel_variance", "likelihood_variance", "kernel_alpha"]
@@ -156,7 +112,7 @@ def test_model_param_names_accessors_and_fixed_params():
 
 
 def test_model_refusals():
-    X, y, _ = _tile(4, 12, 2)
+    X, y, _, _ = _tile(4, 12, 2)
     with pytest.raises(NotImplementedError, match="dtype='f64'"):
         HipGPRModel(coords=X, obs=y, engine=_NoDevice(), kernel="RationalQuadratic", dtype="f32")
     with pytest.raises(NotImplementedError, match="dtype='f64'"):
@@ -174,7 +130,7 @@ def test_model_refusals():
 def test_engine_states_the_expected_width():
     """The check runs before anything reaches the library."""
     eng = object.__new__(Engine)
-    X, y, Xs = _tile(5, 10, 2)
+    X, y, _, Xs = _tile(5, 10, 2)
     kw = dict(D=2, obs_off=[0, 10], X=X, y=y, pred_off=[0, 7], Xs=Xs, kernel="RationalQuadratic", dtype="f64", optimiser="none")
     with pytest.raises(GpsatError, match=r"H = D \+ 3 = 5"):
         eng.fit_predict_batch(theta0=np.ones((1, 4)), **kw)
@@ -189,7 +145,7 @@ def _rq_case(n_locs=6, seed=3):
     so the move-within-tol of a later run leaves loaded values alone."""
     rng = np.random.default_rng(seed)
     x = np.sort(rng.uniform(0.0, 10.0, 300))
-    df = pd.DataFrame({"x": x, "y": rq.rq_prior_draw(rng, x[:, None], np.array([0.6]), 1.0, 0.05 ** 2, 0.4)})
+    df = pd.DataFrame({"x": x, "y": vn.rq_prior_draw(rng, x[:, None], np.array([0.6]), 1.0, 0.05 ** 2, 0.4)})
     locs = np.linspace(2.0, 8.0, n_locs)
     radius = 2.0
     cfg = dict(expert_loc_config={"source": pd.DataFrame({"x": locs})},
@@ -205,7 +161,7 @@ def _rq_case(n_locs=6, seed=3):
 
 def test_orchestrator_stores_kernel_alpha_and_reads_it_back(tmp_path):
     cfg, locs = _rq_case()
-    eng = rq.RqNumpyEngine()
+    eng = RqNumpyEngine()
     oi = BatchedLocalExpertOI(engine=eng, **cfg)
     assert oi.dtype == "f64" and oi.H == 4 and oi.params_to_store[-1] == "kernel_alpha"
     store = str(tmp_path / "store")
@@ -219,7 +175,7 @@ def test_orchestrator_stores_kernel_alpha_and_reads_it_back(tmp_path):
     # the start: the defaults, alpha = 1 inside its box; the constraints reached the engine
     np.testing.assert_array_equal(eng.calls[0]["theta0"], np.tile([1.0, 1.0, 0.05 ** 2, 1.0], (3, 1)))
     # second run: parameters from the store, no optimisation -> the same predictions
-    eng2 = rq.RqNumpyEngine()
+    eng2 = RqNumpyEngine()
     cfg2 = {**cfg, "model_config": {**cfg["model_config"], "load_params": {"file": store, "table_suffix": ""}}}
     tabs2 = BatchedLocalExpertOI(engine=eng2, **cfg2).run(store_path=str(tmp_path / "store2"), optimise=False, table_suffix="_P")
     assert all(c["optimiser"] == "none" for c in eng2.calls)
@@ -230,7 +186,7 @@ def test_orchestrator_stores_kernel_alpha_and_reads_it_back(tmp_path):
     np.testing.assert_array_equal(tabs2["preds_P"]["f*_var"].values, tabs["preds"]["f*_var"].values)
     np.testing.assert_array_equal(tabs2["kernel_alpha_P"]["kernel_alpha"].values, ka["kernel_alpha"].values)
     # direct values
-    eng3 = rq.RqNumpyEngine()
+    eng3 = RqNumpyEngine()
     cfg3 = {**cfg, "model_config": {**cfg["model_config"], "load_params": {"kernel_alpha": 3.0, "lengthscales": [0.8]}}}
     BatchedLocalExpertOI(engine=eng3, **cfg3).run(store_path=None, optimise=False)
     th3 = np.concatenate([c["theta0"] for c in eng3.calls])
@@ -239,7 +195,7 @@ def test_orchestrator_stores_kernel_alpha_and_reads_it_back(tmp_path):
 
 def test_orchestrator_previous_running_mean_includes_alpha():
     cfg, locs = _rq_case(n_locs=4)
-    eng = rq.RqNumpyEngine()
+    eng = RqNumpyEngine()
     cfgp = {**cfg, "model_config": {**cfg["model_config"], "load_params": {"previous": True}}}
     tabs = BatchedLocalExpertOI(engine=eng, **cfgp).run(store_path=None, engine_chunk=1)
     th0 = np.concatenate([c["theta0"] for c in eng.calls])
@@ -257,25 +213,25 @@ def test_orchestrator_refusals():
     cfg, _ = _rq_case()
     mc = cfg["model_config"]
     with pytest.raises(NotImplementedError, match="fp64 only"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), dtype="f32", **cfg)
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), dtype="f32", **cfg)
     with pytest.raises(NotImplementedError, match="replacement"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), **{**cfg, "model_config": {**mc, "replacement_threshold": 10}})
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), **{**cfg, "model_config": {**mc, "replacement_threshold": 10}})
     m32 = {**mc, "init_params": {"kernel": "Matern32"}, "constraints": None, "replacement_threshold": 10,
            "replacement_init_params": {"kernel": "RationalQuadratic"}}
     with pytest.raises(NotImplementedError, match="replacement"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), dtype="f64", **{**cfg, "model_config": m32})
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), dtype="f64", **{**cfg, "model_config": m32})
     for cv in ("loo", {"by": ["x"]}, {"by": ["x"], "refit": True}):
         with pytest.raises(NotImplementedError, match="cv"):
-            BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), cv=cv, **cfg)
+            BatchedLocalExpertOI(engine=RqNumpyEngine(), cv=cv, **cfg)
     with pytest.raises(NotImplementedError, match="SGPR"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), **{**cfg, "model_config": {**mc, "oi_model": "GPflowSGPRModel"}})
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), **{**cfg, "model_config": {**mc, "oi_model": "GPflowSGPRModel"}})
     df4 = pd.DataFrame(np.random.default_rng(0).uniform(size=(30, 5)), columns=["a", "b", "c", "d", "y"])
     cfg4 = {**cfg, "data_config": {"data_source": df4, "obs_col": ["y"], "coords_col": ["a", "b", "c", "d"], "local_select": []},
             "expert_loc_config": {"source": df4[["a", "b", "c", "d"]].iloc[:2]}, "pred_loc_config": {"method": "expert_loc"},
             "model_config": {**mc, "constraints": None}}
     with pytest.raises(NotImplementedError, match="1..3 coordinate columns"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), **cfg4)
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), **cfg4)
     with pytest.raises(NotImplementedError, match="params_to_store"):
-        BatchedLocalExpertOI(engine=rq.RqNumpyEngine(), dtype="f64",
+        BatchedLocalExpertOI(engine=RqNumpyEngine(), dtype="f64",
                              **{**cfg, "model_config": {**mc, "init_params": {"kernel": "Matern32"}, "constraints": None,
                                                         "params_to_store": ["kernel_alpha"]}})
