@@ -166,7 +166,8 @@ def _host_meta(D, offs, theta0, lo, hi, trainable, H=None):
     ``H``: hyper-parameters per tile (variants.n_hyper), by default those of the plain call."""
     offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
     T, H = len(offs[0]) - 1, (V.n_hyper(D) if H is None else int(H))
-    assert all(len(o) == T + 1 for o in offs)
+    if not all(len(o) == T + 1 for o in offs):
+        raise GpsatError(f"offset tables of {[len(o) for o in offs]} entries: all need T + 1 = {T + 1}")
 
     def per_tile(a):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (T, H)))
@@ -174,7 +175,8 @@ def _host_meta(D, offs, theta0, lo, hi, trainable, H=None):
     hi = np.full((T, H), np.nan) if hi is None else per_tile(hi)
     trainable = np.ones(H, dtype=np.uint8) if trainable is None else \
         np.ascontiguousarray(np.asarray(trainable).astype(bool).astype(np.uint8))
-    assert trainable.shape == (H,)
+    if trainable.shape != (H,):
+        raise GpsatError(f"trainable has shape {trainable.shape}: ({H},) is expected, one flag per hyper-parameter")
     return offs, per_tile(theta0), lo, hi, trainable
 
 
@@ -206,30 +208,53 @@ class Engine:
         except Exception:
             pass
 
+    def _check_tensor(self, name, t, dtype, numel=None, at_least=None):
+        """One bulk argument of a device-mode call: a contiguous torch tensor of the call's dtype on the engine's GPU, of
+        exactly ``numel`` elements (an input) or of ``at_least`` elements (an output).  Raises GpsatError naming ``name``."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise GpsatError(f"{name}: device mode needs torch tensors for every bulk argument, got {type(t).__name__}")
+        if not t.is_cuda or t.device.index != self.device_id:
+            raise GpsatError(f"{name}: lives on {t.device}, the engine on cuda:{self.device_id}")
+        want = torch.float32 if dtype == "f32" else torch.float64
+        if t.dtype != want:
+            raise GpsatError(f"{name}: has dtype {t.dtype}, the call's dtype {dtype!r} needs {want}")
+        if not t.is_contiguous():
+            raise GpsatError(f"{name}: device mode needs a contiguous tensor (shape {tuple(t.shape)}, strides {t.stride()})")
+        if numel is not None and t.numel() != numel:
+            raise GpsatError(f"{name}: has {t.numel()} elements, {numel} expected")
+        if at_least is not None and t.numel() < at_least:
+            raise GpsatError(f"{name}: has {t.numel()} elements, at least {at_least} (sum P) are written")
+
     def _device_io(self, inputs, dtype, sumP, out):
         """Device mode: check the input tensors (name -> (tensor, elements)), take or allocate the three prediction outputs
-        and wait for the caller's stream.  Returns (f_mean, f_var, y_var)."""
+        and wait for the caller's stream.  Returns (f_mean, f_var, y_var), flat."""
         import torch
-        t_dt = torch.float32 if dtype == "f32" else torch.float64
-        for tname, (t_, _) in inputs.items():
-            if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.dtype == t_dt and t_.is_contiguous()):
-                raise GpsatError(f"{tname}: device mode needs contiguous {dtype} CUDA tensors")
-        dev = inputs["X"][0].device
-        if dev.index != self.device_id:
-            raise GpsatError(f"tensors live on cuda:{dev.index}, engine on device {self.device_id}")
-        assert all(t_.numel() == n for t_, n in inputs.values())
+        for tname, (t_, n) in inputs.items():
+            self._check_tensor(tname, t_, dtype, numel=n)
         if out is None:
             out = tuple(_alloc(sumP, dtype, inputs["X"][0]) for _ in range(3))
-        torch.cuda.current_stream(dev).synchronize()   # inputs must be complete before our stream reads them
-        return tuple(out)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise GpsatError(f"out: three tensors (f_mean, f_var, y_var) are expected, got "
+                                 f"{len(out) if isinstance(out, (tuple, list)) else type(out).__name__}")
+            for oname, o in zip(("f_mean", "f_var", "y_var"), out):
+                self._check_tensor(f"out ({oname})", o, dtype, at_least=sumP)
+            out = tuple(o if o.dim() == 1 else o.view(-1) for o in out)
+        torch.cuda.current_stream(inputs["X"][0].device).synchronize()   # inputs must be complete before our stream reads them
+        return out
 
     def _stage(self, D, dtype, sumN, sumP, X, y, Xs, out, more=None):
         """The bulk inputs and the three prediction outputs as the library takes them: (device_mode, (X, y, Xs), preds).
         Device mode (``X`` is not a numpy array): the tensors, and those of ``more`` (name -> (tensor, elements)), are
-        checked and taken as they are.  Host mode: X, y and Xs are cast to ``dtype`` and laid out contiguously."""
+        checked and handed on as views of shape (sumN, D), (sumN,) and (sumP, D), whatever shape the caller gave them.
+        Host mode: X, y and Xs are cast to ``dtype`` and laid out contiguously; ``out`` is refused."""
         if not isinstance(X, np.ndarray):
-            return True, (X, y, Xs), self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D), **(more or {})},
-                                                     dtype, sumP, out)
+            preds = self._device_io({"X": (X, sumN * D), "y": (y, sumN), "Xs": (Xs, sumP * D), **(more or {})}, dtype, sumP, out)
+            return True, (X.view(sumN, D), y.view(sumN), Xs.view(sumP, D)), preds
+        if out is not None:
+            raise GpsatError("out: preallocated outputs belong to device mode (X, y, Xs as torch tensors on the GPU); with numpy "
+                             "inputs the predictions are returned as new numpy arrays")
         np_dt = NP_DTYPES[dtype]
         data = (np.ascontiguousarray(X, dtype=np_dt).reshape(sumN, D), np.ascontiguousarray(y, dtype=np_dt).reshape(sumN),
                 np.ascontiguousarray(Xs, dtype=np_dt).reshape(sumP, D))
@@ -345,6 +370,13 @@ class Engine:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
+        Device mode returns the bits of host mode in every field, reads the inputs without changing them and writes
+        nothing of the caller's but ``out[i][:sumP]``.  Every bulk argument (X, y, Xs, obs_var, and Z of the sparse call)
+        must be a contiguous tensor of the call's dtype on this engine's GPU with exactly sumN D, sumN, sumP D (sumN, sumM D)
+        elements, in any shape: rows are taken in the order of the flat memory.  ``out``: exactly three such tensors of at
+        least sumP elements each (larger is allowed, the rest is left alone; the result holds the ``[:sumP]`` views of the
+        same storage).  Anything else raises GpsatError naming the argument before the library is called, as does
+        ``out`` with numpy inputs: host mode returns new arrays.
         ``dtype``: "f32" (default; fp32 MFMA kernels) or "f64" (the reference's native precision, fp64 MFMA
         kernels); host arrays are cast, device tensors must already have that dtype.  Offsets / theta0 / bounds
         are always host numpy (fp64).  ``full_cov``: also return the P_t x P_t posterior covariance of every tile
@@ -434,7 +466,8 @@ class Engine:
         # expanded rows per tile: every fold leaves N - g rows, so F N - (rows that are held out at all)
         held = np.bincount(np.repeat(np.arange(T), np.diff(obs_off))[labels >= 0], minlength=T)
         per_tile = np.diff(fold_off) * np.diff(obs_off) - held
-        assert int(per_tile.sum()) == rows.value
+        if int(per_tile.sum()) != rows.value:
+            raise GpsatError(f"cv_refit: {int(per_tile.sum())} expanded rows counted here, {rows.value} by gpsat_cv_refit_count")
         budget = int(opts["max_expanded_rows"])
         ranges, t0, acc = [], 0, 0
         for t in range(T):
