@@ -78,6 +78,10 @@ class GpsatCvRefit(C.Structure):
                 ("fold_n_obs", C.c_void_p), ("fold_label", C.c_void_p), ("reserved", C.c_int32 * 8)]
 
 
+class GpsatCvJoint(C.Structure):
+    _fields_ = [("fold_off", C.c_void_p), ("fold_lpd", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
 CV_START_IDS = {"theta0": 0, "full": 1}
 
 SEL_MAXCRIT = 4
@@ -167,6 +171,10 @@ SIGNATURES = {
     "gpsat_glue_keyed_timing": (_I, [_P, _P], False),
     # the entry points of the variant table: (handle, batch, extension struct); the sparse one has been there since ABI 4
     **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(st)], name == "gpsat_sgpr_fit_predict_batch") for name, st in _EXT.items()},
+    # the joint density per fold: the cv row's call with its struct, and gpsat_cv_joint behind it
+    **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(_EXT[variants.VARIANTS[row].entry]),
+                   C.POINTER(globals()[variants.JOINT_STRUCT])], False)
+       for row, name in variants.JOINT_ENTRY.items()},
 }
 EXPORTS = list(SIGNATURES)
 OPTIONAL_EXPORTS = [name for name, (_, _, required) in SIGNATURES.items() if not required]

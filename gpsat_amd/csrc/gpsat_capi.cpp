@@ -8,6 +8,8 @@
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
 //     cvr_stage_expand, cvr_derived_batch, cvr_unpack, cvr_scatter_fetch.
+//   gpsat_fit_predict_batch_cv_joint / _cv_refit_joint: the same two with the folds' joint densities (check_cv_joint,
+//     check_cv_joint_offsets; stage_cv / fetch_cv carry CvArgs::fold_lpd; cvr_joint_stage and cvr_joint_run around the derived batch).
 //   gpsat_select_batch_ex (gpsat_select_plan.h): check -> cache hit? -> chunks -> stage -> bin (select_bin_table, optional) ->
 //     boxes -> count -> scan -> fill -> unbin (select_unbin_indices, optional) -> fetch -> remember.
 //   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
@@ -116,6 +118,7 @@ struct gpsat_handle : HandleQueue {
     // device buffers (grown lazily, owned by the handle, freed by its destructor)
     DevBuf meta_i64, meta_f64, meta_misc, out_f64, out_i32, bulk_in, bulk_out, ws, prof, ring, state, coop, pq;
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
+    DevBuf cvr_cov;                   // refitted cross-validation with the joint density: cov_off, the derived batch's f_cov, sn2, residuals, lpd
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
     DevBuf memo;                      // 64 bytes of developer statistics, then the evaluation memo [T][MEMO_WORDS] (fp32 L-BFGS batches)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
@@ -328,11 +331,34 @@ int check_cv(const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, CvTab
     return GPSAT_OK;
 }
 
+// The joint density's extension struct (both flavours), in front of everything else; and its fold_off against the count's
+// (`who`: the struct's name in messages, as check_cv_refit names its own).
+int check_cv_joint(const gpsat_cv_joint* jt, const char* entry) {
+    const std::string who = std::string(entry) + ": ";
+    if (!jt) return fail(GPSAT_EINVAL, who + "NULL gpsat_cv_joint");
+    if (!jt->fold_off) return fail(GPSAT_EINVAL, who + "gpsat_cv_joint: fold_off is NULL");
+    if (!jt->fold_lpd) return fail(GPSAT_EINVAL, who + "gpsat_cv_joint: fold_lpd is NULL");
+    for (int i = 0; i < 8; ++i)
+        if (jt->reserved[i] != 0) return fail(GPSAT_EINVAL, who + "gpsat_cv_joint: reserved[" + std::to_string(i) + "] must be 0");
+    return GPSAT_OK;
+}
+
+template <class Off>
+int check_cv_joint_offsets(const gpsat_cv_joint* jt, int T, const Off* fold_off) {
+    for (int t = 0; t <= T; ++t)
+        if (jt->fold_off[t] != (int64_t)fold_off[t])
+            return fail(GPSAT_EINVAL, "gpsat_cv_joint: fold_off[" + std::to_string(t) + "] = " + std::to_string(jt->fold_off[t]) +
+                                          " differs from gpsat_cv_refit_count's " + std::to_string((int64_t)fold_off[t]));
+    return GPSAT_OK;
+}
+
 // The fold tables to the device; the outputs in the handle's buffer (host mode, or no cv_y_var) or the caller's device arrays.
-int stage_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, const CvTables& tb, gpsat::CvArgs& ca) {
+int stage_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const gpsat_cv_joint* jt, const BatchDims& d, const CvTables& tb,
+             gpsat::CvArgs& ca) {
     const size_t nint = (tb.all.size() + 1) & ~size_t(1), sumN = (size_t)d.sumN;
+    const size_t F = jt ? tb.o_fold_a - tb.o_fold_ptr - 1 : 0;       // the joint density: one double per fold behind the outputs
     int rc;
-    if ((rc = h->cv.reserve(nint * sizeof(int) + 3 * std::max<size_t>(sumN, 1) * sizeof(double)))) return rc;
+    if ((rc = h->cv.reserve(nint * sizeof(int) + (3 * std::max<size_t>(sumN, 1) + F) * sizeof(double)))) return rc;
     int* base = static_cast<int*>(h->cv.p);
     HIP_TRY(hipMemcpyAsync(base, tb.all.data(), tb.all.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     ca.pair_off = base + tb.o_pair_off; ca.pairs = base + tb.o_pairs; ca.fold_off = base + tb.o_fold_off;
@@ -343,10 +369,13 @@ int stage_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const Ba
     ca.mean = dev ? static_cast<double*>(cv->cv_mean) : out;
     ca.f_var = dev ? static_cast<double*>(cv->cv_f_var) : out + sumN;
     ca.y_var = dev && cv->cv_y_var ? static_cast<double*>(cv->cv_y_var) : out + 2 * sumN;
+    ca.fold_lpd = F ? out + 3 * std::max<size_t>(sumN, 1) : nullptr;
     return GPSAT_OK;
 }
 
-int fetch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const BatchDims& d, const gpsat::CvArgs& ca) {
+int fetch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const gpsat_cv_joint* jt, const BatchDims& d, const gpsat::CvArgs& ca) {
+    if (ca.fold_lpd)                                  // host memory in either mode
+        HIP_TRY(hipMemcpyAsync(jt->fold_lpd, ca.fold_lpd, (size_t)jt->fold_off[b->T] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (b->memory != GPSAT_MEM_HOST || d.sumN == 0) return GPSAT_OK;
     void* const host[3] = {cv->cv_mean, cv->cv_f_var, cv->cv_y_var};
     const double* const dev[3] = {ca.mean, ca.f_var, ca.y_var};
@@ -643,6 +672,7 @@ struct DenseJob {
     const gpsat_multistart* ms;       // nullptr: gpsat_fit_predict_batch
     const gpsat_cv* cv = nullptr;     // held-out predictions (gpsat_fit_predict_batch_cv), with their fold tables
     CvTables cv_tables;
+    const gpsat_cv_joint* cv_joint = nullptr;     // ... and the folds' joint densities (gpsat_fit_predict_batch_cv_joint)
     int mean = GPSAT_MEAN_ZERO;       // GPSAT_MEAN_CONSTANT: gpsat_fit_predict_batch_mean with a trainable constant mean
     const void* obs_var = nullptr;    // gpsat_fit_predict_batch_noise: noise variances per observation, behind gpsat::check_noise
     bool ms_on;                       // ms given and the optimiser runs
@@ -687,7 +717,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     gpsat::NoiseArgs na;
     na.obs_var = s.obs_var;
     gpsat::CvArgs ca;
-    if (j.cv && (rc = stage_cv(h, b, j.cv, d, j.cv_tables, ca))) return rc;
+    if (j.cv && (rc = stage_cv(h, b, j.cv, j.cv_joint, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
     if (h->dump_dev && !f64) {
         const size_t need = ((size_t)p.NBmax * p.NBmax + p.NBmax) * 1024 + 2 * (size_t)p.NBmax * 32 + 16 + 8 * 1024;
@@ -704,7 +734,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
-    if (j.cv && (rc = fetch_cv(h, b, j.cv, d, ca))) return rc;
+    if (j.cv && (rc = fetch_cv(h, b, j.cv, j.cv_joint, d, ca))) return rc;
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 #ifdef GPSAT_PROFILE
@@ -718,11 +748,11 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
 }
 
 int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr,
-                const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr) {
+                const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr, const gpsat_cv_joint* jt = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
-    j.b = b; j.ms = ms; j.cv = cv;
+    j.b = b; j.ms = ms; j.cv = cv; j.cv_joint = jt;
     int rc;
     if ((rc = check_batch(b, false, j.dims))) return rc;
     if ((rc = check_rq(b, ms ? "gpsat_fit_predict_batch_ms" : cv ? "gpsat_fit_predict_batch_cv" : nullptr))) return rc;
@@ -753,6 +783,7 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
                                       " observations per tile for this dtype and D (gpsat_max_tile_obs)");
     if ((rc = check_batch_data(b, d, j.mean))) return rc;
     if (cv && (rc = check_cv(b, cv, d, j.cv_tables))) return rc;
+    if (jt && (rc = check_cv_joint_offsets(jt, b->T, j.cv_tables.all.data() + j.cv_tables.o_fold_off))) return rc;
     j.ms_on = ms && b->optimiser != GPSAT_OPT_NONE && b->max_iter > 0;
     if (ms && (rc = check_multistart(b, ms, j.ms_on, j.theta0_clipped, j.starts_clipped))) return rc;
     j.theta0 = j.ms_on ? j.theta0_clipped.data() : b->theta0;
@@ -933,8 +964,46 @@ int cvr_scatter_fetch(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refi
     return record_timing(h);
 }
 
-// The batch itself, then its fitted folds as a second batch through fit_predict; the timing is the sum of the four steps.
-int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
+// The joint density of the fitted folds, in front of the derived batch: that batch returns its posterior covariances into
+// h->cvr_cov, laid out as doubles [C] f_cov, [F2] sn2, [P2] residuals, [F2] lpd, then cov_off [F2+1].  `cov_off`: host
+// memory of the caller, alive until the derived batch has run.
+int cvr_joint_stage(gpsat_handle* h, const gpsat::CvFoldDerived& dv, std::vector<int64_t>& cov_off, gpsat::CvFoldArgs& a, gpsat_batch& b2) {
+    const size_t F2 = dv.d_fold.size(), P2 = (size_t)dv.d_pred_off[F2];
+    cov_off = gpsat::cvfold_cov_off(dv);
+    const size_t C = (size_t)cov_off[F2];
+    int rc;
+    if ((rc = h->cvr_cov.reserve((C + 2 * F2 + P2 + F2 + 1) * sizeof(double)))) return rc;
+    double* base = static_cast<double*>(h->cvr_cov.p);
+    a.f_cov = base; a.sn2 = base + C; a.resid = base + C + F2; a.lpd = base + C + F2 + P2;
+    a.cov_off = reinterpret_cast<const long long*>(base + C + 2 * F2 + P2);
+    HIP_TRY(hipMemcpyAsync(const_cast<long long*>(a.cov_off), cov_off.data(), (F2 + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    b2.cov_off = cov_off.data(); b2.f_cov = a.f_cov;
+    return GPSAT_OK;
+}
+
+// ... and behind it: status and likelihood variance of every derived tile to the device, cvfold_lpd, the numbers to the
+// caller's folds.  Synchronises and records the timing.
+int cvr_joint_run(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_joint* jt, const gpsat::CvFoldDerived& dv, const DerivedBatch& db,
+                  const gpsat::CvFoldArgs& a) {
+    const size_t F2 = dv.d_fold.size(), H = (size_t)n_hyper(b);
+    std::vector<double> sn2(F2), lpd(F2);
+    for (size_t j = 0; j < F2; ++j) sn2[j] = db.theta[j * H + b->D + 1];
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    HIP_TRY(hipMemcpyAsync(const_cast<int*>(a.d_status), db.status.data(), F2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(a.sn2), sn2.data(), F2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::launch_cvfold_lpd(a, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    HIP_TRY(hipMemcpyAsync(lpd.data(), a.lpd, F2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // sn2, lpd and the status are host memory of this call
+    for (size_t j = 0; j < F2; ++j) jt->fold_lpd[dv.d_fold[j]] = lpd[j];
+    return record_timing(h);
+}
+
+// The batch itself, then its fitted folds as a second batch through fit_predict; the timing is the sum of the four steps
+// (five with the joint density `jt`).
+int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat_cv_joint* jt = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL handle or batch");
     if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit: NULL gpsat_cv_refit");
     if (b->T == 0) return GPSAT_OK;
@@ -942,13 +1011,17 @@ int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_r
     int rc;
     if ((rc = check_batch(b, false, d))) return rc;
     if ((rc = check_rq(b, "gpsat_fit_predict_batch_cv_refit"))) return rc;
+    if (jt && b->dtype != GPSAT_F64)
+        return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv_refit_joint: the joint density of refitted folds is built for GPSAT_F64 only");
     gpsat::CvFoldTables tb;
     if ((rc = check_cv_refit(b, cv, tb))) return rc;
+    if (jt && (rc = check_cv_joint_offsets(jt, b->T, tb.fold_off.data()))) return rc;
     if ((rc = fit_predict(h, b, nullptr))) return rc;
     double kernel_ms = h->last_kernel_ms, total_ms = h->last_total_ms;
     gpsat::CvFoldDerived dv;
     gpsat::cvfold_derive(tb, b->obs_off, cv->min_obs, dv);
     cvr_folds_skipped(b, cv, tb);
+    if (jt) std::fill(jt->fold_lpd, jt->fold_lpd + tb.fold_off[b->T], std::numeric_limits<double>::quiet_NaN());
     const size_t sumN = (size_t)d.sumN, F2 = dv.d_fold.size();
     if (sumN == 0) return GPSAT_OK;
     const gpsat::CvFoldPacked pk = gpsat::cvfold_pack(tb, dv);
@@ -959,9 +1032,15 @@ int fit_predict_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_r
     kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
     DerivedBatch db;
     cvr_derived_batch(b, cv, tb, dv, a, db);
+    std::vector<int64_t> cov_off;
     if (F2) {
+        if (jt && (rc = cvr_joint_stage(h, dv, cov_off, a, db.b2))) return rc;
         if ((rc = fit_predict(h, &db.b2, nullptr))) return rc;
         kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+        if (jt) {
+            if ((rc = cvr_joint_run(h, b, jt, dv, db, a))) return rc;
+            kernel_ms += h->last_kernel_ms; total_ms += h->last_total_ms;
+        }
     }
     cvr_unpack(b, cv, dv, db, delta);
     if ((rc = cvr_scatter_fetch(h, b, cv, sumN, a, db.status))) return rc;
@@ -1162,6 +1241,18 @@ int gpsat_cv_refit_count(int32_t T, const int64_t* obs_off, const int32_t* fold,
 
 int gpsat_fit_predict_batch_cv_refit(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv) {
     return fit_predict_cv_refit(h, b, cv);
+}
+
+int gpsat_fit_predict_batch_cv_joint(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const gpsat_cv_joint* joint) {
+    if (int rc = check_cv_joint(joint, "gpsat_fit_predict_batch_cv_joint")) return rc;
+    if (!cv) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_cv: NULL gpsat_cv");
+    if (b && b->dtype != GPSAT_F64) return fail(GPSAT_EINVAL, "held-out predictions are built for GPSAT_F64 only");
+    return fit_predict(h, b, nullptr, cv, nullptr, nullptr, joint);
+}
+
+int gpsat_fit_predict_batch_cv_refit_joint(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv_refit* cv, const gpsat_cv_joint* joint) {
+    if (int rc = check_cv_joint(joint, "gpsat_fit_predict_batch_cv_refit_joint")) return rc;
+    return fit_predict_cv_refit(h, b, cv, joint);
 }
 
 #ifdef GPSAT_DUMP

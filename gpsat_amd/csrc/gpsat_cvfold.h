@@ -93,6 +93,18 @@ inline void cvfold_derive(const CvFoldTables& tb, const int64_t* obs_off, int mi
     }
 }
 
+// The joint density of the fitted folds (gpsat_fit_predict_batch_cv_refit_joint): the derived batch returns its posterior
+// covariances, g_j x g_j per derived tile.  cov_off [F2+1] in elements, cov_off[j+1] - cov_off[j] = g_j^2.
+inline std::vector<int64_t> cvfold_cov_off(const CvFoldDerived& dv) {
+    const size_t F2 = dv.d_fold.size();
+    std::vector<int64_t> off(F2 + 1, 0);
+    for (size_t j = 0; j < F2; ++j) {
+        const int64_t g = dv.d_pred_off[j + 1] - dv.d_pred_off[j];
+        off[j + 1] = off[j] + g * g;
+    }
+    return off;
+}
+
 // The tables the two kernels read, packed for one copy each: a block of 64-bit words and a block of int32, laid out once for the
 // host copy and the device.  Each block ends with F2 words that only the device holds (delta as doubles; d_status).
 struct CvFoldPacked {

@@ -10,6 +10,8 @@
 //   cvfold_scatter: one thread per source row: the derived tile's f*, f*_var, y_var at (fold, position in fold), delta added
 //                   to the mean in fp64; NaN for a row that is never held out, whose fold was not fitted, or whose derived
 //                   tile ended NOT_PD / NAN.
+//   cvfold_lpd    : (gpsat_fit_predict_batch_cv_refit_joint, fp64) one workgroup per derived tile: the joint log density of
+//                   the fold's rows under the derived tile's posterior, from its g x g covariance (see the kernel).
 // delta is ONE fp64 sum in a fixed order: thread k adds rows k, k + 256, ... in ascending order, the 256 partial sums are
 // added by a fixed binary tree in LDS.  The workgroup size is a compile-time constant and a derived tile belongs to one
 // workgroup, so the bits do not depend on the grid or on which wave ran first; there is no float atomic.
@@ -103,6 +105,90 @@ __global__ __launch_bounds__(CVF_THREADS) void cvfold_scatter_kernel(CvFoldArgs 
     om[r] = m;
     of[r] = v;
     if (oy) oy[r] = w;
+}
+
+// The joint log predictive density of every fitted fold (gpsat_fit_predict_batch_cv_refit_joint, fp64):
+//   lpd = log N(y'_G; f*, f_cov + sn2 I) = -1/2 w^T w - sum_k log L_kk - g/2 log 2 pi,  L L^T = f_cov + sn2 I,  w = L^-1 (y'_G - f*)
+// from the g x g posterior covariance the derived tile returned.  One workgroup per derived tile, everything in the tile's
+// own f_cov block (lower triangle, in place) and g doubles of `resid`:
+//   - r = (y_G - delta) - f*, sn2 onto the diagonal;
+//   - left-looking Cholesky, column k: every thread forms the pivot from row k (the same k terms in ascending order, so
+//     the value and the branch on it are uniform without a broadcast), thread i - k - 1 (mod CVF_THREADS) owns row i of the
+//     column; one barrier per column;
+//   - forward substitution by columns: w_k = r_k / L_kk is uniform, row i > k takes r_i -= L_ik w_k (one writer per
+//     element, ascending k), thread k mod CVF_THREADS adds w_k^2 to its partial sum (ascending k);
+//   - w^T w: the CVF_THREADS partial sums by the fixed binary tree in LDS that cvfold_expand uses for delta.
+// No float atomic; the bits depend neither on the grid nor on which wave ran.  NaN for a derived tile that ended NOT_PD /
+// NAN and for a pivot <= 0.  Latency-bound: g barriers twice per fold.
+__global__ __launch_bounds__(CVF_THREADS) void cvfold_lpd_kernel(CvFoldArgs a) {
+    __shared__ double part[CVF_THREADS];
+    const int tid = threadIdx.x;
+    constexpr double LOG_2PI = 1.8378770664093453;
+    const double* __restrict__ y = static_cast<const double*>(a.y);
+    const double* __restrict__ fm = static_cast<const double*>(a.fm);
+    for (int j = blockIdx.x; j < a.F2; j += gridDim.x) {
+        const int f = a.d_fold[j], st = a.d_status[j];
+        const int* __restrict__ rows = a.fold_rows + a.fold_ptr[f];
+        const int g = a.fold_ptr[f + 1] - a.fold_ptr[f];
+        if (st == GPSAT_STATUS_NOT_PD || st == GPSAT_STATUS_NAN) {        // uniform: a value of the derived tile
+            if (tid == 0) a.lpd[j] = NAN;
+            continue;
+        }
+        const long long o0 = a.d_src_off[j], po = a.d_pred_off[j];
+        double* S = a.f_cov + a.cov_off[j];                  // not __restrict__: rows written by other threads are read back
+        double* r = a.resid + po;
+        const double delta = a.delta[j], sn2 = a.sn2[j];
+        for (int k = tid; k < g; k += CVF_THREADS) {
+            r[k] = (y[o0 + rows[k]] - delta) - fm[po + k];
+            S[(size_t)k * g + k] += sn2;
+        }
+        __syncthreads();
+        bool bad = false;
+        double sld = 0.0;
+        for (int k = 0; k < g; ++k) {
+            const double* Sk = S + (size_t)k * g;
+            double sp = Sk[k];
+            for (int m = 0; m < k; ++m) { const double l = Sk[m]; sp = fma(-l, l, sp); }
+            if (!(sp > 0.0)) { bad = true; break; }
+            const double dk = sqrt(sp);
+            sld += log(dk);
+            for (int i = k + 1 + tid; i < g; i += CVF_THREADS) {
+                double* Si = S + (size_t)i * g;
+                double s = Si[k];
+                for (int m = 0; m < k; ++m) s = fma(-Si[m], Sk[m], s);
+                Si[k] = s / dk;
+            }
+            __syncthreads();                                 // every read of S[k][k] lies in front of its overwrite
+            if (tid == 0) S[(size_t)k * g + k] = dk;
+        }
+        __syncthreads();
+        if (bad) {
+            if (tid == 0) a.lpd[j] = NAN;
+            continue;
+        }
+        double acc = 0.0;
+        for (int k = 0; k < g; ++k) {
+            const double wk = r[k] / S[(size_t)k * g + k];
+            if (tid == k % CVF_THREADS) acc = fma(wk, wk, acc);
+            for (int i = k + 1 + tid; i < g; i += CVF_THREADS) r[i] = fma(-S[(size_t)i * g + k], wk, r[i]);
+            __syncthreads();
+        }
+        part[tid] = acc;
+        __syncthreads();
+        for (int w = CVF_THREADS / 2; w > 0; w >>= 1) {
+            if (tid < w) part[tid] += part[tid + w];
+            __syncthreads();
+        }
+        if (tid == 0) a.lpd[j] = -0.5 * part[0] - sld - 0.5 * (double)g * LOG_2PI;
+        __syncthreads();                                     // part[] is written again for the next derived tile
+    }
+}
+
+hipError_t launch_cvfold_lpd(const CvFoldArgs& a, hipStream_t stream) {
+    if (a.F2 <= 0) return hipSuccess;
+    if (!a.f64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cvfold_lpd_kernel, dim3(a.F2), dim3(CVF_THREADS), 0, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_cvfold_expand(const CvFoldArgs& a, hipStream_t stream) {

@@ -116,6 +116,7 @@ struct CvArgs {
     double* mean = nullptr;           // [sumN] outputs
     double* f_var = nullptr;
     double* y_var = nullptr;
+    double* fold_lpd = nullptr;       // [F] joint log predictive density of every fold (gpsat_fit_predict_batch_cv_joint), nullptr: off
 };
 // Known noise variances per observation for the fp64 tile kernels (gpsat_fit_predict_batch_noise); a device pointer.
 struct NoiseArgs {
@@ -238,9 +239,16 @@ struct CvFoldArgs {
     double* delta;                    // [F2] mean of the remaining rows (0 without recentre)
     const void *fm, *fv, *yv;         // [P2] predictions of the derived batch (scatter)
     void *cv_mean, *cv_f_var, *cv_y_var;          // [sumN]; cv_y_var may be nullptr
+    // joint log predictive density of every fitted fold (gpsat_fit_predict_batch_cv_refit_joint, fp64 only; cvfold_lpd)
+    const long long* cov_off = nullptr;           // [F2+1] into f_cov: g_j^2 elements per derived tile
+    double* f_cov = nullptr;                      // the derived batch's posterior covariances; factorised in place
+    const double* sn2 = nullptr;                  // [F2] fitted likelihood variance of every derived tile
+    double* resid = nullptr;                      // [P2] scratch: y'_G - f*, consumed by the forward substitution
+    double* lpd = nullptr;                        // [F2] out
 };
 hipError_t launch_cvfold_expand(const CvFoldArgs& a, hipStream_t stream);
 hipError_t launch_cvfold_scatter(const CvFoldArgs& a, hipStream_t stream);
+hipError_t launch_cvfold_lpd(const CvFoldArgs& a, hipStream_t stream);
 
 #define GPSAT_GLUE_MAXVARS 4
 // post-processing (gpsat_post.hip); device pointers

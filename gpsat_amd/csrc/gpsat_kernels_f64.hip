@@ -1378,7 +1378,11 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
 //      (A_GG^-1 alpha_G)_j = sum_i X_ij u_i.
 // Every element of A_GG has one writer and every sum one fixed order, whatever wave runs an item: a tile's held-out bits do
 // not depend on the batch around it.  The fold arrays are global memory written by the host only; the kernel sorts nothing.
-template <int D, int KN>
+// With CvArgs::fold_lpd the fold's joint density log N(y_G; mean, A_GG^-1) = -1/2 u^T u + sum_k log L_kk - g/2 log 2 pi leaves
+// too (gpsat_fit_predict_batch_cv_joint): the lane that finishes a one-row fold in (1), lane 0 of the fold's wave in (2);
+// sum log L_kk in ascending k, u^T u by lane-strided sums in ascending index and the xor tree.  That is JOINT = true, in a
+// kernel of its own (below); JOINT = false holds none of it.
+template <int D, int KN, bool JOINT>
 __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const int t, const long long o0, const bool failed) {
     const int NB = c.NB, lane = c.lane;
     double* __restrict__ mean = cv.mean + o0;
@@ -1390,7 +1394,14 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
     // rows that are never held out, and every row of a tile without a factor
     for (int i = c.tid; i < c.N; i += NT)
         if (failed || rf[i] < 0) { mean[i] = qnan; fvar[i] = qnan; yvar[i] = qnan; }
-    if (failed) return;
+    // the joint log predictive density of every fold (JOINT: the host launches that kernel when CvArgs::fold_lpd is set):
+    // one writer per fold, like the rows' outputs
+    [[maybe_unused]] double* __restrict__ flpd = cv.fold_lpd;
+    constexpr double LOG_2PI = 1.8378770664093453;
+    if (failed) {
+        if constexpr (JOINT) for (int f = cv.fold_off[t] + c.tid; f < cv.fold_off[t + 1]; f += NT) flpd[f] = qnan;
+        return;
+    }
     double* ag = c.ws + (size_t)c.vs0 * BLK;
     // ---- (1)
     const int pb = cv.pair_off[t], pe = cv.pair_off[t + 1];
@@ -1435,6 +1446,10 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
                         mean[i] = lds_d[c.L.y + i] - lds_d[c.L.alpha + i] * var;
                         fvar[i] = var - c.sn2;
                         yvar[i] = var;
+                        if constexpr (JOINT) {               // -1/2 alpha^2 / A_ii - 1/2 log(2 pi / A_ii); NaN with var
+                            const double al = lds_d[c.L.alpha + i];
+                            flpd[fj] = -0.5 * (al * al * var) - 0.5 * (LOG_2PI + log(var));
+                        }
                     } else {
                         const int pi = rp[i];
                         Af[pi * gsz + pj] = acc[r];
@@ -1454,11 +1469,13 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
         const int* __restrict__ rows = cv.fold_rows + r0;
         double* Af = ag + cv.fold_a[f];
         bool bad = false;
+        [[maybe_unused]] double sld = 0.0;                   // sum_k log (L_A)_kk in ascending k (wave-uniform, joint density only)
         for (int k = 0; k < g; ++k) {                        // left-looking Cholesky, column k
             double sp = Af[k * g + k];
             for (int m = 0; m < k; ++m) { const double l = Af[k * g + m]; sp = fma(-l, l, sp); }
             if (!(sp > 0.0)) { bad = true; break; }
             const double dk = sqrt(sp);
+            if constexpr (JOINT) sld += log(dk);
             for (int i = k + 1 + lane; i < g; i += 64) {
                 double s = Af[i * g + k];
 #pragma unroll 4
@@ -1470,6 +1487,7 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
         }
         if (bad) {
             for (int k = lane; k < g; k += 64) { const int i = rows[k]; mean[i] = qnan; fvar[i] = qnan; yvar[i] = qnan; }
+            if constexpr (JOINT) { if (lane == 0) flpd[f] = qnan; }
             continue;
         }
         for (int k = 0; k < g; ++k) {                        // u = L^-1 alpha_G
@@ -1479,6 +1497,13 @@ __device__ __forceinline__ void phase_cv(Ctx<D, KN>& c, const CvArgs& cv, const 
             for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
             if (lane == 0) lds_d[ub + k] = (lds_d[c.L.alpha + rows[k]] - s) / Af[k * g + k];
             wave_lds_sync();
+        }
+        if constexpr (JOINT) {                               // -1/2 u^T u + sum log L_kk - g/2 log 2 pi
+            double s = 0.0;
+            for (int m = lane; m < g; m += 64) { const double um = lds_d[ub + m]; s = fma(um, um, s); }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) flpd[f] = -0.5 * s + sld - 0.5 * (double)g * LOG_2PI;
         }
         for (int j = lane; j < g; j += 64) {                 // column j of X = L^-1
             const double xjj = 1.0 / Af[j * g + j];
@@ -1532,13 +1557,19 @@ __device__ __forceinline__ void predict_prior(const KernelArgs& A, int t, int ti
 // The kernel of every variant.  `cvA` is a parameter of the held-out variant only, `nzA` of the noise variant only -- the one
 // place a variant's row reaches the preprocessor inside the device code: the other variants keep their kernel-argument layout
 // and their mangled names.  There the names stand for these, in the discarded `if constexpr (CV)` / `(NOISE)`.
-#if !F64_ROW(F64_COL_CV)
-constexpr CvArgs cvA{};
-#endif
+// The held-out variant has two kernels per (D, KN): JOINT = true is the one with the folds' joint densities in phase_cv,
+// launched when CvArgs::fold_lpd is set; JOINT = false holds nothing of them, so that its instruction stream and its
+// register allocation are those of the kernel without that output.
 #if !F64_ROW(F64_COL_NOISE)
 constexpr NoiseArgs nzA{};
 #endif
+#if !F64_ROW(F64_COL_CV)
+constexpr CvArgs cvA{};
+constexpr bool JOINT = false;
 template <int D, int KN>
+#else
+template <int D, int KN, bool JOINT>
+#endif
 __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArgs A
 #if F64_ROW(F64_COL_CV)
                                                                  , const CvArgs cvA
@@ -1636,7 +1667,7 @@ __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArg
         }
         if constexpr (CV) {
             __syncthreads();                         // the prediction scratch of every wave is free
-            phase_cv<D, KN>(c, cvA, t, o0, sh->fail != 0);
+            phase_cv<D, KN, JOINT>(c, cvA, t, o0, sh->fail != 0);
         }
         if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1786,9 +1817,14 @@ static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs*
             if constexpr (TEAMS) return launch_kernel(gp_team_kernel_f64<D, KN>, grid, smem, stream, a);
             else return hipErrorInvalidValue;
         }
-        if constexpr (CV) return cv ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *cv) : hipErrorInvalidValue;
-        else if constexpr (NOISE) return nz && nz->obs_var ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *nz) : hipErrorInvalidValue;
+#if F64_ROW(F64_COL_CV)
+        if (!cv) return hipErrorInvalidValue;
+        return cv->fold_lpd ? launch_kernel(gp_tile_kernel_f64<D, KN, true>, grid, smem, stream, a, *cv)
+                            : launch_kernel(gp_tile_kernel_f64<D, KN, false>, grid, smem, stream, a, *cv);
+#else
+        if constexpr (NOISE) return nz && nz->obs_var ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *nz) : hipErrorInvalidValue;
         else return launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a);
+#endif
     }
 }
 

@@ -46,6 +46,8 @@ class BatchResult:
     cv_n_obs: np.ndarray | None = None      # [F] rows the fold leaves
     cv_shift: np.ndarray | None = None      # [F] mean of those rows, in the units of y (0 without recentre)
     cv_label: np.ndarray | None = None      # [F]
+    # cv_joint (either flavour, with cv_fold_off): the joint log predictive density of every fold, in the units of the tile's y
+    cv_lpd: np.ndarray | None = None        # [F] NaN: the fold's rows are NaN, or the fold was not fitted
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -296,9 +298,14 @@ class Engine:
         return BatchResult(f_mean=fm, f_var=fv, y_var=yv, kernel_ms=km.value, total_ms=tm.value, **res, **more)
 
     @staticmethod
-    def _check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov):
+    def _check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov, cv_joint=False):
         """The rows of variants.VARIANTS the call asks for, and the options of ``cv_refit`` (None without it).  Raises for
         what the wrapper refuses itself; what one library call can express is left to the library's own message."""
+        if cv_joint and cv_fold is None:
+            raise GpsatError("cv_joint is the joint density of the held-out folds: it needs cv_fold")
+        if cv_joint and dtype == "f32" and cv_refit not in (None, False):
+            raise GpsatError("cv_joint with cv_refit is built in fp64 only (the g x g factorisation of an fp32 covariance would "
+                             "need a tolerance nobody has measured): pass dtype='f64'")
         if dtype not in NP_DTYPES:
             raise GpsatError(f"dtype {dtype!r}: use 'f32' or 'f64'")
         if mean not in L.MEAN_IDS:
@@ -362,11 +369,29 @@ class Engine:
             fields.update(cv_mean=cvo[0][:sumN], cv_f_var=cvo[1][:sumN], cv_y_var=cvo[2][:sumN])
         return ext, fields, keep
 
+    def _cv_fold_off(self, T, obs_off, labels):
+        """Folds per tile as CSR offsets [T+1], as gpsat_cv_refit_count numbers them; ``labels`` None (leave-one-out): fold k
+        of a tile is its row k, so the offsets are ``obs_off``.  Returns (fold_off, expanded rows or None)."""
+        if labels is None:
+            return np.array(obs_off, dtype=np.int64), None
+        fold_off = np.zeros(T + 1, dtype=np.int64)
+        rows = C.c_int64(0)
+        rc = self._lib.gpsat_cv_refit_count(T, _ptr(obs_off), _ptr(labels), _ptr(fold_off), C.byref(rows))
+        if rc != 0:
+            raise GpsatError(f"gpsat_cv_refit_count failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        return fold_off, rows.value
+
+    def _joint_entry(self, key):
+        name = V.JOINT_ENTRY[key]
+        if not hasattr(self._lib, name):
+            raise GpsatError(f"this libgpsat_hip.so has no {name} (cv_joint: the joint density of every held-out fold)")
+        return name
+
     def fit_predict_batch(self, *, D, obs_off, X, y, pred_off, Xs, theta0, lo=None, hi=None,
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
                           out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
-                          cv_refit=None, mean=None, obs_var=None) -> BatchResult:
+                          cv_refit=None, mean=None, obs_var=None, cv_joint=False) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -399,6 +424,13 @@ class Engine:
         (default CV_REFIT_MAX_EXPANDED_ROWS = 2^25 rows: (D + 1) elements each on the device, 0.5 GiB in fp32 and 1 GiB
         in fp64 at D = 3), consecutive ranges of tiles are run by one library call each and the results concatenated; a
         single tile above the budget is an error.  Refused with cv_fold="loo".
+        ``cv_joint`` (with ``cv_fold``, either flavour; with ``cv_refit`` fp64 only): also ``cv_lpd`` [F], the joint log
+        predictive density log N(y_G; mean, covariance of the held-out fold) of every fold in the units of the tile's y, and
+        ``cv_fold_off`` [T+1] (gpsat_fit_predict_batch_cv_joint / _cv_refit_joint).  NaN where the
+        fold's rows are NaN or the fold was not fitted.  Without ``cv_refit`` every other field has the bits of the call
+        without it.  With ``cv_refit`` the folds' batch returns its posterior covariances for it: a tile's folds count
+        sum g^2 elements against ``max_expanded_rows`` as well, at D + 1 elements per row, and the predictions need not
+        have the bits of the call without ``cv_joint``.
         ``kernel="RationalQuadratic"``: one more hyper-parameter per tile, H = D + 3 with alpha last, so theta0 / lo / hi are
         (H,) or (T, H) and trainable is (H,); fp64 and D <= 3 only.
         ``mean="constant"`` (gpsat_fit_predict_batch_mean): a trainable constant mean c, GPflow's mean_functions.Constant --
@@ -414,7 +446,7 @@ class Engine:
         Which of these arguments cannot be combined is the table of gpsat_amd/variants.py: a pairing
         that one library call cannot express is refused here, any other by the library with its own message.
         """
-        asked, refit = self._check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov)
+        asked, refit = self._check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov, cv_joint)
         self._check_widths(asked, kernel, D, theta0=theta0, lo=lo, hi=hi, trainable=trainable)
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, V.n_hyper(D, asked))
         obs_off, pred_off = meta[0]
@@ -443,36 +475,57 @@ class Engine:
         key, name = self._entry(asked)
         labels = None if cv_fold is None else _fold_labels(cv_fold, sumN)
         if refit:
-            return self._cv_refit(D, dtype, device_mode, meta, data, preds, labels, refit, run)
+            return self._cv_refit(D, dtype, device_mode, meta, data, preds, labels, refit, run, bool(cv_joint))
         args = [self._h, C.byref(b)]
         if key:
             ext, more, keep = self._extension(key, T, H, sumN, dtype, beside, n_starts, starts, obs_var, labels)
             fields.update(more)
             args.append(C.byref(ext))
+        if cv_joint and key == "cv":
+            name = self._joint_entry(key)
+            fold_off, _ = self._cv_fold_off(T, obs_off, labels)
+            lpd = np.full(int(fold_off[-1]), np.nan)
+            jt = L.GpsatCvJoint()
+            jt.fold_off, jt.fold_lpd = _ptr(fold_off), _ptr(lpd)
+            fields.update(cv_fold_off=fold_off, cv_lpd=lpd)
+            args.append(C.byref(jt))
         rc = getattr(self._lib, name)(*args)
         return self._result(rc, name, res, preds, sumP, **fields)
 
-    def _cv_refit(self, D, dtype, device_mode, meta, data, preds, labels, opts, run) -> BatchResult:
-        """gpsat_fit_predict_batch_cv_refit over consecutive ranges of tiles, each within ``max_expanded_rows``."""
+    @staticmethod
+    def _joint_cov_rows(D, T, obs_off, labels):
+        """cv_joint with cv_refit: what a tile's folds add to the budget of expanded rows -- the derived batch returns a g x g
+        covariance per fold, sum g^2 elements, counted at the D + 1 elements an expanded row holds (rounded up)."""
+        tile = np.repeat(np.arange(T, dtype=np.int64), np.diff(obs_off))
+        held = labels >= 0
+        key = tile[held] * (int(labels.max(initial=0)) + 1) + labels[held].astype(np.int64)
+        uk, g = np.unique(key, return_counts=True)
+        elems = np.bincount(uk // (int(labels.max(initial=0)) + 1), weights=(g * g).astype(np.float64), minlength=T).astype(np.int64)
+        return -(-elems // (D + 1))
+
+    def _cv_refit(self, D, dtype, device_mode, meta, data, preds, labels, opts, run, joint=False) -> BatchResult:
+        """gpsat_fit_predict_batch_cv_refit over consecutive ranges of tiles, each within ``max_expanded_rows``; ``joint``:
+        gpsat_fit_predict_batch_cv_refit_joint, whose covariances count against the same budget."""
         (obs_off, pred_off), theta0, lo, hi, trainable = meta
         X, y, Xs = data
         T, H = len(obs_off) - 1, theta0.shape[1]
         sumN, sumP = int(obs_off[-1]), int(pred_off[-1])
-        fold_off = np.zeros(T + 1, dtype=np.int64)
-        rows = C.c_int64(0)
-        rc = self._lib.gpsat_cv_refit_count(T, _ptr(obs_off), _ptr(labels), _ptr(fold_off), C.byref(rows))
-        if rc != 0:
-            raise GpsatError(f"gpsat_cv_refit_count failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        entry = self._joint_entry("cv_refit") if joint else "gpsat_fit_predict_batch_cv_refit"
+        fold_off, n_rows = self._cv_fold_off(T, obs_off, labels)
         # expanded rows per tile: every fold leaves N - g rows, so F N - (rows that are held out at all)
         held = np.bincount(np.repeat(np.arange(T), np.diff(obs_off))[labels >= 0], minlength=T)
         per_tile = np.diff(fold_off) * np.diff(obs_off) - held
-        if int(per_tile.sum()) != rows.value:
-            raise GpsatError(f"cv_refit: {int(per_tile.sum())} expanded rows counted here, {rows.value} by gpsat_cv_refit_count")
+        if int(per_tile.sum()) != n_rows:
+            raise GpsatError(f"cv_refit: {int(per_tile.sum())} expanded rows counted here, {n_rows} by gpsat_cv_refit_count")
+        if joint:
+            per_tile = per_tile + self._joint_cov_rows(D, T, obs_off, labels)
         budget = int(opts["max_expanded_rows"])
         ranges, t0, acc = [], 0, 0
         for t in range(T):
             if per_tile[t] > budget:
-                raise GpsatError(f"cv_refit: tile {t} alone expands to {int(per_tile[t])} rows, above max_expanded_rows = {budget}")
+                raise GpsatError(f"cv_refit: tile {t} alone expands to {int(per_tile[t])} rows" +
+                                 (" (its folds' covariances for cv_joint included)" if joint else "") +
+                                 f", above max_expanded_rows = {budget}")
             if acc + per_tile[t] > budget:
                 ranges.append((t0, t))
                 t0, acc = t, 0
@@ -483,6 +536,8 @@ class Engine:
         fo = dict(cv_theta=np.full((F, H), np.nan), cv_nll=np.full(F, np.nan), cv_shift=np.full(F, np.nan),
                   cv_status=np.full(F, 4, dtype=np.int32), cv_n_eval=np.zeros(F, dtype=np.int32), cv_n_iter=np.zeros(F, dtype=np.int32),
                   cv_n_obs=np.zeros(F, dtype=np.int32), cv_label=np.zeros(F, dtype=np.int32))
+        if joint:
+            fo["cv_lpd"] = np.full(F, np.nan)
         parts, km, tm = [], 0.0, 0.0
         for t0, t1 in ranges:
             a, e, pa, pe, f0, f1 = (int(v) for v in (obs_off[t0], obs_off[t1], pred_off[t0], pred_off[t1], fold_off[t0], fold_off[t1]))
@@ -500,8 +555,13 @@ class Engine:
             cv.fold_theta, cv.fold_nll, cv.fold_shift = _ptr(sub_fo["cv_theta"]), _ptr(sub_fo["cv_nll"]), _ptr(sub_fo["cv_shift"])
             cv.fold_status, cv.fold_n_eval, cv.fold_n_iter = _ptr(sub_fo["cv_status"]), _ptr(sub_fo["cv_n_eval"]), _ptr(sub_fo["cv_n_iter"])
             cv.fold_n_obs, cv.fold_label = _ptr(sub_fo["cv_n_obs"]), _ptr(sub_fo["cv_label"])
-            rc = self._lib.gpsat_fit_predict_batch_cv_refit(self._h, C.byref(b), C.byref(cv))
-            r = self._result(rc, "gpsat_fit_predict_batch_cv_refit", res, sub_preds, pe - pa)
+            more = ()
+            if joint:
+                jt = L.GpsatCvJoint()
+                jt.fold_off, jt.fold_lpd = _ptr(sub_off), _ptr(sub_fo["cv_lpd"])
+                more = (C.byref(jt),)
+            rc = getattr(self._lib, entry)(self._h, C.byref(b), C.byref(cv), *more)
+            r = self._result(rc, entry, res, sub_preds, pe - pa)
             parts.append(res)
             km, tm = km + r.kernel_ms, tm + r.total_ms
         res = {k: (None if parts[0][k] is None else np.concatenate([p_[k] for p_ in parts])) for k in parts[0]}

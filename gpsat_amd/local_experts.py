@@ -106,6 +106,13 @@ section 19; ``postprocessing.glue_cv_predictions``, the grouping and the weighte
 (``postprocessing.score_cv_predictions``: overall and per combination of the ``by`` columns).  ``max_dist`` leaves out the
 experts at that distance or beyond in ``xprt_loc_cols`` (default: the first two coordinate columns).  Both tables are of
 the experts THIS run fitted: a resumed run glues what it ran, ``glue_cv_predictions`` on the store glues everything.
+``cv_joint=True`` (constructor; needs ``cv={"by": [...]}``, with or without ``"refit"``; a refit run in fp64 only): the joint
+log predictive density of every held-out fold, log N(obs_G; mean, covariance of the fold given the expert's other rows)
+(Engine.fit_predict_batch ``cv_joint``).  Table ``cv_folds``, committed with the waves like
+``cv_preds``, has one row per expert and fold: expert index; the ``by`` columns' values; ``n`` (rows of the fold); ``lpd`` in
+RAW observation units (the device's value minus n log ``obs_scale``); and ``lpd_marginal``, the sum of the fold's univariate
+terms from that expert's own ``cv_preds`` rows in raw units, so that the two stand side by side.  The other tables keep
+their columns.  Refused with ``cv="loo"``: a one-row fold's joint density is the marginal one that ``cv_scores`` holds.
 """
 from __future__ import annotations
 
@@ -866,12 +873,13 @@ _Plan = make_dataclass("_Plan", [
 # ----------------------------------------------------------------------------------------------------------
 class BatchedLocalExpertOI:
     def __init__(self, expert_loc_config: dict, data_config: dict, model_config: dict, pred_loc_config: dict,
-                 engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None, cv_glue=None):
+                 engine=None, device_select: bool = False, dtype: Optional[str] = None, cv=None, cv_glue=None, cv_joint=False):
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
         self.dtype = self._ask_variants(data_config, model_config, dtype, cv)
         self._parse_cv(cv)
         self._parse_cv_glue(cv_glue, data_config)
+        self._parse_cv_joint(cv_joint)
         self._load_data(data_config)
         self._load_expert_locs(expert_loc_config, data_config, device_select)
         self._set_profiles(model_config)
@@ -950,6 +958,21 @@ class BatchedLocalExpertOI:
             raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
         self.cv = cv
         self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
+
+    def _parse_cv_joint(self, cv_joint):
+        """``cv_joint``: the joint log predictive density of every held-out fold (table cv_folds).  False: nothing of a run
+        differs.  Sets ``cv_joint`` and records it in the run's configuration."""
+        self.cv_joint = bool(cv_joint)
+        if not self.cv_joint:
+            return
+        if self.cv is None:
+            raise ValueError("cv_joint is the joint density of the held-out folds of a run with cv: give cv={'by': [...]} too")
+        if self.cv == "loo":
+            raise ValueError("cv_joint: the joint density of a leave-one-out fold is the marginal one, which cv_scores already "
+                             "holds (cv_glue); give cv={'by': [column, ...]}")
+        if self.cv_refit is not None and self.dtype == "f32":
+            raise NotImplementedError("cv_joint with refitted folds is built in fp64 only: pass dtype='f64'")
+        self.config["cv_joint"] = True
 
     def _parse_cv_glue(self, cv_glue, data_config):
         """``cv_glue``: glue the held-out predictions per observation and score them after the run (tables cv_glued and
@@ -1216,7 +1239,7 @@ class BatchedLocalExpertOI:
                 sh = shards[0]
                 out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
                 if self.cv is not None and sh.tables is None:
-                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped, sh.cvp_frames)
+                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped, sh.cvp_frames, sh.cvf_frames)
                 if self.cv_glue is not None:
                     self._cv_glue_tables(plan, out, sh.cv_pos)
         finally:
@@ -1522,11 +1545,40 @@ class BatchedLocalExpertOI:
         fr["f_bar"] = np.repeat(np.asarray(f_bar, dtype=np.float64), cnt) + np.repeat(osc, cnt) * v[:, H + 3]
         return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
 
-    def _cv_tables(self, plan, tables, items, frames, skipped, param_frames=()):
-        """``cv_preds`` (with refit: and ``cv_params``) and the run_details column ``cv_rows_skipped`` into a run's (or a
-        wave's) tables."""
+    def _cv_folds_frame(self, plan, items, folds, cv_rows, f_bar):
+        """Table ``cv_folds`` of the tiles among ``items``: one row per expert and fold.  ``folds``: per item ([F, 3]: position
+        in the tile of the fold's first row, rows of the fold, joint density in the units of the tile's y; [N]: fold of every
+        row of the tile, -1: none); ``cv_rows``, ``f_bar``: as ``_cv_frame`` takes them.  ``lpd``: the joint density of the
+        observations in raw units, the device's minus n log(obs_scale); ``lpd_marginal``: the sum of the fold's univariate
+        terms log N(obs; f_bar + obs_scale f*, obs_scale^2 y_var) from the expert's own cv_preds rows, to set beside it."""
+        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
+        cnt = np.array([len(f_[0]) for f_ in folds], dtype=np.int64)
+        first, n, lpd, marg = [np.zeros(0, dtype=np.int64)], [np.zeros(0)], [np.zeros(0)], [np.zeros(0)]
+        for i, (ff, rf), c3, fb in zip(items, folds, cv_rows, np.asarray(f_bar, dtype=np.float64)):
+            if not len(ff):
+                continue
+            s = float(plan.profiles[plan.prof_id[i]].obs_scale)
+            rows = plan.idx[plan.off[i]:plan.off[i + 1]]
+            mean, var = fb + s * c3[:, 0], s * s * c3[:, 2]
+            term = -0.5 * (plan.obs_all[rows] - mean) ** 2 / var - 0.5 * np.log(2.0 * np.pi * var)
+            held = rf >= 0
+            first.append(rows[ff[:, 0].astype(np.int64)])
+            n.append(ff[:, 1])
+            lpd.append(ff[:, 2] - ff[:, 1] * np.log(s))
+            marg.append(np.bincount(rf[held], weights=term[held], minlength=len(ff)))
+        rows = np.concatenate(first).astype(np.int64)
+        fr = {c_: self.df[c_].values[rows] for c_ in self.cv_by}
+        fr.update({"n": np.concatenate(n).astype(np.int64), "lpd": np.concatenate(lpd), "lpd_marginal": np.concatenate(marg)})
+        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
+
+    def _cv_tables(self, plan, tables, items, frames, skipped, param_frames=(), fold_frames=()):
+        """``cv_preds`` (with refit: and ``cv_params``; with cv_joint: and ``cv_folds``) and the run_details column
+        ``cv_rows_skipped`` into a run's (or a wave's) tables."""
         frames = [f_ for f_ in frames if len(f_)]
         tables[f"cv_preds{plan.table_suffix}"] = pd.concat(frames) if len(frames) > 1 else (frames[0] if frames else pd.DataFrame())
+        if self.cv_joint:
+            ff_ = [f_ for f_ in fold_frames if len(f_)]
+            tables[f"cv_folds{plan.table_suffix}"] = pd.concat(ff_) if len(ff_) > 1 else (ff_[0] if ff_ else pd.DataFrame())
         if self.cv_refit is not None:
             pf_ = [f_ for f_ in param_frames if len(f_)]
             tables[f"cv_params{plan.table_suffix}"] = pd.concat(pf_) if len(pf_) > 1 else (pf_[0] if pf_ else pd.DataFrame())
@@ -1682,6 +1734,7 @@ class _ShardRunner:
         self.cv_pos = []                            # per closed wave: the positional rows of its cv_preds frame (cv_glue keys on them)
         self.open_cv, self.cv_frames, self.cv_skipped = {}, [], np.zeros(0, dtype=np.int64)   # held-out rows of the open waves; closed waves' frames
         self.open_cvp, self.cvp_frames = {}, []     # cv refit: per-fold rows of the open waves; closed waves' cv_params frames
+        self.open_cvf, self.cvf_frames = {}, []     # cv_joint: per-fold rows of the open waves; closed waves' cv_folds frames
         self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
         self.counts = np.where(plan.kind[items] == 2, plan.n_pred[items] if plan.predict else 0, 0).astype(np.int64)
 
@@ -1776,6 +1829,8 @@ class _ShardRunner:
                     kw["cv_fold"] = pk["cv_fold"]
                 if self.oi.cv_refit is not None:
                     kw["cv_refit"] = dict(self.oi.cv_refit, recentre=bool(pf.local_mean), min_obs=self.oi._cv_min_obs)
+                if self.oi.cv_joint:
+                    kw["cv_joint"] = True
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
                                            **kw, **({"full_cov": True} if pf.full_cov else {}))
             t1 = time.perf_counter()
@@ -1810,6 +1865,16 @@ class _ShardRunner:
             for kk, j in enumerate(loc_ids):
                 cvr[j] = cv3[o_off[kk]:o_off[kk + 1]]
             skp[loc_ids] = pk["cv_skipped"]
+            if self.oi.cv_joint:
+                cvf, lab, f_off = self.open_cvf[wi], pk["cv_fold"], r.cv_fold_off
+                for kk, j in enumerate(loc_ids):
+                    lt = lab[o_off[kk]:o_off[kk + 1]]
+                    # folds ascend with the label: np.unique's order
+                    codes, pos, inv, n = np.unique(lt[lt >= 0], return_index=True, return_inverse=True, return_counts=True)
+                    row_fold = np.full(len(lt), -1, dtype=np.int64)
+                    row_fold[lt >= 0] = inv.reshape(-1)
+                    cvf[j] = (np.column_stack([np.flatnonzero(lt >= 0)[pos] if len(pos) else np.zeros(0), n,
+                                               r.cv_lpd[f_off[kk]:f_off[kk + 1]]]), row_fold)
             if self.oi.cv_refit is not None:
                 cvp, lab, f_off = self.open_cvp[wi], pk["cv_fold"], r.cv_fold_off
                 per_fold = np.column_stack([r.cv_theta, r.cv_nll, r.cv_status, r.cv_n_obs, r.cv_shift, np.zeros(len(r.cv_nll))])
@@ -1850,6 +1915,7 @@ class _ShardRunner:
             self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
             self.open_cv[wi] = ([np.zeros((0, 3))] * n, np.zeros(n, dtype=np.int64))
             self.open_cvp[wi] = [np.zeros((0, self.H + 5))] * n
+            self.open_cvf[wi] = [(np.zeros((0, 3)), np.zeros(0, dtype=np.int64))] * n
         return self.open[wi]
 
     def _close_waves_to(self, w):
@@ -1871,13 +1937,16 @@ class _ShardRunner:
         tables = oi._tables(p, items, fixed, pred_cat, cov_cat, with_preds=not lazy)
         cvr, skp = self.open_cv.pop(wi)
         cvp = self.open_cvp.pop(wi)
+        cvf = self.open_cvf.pop(wi)
         if oi.cv is not None:
             self.cv_frames.append(oi._cv_frame(p, items, cvr, fixed[:, self.H + _OBS_MEAN]))
             self.cv_pos.append(oi._cv_positions(p, items, cvr))
             if oi.cv_refit is not None:
                 self.cvp_frames.append(oi._cv_params_frame(p, items, cvp, fixed[:, self.H + _OBS_MEAN]))
+            if oi.cv_joint:
+                self.cvf_frames.append(oi._cv_folds_frame(p, items, cvf, cvr, fixed[:, self.H + _OBS_MEAN]))
             self.cv_skipped = np.concatenate([self.cv_skipped, skp])
-            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp, self.cvp_frames[-1:])
+            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp, self.cvp_frames[-1:], self.cvf_frames[-1:])
         oi.timings["tables_s"] += time.perf_counter() - tt
         tf = time.perf_counter()
         # commit: these experts are done.  The parts are written by the writer thread while the next wave runs (one writer,

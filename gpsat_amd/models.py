@@ -443,7 +443,7 @@ class HipGPRModel:
             out["f_bar"] = f_bar
         return out
 
-    def cross_validate(self, fold=None, apply_scale=True, refit=False, **refit_kwargs) -> Dict[str, np.ndarray]:
+    def cross_validate(self, fold=None, apply_scale=True, refit=False, joint=False, **refit_kwargs) -> Dict[str, np.ndarray]:
         """Held-out predictions.  ``refit=False``: at the model's current parameters (no optimisation, nothing is fitted
         again without the fold; for that see ``refit`` below): every row predicted from the rows of all OTHER folds, from the tile's own factor (gpsat_fit_predict_batch_cv).
         ``fold``: None = leave-one-out; an array-like of N labels of any hashable kind, or a 2-D array whose equal rows form
@@ -457,14 +457,18 @@ class HipGPRModel:
         Engine.fit_predict_batch takes them in ``cv_refit``, and ``max_iter`` / ``optimiser`` / ``max_ls`` / ``ftol`` /
         ``gtol`` as ``optimise_parameters`` does.  "f*" is in the units of the tile's own "f_bar"; the result also holds,
         per fold in ascending order of the factorised label, "fold" (the code of factorise_folds), "theta" [F, H],
-        "objective_value", "status", "num_obs" and "shift" (the mean of the rows the fold leaves, in the units of "f*")."""
+        "objective_value", "status", "num_obs" and "shift" (the mean of the rows the fold leaves, in the units of "f*").
+        ``joint=True`` (either flavour; with ``refit`` fp64 only): also, per fold in ascending order of the factorised label
+        (leave-one-out: per row), "fold" (the label's code), "fold_size" (its rows) and "lpd", the joint log predictive
+        density log N(y_G; mean, covariance of the held-out fold) in the units of "f*" (Engine.fit_predict_batch
+        ``cv_joint``); NaN where the fold's rows are NaN.  Without ``joint`` the result has exactly the keys above."""
         from .engine import factorise_folds
         N, D = self.coords.shape
         why = V.why_refused(self._variants + ["cv_refit" if refit else "cv"], None, None)
         if why:
             raise NotImplementedError(why)
         if refit:
-            return self._cross_validate_refit(fold, **refit_kwargs)
+            return self._cross_validate_refit(fold, joint=joint, **refit_kwargs)
         if refit_kwargs:
             raise TypeError(f"cross_validate: {sorted(refit_kwargs)} are options of refit=True")
         nmax = L.max_tile_obs("f64", D)
@@ -477,24 +481,45 @@ class HipGPRModel:
             counts = np.bincount(labels[labels >= 0]) if (labels >= 0).any() else np.zeros(1, dtype=int)
             if counts.max() > gmax:
                 raise ValueError(f"a fold of {int(counts.max())} rows: at most {gmax} rows are held out together (gpsat_max_cv_fold)")
-        r = self._engine.fit_predict_batch(dtype="f64", optimiser="none", max_iter=0, cv_fold=labels, **self._tile_args())
+        more = {"cv_joint": True} if joint else {}
+        r = self._engine.fit_predict_batch(dtype="f64", optimiser="none", max_iter=0, cv_fold=labels, **self._tile_args(), **more)
         if r.status[0] in (2, 3):
             raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
-        return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
-                "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N)}
+        out = {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
+               "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N)}
+        if joint:
+            out.update(self._joint_folds(np.arange(N, dtype=np.int32) if fold is None else labels, r.cv_lpd))
+        return out
+
+    @staticmethod
+    def _joint_folds(labels, lpd):
+        """The per-fold arrays of ``joint=True``: folds in ascending code, as the engine numbers them."""
+        codes, sizes = np.unique(labels[labels >= 0], return_counts=True)
+        if len(codes) != len(lpd):
+            from .engine import GpsatError
+            raise GpsatError(f"cross_validate(joint=True): {len(codes)} folds counted here, {len(lpd)} by the engine")
+        return {"fold": codes.astype(np.int32), "fold_size": sizes.astype(np.int64), "lpd": np.asarray(lpd, dtype=np.float64)}
 
 
-    def _cross_validate_refit(self, fold, max_iter=10_000, optimiser="lbfgs", **kw):
+    def _cross_validate_refit(self, fold, max_iter=10_000, optimiser="lbfgs", joint=False, **kw):
         from .engine import factorise_folds
         N = len(self.coords)
         labels = np.arange(N, dtype=np.int32) if fold is None else factorise_folds(fold, N)
         run = {k: kw.pop(k) for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in kw}
         r = self._engine.fit_predict_batch(dtype=self.dtype, optimiser=optimiser, max_iter=max_iter, cv_fold=labels,
-                                           cv_refit=kw or True, **self._tile_args(), **run)
-        return {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
-                "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N),
-                "fold": r.cv_label, "theta": r.cv_theta, "objective_value": r.cv_nll, "status": r.cv_status,
-                "num_obs": r.cv_n_obs, "shift": r.cv_shift}
+                                           cv_refit=kw or True, **self._tile_args(), **run, **({"cv_joint": True} if joint else {}))
+        out = {"f*": np.asarray(r.cv_mean, dtype=np.float64), "f*_var": np.asarray(r.cv_f_var, dtype=np.float64),
+               "y_var": np.asarray(r.cv_y_var, dtype=np.float64), "f_bar": np.repeat(self.obs_mean[:, 0], N),
+               "fold": r.cv_label, "theta": r.cv_theta, "objective_value": r.cv_nll, "status": r.cv_status,
+               "num_obs": r.cv_n_obs, "shift": r.cv_shift}
+        if joint:
+            jf = self._joint_folds(labels, r.cv_lpd)
+            if not np.array_equal(jf["fold"], out["fold"]):
+                from .engine import GpsatError
+                raise GpsatError(f"cross_validate(joint=True): folds {jf['fold'].tolist()} counted here, "
+                                 f"{np.asarray(out['fold']).tolist()} by the engine")
+            out.update(fold_size=jf["fold_size"], lpd=jf["lpd"])
+        return out
 
 
 def select_inducing_points(coords: np.ndarray, num_inducing_points: int, seed: int = 0, expert_index: int = 0) -> np.ndarray:

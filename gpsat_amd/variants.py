@@ -53,6 +53,10 @@ VARIANTS = {
     "full_cov": Variant("full_cov", "the full covariance (pred_kwargs.full_cov)", excludes=frozenset({"cv", "cv_refit", "sgpr"})),
 }
 PLAIN_ENTRY = "gpsat_fit_predict_batch"       # the call without any extension struct
+# The joint log predictive density per fold (cv_joint) is an option of the two cv rows, not a row: the entry point that
+# carries it takes the row's struct and, behind it, JOINT_STRUCT.
+JOINT_ENTRY = {"cv": "gpsat_fit_predict_batch_cv_joint", "cv_refit": "gpsat_fit_predict_batch_cv_refit_joint"}
+JOINT_STRUCT = "GpsatCvJoint"
 
 for _k, _v in VARIANTS.items():
     assert all(_k in VARIANTS[_o].excludes for _o in _v.excludes), f"{_k}: excludes is not symmetric"

@@ -338,6 +338,41 @@ int gpsat_cv_refit_count(int32_t T, const int64_t *obs_off, const int32_t *fold,
  * gpsat_cv_refit_count's, start or recentre outside {0, 1}, and cov_off / f_cov in the same call. */
 int gpsat_fit_predict_batch_cv_refit(gpsat_handle *h, const gpsat_batch *b, const gpsat_cv_refit *cv);
 
+/*
+ * The joint log predictive density of every fold, an optional output of both cross-validation calls: one fp64 number per
+ * fold, in the units of the tile's y as cv_mean is.  Callers detect it by the presence of the two symbols below; no
+ * existing struct changes its layout and GPSAT_ABI_VERSION stays 4.  Summed over a tile's folds it is the cross-validation
+ * pseudo-likelihood (Rasmussen & Williams section 5.4.2).
+ *   gpsat_fit_predict_batch_cv_joint: with A = K_y^-1, alpha = A y, L_A the lower Cholesky factor of A_GG and
+ *     u = L_A^-1 alpha_G:   fold_lpd = log N(y_G; cv_mean_G, A_GG^-1) = -1/2 u^T u + sum_k log (L_A)_kk - g/2 log 2 pi
+ *     (one row: -1/2 alpha_i^2 / A_ii - 1/2 log(2 pi / A_ii)).  Every other output has the bits of
+ *     gpsat_fit_predict_batch_cv; a tile's fold_lpd has the same bits alone, inside any batch and on a second call.
+ *   gpsat_fit_predict_batch_cv_refit_joint (GPSAT_F64 only: the g x g factorisation of an fp32 covariance would need a
+ *     tolerance nobody has measured): for the fold's derived tile at its own fitted theta,
+ *     fold_lpd = log N(y'_G; f*, f_cov + sn2 I), y'_G the fold's rows shifted by the fold's delta as the remaining rows
+ *     were, sn2 the fold's fitted likelihood variance.  The derived batch returns its posterior covariances for it, into a
+ *     buffer of the handle (sum over the fitted folds of g^2 doubles, kept until gpsat_destroy; a fold has no size limit),
+ *     so that batch is planned as a batch with f_cov is: its predictions need not have the bits of
+ *     gpsat_fit_predict_batch_cv_refit's.  A second call returns the same bits.
+ * NaN: where the fold's rows are NaN (a failed tile, a pivot <= 0 in A_GG, a derived tile that ended NOT_PD / NAN), a fold
+ * that was not fitted (refit: fewer than max(min_obs, 1) rows left) and a pivot <= 0 in the refit flavour's g x g
+ * factorisation.  Rows of label < 0 belong to no fold.
+ * Folds are numbered as gpsat_cv_refit_count numbers them, in both calls: fold_off[t] + k is fold k of tile t, folds of a
+ * tile in ascending label; with gpsat_cv.fold == NULL (leave-one-out) fold k of a tile is its row k, so fold_off = obs_off.
+ */
+typedef struct gpsat_cv_joint {
+    const int64_t *fold_off;   /* [T+1] host, from gpsat_cv_refit_count (fold == NULL: fold_off = obs_off) */
+    double        *fold_lpd;   /* [F] host, F = fold_off[T] */
+    int32_t        reserved[8];/* must be 0 */
+} gpsat_cv_joint;
+
+/* as the call without _joint, which refuses what it refuses as before.  GPSAT_EINVAL (with a message; the handle stays
+ * usable) also for a NULL joint, a NULL member of it, non-zero reserved words and a fold_off that differs from
+ * gpsat_cv_refit_count's (the message names the index); the refit flavour also for GPSAT_F32. */
+int gpsat_fit_predict_batch_cv_joint(gpsat_handle *h, const gpsat_batch *b, const gpsat_cv *cv, const gpsat_cv_joint *joint);
+int gpsat_fit_predict_batch_cv_refit_joint(gpsat_handle *h, const gpsat_batch *b, const gpsat_cv_refit *cv,
+                                           const gpsat_cv_joint *joint);
+
 /* library / ABI version (GPSAT_ABI_VERSION) */
 int gpsat_version(void);
 

@@ -14,6 +14,13 @@ the time of the two streaming kernels alone with the bytes they move (read: ever
 fold; written: the derived X', y', Xs').
 
     python scripts/cv_bench.py --refit [--tiles 4096] [--obs 500] [--fold 25] [--max-iter 10000]
+
+``--joint``: the cost of the joint log predictive density per fold (cv_joint): the same tiles with
+contiguous folds of ``--fold`` rows in fp64, the factor flavour (optimiser "none") and the refit flavour (L-BFGS from theta0 = 1,
+``--max-iter``), each without and with ``cv_joint``.  With a library that lacks the entry points (an earlier commit's) the calls
+without it are timed alone, so that the unchanged path can be set beside its parent's.
+
+    python scripts/cv_bench.py --joint [--tiles 4096] [--obs 500] [--fold 25] [--max-iter 10000] [--reps 5]
 """
 import argparse
 import json
@@ -91,15 +98,44 @@ def refit_bench(a):
     print(json.dumps(out))
 
 
+def joint_bench(a):
+    """The cost of the joint density per fold (cv_joint) beside the same call without it, both flavours, fp64."""
+    T, N, D, G = a.tiles, a.obs, 3, a.fold
+    b = syn.make_batch(T, N, 0, D, 0, base_seed=2000, dtype=np.float64)
+    labels = np.tile(np.arange(N, dtype=np.int32) // G, T)
+    lo, hi = syn.default_bounds(T, D)
+    eng = Engine(0)
+    out = {"tiles": T, "obs": N, "D": D, "fold": G, "kernel": "RBF", "dtype": "f64", "device": eng.device_name, "reps": a.reps,
+           "refit_max_iter": a.max_iter, "has_joint": hasattr(eng._lib, "gpsat_fit_predict_batch_cv_joint"), "kernel_ms": {}}
+    kw = dict(D=D, obs_off=b["obs_off"], X=b["X"], y=b["y"], pred_off=b["pred_off"], Xs=b["Xs"], kernel="RBF", dtype="f64", cv_fold=labels)
+    factor = dict(kw, theta0=np.ones((T, D + 2)), optimiser="none")
+    refit = dict(kw, theta0=np.ones((T, D + 2)), lo=lo, hi=hi, optimiser="lbfgs", max_iter=a.max_iter,
+                 cv_refit={"max_expanded_rows": 1 << 40})
+    cases = {"factor": factor, "refit": refit}
+    if out["has_joint"]:                                  # a library without the entry points: the calls without it only
+        cases.update(factor_joint=dict(factor, cv_joint=True), refit_joint=dict(refit, cv_joint=True))
+    for name, c in cases.items():
+        reps = a.reps if name.startswith("factor") else max(1, min(a.reps, 2))
+        eng.fit_predict_batch(**c)                        # warm-up: buffers, code objects
+        ms = [eng.fit_predict_batch(**c).kernel_ms for _ in range(reps)]
+        out["kernel_ms"][name] = {"median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+        print(name, out["kernel_ms"][name], file=sys.stderr, flush=True)
+    eng.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--refit", action="store_true")
+    ap.add_argument("--joint", action="store_true")
     ap.add_argument("--max-iter", type=int, default=10_000)
     ap.add_argument("--tiles", type=int, default=4096)
     ap.add_argument("--obs", type=int, default=500)
     ap.add_argument("--fold", type=int, default=25)
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
+    if a.joint:
+        return joint_bench(a)
     if a.refit:
         return refit_bench(a)
     T, N, D = a.tiles, a.obs, 3
