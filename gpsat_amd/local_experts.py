@@ -113,6 +113,7 @@ log predictive density of every held-out fold, log N(obs_G; mean, covariance of 
 RAW observation units (the device's value minus n log ``obs_scale``); and ``lpd_marginal``, the sum of the fold's univariate
 terms from that expert's own ``cv_preds`` rows in raw units, so that the two stand side by side.  The other tables keep
 their columns.  Refused with ``cv="loo"``: a one-row fold's joint density is the marginal one that ``cv_scores`` holds.
+The code behind ``cv``, ``cv_glue`` and ``cv_joint`` is gpsat_amd/local_cv.py.
 """
 from __future__ import annotations
 
@@ -131,6 +132,7 @@ import pandas as pd
 from scipy.spatial import cKDTree
 
 from . import _lib as L
+from . import local_cv as LC
 from . import sharding
 from . import variants as V
 from .models import (HipGPRModel, HipSGPRModel, LIKELIHOOD_VARIANCE_LOWER_BOUND, SGPR_MODEL_NAMES, clamp_within,
@@ -864,8 +866,9 @@ _Profile = make_dataclass("_Profile", [
 # row; prof_id indexes profiles; theta0, lo, hi [T, H] its start parameters and box.
 _Plan = make_dataclass("_Plan", [
     "ex", "locs", "off", "idx", "n_obs", "pcs", "n_pred", "kind", "prof_id", "profiles", "theta0", "lo", "hi", "save_params",
-    "want_cov", "coords_all", "obs_all", "config_id", "table_suffix", "optimise", "predict", "var_all"])
-# var_all: the noise variance of every row of obs_all (data_config["obs_var_col"], raw observation units), or None
+    "want_cov", "coords_all", "obs_all", "config_id", "table_suffix", "optimise", "predict", "var_all", "min_obs"])
+# var_all: the noise variance of every row of obs_all (data_config["obs_var_col"], raw observation units), or None;
+# min_obs: the run's option (a tile below it is a stub row; a refitted cv fold that leaves fewer rows is not fitted)
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -877,9 +880,13 @@ class BatchedLocalExpertOI:
         self.config = {"locations": _jsonable(expert_loc_config), "data": _jsonable(data_config),
                        "model": _jsonable(model_config), "pred_loc": _jsonable(pred_loc_config)}
         self.dtype = self._ask_variants(data_config, model_config, dtype, cv)
-        self._parse_cv(cv)
-        self._parse_cv_glue(cv_glue, data_config)
-        self._parse_cv_joint(cv_joint)
+        # cross-validation (local_cv.py): ``cv`` the parsed options, None in a run without it
+        self.cv = LC.parse_options(cv, cv_glue, cv_joint, data_config, self.dtype)
+        self.cv_glue = self.cv.glue if self.cv is not None else None
+        if self.cv_glue is not None:
+            self.config["cv_glue"] = dict(self.cv_glue)
+        if self.cv is not None and self.cv.joint:
+            self.config["cv_joint"] = True
         self._load_data(data_config)
         self._load_expert_locs(expert_loc_config, data_config, device_select)
         self._set_profiles(model_config)
@@ -937,72 +944,8 @@ class BatchedLocalExpertOI:
         self.H = V.n_hyper(D, self._variants)
         return dtype
 
-    def _parse_cv(self, cv):
-        """``cv``: held-out predictions (table cv_preds): "loo", or {"by": [columns of the data source]} -- rows of a tile with
-        equal values in those columns are held out together.  None: nothing of a run differs.  With "refit": True every fold is
-        fitted again without its rows (tables cv_preds and cv_params; fp32 or fp64), from "start": "theta0" (default) | "full".
-        Sets ``cv``, ``cv_by`` and ``cv_refit``."""
-        self.cv_refit = None
-        if isinstance(cv, dict) and "refit" in cv:
-            if not set(cv) <= {"by", "refit", "start"}:
-                raise ValueError("cv must be None, 'loo', {'by': [column, ...]} or {'by': [...], 'refit': True, 'start': 'theta0' | 'full'}")
-            if cv.get("by") in (None, "loo") or len(_as_list(cv["by"])) == 0:
-                raise NotImplementedError("cv: refit is not built for leave-one-out through the orchestrator: give {'by': [column, ...]}")
-            if cv.get("start", "theta0") not in ("theta0", "full"):
-                raise ValueError(f"cv: start must be 'theta0' or 'full', got {cv.get('start')!r}")
-            if cv["refit"]:
-                self.cv_refit = {"start": cv.get("start", "theta0")}
-            elif "start" in cv:
-                raise ValueError("cv: start is an option of refit=True")
-        elif not (cv is None or cv == "loo" or (isinstance(cv, dict) and set(cv) == {"by"} and len(_as_list(cv["by"])) > 0)):
-            raise ValueError("cv must be None, 'loo' or {'by': [column, ...]}")
-        self.cv = cv
-        self.cv_by = [] if cv in (None, "loo") else _as_list(cv["by"])
-
-    def _parse_cv_joint(self, cv_joint):
-        """``cv_joint``: the joint log predictive density of every held-out fold (table cv_folds).  False: nothing of a run
-        differs.  Sets ``cv_joint`` and records it in the run's configuration."""
-        self.cv_joint = bool(cv_joint)
-        if not self.cv_joint:
-            return
-        if self.cv is None:
-            raise ValueError("cv_joint is the joint density of the held-out folds of a run with cv: give cv={'by': [...]} too")
-        if self.cv == "loo":
-            raise ValueError("cv_joint: the joint density of a leave-one-out fold is the marginal one, which cv_scores already "
-                             "holds (cv_glue); give cv={'by': [column, ...]}")
-        if self.cv_refit is not None and self.dtype == "f32":
-            raise NotImplementedError("cv_joint with refitted folds is built in fp64 only: pass dtype='f64'")
-        self.config["cv_joint"] = True
-
-    def _parse_cv_glue(self, cv_glue, data_config):
-        """``cv_glue``: glue the held-out predictions per observation and score them after the run (tables cv_glued and
-        cv_scores): {"inference_radius": r, "R": 3, "max_dist": d | None, "xprt_loc_cols": [...] | None}.  None: nothing of a
-        run differs.  Sets ``cv_glue`` (the option with its defaults filled in) and records it in the run's configuration."""
-        self.cv_glue = None
-        if cv_glue is None:
-            return
-        if self.cv is None:
-            raise ValueError("cv_glue glues the held-out predictions of a run with cv: give cv='loo' or cv={'by': [...]} too")
-        if not isinstance(cv_glue, dict) or "inference_radius" not in cv_glue or \
-                not set(cv_glue) <= {"inference_radius", "R", "max_dist", "xprt_loc_cols"}:
-            raise ValueError("cv_glue must be None or {'inference_radius': r, 'R': 3, 'max_dist': d | None, 'xprt_loc_cols': [...] | None}")
-        r = cv_glue["inference_radius"]
-        if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not (r > 0 and np.isfinite(r)):
-            raise ValueError(f"cv_glue: inference_radius must be one finite positive number, got {r!r}")
-        coords = list(data_config["coords_col"])
-        cols = cv_glue.get("xprt_loc_cols")
-        cols = coords[:2] if cols is None else _as_list(cols)
-        if not 1 <= len(cols) <= 2 or any(c not in coords for c in cols):
-            raise ValueError(f"cv_glue: xprt_loc_cols must be 1 or 2 of the coordinate columns {coords}, got {cols}")
-        md = cv_glue.get("max_dist")
-        if md is not None and not (md == md):
-            raise ValueError("cv_glue: max_dist is NaN")
-        self.cv_glue = {"inference_radius": float(r), "R": float(cv_glue.get("R", 3)), "max_dist": None if md is None else float(md),
-                        "xprt_loc_cols": list(cols)}
-        self.config["cv_glue"] = dict(self.cv_glue)
-
     def _load_data(self, data_config):
-        """The globally selected frame (local_experts.py:266-290) and, with ``cv_by``, the fold code of every row."""
+        """The globally selected frame (local_experts.py:266-290) and, with ``cv`` by columns, the fold code of every row."""
         self.obs_col = data_config["obs_col"]
         self.coords_col = list(data_config["coords_col"])
         if isinstance(self.obs_col, (list, tuple)):
@@ -1014,15 +957,7 @@ class BatchedLocalExpertOI:
         self.df = df
         if self.obs_var_col is not None and self.obs_var_col not in df.columns:
             raise KeyError(f"obs_var_col: column {self.obs_var_col!r} is not in the data source")
-        missing = [c for c in self.cv_by if c not in df.columns]
-        if missing:
-            raise KeyError(f"cv: columns {missing} are not in the data source")
-        # one code per distinct combination of the `by` columns over the whole frame: equal codes inside a tile = one fold;
-        # -1: a missing value in a `by` column, such a row is never held out
-        self._cv_codes = pd.factorize(pd.MultiIndex.from_frame(df[self.cv_by]) if len(self.cv_by) > 1 else df[self.cv_by[0]])[0] \
-            .astype(np.int64) if self.cv_by else None
-        if self.cv_by:
-            self._cv_codes[df[self.cv_by].isna().any(axis=1).values] = -1
+        self._cv_codes = LC.fold_codes(df, self.cv.by) if self.cv is not None else None
 
     def _load_expert_locs(self, expert_loc_config, data_config, device_select):
         """Expert locations (local_experts.py:349-422) and the dynamic global_select entries as per-expert rank intervals."""
@@ -1195,7 +1130,6 @@ class BatchedLocalExpertOI:
         in_group = (not logical) and world_size > 1 and d_world == world_size
         if self.cv is not None and world_size > 1:
             raise NotImplementedError("cv: held-out predictions are not built for sharded runs (world_size > 1, real or logical)")
-        self._cv_min_obs = int(min_obs)
         if world_size > 1 and not logical and not in_group and gather:
             # explicit rank / world_size without a process group of that size: the caller synchronises the ranks itself
             # (nothing here can separate reading the resume state from rank 0's writes, and nothing can gather)
@@ -1218,7 +1152,7 @@ class BatchedLocalExpertOI:
         parts = [p_[plan.kind[p_] != 0] for p_ in parts]
         self.timings.update(engine_s=0.0, engine_call_s=0.0, kernel_s=0.0, tables_s=0.0, flush_s=0.0)
         self.timings["calls"] = []          # per engine call: (job, tiles, start, end, kernel seconds), times from the start of run()
-        shards, got = [], None
+        shards, got, whole = [], None, []
         try:
             if logical:
                 # every logical shard on this engine, merged by the routine that closes the gather
@@ -1238,19 +1172,16 @@ class BatchedLocalExpertOI:
             else:
                 sh = shards[0]
                 out = sh.tables if sh.tables is not None else self._tables(plan, sh.items, sh.fixed, sh.preds, sh.cov)
-                if self.cv is not None and sh.tables is None:
-                    self._cv_tables(plan, out, sh.items, sh.cv_frames, sh.cv_skipped, sh.cvp_frames, sh.cvf_frames)
-                if self.cv_glue is not None:
-                    self._cv_glue_tables(plan, out, sh.cv_pos)
+                if sh.cv is not None:
+                    whole = sh.cv.finish(out, whole_run=sh.tables is None)
         finally:
             tf = time.perf_counter()                               # also after a fault: what was committed is on disk
             for sh in reversed(shards):
                 while sh.flush:
                     sh.flush.pop().result()
             self.timings["flush_wait_s"] += time.perf_counter() - tf
-        if self.cv_glue is not None and len(out.get(f"cv_glued{table_suffix}", ())):
-            for name in (f"cv_glued{table_suffix}", f"cv_scores{table_suffix}"):      # whole tables, behind the waves' commits
-                store.put(name, out[name])
+        for name in whole:                                         # whole tables (cv_glued, cv_scores), behind the waves' commits
+            store.put(name, out[name])
         self.run_seconds = time.perf_counter() - t_start
         self.timings["total_s"] = self.run_seconds
         return out
@@ -1306,7 +1237,7 @@ class BatchedLocalExpertOI:
         return _Plan(ex=ex, locs=locs, off=off, idx=idx, n_obs=n_obs, pcs=pcs, n_pred=n_pred, kind=kind, prof_id=prof_id,
                      profiles=profiles, theta0=theta0, lo=lo, hi=hi, save_params=save_params, coords_all=coords_all,
                      want_cov=any(pf.full_cov for pf in profiles), obs_all=obs_all, config_id=config_id,
-                     table_suffix=table_suffix, optimise=optimise, predict=predict, var_all=var_all)
+                     table_suffix=table_suffix, optimise=optimise, predict=predict, var_all=var_all, min_obs=int(min_obs))
 
     def _select(self, refs, locs):
         """Membership CSR (off, idx) of every expert in ``refs`` and its prediction coordinates; with ``device_select`` the
@@ -1452,7 +1383,7 @@ class BatchedLocalExpertOI:
         if var is not None:
             out["obs_var"] = var
         if self.cv is not None:
-            out["cv_fold"], out["cv_skipped"] = self._cv_labels(plan, ids, Ns)
+            out["cv_fold"], out["cv_skipped"] = LC.call_labels(self, plan, ids, Ns)
         if pf.sgpr:
             # per tile the inducing points HipSGPRModel picks: a seeded subset of the tile's scaled coordinates
             Zs = [select_inducing_points(X[o_off[j]:o_off[j + 1]], pf.n_inducing, pf.inducing_seed, int(plan.ex[i]))
@@ -1460,131 +1391,6 @@ class BatchedLocalExpertOI:
             out["z_off"] = np.concatenate([[0], np.cumsum([len(z) for z in Zs])]).astype(np.int64)
             out["Z"] = np.concatenate(Zs) if Zs else np.zeros((0, D))
         return out
-
-    def _cv_labels(self, plan, ids, Ns):
-        """The fold labels of one engine call's rows ("loo", or int32 [sum N]) and, per tile, the rows that are not held out
-        because their fold is above the kernel's limit (label -1)."""
-        skipped = np.zeros(len(ids), dtype=np.int64)
-        if not self.cv_by:
-            return "loo", skipped
-        rows = np.concatenate([plan.idx[plan.off[i]:plan.off[i + 1]] for i in ids]) if len(ids) else np.zeros(0, dtype=np.int64)
-        tile = np.repeat(np.arange(len(ids), dtype=np.int64), Ns)
-        code = self._cv_codes[rows]
-        known = code >= 0
-        key = tile * (int(self._cv_codes.max(initial=0)) + 1) + np.where(known, code, 0)
-        _, inv, cnt = np.unique(key[known], return_inverse=True, return_counts=True)
-        inv = inv.reshape(-1)
-        labels = np.full(len(rows), -1, dtype=np.int32)
-        labels[known] = inv
-        big = np.zeros(len(rows), dtype=bool)
-        if len(inv) and self.cv_refit is None:       # a refitted fold is a prediction set: no limit
-            big[known] = cnt[inv] > L.max_cv_fold("f64", len(self.coords_col))
-        labels[big] = -1
-        skip = big | ~known
-        np.add.at(skipped, tile[skip], 1)
-        return labels, skipped
-
-    def _cv_positions(self, plan, items, cv_rows):
-        """The positional row in the selected frame of every row of ``_cv_frame(plan, items, cv_rows, ...)``."""
-        parts = [plan.idx[plan.off[i]:plan.off[i + 1]] for i, c in zip(np.asarray(items, dtype=np.int64), cv_rows) if len(c)]
-        return np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
-
-    def _cv_glue_tables(self, plan, tables, positions):
-        """``cv_glued`` and ``cv_scores`` of a run's ``cv_preds`` into its tables: one glued held-out prediction per
-        observation, keyed on the observation's positional row in the selected frame (``positions``: per wave, the rows of
-        the wave's cv_preds frame), in raw units by the profile's ``obs_scale`` (postprocessing.glue_cv_predictions)."""
-        from . import postprocessing as post
-        cvp = tables[f"cv_preds{plan.table_suffix}"]
-        g = self.cv_glue
-        if len(cvp):
-            key = np.concatenate(positions) if len(positions) else np.zeros(0, dtype=np.int64)
-            assert len(key) == len(cvp)
-            glued = post._glue_cv_frame(cvp, key, g["xprt_loc_cols"], g["inference_radius"], g["R"], g["max_dist"],
-                                        plan.profiles[0].obs_scale, self.engine)
-            scores = post.score_cv_predictions(glued, by=self.cv_by or None)
-        else:
-            glued, scores = pd.DataFrame(), pd.DataFrame()
-        tables[f"cv_glued{plan.table_suffix}"] = glued
-        tables[f"cv_scores{plan.table_suffix}"] = scores
-
-    def _cv_frame(self, plan, items, cv_rows, f_bar):
-        """Table ``cv_preds`` of the tiles among ``items`` (``cv_rows``: per item the [N, 3] held-out f*, f*_var, y_var of its
-        rows, in the order of the tile; ``f_bar``: per item the tile's de-meaning constant): expert coordinates as the index,
-        like ``preds``, and the values in the units of ``preds`` -- the observation is ``f_bar + obs_scale f*`` plus noise."""
-        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
-        cnt = np.array([len(c) for c in cv_rows], dtype=np.int64)
-        rows = self._cv_positions(plan, items, cv_rows)
-        vals = _cat([c for c in cv_rows if len(c)], 3)
-        tot = int(cnt.sum())
-        fr = {"_dim_0": np.arange(tot) - np.repeat(np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt),
-              "obs_index": self.df.index.values[rows]}
-        for c_ in self.cv_by:
-            fr[c_] = self.df[c_].values[rows]
-        for ci, c_ in enumerate(cc):
-            fr[f"pred_loc_{c_}"] = plan.coords_all[rows, ci]
-        fr[self.obs_col] = plan.obs_all[rows]
-        fr.update({"f*": vals[:, 0], "f*_var": vals[:, 1], "y_var": vals[:, 2], "f_bar": np.repeat(np.asarray(f_bar, dtype=np.float64), cnt)})
-        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
-
-    def _cv_params_frame(self, plan, items, folds, f_bar):
-        """Table ``cv_params`` of the tiles among ``items`` (``folds``: per item [F, H + 5]: theta, objective, status, rows
-        fitted, shift, position in the tile of the fold's first row; ``f_bar``: per item the tile's de-meaning constant)."""
-        cc, items, H = self.coords_col, np.asarray(items, dtype=np.int64), self.H
-        cnt = np.array([len(c) for c in folds], dtype=np.int64)
-        v = _cat([c for c in folds if len(c)], H + 5)
-        rows = np.concatenate([plan.idx[plan.off[i] + c[:, H + 4].astype(np.int64)] for i, c in zip(items, folds) if len(c)]).astype(np.int64) \
-            if cnt.sum() else np.zeros(0, dtype=np.int64)
-        fr = {c_: self.df[c_].values[rows] for c_ in self.cv_by}
-        fr["num_obs"] = v[:, H + 2].astype(np.int64)
-        for pn, (start, width) in V.slots(len(cc), self._variants).items():
-            for k in range(width):
-                fr[f"{pn}_{k}" if pn == "lengthscales" else pn] = v[:, start + k]
-        fr["objective_value"] = v[:, H]
-        fr["optimise_success"] = bool(plan.optimise) & (v[:, H + 1] == 0)
-        osc = np.array([plan.profiles[p].obs_scale for p in plan.prof_id[items]], dtype=np.float64)
-        fr["f_bar"] = np.repeat(np.asarray(f_bar, dtype=np.float64), cnt) + np.repeat(osc, cnt) * v[:, H + 3]
-        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
-
-    def _cv_folds_frame(self, plan, items, folds, cv_rows, f_bar):
-        """Table ``cv_folds`` of the tiles among ``items``: one row per expert and fold.  ``folds``: per item ([F, 3]: position
-        in the tile of the fold's first row, rows of the fold, joint density in the units of the tile's y; [N]: fold of every
-        row of the tile, -1: none); ``cv_rows``, ``f_bar``: as ``_cv_frame`` takes them.  ``lpd``: the joint density of the
-        observations in raw units, the device's minus n log(obs_scale); ``lpd_marginal``: the sum of the fold's univariate
-        terms log N(obs; f_bar + obs_scale f*, obs_scale^2 y_var) from the expert's own cv_preds rows, to set beside it."""
-        cc, items = self.coords_col, np.asarray(items, dtype=np.int64)
-        cnt = np.array([len(f_[0]) for f_ in folds], dtype=np.int64)
-        first, n, lpd, marg = [np.zeros(0, dtype=np.int64)], [np.zeros(0)], [np.zeros(0)], [np.zeros(0)]
-        for i, (ff, rf), c3, fb in zip(items, folds, cv_rows, np.asarray(f_bar, dtype=np.float64)):
-            if not len(ff):
-                continue
-            s = float(plan.profiles[plan.prof_id[i]].obs_scale)
-            rows = plan.idx[plan.off[i]:plan.off[i + 1]]
-            mean, var = fb + s * c3[:, 0], s * s * c3[:, 2]
-            term = -0.5 * (plan.obs_all[rows] - mean) ** 2 / var - 0.5 * np.log(2.0 * np.pi * var)
-            held = rf >= 0
-            first.append(rows[ff[:, 0].astype(np.int64)])
-            n.append(ff[:, 1])
-            lpd.append(ff[:, 2] - ff[:, 1] * np.log(s))
-            marg.append(np.bincount(rf[held], weights=term[held], minlength=len(ff)))
-        rows = np.concatenate(first).astype(np.int64)
-        fr = {c_: self.df[c_].values[rows] for c_ in self.cv_by}
-        fr.update({"n": np.concatenate(n).astype(np.int64), "lpd": np.concatenate(lpd), "lpd_marginal": np.concatenate(marg)})
-        return pd.DataFrame(fr, index=_index_for_repeated(cc, plan.locs[items], cnt))
-
-    def _cv_tables(self, plan, tables, items, frames, skipped, param_frames=(), fold_frames=()):
-        """``cv_preds`` (with refit: and ``cv_params``; with cv_joint: and ``cv_folds``) and the run_details column
-        ``cv_rows_skipped`` into a run's (or a wave's) tables."""
-        frames = [f_ for f_ in frames if len(f_)]
-        tables[f"cv_preds{plan.table_suffix}"] = pd.concat(frames) if len(frames) > 1 else (frames[0] if frames else pd.DataFrame())
-        if self.cv_joint:
-            ff_ = [f_ for f_ in fold_frames if len(f_)]
-            tables[f"cv_folds{plan.table_suffix}"] = pd.concat(ff_) if len(ff_) > 1 else (ff_[0] if ff_ else pd.DataFrame())
-        if self.cv_refit is not None:
-            pf_ = [f_ for f_ in param_frames if len(f_)]
-            tables[f"cv_params{plan.table_suffix}"] = pd.concat(pf_) if len(pf_) > 1 else (pf_[0] if pf_ else pd.DataFrame())
-        rd = tables[f"run_details{plan.table_suffix}"]
-        assert len(rd) == len(items) == len(skipped)
-        rd["cv_rows_skipped"] = np.asarray(skipped, dtype=np.int64)
 
     def _cov_counts(self, plan, items, counts):
         """Full-covariance rows per item: P^2 where the item's profile wants ``full_cov``, else 0."""
@@ -1731,10 +1537,7 @@ class _ShardRunner:
         self.piece_futs, self.packs = {}, {}   # wave -> writes of its preds pieces; job -> its packed arrays (future)
         self.rows = ([], [], [])               # fixed, preds, cov of the closed waves
         self.tables, self.flush = None, []     # the only wave's tables; the flush queued last
-        self.cv_pos = []                            # per closed wave: the positional rows of its cv_preds frame (cv_glue keys on them)
-        self.open_cv, self.cv_frames, self.cv_skipped = {}, [], np.zeros(0, dtype=np.int64)   # held-out rows of the open waves; closed waves' frames
-        self.open_cvp, self.cvp_frames = {}, []     # cv refit: per-fold rows of the open waves; closed waves' cv_params frames
-        self.open_cvf, self.cvf_frames = {}, []     # cv_joint: per-fold rows of the open waves; closed waves' cv_folds frames
+        self.cv = LC.Collector(oi, plan) if oi.cv is not None else None       # the held-out results and their tables
         self.free_engines, self.flusher = queue.Queue(), ThreadPoolExecutor(max_workers=1)
         self.counts = np.where(plan.kind[items] == 2, plan.n_pred[items] if plan.predict else 0, 0).astype(np.int64)
 
@@ -1826,11 +1629,7 @@ class _ShardRunner:
                 r = eng_.sgpr_fit_predict_batch(z_off=pk["z_off"], Z=pk["Z"], theta0=p.theta0[ids], dtype="f64", **kw)
             else:
                 if self.oi.cv is not None:
-                    kw["cv_fold"] = pk["cv_fold"]
-                if self.oi.cv_refit is not None:
-                    kw["cv_refit"] = dict(self.oi.cv_refit, recentre=bool(pf.local_mean), min_obs=self.oi._cv_min_obs)
-                if self.oi.cv_joint:
-                    kw["cv_joint"] = True
+                    kw.update(LC.engine_kw(self.oi.cv, pk["cv_fold"], pf.local_mean, p.min_obs))
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
                                            **kw, **({"full_cov": True} if pf.full_cov else {}))
             t1 = time.perf_counter()
@@ -1857,35 +1656,8 @@ class _ShardRunner:
         fixed[loc_ids, H + _N_ITER] = r.n_iter if getattr(r, "n_iter", None) is not None else np.nan
         fixed[loc_ids, H + _SECONDS] = call_s / len(ids)
         fixed[loc_ids, H + _OBS_MEAN] = pk["mean"]
-        if self.oi.cv is not None:
-            cvr, skp = self.open_cv[wi]
-            cv3 = np.stack([np.asarray(r.cv_mean, dtype=np.float64), np.asarray(r.cv_f_var, dtype=np.float64),
-                            np.asarray(r.cv_y_var, dtype=np.float64)], axis=1)
-            o_off = pk["o_off"]
-            for kk, j in enumerate(loc_ids):
-                cvr[j] = cv3[o_off[kk]:o_off[kk + 1]]
-            skp[loc_ids] = pk["cv_skipped"]
-            if self.oi.cv_joint:
-                cvf, lab, f_off = self.open_cvf[wi], pk["cv_fold"], r.cv_fold_off
-                for kk, j in enumerate(loc_ids):
-                    lt = lab[o_off[kk]:o_off[kk + 1]]
-                    # folds ascend with the label: np.unique's order
-                    codes, pos, inv, n = np.unique(lt[lt >= 0], return_index=True, return_inverse=True, return_counts=True)
-                    row_fold = np.full(len(lt), -1, dtype=np.int64)
-                    row_fold[lt >= 0] = inv.reshape(-1)
-                    cvf[j] = (np.column_stack([np.flatnonzero(lt >= 0)[pos] if len(pos) else np.zeros(0), n,
-                                               r.cv_lpd[f_off[kk]:f_off[kk + 1]]]), row_fold)
-            if self.oi.cv_refit is not None:
-                cvp, lab, f_off = self.open_cvp[wi], pk["cv_fold"], r.cv_fold_off
-                per_fold = np.column_stack([r.cv_theta, r.cv_nll, r.cv_status, r.cv_n_obs, r.cv_shift, np.zeros(len(r.cv_nll))])
-                for kk, j in enumerate(loc_ids):
-                    lt = lab[o_off[kk]:o_off[kk + 1]]
-                    rows_f = per_fold[f_off[kk]:f_off[kk + 1]]
-                    # folds ascend with the label: np.unique's order; the first row of each names the fold's `by` values
-                    rows_f[:, H + 4] = np.unique(np.where(lt >= 0, lt, np.iinfo(np.int32).max), return_index=True)[1][:len(rows_f)]
-                    cvp[j] = rows_f
-                    not_fitted = rows_f[:, H + 1] == 4
-                    skp[j] += int((len(lt) - rows_f[not_fitted, H + 2]).sum())
+        if self.cv is not None:
+            self.cv.take(wi, len(self.waves[wi]), loc_ids, pk, r)
         if p.predict:
             pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
                            np.asarray(r.y_var, dtype=np.float64)], axis=1)
@@ -1913,9 +1685,6 @@ class _ShardRunner:
         if wi not in self.open:
             n = len(self.waves[wi])
             self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
-            self.open_cv[wi] = ([np.zeros((0, 3))] * n, np.zeros(n, dtype=np.int64))
-            self.open_cvp[wi] = [np.zeros((0, self.H + 5))] * n
-            self.open_cvf[wi] = [(np.zeros((0, 3)), np.zeros(0, dtype=np.int64))] * n
         return self.open[wi]
 
     def _close_waves_to(self, w):
@@ -1935,18 +1704,8 @@ class _ShardRunner:
         # built (after the flush is queued) only where it is returned -- the only wave of a run
         lazy = bool(pieces) and not p.want_cov
         tables = oi._tables(p, items, fixed, pred_cat, cov_cat, with_preds=not lazy)
-        cvr, skp = self.open_cv.pop(wi)
-        cvp = self.open_cvp.pop(wi)
-        cvf = self.open_cvf.pop(wi)
-        if oi.cv is not None:
-            self.cv_frames.append(oi._cv_frame(p, items, cvr, fixed[:, self.H + _OBS_MEAN]))
-            self.cv_pos.append(oi._cv_positions(p, items, cvr))
-            if oi.cv_refit is not None:
-                self.cvp_frames.append(oi._cv_params_frame(p, items, cvp, fixed[:, self.H + _OBS_MEAN]))
-            if oi.cv_joint:
-                self.cvf_frames.append(oi._cv_folds_frame(p, items, cvf, cvr, fixed[:, self.H + _OBS_MEAN]))
-            self.cv_skipped = np.concatenate([self.cv_skipped, skp])
-            oi._cv_tables(p, tables, items, self.cv_frames[-1:], skp, self.cvp_frames[-1:], self.cvf_frames[-1:])
+        if self.cv is not None:
+            self.cv.close_wave(wi, items, fixed[:, self.H + _OBS_MEAN], tables)
         oi.timings["tables_s"] += time.perf_counter() - tt
         tf = time.perf_counter()
         # commit: these experts are done.  The parts are written by the writer thread while the next wave runs (one writer,

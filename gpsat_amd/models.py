@@ -494,11 +494,12 @@ class HipGPRModel:
     @staticmethod
     def _joint_folds(labels, lpd):
         """The per-fold arrays of ``joint=True``: folds in ascending code, as the engine numbers them."""
-        codes, sizes = np.unique(labels[labels >= 0], return_counts=True)
-        if len(codes) != len(lpd):
+        from .local_cv import fold_layout
+        lay = fold_layout(labels)
+        if len(lay.codes) != len(lpd):
             from .engine import GpsatError
-            raise GpsatError(f"cross_validate(joint=True): {len(codes)} folds counted here, {len(lpd)} by the engine")
-        return {"fold": codes.astype(np.int32), "fold_size": sizes.astype(np.int64), "lpd": np.asarray(lpd, dtype=np.float64)}
+            raise GpsatError(f"cross_validate(joint=True): {len(lay.codes)} folds counted here, {len(lpd)} by the engine")
+        return {"fold": lay.codes.astype(np.int32), "fold_size": lay.size, "lpd": np.asarray(lpd, dtype=np.float64)}
 
 
     def _cross_validate_refit(self, fold, max_iter=10_000, optimiser="lbfgs", joint=False, **kw):
