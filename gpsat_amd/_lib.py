@@ -82,6 +82,21 @@ class GpsatCvJoint(C.Structure):
     _fields_ = [("fold_off", C.c_void_p), ("fold_lpd", C.c_void_p), ("reserved", C.c_int32 * 8)]
 
 
+PROJECT_IDS = {"forward": 0, "inverse": 1}      # GPSAT_PROJECT_*
+TRACK_MODES = {"cut": 0, "runs": 1, "given": 2}             # GPSAT_TRACK_*
+
+
+class GpsatProject(C.Structure):
+    _fields_ = [("n", C.c_int64), ("direction", C.c_int32), ("memory", C.c_int32), ("lon_0", C.c_double), ("lat_0", C.c_double),
+                ("in0", C.c_void_p), ("in1", C.c_void_p), ("out0", C.c_void_p), ("out1", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
+class GpsatTrack(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_cols", C.c_int32), ("memory", C.c_int32), ("cols", C.c_void_p * 3), ("group", C.c_void_p),
+                ("cut_off", C.c_double), ("start_track", C.c_int32), ("mode", C.c_int32), ("out_delta", C.c_void_p),
+                ("out_track", C.c_void_p), ("out_order", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
 CV_START_IDS = {"theta0": 0, "full": 1}
 
 SEL_MAXCRIT = 4
@@ -169,6 +184,8 @@ SIGNATURES = {
     "gpsat_bin_batch": (_I, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _D, _I32, _P, _D, _U32, _I64, _P, _P, _P], False),
     "gpsat_glue_keyed_batch": (_I, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _D, _P, _D, _I64, C.POINTER(_I64), _P, _P, _P], False),
     "gpsat_glue_keyed_timing": (_I, [_P, _P], False),
+    "gpsat_project_batch": (_I, [_P, C.POINTER(GpsatProject)], False),
+    "gpsat_track_batch": (_I, [_P, C.POINTER(GpsatTrack)], False),
     # the entry points of the variant table: (handle, batch, extension struct); the sparse one has been there since ABI 4
     **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(st)], name == "gpsat_sgpr_fit_predict_batch") for name, st in _EXT.items()},
     # the joint density per fold: the cv row's call with its struct, and gpsat_cv_joint behind it

@@ -15,6 +15,8 @@
 //   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
 //   gpsat_glue_keyed_batch (gpsat_glue_plan.h): check -> key range, layout -> stage -> sort, run heads -> read the group count ->
 //     reduce -> fetch.
+//   gpsat_project_batch / gpsat_track_batch (gpsat_prep_plan.h): check -> constants / layout -> stage (host mode) -> kernels
+//     (tracks with groups: keys, the keyed glue's sort and run heads) -> fetch (host mode).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -33,6 +35,7 @@
 #include "gpsat_select_plan.h"
 #include "gpsat_bin_plan.h"
 #include "gpsat_glue_plan.h"
+#include "gpsat_prep_plan.h"
 
 namespace {
 
@@ -135,6 +138,7 @@ struct gpsat_handle : HandleQueue {
         double ms[3] = {0.0, 0.0, 0.0};
         ~GlueBufs() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     } glue;
+    struct PrepBufs { DevBuf in, keys, rows, runs, tmp, out; } prep;         // gpsat_project_batch / gpsat_track_batch (layout: gpsat_prep_plan.h)
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
@@ -1660,6 +1664,128 @@ int gpsat_glue_keyed_timing(gpsat_handle* h, double* ms) {
     if (!h || !ms) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_timing: NULL argument");
     for (int i = 0; i < 3; ++i) ms[i] = h->glue.ms[i];
     return GPSAT_OK;
+}
+
+// check (gpsat_prep_plan.h) -> constants -> stage (host mode) -> kernel -> fetch (host mode)
+int gpsat_project_batch(gpsat_handle* h, const gpsat_project* p) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_project_batch: handle is NULL");
+    char why[160];
+    int rc;
+    if ((rc = gpsat::check_project(p, why, sizeof(why)))) return fail(rc, why);
+    if (p->n == 0) return GPSAT_OK;
+    const gpsat::ProjConst pc = gpsat::proj_const();
+    if ((rc = begin_call(h))) return rc;
+    const size_t nb = (size_t)p->n * sizeof(double);
+    const bool host = p->memory == GPSAT_MEM_HOST;
+    gpsat::ProjectArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = p->n; a.lon_0 = p->lon_0;
+    a.a = pc.a; a.e = pc.e; a.e2 = pc.e2; a.one_m_e2 = pc.one_m_e2; a.inv_2e = pc.inv_2e; a.qp = pc.qp; a.qp_lo = pc.qp_lo;
+    a.in0 = p->in0; a.in1 = p->in1; a.out0 = p->out0; a.out1 = p->out1;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (host) {
+        if ((rc = h->prep.in.reserve(2 * nb))) return rc;
+        if ((rc = h->prep.out.reserve(2 * nb))) return rc;
+        double* d_in = static_cast<double*>(h->prep.in.p);
+        double* d_out = static_cast<double*>(h->prep.out.p);
+        HIP_TRY(hipMemcpyAsync(d_in, p->in0, nb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_in + p->n, p->in1, nb, hipMemcpyHostToDevice, h->stream));
+        a.in0 = d_in; a.in1 = d_in + p->n; a.out0 = d_out; a.out1 = d_out + p->n;
+    }
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(gpsat::launch_project(a, p->direction == GPSAT_PROJECT_FORWARD, p->lat_0 < 0.0, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(p->out0, a.out0, nb, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(p->out1, a.out1, nb, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return record_timing(h);
+}
+
+// check (gpsat_prep_plan.h) -> layout -> stage (host mode) -> with groups: keys, sort, run heads (the keyed glue's) -> distances
+// and flags, scan -> fetch (host mode)
+int gpsat_track_batch(gpsat_handle* h, const gpsat_track* t) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_track_batch: handle is NULL");
+    char why[160];
+    int rc;
+    unsigned long long sentinel = 0;
+    if ((rc = gpsat::check_track(t, &sentinel, why, sizeof(why)))) return fail(rc, why);
+    if (t->n == 0) return GPSAT_OK;
+    const bool host = t->memory == GPSAT_MEM_HOST, grouped = t->group != nullptr;
+    const gpsat::TrackLayout l = gpsat::track_layout(t->n, t->n_cols, grouped, host, gpsat::prep_scan_block());
+    if ((rc = begin_call(h))) return rc;
+    gpsat_handle::PrepBufs& pb = h->prep;
+    if ((rc = pb.in.reserve(std::max<size_t>(l.in_bytes, 16)))) return rc;
+    if ((rc = pb.out.reserve(l.out_bytes))) return rc;
+    if (grouped) {
+        if ((rc = pb.keys.reserve(l.keys_bytes))) return rc;
+        if ((rc = pb.rows.reserve(l.rows_bytes))) return rc;
+        if ((rc = pb.runs.reserve(l.runs_bytes))) return rc;
+    }
+    const size_t nN = (size_t)t->n;
+    char* d_in = static_cast<char*>(pb.in.p);
+    char* d_out = static_cast<char*>(pb.out.p);
+    gpsat::TrackArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = t->n; a.n_cols = t->n_cols; a.mode = t->mode;
+    a.cut_off = t->cut_off; a.start_track = t->start_track;
+    const int32_t* d_group = t->group;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (host) {
+        for (int c = 0; c < t->n_cols; ++c) {
+            double* d_c = reinterpret_cast<double*>(d_in + l.in_cols) + (size_t)c * nN;
+            HIP_TRY(hipMemcpyAsync(d_c, t->cols[c], nN * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            a.cols[c] = d_c;
+        }
+        if (grouped) {
+            HIP_TRY(hipMemcpyAsync(d_in + l.in_group, t->group, nN * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            d_group = reinterpret_cast<const int32_t*>(d_in + l.in_group);
+        }
+        a.delta = reinterpret_cast<double*>(d_out);
+        a.track = reinterpret_cast<int*>(d_out + l.out_track);
+        a.order = reinterpret_cast<int*>(d_out + l.out_order);
+    } else {
+        for (int c = 0; c < t->n_cols; ++c) a.cols[c] = t->cols[c];
+        a.delta = t->out_delta; a.track = t->out_track; a.order = t->out_order;
+    }
+    a.block_sums = reinterpret_cast<int*>(d_out + l.out_sums);
+    if (grouped) {
+        gpsat::GlueKeyedArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.R = t->n; g.sentinel = sentinel;
+        g.key = reinterpret_cast<const long long*>(d_in + l.in_key);
+        g.keys = static_cast<unsigned long long*>(pb.keys.p); g.keys_sorted = g.keys + nN;
+        g.rows = static_cast<unsigned*>(pb.rows.p); g.perm = g.rows + nN;
+        char* d_runs = static_cast<char*>(pb.runs.p);
+        g.starts = reinterpret_cast<unsigned*>(d_runs);
+        g.n_groups = reinterpret_cast<long long*>(d_runs + l.runs_n_groups);
+        g.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
+        g.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+        // the kernel time starts in front of the keys, once the sort's scratch is there
+        if ((rc = run_with_temp(h, pb.tmp, "glue_keyed_sort", h->ev[1], [&](void* temp, size_t& tb) {
+                if (temp) {
+                    const hipError_t e = gpsat::launch_track_keys(t->n, d_group, reinterpret_cast<long long*>(d_in + l.in_key), h->stream);
+                    if (e != hipSuccess) return e;
+                }
+                return gpsat::glue_keyed_sort(g, temp, tb, nullptr, h->stream);
+            })))
+            return rc;
+        a.perm = g.perm; a.heads = g.flags; a.n_valid = g.n_groups + 1;
+    } else {
+        HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    }
+    HIP_TRY(gpsat::launch_track(a, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    if (host) {
+        if (t->mode != GPSAT_TRACK_RUNS) HIP_TRY(hipMemcpyAsync(t->out_delta, a.delta, nN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(t->out_track, a.track, nN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(t->out_order, a.order, nN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return record_timing(h);
 }
 
 #ifdef GPSAT_PROFILE

@@ -282,6 +282,37 @@ hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_byte
 hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream);
 int glue_keyed_team();                // the team width of the product
 
+// raw rows to x / y and track numbers (gpsat_prep.hip); device pointers.  The scalars come from gpsat_prep_plan.h.
+struct ProjectArgs {
+    long long n;                      // rows (< 2^31)
+    const double *in0, *in1;          // forward: lon, lat (degrees); inverse: x, y (metres)
+    double *out0, *out1;              // forward: x, y; inverse: lon, lat
+    double lon_0;                     // degrees
+    double a, e, e2, one_m_e2, inv_2e, qp;        // WGS84: semi-major axis, eccentricity, e^2, 1 - e^2, 1 / (2e), q(90 degrees)
+    double qp_lo;                     // qp + qp_lo: q(90 degrees) to twice the precision (the inverse beyond the equator)
+};
+hipError_t launch_project(const ProjectArgs& a, bool forward, bool south, hipStream_t stream);
+
+struct TrackArgs {
+    long long n;                      // rows (< 2^31)
+    int n_cols, mode;                 // columns of the distance; GPSAT_TRACK_*: 0 cut, 1 runs, 2 given
+    const double* cols[3];            // [n] in SOURCE order
+    const unsigned* perm;             // [n] source row of every taken row, or nullptr: the rows as they are
+    const unsigned char* heads;       // [n] 1 at the first taken row of every group (run heads of the sort), or nullptr: one group
+    const long long* n_valid;         // [1] taken rows that are in a group (the others follow them), or nullptr: all
+    double cut_off;
+    int start_track;
+    double* delta;                    // [n] out, or nullptr (runs only)
+    int* track;                       // [n] out; between the passes: what the scan adds up
+    int* order;                       // [n] out
+    int* block_sums;                  // [prep_scan_blocks(n)] scratch of the scan
+};
+int prep_scan_block();                // B: rows per block of the three-pass scan
+// int32 group codes as the 64-bit keys glue_keyed_sort takes (negative: in no group)
+hipError_t launch_track_keys(long long n, const int* group, long long* key, hipStream_t stream);
+// distances and flags, block sums, their scan, the scan applied: track[] and order[] final
+hipError_t launch_track(const TrackArgs& a, hipStream_t stream);
+
 // sparse GP experts (gpsat_sgpr.hip, fp64 only); device pointers.  One workgroup per tile from an atomic queue.
 struct SgprArgs {
     int T, kernel, optimiser, max_iter, max_ls, Mmax;

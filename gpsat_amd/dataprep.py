@@ -260,6 +260,73 @@ class DataPrep:
         return xr.Dataset(data, coords=coords)
 
     @staticmethod
+    def assign_tracks(df, sort_by, get_track_by=None, delta_measure="dr", cut_off=600_000, start_track=0,
+                      add_by_track_date=False, lon_col="lon", lat_col="lat", lon_0=0, lat_0=90, datetime_col="datetime",
+                      engine=None):
+        """Raw ``lon``, ``lat``, ``datetime`` rows to ``t``, ``x``, ``y``, ``dr``, ``dt`` and a ``track`` number: the body of
+        the reference's ``TrackId`` (examples/generate_track_id.py: ``add_xyt_columns`` + ``add_tracks``) without its files and
+        plots.  ``t`` is the time in ms; ``x``, ``y`` the EASE2 projection (``Engine.project_batch``); the rows are sorted by
+        ``sort_by``; within every value of ``get_track_by`` (one column; None: the whole frame) ``dr`` / ``dt`` are the
+        distance in space / time to the row before and ``track`` goes up by one where ``delta_measure`` exceeds
+        ``cut_off``, each group starting one above the last one's largest track (``Engine.track_batch``, one call for all
+        groups).  ``add_by_track_date`` adds ``start_date`` (the day of a track's first row) and ``track_start`` (the
+        track's number among its group's tracks of that day); the per-track minimum and the merge run on the host.
+
+        The rows come back in the reference's order: groups in order of first appearance, the sorted order inside a group;
+        rows whose group value is null are dropped (the reference's ``==`` selects them for no group).  A copy is returned,
+        ``df`` is left as it was.  With ``add_by_track_date`` the index is a new RangeIndex (the reference's merge makes
+        one per group)."""
+        assert sort_by is not None
+        assert isinstance(sort_by, (list, tuple, str)), f"sort_by should be str, list or tuple, got: {type(sort_by)}"
+        assert isinstance(add_by_track_date, bool)
+        assert isinstance(cut_off, (int, float))
+        assert delta_measure in ['dt', 'dr'], f"delta_measure: '{delta_measure}', must in ['dt', 'dr']"
+        assert datetime_col in df, f"'{datetime_col}' is not in data"
+        for c in [lon_col, lat_col]:
+            assert c in df, f"column: '{c}' is not in data"
+        if isinstance(get_track_by, (list, tuple)):
+            if len(get_track_by) != 1:
+                raise NotImplementedError("get_track_by takes one column (the reference's df[get_track_by].unique() does too)")
+            get_track_by = get_track_by[0]
+        if get_track_by is not None:
+            assert get_track_by in df, f"get_track_by: '{get_track_by}' is not in data"
+        eng = engine if engine is not None else _engine()
+        df = df.copy()
+        df['t'] = df[datetime_col].values.astype("datetime64[ms]").astype(float)
+        x, y = eng.project_batch(df[lon_col].to_numpy(dtype=np.float64), df[lat_col].to_numpy(dtype=np.float64), "forward",
+                                 lon_0, lat_0)
+        df['x'], df['y'] = np.asarray(x), np.asarray(y)
+        df.sort_values(sort_by, inplace=True)
+        codes = None
+        if get_track_by is not None:
+            # numbered in order of first appearance, null -> -1: df[get_track_by].unique() without its null entry
+            codes = pd.factorize(df[get_track_by].to_numpy())[0].astype(np.int32)
+        cols = {"dr": [df['x'].to_numpy(dtype=np.float64), df['y'].to_numpy(dtype=np.float64)],
+                "dt": [df['t'].to_numpy(dtype=np.float64)]}
+        other = "dt" if delta_measure == "dr" else "dr"
+        delta, track, order = eng.track_batch(cols[delta_measure], group=codes, cut_off=cut_off, start_track=start_track)
+        delta2, _, order2 = eng.track_batch(cols[other], group=codes, cut_off=cut_off, start_track=start_track)
+        order = np.asarray(order)
+        assert np.array_equal(order, np.asarray(order2))
+        n_in = len(order) if codes is None else int((codes >= 0).sum())
+        out = df.iloc[order[:n_in]].copy()
+        out[delta_measure] = np.asarray(delta)[:n_in]
+        out[other] = np.asarray(delta2)[:n_in]
+        out = out[[c for c in out.columns if c not in ("dr", "dt")] + ["dr", "dt"]]
+        out['track'] = np.asarray(track)[:n_in].astype(int)
+        if add_by_track_date:
+            # per track, not per row: the first row of every track on the host, the counter on the device
+            first = np.flatnonzero(np.diff(out['track'].to_numpy(), prepend=start_track - 1) != 0)
+            tsd = out.groupby('track', sort=True)[datetime_col].min().reset_index()
+            tsd.rename(columns={datetime_col: "start_date"}, inplace=True)
+            tsd['start_date'] = tsd['start_date'].values.astype("datetime64[D]")
+            tgroup = None if codes is None else codes[order[:n_in]][first]
+            _, run, _ = eng.track_batch([tsd['start_date'].values.astype('int64').astype(np.float64)], group=tgroup, mode="runs")
+            tsd['track_start'] = np.asarray(run).astype(int)
+            out = out.merge(tsd, on=['track'], how='left')
+        return out
+
+    @staticmethod
     def bin_data(df, x_range=None, y_range=None, grid_res=None, x_col="x", y_col="y", val_col=None,
                  bin_statistic="mean", bin_2d=True, return_bin_center=True):
         """Bin ``val_col`` of ``df`` on a regular grid: returns ``(binned, (x_out, y_out))``, or ``(binned, x_out)`` when

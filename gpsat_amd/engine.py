@@ -790,6 +790,96 @@ class Engine:
         self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
         return BinResult(keys=keys, gid=g, iy=iy, ix=ix, stats=stats, kernel_ms=km.value, total_ms=tm.value)
 
+    def _prep_inputs(self, name, arrays, group=None):
+        """The [n] fp64 columns of a project_batch / track_batch call (and the int32 group codes) as the library takes them:
+        (device_mode, columns, group, n).  NumPy arrays are laid out contiguously; device tensors are checked, not copied."""
+        if not hasattr(self._lib, name):
+            raise GpsatError(f"{L.LIB_PATH} does not export {name}: rebuild the library (there is no host fallback)")
+        device_mode = not isinstance(arrays[0], np.ndarray) and hasattr(arrays[0], "data_ptr")
+        if device_mode:
+            import torch
+            n = arrays[0].numel()
+            for k, t_ in enumerate(arrays):
+                self._check_tensor(f"{name}: column {k}", t_, "f64", numel=n)
+            if group is not None:
+                if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or not group.is_contiguous() or \
+                        group.device != arrays[0].device or group.numel() != n:
+                    raise GpsatError(f"{name}: group must be a contiguous int32 tensor of {n} codes beside the columns")
+            torch.cuda.current_stream(arrays[0].device).synchronize()      # inputs must be complete before our stream reads them
+        else:
+            arrays = [np.ascontiguousarray(a_, dtype=np.float64).reshape(-1) for a_ in arrays]
+            n = arrays[0].shape[0]
+            if any(a_.shape != (n,) for a_ in arrays):
+                raise GpsatError(f"{name}: columns of {[a_.shape[0] for a_ in arrays]} rows")
+            if group is not None:
+                group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+                if group.shape != (n,):
+                    raise GpsatError(f"{name}: {group.shape[0]} group codes for {n} rows")
+        if n > 2**31 - 1:
+            raise GpsatError(f"{name} takes at most 2^31 - 1 rows per call, got {n}")
+        return device_mode, list(arrays), group, n
+
+    def _prep_timing(self):
+        km, tm = C.c_double(0.0), C.c_double(0.0)
+        self._lib.gpsat_last_timing(self._h, C.byref(km), C.byref(tm))
+        self.last_prep_ms = (km.value, tm.value)
+
+    def project_batch(self, in0, in1, direction="forward", lon_0=0.0, lat_0=90.0):
+        """Lambert azimuthal equal-area projection on WGS84, polar aspects (gpsat_project_batch).  direction "forward":
+        in0, in1 = lon, lat in degrees -> (x, y) in metres; "inverse": x, y -> (lon, lat).  in0, in1: [n] NumPy arrays or
+        fp64 device tensors; the outputs are of the same kind.  (kernel, total) ms of the call: ``last_prep_ms``."""
+        if direction not in L.PROJECT_IDS:
+            raise GpsatError(f"direction {direction!r}: choose from {list(L.PROJECT_IDS)}")
+        dev, (a0, a1), _, n = self._prep_inputs("gpsat_project_batch", [in0, in1])
+        if dev:
+            import torch
+            o0, o1 = torch.empty(max(n, 1), dtype=a0.dtype, device=a0.device), torch.empty(max(n, 1), dtype=a0.dtype, device=a0.device)
+        else:
+            o0, o1 = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        p = L.GpsatProject(n=n, direction=L.PROJECT_IDS[direction], memory=L.MEM_DEVICE if dev else L.MEM_HOST,
+                           lon_0=float(lon_0), lat_0=float(lat_0), in0=_bulk_ptr(a0), in1=_bulk_ptr(a1), out0=_bulk_ptr(o0),
+                           out1=_bulk_ptr(o1))
+        rc = self._lib.gpsat_project_batch(self._h, C.byref(p))
+        if rc != 0:
+            raise GpsatError(f"gpsat_project_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        self._prep_timing()
+        return o0[:n], o1[:n]
+
+    def track_batch(self, cols, group=None, cut_off=0.0, start_track=0, mode="cut"):
+        """Distance to the previous row of the same group and the track number of every row (gpsat_track_batch).
+        cols: 1..3 columns [n] (NumPy or fp64 device tensors); group: int32 codes [n] in order of first appearance, -1 for a
+        row in no group, or None.  The rows are taken group by group, in the order given inside a group.  Returns
+        (delta, track, order), all in the order taken: order[i] is the source row taken i-th; rows of code -1 come last with
+        delta NaN and track -1.  mode "cut": track = start_track + the flags so far (delta > cut_off, or the first row of a
+        later group); mode "given": the same on distances that are there already (cols[0] is delta, a group's first row
+        included); mode "runs": track = rows since cols[0] last changed (delta is None)."""
+        if mode not in L.TRACK_MODES:
+            raise GpsatError(f"mode {mode!r}: choose from {list(L.TRACK_MODES)}")
+        cols = list(cols)
+        if not 1 <= len(cols) <= (3 if mode == "cut" else 1):
+            raise GpsatError(f"track_batch takes 1..3 columns (mode 'runs' and 'given': one), got {len(cols)}")
+        dev, cols, group, n = self._prep_inputs("gpsat_track_batch", cols, group)
+        runs = mode == "runs"
+        if dev:
+            import torch
+            where = dict(device=cols[0].device)
+            delta = None if runs else torch.empty(max(n, 1), dtype=torch.float64, **where)
+            track, order = torch.empty(max(n, 1), dtype=torch.int32, **where), torch.empty(max(n, 1), dtype=torch.int32, **where)
+        else:
+            delta = None if runs else np.empty(n, dtype=np.float64)
+            track, order = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        t = L.GpsatTrack(n=n, n_cols=len(cols), memory=L.MEM_DEVICE if dev else L.MEM_HOST,
+                         group=None if group is None else _bulk_ptr(group), cut_off=float(cut_off), start_track=int(start_track),
+                         mode=L.TRACK_MODES[mode], out_delta=None if runs else _bulk_ptr(delta), out_track=_bulk_ptr(track),
+                         out_order=_bulk_ptr(order))
+        for k, c_ in enumerate(cols):
+            t.cols[k] = c_.data_ptr() if dev else c_.ctypes.data
+        rc = self._lib.gpsat_track_batch(self._h, C.byref(t))
+        if rc != 0:
+            raise GpsatError(f"gpsat_track_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        self._prep_timing()
+        return (None if runs else delta[:n]), track[:n], order[:n]
+
 
 _default_engine = None
 

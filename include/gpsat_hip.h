@@ -552,6 +552,79 @@ int gpsat_bin_batch(gpsat_handle *h, int64_t R, const double *x, const double *y
                     uint32_t stats, int64_t capacity, int64_t *n_cells, int64_t *keys, double *out);
 
 /*
+ * Raw rows to the columns the pipeline starts from (added within ABI 4, check for the symbols): the projection of lon / lat
+ * to EASE2 metres and back, and the track number of every row.  Replaces GPSat.utils.WGS84toEASE2 / EASE2toWGS84 (pyproj,
+ * "+proj=laea +lat_0=.. +lon_0=.. +ellps=WGS84") and diff_distance / guess_track_num / track_num_for_date (numba loops) as
+ * examples/generate_track_id.py TrackId.assign_tracks / add_tracks uses them.
+ *
+ * gpsat_project_batch: Lambert azimuthal equal-area on the WGS84 ellipsoid (a = 6378137, 1/f = 298.257223563), POLAR aspects
+ * only, fp64 (Snyder 3-12, 24-23, 24-25; the inverse solves q(phi) = q by Newton's iteration, Snyder 3-16, to the last bit
+ * instead of PROJ's truncated authalic-latitude series).
+ *   direction GPSAT_PROJECT_FORWARD: in0 = lon, in1 = lat (degrees) -> out0 = x, out1 = y (metres);
+ *   direction GPSAT_PROJECT_INVERSE: in0 = x, in1 = y (metres) -> out0 = lon in (-180, 180], out1 = lat (degrees).
+ *   A NaN in either input gives NaN in both outputs.  The inverse of (0, 0) is (lon_0, lat_0); a point outside the
+ *   projection's disc gives +inf in both outputs.
+ * in0, in1, out0, out1: [n] fp64, host pointers (GPSAT_MEM_HOST) or device pointers (GPSAT_MEM_DEVICE: nothing is copied,
+ * the arrays are not inspected; out may alias in).  GPSAT_EINVAL: lat_0 not +90 / -90, lon_0 not finite, an unknown
+ * direction or memory flag, n < 0 or > 2^31 - 1, a NULL array with n > 0, non-zero reserved words.  n = 0 is valid.
+ */
+#define GPSAT_PROJECT_FORWARD 0
+#define GPSAT_PROJECT_INVERSE 1
+typedef struct gpsat_project {
+    int64_t       n;
+    int32_t       direction;   /* GPSAT_PROJECT_*                         */
+    int32_t       memory;      /* GPSAT_MEM_*                             */
+    double        lon_0;       /* central meridian, degrees               */
+    double        lat_0;       /* +90 or -90                              */
+    const double *in0, *in1;   /* [n] */
+    double       *out0, *out1; /* [n] */
+    int32_t       reserved[8]; /* 0 */
+} gpsat_project;
+int gpsat_project_batch(gpsat_handle *h, const gpsat_project *p);
+
+/*
+ * gpsat_track_batch: the rows are taken group by group (groups in ascending code, a group's rows in the order given: a
+ * stable sort), every row gets the distance to its predecessor IN ITS GROUP, and
+ *   mode GPSAT_TRACK_CUT  : track = start_track + the number of flags up to and including the row, where a row is flagged
+ *                           when delta > cut_off (NaN compares false) or when it is the first row of a group other than the
+ *                           first: guess_track_num per group with start_track = the previous group's max + 1, in one pass;
+ *   mode GPSAT_TRACK_RUNS : out_track = rows since the last row whose cols[0] differed from its predecessor's (!=, so a NaN
+ *                           restarts) or that began a group: track_num_for_date.  n_cols must be 1; cut_off and start_track
+ *                           are not read; out_delta may be NULL.
+ *   mode GPSAT_TRACK_GIVEN: as GPSAT_TRACK_CUT on distances that are there already: delta = cols[0] itself, a group's first
+ *                           row included (guess_track_num on a column of diff_distance).  n_cols must be 1.
+ * cols     : n_cols (1..3) arrays [n] fp64; delta = sqrt(sum_c (cols[c][i] - cols[c][i-1])^2): difference, square, sum from
+ *            the left, root, none of them fused; NaN for the first row of a group (diff_distance(x, p=2, k=1)).
+ * group    : [n] int32 codes >= 0 numbered in order of first appearance (pd.factorize), -1: the row is in no group; NULL: one
+ *            group.  Rows of code -1 come last in out_order, with delta NaN and track -1.
+ * Outputs, in the order the rows were TAKEN: out_order[i] is the source row taken i-th, out_delta[i] and out_track[i] are
+ * its values.  Without groups out_order is 0, 1, 2, ...
+ * Host or device pointers by `memory`, as gpsat_project.  GPSAT_EINVAL: n_cols outside 1..3, cut_off not finite,
+ * start_track < 0 or start_track + n > 2^31 - 1, an unknown mode or memory flag, n < 0 or > 2^31 - 1, a NULL array with
+ * n > 0, non-zero reserved words, and in host mode a group code below -1 (the message names the row).  The results are
+ * integers and exact doubles of fixed operation order: a second call returns the same bytes.
+ * gpsat_last_timing covers both calls: kernel_ms = the kernels (with the sort), total_ms = with the copies of host mode.
+ */
+#define GPSAT_TRACK_CUT  0
+#define GPSAT_TRACK_RUNS 1
+#define GPSAT_TRACK_GIVEN 2
+typedef struct gpsat_track {
+    int64_t        n;
+    int32_t        n_cols;      /* 1..3 */
+    int32_t        memory;      /* GPSAT_MEM_* */
+    const double  *cols[3];     /* n_cols arrays [n] */
+    const int32_t *group;       /* [n] or NULL */
+    double         cut_off;
+    int32_t        start_track;
+    int32_t        mode;        /* GPSAT_TRACK_* */
+    double        *out_delta;   /* [n] */
+    int32_t       *out_track;   /* [n] */
+    int32_t       *out_order;   /* [n] */
+    int32_t        reserved[8]; /* 0 */
+} gpsat_track;
+int gpsat_track_batch(gpsat_handle *h, const gpsat_track *t);
+
+/*
  * Timing of the last gpsat_fit_predict_batch on this handle, measured with HIP events on the
  * handle's stream: kernel_ms = the persistent tile kernel alone, total_ms = H2D + kernel + D2H.
  */
