@@ -65,6 +65,10 @@ class GpsatNoise(C.Structure):
     _fields_ = [("obs_var", C.c_void_p), ("reserved", C.c_int32 * 8)]
 
 
+class GpsatPredGrad(C.Structure):
+    _fields_ = [("f_grad", C.c_void_p), ("f_grad_var", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
 class GpsatCv(C.Structure):
     _fields_ = [("fold", C.c_void_p), ("cv_mean", C.c_void_p), ("cv_f_var", C.c_void_p), ("cv_y_var", C.c_void_p),
                 ("reserved", C.c_int32 * 8)]
@@ -192,6 +196,8 @@ SIGNATURES = {
     **{name: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(_EXT[variants.VARIANTS[row].entry]),
                    C.POINTER(globals()[variants.JOINT_STRUCT])], False)
        for row, name in variants.JOINT_ENTRY.items()},
+    # the gradient of the posterior mean: the plain call with gpsat_pred_grad behind the batch
+    variants.PRED_GRAD_ENTRY: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(globals()[variants.PRED_GRAD_STRUCT])], False),
 }
 EXPORTS = list(SIGNATURES)
 OPTIONAL_EXPORTS = [name for name, (_, _, required) in SIGNATURES.items() if not required]

@@ -3,7 +3,7 @@
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
 // Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
 // translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
-//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise / check_pred_grad, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
 //     setup_*, launch, fetch_batch / fetch_cv, record_timing.
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
@@ -123,6 +123,7 @@ struct gpsat_handle : HandleQueue {
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
     DevBuf cvr_cov;                   // refitted cross-validation with the joint density: cov_off, the derived batch's f_cov, sn2, residuals, lpd
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
+    DevBuf pgrad;                     // gpsat_fit_predict_batch_grad, host mode: f_grad, f_grad_var [sumP, D] each
     DevBuf memo;                      // 64 bytes of developer statistics, then the evaluation memo [T][MEMO_WORDS] (fp32 L-BFGS batches)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     // gpsat_select_batch_ex.  gpsat_smooth_batch and gpsat_glue_batch stage their inputs in sel.pts (glue: its segments in
@@ -679,6 +680,7 @@ struct DenseJob {
     const gpsat_cv_joint* cv_joint = nullptr;     // ... and the folds' joint densities (gpsat_fit_predict_batch_cv_joint)
     int mean = GPSAT_MEAN_ZERO;       // GPSAT_MEAN_CONSTANT: gpsat_fit_predict_batch_mean with a trainable constant mean
     const void* obs_var = nullptr;    // gpsat_fit_predict_batch_noise: noise variances per observation, behind gpsat::check_noise
+    const gpsat_pred_grad* pred_grad = nullptr;   // gpsat_fit_predict_batch_grad: the two outputs, behind gpsat::check_pred_grad
     bool ms_on;                       // ms given and the optimiser runs
     BatchDims dims;
     const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
@@ -692,7 +694,8 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     const BatchDims& d = j.dims;
     const bool f64 = b->dtype == GPSAT_F64;
     const gpsat::F64Variant variant = j.cv ? gpsat::CV : b->kernel == GPSAT_KERNEL_RQ ? gpsat::RQ
-                                      : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : j.obs_var ? gpsat::NOISE : gpsat::PLAIN;
+                                      : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : j.obs_var ? gpsat::NOISE
+                                      : j.pred_grad ? gpsat::GRAD : gpsat::PLAIN;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
                            h->num_cu, h->wg_per_cu, solo || variant != gpsat::PLAIN, unsliced, read_dev_knobs()};     // a variant: one workgroup per tile
     gpsat::TilePlan p;
@@ -720,6 +723,21 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if (!launch) return fail(GPSAT_EINVAL, variant == gpsat::CV ? "held-out predictions: no kernel in this build" : "no kernel for this model in this build");
     gpsat::NoiseArgs na;
     na.obs_var = s.obs_var;
+    // the gradient's two outputs: the caller's device memory, or (host mode) the handle's, fetched behind the launch
+    gpsat::GradArgs ga;
+    const size_t grad_bytes = (size_t)d.sumP * b->D * sizeof(double);
+    if (j.pred_grad) {
+        if (b->memory == GPSAT_MEM_HOST) {
+            if ((rc = h->pgrad.reserve(std::max<size_t>(2 * grad_bytes, 16)))) return rc;
+            ga.f_grad = static_cast<double*>(h->pgrad.p);
+            ga.f_grad_var = ga.f_grad + (size_t)d.sumP * b->D;
+        } else if (d.sumP > 0) {
+            ga.f_grad = static_cast<double*>(j.pred_grad->f_grad);
+            ga.f_grad_var = static_cast<double*>(j.pred_grad->f_grad_var);
+        } else {                                      // nothing is written: any valid address will do
+            ga.f_grad = ga.f_grad_var = static_cast<double*>(h->ws.p);
+        }
+    }
     gpsat::CvArgs ca;
     if (j.cv && (rc = stage_cv(h, b, j.cv, j.cv_joint, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
@@ -735,10 +753,14 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     a.prof = static_cast<unsigned long long*>(h->prof.p);
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, p.grid, p.smem, h->stream));
+    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, j.pred_grad ? &ga : nullptr, p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, j.cv_joint, d, ca))) return rc;
+    if (j.pred_grad && b->memory == GPSAT_MEM_HOST && grad_bytes > 0) {
+        HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad, ga.f_grad, grad_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad_var, ga.f_grad_var, grad_bytes, hipMemcpyDeviceToHost, h->stream));
+    }
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 #ifdef GPSAT_PROFILE
@@ -752,7 +774,8 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
 }
 
 int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr,
-                const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr, const gpsat_cv_joint* jt = nullptr) {
+                const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr, const gpsat_cv_joint* jt = nullptr,
+                const gpsat_pred_grad* pg = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
@@ -769,6 +792,11 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
         char why[160];
         if ((rc = gpsat::check_noise(b, nz, why, sizeof(why)))) return fail(rc, why);
         j.obs_var = nz->obs_var;
+    }
+    if (pg) {
+        char why[200];
+        if ((rc = gpsat::check_pred_grad(b, pg, why, sizeof(why)))) return fail(rc, why);
+        j.pred_grad = pg;
     }
     BatchDims& d = j.dims;
     d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
@@ -1215,6 +1243,11 @@ int gpsat_fit_predict_batch_mean(gpsat_handle* h, const gpsat_batch* b, const gp
 int gpsat_fit_predict_batch_noise(gpsat_handle* h, const gpsat_batch* b, const gpsat_noise* nz) {
     if (!nz) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_noise: noise is NULL");
     return fit_predict(h, b, nullptr, nullptr, nullptr, nz);
+}
+
+int gpsat_fit_predict_batch_grad(gpsat_handle* h, const gpsat_batch* b, const gpsat_pred_grad* pg) {
+    if (!pg) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_grad: pred_grad is NULL");
+    return fit_predict(h, b, nullptr, nullptr, nullptr, nullptr, nullptr, pg);
 }
 
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {

@@ -122,6 +122,12 @@ struct CvArgs {
 struct NoiseArgs {
     const double* obs_var = nullptr;  // [sumN] v of K_y = K + sn2 I + diag(v), in the order of y
 };
+// The gradient of the posterior mean at the prediction points and its variance per component (gpsat_fit_predict_batch_grad);
+// device pointers, both [sumP, D] row-major.
+struct GradArgs {
+    double* f_grad = nullptr;
+    double* f_grad_var = nullptr;
+};
 #define GPSAT_MAX_CV_FOLD 256         // largest fold: sum g^2 <= 256 N doubles fits the prediction scratch of a tile's workspace
 
 size_t shared_bytes(int D, int NBmax);
@@ -134,17 +140,18 @@ size_t shared_bytes_f64_w4(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
 // The variants of the fp64 tile loop (the table at the top of gpsat_kernels_f64.hip), launch_tiles_f64[_variant][_w4], one
-// signature: `cv` is null unless the variant is cv, `nz` unless it is noise.  A (D, a.kernel, a.team_size) a variant does not have: hipErrorInvalidValue.
+// signature: `cv` is null unless the variant is cv, `nz` unless it is noise, `gr` unless it is grad.  A (D, a.kernel, a.team_size) a variant does not have: hipErrorInvalidValue.
 //   plain  kernels 0..3, D = 1..4, H = D + 2; teams in the 8-wave build
 //   cv     the same with the held-out phase (gpsat_fit_predict_batch_cv), one workgroup per tile
 //   rq     the RationalQuadratic covariance function: kernel 4, D = 1..3, H = D + 3, one workgroup per tile
 //   mean   a trainable constant mean: kernels 0..3, D = 1..3, H = D + 3 with c last, one workgroup per tile
 //   noise  known noise variances per observation (NoiseArgs): kernels 0..3, D = 1..4, H = D + 2, one workgroup per tile
+//   grad   the gradient of the posterior mean and its variance (GradArgs): kernels 0, 2, 3, D = 1..4, H = D + 2, one workgroup per tile, no f_cov
 // LDS, workspace and state words of every variant are those of the build of the same wave count.
-typedef hipError_t F64Launch(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, int grid, size_t smem, hipStream_t stream);
+typedef hipError_t F64Launch(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, int grid, size_t smem, hipStream_t stream);
 F64Launch launch_tiles_f64, launch_tiles_f64_w4, launch_tiles_f64_cv, launch_tiles_f64_cv_w4;
 F64Launch launch_tiles_f64_rq, launch_tiles_f64_rq_w4, launch_tiles_f64_mean, launch_tiles_f64_mean_w4;
-F64Launch launch_tiles_f64_noise, launch_tiles_f64_noise_w4;
+F64Launch launch_tiles_f64_noise, launch_tiles_f64_noise_w4, launch_tiles_f64_grad, launch_tiles_f64_grad_w4;
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

@@ -18,24 +18,25 @@ struct Build {
     size_t (*workspace_per_wg)(int NBmax, int PCcov);         // floats (fp32 builds) or doubles (fp64 builds)
     int (*state_words)();
     size_t (*pq_floats_per_slot)(int D, int NBmax);           // nullptr: the build has no deferred predictions
-    // the tile loop per F64Variant (`cv`: the held-out variant's arguments, `nz`: the noise variant's, else null); nullptr: the
-    // build has no such variant
-    F64Launch* launch_variant[5];
+    // the tile loop per F64Variant (`cv`: the held-out variant's arguments, `nz`: the noise variant's, `gr`: the gradient
+    // variant's, else null); nullptr: the build has no such variant
+    F64Launch* launch_variant[6];
 };
 enum { BUILD_F32_W4 = 0, BUILD_F32_W8 = 1, BUILD_F64_W8 = 2, BUILD_F64_W4 = 3 };
 // The variants of the fp64 tile loop (gpsat_kernels_f64.hip): held-out predictions, the RationalQuadratic covariance function,
-// a trainable constant mean, known noise variances per observation.  A job is one of them; every one but PLAIN runs one workgroup per tile.
-enum F64Variant { PLAIN = 0, CV = 1, RQ = 2, MEAN = 3, NOISE = 4 };
+// a trainable constant mean, known noise variances per observation, the gradient of the posterior mean at the prediction points.
+// A job is one of them; every one but PLAIN runs one workgroup per tile.
+enum F64Variant { PLAIN = 0, CV = 1, RQ = 2, MEAN = 3, NOISE = 4, GRAD = 5 };
 // the fp32 builds (no variants) behind the same signature
-inline hipError_t launch_f32_w4(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles(D, a, grid, smem, stream); }
-inline hipError_t launch_f32_w8(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles_w8(D, a, grid, smem, stream); }
+inline hipError_t launch_f32_w4(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles(D, a, grid, smem, stream); }
+inline hipError_t launch_f32_w8(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles_w8(D, a, grid, smem, stream); }
 const Build builds[4] = {
-    {shared_bytes, workspace_floats_per_wg, state_words, pq_floats_per_slot, {launch_f32_w4, nullptr, nullptr, nullptr, nullptr}},
-    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, nullptr, {launch_f32_w8, nullptr, nullptr, nullptr, nullptr}},
+    {shared_bytes, workspace_floats_per_wg, state_words, pq_floats_per_slot, {launch_f32_w4, nullptr, nullptr, nullptr, nullptr, nullptr}},
+    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, nullptr, {launch_f32_w8, nullptr, nullptr, nullptr, nullptr, nullptr}},
     {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, nullptr,
-     {launch_tiles_f64, launch_tiles_f64_cv, launch_tiles_f64_rq, launch_tiles_f64_mean, launch_tiles_f64_noise}},
+     {launch_tiles_f64, launch_tiles_f64_cv, launch_tiles_f64_rq, launch_tiles_f64_mean, launch_tiles_f64_noise, launch_tiles_f64_grad}},
     {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, nullptr,
-     {launch_tiles_f64_w4, launch_tiles_f64_cv_w4, launch_tiles_f64_rq_w4, launch_tiles_f64_mean_w4, launch_tiles_f64_noise_w4}},
+     {launch_tiles_f64_w4, launch_tiles_f64_cv_w4, launch_tiles_f64_rq_w4, launch_tiles_f64_mean_w4, launch_tiles_f64_noise_w4, launch_tiles_f64_grad_w4}},
 };
 
 // One developer knob (GPSAT_DEBUG_*, read through dev_env() only): whether it is set, and atoi of its text.
@@ -203,6 +204,31 @@ int check_noise(const gpsat_batch* b, const gpsat_noise* nz, char* why, size_t w
                 std::snprintf(why, why_len, "obs_var must be finite and not negative: tile %d, row %lld is %g", t, (long long)(i - b->obs_off[t]), v[i]);
                 return GPSAT_EINVAL;
             }
+    return GPSAT_OK;
+}
+
+// gpsat_fit_predict_batch_grad's own checks (behind check_batch, which has seen T, D, dtype, kernel, the metadata pointers and
+// that pred_off is a valid offset table): a pure function of host data like check_noise, reached by tests through its exported
+// symbol.  GPSAT_OK, or GPSAT_EINVAL with the reason in why[why_len].  The outputs are not dereferenced in either memory mode.
+int check_pred_grad(const gpsat_batch* b, const gpsat_pred_grad* pg, char* why, size_t why_len) {
+    if (why_len > 0) why[0] = 0;
+    if (!pg) { std::snprintf(why, why_len, "gpsat_fit_predict_batch_grad: pred_grad is NULL"); return GPSAT_EINVAL; }
+    for (int i = 0; i < 8; ++i)
+        if (pg->reserved[i] != 0) { std::snprintf(why, why_len, "pred_grad: reserved words must be 0"); return GPSAT_EINVAL; }
+    if (b->dtype != GPSAT_F64) { std::snprintf(why, why_len, "the gradient of the posterior mean (pred_grad) is built for GPSAT_F64 only"); return GPSAT_EINVAL; }
+    if (b->kernel == GPSAT_KERNEL_MATERN12) {
+        std::snprintf(why, why_len, "the gradient of the posterior mean (pred_grad) does not exist for GPSAT_KERNEL_MATERN12: the process is not mean-square differentiable");
+        return GPSAT_EINVAL;
+    }
+    if (b->kernel == GPSAT_KERNEL_RQ) { std::snprintf(why, why_len, "the gradient of the posterior mean (pred_grad) is not built for GPSAT_KERNEL_RQ"); return GPSAT_EINVAL; }
+    if (b->cov_off || b->f_cov) {
+        std::snprintf(why, why_len, "pred_grad and the full covariance cannot be asked for in the same call: cov_off / f_cov must be NULL");
+        return GPSAT_EINVAL;
+    }
+    if (b->pred_off[b->T] > 0) {
+        if (!pg->f_grad) { std::snprintf(why, why_len, "pred_grad: f_grad is NULL"); return GPSAT_EINVAL; }
+        if (!pg->f_grad_var) { std::snprintf(why, why_len, "pred_grad: f_grad_var is NULL"); return GPSAT_EINVAL; }
+    }
     return GPSAT_OK;
 }
 

@@ -48,6 +48,10 @@ class BatchResult:
     cv_label: np.ndarray | None = None      # [F]
     # cv_joint (either flavour, with cv_fold_off): the joint log predictive density of every fold, in the units of the tile's y
     cv_lpd: np.ndarray | None = None        # [F] NaN: the fold's rows are NaN, or the fold was not fitted
+    # pred_grad: the gradient of the posterior mean with respect to the prediction point and its posterior variance per
+    # component, [sum P, D] each (numpy / torch as f_mean), in the units of y (y^2) per unit of X; None unless asked for
+    f_grad: object = None
+    f_grad_var: object = None
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -391,7 +395,7 @@ class Engine:
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
                           out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
-                          cv_refit=None, mean=None, obs_var=None, cv_joint=False) -> BatchResult:
+                          cv_refit=None, mean=None, obs_var=None, cv_joint=False, pred_grad=False) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -443,9 +447,24 @@ class Engine:
         are those of the plain call; likelihood_variance is what obs_var does not explain (fix it through ``trainable`` to
         trust obs_var alone) and ``y_var`` = ``f_var`` + likelihood_variance.  fp64 only, D <= 4, with either optimiser.  All
         zeros return the bits of the plain call; None is the plain call.
+        ``pred_grad`` (gpsat_fit_predict_batch_grad): also ``f_grad`` and ``f_grad_var`` [sum P, D], the
+        gradient of the posterior mean with respect to the prediction point, d f*(x*) / dx*_a, and the posterior variance of
+        that derivative, in the units of y (y^2) per unit of X -- numpy arrays or device tensors as ``f_mean`` is.  Every other
+        field has the bits of the call without it.  A tile without observations returns the prior at theta0 (0 and
+        kernel_variance gg(0) / l_a^2, gg(0) = 1 RBF, 3 Matern32, 5/3 Matern52), a tile that is not positive definite NaN.
+        fp64, RBF / Matern32 / Matern52 (Matern12 is not mean-square differentiable), D <= 4, either optimiser; refused beside
+        mean, obs_var, cv_fold / cv_refit, n_starts and full_cov.
         Which of these arguments cannot be combined is the table of gpsat_amd/variants.py: a pairing
         that one library call cannot express is refused here, any other by the library with its own message.
         """
+        if pred_grad:
+            on = {"mean": mean not in (None, "zero"), "noise": obs_var is not None, "cv_refit": cv_refit not in (None, False),
+                  "cv": cv_fold is not None and cv_refit in (None, False), "multistart": n_starts is not None, "full_cov": bool(full_cov),
+                  "rq": kernel in ("RationalQuadratic", L.KERNEL_RQ)}
+            names = {v: k for k, v in L.KERNEL_IDS.items()}
+            why = V.why_refused_pred_grad([k for k in on if on[k]], dtype, kernel if isinstance(kernel, str) else names.get(int(kernel)))
+            if why:
+                raise GpsatError(why)
         asked, refit = self._check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov, cv_joint)
         self._check_widths(asked, kernel, D, theta0=theta0, lo=lo, hi=hi, trainable=trainable)
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, V.n_hyper(D, asked))
@@ -489,6 +508,15 @@ class Engine:
             jt.fold_off, jt.fold_lpd = _ptr(fold_off), _ptr(lpd)
             fields.update(cv_fold_off=fold_off, cv_lpd=lpd)
             args.append(C.byref(jt))
+        if pred_grad:
+            name = V.PRED_GRAD_ENTRY
+            if not hasattr(self._lib, name):
+                raise GpsatError(f"this libgpsat_hip.so has no {name} ({V.PRED_GRAD_LABEL})")
+            go = tuple(_alloc(sumP * D, dtype, beside) for _ in range(2))
+            pg = getattr(L, V.PRED_GRAD_STRUCT)()
+            pg.f_grad, pg.f_grad_var = (_bulk_ptr(a) for a in go)
+            fields.update(f_grad=go[0][:sumP * D].reshape(sumP, D), f_grad_var=go[1][:sumP * D].reshape(sumP, D))
+            args.append(C.byref(pg))
         rc = getattr(self._lib, name)(*args)
         return self._result(rc, name, res, preds, sumP, **fields)
 

@@ -73,6 +73,15 @@ gpsat_amd/variants.py; the constructor refuses such a con
 per model profile and wave).  ``pred_kwargs.full_cov=True`` adds the table ``preds_2`` (``_dim_0``, ``_dim_1``, ``f*_cov``,
 ``y_cov``: what ``dict_of_array_to_table(concat=True, table="preds")`` makes of the 2-D arrays of the prediction dict,
 local_experts.py:691-747, gpflow_models.py:245-263).
+``pred_kwargs.gradient=True`` (exact-GP experts, fp64: ``dtype`` None then means fp64; kernels RBF, Matern32, Matern52; DESIGN.md
+section 24) adds to ``preds``, for every column ``<c>`` of ``coords_col``, ``f*_grad_<c>`` and ``f*_grad_var_<c>``: the derivative
+of the posterior mean with respect to that coordinate of the prediction location, and the posterior variance of the derivative.
+Their units are those in which ``f*`` is stored there -- divided by ``obs_scale`` -- per RAW unit of the coordinate (``coords_scale``
+is undone; with ``pred_kwargs.apply_scale=False`` the coordinate's unit is the one the prediction locations are given in): the
+slope of the raw field is ``obs_scale * f*_grad_<c>``, its variance ``obs_scale**2 * f*_grad_var_<c>``.  The option holds for
+the whole run (a replacement profile predicts the same columns), no other table changes, and the glue does not combine
+these columns.  The constructor refuses what HipGPRModel.predict(gradient=True) refuses: fp32, Matern12 / RationalQuadratic
+(also as a replacement profile's kernel), a constant mean, ``obs_var_col``, ``cv``, SGPR experts and ``full_cov``.
 ``load_params.previous=True`` (local_experts.py:1059-1064,1200-1217: every tile starts from an exponential moving average,
 rho = 0.95, of the optima of the successfully optimised tiles before it) is a serial cross-tile dependency; its batched
 definition here is CALL-LAGGED: all tiles of one engine call start from the average as it stood when the call was
@@ -860,7 +869,8 @@ _N_RES = 6
 # box, trainable mask, the clamp's (slice, tol) pairs, scales, local mean) and the profile's engine and predict settings.
 _Profile = make_dataclass("_Profile", [
     "theta_default", "lo", "hi", "trainable", "clamp", "coords_scale", "obs_scale", "local_mean", "unconstrained_noise",
-    "device", "sgpr", "n_inducing", "inducing_seed", "kernel", "max_iter", "eng_kw", "optimiser", "apply_scale", "full_cov"])
+    "device", "sgpr", "n_inducing", "inducing_seed", "kernel", "max_iter", "eng_kw", "optimiser", "apply_scale", "full_cov",
+    "pred_grad"])
 # Pass 1: the expert locations of a run -- item i is expert ex[i] at locs[i]; its observation rows are idx[off[i]:off[i + 1]]
 # of coords_all / obs_all (fp64), its prediction coordinates pcs[i]; kind 0 skipped silently, 1 stub row, 2 tile, 3 error
 # row; prof_id indexes profiles; theta0, lo, hi [T, H] its start parameters and box.
@@ -921,8 +931,10 @@ class BatchedLocalExpertOI:
         kind = self._variants + ["noise"] * (self.obs_var_col is not None) + ["sgpr"] * self.sgpr
         # dtype None: fp32 for exact-GP experts, fp64 for the kinds of expert that are built in fp64 only (an explicit fp32
         # is refused below)
+        # pred_kwargs.gradient (either profile's) holds for the run: the gradient of the posterior mean beside every prediction
+        self.pred_grad = any(bool((model_config.get(k) or {}).get("gradient", False)) for k in ("pred_kwargs", "replacement_pred_kwargs"))
         if dtype is None:
-            dtype = "f32" if all("f32" in V.VARIANTS[k].dtypes for k in kind) else "f64"
+            dtype = "f32" if all("f32" in V.VARIANTS[k].dtypes for k in kind) and not self.pred_grad else "f64"
         if dtype not in DTYPES:
             raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
         # one check per model profile: the main one carries the kind of expert; the replacement stays a plain exact GP
@@ -937,6 +949,14 @@ class BatchedLocalExpertOI:
                                 dims="coordinate columns")
             if why:
                 raise NotImplementedError(why)
+        if self.pred_grad:
+            main_ip = model_config.get("init_params") or {}
+            rip = model_config.get("replacement_init_params")
+            kernels = [main_ip.get("kernel", "Matern32")] + [(main_ip if rip is None else rip).get("kernel", "Matern32")] * bool(replaced)
+            for (asked, pk), kern in zip(profiles, kernels):
+                why = V.why_refused_pred_grad(asked + held_out + ["full_cov"] * bool((pk or {}).get("full_cov", False)), dtype, kern)
+                if why:
+                    raise NotImplementedError(why)
         row = next((V.VARIANTS[k] for k in self._variants if V.VARIANTS[k].param), None)
         self.extra = (row.param, row.arg) if row else None          # the ONE extra named parameter and what asks for it
         self.rq = "rq" in self._variants
@@ -1072,7 +1092,7 @@ class BatchedLocalExpertOI:
             inducing_seed=int(pf["init_params"].get("inducing_seed", 0)), kernel=kernel, max_iter=int(ok.get("max_iter", 10_000)),
             eng_kw={**{k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok}, **m._variant_args()},
             optimiser=ok.get("optimiser", "lbfgs") if optimise else "none", apply_scale=pf["pred_kwargs"].get("apply_scale", True),
-            full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict)
+            full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict, pred_grad=self.pred_grad and predict)
 
     def _loaded_theta(self, tabs, locs, theta, unconstrained_noise):
         """Overwrite rows of ``theta`` [T, H] with the stored parameters of each expert location.  Returns the mask of
@@ -1443,6 +1463,10 @@ class BatchedLocalExpertOI:
         dim0 = np.arange(tot) - np.repeat(np.concatenate([[0], np.cumsum(cnt)])[:-1], cnt)
         pr = {"_dim_0": dim0, "f*": pred_cat[:, 0], "f*_var": pred_cat[:, 1], "y_var": pred_cat[:, 2],
               "f_bar": np.repeat(f_bar, cnt)}
+        if self.pred_grad:                                         # behind the three: D gradients, then their D variances
+            for ci, c_ in enumerate(cc):
+                pr[f"f*_grad_{c_}"] = pred_cat[:, 3 + ci]
+                pr[f"f*_grad_var_{c_}"] = pred_cat[:, 3 + len(cc) + ci]
         for ci, c_ in enumerate(cc):
             pr[f"pred_loc_{c_}"] = raw[:, ci]
         return pd.DataFrame(pr, index=_index_for_repeated(cc, plan.locs[items], cnt))
@@ -1519,6 +1543,7 @@ class _ShardRunner:
     def __init__(self, oi: BatchedLocalExpertOI, plan: _Plan, items, store: ResultStore, wave_n, chunk_n, t_start):
         self.oi, self.plan, self.items, self.store, self.t_start = oi, plan, items, store, t_start
         self.H = oi.H
+        self.pred_width = 3 + 2 * len(oi.coords_col) * bool(oi.pred_grad)      # f*, f*_var, y_var[, D gradients, D variances]
         self.waves = [items[w0:w0 + wave_n] for w0 in range(0, len(items), wave_n)]
         self.jobs, self.jobs_of_wave = [], {}          # jobs: (wave, profile, positions within the wave, items)
         for wi, w in enumerate(self.waves):
@@ -1565,7 +1590,7 @@ class _ShardRunner:
                 raise
         # the last queued flush goes on while the caller's tables are assembled (run() waits for it), then the writer ends
         self.flusher.shutdown(wait=False)
-        self.fixed, self.preds = _cat(self.rows[0], self.H + _N_RES), _cat(self.rows[1], 3)
+        self.fixed, self.preds = _cat(self.rows[0], self.H + _N_RES), _cat(self.rows[1], self.pred_width)
         self.cov = _cat(self.rows[2], 2) if self.plan.want_cov else None
         return self
 
@@ -1631,7 +1656,8 @@ class _ShardRunner:
                 if self.oi.cv is not None:
                     kw.update(LC.engine_kw(self.oi.cv, pk["cv_fold"], pf.local_mean, p.min_obs))
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
-                                           **kw, **({"full_cov": True} if pf.full_cov else {}))
+                                           **kw, **({"full_cov": True} if pf.full_cov else {}),
+                                           **({"pred_grad": True} if pf.pred_grad else {}))
             t1 = time.perf_counter()
             self.oi.timings["calls"].append((k, len(ids), round(te - self.t_start, 4), round(t1 - self.t_start, 4),
                                              round(r.kernel_ms * 1e-3, 4)))
@@ -1661,6 +1687,10 @@ class _ShardRunner:
         if p.predict:
             pr = np.stack([np.asarray(r.f_mean, dtype=np.float64), np.asarray(r.f_var, dtype=np.float64),
                            np.asarray(r.y_var, dtype=np.float64)], axis=1)
+            if pf.pred_grad:
+                # per RAW coordinate unit, in the units f* is stored in: the model's gradient with coords_scale undone
+                cs = pf.coords_scale if pf.apply_scale else np.ones_like(pf.coords_scale)
+                pr = np.concatenate([pr, np.asarray(r.f_grad, dtype=np.float64) / cs, np.asarray(r.f_grad_var, dtype=np.float64) / cs ** 2], axis=1)
             p_off = pk["p_off"]
             for kk, j in enumerate(loc_ids):
                 preds[j] = pr[p_off[kk]:p_off[kk + 1]]
@@ -1684,7 +1714,7 @@ class _ShardRunner:
         """The state of wave wi, opened on first use: (fixed, preds per item, covariance rows per item)."""
         if wi not in self.open:
             n = len(self.waves[wi])
-            self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, 3))] * n, [np.zeros((0, 2))] * n)
+            self.open[wi] = (np.full((n, self.H + _N_RES), np.nan), [np.zeros((0, self.pred_width))] * n, [np.zeros((0, 2))] * n)
         return self.open[wi]
 
     def _close_waves_to(self, w):
@@ -1698,7 +1728,7 @@ class _ShardRunner:
         self._wave(wi)                                             # a wave without model tiles opens here
         fixed, preds, covs = self.open.pop(wi)
         tt = time.perf_counter()
-        pred_cat, cov_cat = _cat(preds, 3), _cat(covs, 2) if p.want_cov else None
+        pred_cat, cov_cat = _cat(preds, self.pred_width), _cat(covs, 2) if p.want_cov else None
         pieces = self.piece_futs.pop(wi, [])
         # the predictions went out as pieces: the wave's flush needs the small tables only, and the wave's preds frame is
         # built (after the flush is queued) only where it is returned -- the only wave of a run

@@ -404,8 +404,20 @@ class HipGPRModel:
         r = self._run(optimiser="none")
         return float(r.nll[0])
 
-    def predict(self, coords, full_cov=False, apply_scale=True) -> Dict[str, np.ndarray]:
-        # gpflow_models.py:187-273
+    def _why_no_gradient(self, full_cov=False):
+        """Why predict(gradient=True) is refused for this model (variants.why_refused_pred_grad), or None."""
+        return V.why_refused_pred_grad(self._variants + ["full_cov"] * bool(full_cov), self.dtype, self.kernel)
+
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
+        """gpflow_models.py:187-273.  ``gradient=True`` (fp64; RBF, Matern32, Matern52): also the 1-D arrays
+        ``f*_grad_<k>`` and ``f*_grad_var_<k>``, k = 0 .. D - 1 -- the derivative of the posterior mean with respect to
+        coordinate k of the prediction point, and the posterior variance of that derivative.  With ``apply_scale`` they are in
+        raw units, observation units per unit of the raw coordinate: obs_scale g_k / coords_scale_k and obs_scale^2 v_k /
+        coords_scale_k^2; without it they are the scaled model's, as the coordinates given are."""
+        if gradient:
+            why = self._why_no_gradient(full_cov)
+            if why:
+                raise NotImplementedError(why)
         if pd is not None and isinstance(coords, (pd.Series, pd.DataFrame)):
             if self.coords_col is not None:
                 coords = coords[self.coords_col].values
@@ -419,7 +431,7 @@ class HipGPRModel:
         coords = coords.astype(self.coords.dtype)
         if apply_scale:
             coords = coords / self.coords_scale
-        r = self._run(optimiser="none", pred_coords=coords, full_cov=bool(full_cov))
+        r = self._run(optimiser="none", pred_coords=coords, **({"pred_grad": True} if gradient else {"full_cov": bool(full_cov)}))
         if r.status[0] in (2, 3):
             raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
         if not full_cov:
@@ -435,6 +447,13 @@ class HipGPRModel:
             y_cov = f_cov.copy()
             y_cov[np.arange(P), np.arange(P)] += y_var - f_var
             out = {"f*": r.f_mean.astype(np.float64), "f*_var": f_var, "y_var": y_var, "f*_cov": f_cov, "y_cov": y_cov}
+        if gradient:
+            cs = np.broadcast_to(self.coords_scale, (1, self.D))[0] if apply_scale else np.ones(self.D)
+            osc = float(self.obs_scale[0, 0]) if apply_scale else 1.0
+            fg, fgv = np.asarray(r.f_grad, dtype=np.float64), np.asarray(r.f_grad_var, dtype=np.float64)
+            for k in range(self.D):
+                out[f"f*_grad_{k}"] = osc * fg[:, k] / cs[k]
+                out[f"f*_grad_var_{k}"] = osc ** 2 * fgv[:, k] / cs[k] ** 2
         f_bar = self.obs_mean[:, 0]
         if len(f_bar) != len(out["f*"]):
             assert len(f_bar) == 1, f"'f_bar' did not match the length of 'f*' and f_bar len is not, got: {len(f_bar)}"
@@ -606,9 +625,11 @@ class HipSGPRModel(HipGPRModel):
         r = self._run(optimiser="none")
         return -float(r.nll[0])
 
-    def predict(self, coords, full_cov=False, apply_scale=True) -> Dict[str, np.ndarray]:
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
         if full_cov:
             raise NotImplementedError("HipSGPRModel.predict(full_cov=True) is not built")
+        if gradient:
+            raise NotImplementedError(V.why_refused_pred_grad(["sgpr"], None, None))
         return super().predict(coords, full_cov=False, apply_scale=apply_scale)
 
 
@@ -767,9 +788,11 @@ class HipSklearnGPRModel(HipGPRModel):
         r = self._run(optimiser="none")
         return float(r.nll[0])
 
-    def predict(self, coords, full_cov=False, apply_scale=True) -> Dict[str, np.ndarray]:
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
         """f* and the latent variance f*_var (clipped at 0) as sklearn returns them: no y_var, no f_bar, no rescale by
         obs_scale (sklearn_models.py:116-178); ``full_cov`` adds f*_cov."""
+        if gradient:
+            raise NotImplementedError(V.why_refused_pred_grad(["multistart"], None, None))
         out = super().predict(coords, full_cov=full_cov, apply_scale=apply_scale)
         res = {"f*": np.atleast_1d(out["f*"]), "f*_var": np.maximum(np.atleast_1d(out["f*_var"]), 0.0)}
         if full_cov:

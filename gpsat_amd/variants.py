@@ -58,8 +58,19 @@ PLAIN_ENTRY = "gpsat_fit_predict_batch"       # the call without any extension s
 JOINT_ENTRY = {"cv": "gpsat_fit_predict_batch_cv_joint", "cv_refit": "gpsat_fit_predict_batch_cv_refit_joint"}
 JOINT_STRUCT = "GpsatCvJoint"
 
+# The gradient of the posterior mean at the prediction points, with its variance per component (pred_grad; DESIGN.md section
+# 24), is an option of the plain call in the same way: its entry point takes PRED_GRAD_STRUCT behind the batch, and the rows
+# below cannot be asked for beside it.  Matern12 is refused for what it is, not for what is built.
+PRED_GRAD_ENTRY = "gpsat_fit_predict_batch_grad"
+PRED_GRAD_STRUCT = "GpsatPredGrad"
+PRED_GRAD_ARG = "pred_grad"
+PRED_GRAD_LABEL = "the gradient of the posterior mean at the prediction points (pred_kwargs.gradient)"
+PRED_GRAD_KERNELS = ("RBF", "SquaredExponential", "Matern32", "Matern52")
+PRED_GRAD_EXCLUDES = ("rq", "mean", "noise", "cv", "cv_refit", "multistart", "sgpr", "full_cov")
+
 for _k, _v in VARIANTS.items():
     assert all(_k in VARIANTS[_o].excludes for _o in _v.excludes), f"{_k}: excludes is not symmetric"
+assert all(_k in VARIANTS for _k in PRED_GRAD_EXCLUDES)
 
 
 def _param_rows(asked):
@@ -102,4 +113,20 @@ def why_refused(asked, dtype: Optional[str], D: Optional[int], dims: str = "inpu
             return f"{v.arg}: built in {only} only, not in {dtype!r} ({v.label}): pass dtype={v.dtypes[-1]!r}"
         if D is not None and D > v.max_D and not host_only:
             return f"{v.arg}: built for 1..{v.max_D} {dims} only, got {D} ({v.label})"
+    return None
+
+
+def why_refused_pred_grad(asked, dtype: Optional[str], kernel: Optional[str]):
+    """None when the gradient of the posterior mean (pred_grad) can be asked for beside the rows ``asked`` at ``dtype`` ("f32" /
+    "f64"; None: not checked) with ``kernel`` (a name; None: not checked), else the reason, one sentence."""
+    if dtype is not None and dtype != "f64":
+        return f"{PRED_GRAD_ARG}: built in fp64 only, not in {dtype!r} ({PRED_GRAD_LABEL}): pass dtype='f64'"
+    if kernel in ("Matern12", "Exponential"):
+        return (f"{PRED_GRAD_ARG}: kernel {kernel!r} has no gradient to return, a Matern-1/2 process is not mean-square "
+                f"differentiable ({PRED_GRAD_LABEL})")
+    for k in VARIANTS:                                               # table order, whatever the caller's
+        if k in asked and k in PRED_GRAD_EXCLUDES:
+            return f"{PRED_GRAD_ARG} and {VARIANTS[k].arg} cannot be combined ({PRED_GRAD_LABEL}; {VARIANTS[k].label})"
+    if kernel is not None and kernel not in PRED_GRAD_KERNELS:
+        return f"{PRED_GRAD_ARG}: not built for kernel {kernel!r}, only for {', '.join(PRED_GRAD_KERNELS)} ({PRED_GRAD_LABEL})"
     return None

@@ -248,6 +248,33 @@ typedef struct gpsat_noise {
 int gpsat_fit_predict_batch_noise(gpsat_handle *h, const gpsat_batch *b, const gpsat_noise *nz);
 
 /*
+ * The gradient of the posterior mean with respect to the prediction point, with its posterior variance per component: the
+ * extension of gpsat_fit_predict_batch_grad.  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout
+ * and GPSAT_ABI_VERSION stays 4.
+ *
+ * At the returned theta, for every prediction point x* of a tile and every input dimension a, with K_y = L L^T, z = L^-1 y,
+ * d_i = (x_i - x*) / l (per dimension), r^2 = sum d_i^2 and gg(r^2) = -k'(r) / r of the unit-variance kernel:
+ *   g_a[i] = dk(x*, x_i)/dx*_a = sf2 gg(r^2) d_{i,a} / l_a,   V_a = L^-1 g_a,
+ *   f_grad[a] = V_a^T z = d f*(x*) / dx*_a,   f_grad_var[a] = sf2 gg(0) / l_a^2 - V_a^T V_a = var(df/dx_a at x* | y),
+ * gg(0) = 1 (GPSAT_KERNEL_RBF), 3 (GPSAT_KERNEL_MATERN32), 5/3 (GPSAT_KERNEL_MATERN52).  Both are [sum P, D] row-major doubles
+ * in the units of y (y^2) per unit of X.  A tile without observations returns the prior at theta0 (gradient 0, variance
+ * sf2 gg(0) / l_a^2), a tile whose status is GPSAT_STATUS_NOT_PD or GPSAT_STATUS_NAN returns NaN in both.  The covariance
+ * between components and between points is not returned.  Built for GPSAT_F64, the three kernels above and D <= 4, one
+ * workgroup per tile, with both optimisers.  Every other output of the call has the bits gpsat_fit_predict_batch returns;
+ * a tile's two outputs have the same bits alone, inside any batch and on a second call.
+ */
+typedef struct gpsat_pred_grad {
+    void *f_grad;              /* [sum P * D] doubles, host|device as b->memory: out           */
+    void *f_grad_var;          /* [sum P * D] doubles: out                                     */
+    int32_t reserved[8];       /* must be 0                                                   */
+} gpsat_pred_grad;             /* 48 bytes */
+
+/* as gpsat_fit_predict_batch, with the two outputs above.  GPSAT_EINVAL (with a message that names the reason; the handle
+ * stays usable) for GPSAT_F32, GPSAT_KERNEL_MATERN12 (not mean-square differentiable), GPSAT_KERNEL_RQ, a NULL pg, a NULL
+ * output when sum P > 0, non-zero reserved words, and cov_off / f_cov given (no full covariance in the same call). */
+int gpsat_fit_predict_batch_grad(gpsat_handle *h, const gpsat_batch *b, const gpsat_pred_grad *pg);
+
+/*
  * Held-out (cross-validation) predictions from every tile's own factor: the extension of gpsat_fit_predict_batch_cv
  * (fp64 only).  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
  *
