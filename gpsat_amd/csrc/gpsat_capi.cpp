@@ -1601,16 +1601,17 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     return record_timing(h, 1, 2);                              // no ev[0] / ev[3] here: the total is the kernel time
 }
 
-// check (gpsat_glue_plan.h) -> key range -> stage -> sort, run heads -> read the group count -> reduce -> fetch
-int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
-                           const double* xprt, const double* vals, double sigma, const double* sigma_rows, double max_dist,
-                           int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out) {
-    if (!h) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_batch: handle is NULL");
+// The two keyed glues behind their checks (gpsat_glue_plan.h): key range -> stage -> sort, run heads -> read the group count ->
+// reduce -> fetch.  Without with_grad: gpsat_glue_keyed_batch, vals [nvars][R] -> out [nvars][capacity].  Otherwise
+// gpsat_glue_keyed_grad_batch: nvars is 1, vals the value [R] and grad [ndim][R] are staged as 1 + ndim columns of the layout,
+// out is out_val [capacity] and out_grad [ndim][capacity].
+static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
+                          const double* xprt, const double* vals, const double* grad, double sigma, const double* sigma_rows,
+                          double max_dist, int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out,
+                          double* out_grad, bool with_grad) {
     char why[160];
     int rc;
-    if ((rc = gpsat::check_glue_keyed(R, ndim, nvars, key, pred, xprt, vals, sigma, sigma_rows, max_dist, capacity, G, out_key,
-                                      out_count, out, why, sizeof(why))))
-        return fail(rc, why);
+    const int ncols = with_grad ? 1 + ndim : nvars;
     *G = 0;
     h->glue.ms[0] = h->glue.ms[1] = h->glue.ms[2] = 0.0;
     const unsigned long long sentinel = gpsat::glue_keyed_sentinel(R, key);
@@ -1619,7 +1620,7 @@ int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nva
     if (const char* e = dev_env("GPSAT_DEBUG_GLUE_TEAM")) team = std::atoi(e);       // scripts/cv_glue_bench.py
     if (team != 1 && team != 4 && team != 8 && team != 16 && team != 32 && team != 64)
         return fail(GPSAT_EINVAL, "GPSAT_DEBUG_GLUE_TEAM must be 1, 4, 8, 16, 32 or 64");
-    const gpsat::GlueKeyedLayout l = gpsat::glue_keyed_layout(R, ndim, nvars);
+    const gpsat::GlueKeyedLayout l = gpsat::glue_keyed_layout(R, ndim, ncols);
     if ((rc = begin_call(h))) return rc;
     gpsat_handle::GlueBufs& gb = h->glue;
     for (hipEvent_t& ev : gb.ev)
@@ -1640,6 +1641,8 @@ int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nva
     HIP_TRY(hipMemcpyAsync(d_in + l.in_pred, pred, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_in + l.in_xprt, xprt, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_in + l.in_vals, vals, (size_t)nvars * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const double* d_grad = reinterpret_cast<const double*>(d_in + l.in_vals) + nR;       // behind the one value column
+    if (with_grad) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + nR * sizeof(double), grad, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sigma_rows) HIP_TRY(hipMemcpyAsync(d_in + l.in_sigma, sigma_rows, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     a.key = reinterpret_cast<const long long*>(d_in);
     a.pred = reinterpret_cast<const double*>(d_in + l.in_pred);
@@ -1666,17 +1669,21 @@ int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nva
     // ---- reduce, fetch
     if (ng > 0 && capacity >= ng) {
         const size_t nG = (size_t)ng;
-        if ((rc = gb.out.reserve(nG * ((size_t)nvars + 1) * sizeof(double) + nG * sizeof(int)))) return rc;
+        if ((rc = gb.out.reserve(nG * ((size_t)ncols + 1) * sizeof(double) + nG * sizeof(int)))) return rc;
         a.out_key = static_cast<long long*>(gb.out.p);
         a.out = reinterpret_cast<double*>(a.out_key + nG);
-        a.out_count = reinterpret_cast<int*>(a.out + (size_t)nvars * nG);
+        a.out_count = reinterpret_cast<int*>(a.out + (size_t)ncols * nG);
+        double* d_out_grad = a.out + nG;                        // behind the one value column
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // behind the reservation
-        HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, h->stream));
+        if (with_grad) HIP_TRY(gpsat::launch_glue_keyed_grad(a, ng, team, d_grad, d_out_grad, h->stream));
+        else HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, h->stream));
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         HIP_TRY(hipMemcpyAsync(out_key, a.out_key, nG * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(out_count, a.out_count, nG * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         for (int v = 0; v < nvars; ++v)
             HIP_TRY(hipMemcpyAsync(out + (size_t)v * capacity, a.out + (size_t)v * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        for (int d = 0; with_grad && d < ndim; ++d)
+            HIP_TRY(hipMemcpyAsync(out_grad + (size_t)d * capacity, d_out_grad + (size_t)d * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     } else {
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // no reduction: an empty interval
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1691,6 +1698,31 @@ int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nva
     for (int i = 0; i < 3; ++i) gb.ms[i] = ms[i];
     if ((rc = gpsat::check_glue_capacity(capacity, ng, why, sizeof(why)))) return fail(rc, why);
     return GPSAT_OK;
+}
+
+int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
+                           const double* xprt, const double* vals, double sigma, const double* sigma_rows, double max_dist,
+                           int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_batch: handle is NULL");
+    char why[160];
+    if (int rc = gpsat::check_glue_keyed(R, ndim, nvars, key, pred, xprt, vals, sigma, sigma_rows, max_dist, capacity, G, out_key,
+                                         out_count, out, why, sizeof(why)))
+        return fail(rc, why);
+    return glue_keyed_run(h, R, ndim, nvars, key, pred, xprt, vals, nullptr, sigma, sigma_rows, max_dist, capacity, G, out_key,
+                          out_count, out, nullptr, false);
+}
+
+int gpsat_glue_keyed_grad_batch(gpsat_handle* h, int64_t R, int32_t ndim, const int64_t* key, const double* pred,
+                                const double* xprt, const double* val, const double* grad, double sigma, const double* sigma_rows,
+                                double max_dist, int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count,
+                                double* out_val, double* out_grad) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_grad_batch: handle is NULL");
+    char why[160];
+    if (int rc = gpsat::check_glue_keyed_grad(R, ndim, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key,
+                                              out_count, out_val, out_grad, why, sizeof(why)))
+        return fail(rc, why);
+    return glue_keyed_run(h, R, ndim, 1, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count,
+                          out_val, out_grad, true);
 }
 
 int gpsat_glue_keyed_timing(gpsat_handle* h, double* ms) {

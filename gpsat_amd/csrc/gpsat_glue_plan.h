@@ -1,5 +1,5 @@
-// gpsat_glue_plan.h -- host side of gpsat_glue_keyed_batch: the argument checks, the key range of a call and the layout of the
-// handle's buffers.  Plain C++ without a HIP call, in the manner of gpsat_bin_plan.h; the two checks are exported like
+// gpsat_glue_plan.h -- host side of gpsat_glue_keyed_batch and gpsat_glue_keyed_grad_batch: the argument checks, the key range of
+// a call and the layout of the handle's buffers.  Plain C++ without a HIP call, in the manner of gpsat_bin_plan.h; the checks are exported like
 // gpsat::check_noise (gpsat_plan.h), so that tests drive every refusal without a device.  Part of gpsat_capi.cpp's
 // translation unit.
 #ifndef GPSAT_GLUE_PLAN_H
@@ -36,6 +36,24 @@ int check_glue_keyed(int64_t R, int32_t ndim, int32_t nvars, const int64_t* key,
     if (max_dist != max_dist) return bad("max_dist is NaN (+inf or a value <= 0 switches the limit off)");
     if (R > 0 && (!key || !pred || !xprt || !vals)) return bad("key / pred / xprt / vals is NULL");
     if (capacity > 0 && (!out_key || !out_count || !out)) return bad("out_key / out_count / out is NULL");
+    return GPSAT_OK;
+}
+
+// The same for gpsat_glue_keyed_grad_batch: one value column and its gradient, [ndim][R], instead of vals [nvars][R].
+int check_glue_keyed_grad(int64_t R, int32_t ndim, const int64_t* key, const double* pred, const double* xprt, const double* val,
+                          const double* grad, double sigma, const double* sigma_rows, double max_dist, int64_t capacity,
+                          const int64_t* G, const int64_t* out_key, const int32_t* out_count, const double* out_val,
+                          const double* out_grad, char* why, size_t why_len) {
+    if (why_len > 0) why[0] = 0;
+    auto bad = [&](const char* msg) { std::snprintf(why, why_len, "gpsat_glue_keyed_grad_batch: %s", msg); return GPSAT_EINVAL; };
+    if (!G) return bad("G is NULL");
+    if (R < 0 || capacity < 0) return bad("R and capacity must not be negative");
+    if (R > 2147483647LL) return bad("more than 2^31-1 rows in one call");
+    if (ndim < 1 || ndim > 2) return bad("ndim must be 1 or 2");
+    if (!sigma_rows && (!(sigma > 0.0) || !std::isfinite(sigma))) return bad("sigma must be finite and positive when sigma_rows is NULL");
+    if (max_dist != max_dist) return bad("max_dist is NaN (+inf or a value <= 0 switches the limit off)");
+    if (R > 0 && (!key || !pred || !xprt || !val || !grad)) return bad("key / pred / xprt / val / grad is NULL");
+    if (capacity > 0 && (!out_key || !out_count || !out_val || !out_grad)) return bad("out_key / out_count / out_val / out_grad is NULL");
     return GPSAT_OK;
 }
 

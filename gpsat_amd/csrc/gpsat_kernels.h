@@ -288,6 +288,10 @@ hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_byte
 // one team of `team` lanes per group, gathering through the permutation; team in {1, 4, 8, 16, 32, 64}
 hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream);
 int glue_keyed_team();                // the team width of the product
+// the glued value and the exact slope of the glued map (gpsat_glue_keyed_grad_batch): a.vals is the value [R], a.nvars 1,
+// a.out the glued value [G]; grad [ndim][R] in source order, out_grad [ndim][G].  The teams and the tree of launch_glue_keyed.
+hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
+                                  hipStream_t stream);
 
 // raw rows to x / y and track numbers (gpsat_prep.hip); device pointers.  The scalars come from gpsat_prep_plan.h.
 struct ProjectArgs {

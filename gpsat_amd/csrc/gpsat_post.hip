@@ -18,6 +18,8 @@
 //                   the group's rows l, l + W, l + 2W, ... in that order and a fixed xor tree over the team's W lanes joins
 //                   them.  A group's bits are a function of its own rows in source order (the sort is stable) and of W, a
 //                   compile-time constant of the product: not of the other keys, the grid or the capacity.  No float atomics.
+//   glue_keyed_grad_kernel : the same walk for one value with its gradient: the glued value and the slope of the glued map,
+//                   which has a term from the weights' own dependence on the prediction location.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -185,6 +187,75 @@ __global__ void __launch_bounds__(256) glue_keyed_kernel(const GlueKeyedArgs a, 
     }
 }
 
+// The glued value and the exact slope of the glued map F(p) = sum w_i(p) f_i(p) / sum w_i(p): the
+// weights move with p, dw_i/dp_a = w_i u_ia with u_ia = (xprt_ia - pred_ia) / sigma_i^2, so
+//   G_a = (S_a - F U_a) / W,   S_a = sum w_i (g_ia + u_ia f_i) over rows whose f_i and g_ia are not NaN,   U_a = sum w_i u_ia,
+// with u centred on the row's own expert (coordinates are ~3e6 m, their differences a few sigma).  The team, the walk and the
+// tree of glue_keyed_kernel; the weight, the limit and the value's sum are its statements, so that out[g] holds the bytes
+// glue_keyed_kernel returns for nvars = 1.  a.vals: the value [R]; grad [ndim][R]; out_grad [ndim][G].
+template <int W>
+__global__ void __launch_bounds__(256) glue_keyed_grad_kernel(const GlueKeyedArgs a, long long G, const double* __restrict__ grad,
+                                                              double* __restrict__ out_grad) {
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) / W;
+    const int tl = threadIdx.x & (W - 1);
+    const bool live = g < G;
+    const unsigned s = live ? a.starts[g] : 0u, e = live ? a.starts[g + 1] : 0u;
+    const size_t R = (size_t)a.R;
+    const int ndim = a.ndim;
+    double ws = 0.0, acc = 0.0;
+    int cnt = 0;
+    double sa[2] = {0.0, 0.0}, ua[2] = {0.0, 0.0};
+    for (unsigned i = s + tl; i < e; i += W) {
+        const size_t r = a.perm[i];
+        const double sg = a.sigma_rows ? a.sigma_rows[r] : a.sigma;
+        const double cnorm = 1.0 / (sg * 2.5066282746310002);       // 1 / (sigma sqrt(2 pi))
+        double w = 1.0, d2 = 0.0;
+        double u[2] = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                const double df = a.pred[(size_t)d * R + r] - a.xprt[(size_t)d * R + r];
+                const double zz = df / sg;
+                d2 += df * df;
+                w *= exp(-zz * zz / 2) * cnorm;
+                u[d] = -df / (sg * sg);
+            }
+        if (a.md2 >= 0.0 && !(d2 < a.md2)) continue;                // strict, and a NaN distance is outside
+        ++cnt;
+        ws += w;
+        const double x = a.vals[r];                                 // NaN: out of the sums, its weight stays
+        const bool has = x == x;
+        if (has) acc += w * x;
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                ua[d] += w * u[d];
+                const double gr = grad[(size_t)d * R + r];
+                if (has && gr == gr) sa[d] += w * (gr + u[d] * x);
+            }
+    }
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) {
+        ws += __shfl_xor(ws, off);
+        cnt += __shfl_xor(cnt, off);
+        acc += __shfl_xor(acc, off);
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            sa[d] += __shfl_xor(sa[d], off);
+            ua[d] += __shfl_xor(ua[d], off);
+        }
+    }
+    if (live && tl == 0) {
+        a.out_key[g] = (long long)a.keys_sorted[s];
+        a.out_count[g] = cnt;
+        const double f = acc / ws;
+        a.out[g] = cnt ? f : __builtin_nan("");
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) out_grad[(size_t)d * (size_t)G + (size_t)g] = cnt ? (sa[d] - f * ua[d]) / ws : __builtin_nan("");
+    }
+}
+
 static inline int glue_key_bits(unsigned long long sentinel) {
     int bits = 1;
     while (bits < 64 && (sentinel >> bits) != 0) ++bits;
@@ -227,6 +298,22 @@ hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipS
         case 16: hipLaunchKernelGGL(glue_keyed_kernel<16>, grid, block, 0, stream, a, G); break;
         case 32: hipLaunchKernelGGL(glue_keyed_kernel<32>, grid, block, 0, stream, a, G); break;
         case 64: hipLaunchKernelGGL(glue_keyed_kernel<64>, grid, block, 0, stream, a, G); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
+                                  hipStream_t stream) {
+    if (G <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
+    switch (team) {
+        case 1: hipLaunchKernelGGL(glue_keyed_grad_kernel<1>, grid, block, 0, stream, a, G, grad, out_grad); break;
+        case 4: hipLaunchKernelGGL(glue_keyed_grad_kernel<4>, grid, block, 0, stream, a, G, grad, out_grad); break;
+        case 8: hipLaunchKernelGGL(glue_keyed_grad_kernel<8>, grid, block, 0, stream, a, G, grad, out_grad); break;
+        case 16: hipLaunchKernelGGL(glue_keyed_grad_kernel<16>, grid, block, 0, stream, a, G, grad, out_grad); break;
+        case 32: hipLaunchKernelGGL(glue_keyed_grad_kernel<32>, grid, block, 0, stream, a, G, grad, out_grad); break;
+        case 64: hipLaunchKernelGGL(glue_keyed_grad_kernel<64>, grid, block, 0, stream, a, G, grad, out_grad); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -753,8 +753,40 @@ class Engine:
             raise GpsatError(f"gpsat_glue_keyed_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         return keys[:n].copy(), counts[:n].copy(), np.ascontiguousarray(out[:, :n])
 
+    def glue_keyed_grad_batch(self, key, pred, xprt, val, grad, sigma, max_dist=None):
+        """The glued value and the exact slope of the glued map per key (gpsat_glue_keyed_grad_batch): the arguments of
+        glue_keyed_batch with one value column val [R] and its gradient grad [ndim, R] along the glue axes.  Returns
+        (keys [G] ascending, counts [G], out_val [G], out_grad [ndim, G]); out_val holds the bytes glue_keyed_batch returns
+        for val, out_grad the derivative of that formula with respect to the prediction location, the term from the
+        weights' own dependence on it included."""
+        if not hasattr(self._lib, "gpsat_glue_keyed_grad_batch"):
+            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_grad_batch: rebuild the library (there is no host fallback)")
+        key = np.ascontiguousarray(key, dtype=np.int64)
+        pred = np.ascontiguousarray(pred, dtype=np.float64)
+        xprt = np.ascontiguousarray(xprt, dtype=np.float64)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        grad = np.ascontiguousarray(grad, dtype=np.float64)
+        ndim, R = pred.shape
+        assert key.shape == (R,) and xprt.shape == pred.shape and val.shape == (R,) and grad.shape == pred.shape
+        srow = None
+        if np.ndim(sigma) > 0:
+            srow = np.ascontiguousarray(sigma, dtype=np.float64)
+            assert srow.shape == (R,)
+        md = float("inf") if max_dist is None else float(max_dist)
+        # capacity R always suffices (glue_keyed_batch)
+        keys, counts = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int32)
+        out_val, out_grad = np.empty(R, dtype=np.float64), np.empty((ndim, R), dtype=np.float64)
+        n = C.c_int64(0)
+        rc = self._lib.gpsat_glue_keyed_grad_batch(self._h, R, ndim, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(val), _ptr(grad),
+                                                   0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
+                                                   md, R, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out_val), _ptr(out_grad))
+        if rc != 0:
+            raise GpsatError(f"gpsat_glue_keyed_grad_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        n = int(n.value)
+        return keys[:n].copy(), counts[:n].copy(), out_val[:n].copy(), np.ascontiguousarray(out_grad[:, :n])
+
     def glue_keyed_timing(self):
-        """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch on this engine."""
+        """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch or glue_keyed_grad_batch on this engine."""
         ms = np.zeros(3)
         rc = self._lib.gpsat_glue_keyed_timing(self._h, _ptr(ms))
         if rc != 0:

@@ -230,6 +230,102 @@ def score_cv_predictions(cv_glued: pd.DataFrame, by: Optional[List[str]] = None)
     return pd.DataFrame(recs, columns=by + ["n", "n_missing", "bias", "rmse", "nll", "mean_z2"])
 
 
+def _location_keys(pred):
+    """Rows grouped by prediction location without sorting the rows: pred [ndim, R] -> (key [R], loc [n, ndim]).  The
+    locations are factorised (a hash pass per axis), only the unique ones are sorted -- lexicographically, the order
+    ``np.unique(axis=0)`` gives ``_glue`` -- and a row's key is the rank of its location.  A NaN coordinate: key -1."""
+    ndim = pred.shape[0]
+    code, uniq = pd.factorize(pred[0])                      # NaN: code -1
+    code = code.astype(np.int64)
+    if ndim == 2:                                           # a pair of codes as one integer, factorised again
+        c1, u1 = pd.factorize(pred[1])
+        n1 = max(len(u1), 1)
+        code, pairs = pd.factorize(np.where((code < 0) | (c1 < 0), -1, code * n1 + c1))
+        pairs = np.asarray(pairs, dtype=np.int64)
+        real = pairs >= 0
+        loc = np.stack([uniq[pairs[real] // n1], u1[pairs[real] % n1]], axis=1)
+    else:
+        real = np.ones(len(uniq), dtype=bool)
+        loc = np.asarray(uniq, dtype=np.float64)[:, None]
+    order = np.lexsort(loc.T[::-1])                         # the first column is the primary key
+    rank = np.full(len(real) + 1, -1, dtype=np.int64)       # the last entry: what code -1 finds
+    rank[np.nonzero(real)[0][order]] = np.arange(len(order))
+    return rank[code], loc[order]
+
+
+def glue_local_gradient(preds_df: pd.DataFrame, pred_loc_cols: List[str], xprt_loc_cols: List[str], inference_radius: float,
+                        R=3, value_col: str = "f*", grad_cols: Optional[List[str]] = None, mean_col: Optional[str] = "f_bar",
+                        obs_scale: float = 1.0, also_glue: Optional[List[str]] = None, max_dist: Optional[float] = None,
+                        engine=None) -> pd.DataFrame:
+    """The glued map with its exact slope.  Overlapping local predictions are glued as ``glue_local_predictions_1d`` / ``_2d``
+    glue them, ``F(p) = sum w_i(p) f_i(p) / sum w_i(p)`` with ``w_i = normpdf(p; expert_i, inference_radius / R)`` per glue
+    axis -- and the weights depend on ``p``, so the slope of ``F`` is not the glued slope: beside ``sum w~_i df_i/dp`` it has
+    the term ``sum (dw~_i/dp) f_i`` (``w~ = w / sum w``), of the size (disagreement of neighbouring experts) x (their spacing)
+    / sigma^2.  Gluing ``f*_grad_<c>`` with ``glue_local_predictions_2d`` returns the first term only, which is the gradient
+    of nothing; this returns both (``Engine.glue_keyed_grad_batch``, grouped on the device).
+
+    ``pred_loc_cols`` / ``xprt_loc_cols``: the 1 or 2 glue axes, as columns of ``preds_df`` (prediction and expert location).
+    ``grad_cols``: the gradient of ``value_col`` along each glue axis, by default ``f*_grad_<c>`` (``pred_grad`` of the run)
+    with ``<c>`` the ``pred_loc_cols`` name without a leading ``pred_loc_``.  The glued field is in raw units:
+    ``mean_col + obs_scale * value_col`` (``mean_col=None``: no mean) with gradient ``obs_scale * grad_cols`` -- the slope is
+    only exact when every expert's own de-meaning constant is inside the value, since experts that disagree by a constant
+    tilt the glued map.  ``max_dist``: a row takes part only if its expert lies nearer than that (strictly).
+
+    ``also_glue``: further columns glued with the plain rule on the same rows (``Engine.glue_keyed_batch``, GLUE_MAXVARS per
+    call), unscaled: ``f*_var``, ``f*_grad_var_<c>``, and the gradient along a coordinate that is no glue axis (``t``), where
+    the weights do not depend on it and the plain rule is exact.  A glued variance is the reference's convention, a
+    weighted average of variances; it is not the variance of the glued slope.
+
+    Returns one row per unique prediction location, the rows and their order those of ``glue_local_predictions_1d`` /
+    ``_2d``: the ``pred_loc_cols``, ``value_col``, the ``grad_cols``, ``n_experts`` (rows that took part; 0: NaN values) and
+    the ``also_glue`` columns."""
+    eng = engine or default_engine()
+    pcols = [pred_loc_cols] if isinstance(pred_loc_cols, str) else list(pred_loc_cols)
+    xcols = [xprt_loc_cols] if isinstance(xprt_loc_cols, str) else list(xprt_loc_cols)
+    if isinstance(inference_radius, bool) or not isinstance(inference_radius, (int, float, np.integer, np.floating)):
+        raise TypeError("inference_radius must be one number: per-expert radii are not built for the glued gradient")
+    if not 1 <= len(pcols) <= 2:
+        raise ValueError(f"the glued gradient takes 1 or 2 glue axes, got pred_loc_cols {pcols}")
+    if len(xcols) != len(pcols):
+        raise ValueError(f"xprt_loc_cols {xcols} and pred_loc_cols {pcols} must name the same number of glue axes")
+    if grad_cols is None:
+        grad_cols = [f"{value_col}_grad_{c[len('pred_loc_'):] if c.startswith('pred_loc_') else c}" for c in pcols]
+    gcols = [grad_cols] if isinstance(grad_cols, str) else list(grad_cols)
+    if len(gcols) != len(pcols):
+        raise ValueError(f"grad_cols {gcols} must name one gradient column per glue axis {pcols}")
+    extra = [] if also_glue is None else ([also_glue] if isinstance(also_glue, str) else list(also_glue))
+    needed = pcols + xcols + [value_col] + gcols + ([mean_col] if mean_col is not None else []) + extra
+    missing = [c for c in needed if c not in preds_df.columns]
+    if missing:
+        raise ValueError(f"preds_df has no column {missing} (columns: {list(preds_df.columns)})")
+    col = lambda c: preds_df[c].values.astype(np.float64)
+    pred, xprt = np.stack([col(c) for c in pcols]), np.stack([col(c) for c in xcols])
+    osc = float(obs_scale)
+    val = osc * col(value_col) if mean_col is None else col(mean_col) + osc * col(value_col)
+    grad = np.stack([osc * col(c) for c in gcols])
+    key, loc = _location_keys(pred)
+    sigma = float(inference_radius) / R
+    n = len(loc)
+
+    def placed(keys, rows):                                 # by key: every location has one, so this is the identity
+        out = np.full(rows.shape[:-1] + (n,), np.nan)
+        out[..., keys] = rows
+        return out
+
+    keys, counts, gval, ggrad = eng.glue_keyed_grad_batch(key, pred, xprt, val, grad, sigma, max_dist)
+    fr = {c: loc[:, i] for i, c in enumerate(pcols)}
+    fr[value_col] = placed(keys, gval)
+    fr.update({c: placed(keys, ggrad)[i] for i, c in enumerate(gcols)})
+    n_experts = np.zeros(n, dtype=np.int64)
+    n_experts[keys] = counts
+    fr["n_experts"] = n_experts
+    for i in range(0, len(extra), GLUE_MAXVARS):
+        names = extra[i:i + GLUE_MAXVARS]
+        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([col(c) for c in names]), sigma, max_dist)
+        fr.update({c: placed(keys, out)[j] for j, c in enumerate(names)})
+    return pd.DataFrame(fr)
+
+
 def glue_local_predictions_1d(preds_df: pd.DataFrame, pred_loc_col: str, xprt_loc_col: str,
                               vars_to_glue: Union[str, List[str]], inference_radius: float, R=3, engine=None):
     """GPSat/postprocessing.py:476-524: one row per unique prediction location, each variable the normal-pdf-weighted

@@ -536,6 +536,27 @@ int gpsat_glue_keyed_batch(gpsat_handle *h, int64_t R, int32_t ndim, int32_t nva
 int gpsat_glue_keyed_timing(gpsat_handle *h, double *ms);
 
 /*
+ * The glued value with the exact slope of the glued map, by key (added within ABI 4, check for the symbol).  Every row
+ * carries a value f_i and its gradient g_ia = df_i/dp_a along the ndim glue axes.  The glued map is
+ * F(p) = sum w_i(p) f_i(p) / sum w_i(p), and its weights move with p: dw_i/dp_a = w_i u_ia with
+ * u_ia = (xprt_ia - pred_ia) / sigma_i^2.  Per key, over the rows that take part (the rules of gpsat_glue_keyed_batch):
+ *     W = sum w_i,   F = (sum_{f_i not NaN} w_i f_i) / W,   U_a = sum w_i u_ia,
+ *     S_a = sum_{f_i and g_ia not NaN} w_i (g_ia + u_ia f_i),   G_a = (S_a - F U_a) / W.
+ * G_a is the derivative of the formula of gpsat_glue_keyed_batch, its NaN rule included; the plain weighted average of the
+ * g_ia leaves out the term of size (disagreement of neighbouring experts) x (their spacing) / sigma^2.
+ * val        : host fp64 [R];  grad: host fp64 [ndim][R].
+ *   out_val  : host out [capacity], F: the bytes gpsat_glue_keyed_batch returns for nvars = 1, vals = val on these rows;
+ *   out_grad : host out, component a of record j at out_grad[a * capacity + j].
+ * Everything else -- key, pred, xprt, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count, the return codes (capacity
+ * < G: GPSAT_EINVAL with G valid), the determinism, the workspace (1 + ndim value columns) and the timing calls -- is as
+ * in gpsat_glue_keyed_batch.  A key with count 0 has NaN in F and every G_a.
+ */
+int gpsat_glue_keyed_grad_batch(gpsat_handle *h, int64_t R, int32_t ndim, const int64_t *key, const double *pred,
+                                const double *xprt, const double *val, const double *grad, double sigma,
+                                const double *sigma_rows, double max_dist, int64_t capacity, int64_t *G, int64_t *out_key,
+                                int32_t *out_count, double *out_val, double *out_grad);
+
+/*
  * Binning of raw observations on a regular grid, all groups in one call (added within ABI 4, check for the symbol).
  * Replaces DataPrep.bin_data_by / DataPrep.bin_data (GPSat/dataprepper.py:21-401): per group (day, satellite, ...) a
  * scipy.stats.binned_statistic_2d (1-D: binned_statistic) of `v` over the bins of `ex` x `ey`.  Every statistic of every
