@@ -11,8 +11,8 @@
 //     that order with uncontracted arithmetic (__dadd_rn / __dmul_rn / __ddiv_rn / __dsqrt_rn; -ffp-contract=on would
 //     otherwise fuse d*d + q).  No float atomics, no tree reduction: both would change the order of the additions.
 // Stages: (1) 64-bit cell key per row, key = (gid (ny-1) + iy)(nx-1) + ix, rows outside the grid / with a NaN coordinate
-// get the sentinel key G*cells and sort behind everything; (2) rocPRIM radix sort of (key, source row) over the key bits in
-// use, gather of the values into sorted order; (3) run heads -> rocPRIM select -> one lane per non-empty cell, results
+// get the sentinel key G*cells and sort behind everything; (2) the keyed sort-and-run-heads stage (gpsat_key_runs.hip), with
+// the gather of the values into sorted order in the pass that writes its head flags; (3) one lane per non-empty cell, results
 // written sparse in ascending key order; cells of BIN_LONG rows or more are left to one WAVE each (bin_long_kernel), which
 // loads 64 values at a time and adds them in the same order.  The median sorts every cell's values (rocPRIM segmented
 // radix sort, NaN last as np.lexsort has it) and is only computed when asked for.
@@ -23,10 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 #include "gpsat_kernels.h"
 
 namespace gpsat {
@@ -63,19 +60,7 @@ __global__ void __launch_bounds__(256) bin_gather_kernel(const BinArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.R) return;
     a.vs[i] = a.v[a.perm[i]];
-    a.flags[i] = (i == 0 || a.keys_sorted[i] != a.keys_sorted[i - 1]) ? 1 : 0;
-}
-
-// runs -> cells: the sentinel run (rows outside the grid), when there is one, is the last; starts[n_cells] = first row past
-// the cells
-__global__ void bin_finish_kernel(const BinArgs a) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    long long n = *a.n_runs;
-    long long valid = a.R;
-    if (n > 0 && a.keys_sorted[a.starts[n - 1]] == a.sentinel) { valid = a.starts[n - 1]; --n; }
-    a.starts[n] = (unsigned)valid;
-    a.n_cells[0] = n;
-    a.n_cells[1] = valid;
+    a.flags[i] = key_run_head(a.keys_sorted, i);
 }
 
 // the copy the median sorts: every NaN becomes the positive quiet NaN, which the radix order puts behind +inf (a NaN with
@@ -225,33 +210,15 @@ __global__ void __launch_bounds__(256) bin_long_kernel(const BinArgs a, long lon
     }
 }
 
-static inline int bin_key_bits(unsigned long long sentinel) {
-    int bits = 1;
-    while (bits < 64 && (sentinel >> bits) != 0) ++bits;
-    return bits;
+static void bin_gather(const void* ctx, hipStream_t stream) {
+    const BinArgs& a = *static_cast<const BinArgs*>(ctx);
+    hipLaunchKernelGGL(bin_gather_kernel, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 // temp == nullptr: only the size of the temporary storage is returned in temp_bytes
 hipError_t bin_sort_rows(const BinArgs& a, void* temp, size_t& temp_bytes, hipStream_t stream) {
-    const int bits = bin_key_bits(a.sentinel);
-    rocprim::counting_iterator<unsigned> rows0(0);
-    if (!temp) {
-        size_t t1 = 0, t2 = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, t1, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);
-        if (e != hipSuccess) return e;
-        e = rocprim::select(nullptr, t2, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
-        temp_bytes = t1 > t2 ? t1 : t2;
-        return e;
-    }
-    const unsigned grid = (unsigned)((a.R + 255) / 256);
-    hipLaunchKernelGGL(bin_key_kernel, dim3(grid), dim3(256), 0, stream, a);
-    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);   // stable
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bin_gather_kernel, dim3(grid), dim3(256), 0, stream, a);
-    e = rocprim::select(temp, temp_bytes, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bin_finish_kernel, dim3(1), dim3(64), 0, stream, a);
-    return hipGetLastError();
+    if (temp) hipLaunchKernelGGL(bin_key_kernel, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0, stream, a);
+    return key_runs(a, bin_gather, &a, nullptr, temp, temp_bytes, stream);
 }
 
 // temp == nullptr: only the size of the temporary storage (the median's segmented sort) is returned in temp_bytes

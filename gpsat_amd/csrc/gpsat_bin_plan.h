@@ -10,6 +10,7 @@
 #include <string>
 
 #include "gpsat_hip.h"
+#include "gpsat_key_runs_plan.h"
 
 namespace gpsat {
 
@@ -52,39 +53,31 @@ inline std::string bin_check(int64_t R, const double* x, const double* y, const 
     return std::string();
 }
 
-// Bytes of the handle's bin buffers and the byte offsets of what lies in them.
-struct BinLayout {
+// Bytes of the handle's bin buffers and the byte offsets of what lies in them.  keys, rows and runs are the stage's
+// (KeyRunsLayout; runs_counts: n_cells [2]), with binning's own words in and behind `runs`.
+struct BinLayout : KeyRunsLayout {
     // `in`: both axes' edges (ex, then ey), rounded to 256 B, then the columns x, v, y (2-D), gid (int32, when given); the room
     // of gid is reserved either way
     size_t in_bytes, in_x, in_v, in_y, in_gid;
-    size_t keys_bytes;                // [2][R] 64-bit keys: as computed, sorted
-    size_t rows_bytes;                // [2][R] 32-bit rows: source, sorted
     size_t vals_bytes;                // [R] values in sorted order; with the median [3][R]: then one NaN pattern, then sorted per cell
-    // `runs`: starts [R + 1] rounded to 256 B, a 256-B block with n_cells [2] / n_runs / n_long, the flags [R] rounded to
-    // 256 B, the list of long cells [R / long_rows + 1]
-    size_t runs_bytes, runs_n_cells, runs_n_runs, runs_n_long, runs_flags, runs_long_list;
+    // `runs` of the stage with n_long at +32 of its 256-B block, the flags [R] rounded to 256 B, then the long cells [R / long_rows + 1]
+    size_t runs_n_cells, runs_n_long, runs_long_list;     // runs_n_cells: the stage's runs_counts, by binning's name
 };
 
 inline BinLayout bin_layout(int64_t R, int nx, int ny, bool two_d, bool has_gid, bool median, int long_rows) {
     const size_t nR = (size_t)R;
     BinLayout l = {};
+    static_cast<KeyRunsLayout&>(l) = key_runs_layout(R);
     const size_t edge_bytes = ((size_t)(nx + (two_d ? ny : 0)) * sizeof(double) + 255) & ~size_t(255);
     l.in_bytes = edge_bytes + (two_d ? 3 : 2) * nR * sizeof(double) + nR * sizeof(int);
     l.in_x = edge_bytes;
     l.in_v = l.in_x + nR * sizeof(double);
     l.in_y = two_d ? l.in_v + nR * sizeof(double) : 0;
     l.in_gid = has_gid ? edge_bytes + (two_d ? 3 : 2) * nR * sizeof(double) : 0;
-    l.keys_bytes = 2 * nR * sizeof(unsigned long long);
-    l.rows_bytes = 2 * nR * sizeof(unsigned);
     l.vals_bytes = (median ? 3 : 1) * nR * sizeof(double);
-    const size_t starts_bytes = ((nR + 1) * sizeof(unsigned) + 255) & ~size_t(255);
-    const size_t flag_bytes = (nR + 255) & ~size_t(255);
-    l.runs_bytes = starts_bytes + 256 + flag_bytes + (nR / long_rows + 1) * sizeof(unsigned);
-    l.runs_n_cells = starts_bytes;
-    l.runs_n_runs = starts_bytes + 16;
-    l.runs_n_long = starts_bytes + 32;
-    l.runs_flags = starts_bytes + 256;
-    l.runs_long_list = starts_bytes + 256 + flag_bytes;
+    l.runs_n_cells = l.runs_counts; l.runs_n_long = l.runs_counts + 32;
+    l.runs_long_list = l.runs_flags + ((nR + 255) & ~size_t(255));
+    l.runs_bytes = l.runs_long_list + (nR / long_rows + 1) * sizeof(unsigned);
     return l;
 }
 

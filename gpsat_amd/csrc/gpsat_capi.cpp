@@ -33,6 +33,7 @@
 #include "gpsat_plan.h"
 #include "gpsat_cvfold.h"
 #include "gpsat_select_plan.h"
+#include "gpsat_key_runs_plan.h"
 #include "gpsat_bin_plan.h"
 #include "gpsat_glue_plan.h"
 #include "gpsat_prep_plan.h"
@@ -96,6 +97,27 @@ struct DevBuf {
     }
 };
 
+// What one user of the keyed sort-and-run-heads stage (gpsat_key_runs.hip) holds on the device: the three buffers of
+// gpsat_key_runs_plan.h and the stage's scratch.  bind: the stage's arrays of k.R rows, behind reserve() for that many rows.
+struct KeyRunBufs {
+    DevBuf keys, rows, runs, tmp;
+    int reserve(const gpsat::KeyRunsLayout& l) {
+        if (int rc = keys.reserve(l.keys_bytes)) return rc;
+        if (int rc = rows.reserve(l.rows_bytes)) return rc;
+        return runs.reserve(l.runs_bytes);
+    }
+    void bind(gpsat::KeyRuns& k) const {
+        const gpsat::KeyRunsLayout l = gpsat::key_runs_layout(k.R);
+        char* d_runs = static_cast<char*>(runs.p);
+        k.keys = static_cast<unsigned long long*>(keys.p); k.keys_sorted = k.keys + k.R;
+        k.rows = static_cast<unsigned*>(rows.p); k.perm = k.rows + k.R;
+        k.starts = reinterpret_cast<unsigned*>(d_runs);
+        k.counts = reinterpret_cast<long long*>(d_runs + l.runs_counts);
+        k.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
+        k.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+    }
+};
+
 // Stream and events of a handle.  A base of gpsat_handle, so that they are destroyed AFTER the handle's members: the device
 // buffers are freed first, then the events, then the stream.
 struct HandleQueue {
@@ -130,16 +152,17 @@ struct gpsat_handle : HandleQueue {
     // sel.cnt) instead of buffers of their own: the post-processing follows the selection, whose tables are no longer needed
     // then, and no call leaves anything in the two for a later one (the selection cache holds neither).
     struct SelectBufs { DevBuf pts, refs, cnt, idx, box, perm, keys, tmp, ord, bnd; } sel;
-    struct BinBufs { DevBuf in, keys, rows, vals, runs, tmp, out; } bin;     // gpsat_bin_batch (layout: gpsat_bin_plan.h)
+    struct BinBufs { DevBuf in, vals, out; KeyRunBufs kr; } bin;             // gpsat_bin_batch (layout: gpsat_bin_plan.h)
     // gpsat_glue_keyed_batch (layout: gpsat_glue_plan.h); ev: after the sort, after the run heads, in front of the reduce
     // kernel; ms: the last call's sort, run detection and reduce (gpsat_glue_keyed_timing)
     struct GlueBufs {
-        DevBuf in, keys, rows, runs, tmp, out;
+        DevBuf in, out;
+        KeyRunBufs kr;
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
         double ms[3] = {0.0, 0.0, 0.0};
         ~GlueBufs() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     } glue;
-    struct PrepBufs { DevBuf in, keys, rows, runs, tmp, out; } prep;         // gpsat_project_batch / gpsat_track_batch (layout: gpsat_prep_plan.h)
+    struct PrepBufs { DevBuf in, out; KeyRunBufs kr; } prep;                 // gpsat_project_batch / gpsat_track_batch (layout: gpsat_prep_plan.h)
     float* dump_dev = nullptr;         // diagnostic build (-DGPSAT_DUMP): caller's device buffer for per-tile factor dumps
     size_t dump_stride = 0;
     unsigned long long prof_host[64 + 8 * 1024 + 4096] = {0};     // counters + event trace + per-workgroup start / end / first empty ring / CU (diagnostic build)
@@ -165,7 +188,7 @@ int record_timing(gpsat_handle* h, int t0 = 0, int t1 = 3) {
     return GPSAT_OK;
 }
 
-// The two-pass idiom of the sort-based steps (select_bin_rows, select_unbin, bin_sort_rows, bin_cell_stats): step(nullptr, bytes)
+// The two-pass idiom of the sort-based steps (select_bin_rows, select_unbin, bin_cell_stats; key_runs behind bin_sort_rows and glue_keyed_sort): step(nullptr, bytes)
 // only reports the scratch it needs, step(scratch, bytes) runs.  `mark`, when given, is recorded between the two: after the
 // reservation, so that an allocation is not timed as kernel time.
 template <class Step>
@@ -178,6 +201,13 @@ int run_with_temp(gpsat_handle* h, DevBuf& tmp, const char* what, hipEvent_t mar
     if (mark) HIP_TRY(hipEventRecord(mark, h->stream));
     e = step(tmp.p, bytes);
     return e != hipSuccess ? failed(e) : GPSAT_OK;
+}
+
+// The counts the keyed sort-and-run-heads stage left on the device, on the host: {groups, rows in them}.  Synchronises.
+int read_key_run_counts(gpsat_handle* h, const gpsat::KeyRuns& k, long long info[2]) {
+    HIP_TRY(hipMemcpyAsync(info, k.counts, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return GPSAT_OK;
 }
 
 // Hyper-parameters per tile: D + 2, or D + 3 with the RationalQuadratic kernel's alpha behind them (gpsat_n_hyper).  Read
@@ -1477,10 +1507,8 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
     if ((rc = begin_call(h))) return rc;
     gpsat_handle::BinBufs& bb = h->bin;
     if ((rc = bb.in.reserve(l.in_bytes))) return rc;
-    if ((rc = bb.keys.reserve(l.keys_bytes))) return rc;
-    if ((rc = bb.rows.reserve(l.rows_bytes))) return rc;
     if ((rc = bb.vals.reserve(l.vals_bytes))) return rc;
-    if ((rc = bb.runs.reserve(l.runs_bytes))) return rc;
+    if ((rc = bb.kr.reserve(l))) return rc;
     // ---- stage: edges and columns to the device
     const size_t nR = (size_t)R;
     gpsat::BinArgs a;
@@ -1509,24 +1537,18 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
     }
     a.x_hi = x_hi; a.y_hi = y_hi;
     a.inv_x = sc.inv_x; a.inv_y = sc.inv_y; a.sentinel = sc.sentinel;
-    a.keys = static_cast<unsigned long long*>(bb.keys.p); a.keys_sorted = a.keys + nR;
-    a.rows = static_cast<unsigned*>(bb.rows.p); a.perm = a.rows + nR;
+    bb.kr.bind(a);
     a.vs = static_cast<double*>(bb.vals.p);
     if (median) { a.vcanon = a.vs + nR; a.vsorted = a.vs + 2 * nR; }
-    char* d_runs = static_cast<char*>(bb.runs.p);
-    a.starts = reinterpret_cast<unsigned*>(d_runs);
-    a.n_cells = reinterpret_cast<long long*>(d_runs + l.runs_n_cells);
-    a.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
+    char* d_runs = static_cast<char*>(bb.kr.runs.p);
     a.n_long = reinterpret_cast<unsigned*>(d_runs + l.runs_n_long);
-    a.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
     a.long_list = reinterpret_cast<unsigned*>(d_runs + l.runs_long_list);
     a.mask = stats;
     // ---- sort (the kernel time starts once its scratch is there), read the counts
-    if ((rc = run_with_temp(h, bb.tmp, "bin_sort_rows", h->ev[1], [&](void* temp, size_t& tb) { return gpsat::bin_sort_rows(a, temp, tb, h->stream); })))
+    if ((rc = run_with_temp(h, bb.kr.tmp, "bin_sort_rows", h->ev[1], [&](void* temp, size_t& tb) { return gpsat::bin_sort_rows(a, temp, tb, h->stream); })))
         return rc;
-    long long info[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(info, a.n_cells, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    long long info[2];
+    if ((rc = read_key_run_counts(h, a, info))) return rc;
     const long long nc = info[0], n_valid = info[1];
     *n_cells = nc;
     // ---- stats, fetch
@@ -1535,7 +1557,7 @@ int gpsat_bin_batch(gpsat_handle* h, int64_t R, const double* x, const double* y
         if ((rc = bb.out.reserve((size_t)nc * (sc.n_stat + 1) * sizeof(double)))) return rc;
         a.out_keys = static_cast<long long*>(bb.out.p);
         a.out = reinterpret_cast<double*>(a.out_keys + nc);
-        if ((rc = run_with_temp(h, bb.tmp, "bin_cell_stats", nullptr,
+        if ((rc = run_with_temp(h, bb.kr.tmp, "bin_cell_stats", nullptr,
                                 [&](void* temp, size_t& tb) { return gpsat::bin_cell_stats(a, nc, n_valid, temp, tb, h->stream); })))
             return rc;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1626,9 +1648,7 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
     for (hipEvent_t& ev : gb.ev)
         if (!ev) HIP_TRY(hipEventCreate(&ev));
     if ((rc = gb.in.reserve(l.in_bytes))) return rc;
-    if ((rc = gb.keys.reserve(l.keys_bytes))) return rc;
-    if ((rc = gb.rows.reserve(l.rows_bytes))) return rc;
-    if ((rc = gb.runs.reserve(l.runs_bytes))) return rc;
+    if ((rc = gb.kr.reserve(l))) return rc;
     // ---- stage
     const size_t nR = (size_t)R;
     gpsat::GlueKeyedArgs a;
@@ -1644,26 +1664,19 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
     const double* d_grad = reinterpret_cast<const double*>(d_in + l.in_vals) + nR;       // behind the one value column
     if (with_grad) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + nR * sizeof(double), grad, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sigma_rows) HIP_TRY(hipMemcpyAsync(d_in + l.in_sigma, sigma_rows, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    a.key = reinterpret_cast<const long long*>(d_in);
+    const long long* d_key = reinterpret_cast<const long long*>(d_in);
     a.pred = reinterpret_cast<const double*>(d_in + l.in_pred);
     a.xprt = reinterpret_cast<const double*>(d_in + l.in_xprt);
     a.vals = reinterpret_cast<const double*>(d_in + l.in_vals);
     a.sigma_rows = sigma_rows ? reinterpret_cast<const double*>(d_in + l.in_sigma) : nullptr;
-    a.keys = static_cast<unsigned long long*>(gb.keys.p); a.keys_sorted = a.keys + nR;
-    a.rows = static_cast<unsigned*>(gb.rows.p); a.perm = a.rows + nR;
-    char* d_runs = static_cast<char*>(gb.runs.p);
-    a.starts = reinterpret_cast<unsigned*>(d_runs);
-    a.n_groups = reinterpret_cast<long long*>(d_runs + l.runs_n_groups);
-    a.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
-    a.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+    gb.kr.bind(a);
     // ---- sort and run heads (the kernel time starts once the scratch is there), read the counts
-    if ((rc = run_with_temp(h, gb.tmp, "glue_keyed_sort", h->ev[1],
-                            [&](void* temp, size_t& tb) { return gpsat::glue_keyed_sort(a, temp, tb, gb.ev[0], h->stream); })))
+    if ((rc = run_with_temp(h, gb.kr.tmp, "glue_keyed_sort", h->ev[1],
+                            [&](void* temp, size_t& tb) { return gpsat::glue_keyed_sort(a, d_key, temp, tb, gb.ev[0], h->stream); })))
         return rc;
     HIP_TRY(hipEventRecord(gb.ev[1], h->stream));
-    long long info[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(info, a.n_groups, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    long long info[2];
+    if ((rc = read_key_run_counts(h, a, info))) return rc;
     const long long ng = info[0];
     *G = ng;
     // ---- reduce, fetch
@@ -1784,11 +1797,7 @@ int gpsat_track_batch(gpsat_handle* h, const gpsat_track* t) {
     gpsat_handle::PrepBufs& pb = h->prep;
     if ((rc = pb.in.reserve(std::max<size_t>(l.in_bytes, 16)))) return rc;
     if ((rc = pb.out.reserve(l.out_bytes))) return rc;
-    if (grouped) {
-        if ((rc = pb.keys.reserve(l.keys_bytes))) return rc;
-        if ((rc = pb.rows.reserve(l.rows_bytes))) return rc;
-        if ((rc = pb.runs.reserve(l.runs_bytes))) return rc;
-    }
+    if (grouped && (rc = pb.kr.reserve(l))) return rc;
     const size_t nN = (size_t)t->n;
     char* d_in = static_cast<char*>(pb.in.p);
     char* d_out = static_cast<char*>(pb.out.p);
@@ -1817,27 +1826,21 @@ int gpsat_track_batch(gpsat_handle* h, const gpsat_track* t) {
     }
     a.block_sums = reinterpret_cast<int*>(d_out + l.out_sums);
     if (grouped) {
-        gpsat::GlueKeyedArgs g;
+        gpsat::KeyRuns g;
         std::memset(&g, 0, sizeof(g));
         g.R = t->n; g.sentinel = sentinel;
-        g.key = reinterpret_cast<const long long*>(d_in + l.in_key);
-        g.keys = static_cast<unsigned long long*>(pb.keys.p); g.keys_sorted = g.keys + nN;
-        g.rows = static_cast<unsigned*>(pb.rows.p); g.perm = g.rows + nN;
-        char* d_runs = static_cast<char*>(pb.runs.p);
-        g.starts = reinterpret_cast<unsigned*>(d_runs);
-        g.n_groups = reinterpret_cast<long long*>(d_runs + l.runs_n_groups);
-        g.n_runs = reinterpret_cast<unsigned*>(d_runs + l.runs_n_runs);
-        g.flags = reinterpret_cast<unsigned char*>(d_runs + l.runs_flags);
+        pb.kr.bind(g);
+        long long* d_key = reinterpret_cast<long long*>(d_in + l.in_key);
         // the kernel time starts in front of the keys, once the sort's scratch is there
-        if ((rc = run_with_temp(h, pb.tmp, "glue_keyed_sort", h->ev[1], [&](void* temp, size_t& tb) {
+        if ((rc = run_with_temp(h, pb.kr.tmp, "glue_keyed_sort", h->ev[1], [&](void* temp, size_t& tb) {
                 if (temp) {
-                    const hipError_t e = gpsat::launch_track_keys(t->n, d_group, reinterpret_cast<long long*>(d_in + l.in_key), h->stream);
+                    const hipError_t e = gpsat::launch_track_keys(t->n, d_group, d_key, h->stream);
                     if (e != hipSuccess) return e;
                 }
-                return gpsat::glue_keyed_sort(g, temp, tb, nullptr, h->stream);
+                return gpsat::glue_keyed_sort(g, d_key, temp, tb, nullptr, h->stream);
             })))
             return rc;
-        a.perm = g.perm; a.heads = g.flags; a.n_valid = g.n_groups + 1;
+        a.perm = g.perm; a.heads = g.flags; a.n_valid = g.counts + 1;
     } else {
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     }

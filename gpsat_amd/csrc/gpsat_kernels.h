@@ -191,6 +191,29 @@ hipError_t select_bin_rows(long long M, int C, const double* pts, const BinSpec&
 hipError_t select_unbin(int T, long long total, const unsigned* seg_off, const int* perm, int* idx, int* idx_out, void* temp,
                         size_t& temp_bytes, hipStream_t stream);
 
+// The keyed sort-and-run-heads stage (gpsat_key_runs.hip); device pointers, carved out of the user's
+// buffers as gpsat_key_runs_plan.h lays them out.  The user's key kernel writes keys[i] and rows[i] = i.
+struct KeyRuns {
+    long long R;                      // rows (< 2^31)
+    unsigned long long sentinel;      // the key of rows that take no part: above every other key, so they sort behind every group
+    unsigned long long *keys, *keys_sorted;   // [R]
+    unsigned *rows, *perm;            // [R] source rows, and the same in sorted order
+    unsigned char* flags;             // [R] 1 at the first row of every run of equal keys
+    unsigned* starts;                 // [R + 1] first sorted row of every run; starts[counts[0]] = counts[1]
+    unsigned* n_runs;                 // [1] runs, the sentinel's included
+    long long* counts;                // [2] runs without the sentinel's (cells, groups), rows in them
+};
+// the head flag of sorted row i
+__device__ __forceinline__ unsigned char key_run_head(const unsigned long long* __restrict__ keys_sorted, long long i) {
+    return (i == 0 || keys_sorted[i] != keys_sorted[i - 1]) ? 1 : 0;
+}
+// Launches the kernel that writes k.flags[0 .. R) from k.keys_sorted (key_run_head), and whatever the user does in that pass.
+typedef void KeyRunsFlags(const void* ctx, hipStream_t stream);
+// Stable sort of (key, row) over the sentinel's bits, head flags (write_flags(ctx, stream); nullptr: the stage's own kernel), run starts,
+// the sentinel's run dropped; leaves counts[0..1] on the device.  temp == nullptr: only the scratch size is returned.  `after_sort`: recorded behind the sort.
+hipError_t key_runs(const KeyRuns& k, KeyRunsFlags* write_flags, const void* ctx, hipEvent_t after_sort, void* temp,
+                    size_t& temp_bytes, hipStream_t stream);
+
 // binning of raw observations (gpsat_bin.hip); device pointers.  The statistic bits are those of include/gpsat_hip.h.
 #ifndef GPSAT_BIN_COUNT
 #define GPSAT_BIN_COUNT  1u
@@ -201,30 +224,22 @@ hipError_t select_unbin(int T, long long total, const unsigned* seg_off, const i
 #define GPSAT_BIN_MAX    32u
 #define GPSAT_BIN_MEDIAN 64u
 #endif
-struct BinArgs {
-    long long R;                      // rows (< 2^31)
+struct BinArgs : KeyRuns {            // sentinel: G * cells, the key of rows outside the grid; counts: non-empty cells, rows inside the grid
     int nx, ny;                       // edges per axis (>= 2); ny is not read when y == nullptr (1-D)
     const double *x, *y, *v;          // [R] coordinates and values; y == nullptr: 1-D
     const int* gid;                   // [R] group of every row, or nullptr (all rows in group 0)
     const double *ex, *ey;            // [nx], [ny] increasing bin edges
     double x_hi, y_hi;                // inclusive upper limit of the last bin (>= the last edge)
     double inv_x, inv_y;              // bins / (last edge - first edge): the guess of bin_index
-    unsigned long long sentinel;      // G * cells: the key of rows outside the grid
-    unsigned long long *keys, *keys_sorted;   // [R]
-    unsigned *rows, *perm;            // [R] source rows, and the same in sorted order
     double* vs;                       // [R] values in sorted order
     double *vcanon, *vsorted;         // [R] median only: vs with one NaN pattern, and every cell's values ascending
-    unsigned char* flags;             // [R] 1 at the first row of every run of equal keys
-    unsigned* starts;                 // [R + 1] first sorted row of every run; starts[n_cells] = rows inside the grid
-    unsigned* n_runs;                 // [1]
-    long long* n_cells;               // [2] non-empty cells, rows inside the grid
-    unsigned* n_long;                 // [1] cells of bin_long_rows() rows or more (zeroed by bin_cell_stats)
+    unsigned* n_long;                // [1] cells of bin_long_rows() rows or more (zeroed by bin_cell_stats)
     unsigned* long_list;              // [R / bin_long_rows() + 1] those cells, in no particular order
     unsigned mask;                    // GPSAT_BIN_* statistics wanted
     long long* out_keys;              // [n_cells] ascending
     double* out;                      // [statistics in bit order][n_cells]
 };
-// key per row, stable sort, gather, run heads; leaves n_cells[0..1] on the device
+// key per row, then key_runs with the gather of the values in its flag pass; leaves counts[0..1] on the device
 hipError_t bin_sort_rows(const BinArgs& a, void* temp, size_t& temp_bytes, hipStream_t stream);
 hipError_t bin_cell_stats(const BinArgs& a, long long n_cells, long long n_valid, void* temp, size_t& temp_bytes, hipStream_t stream);
 int bin_long_rows();                  // rows from which a cell's sums are walked by a wave instead of a lane
@@ -264,17 +279,8 @@ hipError_t launch_smooth(int T, const double* x, const double* y, const double* 
 hipError_t launch_glue(int G, int ndim, int nvars, long long R, const long long* seg, const double* pred, const double* xprt,
                        const double* vals, double sigma, const double* sigma_rows, double* out, hipStream_t stream);
 // keyed glue (gpsat_glue_keyed_batch): rows in any order, grouped by an integer key on the device
-struct GlueKeyedArgs {
-    long long R;                      // rows (< 2^31)
+struct GlueKeyedArgs : KeyRuns {      // sentinel: largest key + 1, the key of ignored rows; counts: distinct keys >= 0, rows that have one
     int ndim, nvars;
-    const long long* key;             // [R] as the caller gave them; < 0: the row is ignored
-    unsigned long long sentinel;      // largest key + 1: the key of ignored rows, they sort behind every group
-    unsigned long long *keys, *keys_sorted;   // [R]
-    unsigned *rows, *perm;            // [R] source rows, and the same in sorted order
-    unsigned char* flags;             // [R] 1 at the first row of every run of equal keys
-    unsigned* starts;                 // [R + 1] first sorted row of every run; starts[n_groups] = rows with a key >= 0
-    unsigned* n_runs;                 // [1]
-    long long* n_groups;              // [2] distinct keys >= 0, rows that have one
     const double *pred, *xprt, *vals, *sigma_rows;   // [ndim][R], [ndim][R], [nvars][R], [R] or nullptr; in SOURCE order
     double sigma;
     double md2;                       // max_dist^2; < 0: no limit
@@ -282,9 +288,8 @@ struct GlueKeyedArgs {
     int* out_count;                   // [G] rows that took part
     double* out;                      // [nvars][G]
 };
-// key per row, stable sort of (key, row), run heads; leaves n_groups[0..1] on the device.  temp == nullptr: only the size
-// of the temporary storage is returned.  `after_sort`, when given, is recorded between the sort and the run detection.
-hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream);
+// key_runs on the keys as a caller gave them: key [R], < 0: the row is ignored.  Also the sort of the grouped tracks.
+hipError_t glue_keyed_sort(const KeyRuns& k, const long long* key, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream);
 // one team of `team` lanes per group, gathering through the permutation; team in {1, 4, 8, 16, 32, 64}
 hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream);
 int glue_keyed_team();                // the team width of the product

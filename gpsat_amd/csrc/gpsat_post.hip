@@ -12,8 +12,8 @@
 // scripts/experiments/r4_smooth_kernel_lds_tiled.patch) measured 390 G pairs/s at 131 072 locations and 17 instead of 229 at
 // 4 096 (a quarter of the waves in flight, one dependent accumulation chain per thread) -- not adopted.
 //   glue_keyed_kernel : the same average over rows that arrive in ANY order with an integer key per row (held-out
-//                   predictions keyed by observation: groups of 3..20 rows, millions of them).  A stable rocPRIM radix sort
-//                   of (key, source row) over the bits of the largest key, run heads by flag + select (as gpsat_bin.hip),
+//                   predictions keyed by observation: groups of 3..20 rows, millions of them).  The keyed sort-and-run-heads
+//                   stage (gpsat_key_runs.hip: a stable sort of (key, source row), run starts, ignored rows dropped),
 //                   then one TEAM of lanes per group that gathers its rows through the permutation: lane l of the team adds
 //                   the group's rows l, l + W, l + 2W, ... in that order and a fixed xor tree over the team's W lanes joins
 //                   them.  A group's bits are a function of its own rows in source order (the sort is stable) and of W, a
@@ -22,9 +22,7 @@
 //                   which has a term from the weights' own dependence on the prediction location.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include <type_traits>
 #include "gpsat_kernels.h"
 
 namespace gpsat {
@@ -110,29 +108,12 @@ hipError_t launch_glue(int G, int ndim, int nvars, long long R, const long long*
 }
 
 // ---- keyed glue
-__global__ void __launch_bounds__(256) glue_key_kernel(const GlueKeyedArgs a) {
+__global__ void __launch_bounds__(256) glue_key_kernel(const KeyRuns a, const long long* __restrict__ key) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.R) return;
-    const long long k = a.key[i];
+    const long long k = key[i];
     a.keys[i] = k < 0 ? a.sentinel : (unsigned long long)k;
     a.rows[i] = (unsigned)i;
-}
-
-__global__ void __launch_bounds__(256) glue_flag_kernel(const GlueKeyedArgs a) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.R) return;
-    a.flags[i] = (i == 0 || a.keys_sorted[i] != a.keys_sorted[i - 1]) ? 1 : 0;
-}
-
-// runs -> groups: the run of ignored rows, when there is one, is the last; starts[n_groups] = first row past the groups
-__global__ void glue_finish_kernel(const GlueKeyedArgs a) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    long long n = *a.n_runs;
-    long long valid = a.R;
-    if (n > 0 && a.keys_sorted[a.starts[n - 1]] == a.sentinel) { valid = a.starts[n - 1]; --n; }
-    a.starts[n] = (unsigned)valid;
-    a.n_groups[0] = n;
-    a.n_groups[1] = valid;
 }
 
 // W lanes per group, 256 / W groups per workgroup.  No lane leaves before the shuffles: a team past the last group walks an
@@ -256,67 +237,40 @@ __global__ void __launch_bounds__(256) glue_keyed_grad_kernel(const GlueKeyedArg
     }
 }
 
-static inline int glue_key_bits(unsigned long long sentinel) {
-    int bits = 1;
-    while (bits < 64 && (sentinel >> bits) != 0) ++bits;
-    return bits;
-}
-
-hipError_t glue_keyed_sort(const GlueKeyedArgs& a, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream) {
-    const int bits = glue_key_bits(a.sentinel);
-    rocprim::counting_iterator<unsigned> rows0(0);
-    if (!temp) {
-        size_t t1 = 0, t2 = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, t1, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);
-        if (e != hipSuccess) return e;
-        e = rocprim::select(nullptr, t2, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
-        temp_bytes = t1 > t2 ? t1 : t2;
-        return e;
-    }
-    const unsigned grid = (unsigned)((a.R + 255) / 256);
-    hipLaunchKernelGGL(glue_key_kernel, dim3(grid), dim3(256), 0, stream, a);
-    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, a.keys, a.keys_sorted, a.rows, a.perm, (size_t)a.R, 0, bits, stream);   // stable
-    if (e != hipSuccess) return e;
-    if (after_sort && (e = hipEventRecord(after_sort, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(glue_flag_kernel, dim3(grid), dim3(256), 0, stream, a);
-    e = rocprim::select(temp, temp_bytes, rows0, a.flags, a.starts, a.n_runs, (size_t)a.R, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(glue_finish_kernel, dim3(1), dim3(64), 0, stream, a);
-    return hipGetLastError();
+hipError_t glue_keyed_sort(const KeyRuns& k, const long long* key, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream) {
+    if (temp) hipLaunchKernelGGL(glue_key_kernel, dim3((unsigned)((k.R + 255) / 256)), dim3(256), 0, stream, k, key);
+    return key_runs(k, nullptr, nullptr, after_sort, temp, temp_bytes, stream);
 }
 
 constexpr int GLUE_KEYED_TEAM = 8;
 int glue_keyed_team() { return GLUE_KEYED_TEAM; }
 
-hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream) {
-    if (G <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
+// launch(std::integral_constant<int, W>()) for the team width W of the call
+template <class Launch>
+static hipError_t dispatch_team(int team, Launch launch) {
     switch (team) {
-        case 1: hipLaunchKernelGGL(glue_keyed_kernel<1>, grid, block, 0, stream, a, G); break;
-        case 4: hipLaunchKernelGGL(glue_keyed_kernel<4>, grid, block, 0, stream, a, G); break;
-        case 8: hipLaunchKernelGGL(glue_keyed_kernel<8>, grid, block, 0, stream, a, G); break;
-        case 16: hipLaunchKernelGGL(glue_keyed_kernel<16>, grid, block, 0, stream, a, G); break;
-        case 32: hipLaunchKernelGGL(glue_keyed_kernel<32>, grid, block, 0, stream, a, G); break;
-        case 64: hipLaunchKernelGGL(glue_keyed_kernel<64>, grid, block, 0, stream, a, G); break;
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 8: launch(std::integral_constant<int, 8>()); break;
+        case 16: launch(std::integral_constant<int, 16>()); break;
+        case 32: launch(std::integral_constant<int, 32>()); break;
+        case 64: launch(std::integral_constant<int, 64>()); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream) {
+    if (G <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
+    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_kernel<decltype(w)::value>, grid, block, 0, stream, a, G); });
 }
 
 hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
                                   hipStream_t stream) {
     if (G <= 0) return hipSuccess;
     const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
-    switch (team) {
-        case 1: hipLaunchKernelGGL(glue_keyed_grad_kernel<1>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        case 4: hipLaunchKernelGGL(glue_keyed_grad_kernel<4>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        case 8: hipLaunchKernelGGL(glue_keyed_grad_kernel<8>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        case 16: hipLaunchKernelGGL(glue_keyed_grad_kernel<16>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        case 32: hipLaunchKernelGGL(glue_keyed_grad_kernel<32>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        case 64: hipLaunchKernelGGL(glue_keyed_grad_kernel<64>, grid, block, 0, stream, a, G, grad, out_grad); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_grad_kernel<decltype(w)::value>, grid, block, 0, stream, a, G, grad, out_grad); });
 }
 
 }  // namespace gpsat

@@ -12,8 +12,8 @@
 //       NaN in -> NaN out; rho = 0 -> (lon_0, +-90); outside the disc ((rho / a)^2 > 2 q_p) -> +inf twice.
 //   prep_delta_kernel<RUNS> : diff_distance(x, p=2, k=1) inside groups and the flag of every row -- delta > cut_off (NaN is
 //       false, as guess_track_num has it) or the first row of a later group; RUNS: cols[0] differs from the row before
-//       (track_num_for_date).  The rows are taken through the permutation of gpsat_post.hip's stable radix sort of the group
-//       codes (glue_keyed_sort: reused, not restated), so a group's rows keep the order they came in.  Difference, square, sum
+//       (track_num_for_date).  The rows are taken through the permutation of the keyed sort-and-run-heads stage on the group
+//       codes (gpsat_key_runs.hip, behind the keyed glue's key kernel: glue_keyed_sort), so a group's rows keep the order they came in.  Difference, square, sum
 //       from the left and root are single rounded operations (__dsub_rn ...): -ffp-contract has nothing to fuse.
 //   the scan : track = start_track + inclusive prefix sum of the flags (RUNS: the row's position minus the inclusive prefix
 //       MAXIMUM of the flagged positions), int32, three passes over blocks of PREP_BLOCK rows: prep_delta_kernel leaves what a

@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "gpsat_hip.h"
+#include "gpsat_key_runs_plan.h"
 
 namespace gpsat {
 
@@ -117,14 +118,11 @@ inline ScanGeometry prep_scan_geometry(int64_t n, int block) {
 }
 
 // Bytes of the handle's buffers and the byte offsets of what lies in them.  Device mode stages nothing: `in` holds the 64-bit
-// keys only, `out` the block sums only.
-struct TrackLayout {
+// keys only, `out` the block sums only.  keys, rows and runs are the stage's (KeyRunsLayout; runs_counts: n_groups [2]);
+// all 0 without groups.
+struct TrackLayout : KeyRunsLayout {
     // `in`: the columns [n_cols][n], the codes [n] int32 rounded to 8 B, the 64-bit keys of the sort [n] (the last two with groups)
-    size_t in_bytes, in_cols, in_group, in_key;
-    size_t keys_bytes;                // [2][n] 64-bit keys: as given (negative ones replaced), sorted; 0 without groups
-    size_t rows_bytes;                // [2][n] 32-bit rows: source, sorted; 0 without groups
-    // `runs`: starts [n + 1] rounded to 256 B, a 256-B block with n_groups [2] and n_runs, the head flags [n]; 0 without groups
-    size_t runs_bytes, runs_n_groups, runs_n_runs, runs_flags;
+    size_t in_bytes, in_cols, in_group, in_key, runs_n_groups;        // runs_n_groups: the stage's runs_counts, by the tracks' name
     // `out`: delta [n] fp64, track [n], order [n] (host mode), the block sums of the scan
     size_t out_bytes, out_track, out_order, out_sums;
 };
@@ -139,15 +137,8 @@ inline TrackLayout track_layout(int64_t n, int n_cols, bool has_group, bool host
         l.in_key = at; at += nN * sizeof(int64_t);
     }
     l.in_bytes = at;
-    if (has_group) {
-        l.keys_bytes = 2 * nN * sizeof(unsigned long long);
-        l.rows_bytes = 2 * nN * sizeof(unsigned);
-        const size_t starts_bytes = ((nN + 1) * sizeof(unsigned) + 255) & ~size_t(255);
-        l.runs_n_groups = starts_bytes;
-        l.runs_n_runs = starts_bytes + 16;
-        l.runs_flags = starts_bytes + 256;
-        l.runs_bytes = l.runs_flags + nN;
-    }
+    if (has_group) static_cast<KeyRunsLayout&>(l) = key_runs_layout(n);
+    l.runs_n_groups = l.runs_counts;
     at = 0;
     if (host_mode) {
         at += nN * sizeof(double);

@@ -1,8 +1,9 @@
 // Host check of gpsat_amd/csrc/gpsat_prep_plan.h: the launch geometry, the buffer layout and the refusals of
-// gpsat_project_batch / gpsat_track_batch, without a device.  Built with the host sanitizers and run directly:
+// gpsat_project_batch / gpsat_track_batch, without a device; and of gpsat_key_runs_plan.h, the layout of the keyed
+// sort-and-run-heads stage, with the three layouts built on it (tracks here, binning and the keyed glues from their headers).  Built with the host sanitizers and run directly:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I gpsat_amd/csrc -I include tests/prep_plan_host_check.cpp
 // usage: prep_plan_host_check BLOCK      (gpsat::prep_scan_block() of the library)
-// Prints one line per case ("blocks n value", "scan n blocks rounds", "layout ...", "refuse <what>: <message>"); a failed
+// Prints one line per case ("blocks n value", "scan n blocks rounds", "layout ...", "key_runs ...", "refuse <what>: <message>"); a failed
 // internal check ends it non-zero.
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,8 @@
 #include <vector>
 
 #include "gpsat_prep_plan.h"
+#include "gpsat_bin_plan.h"
+#include "gpsat_glue_plan.h"
 
 static int failures = 0;
 #define CHECK(cond)                                                          \
@@ -109,6 +112,31 @@ int main(int argc, char** argv) {
                         std::printf("layout %lld %d %d %zu %zu %zu %zu %zu\n", (long long)n, grouped, host, l.in_bytes, l.in_key, l.runs_bytes,
                                     l.out_sums, l.out_bytes);
                 }
+
+    // ---- the stage's layout: keys and rows twice, starts [n + 1] rounded to 256 B, the counts at +0 and n_runs at +16 of a
+    // 256-B block, the flags [n] behind it; and its three users' layouts, field by field
+    for (int64_t n : {0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024}) {
+        const gpsat::KeyRunsLayout k = gpsat::key_runs_layout(n);
+        const size_t nN = (size_t)n, starts = ((nN + 1) * 4 + 255) / 256 * 256;
+        CHECK(k.keys_bytes == 16 * nN && k.rows_bytes == 8 * nN);
+        CHECK(k.runs_counts == starts && k.runs_n_runs == starts + 16 && k.runs_flags == starts + 256);
+        CHECK(k.runs_bytes == starts + 256 + nN);
+        auto same = [&](const gpsat::KeyRunsLayout& l) {
+            return l.keys_bytes == k.keys_bytes && l.rows_bytes == k.rows_bytes && l.runs_counts == k.runs_counts &&
+                   l.runs_n_runs == k.runs_n_runs && l.runs_flags == k.runs_flags;
+        };
+        const gpsat::TrackLayout t = gpsat::track_layout(n, 2, true, true, B);
+        CHECK(same(t) && t.runs_bytes == k.runs_bytes && t.runs_n_groups == k.runs_counts);
+        const gpsat::GlueKeyedLayout g = gpsat::glue_keyed_layout(n, 2, 3);
+        CHECK(same(g) && g.runs_bytes == k.runs_bytes);
+        // binning: n_long at +32 of the block, the flags rounded to 256 B, the list of long cells behind them
+        const gpsat::BinLayout b = gpsat::bin_layout(n, 11, 11, true, true, true, 1024);
+        const size_t flags = (nN + 255) / 256 * 256;
+        CHECK(same(b) && b.runs_n_cells == k.runs_counts && b.runs_n_long == starts + 32 && b.runs_long_list == starts + 256 + flags);
+        CHECK(b.runs_bytes == starts + 256 + flags + (nN / 1024 + 1) * 4);
+        std::printf("key_runs %lld %zu %zu %zu %zu %zu %zu\n", (long long)n, k.keys_bytes, k.rows_bytes, k.runs_bytes, k.runs_counts,
+                    k.runs_n_runs, k.runs_flags);
+    }
 
     // ---- the constants of the projection
     const gpsat::ProjConst pc = gpsat::proj_const();

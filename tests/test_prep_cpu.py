@@ -476,3 +476,6 @@ def test_plan_header_under_the_host_sanitizers(tmp_path):
     const = [float(v) for v in next(l for l in lines if l.startswith("const ")).split()[1:]]
     assert const == [pn.E2, pn.E, pn.INV_2E, pn.QP, pn.QP_LO]           # the host's constants are the restatement's, bit for bit
     assert sum(l.startswith("refuse project") for l in lines) >= 19 and sum(l.startswith("refuse track") for l in lines) >= 25
+    key_runs = {int(l.split()[1]): tuple(map(int, l.split()[2:])) for l in lines if l.startswith("key_runs ")}
+    assert sorted(key_runs) == [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024]
+    assert key_runs[63] == (1008, 504, 256 + 256 + 63, 256, 272, 512) and key_runs[64] == (1024, 512, 512 + 256 + 64, 512, 528, 768)
