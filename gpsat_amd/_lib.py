@@ -69,6 +69,12 @@ class GpsatPredGrad(C.Structure):
     _fields_ = [("f_grad", C.c_void_p), ("f_grad_var", C.c_void_p), ("reserved", C.c_int32 * 8)]
 
 
+class GpsatPredHess(C.Structure):
+    _fields_ = [("f_hess", C.c_void_p), ("f_hess_var", C.c_void_p), ("f_lap", C.c_void_p), ("f_lap_var", C.c_void_p),
+                ("f_grad", C.c_void_p), ("f_grad_var", C.c_void_p), ("lap_weight", C.c_double * 4), ("dims", C.c_uint32),
+                ("reserved", C.c_int32 * 7)]
+
+
 class GpsatCv(C.Structure):
     _fields_ = [("fold", C.c_void_p), ("cv_mean", C.c_void_p), ("cv_f_var", C.c_void_p), ("cv_y_var", C.c_void_p),
                 ("reserved", C.c_int32 * 8)]
@@ -199,6 +205,8 @@ SIGNATURES = {
        for row, name in variants.JOINT_ENTRY.items()},
     # the gradient of the posterior mean: the plain call with gpsat_pred_grad behind the batch
     variants.PRED_GRAD_ENTRY: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(globals()[variants.PRED_GRAD_STRUCT])], False),
+    # its second derivatives, with the gradient when asked for: gpsat_pred_hess behind the batch
+    variants.PRED_HESS_ENTRY: (_I, [_P, C.POINTER(GpsatBatch), C.POINTER(globals()[variants.PRED_HESS_STRUCT])], False),
 }
 EXPORTS = list(SIGNATURES)
 OPTIONAL_EXPORTS = [name for name, (_, _, required) in SIGNATURES.items() if not required]

@@ -3,7 +3,7 @@
 // validation, device buffers owned by the handle, cost-sorted tile order, launch, copy-back.
 // Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
 // translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
-//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise / check_pred_grad, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
+//   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise / check_pred_grad / check_pred_hess, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
 //     setup_*, launch, fetch_batch / fetch_cv, record_timing.
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
@@ -146,6 +146,7 @@ struct gpsat_handle : HandleQueue {
     DevBuf cvr_cov;                   // refitted cross-validation with the joint density: cov_off, the derived batch's f_cov, sn2, residuals, lpd
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
     DevBuf pgrad;                     // gpsat_fit_predict_batch_grad, host mode: f_grad, f_grad_var [sumP, D] each
+    DevBuf phess;                     // gpsat_fit_predict_batch_hess, host mode: its (up to) six outputs, one behind the other
     DevBuf memo;                      // 64 bytes of developer statistics, then the evaluation memo [T][MEMO_WORDS] (fp32 L-BFGS batches)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     // gpsat_select_batch_ex.  gpsat_smooth_batch and gpsat_glue_batch stage their inputs in sel.pts (glue: its segments in
@@ -711,6 +712,7 @@ struct DenseJob {
     int mean = GPSAT_MEAN_ZERO;       // GPSAT_MEAN_CONSTANT: gpsat_fit_predict_batch_mean with a trainable constant mean
     const void* obs_var = nullptr;    // gpsat_fit_predict_batch_noise: noise variances per observation, behind gpsat::check_noise
     const gpsat_pred_grad* pred_grad = nullptr;   // gpsat_fit_predict_batch_grad: the two outputs, behind gpsat::check_pred_grad
+    const gpsat_pred_hess* pred_hess = nullptr;   // gpsat_fit_predict_batch_hess: outputs, dims and weights, behind gpsat::check_pred_hess
     bool ms_on;                       // ms given and the optimiser runs
     BatchDims dims;
     const double* theta0;             // the caller's, or clipped into the bounds (multi-start)
@@ -725,7 +727,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     const bool f64 = b->dtype == GPSAT_F64;
     const gpsat::F64Variant variant = j.cv ? gpsat::CV : b->kernel == GPSAT_KERNEL_RQ ? gpsat::RQ
                                       : j.mean == GPSAT_MEAN_CONSTANT ? gpsat::MEAN : j.obs_var ? gpsat::NOISE
-                                      : j.pred_grad ? gpsat::GRAD : gpsat::PLAIN;
+                                      : j.pred_grad ? gpsat::GRAD : j.pred_hess ? gpsat::HESS : gpsat::PLAIN;
     gpsat::PlanInput in = {b->T, b->D, f64, b->obs_off, d.maxP, d.want_cov, d.sumP > 0, b->optimiser, b->max_iter,
                            h->num_cu, h->wg_per_cu, solo || variant != gpsat::PLAIN, unsliced, read_dev_knobs()};     // a variant: one workgroup per tile
     gpsat::TilePlan p;
@@ -768,6 +770,37 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
             ga.f_grad = ga.f_grad_var = static_cast<double*>(h->ws.p);
         }
     }
+    // the second derivatives' outputs in the same way.  hess_out: (the caller's pointer, the kernel's, bytes) of what was asked for
+    gpsat::HessArgs ha;
+    struct { void* host; double** dev; size_t bytes; } hess_out[6];
+    int n_hess_out = 0;
+    if (const gpsat_pred_hess* ph = j.pred_hess) {
+        const int m = __builtin_popcount(ph->dims);
+        ha.dims = ph->dims;
+        ha.npair = m * (m + 1) / 2;
+        bool lap = ph->f_lap || ph->f_lap_var;
+        for (int k = 0; k < 4; ++k) { ha.lap_w[k] = ph->lap_weight[k]; lap = lap || ph->lap_weight[k] > 0.0; }
+        const size_t pair_bytes = (size_t)d.sumP * ha.npair * sizeof(double), lap_bytes = (size_t)d.sumP * sizeof(double);
+        hess_out[n_hess_out++] = {ph->f_hess, &ha.f_hess, pair_bytes};
+        hess_out[n_hess_out++] = {ph->f_hess_var, &ha.f_hess_var, pair_bytes};
+        if (lap) {
+            hess_out[n_hess_out++] = {ph->f_lap, &ha.f_lap, lap_bytes};
+            hess_out[n_hess_out++] = {ph->f_lap_var, &ha.f_lap_var, lap_bytes};
+        }
+        if (ph->f_grad) {
+            hess_out[n_hess_out++] = {ph->f_grad, &ha.f_grad, grad_bytes};
+            hess_out[n_hess_out++] = {ph->f_grad_var, &ha.f_grad_var, grad_bytes};
+        }
+        size_t total = 0;
+        for (int k = 0; k < n_hess_out; ++k) total += hess_out[k].bytes;
+        if (b->memory == GPSAT_MEM_HOST && (rc = h->phess.reserve(std::max<size_t>(total, 16)))) return rc;
+        size_t at = 0;
+        for (int k = 0; k < n_hess_out; ++k) {
+            if (b->memory == GPSAT_MEM_HOST) *hess_out[k].dev = reinterpret_cast<double*>(static_cast<char*>(h->phess.p) + at);
+            else *hess_out[k].dev = static_cast<double*>(d.sumP > 0 ? hess_out[k].host : h->ws.p);   // sum P = 0: nothing is written
+            at += hess_out[k].bytes;
+        }
+    }
     gpsat::CvArgs ca;
     if (j.cv && (rc = stage_cv(h, b, j.cv, j.cv_joint, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
@@ -783,7 +816,8 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     a.prof = static_cast<unsigned long long*>(h->prof.p);
 #endif
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, j.pred_grad ? &ga : nullptr, p.grid, p.smem, h->stream));
+    HIP_TRY(launch(b->D, a, j.cv ? &ca : nullptr, j.obs_var ? &na : nullptr, j.pred_grad ? &ga : nullptr, j.pred_hess ? &ha : nullptr,
+                   p.grid, p.smem, h->stream));
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, j.cv_joint, d, ca))) return rc;
@@ -791,6 +825,9 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
         HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad, ga.f_grad, grad_bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad_var, ga.f_grad_var, grad_bytes, hipMemcpyDeviceToHost, h->stream));
     }
+    if (j.pred_hess && b->memory == GPSAT_MEM_HOST)
+        for (int k = 0; k < n_hess_out; ++k)
+            if (hess_out[k].bytes > 0) HIP_TRY(hipMemcpyAsync(hess_out[k].host, *hess_out[k].dev, hess_out[k].bytes, hipMemcpyDeviceToHost, h->stream));
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 #ifdef GPSAT_PROFILE
@@ -805,7 +842,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
 
 int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms, const gpsat_cv* cv = nullptr,
                 const gpsat_mean* mn = nullptr, const gpsat_noise* nz = nullptr, const gpsat_cv_joint* jt = nullptr,
-                const gpsat_pred_grad* pg = nullptr) {
+                const gpsat_pred_grad* pg = nullptr, const gpsat_pred_hess* ph = nullptr) {
     if (!h || !b) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch: NULL handle or batch");
     if (b->T == 0) return GPSAT_OK;
     DenseJob j;
@@ -827,6 +864,11 @@ int fit_predict(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* m
         char why[200];
         if ((rc = gpsat::check_pred_grad(b, pg, why, sizeof(why)))) return fail(rc, why);
         j.pred_grad = pg;
+    }
+    if (ph) {
+        char why[240];
+        if ((rc = gpsat::check_pred_hess(b, ph, why, sizeof(why)))) return fail(rc, why);
+        j.pred_hess = ph;
     }
     BatchDims& d = j.dims;
     d.want_cov = b->f_cov != nullptr;             // optional full posterior covariance: one P_t x P_t block per tile
@@ -1278,6 +1320,11 @@ int gpsat_fit_predict_batch_noise(gpsat_handle* h, const gpsat_batch* b, const g
 int gpsat_fit_predict_batch_grad(gpsat_handle* h, const gpsat_batch* b, const gpsat_pred_grad* pg) {
     if (!pg) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_grad: pred_grad is NULL");
     return fit_predict(h, b, nullptr, nullptr, nullptr, nullptr, nullptr, pg);
+}
+
+int gpsat_fit_predict_batch_hess(gpsat_handle* h, const gpsat_batch* b, const gpsat_pred_hess* ph) {
+    if (!ph) return fail(GPSAT_EINVAL, "gpsat_fit_predict_batch_hess: pred_hess is NULL");
+    return fit_predict(h, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ph);
 }
 
 int gpsat_fit_predict_batch_ms(gpsat_handle* h, const gpsat_batch* b, const gpsat_multistart* ms) {

@@ -128,6 +128,21 @@ struct GradArgs {
     double* f_grad = nullptr;
     double* f_grad_var = nullptr;
 };
+// The second derivatives of the posterior mean at the prediction points (gpsat_fit_predict_batch_hess); device pointers.  The
+// pairs a <= b of the coordinates in `dims` (bit a: coordinate a), a ascending, then b, are the npair columns of f_hess and
+// f_hess_var, [sumP, npair] row-major.  f_lap / f_lap_var [sumP]: sum_a lap_w[a] d2f/dx_a^2 and its variance; both null: no
+// such pass.  f_grad / f_grad_var [sumP, D]: the grad row's two outputs from the same launch; both null: not asked for.
+struct HessArgs {
+    double* f_hess = nullptr;
+    double* f_hess_var = nullptr;
+    double* f_lap = nullptr;
+    double* f_lap_var = nullptr;
+    double* f_grad = nullptr;
+    double* f_grad_var = nullptr;
+    double lap_w[4] = {0.0, 0.0, 0.0, 0.0};
+    unsigned dims = 0;
+    int npair = 0;
+};
 #define GPSAT_MAX_CV_FOLD 256         // largest fold: sum g^2 <= 256 N doubles fits the prediction scratch of a tile's workspace
 
 size_t shared_bytes(int D, int NBmax);
@@ -140,18 +155,22 @@ size_t shared_bytes_f64_w4(int D, int NBmax);
 size_t workspace_doubles_per_wg_f64_w4(int NBmax, int PCcov);
 int state_words_f64_w4();
 // The variants of the fp64 tile loop (the table at the top of gpsat_kernels_f64.hip), launch_tiles_f64[_variant][_w4], one
-// signature: `cv` is null unless the variant is cv, `nz` unless it is noise, `gr` unless it is grad.  A (D, a.kernel, a.team_size) a variant does not have: hipErrorInvalidValue.
+// signature: `cv` is null unless the variant is cv, `nz` unless it is noise, `gr` unless it is grad, `hs` unless it is hess.  A (D, a.kernel, a.team_size) a variant does not have: hipErrorInvalidValue.
 //   plain  kernels 0..3, D = 1..4, H = D + 2; teams in the 8-wave build
 //   cv     the same with the held-out phase (gpsat_fit_predict_batch_cv), one workgroup per tile
 //   rq     the RationalQuadratic covariance function: kernel 4, D = 1..3, H = D + 3, one workgroup per tile
 //   mean   a trainable constant mean: kernels 0..3, D = 1..3, H = D + 3 with c last, one workgroup per tile
 //   noise  known noise variances per observation (NoiseArgs): kernels 0..3, D = 1..4, H = D + 2, one workgroup per tile
 //   grad   the gradient of the posterior mean and its variance (GradArgs): kernels 0, 2, 3, D = 1..4, H = D + 2, one workgroup per tile, no f_cov
+//   hess   the second derivatives of the posterior mean, their variances and a weighted Laplacian (HessArgs), with the grad
+//          row's outputs when asked for: kernels 0, 3, D = 1..4, H = D + 2, one workgroup per tile, no f_cov
 // LDS, workspace and state words of every variant are those of the build of the same wave count.
-typedef hipError_t F64Launch(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, int grid, size_t smem, hipStream_t stream);
+typedef hipError_t F64Launch(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, const HessArgs* hs,
+                             int grid, size_t smem, hipStream_t stream);
 F64Launch launch_tiles_f64, launch_tiles_f64_w4, launch_tiles_f64_cv, launch_tiles_f64_cv_w4;
 F64Launch launch_tiles_f64_rq, launch_tiles_f64_rq_w4, launch_tiles_f64_mean, launch_tiles_f64_mean_w4;
 F64Launch launch_tiles_f64_noise, launch_tiles_f64_noise_w4, launch_tiles_f64_grad, launch_tiles_f64_grad_w4;
+F64Launch launch_tiles_f64_hess, launch_tiles_f64_hess_w4;
 size_t pq_floats_per_slot(int D, int NBmax);              // deferred-prediction snapshot slot (KernelArgs::pq_stride)
 size_t workspace_floats_per_wg(int NBmax, int PCcov);     // PCcov: prediction chunks kept for f_cov (0 = none)
 hipError_t launch_tiles(int D, const KernelArgs& a, int grid, size_t smem, hipStream_t stream);

@@ -18,14 +18,14 @@
 
 namespace gpsat {
 // ---- which object this is ---------------------------------------------------------------------
-// The file is compiled twelve times: with 8 waves per workgroup and one workgroup per CU (the default) or, -DGPSAT_F64_W4,
+// The file is compiled fourteen times: with 8 waves per workgroup and one workgroup per CU (the default) or, -DGPSAT_F64_W4,
 // with 4 waves and two workgroups per CU for tiles whose LDS fits twice (a second TILE per CU overlaps the serial diagonal
 // work of the first) -- and each of the two as one VARIANT of the one-workgroup-per-tile kernel: plain, or with one of
-// -DGPSAT_F64_CV, -DGPSAT_F64_RQ, -DGPSAT_F64_MEAN, -DGPSAT_F64_NOISE, -DGPSAT_F64_GRAD.  A variant is one row of the table below: the row becomes
-// the constants CV, MEAN, NOISE, GRAD, KN_SET and D_MAX, the templates ask them with `if constexpr`, and an object instantiates
+// -DGPSAT_F64_CV, -DGPSAT_F64_RQ, -DGPSAT_F64_MEAN, -DGPSAT_F64_NOISE, -DGPSAT_F64_GRAD, -DGPSAT_F64_HESS.  A variant is one row of the table below: the row becomes
+// the constants CV, MEAN, NOISE, GRAD, HESS, KN_SET and D_MAX, the templates ask them with `if constexpr`, and an object instantiates
 // gp_tile_kernel_f64<D, KN> for the row's D and KN only, in the row's namespace, behind the row's one exported entry point.
 // A new variant is a new row and the `if constexpr` that reads its constant.  Beyond this block the preprocessor sees a
-// variant in three places: the kernel's parameter list (cv, noise, grad), the host's sizing functions at the end of the file (plain),
+// variant in three places: the kernel's parameter list (cv, noise, grad, hess), the host's sizing functions at the end of the file (plain),
 // and GPSAT_OPT_IDENTITY below (mean), which gpsat_opt.h asks with #ifdef.
 //   plain  gpsat_fit_predict_batch: the four stationary kernels, H = D + 2, theta = (l_0 .. l_{D-1}, kernel variance,
 //          likelihood variance).  The only variant with the team kernel (8 waves) and the host's sizing functions.
@@ -44,14 +44,20 @@ namespace gpsat {
 //   grad   the gradient of the posterior mean with respect to the prediction point, and its posterior variance per component
 //          (gpsat_fit_predict_batch_grad): predict_grad_tile behind every tile's prediction, D more passes of its triangular
 //          solve.  Matern-1/2 is not mean-square differentiable and has no kernel here.  One more parameter, GradArgs.
-//                         namespace         entry point             sizing,                                kernels   D up
-//                         8 / 4 waves       (+ _w4)                 teams   CV     MEAN   NOISE  GRAD      (bit KN)  to
-#define F64_VARIANT_plain  f64k,   f64k4,    launch_tiles_f64,       true,   false, false, false, false,    0x0f,     4
-#define F64_VARIANT_cv     f64kcv, f64k4cv,  launch_tiles_f64_cv,    false,  true,  false, false, false,    0x0f,     4
-#define F64_VARIANT_rq     f64krq, f64k4rq,  launch_tiles_f64_rq,    false,  false, false, false, false,    0x10,     3
-#define F64_VARIANT_mean   f64kmn, f64k4mn,  launch_tiles_f64_mean,  false,  false, true,  false, false,    0x0f,     3
-#define F64_VARIANT_noise  f64knz, f64k4nz,  launch_tiles_f64_noise, false,  false, false, true,  false,    0x0f,     4
-#define F64_VARIANT_grad   f64kgr, f64k4gr,  launch_tiles_f64_grad,  false,  false, false, false, true,     0x0d,     4
+//   hess   the second derivatives of the posterior mean with respect to the prediction point, their posterior variances and a
+//          weighted Laplacian (gpsat_fit_predict_batch_hess): predict_hess_tile behind every tile's prediction, one more pass
+//          of its triangular solve per pair of the chosen coordinates and one for the Laplacian.  RBF and Matern-5/2 only
+//          (Matern-3/2's derivative process is not mean-square differentiable).  The row's kernel holds the grad row's phase
+//          too, for a call that asks for both.  One more parameter, HessArgs.
+//                         namespace         entry point             sizing,                                       kernels   D up
+//                         8 / 4 waves       (+ _w4)                 teams   CV     MEAN   NOISE  GRAD   HESS      (bit KN)  to
+#define F64_VARIANT_plain  f64k,   f64k4,    launch_tiles_f64,       true,   false, false, false, false, false,    0x0f,     4
+#define F64_VARIANT_cv     f64kcv, f64k4cv,  launch_tiles_f64_cv,    false,  true,  false, false, false, false,    0x0f,     4
+#define F64_VARIANT_rq     f64krq, f64k4rq,  launch_tiles_f64_rq,    false,  false, false, false, false, false,    0x10,     3
+#define F64_VARIANT_mean   f64kmn, f64k4mn,  launch_tiles_f64_mean,  false,  false, true,  false, false, false,    0x0f,     3
+#define F64_VARIANT_noise  f64knz, f64k4nz,  launch_tiles_f64_noise, false,  false, false, true,  false, false,    0x0f,     4
+#define F64_VARIANT_grad   f64kgr, f64k4gr,  launch_tiles_f64_grad,  false,  false, false, false, true,  false,    0x0d,     4
+#define F64_VARIANT_hess   f64khs, f64k4hs,  launch_tiles_f64_hess,  false,  false, false, false, false, true,     0x09,     4
 #ifndef GPSAT_F64_CV
 #define GPSAT_F64_CV 0
 #endif
@@ -67,9 +73,12 @@ namespace gpsat {
 #ifndef GPSAT_F64_GRAD
 #define GPSAT_F64_GRAD 0
 #endif
+#ifndef GPSAT_F64_HESS
+#define GPSAT_F64_HESS 0
+#endif
 // A variant adds ONE thing to the plain kernel; no combination is built, dispatched or tested.
-static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE + GPSAT_F64_GRAD <= 1,
-              "GPSAT_F64_CV, GPSAT_F64_RQ, GPSAT_F64_MEAN, GPSAT_F64_NOISE and GPSAT_F64_GRAD are builds of their own");
+static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE + GPSAT_F64_GRAD + GPSAT_F64_HESS <= 1,
+              "GPSAT_F64_CV, GPSAT_F64_RQ, GPSAT_F64_MEAN, GPSAT_F64_NOISE, GPSAT_F64_GRAD and GPSAT_F64_HESS are builds of their own");
 #if GPSAT_F64_CV
 #define F64_VARIANT F64_VARIANT_cv
 #elif GPSAT_F64_RQ
@@ -80,6 +89,8 @@ static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE + G
 #define F64_VARIANT F64_VARIANT_noise
 #elif GPSAT_F64_GRAD
 #define F64_VARIANT F64_VARIANT_grad
+#elif GPSAT_F64_HESS
+#define F64_VARIANT F64_VARIANT_hess
 #else
 #define F64_VARIANT F64_VARIANT_plain
 #endif
@@ -101,9 +112,10 @@ static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE + G
 #define F64_COL_MEAN(ns8_, ns4_, fn_, base_, cv_, mean_, ...) mean_
 #define F64_COL_NOISE(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, ...) noise_
 #define F64_COL_GRAD(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, grad_, ...) grad_
-#define F64_CONSTANTS(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, grad_, kn_, dmax_)    \
-    constexpr bool BASE = base_, CV = cv_, MEAN = mean_, NOISE = noise_, GRAD = grad_;  \
-    constexpr unsigned KN_SET = kn_;                                                    \
+#define F64_COL_HESS(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, grad_, hess_, ...) hess_
+#define F64_CONSTANTS(ns8_, ns4_, fn_, base_, cv_, mean_, noise_, grad_, hess_, kn_, dmax_)          \
+    constexpr bool BASE = base_, CV = cv_, MEAN = mean_, NOISE = noise_, GRAD = grad_, HESS = hess_;  \
+    constexpr unsigned KN_SET = kn_;                                                                  \
     constexpr int D_MAX = dmax_;
 #define F64NS F64_ROW(F64_COL_NS)
 #if F64_ROW(F64_COL_MEAN)
@@ -112,7 +124,7 @@ static_assert(GPSAT_F64_CV + GPSAT_F64_RQ + GPSAT_F64_MEAN + GPSAT_F64_NOISE + G
 namespace F64NS {
 
 F64_ROW(F64_CONSTANTS)
-static_assert(int(BASE) + int(CV) + int(MEAN) + int(NOISE) + int(GRAD) + int(KN_SET == 0x10u) == 1, "a row of the variant table is plain, or adds one thing");
+static_assert(int(BASE) + int(CV) + int(MEAN) + int(NOISE) + int(GRAD) + int(HESS) + int(KN_SET == 0x10u) == 1, "a row of the variant table is plain, or adds one thing");
 constexpr int MIN_WG = GPSAT_F64_NW == 4 ? 2 : 1;       // workgroups per CU the kernel is compiled for
 constexpr bool TEAMS = BASE && GPSAT_F64_NW == 8;       // the object with the team kernel
 
@@ -463,6 +475,34 @@ __device__ __forceinline__ f64x4 kgblock(const Ctx<D, KN>& c, int bj, const doub
         [[maybe_unused]] double kf, gg, ga;
         kfun_c(c, r2, kf, gg, ga);
         out[r] = ((p < c.N) && qvalid) ? c.sf2 * gg * da * ila : 0.0;
+    }
+    return out;
+}
+
+// HESS: kgblock's sibling for one pass of predict_hess_tile, sf2 (hh Q - gg G) with hh = -2 dgg/d(r2) (kfun_hh), finite at r = 0:
+//   the pair (a, b):  d2k(x*, x_p)/dx*_a dx*_b,         Q = d_a d_b / (l_a l_b) (sab = 1 / (l_a l_b)),  G = delta_ab / l_a^2
+//   the Laplacian:    sum_d c_d d2k(x*, x_p)/dx*_d^2,   Q = sum_d wl_d d_d^2 (wl_d = c_d / l_d^2),      G = sum_d wl_d
+// a, b and lap are run-time values (the Laplacian pass comes with a = b = D, which no d equals): one copy of the code.
+template <int D, int KN>
+__device__ __forceinline__ f64x4 khblock(const Ctx<D, KN>& c, int bj, const double (&xq)[D], bool qvalid, int a, int b, bool lap,
+                                         double sab, const double (&wl)[D], double G) {
+    f64x4 out;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int p = BS * bj + rowof(r, c.q);
+        double r2 = 0.0, da = 0.0, db = 0.0, ql = 0.0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const double df = lds_d[c.L.xsc + d * c.Npad + p] - xq[d];
+            r2 = fma(df, df, r2);
+            ql = fma(wl[d] * df, df, ql);
+            if (d == a) da = df;
+            if (d == b) db = df;
+        }
+        [[maybe_unused]] double kf, gg, ga;
+        kfun_c(c, r2, kf, gg, ga);
+        const double Q = lap ? ql : sab * da * db;
+        out[r] = ((p < c.N) && qvalid) ? c.sf2 * (kfun_hh<KN>(r2) * Q - gg * G) : 0.0;
     }
     return out;
 }
@@ -1507,6 +1547,167 @@ __device__ __forceinline__ void predict_grad_fill(const double* theta0, int tid,
     }
 }
 
+// ---- the second derivatives of the posterior mean at the prediction points, with their variances (gpsat_fit_predict_batch_hess):
+// predict_grad_tile's sibling, behind it and from the same factor and z.  For every pair a <= b of the coordinates in H.dims
+// (a ascending, then b; column `col` of the two outputs), and once more for the weighted Laplacian when it is asked for,
+//   h = khblock,  V = L^-1 h,  mean = V^T z,  variance = prior - V^T V,
+//   prior(a, b) = sf2 hh(0) (1 + 2 delta_ab) / (l_a^2 l_b^2),  prior(Laplacian) = sf2 hh(0) (2 sum_d wl_d^2 + (sum_d wl_d)^2)
+// with wl_d = lap_w[d] / l_d^2: the fourth derivative of k at 0.  The pass is a run-time loop around ONE copy of the panelled
+// solve; one writer and one order of summation per output, no barrier, the wave's own V scratch.
+template <int KN> constexpr double hh_at_zero() { return KN == 0 ? 1.0 : 25.0 / 3.0; }
+
+template <int D, int KN>
+__device__ __forceinline__ void predict_hess_tile(Ctx<D, KN>& c, const double* __restrict__ Xs, const HessArgs& H, long long p0,
+                                                  const double* theta) {
+    constexpr bool TEAM = false;
+    const int NB = c.NB, lane = c.lane;
+    const int PC = (c.P + BS - 1) / BS;
+    const bool want_lap = H.f_lap != nullptr;
+    double wl[D], wsum = 0.0, wsq = 0.0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        wl[d] = want_lap ? H.lap_w[d] / (theta[d] * theta[d]) : 0.0;
+        wsum += wl[d];
+        wsq = fma(wl[d], wl[d], wsq);
+    }
+    for (int pc0 = 2 * c.w; pc0 < PC; pc0 += 2 * NW) {
+        const int v0 = c.vs0 + c.w * 4 * NB;
+        double xa[2][D];
+        bool va[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int qa = BS * (pc0 + n) + c.g;
+            va[n] = qa < c.P;
+#pragma unroll
+            for (int d = 0; d < D; ++d) xa[n][d] = va[n] ? Xs[(size_t)qa * D + d] / theta[d] : 0.0;
+        }
+        int col = 0;
+#pragma unroll 1
+        for (int a = 0; a <= D; ++a) {
+            const bool lap = a == D;                                // the last pass: the Laplacian, with b = D too
+            if (lap ? !want_lap : !((H.dims >> a) & 1u)) continue;
+#pragma unroll 1
+            for (int b = a; b < (lap ? D + 1 : D); ++b) {
+                if (!lap && !((H.dims >> b) & 1u)) continue;
+                const double sab = lap ? 0.0 : 1.0 / (theta[a] * theta[b]);
+                const double G = lap ? wsum : (a == b ? sab : 0.0);
+                double vs[2] = {0.0, 0.0}, ms[2] = {0.0, 0.0};
+                for (int j0 = 0; j0 < NB; j0 += PR) {
+                    const int nr = min(PR, NB - j0);
+                    f64x4 acc[PR][2];
+#pragma unroll
+                    for (int r = 0; r < PR; ++r) { acc[r][0] = zero4(); acc[r][1] = zero4(); }
+                    if (j0 > 0) {
+                        f64x4 A[PR], B0, B1;
+#pragma unroll
+                        for (int r = 0; r < PR; ++r) A[r] = ldg(c.ws, (r < nr) ? j0 + r : c.zb, lane);
+                        B0 = ldg(c.ws, v0, lane);
+                        B1 = ldg(c.ws, v0 + NB, lane);
+                        for (int k = 0; k + 1 < j0; ++k) {
+                            f64x4 nA[PR], nB0, nB1;
+#pragma unroll
+                            for (int r = 0; r < PR; ++r) nA[r] = ldg(c.ws, (r < nr) ? (k + 1) * NB + j0 + r : c.zb, lane);
+                            nB0 = ldg(c.ws, v0 + k + 1, lane);
+                            nB1 = ldg(c.ws, v0 + NB + k + 1, lane);
+#pragma unroll
+                            for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
+#pragma unroll
+                            for (int r = 0; r < PR; ++r) A[r] = nA[r];
+                            B0 = nB0; B1 = nB1;
+                        }
+#pragma unroll
+                        for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
+                    }
+#pragma unroll
+                    for (int r = 0; r < PR; ++r) {
+                        if (r < nr) {
+                            const int jr = j0 + r;
+                            const f64x4 Lop = ldg(c.ws, c.dT0 + jr, lane);
+                            f64x4 V[2];
+#pragma unroll
+                            for (int n = 0; n < 2; ++n) {
+                                const f64x4 Wb = khblock<D, KN>(c, jr, xa[n], va[n], a, b, lap, sab, wl, G) - acc[r][n];
+                                V[n] = zero4();
+                                mma_blk(V[n], Lop, Wb);
+                                stg(c.ws, v0 + n * NB + jr, lane, V[n]);
+#pragma unroll
+                                for (int rr = 0; rr < 4; ++rr) {
+                                    vs[n] = fma(V[n][rr], V[n][rr], vs[n]);
+                                    ms[n] = fma(V[n][rr], lds_d[c.L.z + BS * jr + rowof(rr, c.q)], ms[n]);
+                                }
+                            }
+#pragma unroll
+                            for (int r2 = r + 1; r2 < PR; ++r2) {
+                                if (r2 < nr) {
+                                    const f64x4 U = ldg(c.ws, jr * NB + j0 + r2, lane);
+                                    mma_blk(acc[r2][0], U, V[0]);
+                                    mma_blk(acc[r2][1], U, V[1]);
+                                }
+                            }
+                        }
+                    }
+                }
+                const double prior = c.sf2 * hh_at_zero<KN>() * (lap ? 2.0 * wsq + wsum * wsum : (a == b ? 3.0 : 1.0) * sab * sab);
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const double vsum = qsum(vs[n]), msum = qsum(ms[n]);
+                    const int qa = BS * (pc0 + n) + c.g;
+                    if (c.q == 0 && va[n]) {
+                        if (lap) {
+                            H.f_lap[p0 + qa] = msum;
+                            H.f_lap_var[p0 + qa] = prior - vsum;
+                        } else {
+                            H.f_hess[(size_t)(p0 + qa) * H.npair + col] = msum;
+                            H.f_hess_var[(size_t)(p0 + qa) * H.npair + col] = prior - vsum;
+                        }
+                    }
+                }
+                ++col;
+            }
+        }
+    }
+}
+
+// all threads: the outputs of the tile's P points (rows p0 .. p1) without a solve -- a tile without observations (the prior at
+// theta0: zeros and the prior variances above), or a failed one (theta0 == nullptr: NaN)
+template <int D, int KN>
+__device__ __forceinline__ void predict_hess_fill(const double* theta0, int tid, long long p0, long long p1, const HessArgs& H) {
+    const double nan = __builtin_nan("");
+    double wsum = 0.0, wsq = 0.0;
+    if (theta0) {
+        for (int d = 0; d < D; ++d) {
+            const double w = H.f_lap ? H.lap_w[d] / (theta0[d] * theta0[d]) : 0.0;
+            wsum += w;
+            wsq = fma(w, w, wsq);
+        }
+    }
+    int col = 0;
+    for (int a = 0; a < D; ++a) {
+        if (!((H.dims >> a) & 1u)) continue;
+        for (int b = a; b < D; ++b) {
+            if (!((H.dims >> b) & 1u)) continue;
+            double v = nan;
+            if (theta0) {
+                const double sab = 1.0 / (theta0[a] * theta0[b]);
+                v = theta0[D] * hh_at_zero<KN>() * ((a == b ? 3.0 : 1.0) * sab * sab);
+            }
+            for (long long q = p0 + tid; q < p1; q += NT) {
+                H.f_hess[(size_t)q * H.npair + col] = theta0 ? 0.0 : nan;
+                H.f_hess_var[(size_t)q * H.npair + col] = v;
+            }
+            ++col;
+        }
+    }
+    if (H.f_lap) {
+        const double v = theta0 ? theta0[D] * hh_at_zero<KN>() * (2.0 * wsq + wsum * wsum) : nan;
+        for (long long q = p0 + tid; q < p1; q += NT) {
+            H.f_lap[q] = theta0 ? 0.0 : nan;
+            H.f_lap_var[q] = v;
+        }
+    }
+    if (H.f_grad) predict_grad_fill<D, KN>(theta0, tid, p0, p1, H.f_grad, H.f_grad_var);
+}
+
 // ---- held-out predictions (gpsat_fit_predict_batch_cv): the rows G of a fold predicted from all other rows of the tile at
 // the returned parameters, from what the last evaluation left behind -- M = L^-1 in the lower slots and alpha = K_y^-1 y in
 // LDS.  With A = K_y^-1 = M^T M:   A_GG = M[:, G]^T M[:, G],   mean = y_G - A_GG^-1 alpha_G,   cov(y_G) = A_GG^-1
@@ -1698,8 +1899,8 @@ __device__ __forceinline__ void predict_prior(const KernelArgs& A, int t, int ti
 
 // The kernel of every variant.  `cvA` is a parameter of the held-out variant only, `nzA` of the noise variant only -- the one
 // place a variant's row reaches the preprocessor inside the device code: the other variants keep their kernel-argument layout
-// and their mangled names.  There the names stand for these, in the discarded `if constexpr (CV)` / `(NOISE)` / `(GRAD)`.
-// `grA` is the same for the gradient variant.
+// and their mangled names.  There the names stand for these, in the discarded `if constexpr (CV)` / `(NOISE)` / `(GRAD)` / `(HESS)`.
+// `grA` is the same for the gradient variant, `hsA` for the second-derivative variant.
 // The held-out variant has two kernels per (D, KN): JOINT = true is the one with the folds' joint densities in phase_cv,
 // launched when CvArgs::fold_lpd is set; JOINT = false holds nothing of them, so that its instruction stream and its
 // register allocation are those of the kernel without that output.
@@ -1708,6 +1909,9 @@ constexpr NoiseArgs nzA{};
 #endif
 #if !F64_ROW(F64_COL_GRAD)
 constexpr GradArgs grA{};
+#endif
+#if !F64_ROW(F64_COL_HESS)
+constexpr HessArgs hsA{};
 #endif
 #if !F64_ROW(F64_COL_CV)
 constexpr CvArgs cvA{};
@@ -1723,6 +1927,8 @@ __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArg
                                                                  , const NoiseArgs nzA
 #elif F64_ROW(F64_COL_GRAD)
                                                                  , const GradArgs grA
+#elif F64_ROW(F64_COL_HESS)
+                                                                 , const HessArgs hsA
 #endif
 ) {
     constexpr int H = nhyp<D, KN>();
@@ -1777,6 +1983,7 @@ __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArg
             else predict_prior<D, KN>(A, t, c.tid, p0, p1, f_mean, f_var, y_var);
             if (f_cov) prior_cov_empty<D, KN>(A.theta0 + (size_t)t * H, Xs + (size_t)p0 * D, c.P, c.tid, f_cov + A.cov_off[t]);
             if constexpr (GRAD) predict_grad_fill<D, KN>(A.theta0 + (size_t)t * H, c.tid, p0, p1, grA.f_grad, grA.f_grad_var);
+            if constexpr (HESS) predict_hess_fill<D, KN>(A.theta0 + (size_t)t * H, c.tid, p0, p1, hsA);
             if (sliced && c.tid == 0) __hip_atomic_fetch_add(&A.ring_ctl[32], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
         }
@@ -1819,6 +2026,17 @@ __global__ void __launch_bounds__(NT, MIN_WG) gp_tile_kernel_f64(const KernelArg
                 // (every wave goes on in its own scratch, behind its own prediction: no barrier)
                 if (!sh->fail) predict_grad_tile<D, KN>(c, Xs + (size_t)p0 * D, grA.f_grad + (size_t)p0 * D, grA.f_grad_var + (size_t)p0 * D, sh->theta);
                 else predict_grad_fill<D, KN>(nullptr, c.tid, p0, p1, grA.f_grad, grA.f_grad_var);
+            }
+        }
+        if constexpr (HESS) {
+            if (c.P > 0) {
+                // (as the gradient: every wave in its own scratch, behind its own prediction; the gradient first when asked for)
+                if (!sh->fail) {
+                    if (hsA.f_grad) predict_grad_tile<D, KN>(c, Xs + (size_t)p0 * D, hsA.f_grad + (size_t)p0 * D, hsA.f_grad_var + (size_t)p0 * D, sh->theta);
+                    predict_hess_tile<D, KN>(c, Xs + (size_t)p0 * D, hsA, p0, sh->theta);
+                } else {
+                    predict_hess_fill<D, KN>(nullptr, c.tid, p0, p1, hsA);
+                }
             }
         }
         if constexpr (CV) {
@@ -1966,7 +2184,7 @@ static hipError_t launch_kernel(void (*kernel)(Args...), int grid, size_t smem, 
 
 template <int D, int KN>
 static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs* cv, [[maybe_unused]] const NoiseArgs* nz,
-                             [[maybe_unused]] const GradArgs* gr, int grid, size_t smem, hipStream_t stream) {
+                             [[maybe_unused]] const GradArgs* gr, [[maybe_unused]] const HessArgs* hs, int grid, size_t smem, hipStream_t stream) {
     if constexpr (D > D_MAX || !((KN_SET >> KN) & 1u)) {
         return hipErrorInvalidValue;
     } else {
@@ -1981,32 +2199,40 @@ static hipError_t launch_one(const KernelArgs& a, [[maybe_unused]] const CvArgs*
 #else
         if constexpr (NOISE) return nz && nz->obs_var ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *nz) : hipErrorInvalidValue;
         else if constexpr (GRAD) return gr && gr->f_grad && gr->f_grad_var && !a.f_cov ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *gr) : hipErrorInvalidValue;
+        else if constexpr (HESS) {
+            // the outputs come in pairs; dims names coordinates below D, npair is what dims says; no full covariance
+            const unsigned m = hs ? (unsigned)__builtin_popcount(hs->dims) : 0u;
+            const bool ok = hs && hs->f_hess && hs->f_hess_var && !a.f_cov && m > 0 && (hs->dims >> D) == 0u
+                            && hs->npair == (int)(m * (m + 1) / 2) && !hs->f_lap == !hs->f_lap_var && !hs->f_grad == !hs->f_grad_var;
+            return ok ? launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a, *hs) : hipErrorInvalidValue;
+        }
         else return launch_kernel(gp_tile_kernel_f64<D, KN>, grid, smem, stream, a);
 #endif
     }
 }
 
 template <int D>
-static hipError_t launch_d(const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, int grid, size_t smem, hipStream_t stream) {
+static hipError_t launch_d(const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, const HessArgs* hs, int grid, size_t smem, hipStream_t stream) {
     switch (a.kernel) {
-        case 0: return launch_one<D, 0>(a, cv, nz, gr, grid, smem, stream);
-        case 1: return launch_one<D, 1>(a, cv, nz, gr, grid, smem, stream);
-        case 2: return launch_one<D, 2>(a, cv, nz, gr, grid, smem, stream);
-        case 3: return launch_one<D, 3>(a, cv, nz, gr, grid, smem, stream);
-        case 4: return launch_one<D, 4>(a, cv, nz, gr, grid, smem, stream);
+        case 0: return launch_one<D, 0>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 1: return launch_one<D, 1>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 2: return launch_one<D, 2>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 3: return launch_one<D, 3>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 4: return launch_one<D, 4>(a, cv, nz, gr, hs, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace F64NS
 
-// `cv`: the held-out variant's arguments, `nz`: the noise variant's, `gr`: the gradient variant's; null for every other
-hipError_t F64_ROW(F64_COL_ENTRY)(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, int grid, size_t smem, hipStream_t stream) {
+// `cv`: the held-out variant's arguments, `nz`: the noise variant's, `gr`: the gradient variant's, `hs`: the second-derivative
+// variant's; null for every other
+hipError_t F64_ROW(F64_COL_ENTRY)(int D, const KernelArgs& a, const CvArgs* cv, const NoiseArgs* nz, const GradArgs* gr, const HessArgs* hs, int grid, size_t smem, hipStream_t stream) {
     switch (D) {
-        case 1: return F64NS::launch_d<1>(a, cv, nz, gr, grid, smem, stream);
-        case 2: return F64NS::launch_d<2>(a, cv, nz, gr, grid, smem, stream);
-        case 3: return F64NS::launch_d<3>(a, cv, nz, gr, grid, smem, stream);
-        case 4: return F64NS::launch_d<4>(a, cv, nz, gr, grid, smem, stream);
+        case 1: return F64NS::launch_d<1>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 2: return F64NS::launch_d<2>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 3: return F64NS::launch_d<3>(a, cv, nz, gr, hs, grid, smem, stream);
+        case 4: return F64NS::launch_d<4>(a, cv, nz, gr, hs, grid, smem, stream);
         default: return hipErrorInvalidValue;
     }
 }

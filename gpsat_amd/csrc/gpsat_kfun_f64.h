@@ -27,4 +27,17 @@ __device__ __forceinline__ void kfun(double r2, double& kf, double& gg) {
     }
 }
 
+// hh = -2 dgg/d(r2), the radial factor of the second derivatives d2k/dx_a dx_b = hh d_a d_b / (l_a l_b) - delta_ab gg / l_a^2
+// (d = (x' - x) / l), without the variance factor; for the kernels whose sample paths have a mean-square second derivative:
+// KERN 0 (RBF) and 3 (Matern-5/2).  hh(0) = 1 and 25/3.
+template <int KERN>
+__device__ __forceinline__ double kfun_hh(double r2) {
+    static_assert(KERN == 0 || KERN == 3, "hh exists for RBF and Matern-5/2 only");
+    // (the exponentials are written as kfun writes them)
+    if (KERN == 0) return exp(-0.5 * r2);
+    const double r = sqrt(fmax(r2, 1e-36));
+    const double s = 2.23606797749979 * r, e = exp(-s);
+    return (25.0 / 3.0) * e;
+}
+
 #endif

@@ -19,24 +19,27 @@ struct Build {
     int (*state_words)();
     size_t (*pq_floats_per_slot)(int D, int NBmax);           // nullptr: the build has no deferred predictions
     // the tile loop per F64Variant (`cv`: the held-out variant's arguments, `nz`: the noise variant's, `gr`: the gradient
-    // variant's, else null); nullptr: the build has no such variant
-    F64Launch* launch_variant[6];
+    // variant's, `hs`: the second-derivative variant's, else null); nullptr: the build has no such variant
+    F64Launch* launch_variant[7];
 };
 enum { BUILD_F32_W4 = 0, BUILD_F32_W8 = 1, BUILD_F64_W8 = 2, BUILD_F64_W4 = 3 };
 // The variants of the fp64 tile loop (gpsat_kernels_f64.hip): held-out predictions, the RationalQuadratic covariance function,
-// a trainable constant mean, known noise variances per observation, the gradient of the posterior mean at the prediction points.
+// a trainable constant mean, known noise variances per observation, the gradient of the posterior mean at the prediction points,
+// its second derivatives there.
 // A job is one of them; every one but PLAIN runs one workgroup per tile.
-enum F64Variant { PLAIN = 0, CV = 1, RQ = 2, MEAN = 3, NOISE = 4, GRAD = 5 };
+enum F64Variant { PLAIN = 0, CV = 1, RQ = 2, MEAN = 3, NOISE = 4, GRAD = 5, HESS = 6 };
 // the fp32 builds (no variants) behind the same signature
-inline hipError_t launch_f32_w4(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles(D, a, grid, smem, stream); }
-inline hipError_t launch_f32_w8(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles_w8(D, a, grid, smem, stream); }
+inline hipError_t launch_f32_w4(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, const HessArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles(D, a, grid, smem, stream); }
+inline hipError_t launch_f32_w8(int D, const KernelArgs& a, const CvArgs*, const NoiseArgs*, const GradArgs*, const HessArgs*, int grid, size_t smem, hipStream_t stream) { return launch_tiles_w8(D, a, grid, smem, stream); }
 const Build builds[4] = {
-    {shared_bytes, workspace_floats_per_wg, state_words, pq_floats_per_slot, {launch_f32_w4, nullptr, nullptr, nullptr, nullptr, nullptr}},
-    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, nullptr, {launch_f32_w8, nullptr, nullptr, nullptr, nullptr, nullptr}},
+    {shared_bytes, workspace_floats_per_wg, state_words, pq_floats_per_slot, {launch_f32_w4, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}},
+    {shared_bytes_w8, workspace_floats_per_wg_w8, state_words_w8, nullptr, {launch_f32_w8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}},
     {shared_bytes_f64, workspace_doubles_per_wg_f64, state_words_f64, nullptr,
-     {launch_tiles_f64, launch_tiles_f64_cv, launch_tiles_f64_rq, launch_tiles_f64_mean, launch_tiles_f64_noise, launch_tiles_f64_grad}},
+     {launch_tiles_f64, launch_tiles_f64_cv, launch_tiles_f64_rq, launch_tiles_f64_mean, launch_tiles_f64_noise, launch_tiles_f64_grad,
+      launch_tiles_f64_hess}},
     {shared_bytes_f64_w4, workspace_doubles_per_wg_f64_w4, state_words_f64_w4, nullptr,
-     {launch_tiles_f64_w4, launch_tiles_f64_cv_w4, launch_tiles_f64_rq_w4, launch_tiles_f64_mean_w4, launch_tiles_f64_noise_w4, launch_tiles_f64_grad_w4}},
+     {launch_tiles_f64_w4, launch_tiles_f64_cv_w4, launch_tiles_f64_rq_w4, launch_tiles_f64_mean_w4, launch_tiles_f64_noise_w4, launch_tiles_f64_grad_w4,
+      launch_tiles_f64_hess_w4}},
 };
 
 // One developer knob (GPSAT_DEBUG_*, read through dev_env() only): whether it is set, and atoi of its text.
@@ -228,6 +231,46 @@ int check_pred_grad(const gpsat_batch* b, const gpsat_pred_grad* pg, char* why, 
     if (b->pred_off[b->T] > 0) {
         if (!pg->f_grad) { std::snprintf(why, why_len, "pred_grad: f_grad is NULL"); return GPSAT_EINVAL; }
         if (!pg->f_grad_var) { std::snprintf(why, why_len, "pred_grad: f_grad_var is NULL"); return GPSAT_EINVAL; }
+    }
+    return GPSAT_OK;
+}
+
+// gpsat_fit_predict_batch_hess's own checks, as check_pred_grad: a pure function of host data behind check_batch, reached by
+// tests through its exported symbol.  GPSAT_OK, or GPSAT_EINVAL with the reason in why[why_len].  No output is dereferenced.
+int check_pred_hess(const gpsat_batch* b, const gpsat_pred_hess* ph, char* why, size_t why_len) {
+    if (why_len > 0) why[0] = 0;
+    if (!ph) { std::snprintf(why, why_len, "gpsat_fit_predict_batch_hess: pred_hess is NULL"); return GPSAT_EINVAL; }
+    for (int i = 0; i < 7; ++i)
+        if (ph->reserved[i] != 0) { std::snprintf(why, why_len, "pred_hess: reserved words must be 0"); return GPSAT_EINVAL; }
+    if (b->dtype != GPSAT_F64) { std::snprintf(why, why_len, "the second derivatives of the posterior mean (pred_hess) are built for GPSAT_F64 only"); return GPSAT_EINVAL; }
+    if (b->kernel == GPSAT_KERNEL_MATERN12 || b->kernel == GPSAT_KERNEL_MATERN32) {
+        std::snprintf(why, why_len, "the second derivatives of the posterior mean (pred_hess) do not exist for GPSAT_KERNEL_MATERN%s: "
+                      "the derivative process is not mean-square differentiable", b->kernel == GPSAT_KERNEL_MATERN12 ? "12" : "32");
+        return GPSAT_EINVAL;
+    }
+    if (b->kernel != GPSAT_KERNEL_RBF && b->kernel != GPSAT_KERNEL_MATERN52) {
+        std::snprintf(why, why_len, "the second derivatives of the posterior mean (pred_hess) are not built for kernel %d, only for GPSAT_KERNEL_RBF and GPSAT_KERNEL_MATERN52", (int)b->kernel);
+        return GPSAT_EINVAL;
+    }
+    if (b->cov_off || b->f_cov) {
+        std::snprintf(why, why_len, "pred_hess and the full covariance cannot be asked for in the same call: cov_off / f_cov must be NULL");
+        return GPSAT_EINVAL;
+    }
+    if (ph->dims == 0) { std::snprintf(why, why_len, "pred_hess: dims is empty, it names no coordinate"); return GPSAT_EINVAL; }
+    if (b->D < 32 && (ph->dims >> b->D) != 0) { std::snprintf(why, why_len, "pred_hess: dims names a coordinate >= D = %d", (int)b->D); return GPSAT_EINVAL; }
+    bool lap = ph->f_lap || ph->f_lap_var;
+    for (int a = 0; a < 4; ++a) {
+        const double w = ph->lap_weight[a];
+        if (!(w >= 0.0) || !(w <= 1.79769313486231570815e308)) { std::snprintf(why, why_len, "pred_hess: lap_weight[%d] is negative or not finite", a); return GPSAT_EINVAL; }
+        if (w > 0.0 && !((ph->dims >> a) & 1u)) { std::snprintf(why, why_len, "pred_hess: lap_weight[%d] is set for a coordinate outside dims", a); return GPSAT_EINVAL; }
+        lap = lap || w > 0.0;
+    }
+    if (!ph->f_grad != !ph->f_grad_var) { std::snprintf(why, why_len, "pred_hess: f_grad and f_grad_var are given together or not at all"); return GPSAT_EINVAL; }
+    if (b->pred_off[b->T] > 0) {
+        if (!ph->f_hess) { std::snprintf(why, why_len, "pred_hess: f_hess is NULL"); return GPSAT_EINVAL; }
+        if (!ph->f_hess_var) { std::snprintf(why, why_len, "pred_hess: f_hess_var is NULL"); return GPSAT_EINVAL; }
+        if (lap && !ph->f_lap) { std::snprintf(why, why_len, "pred_hess: f_lap is NULL, with a lap_weight or f_lap_var given"); return GPSAT_EINVAL; }
+        if (lap && !ph->f_lap_var) { std::snprintf(why, why_len, "pred_hess: f_lap_var is NULL, with a lap_weight or f_lap given"); return GPSAT_EINVAL; }
     }
     return GPSAT_OK;
 }

@@ -52,6 +52,14 @@ class BatchResult:
     # component, [sum P, D] each (numpy / torch as f_mean), in the units of y (y^2) per unit of X; None unless asked for
     f_grad: object = None
     f_grad_var: object = None
+    # pred_hess: the second derivatives of the posterior mean for the pairs a <= b of the chosen coordinates (hess_pairs, the
+    # columns) and their posterior variances, [sum P, m(m+1)/2] each; the weighted Laplacian and its variance, [sum P] (None
+    # without weights); numpy / torch as f_mean, in the units of y (y^2) per unit of X squared (to the fourth)
+    f_hess: object = None
+    f_hess_var: object = None
+    f_lap: object = None
+    f_lap_var: object = None
+    hess_pairs: list | None = None
     kernel_ms: float = 0.0
     total_ms: float = 0.0
 
@@ -150,6 +158,28 @@ def _alloc(n, dtype, beside=None, at_least=0):
         return np.empty(max(n, at_least), dtype=NP_DTYPES[dtype])
     import torch
     return torch.empty(max(n, 1), dtype=beside.dtype, device=beside.device)
+
+
+def _pred_hess_spec(pred_hess, D):
+    """``pred_hess`` of fit_predict_batch as (sorted coordinate indices, the D Laplacian weights or None for no Laplacian)."""
+    spec = {} if pred_hess is True else pred_hess
+    if not isinstance(spec, dict) or set(spec) - {"dims", "lap_weight"}:
+        raise GpsatError('pred_hess: True, or a dict with "dims" and / or "lap_weight"')
+    dims = list(range(D)) if spec.get("dims") is None else sorted(set(int(a) for a in spec["dims"]))
+    if not dims or dims[0] < 0 or dims[-1] >= D:
+        raise GpsatError(f"pred_hess: dims must name at least one coordinate index in 0..{D - 1}, got {spec.get('dims')!r}")
+    if "lap_weight" not in spec:
+        return dims, [1.0 if a in dims else 0.0 for a in range(D)]
+    if spec["lap_weight"] is None:
+        return dims, None
+    w = [float(c) for c in np.asarray(spec["lap_weight"], dtype=np.float64).reshape(-1)]
+    if len(w) != D:
+        raise GpsatError(f"pred_hess: lap_weight has one weight per coordinate, {D}, got {len(w)}")
+    if any(not (c >= 0.0 and np.isfinite(c)) for c in w):
+        raise GpsatError("pred_hess: lap_weight must be finite and >= 0")
+    if any(c > 0.0 and a not in dims for a, c in enumerate(w)):
+        raise GpsatError("pred_hess: lap_weight is set for a coordinate outside dims")
+    return dims, (w if any(c > 0.0 for c in w) else None)
 
 
 def _fold_labels(cv_fold, sumN):
@@ -395,7 +425,7 @@ class Engine:
                           trainable=None, kernel="Matern32", optimiser="lbfgs", max_iter=10_000,
                           max_ls=0, ftol=0.0, gtol=0.0, adam_lr=0.0, want_grad=False,
                           out=None, dtype="f32", full_cov=False, n_starts=None, starts=None, cv_fold=None,
-                          cv_refit=None, mean=None, obs_var=None, cv_joint=False, pred_grad=False) -> BatchResult:
+                          cv_refit=None, mean=None, obs_var=None, cv_joint=False, pred_grad=False, pred_hess=False) -> BatchResult:
         """
         X [sumN, D], y [sumN], Xs [sumP, D]: numpy arrays (host mode) or contiguous torch.cuda tensors (device
         mode; outputs are then torch tensors, optionally preallocated via ``out`` = (f_mean, f_var, y_var)).
@@ -454,17 +484,28 @@ class Engine:
         kernel_variance gg(0) / l_a^2, gg(0) = 1 RBF, 3 Matern32, 5/3 Matern52), a tile that is not positive definite NaN.
         fp64, RBF / Matern32 / Matern52 (Matern12 is not mean-square differentiable), D <= 4, either optimiser; refused beside
         mean, obs_var, cv_fold / cv_refit, n_starts and full_cov.
+        ``pred_hess`` (gpsat_fit_predict_batch_hess): True, or {"dims": coordinate indices (default: all),
+        "lap_weight": D weights c_a >= 0, 0 outside dims (default: 1 on dims; None: no Laplacian)}.  Also ``f_hess`` and
+        ``f_hess_var`` [sum P, m(m+1)/2], d2 f*(x*) / dx*_a dx*_b and its posterior variance for the pairs a <= b of dims in the
+        order of ``hess_pairs``, and ``f_lap`` / ``f_lap_var`` [sum P], sum_a c_a d2 f*/dx*_a^2 and its variance (which holds the
+        covariances between the second derivatives, not returned otherwise).  Every other field has the bits of the call
+        without it.  A tile without observations returns the prior at theta0, a tile that is not positive definite NaN.  fp64,
+        RBF / Matern52 (the derivative of a Matern32 process is not mean-square differentiable), D <= 4, either optimiser;
+        refused beside what pred_grad is refused beside -- but not beside pred_grad itself, which then comes from the same call.
         Which of these arguments cannot be combined is the table of gpsat_amd/variants.py: a pairing
         that one library call cannot express is refused here, any other by the library with its own message.
         """
-        if pred_grad:
+        if pred_grad or pred_hess:
             on = {"mean": mean not in (None, "zero"), "noise": obs_var is not None, "cv_refit": cv_refit not in (None, False),
                   "cv": cv_fold is not None and cv_refit in (None, False), "multistart": n_starts is not None, "full_cov": bool(full_cov),
                   "rq": kernel in ("RationalQuadratic", L.KERNEL_RQ)}
             names = {v: k for k, v in L.KERNEL_IDS.items()}
-            why = V.why_refused_pred_grad([k for k in on if on[k]], dtype, kernel if isinstance(kernel, str) else names.get(int(kernel)))
+            refusal = V.why_refused_pred_hess if pred_hess else V.why_refused_pred_grad
+            why = refusal([k for k in on if on[k]], dtype, kernel if isinstance(kernel, str) else names.get(int(kernel)))
             if why:
                 raise GpsatError(why)
+        if pred_hess:
+            hess_dims, lap_w = _pred_hess_spec(pred_hess, D)
         asked, refit = self._check_call(dtype, kernel, mean, obs_var, cv_fold, cv_refit, n_starts, full_cov, cv_joint)
         self._check_widths(asked, kernel, D, theta0=theta0, lo=lo, hi=hi, trainable=trainable)
         meta = _host_meta(D, (obs_off, pred_off), theta0, lo, hi, trainable, V.n_hyper(D, asked))
@@ -508,7 +549,29 @@ class Engine:
             jt.fold_off, jt.fold_lpd = _ptr(fold_off), _ptr(lpd)
             fields.update(cv_fold_off=fold_off, cv_lpd=lpd)
             args.append(C.byref(jt))
-        if pred_grad:
+        if pred_hess:
+            name = V.PRED_HESS_ENTRY
+            if not hasattr(self._lib, name):
+                raise GpsatError(f"this libgpsat_hip.so has no {name} ({V.PRED_HESS_LABEL})")
+            pairs = V.pred_hess_pairs(hess_dims)
+            ph = getattr(L, V.PRED_HESS_STRUCT)()
+            ph.dims = sum(1 << a for a in hess_dims)
+            ho = tuple(_alloc(sumP * len(pairs), dtype, beside) for _ in range(2))
+            ph.f_hess, ph.f_hess_var = (_bulk_ptr(a) for a in ho)
+            fields.update(f_hess=ho[0][:sumP * len(pairs)].reshape(sumP, len(pairs)),
+                          f_hess_var=ho[1][:sumP * len(pairs)].reshape(sumP, len(pairs)), hess_pairs=pairs)
+            if lap_w is not None:
+                for a in range(D):
+                    ph.lap_weight[a] = lap_w[a]
+                lo_ = tuple(_alloc(sumP, dtype, beside) for _ in range(2))
+                ph.f_lap, ph.f_lap_var = (_bulk_ptr(a) for a in lo_)
+                fields.update(f_lap=lo_[0][:sumP], f_lap_var=lo_[1][:sumP])
+            if pred_grad:
+                go = tuple(_alloc(sumP * D, dtype, beside) for _ in range(2))
+                ph.f_grad, ph.f_grad_var = (_bulk_ptr(a) for a in go)
+                fields.update(f_grad=go[0][:sumP * D].reshape(sumP, D), f_grad_var=go[1][:sumP * D].reshape(sumP, D))
+            args.append(C.byref(ph))
+        elif pred_grad:
             name = V.PRED_GRAD_ENTRY
             if not hasattr(self._lib, name):
                 raise GpsatError(f"this libgpsat_hip.so has no {name} ({V.PRED_GRAD_LABEL})")

@@ -82,6 +82,14 @@ slope of the raw field is ``obs_scale * f*_grad_<c>``, its variance ``obs_scale*
 the whole run (a replacement profile predicts the same columns), no other table changes, and the glue does not combine
 these columns.  The constructor refuses what HipGPRModel.predict(gradient=True) refuses: fp32, Matern12 / RationalQuadratic
 (also as a replacement profile's kernel), a constant mean, ``obs_var_col``, ``cv``, SGPR experts and ``full_cov``.
+``pred_kwargs.hessian=True`` or a list of names from ``coords_col`` (exact-GP experts, fp64: ``dtype`` None then means fp64; kernels
+RBF and Matern52), alone or beside ``gradient``, adds to ``preds``, for the pairs ``<a>``, ``<b>`` of those
+columns in the order of ``coords_col`` (a, then b from a on), ``f*_hess_<a>_<b>`` and ``f*_hess_var_<a>_<b>``, the second derivative
+of the posterior mean and its posterior variance, and ``f*_lap`` / ``f*_lap_var``, the sum of the ``f*_hess_<a>_<a>`` -- the
+Laplacian over those columns -- with its own variance (which holds the covariances between them).  Units as ``gradient``'s: those
+``f*`` is stored in, per RAW unit of each of the two coordinates.  The constructor refuses what it refuses for ``gradient``, and
+Matern32 as well: the derivative of a Matern-3/2 process is not mean-square differentiable.  The glue does not combine these
+columns (the second derivatives of the glued map need the second-order terms of the weights).
 ``load_params.previous=True`` (local_experts.py:1059-1064,1200-1217: every tile starts from an exponential moving average,
 rho = 0.95, of the optima of the successfully optimised tiles before it) is a serial cross-tile dependency; its batched
 definition here is CALL-LAGGED: all tiles of one engine call start from the average as it stood when the call was
@@ -870,7 +878,16 @@ _N_RES = 6
 _Profile = make_dataclass("_Profile", [
     "theta_default", "lo", "hi", "trainable", "clamp", "coords_scale", "obs_scale", "local_mean", "unconstrained_noise",
     "device", "sgpr", "n_inducing", "inducing_seed", "kernel", "max_iter", "eng_kw", "optimiser", "apply_scale", "full_cov",
-    "pred_grad"])
+    "pred_grad", "pred_hess"])
+
+
+def _pred_hess_arg(pf):
+    """Engine.fit_predict_batch's ``pred_hess`` for a profile: its coordinates, and Laplacian weights 1 / coords_scale_a^2 (1
+    without apply_scale) on them, so that the Laplacian is taken in the raw coordinates."""
+    cs = np.asarray(pf.coords_scale if pf.apply_scale else np.ones_like(pf.coords_scale), dtype=np.float64).reshape(-1)
+    return {"dims": list(pf.pred_hess), "lap_weight": [1.0 / cs[a] ** 2 if a in pf.pred_hess else 0.0 for a in range(len(cs))]}
+
+
 # Pass 1: the expert locations of a run -- item i is expert ex[i] at locs[i]; its observation rows are idx[off[i]:off[i + 1]]
 # of coords_all / obs_all (fp64), its prediction coordinates pcs[i]; kind 0 skipped silently, 1 stub row, 2 tile, 3 error
 # row; prof_id indexes profiles; theta0, lo, hi [T, H] its start parameters and box.
@@ -933,8 +950,18 @@ class BatchedLocalExpertOI:
         # is refused below)
         # pred_kwargs.gradient (either profile's) holds for the run: the gradient of the posterior mean beside every prediction
         self.pred_grad = any(bool((model_config.get(k) or {}).get("gradient", False)) for k in ("pred_kwargs", "replacement_pred_kwargs"))
+        # pred_kwargs.hessian in the same way: True, or names from coords_col -- kept as sorted coordinate indices, None: not asked
+        self.pred_hess = None
+        for k in ("pred_kwargs", "replacement_pred_kwargs"):
+            hs = (model_config.get(k) or {}).get("hessian", False)
+            if self.pred_hess is None and hs is not False and hs is not None:
+                cc = list(data_config["coords_col"])
+                names = cc if hs is True else ([hs] if isinstance(hs, str) else list(hs))
+                if not names or any(n not in cc for n in names):
+                    raise ValueError(f"{k}.hessian: True, or names from coords_col {cc}, got {hs!r}")
+                self.pred_hess = sorted(set(cc.index(n) for n in names))
         if dtype is None:
-            dtype = "f32" if all("f32" in V.VARIANTS[k].dtypes for k in kind) and not self.pred_grad else "f64"
+            dtype = "f32" if all("f32" in V.VARIANTS[k].dtypes for k in kind) and not self.pred_grad and self.pred_hess is None else "f64"
         if dtype not in DTYPES:
             raise ValueError("dtype must be 'f32', 'f64' (the reference's precision) or None")
         # one check per model profile: the main one carries the kind of expert; the replacement stays a plain exact GP
@@ -949,12 +976,13 @@ class BatchedLocalExpertOI:
                                 dims="coordinate columns")
             if why:
                 raise NotImplementedError(why)
-        if self.pred_grad:
+        if self.pred_grad or self.pred_hess is not None:
             main_ip = model_config.get("init_params") or {}
             rip = model_config.get("replacement_init_params")
             kernels = [main_ip.get("kernel", "Matern32")] + [(main_ip if rip is None else rip).get("kernel", "Matern32")] * bool(replaced)
+            refusal = V.why_refused_pred_grad if self.pred_hess is None else V.why_refused_pred_hess
             for (asked, pk), kern in zip(profiles, kernels):
-                why = V.why_refused_pred_grad(asked + held_out + ["full_cov"] * bool((pk or {}).get("full_cov", False)), dtype, kern)
+                why = refusal(asked + held_out + ["full_cov"] * bool((pk or {}).get("full_cov", False)), dtype, kern)
                 if why:
                     raise NotImplementedError(why)
         row = next((V.VARIANTS[k] for k in self._variants if V.VARIANTS[k].param), None)
@@ -1092,7 +1120,8 @@ class BatchedLocalExpertOI:
             inducing_seed=int(pf["init_params"].get("inducing_seed", 0)), kernel=kernel, max_iter=int(ok.get("max_iter", 10_000)),
             eng_kw={**{k: ok[k] for k in ("max_ls", "ftol", "gtol", "adam_lr") if k in ok}, **m._variant_args()},
             optimiser=ok.get("optimiser", "lbfgs") if optimise else "none", apply_scale=pf["pred_kwargs"].get("apply_scale", True),
-            full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict, pred_grad=self.pred_grad and predict)
+            full_cov=bool(pf["pred_kwargs"].get("full_cov", False)) and predict, pred_grad=self.pred_grad and predict,
+            pred_hess=self.pred_hess if predict else None)
 
     def _loaded_theta(self, tabs, locs, theta, unconstrained_noise):
         """Overwrite rows of ``theta`` [T, H] with the stored parameters of each expert location.  Returns the mask of
@@ -1467,6 +1496,14 @@ class BatchedLocalExpertOI:
             for ci, c_ in enumerate(cc):
                 pr[f"f*_grad_{c_}"] = pred_cat[:, 3 + ci]
                 pr[f"f*_grad_var_{c_}"] = pred_cat[:, 3 + len(cc) + ci]
+        if self.pred_hess is not None:                             # behind those: the pairs, their variances, the Laplacian and its
+            pairs = V.pred_hess_pairs(self.pred_hess)
+            h0 = 3 + 2 * len(cc) * bool(self.pred_grad)
+            for k, (a, b) in enumerate(pairs):
+                pr[f"f*_hess_{cc[a]}_{cc[b]}"] = pred_cat[:, h0 + k]
+                pr[f"f*_hess_var_{cc[a]}_{cc[b]}"] = pred_cat[:, h0 + len(pairs) + k]
+            pr["f*_lap"] = pred_cat[:, h0 + 2 * len(pairs)]
+            pr["f*_lap_var"] = pred_cat[:, h0 + 2 * len(pairs) + 1]
         for ci, c_ in enumerate(cc):
             pr[f"pred_loc_{c_}"] = raw[:, ci]
         return pd.DataFrame(pr, index=_index_for_repeated(cc, plan.locs[items], cnt))
@@ -1543,7 +1580,9 @@ class _ShardRunner:
     def __init__(self, oi: BatchedLocalExpertOI, plan: _Plan, items, store: ResultStore, wave_n, chunk_n, t_start):
         self.oi, self.plan, self.items, self.store, self.t_start = oi, plan, items, store, t_start
         self.H = oi.H
-        self.pred_width = 3 + 2 * len(oi.coords_col) * bool(oi.pred_grad)      # f*, f*_var, y_var[, D gradients, D variances]
+        # f*, f*_var, y_var[, D gradients, D variances][, the pairs' second derivatives, their variances, the Laplacian, its variance]
+        self.pred_width = (3 + 2 * len(oi.coords_col) * bool(oi.pred_grad)
+                           + (0 if oi.pred_hess is None else 2 * len(V.pred_hess_pairs(oi.pred_hess)) + 2))
         self.waves = [items[w0:w0 + wave_n] for w0 in range(0, len(items), wave_n)]
         self.jobs, self.jobs_of_wave = [], {}          # jobs: (wave, profile, positions within the wave, items)
         for wi, w in enumerate(self.waves):
@@ -1657,7 +1696,8 @@ class _ShardRunner:
                     kw.update(LC.engine_kw(self.oi.cv, pk["cv_fold"], pf.local_mean, p.min_obs))
                 r = eng_.fit_predict_batch(theta0=p.theta0[ids] if th_override is None else th_override, dtype=self.oi.dtype,
                                            **kw, **({"full_cov": True} if pf.full_cov else {}),
-                                           **({"pred_grad": True} if pf.pred_grad else {}))
+                                           **({"pred_grad": True} if pf.pred_grad else {}),
+                                           **({"pred_hess": _pred_hess_arg(pf)} if pf.pred_hess is not None else {}))
             t1 = time.perf_counter()
             self.oi.timings["calls"].append((k, len(ids), round(te - self.t_start, 4), round(t1 - self.t_start, 4),
                                              round(r.kernel_ms * 1e-3, 4)))
@@ -1691,6 +1731,12 @@ class _ShardRunner:
                 # per RAW coordinate unit, in the units f* is stored in: the model's gradient with coords_scale undone
                 cs = pf.coords_scale if pf.apply_scale else np.ones_like(pf.coords_scale)
                 pr = np.concatenate([pr, np.asarray(r.f_grad, dtype=np.float64) / cs, np.asarray(r.f_grad_var, dtype=np.float64) / cs ** 2], axis=1)
+            if pf.pred_hess is not None:
+                # the same for the second derivatives: 1 / (cs_a cs_b) per pair; the Laplacian's weights (_pred_hess_arg) made it raw
+                cs = np.asarray(pf.coords_scale if pf.apply_scale else np.ones_like(pf.coords_scale), dtype=np.float64).reshape(-1)
+                sc = np.array([cs[a] * cs[b] for a, b in r.hess_pairs])
+                pr = np.concatenate([pr, np.asarray(r.f_hess, dtype=np.float64) / sc, np.asarray(r.f_hess_var, dtype=np.float64) / sc ** 2,
+                                     np.asarray(r.f_lap, dtype=np.float64)[:, None], np.asarray(r.f_lap_var, dtype=np.float64)[:, None]], axis=1)
             p_off = pk["p_off"]
             for kk, j in enumerate(loc_ids):
                 preds[j] = pr[p_off[kk]:p_off[kk + 1]]

@@ -408,13 +408,32 @@ class HipGPRModel:
         """Why predict(gradient=True) is refused for this model (variants.why_refused_pred_grad), or None."""
         return V.why_refused_pred_grad(self._variants + ["full_cov"] * bool(full_cov), self.dtype, self.kernel)
 
-    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
+    def _why_no_hessian(self, full_cov=False):
+        """Why predict(hessian=...) is refused for this model (variants.why_refused_pred_hess), or None."""
+        return V.why_refused_pred_hess(self._variants + ["full_cov"] * bool(full_cov), self.dtype, self.kernel)
+
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False, hessian=False) -> Dict[str, np.ndarray]:
         """gpflow_models.py:187-273.  ``gradient=True`` (fp64; RBF, Matern32, Matern52): also the 1-D arrays
         ``f*_grad_<k>`` and ``f*_grad_var_<k>``, k = 0 .. D - 1 -- the derivative of the posterior mean with respect to
         coordinate k of the prediction point, and the posterior variance of that derivative.  With ``apply_scale`` they are in
         raw units, observation units per unit of the raw coordinate: obs_scale g_k / coords_scale_k and obs_scale^2 v_k /
-        coords_scale_k^2; without it they are the scaled model's, as the coordinates given are."""
-        if gradient:
+        coords_scale_k^2; without it they are the scaled model's, as the coordinates given are.
+        ``hessian=True`` or a list of coordinate indices (fp64; RBF, Matern52), alone or beside ``gradient``:
+        also ``f*_hess_<a>_<b>`` and ``f*_hess_var_<a>_<b>`` for the pairs a <= b of those coordinates -- the second derivative
+        of the posterior mean and its posterior variance -- and ``f*_lap`` / ``f*_lap_var``, the sum of the ``f*_hess_<a>_<a>``
+        and its variance, which holds their covariances.  With ``apply_scale`` in raw units: obs_scale H_ab / (coords_scale_a
+        coords_scale_b), the Laplacian weighted with 1 / coords_scale_a^2 so that it is the Laplacian in raw coordinates, and
+        the variances with the squares; without it the scaled model's."""
+        if hessian is not False and hessian is not None:
+            why = self._why_no_hessian(full_cov)
+            if why:
+                raise NotImplementedError(why)
+            hdims = list(range(self.D)) if hessian is True else sorted(set(int(a) for a in hessian))
+            if not hdims or hdims[0] < 0 or hdims[-1] >= self.D:
+                raise ValueError(f"hessian: True, or coordinate indices in 0..{self.D - 1}, got {hessian!r}")
+        else:
+            hdims = None
+        if gradient and hdims is None:
             why = self._why_no_gradient(full_cov)
             if why:
                 raise NotImplementedError(why)
@@ -431,7 +450,11 @@ class HipGPRModel:
         coords = coords.astype(self.coords.dtype)
         if apply_scale:
             coords = coords / self.coords_scale
-        r = self._run(optimiser="none", pred_coords=coords, **({"pred_grad": True} if gradient else {"full_cov": bool(full_cov)}))
+        cs = np.broadcast_to(self.coords_scale, (1, self.D))[0] if apply_scale else np.ones(self.D)
+        extra = {"pred_grad": True} if gradient else {}
+        if hdims is not None:
+            extra["pred_hess"] = {"dims": hdims, "lap_weight": [1.0 / cs[a] ** 2 if a in hdims else 0.0 for a in range(self.D)]}
+        r = self._run(optimiser="none", pred_coords=coords, **(extra or {"full_cov": bool(full_cov)}))
         if r.status[0] in (2, 3):
             raise FloatingPointError("covariance matrix is not positive definite at the current parameters")
         if not full_cov:
@@ -447,13 +470,19 @@ class HipGPRModel:
             y_cov = f_cov.copy()
             y_cov[np.arange(P), np.arange(P)] += y_var - f_var
             out = {"f*": r.f_mean.astype(np.float64), "f*_var": f_var, "y_var": y_var, "f*_cov": f_cov, "y_cov": y_cov}
+        osc = float(self.obs_scale[0, 0]) if apply_scale else 1.0
         if gradient:
-            cs = np.broadcast_to(self.coords_scale, (1, self.D))[0] if apply_scale else np.ones(self.D)
-            osc = float(self.obs_scale[0, 0]) if apply_scale else 1.0
             fg, fgv = np.asarray(r.f_grad, dtype=np.float64), np.asarray(r.f_grad_var, dtype=np.float64)
             for k in range(self.D):
                 out[f"f*_grad_{k}"] = osc * fg[:, k] / cs[k]
                 out[f"f*_grad_var_{k}"] = osc ** 2 * fgv[:, k] / cs[k] ** 2
+        if hdims is not None:
+            fh, fhv = np.asarray(r.f_hess, dtype=np.float64), np.asarray(r.f_hess_var, dtype=np.float64)
+            for k, (a, b) in enumerate(r.hess_pairs):
+                out[f"f*_hess_{a}_{b}"] = osc * fh[:, k] / (cs[a] * cs[b])
+                out[f"f*_hess_var_{a}_{b}"] = osc ** 2 * fhv[:, k] / (cs[a] * cs[b]) ** 2
+            out["f*_lap"] = osc * np.asarray(r.f_lap, dtype=np.float64)
+            out["f*_lap_var"] = osc ** 2 * np.asarray(r.f_lap_var, dtype=np.float64)
         f_bar = self.obs_mean[:, 0]
         if len(f_bar) != len(out["f*"]):
             assert len(f_bar) == 1, f"'f_bar' did not match the length of 'f*' and f_bar len is not, got: {len(f_bar)}"
@@ -625,11 +654,13 @@ class HipSGPRModel(HipGPRModel):
         r = self._run(optimiser="none")
         return -float(r.nll[0])
 
-    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False, hessian=False) -> Dict[str, np.ndarray]:
         if full_cov:
             raise NotImplementedError("HipSGPRModel.predict(full_cov=True) is not built")
         if gradient:
             raise NotImplementedError(V.why_refused_pred_grad(["sgpr"], None, None))
+        if hessian is not False and hessian is not None:
+            raise NotImplementedError(V.why_refused_pred_hess(["sgpr"], None, None))
         return super().predict(coords, full_cov=False, apply_scale=apply_scale)
 
 
@@ -788,11 +819,13 @@ class HipSklearnGPRModel(HipGPRModel):
         r = self._run(optimiser="none")
         return float(r.nll[0])
 
-    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False) -> Dict[str, np.ndarray]:
+    def predict(self, coords, full_cov=False, apply_scale=True, gradient=False, hessian=False) -> Dict[str, np.ndarray]:
         """f* and the latent variance f*_var (clipped at 0) as sklearn returns them: no y_var, no f_bar, no rescale by
         obs_scale (sklearn_models.py:116-178); ``full_cov`` adds f*_cov."""
         if gradient:
             raise NotImplementedError(V.why_refused_pred_grad(["multistart"], None, None))
+        if hessian is not False and hessian is not None:
+            raise NotImplementedError(V.why_refused_pred_hess(["multistart"], None, None))
         out = super().predict(coords, full_cov=full_cov, apply_scale=apply_scale)
         res = {"f*": np.atleast_1d(out["f*"]), "f*_var": np.maximum(np.atleast_1d(out["f*_var"]), 0.0)}
         if full_cov:

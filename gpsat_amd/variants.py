@@ -72,6 +72,16 @@ for _k, _v in VARIANTS.items():
     assert all(_k in VARIANTS[_o].excludes for _o in _v.excludes), f"{_k}: excludes is not symmetric"
 assert all(_k in VARIANTS for _k in PRED_GRAD_EXCLUDES)
 
+# The second derivatives of the posterior mean at the prediction points, with their variances and a weighted Laplacian
+# (pred_hess): an option of the plain call as pred_grad is, and the one that pred_grad can be combined
+# with -- pred_grad then travels through PRED_HESS_ENTRY.  Matern12 and Matern32 are refused for what they are.
+PRED_HESS_ENTRY = "gpsat_fit_predict_batch_hess"
+PRED_HESS_STRUCT = "GpsatPredHess"
+PRED_HESS_ARG = "pred_hess"
+PRED_HESS_LABEL = "the second derivatives of the posterior mean at the prediction points (pred_kwargs.hessian)"
+PRED_HESS_KERNELS = ("RBF", "SquaredExponential", "Matern52")
+PRED_HESS_EXCLUDES = PRED_GRAD_EXCLUDES
+
 
 def _param_rows(asked):
     return [VARIANTS[k] for k in VARIANTS if k in asked and VARIANTS[k].param]
@@ -130,3 +140,24 @@ def why_refused_pred_grad(asked, dtype: Optional[str], kernel: Optional[str]):
     if kernel is not None and kernel not in PRED_GRAD_KERNELS:
         return f"{PRED_GRAD_ARG}: not built for kernel {kernel!r}, only for {', '.join(PRED_GRAD_KERNELS)} ({PRED_GRAD_LABEL})"
     return None
+
+
+def why_refused_pred_hess(asked, dtype: Optional[str], kernel: Optional[str]):
+    """As why_refused_pred_grad, for the second derivatives of the posterior mean (pred_hess)."""
+    if dtype is not None and dtype != "f64":
+        return f"{PRED_HESS_ARG}: built in fp64 only, not in {dtype!r} ({PRED_HESS_LABEL}): pass dtype='f64'"
+    if kernel in ("Matern12", "Exponential", "Matern32"):
+        return (f"{PRED_HESS_ARG}: kernel {kernel!r} has no second derivatives to return, the derivative of a "
+                f"{'Matern-3/2' if kernel == 'Matern32' else 'Matern-1/2'} process is not mean-square differentiable ({PRED_HESS_LABEL})")
+    for k in VARIANTS:                                               # table order, whatever the caller's
+        if k in asked and k in PRED_HESS_EXCLUDES:
+            return f"{PRED_HESS_ARG} and {VARIANTS[k].arg} cannot be combined ({PRED_HESS_LABEL}; {VARIANTS[k].label})"
+    if kernel is not None and kernel not in PRED_HESS_KERNELS:
+        return f"{PRED_HESS_ARG}: not built for kernel {kernel!r}, only for {', '.join(PRED_HESS_KERNELS)} ({PRED_HESS_LABEL})"
+    return None
+
+
+def pred_hess_pairs(dims):
+    """The pairs (a, b), a <= b, of the coordinate indices ``dims``: a ascending, then b -- the columns of f_hess."""
+    dims = sorted(set(int(d) for d in dims))
+    return [(a, b) for i, a in enumerate(dims) for b in dims[i:]]

@@ -275,6 +275,49 @@ typedef struct gpsat_pred_grad {
 int gpsat_fit_predict_batch_grad(gpsat_handle *h, const gpsat_batch *b, const gpsat_pred_grad *pg);
 
 /*
+ * The second derivatives of the posterior mean with respect to the prediction point, with their posterior variances, and a
+ * weighted Laplacian: the extension of gpsat_fit_predict_batch_hess.  Callers detect it by the presence of that symbol;
+ * gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
+ *
+ * With the notation of gpsat_pred_grad and one more radial factor, hh(r^2) = -2 dgg/d(r^2) (GPSAT_KERNEL_RBF: exp(-r^2 / 2);
+ * GPSAT_KERNEL_MATERN52: (25/3) exp(-sqrt(5) r); hh(0) = 1 and 25/3): for the set S of coordinates named by the bits of
+ * `dims` (bit a: coordinate a; |S| = m) and every pair a <= b in S, a ascending, then b -- the m (m + 1) / 2 columns of the
+ * two outputs --
+ *   h_ab[i] = d2k(x*, x_i)/dx*_a dx*_b = sf2 (hh d_{i,a} d_{i,b} / (l_a l_b) - delta_ab gg / l_a^2),   V_ab = L^-1 h_ab,
+ *   f_hess[ab] = V_ab^T z = d2 f*(x*) / dx*_a dx*_b,
+ *   f_hess_var[ab] = sf2 hh(0) (1 + 2 delta_ab) / (l_a^2 l_b^2) - V_ab^T V_ab = var(d2f/dx_a dx_b at x* | y).
+ * The weighted Laplacian sum_{a in S} c_a d2f/dx_a^2, c = lap_weight >= 0, has a solve of its own, because its variance holds
+ * the covariances between the f_aa, which are not returned otherwise:
+ *   h_lap = sum_a c_a h_aa,   f_lap = V_lap^T z,
+ *   f_lap_var = sf2 hh(0) (2 sum_a c_a^2 / l_a^4 + (sum_a c_a / l_a^2)^2) - V_lap^T V_lap.
+ * f_lap and f_lap_var both NULL and every weight 0: no such pass.  f_grad and f_grad_var, when given, are the two outputs of
+ * gpsat_fit_predict_batch_grad with its bits, from the same launch.  Units: those of y (y^2) per unit of X squared (to the
+ * fourth); a caller whose coordinates were scaled unequally gives c_a = 1 / scale_a^2 for the Laplacian in raw coordinates.
+ * A tile without observations returns the prior at theta0 (zeros and the prior terms above), a tile whose status is
+ * GPSAT_STATUS_NOT_PD or GPSAT_STATUS_NAN returns NaN.  No other covariance between components or points is returned.  Built for
+ * GPSAT_F64, the two kernels above and D <= 4, one workgroup per tile, with both optimisers.  Every other output of the call has
+ * the bits gpsat_fit_predict_batch returns; a tile's outputs have the same bits alone, inside any batch and on a second call.
+ */
+typedef struct gpsat_pred_hess {
+    void *f_hess;              /* [sum P * m(m+1)/2] doubles, host|device as b->memory: out     */
+    void *f_hess_var;          /* [sum P * m(m+1)/2] doubles: out                               */
+    void *f_lap;               /* [sum P] doubles: out, or NULL                                 */
+    void *f_lap_var;           /* [sum P] doubles: out, or NULL                                 */
+    void *f_grad;              /* [sum P * D] doubles: out, or NULL                             */
+    void *f_grad_var;          /* [sum P * D] doubles: out, or NULL                             */
+    double lap_weight[4];      /* c_a >= 0 per coordinate; 0 outside dims and beyond D         */
+    uint32_t dims;             /* bit a set: coordinate a is in S                              */
+    int32_t reserved[7];       /* must be 0                                                   */
+} gpsat_pred_hess;             /* 112 bytes */
+
+/* as gpsat_fit_predict_batch, with the outputs above.  GPSAT_EINVAL (with a message that names the reason; the handle stays
+ * usable) for GPSAT_F32, GPSAT_KERNEL_MATERN12 and GPSAT_KERNEL_MATERN32 (the derivative process is not mean-square
+ * differentiable), GPSAT_KERNEL_RQ (not built), a NULL ph, dims empty or naming a coordinate >= D, a NULL output when
+ * sum P > 0 (f_lap / f_lap_var: when the other or a weight is given; f_grad / f_grad_var: when the other is given), a negative
+ * or non-finite weight or a weight on a coordinate outside dims, non-zero reserved words, and cov_off / f_cov given. */
+int gpsat_fit_predict_batch_hess(gpsat_handle *h, const gpsat_batch *b, const gpsat_pred_hess *ph);
+
+/*
  * Held-out (cross-validation) predictions from every tile's own factor: the extension of gpsat_fit_predict_batch_cv
  * (fp64 only).  Callers detect it by the presence of that symbol; gpsat_batch keeps its layout and GPSAT_ABI_VERSION stays 4.
  *
