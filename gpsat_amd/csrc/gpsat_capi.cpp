@@ -4,7 +4,7 @@
 // Every entry point reads as a sequence of named steps; what is pure host arithmetic lives in a HIP-free header of this
 // translation unit, where it runs without a GPU (tests/test_abi.py, tests/cvfold_host_check.cpp, tests/select_bin_host_check.cpp):
 //   gpsat_fit_predict_batch: check_batch / check_multistart / check_cv / check_mean / check_noise / check_pred_grad / check_pred_hess, plan_tiles (gpsat_plan.h), stage_batch, stage_cv,
-//     setup_*, launch, fetch_batch / fetch_cv, record_timing.
+//     stage_derived, setup_*, launch, fetch_batch / fetch_cv / fetch_derived, record_timing.
 //   gpsat_fit_predict_batch_cv_refit (fit_predict_cv_refit) calls it twice: for the batch, and for the batch of its folds that
 //     gpsat_cvfold.hip builds on the device from the tables of gpsat_cvfold.h (cvfold_tables, cvfold_derive, cvfold_pack):
 //     cvr_stage_expand, cvr_derived_batch, cvr_unpack, cvr_scatter_fetch.
@@ -145,8 +145,7 @@ struct gpsat_handle : HandleQueue {
     DevBuf cv;                        // held-out predictions: fold tables, then the three outputs [sumN] each
     DevBuf cvr_cov;                   // refitted cross-validation with the joint density: cov_off, the derived batch's f_cov, sn2, residuals, lpd
     DevBuf cvr_tab, cvr_in, cvr_out;  // refitted cross-validation: fold tables, the derived batch's inputs, its predictions (+ host mode: cv outputs)
-    DevBuf pgrad;                     // gpsat_fit_predict_batch_grad, host mode: f_grad, f_grad_var [sumP, D] each
-    DevBuf phess;                     // gpsat_fit_predict_batch_hess, host mode: its (up to) six outputs, one behind the other
+    DevBuf derived;                   // gpsat_fit_predict_batch_grad / _hess, host mode: their outputs, one behind the other (stage_derived)
     DevBuf memo;                      // 64 bytes of developer statistics, then the evaluation memo [T][MEMO_WORDS] (fp32 L-BFGS batches)
     DevBuf ms;                        // multi-start: [T][MS_WORDS] state, [T][S-1][H] starts, [T][S] objectives
     // gpsat_select_batch_ex.  gpsat_smooth_batch and gpsat_glue_batch stage their inputs in sel.pts (glue: its segments in
@@ -417,6 +416,62 @@ int fetch_cv(gpsat_handle* h, const gpsat_batch* b, const gpsat_cv* cv, const gp
     const double* const dev[3] = {ca.mean, ca.f_var, ca.y_var};
     for (int i = 0; i < 3; ++i)
         if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], (size_t)d.sumN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return GPSAT_OK;
+}
+
+// The derived outputs of a call: the two of gpsat_fit_predict_batch_grad, or the (up to) six of gpsat_fit_predict_batch_hess.
+// Of each one asked for: the caller's pointer, the kernel's pointer, the byte count.
+struct DerivedOuts {
+    struct { void* user; double** dev; size_t bytes; } o[6];
+    int n = 0;
+    void add(void* user, double*& dev, size_t bytes) { o[n++] = {user, &dev, bytes}; }
+};
+
+// Fill GradArgs or HessArgs (kernel parameters: their layouts are the kernels') from the caller's struct.  The kernel writes
+// into the caller's device memory, or (host mode) into the handle's buffer, one output behind the other, which fetch_derived
+// copies back behind the launch: device mode returns host mode's bits.
+int stage_derived(gpsat_handle* h, const gpsat_batch* b, const BatchDims& d, const gpsat_pred_grad* pg, const gpsat_pred_hess* ph,
+                  gpsat::GradArgs& ga, gpsat::HessArgs& ha, DerivedOuts& t) {
+    const size_t grad_bytes = (size_t)d.sumP * b->D * sizeof(double);
+    if (pg) {
+        t.add(pg->f_grad, ga.f_grad, grad_bytes);
+        t.add(pg->f_grad_var, ga.f_grad_var, grad_bytes);
+    }
+    if (ph) {
+        const int m = __builtin_popcount(ph->dims);
+        ha.dims = ph->dims;
+        ha.npair = m * (m + 1) / 2;
+        bool lap = ph->f_lap || ph->f_lap_var;
+        for (int k = 0; k < 4; ++k) { ha.lap_w[k] = ph->lap_weight[k]; lap = lap || ph->lap_weight[k] > 0.0; }
+        const size_t pair_bytes = (size_t)d.sumP * ha.npair * sizeof(double), lap_bytes = (size_t)d.sumP * sizeof(double);
+        t.add(ph->f_hess, ha.f_hess, pair_bytes);
+        t.add(ph->f_hess_var, ha.f_hess_var, pair_bytes);
+        if (lap) {
+            t.add(ph->f_lap, ha.f_lap, lap_bytes);
+            t.add(ph->f_lap_var, ha.f_lap_var, lap_bytes);
+        }
+        if (ph->f_grad) {
+            t.add(ph->f_grad, ha.f_grad, grad_bytes);
+            t.add(ph->f_grad_var, ha.f_grad_var, grad_bytes);
+        }
+    }
+    const bool host = b->memory == GPSAT_MEM_HOST;
+    size_t total = 0, at = 0;
+    for (int k = 0; k < t.n; ++k) total += t.o[k].bytes;
+    if (host && t.n > 0)
+        if (int rc = h->derived.reserve(std::max<size_t>(total, 16))) return rc;
+    for (int k = 0; k < t.n; ++k) {
+        if (host) *t.o[k].dev = reinterpret_cast<double*>(static_cast<char*>(h->derived.p) + at);
+        else *t.o[k].dev = static_cast<double*>(d.sumP > 0 ? t.o[k].user : h->ws.p);     // sum P = 0: nothing is written, so any valid address serves
+        at += t.o[k].bytes;
+    }
+    return GPSAT_OK;
+}
+
+int fetch_derived(gpsat_handle* h, const gpsat_batch* b, const DerivedOuts& t) {
+    if (b->memory != GPSAT_MEM_HOST) return GPSAT_OK;
+    for (int k = 0; k < t.n; ++k)
+        if (t.o[k].bytes > 0) HIP_TRY(hipMemcpyAsync(t.o[k].user, *t.o[k].dev, t.o[k].bytes, hipMemcpyDeviceToHost, h->stream));
     return GPSAT_OK;
 }
 
@@ -755,52 +810,11 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     if (!launch) return fail(GPSAT_EINVAL, variant == gpsat::CV ? "held-out predictions: no kernel in this build" : "no kernel for this model in this build");
     gpsat::NoiseArgs na;
     na.obs_var = s.obs_var;
-    // the gradient's two outputs: the caller's device memory, or (host mode) the handle's, fetched behind the launch
+    // the outputs of the gradient or second-derivative call: the caller's device memory, or (host mode) the handle's
     gpsat::GradArgs ga;
-    const size_t grad_bytes = (size_t)d.sumP * b->D * sizeof(double);
-    if (j.pred_grad) {
-        if (b->memory == GPSAT_MEM_HOST) {
-            if ((rc = h->pgrad.reserve(std::max<size_t>(2 * grad_bytes, 16)))) return rc;
-            ga.f_grad = static_cast<double*>(h->pgrad.p);
-            ga.f_grad_var = ga.f_grad + (size_t)d.sumP * b->D;
-        } else if (d.sumP > 0) {
-            ga.f_grad = static_cast<double*>(j.pred_grad->f_grad);
-            ga.f_grad_var = static_cast<double*>(j.pred_grad->f_grad_var);
-        } else {                                      // nothing is written: any valid address will do
-            ga.f_grad = ga.f_grad_var = static_cast<double*>(h->ws.p);
-        }
-    }
-    // the second derivatives' outputs in the same way.  hess_out: (the caller's pointer, the kernel's, bytes) of what was asked for
     gpsat::HessArgs ha;
-    struct { void* host; double** dev; size_t bytes; } hess_out[6];
-    int n_hess_out = 0;
-    if (const gpsat_pred_hess* ph = j.pred_hess) {
-        const int m = __builtin_popcount(ph->dims);
-        ha.dims = ph->dims;
-        ha.npair = m * (m + 1) / 2;
-        bool lap = ph->f_lap || ph->f_lap_var;
-        for (int k = 0; k < 4; ++k) { ha.lap_w[k] = ph->lap_weight[k]; lap = lap || ph->lap_weight[k] > 0.0; }
-        const size_t pair_bytes = (size_t)d.sumP * ha.npair * sizeof(double), lap_bytes = (size_t)d.sumP * sizeof(double);
-        hess_out[n_hess_out++] = {ph->f_hess, &ha.f_hess, pair_bytes};
-        hess_out[n_hess_out++] = {ph->f_hess_var, &ha.f_hess_var, pair_bytes};
-        if (lap) {
-            hess_out[n_hess_out++] = {ph->f_lap, &ha.f_lap, lap_bytes};
-            hess_out[n_hess_out++] = {ph->f_lap_var, &ha.f_lap_var, lap_bytes};
-        }
-        if (ph->f_grad) {
-            hess_out[n_hess_out++] = {ph->f_grad, &ha.f_grad, grad_bytes};
-            hess_out[n_hess_out++] = {ph->f_grad_var, &ha.f_grad_var, grad_bytes};
-        }
-        size_t total = 0;
-        for (int k = 0; k < n_hess_out; ++k) total += hess_out[k].bytes;
-        if (b->memory == GPSAT_MEM_HOST && (rc = h->phess.reserve(std::max<size_t>(total, 16)))) return rc;
-        size_t at = 0;
-        for (int k = 0; k < n_hess_out; ++k) {
-            if (b->memory == GPSAT_MEM_HOST) *hess_out[k].dev = reinterpret_cast<double*>(static_cast<char*>(h->phess.p) + at);
-            else *hess_out[k].dev = static_cast<double*>(d.sumP > 0 ? hess_out[k].host : h->ws.p);   // sum P = 0: nothing is written
-            at += hess_out[k].bytes;
-        }
-    }
+    DerivedOuts derived;
+    if ((rc = stage_derived(h, b, d, j.pred_grad, j.pred_hess, ga, ha, derived))) return rc;
     gpsat::CvArgs ca;
     if (j.cv && (rc = stage_cv(h, b, j.cv, j.cv_joint, d, j.cv_tables, ca))) return rc;
 #ifdef GPSAT_DUMP
@@ -821,13 +835,7 @@ int run_tiles(gpsat_handle* h, const DenseJob& j, bool solo, bool unsliced, Laun
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     if ((rc = fetch_batch(h, b, d, s, j.mean))) return rc;
     if (j.cv && (rc = fetch_cv(h, b, j.cv, j.cv_joint, d, ca))) return rc;
-    if (j.pred_grad && b->memory == GPSAT_MEM_HOST && grad_bytes > 0) {
-        HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad, ga.f_grad, grad_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(j.pred_grad->f_grad_var, ga.f_grad_var, grad_bytes, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (j.pred_hess && b->memory == GPSAT_MEM_HOST)
-        for (int k = 0; k < n_hess_out; ++k)
-            if (hess_out[k].bytes > 0) HIP_TRY(hipMemcpyAsync(hess_out[k].host, *hess_out[k].dev, hess_out[k].bytes, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = fetch_derived(h, b, derived))) return rc;
     if (j.ms_on && j.ms->f_start)
         HIP_TRY(hipMemcpyAsync(j.ms->f_start, a.ms_fout, (size_t)b->T * j.ms->n_starts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 #ifdef GPSAT_PROFILE

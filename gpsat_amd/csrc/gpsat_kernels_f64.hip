@@ -1301,14 +1301,81 @@ __device__ __forceinline__ void evaluate(Ctx<D, KN>& c, bool want_grad, const do
     PROF_END(c, 12);
 }
 
+// ---- the panelled solve that predict_tile, predict_grad_tile and predict_hess_tile share, for one pair of 16-column chunks of
+// prediction points.  (The eight lines that load a pair's points stay written out in the three: as a helper, of any shape
+// tried, they cost kernels of every object VGPR spills and scratch -- DESIGN.md section 28.)
+//   V = L^-1 W for the two chunks, W's block in block row jr of chunk n from rhs(jr, n): panels of PR block rows like
+// phase_potrf, 4 x 2 accumulators, every V block (scratch at v0 and v0 + NB) is loaded once per 4 products and the factor once
+// per pair of chunks.  vs[n] gathers sum V^2 and ms[n] sum V z, every lane its own part (qsum adds them up): one order of
+// summation whatever the right-hand side.
+template <bool TEAM, int D, int KN, class Rhs>
+__device__ __forceinline__ void predict_solve(const Ctx<D, KN>& c, int v0, Rhs rhs, double (&vs)[2], double (&ms)[2]) {
+    const int NB = c.NB, lane = c.lane;
+    for (int j0 = 0; j0 < NB; j0 += PR) {
+        const int nr = min(PR, NB - j0);
+        f64x4 acc[PR][2];
+#pragma unroll
+        for (int r = 0; r < PR; ++r) { acc[r][0] = zero4(); acc[r][1] = zero4(); }
+        if (j0 > 0) {
+            f64x4 A[PR], B0, B1;
+#pragma unroll
+            for (int r = 0; r < PR; ++r) A[r] = ldg(c.ws, (r < nr) ? j0 + r : c.zb, lane);
+            B0 = ldg(c.ws, v0, lane);
+            B1 = ldg(c.ws, v0 + NB, lane);
+            for (int k = 0; k + 1 < j0; ++k) {          // last step peeled: unconditional loads, no copy-first
+                f64x4 nA[PR], nB0, nB1;
+#pragma unroll
+                for (int r = 0; r < PR; ++r) nA[r] = ldg(c.ws, (r < nr) ? (k + 1) * NB + j0 + r : c.zb, lane);
+                nB0 = ldg(c.ws, v0 + k + 1, lane);
+                nB1 = ldg(c.ws, v0 + NB + k + 1, lane);
+#pragma unroll
+                for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
+#pragma unroll
+                for (int r = 0; r < PR; ++r) A[r] = nA[r];
+                B0 = nB0; B1 = nB1;
+            }
+#pragma unroll
+            for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
+        }
+#pragma unroll
+        for (int r = 0; r < PR; ++r) {
+            if (r < nr) {
+                const int jr = j0 + r;
+                const f64x4 Lop = ldg(c.ws, c.dT0 + jr, lane);
+                f64x4 V[2];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const f64x4 Wb = rhs(jr, n) - acc[r][n];
+                    V[n] = zero4();
+                    mma_blk(V[n], Lop, Wb);
+                    stg(c.ws, v0 + n * NB + jr, lane, V[n]);
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        vs[n] = fma(V[n][rr], V[n][rr], vs[n]);
+                        ms[n] = fma(V[n][rr], lds_d[c.L.z + BS * jr + rowof(rr, c.q)], ms[n]);
+                    }
+                }
+#pragma unroll
+                for (int r2 = r + 1; r2 < PR; ++r2) {
+                    if (r2 < nr) {
+                        const f64x4 U = ldg(c.ws, jr * NB + j0 + r2, lane);
+                        mma_blk(acc[r2][0], U, V[0]);
+                        mma_blk(acc[r2][1], U, V[1]);
+                    }
+                }
+            }
+        }
+        if (TEAM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the V blocks stored above are this wave's next operands
+    }
+}
+
 template <int D, int KN, bool TEAM>
 __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __restrict__ Xs, double* __restrict__ fm,
                                              double* __restrict__ fv, double* __restrict__ yv, const double* theta,
                                              double* __restrict__ fcov) {
     const int NB = c.NB, lane = c.lane;
     const int PC = (c.P + BS - 1) / BS;
-    // V = L^-1 K_* for two 16-column chunks per wave, by panels of PR block rows like phase_potrf: 4 x 2 accumulators,
-    // every V block (wave-private scratch) is loaded once per 4 products and the factor once per pair of chunks
+    // V = L^-1 K_* for two 16-column chunks per wave (predict_solve, ksblock as the right-hand side)
     for (int pc0 = 2 * c.w; pc0 < PC; pc0 += 2 * NW) {
         // this wave's V scratch [2 chunks][NB] blocks, or (full covariance wanted) the per-tile store of all chunks
         const int v0 = fcov ? c.cv0 + pc0 * NB : c.vs0 + c.w * 4 * NB;
@@ -1322,64 +1389,7 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
             for (int d = 0; d < D; ++d) xa[n][d] = va[n] ? Xs[(size_t)qa * D + d] / theta[d] : 0.0;
         }
         double vs[2] = {0.0, 0.0}, ms[2] = {0.0, 0.0};
-        for (int j0 = 0; j0 < NB; j0 += PR) {
-            const int nr = min(PR, NB - j0);
-            f64x4 acc[PR][2];
-#pragma unroll
-            for (int r = 0; r < PR; ++r) { acc[r][0] = zero4(); acc[r][1] = zero4(); }
-            if (j0 > 0) {
-                f64x4 A[PR], B0, B1;
-#pragma unroll
-                for (int r = 0; r < PR; ++r) A[r] = ldg(c.ws, (r < nr) ? j0 + r : c.zb, lane);
-                B0 = ldg(c.ws, v0, lane);
-                B1 = ldg(c.ws, v0 + NB, lane);
-                for (int k = 0; k + 1 < j0; ++k) {          // last step peeled: unconditional loads, no copy-first
-                    f64x4 nA[PR], nB0, nB1;
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) nA[r] = ldg(c.ws, (r < nr) ? (k + 1) * NB + j0 + r : c.zb, lane);
-                    nB0 = ldg(c.ws, v0 + k + 1, lane);
-                    nB1 = ldg(c.ws, v0 + NB + k + 1, lane);
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) A[r] = nA[r];
-                    B0 = nB0; B1 = nB1;
-                }
-                if (0 < j0) {
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < PR; ++r) {
-                if (r < nr) {
-                    const int jr = j0 + r;
-                    const f64x4 Lop = ldg(c.ws, c.dT0 + jr, lane);
-                    f64x4 V[2];
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) {
-                        const f64x4 Wb = ksblock<D, KN>(c, jr, xa[n], va[n]) - acc[r][n];
-                        V[n] = zero4();
-                        mma_blk(V[n], Lop, Wb);
-                        stg(c.ws, v0 + n * NB + jr, lane, V[n]);
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) {
-                            vs[n] = fma(V[n][rr], V[n][rr], vs[n]);
-                            ms[n] = fma(V[n][rr], lds_d[c.L.z + BS * jr + rowof(rr, c.q)], ms[n]);
-                        }
-                    }
-#pragma unroll
-                    for (int r2 = r + 1; r2 < PR; ++r2) {
-                        if (r2 < nr) {
-                            const f64x4 U = ldg(c.ws, jr * NB + j0 + r2, lane);
-                            mma_blk(acc[r2][0], U, V[0]);
-                            mma_blk(acc[r2][1], U, V[1]);
-                        }
-                    }
-                }
-            }
-            if (TEAM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the V blocks stored above are this wave's next operands
-        }
+        predict_solve<TEAM>(c, v0, [&](int jr, int n) { return ksblock<D, KN>(c, jr, xa[n], va[n]); }, vs, ms);
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             const double vsum = qsum(vs[n]), msum = qsum(ms[n]);
@@ -1441,17 +1451,17 @@ __device__ __forceinline__ void predict_tile(Ctx<D, KN>& c, const double* __rest
 // ---- the gradient of the posterior mean at the prediction points, with its variance (gpsat_fit_predict_batch_grad), behind
 // predict_tile and from what it read: the factor, z = L^-1 y in LDS.  For every coordinate a of the prediction point,
 //   g_a = dk(x*, X)/dx*_a (kgblock),  V_a = L^-1 g_a,  f_grad[a] = V_a^T z,  f_grad_var[a] = sf2 gg(0) / l_a^2 - V_a^T V_a
-// (gg(0) l_a^-2 sf2 = d^2 k / dx*_a dx'_a at x' = x*).  The solve is predict_tile's: panels of PR block rows, two 16-column
-// chunks per wave, the wave's own V scratch -- D passes of it per pair of chunks, with kgblock as the right-hand side.  The
-// sums are accumulated as vs and ms are there: every output has one writer and one order of summation, whatever the batch.
+// (gg(0) l_a^-2 sf2 = d^2 k / dx*_a dx'_a at x' = x*).  The solve is predict_tile's (predict_solve), in the wave's own V
+// scratch -- D passes of it per pair of chunks, with kgblock as the right-hand side: every output has one writer and one order
+// of summation, whatever the batch.  The prior is written with ila = 1 / l_a here and with a division in predict_grad_fill: the
+// two round differently, so they stay two expressions.
 // One workgroup per tile (no team kernel in this row), no full covariance in the same call (the host refuses it).
 template <int KN> constexpr double gg_at_zero() { return KN == 0 ? 1.0 : KN == 2 ? 3.0 : 5.0 / 3.0; }
 
 template <int D, int KN>
 __device__ __forceinline__ void predict_grad_tile(Ctx<D, KN>& c, const double* __restrict__ Xs, double* __restrict__ fg,
                                                   double* __restrict__ fgv, const double* theta) {
-    constexpr bool TEAM = false;
-    const int NB = c.NB, lane = c.lane;
+    const int NB = c.NB;
     const int PC = (c.P + BS - 1) / BS;
     for (int pc0 = 2 * c.w; pc0 < PC; pc0 += 2 * NW) {
         const int v0 = c.vs0 + c.w * 4 * NB;
@@ -1467,61 +1477,7 @@ __device__ __forceinline__ void predict_grad_tile(Ctx<D, KN>& c, const double* _
         for (int a = 0; a < D; ++a) {
             const double ila = 1.0 / theta[a];
             double vs[2] = {0.0, 0.0}, ms[2] = {0.0, 0.0};
-            for (int j0 = 0; j0 < NB; j0 += PR) {
-                const int nr = min(PR, NB - j0);
-                f64x4 acc[PR][2];
-#pragma unroll
-                for (int r = 0; r < PR; ++r) { acc[r][0] = zero4(); acc[r][1] = zero4(); }
-                if (j0 > 0) {
-                    f64x4 A[PR], B0, B1;
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) A[r] = ldg(c.ws, (r < nr) ? j0 + r : c.zb, lane);
-                    B0 = ldg(c.ws, v0, lane);
-                    B1 = ldg(c.ws, v0 + NB, lane);
-                    for (int k = 0; k + 1 < j0; ++k) {
-                        f64x4 nA[PR], nB0, nB1;
-#pragma unroll
-                        for (int r = 0; r < PR; ++r) nA[r] = ldg(c.ws, (r < nr) ? (k + 1) * NB + j0 + r : c.zb, lane);
-                        nB0 = ldg(c.ws, v0 + k + 1, lane);
-                        nB1 = ldg(c.ws, v0 + NB + k + 1, lane);
-#pragma unroll
-                        for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-#pragma unroll
-                        for (int r = 0; r < PR; ++r) A[r] = nA[r];
-                        B0 = nB0; B1 = nB1;
-                    }
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-                }
-#pragma unroll
-                for (int r = 0; r < PR; ++r) {
-                    if (r < nr) {
-                        const int jr = j0 + r;
-                        const f64x4 Lop = ldg(c.ws, c.dT0 + jr, lane);
-                        f64x4 V[2];
-#pragma unroll
-                        for (int n = 0; n < 2; ++n) {
-                            const f64x4 Wb = kgblock<D, KN>(c, jr, xa[n], va[n], a, ila) - acc[r][n];
-                            V[n] = zero4();
-                            mma_blk(V[n], Lop, Wb);
-                            stg(c.ws, v0 + n * NB + jr, lane, V[n]);
-#pragma unroll
-                            for (int rr = 0; rr < 4; ++rr) {
-                                vs[n] = fma(V[n][rr], V[n][rr], vs[n]);
-                                ms[n] = fma(V[n][rr], lds_d[c.L.z + BS * jr + rowof(rr, c.q)], ms[n]);
-                            }
-                        }
-#pragma unroll
-                        for (int r2 = r + 1; r2 < PR; ++r2) {
-                            if (r2 < nr) {
-                                const f64x4 U = ldg(c.ws, jr * NB + j0 + r2, lane);
-                                mma_blk(acc[r2][0], U, V[0]);
-                                mma_blk(acc[r2][1], U, V[1]);
-                            }
-                        }
-                    }
-                }
-            }
+            predict_solve<false>(c, v0, [&](int jr, int n) { return kgblock<D, KN>(c, jr, xa[n], va[n], a, ila); }, vs, ms);
             const double prior = c.sf2 * gg_at_zero<KN>() * ila * ila;
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
@@ -1552,15 +1508,21 @@ __device__ __forceinline__ void predict_grad_fill(const double* theta0, int tid,
 // (a ascending, then b; column `col` of the two outputs), and once more for the weighted Laplacian when it is asked for,
 //   h = khblock,  V = L^-1 h,  mean = V^T z,  variance = prior - V^T V,
 //   prior(a, b) = sf2 hh(0) (1 + 2 delta_ab) / (l_a^2 l_b^2),  prior(Laplacian) = sf2 hh(0) (2 sum_d wl_d^2 + (sum_d wl_d)^2)
-// with wl_d = lap_w[d] / l_d^2: the fourth derivative of k at 0.  The pass is a run-time loop around ONE copy of the panelled
-// solve; one writer and one order of summation per output, no barrier, the wave's own V scratch.
+// with wl_d = lap_w[d] / l_d^2: the fourth derivative of k at 0.  The pass is a run-time loop around ONE copy of predict_solve;
+// one writer and one order of summation per output, no barrier, the wave's own V scratch.
 template <int KN> constexpr double hh_at_zero() { return KN == 0 ? 1.0 : 25.0 / 3.0; }
+// the two priors, for predict_hess_tile (sf2 and theta of the fit) and predict_hess_fill (theta0): sab = 1 / (l_a l_b)
+template <int KN> __device__ __forceinline__ constexpr double hess_pair_prior(double sf2, double sab, bool diag) {
+    return sf2 * hh_at_zero<KN>() * ((diag ? 3.0 : 1.0) * sab * sab);
+}
+template <int KN> __device__ __forceinline__ constexpr double hess_lap_prior(double sf2, double wsq, double wsum) {
+    return sf2 * hh_at_zero<KN>() * (2.0 * wsq + wsum * wsum);
+}
 
 template <int D, int KN>
 __device__ __forceinline__ void predict_hess_tile(Ctx<D, KN>& c, const double* __restrict__ Xs, const HessArgs& H, long long p0,
                                                   const double* theta) {
-    constexpr bool TEAM = false;
-    const int NB = c.NB, lane = c.lane;
+    const int NB = c.NB;
     const int PC = (c.P + BS - 1) / BS;
     const bool want_lap = H.f_lap != nullptr;
     double wl[D], wsum = 0.0, wsq = 0.0;
@@ -1592,62 +1554,8 @@ __device__ __forceinline__ void predict_hess_tile(Ctx<D, KN>& c, const double* _
                 const double sab = lap ? 0.0 : 1.0 / (theta[a] * theta[b]);
                 const double G = lap ? wsum : (a == b ? sab : 0.0);
                 double vs[2] = {0.0, 0.0}, ms[2] = {0.0, 0.0};
-                for (int j0 = 0; j0 < NB; j0 += PR) {
-                    const int nr = min(PR, NB - j0);
-                    f64x4 acc[PR][2];
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) { acc[r][0] = zero4(); acc[r][1] = zero4(); }
-                    if (j0 > 0) {
-                        f64x4 A[PR], B0, B1;
-#pragma unroll
-                        for (int r = 0; r < PR; ++r) A[r] = ldg(c.ws, (r < nr) ? j0 + r : c.zb, lane);
-                        B0 = ldg(c.ws, v0, lane);
-                        B1 = ldg(c.ws, v0 + NB, lane);
-                        for (int k = 0; k + 1 < j0; ++k) {
-                            f64x4 nA[PR], nB0, nB1;
-#pragma unroll
-                            for (int r = 0; r < PR; ++r) nA[r] = ldg(c.ws, (r < nr) ? (k + 1) * NB + j0 + r : c.zb, lane);
-                            nB0 = ldg(c.ws, v0 + k + 1, lane);
-                            nB1 = ldg(c.ws, v0 + NB + k + 1, lane);
-#pragma unroll
-                            for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-#pragma unroll
-                            for (int r = 0; r < PR; ++r) A[r] = nA[r];
-                            B0 = nB0; B1 = nB1;
-                        }
-#pragma unroll
-                        for (int r = 0; r < PR; ++r) { mma_blk(acc[r][0], A[r], B0); mma_blk(acc[r][1], A[r], B1); }
-                    }
-#pragma unroll
-                    for (int r = 0; r < PR; ++r) {
-                        if (r < nr) {
-                            const int jr = j0 + r;
-                            const f64x4 Lop = ldg(c.ws, c.dT0 + jr, lane);
-                            f64x4 V[2];
-#pragma unroll
-                            for (int n = 0; n < 2; ++n) {
-                                const f64x4 Wb = khblock<D, KN>(c, jr, xa[n], va[n], a, b, lap, sab, wl, G) - acc[r][n];
-                                V[n] = zero4();
-                                mma_blk(V[n], Lop, Wb);
-                                stg(c.ws, v0 + n * NB + jr, lane, V[n]);
-#pragma unroll
-                                for (int rr = 0; rr < 4; ++rr) {
-                                    vs[n] = fma(V[n][rr], V[n][rr], vs[n]);
-                                    ms[n] = fma(V[n][rr], lds_d[c.L.z + BS * jr + rowof(rr, c.q)], ms[n]);
-                                }
-                            }
-#pragma unroll
-                            for (int r2 = r + 1; r2 < PR; ++r2) {
-                                if (r2 < nr) {
-                                    const f64x4 U = ldg(c.ws, jr * NB + j0 + r2, lane);
-                                    mma_blk(acc[r2][0], U, V[0]);
-                                    mma_blk(acc[r2][1], U, V[1]);
-                                }
-                            }
-                        }
-                    }
-                }
-                const double prior = c.sf2 * hh_at_zero<KN>() * (lap ? 2.0 * wsq + wsum * wsum : (a == b ? 3.0 : 1.0) * sab * sab);
+                predict_solve<false>(c, v0, [&](int jr, int n) { return khblock<D, KN>(c, jr, xa[n], va[n], a, b, lap, sab, wl, G); }, vs, ms);
+                const double prior = lap ? hess_lap_prior<KN>(c.sf2, wsq, wsum) : hess_pair_prior<KN>(c.sf2, sab, a == b);
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const double vsum = qsum(vs[n]), msum = qsum(ms[n]);
@@ -1686,11 +1594,7 @@ __device__ __forceinline__ void predict_hess_fill(const double* theta0, int tid,
         if (!((H.dims >> a) & 1u)) continue;
         for (int b = a; b < D; ++b) {
             if (!((H.dims >> b) & 1u)) continue;
-            double v = nan;
-            if (theta0) {
-                const double sab = 1.0 / (theta0[a] * theta0[b]);
-                v = theta0[D] * hh_at_zero<KN>() * ((a == b ? 3.0 : 1.0) * sab * sab);
-            }
+            const double v = theta0 ? hess_pair_prior<KN>(theta0[D], 1.0 / (theta0[a] * theta0[b]), a == b) : nan;
             for (long long q = p0 + tid; q < p1; q += NT) {
                 H.f_hess[(size_t)q * H.npair + col] = theta0 ? 0.0 : nan;
                 H.f_hess_var[(size_t)q * H.npair + col] = v;
@@ -1699,7 +1603,7 @@ __device__ __forceinline__ void predict_hess_fill(const double* theta0, int tid,
         }
     }
     if (H.f_lap) {
-        const double v = theta0 ? theta0[D] * hh_at_zero<KN>() * (2.0 * wsq + wsum * wsum) : nan;
+        const double v = theta0 ? hess_lap_prior<KN>(theta0[D], wsq, wsum) : nan;
         for (long long q = p0 + tid; q < p1; q += NT) {
             H.f_lap[q] = theta0 ? 0.0 : nan;
             H.f_lap_var[q] = v;

@@ -566,20 +566,18 @@ class Engine:
                 lo_ = tuple(_alloc(sumP, dtype, beside) for _ in range(2))
                 ph.f_lap, ph.f_lap_var = (_bulk_ptr(a) for a in lo_)
                 fields.update(f_lap=lo_[0][:sumP], f_lap_var=lo_[1][:sumP])
-            if pred_grad:
-                go = tuple(_alloc(sumP * D, dtype, beside) for _ in range(2))
-                ph.f_grad, ph.f_grad_var = (_bulk_ptr(a) for a in go)
-                fields.update(f_grad=go[0][:sumP * D].reshape(sumP, D), f_grad_var=go[1][:sumP * D].reshape(sumP, D))
             args.append(C.byref(ph))
         elif pred_grad:
             name = V.PRED_GRAD_ENTRY
             if not hasattr(self._lib, name):
                 raise GpsatError(f"this libgpsat_hip.so has no {name} ({V.PRED_GRAD_LABEL})")
-            go = tuple(_alloc(sumP * D, dtype, beside) for _ in range(2))
             pg = getattr(L, V.PRED_GRAD_STRUCT)()
-            pg.f_grad, pg.f_grad_var = (_bulk_ptr(a) for a in go)
-            fields.update(f_grad=go[0][:sumP * D].reshape(sumP, D), f_grad_var=go[1][:sumP * D].reshape(sumP, D))
             args.append(C.byref(pg))
+        if pred_grad:                   # the gradient's two outputs: fields of the second derivatives' struct, or of its own
+            go = tuple(_alloc(sumP * D, dtype, beside) for _ in range(2))
+            wants = ph if pred_hess else pg
+            wants.f_grad, wants.f_grad_var = (_bulk_ptr(a) for a in go)
+            fields.update(f_grad=go[0][:sumP * D].reshape(sumP, D), f_grad_var=go[1][:sumP * D].reshape(sumP, D))
         rc = getattr(self._lib, name)(*args)
         return self._result(rc, name, res, preds, sumP, **fields)
 
