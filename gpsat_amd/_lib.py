@@ -195,6 +195,7 @@ SIGNATURES = {
     "gpsat_glue_keyed_batch": (_I, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _D, _P, _D, _I64, C.POINTER(_I64), _P, _P, _P], False),
     "gpsat_glue_keyed_timing": (_I, [_P, _P], False),
     "gpsat_glue_keyed_grad_batch": (_I, [_P, _I64, _I32, _P, _P, _P, _P, _P, _D, _P, _D, _I64, C.POINTER(_I64), _P, _P, _P, _P], False),
+    "gpsat_glue_keyed_hess_batch": (_I, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P, _D, _P, _D, _I64, C.POINTER(_I64), _P, _P, _P, _P, _P], False),
     "gpsat_project_batch": (_I, [_P, C.POINTER(GpsatProject)], False),
     "gpsat_track_batch": (_I, [_P, C.POINTER(GpsatTrack)], False),
     # the entry points of the variant table: (handle, batch, extension struct); the sparse one has been there since ABI 4

@@ -14,7 +14,7 @@
 //     boxes -> count -> scan -> fill -> unbin (select_unbin_indices, optional) -> fetch -> remember.
 //   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
 //   gpsat_glue_keyed_batch (gpsat_glue_plan.h): check -> key range, layout -> stage -> sort, run heads -> read the group count ->
-//     reduce -> fetch.
+//     reduce -> fetch.  gpsat_glue_keyed_grad_batch and gpsat_glue_keyed_hess_batch: the same steps (glue_keyed_run).
 //   gpsat_project_batch / gpsat_track_batch (gpsat_prep_plan.h): check -> constants / layout -> stage (host mode) -> kernels
 //     (tracks with groups: keys, the keyed glue's sort and run heads) -> fetch (host mode).
 #include <hip/hip_runtime.h>
@@ -1681,14 +1681,16 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
 // The two keyed glues behind their checks (gpsat_glue_plan.h): key range -> stage -> sort, run heads -> read the group count ->
 // reduce -> fetch.  Without with_grad: gpsat_glue_keyed_batch, vals [nvars][R] -> out [nvars][capacity].  Otherwise
 // gpsat_glue_keyed_grad_batch: nvars is 1, vals the value [R] and grad [ndim][R] are staged as 1 + ndim columns of the layout,
-// out is out_val [capacity] and out_grad [ndim][capacity].
+// out is out_val [capacity] and out_grad [ndim][capacity].  With hess as well: gpsat_glue_keyed_hess_batch, hess [npair][R]
+// staged behind the gradient (1 + ndim + npair columns), out_hess [npair][capacity].
 static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
                           const double* xprt, const double* vals, const double* grad, double sigma, const double* sigma_rows,
                           double max_dist, int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out,
-                          double* out_grad, bool with_grad) {
+                          double* out_grad, bool with_grad, const double* hess = nullptr, double* out_hess = nullptr) {
     char why[160];
     int rc;
-    const int ncols = with_grad ? 1 + ndim : nvars;
+    const int npair = hess ? ndim * (ndim + 1) / 2 : 0;
+    const int ncols = with_grad ? 1 + ndim + npair : nvars;
     *G = 0;
     h->glue.ms[0] = h->glue.ms[1] = h->glue.ms[2] = 0.0;
     const unsigned long long sentinel = gpsat::glue_keyed_sentinel(R, key);
@@ -1718,6 +1720,8 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
     HIP_TRY(hipMemcpyAsync(d_in + l.in_vals, vals, (size_t)nvars * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const double* d_grad = reinterpret_cast<const double*>(d_in + l.in_vals) + nR;       // behind the one value column
     if (with_grad) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + nR * sizeof(double), grad, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const double* d_hess = d_grad + (size_t)ndim * nR;                                    // behind the gradient
+    if (hess) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + (size_t)(1 + ndim) * nR * sizeof(double), hess, (size_t)npair * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sigma_rows) HIP_TRY(hipMemcpyAsync(d_in + l.in_sigma, sigma_rows, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const long long* d_key = reinterpret_cast<const long long*>(d_in);
     a.pred = reinterpret_cast<const double*>(d_in + l.in_pred);
@@ -1742,8 +1746,10 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
         a.out = reinterpret_cast<double*>(a.out_key + nG);
         a.out_count = reinterpret_cast<int*>(a.out + (size_t)ncols * nG);
         double* d_out_grad = a.out + nG;                        // behind the one value column
+        double* d_out_hess = d_out_grad + (size_t)ndim * nG;    // behind the slope
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // behind the reservation
-        if (with_grad) HIP_TRY(gpsat::launch_glue_keyed_grad(a, ng, team, d_grad, d_out_grad, h->stream));
+        if (hess) HIP_TRY(gpsat::launch_glue_keyed_hess(a, ng, team, d_grad, d_hess, d_out_grad, d_out_hess, h->stream));
+        else if (with_grad) HIP_TRY(gpsat::launch_glue_keyed_grad(a, ng, team, d_grad, d_out_grad, h->stream));
         else HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, h->stream));
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         HIP_TRY(hipMemcpyAsync(out_key, a.out_key, nG * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -1752,6 +1758,8 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
             HIP_TRY(hipMemcpyAsync(out + (size_t)v * capacity, a.out + (size_t)v * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         for (int d = 0; with_grad && d < ndim; ++d)
             HIP_TRY(hipMemcpyAsync(out_grad + (size_t)d * capacity, d_out_grad + (size_t)d * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        for (int k = 0; k < npair; ++k)
+            HIP_TRY(hipMemcpyAsync(out_hess + (size_t)k * capacity, d_out_hess + (size_t)k * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     } else {
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // no reduction: an empty interval
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1791,6 +1799,20 @@ int gpsat_glue_keyed_grad_batch(gpsat_handle* h, int64_t R, int32_t ndim, const 
         return fail(rc, why);
     return glue_keyed_run(h, R, ndim, 1, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count,
                           out_val, out_grad, true);
+}
+
+int gpsat_glue_keyed_hess_batch(gpsat_handle* h, int64_t R, int32_t ndim, const int64_t* key, const double* pred,
+                                const double* xprt, const double* val, const double* grad, const double* hess, double sigma,
+                                const double* sigma_rows, double max_dist, int64_t capacity, int64_t* G, int64_t* out_key,
+                                int32_t* out_count, double* out_val, double* out_grad, double* out_hess) {
+    if (!h) return fail(GPSAT_EINVAL, "gpsat_glue_keyed_hess_batch: handle is NULL");
+    char why[160];
+    if (int rc = gpsat::check_glue_keyed_hess(R, ndim, key, pred, xprt, val, grad, hess, sigma, sigma_rows, max_dist, capacity, G,
+                                              out_key, out_count, out_val, out_grad, out_hess, why, sizeof(why)))
+        return fail(rc, why);
+    // hess doubles as the mode; NULL only with R = 0, where the run returns before it asks
+    return glue_keyed_run(h, R, ndim, 1, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count,
+                          out_val, out_grad, true, hess, out_hess);
 }
 
 int gpsat_glue_keyed_timing(gpsat_handle* h, double* ms) {

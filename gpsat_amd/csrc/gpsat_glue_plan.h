@@ -1,4 +1,4 @@
-// gpsat_glue_plan.h -- host side of gpsat_glue_keyed_batch and gpsat_glue_keyed_grad_batch: the argument checks, the key range of
+// gpsat_glue_plan.h -- host side of gpsat_glue_keyed_batch, gpsat_glue_keyed_grad_batch and gpsat_glue_keyed_hess_batch: the argument checks, the key range of
 // a call and the layout of the handle's buffers.  Plain C++ without a HIP call, in the manner of gpsat_bin_plan.h; the checks are exported like
 // gpsat::check_noise (gpsat_plan.h), so that tests drive every refusal without a device.  Part of gpsat_capi.cpp's
 // translation unit.
@@ -19,7 +19,7 @@
 
 namespace gpsat {
 
-// The refusals of the two keyed glues, in their order, under the entry point's name.  nvars: nullptr where the entry point
+// The refusals of the keyed glues, in their order, under the entry point's name.  nvars: nullptr where the entry point
 // has none.  have_in / have_out: every input (asked for with R > 0) / every output (with capacity > 0) is there.
 inline int check_glue_keyed_common(const char* entry, int64_t R, int32_t ndim, const int32_t* nvars, double sigma,
                                    const double* sigma_rows, double max_dist, int64_t capacity, const int64_t* G, bool have_in,
@@ -58,6 +58,18 @@ int check_glue_keyed_grad(int64_t R, int32_t ndim, const int64_t* key, const dou
     return check_glue_keyed_common("gpsat_glue_keyed_grad_batch", R, ndim, nullptr, sigma, sigma_rows, max_dist, capacity, G,
                                    key && pred && xprt && val && grad, "key / pred / xprt / val / grad is NULL",
                                    out_key && out_count && out_val && out_grad, "out_key / out_count / out_val / out_grad is NULL", why, why_len);
+}
+
+// The same for gpsat_glue_keyed_hess_batch: the value, its gradient [ndim][R] and its second derivatives [npair][R],
+// npair = ndim (ndim + 1) / 2.
+int check_glue_keyed_hess(int64_t R, int32_t ndim, const int64_t* key, const double* pred, const double* xprt, const double* val,
+                          const double* grad, const double* hess, double sigma, const double* sigma_rows, double max_dist,
+                          int64_t capacity, const int64_t* G, const int64_t* out_key, const int32_t* out_count,
+                          const double* out_val, const double* out_grad, const double* out_hess, char* why, size_t why_len) {
+    return check_glue_keyed_common("gpsat_glue_keyed_hess_batch", R, ndim, nullptr, sigma, sigma_rows, max_dist, capacity, G,
+                                   key && pred && xprt && val && grad && hess, "key / pred / xprt / val / grad / hess is NULL",
+                                   out_key && out_count && out_val && out_grad && out_hess,
+                                   "out_key / out_count / out_val / out_grad / out_hess is NULL", why, why_len);
 }
 
 // After the keys are counted: the outputs must hold one record per distinct key.

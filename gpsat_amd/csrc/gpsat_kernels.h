@@ -316,6 +316,11 @@ int glue_keyed_team();                // the team width of the product
 // a.out the glued value [G]; grad [ndim][R] in source order, out_grad [ndim][G].  The teams and the tree of launch_glue_keyed.
 hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
                                   hipStream_t stream);
+// the same with the second derivatives of the glued map (gpsat_glue_keyed_hess_batch): hess [npair][R] in source order,
+// npair = ndim (ndim + 1) / 2 in the order (0,0), (0,1), (1,1); out_hess [npair][G].  a.out and out_grad: the bytes of
+// launch_glue_keyed_grad.
+hipError_t launch_glue_keyed_hess(const GlueKeyedArgs& a, long long G, int team, const double* grad, const double* hess,
+                                  double* out_grad, double* out_hess, hipStream_t stream);
 
 // raw rows to x / y and track numbers (gpsat_prep.hip); device pointers.  The scalars come from gpsat_prep_plan.h.
 struct ProjectArgs {

@@ -20,6 +20,8 @@
 //                   compile-time constant of the product: not of the other keys, the grid or the capacity.  No float atomics.
 //   glue_keyed_grad_kernel : the same walk for one value with its gradient: the glued value and the slope of the glued map,
 //                   which has a term from the weights' own dependence on the prediction location.
+//   glue_keyed_hess_kernel : that walk once more for a value with its gradient and its second derivatives: the glued value,
+//                   the slope and the Hessian of the glued map, with the weights' first and second derivatives.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -237,6 +239,121 @@ __global__ void __launch_bounds__(256) glue_keyed_grad_kernel(const GlueKeyedArg
     }
 }
 
+// The glued value, the slope and the second derivatives of the glued map: N = F W differentiated twice.
+// With q_i = 1 / sigma_i^2 the weights have d2w_i/dp_a dp_b = w_i c_iab, c_iab = u_ia u_ib - delta_ab q_i, and
+//   V_ab = sum w_i c_iab,   T_ab = sum w_i (h_iab + u_ia g_ib + u_ib g_ia + c_iab f_i) over rows whose f_i, g_ia, g_ib and h_iab
+//   are not NaN,   H_ab = (T_ab - G_a U_b - G_b U_a - F V_ab) / W,
+// for the pairs a <= b in the order (0,0), (0,1), (1,1) (ndim 1: (0,0) alone).  The team, the walk and the tree of
+// glue_keyed_grad_kernel; the weight, the limit, ws, acc, sa and ua are its statements, so that out[g] and out_grad hold the
+// bytes it returns (-ffp-contract=on contracts per source expression: the same statement, the same instruction).  A row's
+// ten gathered columns are read at the head of the iteration, before the limit is known.  Making those loads branch-free as
+// well (a column that ndim 1 lacks read as column 0) put all of them in flight at once at 116 instead of 90 VGPRs and measured
+// the same reduce time within the run-to-run spread: the other waves hide the gather already.
+// a.vals: the value [R]; grad [ndim][R]; hess [npair][R]; out_grad [ndim][G]; out_hess [npair][G].
+template <int W>
+__global__ void __launch_bounds__(256) glue_keyed_hess_kernel(const GlueKeyedArgs a, long long G, const double* __restrict__ grad,
+                                                              const double* __restrict__ hess, double* __restrict__ out_grad,
+                                                              double* __restrict__ out_hess) {
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) / W;
+    const int tl = threadIdx.x & (W - 1);
+    const bool live = g < G;
+    const unsigned s = live ? a.starts[g] : 0u, e = live ? a.starts[g + 1] : 0u;
+    const size_t R = (size_t)a.R;
+    const int ndim = a.ndim;
+    const int npair = ndim == 2 ? 3 : 1;
+    double ws = 0.0, acc = 0.0;
+    int cnt = 0;
+    double sa[2] = {0.0, 0.0}, ua[2] = {0.0, 0.0};
+    double ta[3] = {0.0, 0.0, 0.0}, va[3] = {0.0, 0.0, 0.0};
+    for (unsigned i = s + tl; i < e; i += W) {
+        const size_t r = a.perm[i];
+        const double sg = a.sigma_rows ? a.sigma_rows[r] : a.sigma;
+        double pr[2] = {0.0, 0.0}, xp[2] = {0.0, 0.0}, gv[2] = {0.0, 0.0}, hv[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                pr[d] = a.pred[(size_t)d * R + r];
+                xp[d] = a.xprt[(size_t)d * R + r];
+                gv[d] = grad[(size_t)d * R + r];
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < npair) hv[k] = hess[(size_t)k * R + r];
+        const double x = a.vals[r];                                 // NaN: out of the sums, its weight stays
+        const double cnorm = 1.0 / (sg * 2.5066282746310002);       // 1 / (sigma sqrt(2 pi))
+        const double q = 1.0 / (sg * sg);
+        double w = 1.0, d2 = 0.0;
+        double u[2] = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                const double df = pr[d] - xp[d];
+                const double zz = df / sg;
+                d2 += df * df;
+                w *= exp(-zz * zz / 2) * cnorm;
+                u[d] = -df / (sg * sg);
+            }
+        if (a.md2 >= 0.0 && !(d2 < a.md2)) continue;                // strict, and a NaN distance is outside
+        ++cnt;
+        ws += w;
+        const bool has = x == x;
+        if (has) acc += w * x;
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                ua[d] += w * u[d];
+                const double gr = gv[d];
+                if (has && gr == gr) sa[d] += w * (gr + u[d] * x);
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < npair) {
+                const int pa = k == 2 ? 1 : 0, pb = k == 0 ? 0 : 1;       // (0,0), (0,1), (1,1)
+                const double c = pa == pb ? u[pa] * u[pb] - q : u[pa] * u[pb];
+                va[k] += w * c;
+                const double h = hv[k];
+                if (has && gv[pa] == gv[pa] && gv[pb] == gv[pb] && h == h)
+                    ta[k] += w * (h + u[pa] * gv[pb] + u[pb] * gv[pa] + c * x);
+            }
+    }
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) {
+        ws += __shfl_xor(ws, off);
+        cnt += __shfl_xor(cnt, off);
+        acc += __shfl_xor(acc, off);
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            sa[d] += __shfl_xor(sa[d], off);
+            ua[d] += __shfl_xor(ua[d], off);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ta[k] += __shfl_xor(ta[k], off);
+            va[k] += __shfl_xor(va[k], off);
+        }
+    }
+    if (live && tl == 0) {
+        a.out_key[g] = (long long)a.keys_sorted[s];
+        a.out_count[g] = cnt;
+        const double f = acc / ws;
+        a.out[g] = cnt ? f : __builtin_nan("");
+        double gl[2] = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+            if (d < ndim) {
+                gl[d] = (sa[d] - f * ua[d]) / ws;
+                out_grad[(size_t)d * (size_t)G + (size_t)g] = cnt ? gl[d] : __builtin_nan("");
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < npair) {
+                const int pa = k == 2 ? 1 : 0, pb = k == 0 ? 0 : 1;
+                const double t = ta[k] - gl[pa] * ua[pb] - gl[pb] * ua[pa] - f * va[k];
+                out_hess[(size_t)k * (size_t)G + (size_t)g] = cnt ? t / ws : __builtin_nan("");
+            }
+    }
+}
+
 hipError_t glue_keyed_sort(const KeyRuns& k, const long long* key, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream) {
     if (temp) hipLaunchKernelGGL(glue_key_kernel, dim3((unsigned)((k.R + 255) / 256)), dim3(256), 0, stream, k, key);
     return key_runs(k, nullptr, nullptr, after_sort, temp, temp_bytes, stream);
@@ -271,6 +388,13 @@ hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team,
     if (G <= 0) return hipSuccess;
     const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
     return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_grad_kernel<decltype(w)::value>, grid, block, 0, stream, a, G, grad, out_grad); });
+}
+
+hipError_t launch_glue_keyed_hess(const GlueKeyedArgs& a, long long G, int team, const double* grad, const double* hess,
+                                  double* out_grad, double* out_hess, hipStream_t stream) {
+    if (G <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
+    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_hess_kernel<decltype(w)::value>, grid, block, 0, stream, a, G, grad, hess, out_grad, out_hess); });
 }
 
 }  // namespace gpsat

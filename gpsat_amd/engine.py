@@ -846,8 +846,46 @@ class Engine:
         n = int(n.value)
         return keys[:n].copy(), counts[:n].copy(), out_val[:n].copy(), np.ascontiguousarray(out_grad[:, :n])
 
+    def glue_keyed_hess_batch(self, key, pred, xprt, val, grad, hess, sigma, max_dist=None):
+        """The glued value, the exact slope and the exact second derivatives of the glued map per key
+        (gpsat_glue_keyed_hess_batch): the arguments of glue_keyed_grad_batch and hess [npair, R], the second derivatives of
+        val for the pairs a <= b of the glue axes in the order of variants.pred_hess_pairs, (0,0), (0,1), (1,1).  Returns
+        (keys [G] ascending, counts [G], out_val [G], out_grad [ndim, G], out_hess [npair, G]); out_val and out_grad hold the
+        bytes glue_keyed_grad_batch returns, out_hess the second derivative of that formula with respect to the prediction
+        location, the terms from the weights' first and second derivatives included."""
+        if not hasattr(self._lib, "gpsat_glue_keyed_hess_batch"):
+            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_hess_batch: rebuild the library (there is no host fallback)")
+        key = np.ascontiguousarray(key, dtype=np.int64)
+        pred = np.ascontiguousarray(pred, dtype=np.float64)
+        xprt = np.ascontiguousarray(xprt, dtype=np.float64)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        grad = np.ascontiguousarray(grad, dtype=np.float64)
+        hess = np.ascontiguousarray(hess, dtype=np.float64)
+        ndim, R = pred.shape
+        npair = ndim * (ndim + 1) // 2
+        assert key.shape == (R,) and xprt.shape == pred.shape and val.shape == (R,) and grad.shape == pred.shape
+        assert hess.shape == (npair, R)
+        srow = None
+        if np.ndim(sigma) > 0:
+            srow = np.ascontiguousarray(sigma, dtype=np.float64)
+            assert srow.shape == (R,)
+        md = float("inf") if max_dist is None else float(max_dist)
+        # capacity R always suffices (glue_keyed_batch)
+        keys, counts = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int32)
+        out_val, out_grad, out_hess = np.empty(R, dtype=np.float64), np.empty((ndim, R), dtype=np.float64), np.empty((npair, R), dtype=np.float64)
+        n = C.c_int64(0)
+        rc = self._lib.gpsat_glue_keyed_hess_batch(self._h, R, ndim, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(val), _ptr(grad), _ptr(hess),
+                                                   0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
+                                                   md, R, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out_val), _ptr(out_grad), _ptr(out_hess))
+        if rc != 0:
+            raise GpsatError(f"gpsat_glue_keyed_hess_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        n = int(n.value)
+        return (keys[:n].copy(), counts[:n].copy(), out_val[:n].copy(), np.ascontiguousarray(out_grad[:, :n]),
+                np.ascontiguousarray(out_hess[:, :n]))
+
     def glue_keyed_timing(self):
-        """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch or glue_keyed_grad_batch on this engine."""
+        """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch, glue_keyed_grad_batch or
+        glue_keyed_hess_batch on this engine."""
         ms = np.zeros(3)
         rc = self._lib.gpsat_glue_keyed_timing(self._h, _ptr(ms))
         if rc != 0:

@@ -600,6 +600,34 @@ int gpsat_glue_keyed_grad_batch(gpsat_handle *h, int64_t R, int32_t ndim, const 
                                 int32_t *out_count, double *out_val, double *out_grad);
 
 /*
+ * The glued value with the exact slope and the exact second derivatives of the glued map, by key (added within ABI 4, check
+ * for the symbol).  Every row carries a value f_i, its gradient g_ia and its second derivatives h_iab = d2f_i/dp_a dp_b for
+ * the pairs a <= b of the ndim glue axes, npair = ndim (ndim + 1) / 2 of them in the order (0,0), (0,1), (1,1) (ndim 1:
+ * (0,0) alone).  With u_ia as in gpsat_glue_keyed_grad_batch and q_i = 1 / sigma_i^2 the weights have
+ * d2w_i/dp_a dp_b = w_i (u_ia u_ib - delta_ab q_i).  Per key, over the rows that take part, with W, F, U_a, S_a and G_a of
+ * gpsat_glue_keyed_grad_batch:
+ *     V_ab = sum w_i (u_ia u_ib - delta_ab q_i),
+ *     T_ab = sum_{f_i, g_ia, g_ib and h_iab not NaN} w_i (h_iab + u_ia g_ib + u_ib g_ia + (u_ia u_ib - delta_ab q_i) f_i),
+ *     H_ab = (T_ab - G_a U_b - G_b U_a - F V_ab) / W,
+ * which is N = F W differentiated twice.  A row whose entries are NaN stays out of the numerators (of F with a NaN f_i, of
+ * S_a with a NaN f_i or g_ia, of T_ab with a NaN among f_i, g_ia, g_ib, h_iab); its weight stays in W, U and V.  The plain
+ * weighted average of the h_iab leaves out terms of size (disagreement of neighbouring experts) / sigma^2 and
+ * (disagreement of their slopes) x (their spacing) / sigma^2: it is the Hessian of nothing.
+ * val        : host fp64 [R];  grad: host fp64 [ndim][R];  hess: host fp64 [npair][R].
+ *   out_val  : host out [capacity], F;  out_grad: host out, G_a of record j at out_grad[a * capacity + j]: both the bytes
+ *              gpsat_glue_keyed_grad_batch returns on these rows;
+ *   out_hess : host out, pair k of record j at out_hess[k * capacity + j].
+ * Everything else -- key, pred, xprt, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count, the return codes (capacity
+ * < G: GPSAT_EINVAL with G valid), the determinism and the timing calls -- is as in gpsat_glue_keyed_batch; the workspace
+ * holds 1 + ndim + npair value columns (about 32 + 8 (3 ndim + npair + 3) bytes per row).  A key with count 0 has NaN in F,
+ * every G_a and every H_ab.
+ */
+int gpsat_glue_keyed_hess_batch(gpsat_handle *h, int64_t R, int32_t ndim, const int64_t *key, const double *pred,
+                                const double *xprt, const double *val, const double *grad, const double *hess,
+                                double sigma, const double *sigma_rows, double max_dist, int64_t capacity, int64_t *G,
+                                int64_t *out_key, int32_t *out_count, double *out_val, double *out_grad, double *out_hess);
+
+/*
  * Binning of raw observations on a regular grid, all groups in one call (added within ABI 4, check for the symbol).
  * Replaces DataPrep.bin_data_by / DataPrep.bin_data (GPSat/dataprepper.py:21-401): per group (day, satellite, ...) a
  * scipy.stats.binned_statistic_2d (1-D: binned_statistic) of `v` over the bins of `ex` x `ey`.  Every statistic of every
