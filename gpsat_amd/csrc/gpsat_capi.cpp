@@ -13,8 +13,8 @@
 //   gpsat_select_batch_ex (gpsat_select_plan.h): check -> cache hit? -> chunks -> stage -> bin (select_bin_table, optional) ->
 //     boxes -> count -> scan -> fill -> unbin (select_unbin_indices, optional) -> fetch -> remember.
 //   gpsat_bin_batch (gpsat_bin_plan.h): check -> layout, scales -> stage -> sort -> read counts -> stats -> fetch.
-//   gpsat_glue_keyed_batch (gpsat_glue_plan.h): check -> key range, layout -> stage -> sort, run heads -> read the group count ->
-//     reduce -> fetch.  gpsat_glue_keyed_grad_batch and gpsat_glue_keyed_hess_batch: the same steps (glue_keyed_run).
+//   gpsat_glue_keyed_batch, gpsat_glue_keyed_grad_batch, gpsat_glue_keyed_hess_batch (gpsat_glue_plan.h): check, then
+//     glue_keyed_run by order 0, 1, 2: key range, layout -> stage -> sort, run heads -> read the group count -> reduce -> fetch.
 //   gpsat_project_batch / gpsat_track_batch (gpsat_prep_plan.h): check -> constants / layout -> stage (host mode) -> kernels
 //     (tracks with groups: keys, the keyed glue's sort and run heads) -> fetch (host mode).
 #include <hip/hip_runtime.h>
@@ -1678,19 +1678,22 @@ int gpsat_glue_batch(gpsat_handle* h, int64_t R, int32_t G, int32_t ndim, int32_
     return record_timing(h, 1, 2);                              // no ev[0] / ev[3] here: the total is the kernel time
 }
 
-// The two keyed glues behind their checks (gpsat_glue_plan.h): key range -> stage -> sort, run heads -> read the group count ->
-// reduce -> fetch.  Without with_grad: gpsat_glue_keyed_batch, vals [nvars][R] -> out [nvars][capacity].  Otherwise
-// gpsat_glue_keyed_grad_batch: nvars is 1, vals the value [R] and grad [ndim][R] are staged as 1 + ndim columns of the layout,
-// out is out_val [capacity] and out_grad [ndim][capacity].  With hess as well: gpsat_glue_keyed_hess_batch, hess [npair][R]
-// staged behind the gradient (1 + ndim + npair columns), out_hess [npair][capacity].
-static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
-                          const double* xprt, const double* vals, const double* grad, double sigma, const double* sigma_rows,
-                          double max_dist, int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out,
-                          double* out_grad, bool with_grad, const double* hess = nullptr, double* out_hess = nullptr) {
+// What the keyed glue of order 1 (grad [ndim][R] -> out_grad [ndim][capacity]) and of order 2 (hess [npair][R] -> out_hess
+// [npair][capacity] as well) has beside the columns of order 0; nullptr where the order has none.
+struct GlueKeyedDerivs { const double *grad, *hess; double *out_grad, *out_hess; };
+
+// The three keyed glues behind their checks (gpsat_glue_plan.h): key range -> stage -> sort, run heads -> read the group count
+// -> reduce -> fetch.  Order 0: gpsat_glue_keyed_batch, vals [nvars][R] -> out [nvars][capacity].  Order 1:
+// gpsat_glue_keyed_grad_batch, nvars is 1, vals the value [R] -> out the glued value [capacity].  Order 2:
+// gpsat_glue_keyed_hess_batch.  The value columns, the gradient and the second derivatives are staged one behind the other as
+// nvars + ndim + npair columns of the layout, and so are their outputs.
+static int glue_keyed_run(gpsat_handle* h, int order, int64_t R, int32_t ndim, int32_t nvars, const int64_t* key, const double* pred,
+                          const double* xprt, const double* vals, const GlueKeyedDerivs& dv, double sigma, const double* sigma_rows,
+                          double max_dist, int64_t capacity, int64_t* G, int64_t* out_key, int32_t* out_count, double* out) {
     char why[160];
     int rc;
-    const int npair = hess ? ndim * (ndim + 1) / 2 : 0;
-    const int ncols = with_grad ? 1 + ndim + npair : nvars;
+    const int ngrad = order >= 1 ? ndim : 0, npair = order >= 2 ? ndim * (ndim + 1) / 2 : 0;
+    const int ncols = nvars + ngrad + npair;
     *G = 0;
     h->glue.ms[0] = h->glue.ms[1] = h->glue.ms[2] = 0.0;
     const unsigned long long sentinel = gpsat::glue_keyed_sentinel(R, key);
@@ -1708,7 +1711,7 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
     if ((rc = gb.kr.reserve(l))) return rc;
     // ---- stage
     const size_t nR = (size_t)R;
-    gpsat::GlueKeyedArgs a;
+    gpsat::GlueKeyedOrderArgs a;
     std::memset(&a, 0, sizeof(a));
     a.R = R; a.ndim = ndim; a.nvars = nvars; a.sentinel = sentinel;
     a.sigma = sigma; a.md2 = gpsat::glue_keyed_md2(max_dist);
@@ -1717,16 +1720,18 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
     HIP_TRY(hipMemcpyAsync(d_in, key, nR * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_in + l.in_pred, pred, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_in + l.in_xprt, xprt, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + l.in_vals, vals, (size_t)nvars * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const double* d_grad = reinterpret_cast<const double*>(d_in + l.in_vals) + nR;       // behind the one value column
-    if (with_grad) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + nR * sizeof(double), grad, (size_t)ndim * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const double* d_hess = d_grad + (size_t)ndim * nR;                                    // behind the gradient
-    if (hess) HIP_TRY(hipMemcpyAsync(d_in + l.in_vals + (size_t)(1 + ndim) * nR * sizeof(double), hess, (size_t)npair * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double* d_vals = reinterpret_cast<double*>(d_in + l.in_vals);
+    double *d_grad = d_vals + (size_t)nvars * nR, *d_hess = d_grad + (size_t)ngrad * nR;    // behind the value columns, behind the gradient
+    HIP_TRY(hipMemcpyAsync(d_vals, vals, (size_t)nvars * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (ngrad) HIP_TRY(hipMemcpyAsync(d_grad, dv.grad, (size_t)ngrad * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (npair) HIP_TRY(hipMemcpyAsync(d_hess, dv.hess, (size_t)npair * nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sigma_rows) HIP_TRY(hipMemcpyAsync(d_in + l.in_sigma, sigma_rows, nR * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const long long* d_key = reinterpret_cast<const long long*>(d_in);
     a.pred = reinterpret_cast<const double*>(d_in + l.in_pred);
     a.xprt = reinterpret_cast<const double*>(d_in + l.in_xprt);
-    a.vals = reinterpret_cast<const double*>(d_in + l.in_vals);
+    a.vals = d_vals;
+    a.grad = ngrad ? d_grad : nullptr;
+    a.hess = npair ? d_hess : nullptr;
     a.sigma_rows = sigma_rows ? reinterpret_cast<const double*>(d_in + l.in_sigma) : nullptr;
     gb.kr.bind(a);
     // ---- sort and run heads (the kernel time starts once the scratch is there), read the counts
@@ -1745,21 +1750,17 @@ static int glue_keyed_run(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nvar
         a.out_key = static_cast<long long*>(gb.out.p);
         a.out = reinterpret_cast<double*>(a.out_key + nG);
         a.out_count = reinterpret_cast<int*>(a.out + (size_t)ncols * nG);
-        double* d_out_grad = a.out + nG;                        // behind the one value column
-        double* d_out_hess = d_out_grad + (size_t)ndim * nG;    // behind the slope
+        a.out_grad = ngrad ? a.out + (size_t)nvars * nG : nullptr;                    // behind the value columns
+        a.out_hess = npair ? a.out + (size_t)(nvars + ngrad) * nG : nullptr;          // behind the slope
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // behind the reservation
-        if (hess) HIP_TRY(gpsat::launch_glue_keyed_hess(a, ng, team, d_grad, d_hess, d_out_grad, d_out_hess, h->stream));
-        else if (with_grad) HIP_TRY(gpsat::launch_glue_keyed_grad(a, ng, team, d_grad, d_out_grad, h->stream));
-        else HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, h->stream));
+        HIP_TRY(gpsat::launch_glue_keyed(a, ng, team, order, h->stream));
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         HIP_TRY(hipMemcpyAsync(out_key, a.out_key, nG * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(out_count, a.out_count, nG * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        for (int v = 0; v < nvars; ++v)
-            HIP_TRY(hipMemcpyAsync(out + (size_t)v * capacity, a.out + (size_t)v * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        for (int d = 0; with_grad && d < ndim; ++d)
-            HIP_TRY(hipMemcpyAsync(out_grad + (size_t)d * capacity, d_out_grad + (size_t)d * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        for (int k = 0; k < npair; ++k)
-            HIP_TRY(hipMemcpyAsync(out_hess + (size_t)k * capacity, d_out_hess + (size_t)k * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        const struct { double* host; const double* dev; int n; } outs[3] = {{out, a.out, nvars}, {dv.out_grad, a.out_grad, ngrad}, {dv.out_hess, a.out_hess, npair}};
+        for (const auto& o : outs)
+            for (int c = 0; c < o.n; ++c)
+                HIP_TRY(hipMemcpyAsync(o.host + (size_t)c * capacity, o.dev + (size_t)c * nG, nG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     } else {
         HIP_TRY(hipEventRecord(gb.ev[2], h->stream));           // no reduction: an empty interval
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1784,8 +1785,8 @@ int gpsat_glue_keyed_batch(gpsat_handle* h, int64_t R, int32_t ndim, int32_t nva
     if (int rc = gpsat::check_glue_keyed(R, ndim, nvars, key, pred, xprt, vals, sigma, sigma_rows, max_dist, capacity, G, out_key,
                                          out_count, out, why, sizeof(why)))
         return fail(rc, why);
-    return glue_keyed_run(h, R, ndim, nvars, key, pred, xprt, vals, nullptr, sigma, sigma_rows, max_dist, capacity, G, out_key,
-                          out_count, out, nullptr, false);
+    return glue_keyed_run(h, 0, R, ndim, nvars, key, pred, xprt, vals, {nullptr, nullptr, nullptr, nullptr}, sigma, sigma_rows, max_dist,
+                          capacity, G, out_key, out_count, out);
 }
 
 int gpsat_glue_keyed_grad_batch(gpsat_handle* h, int64_t R, int32_t ndim, const int64_t* key, const double* pred,
@@ -1797,8 +1798,8 @@ int gpsat_glue_keyed_grad_batch(gpsat_handle* h, int64_t R, int32_t ndim, const 
     if (int rc = gpsat::check_glue_keyed_grad(R, ndim, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key,
                                               out_count, out_val, out_grad, why, sizeof(why)))
         return fail(rc, why);
-    return glue_keyed_run(h, R, ndim, 1, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count,
-                          out_val, out_grad, true);
+    return glue_keyed_run(h, 1, R, ndim, 1, key, pred, xprt, val, {grad, nullptr, out_grad, nullptr}, sigma, sigma_rows, max_dist,
+                          capacity, G, out_key, out_count, out_val);
 }
 
 int gpsat_glue_keyed_hess_batch(gpsat_handle* h, int64_t R, int32_t ndim, const int64_t* key, const double* pred,
@@ -1810,9 +1811,8 @@ int gpsat_glue_keyed_hess_batch(gpsat_handle* h, int64_t R, int32_t ndim, const 
     if (int rc = gpsat::check_glue_keyed_hess(R, ndim, key, pred, xprt, val, grad, hess, sigma, sigma_rows, max_dist, capacity, G,
                                               out_key, out_count, out_val, out_grad, out_hess, why, sizeof(why)))
         return fail(rc, why);
-    // hess doubles as the mode; NULL only with R = 0, where the run returns before it asks
-    return glue_keyed_run(h, R, ndim, 1, key, pred, xprt, val, grad, sigma, sigma_rows, max_dist, capacity, G, out_key, out_count,
-                          out_val, out_grad, true, hess, out_hess);
+    return glue_keyed_run(h, 2, R, ndim, 1, key, pred, xprt, val, {grad, hess, out_grad, out_hess}, sigma, sigma_rows, max_dist,
+                          capacity, G, out_key, out_count, out_val);
 }
 
 int gpsat_glue_keyed_timing(gpsat_handle* h, double* ms) {

@@ -307,20 +307,20 @@ struct GlueKeyedArgs : KeyRuns {      // sentinel: largest key + 1, the key of i
     int* out_count;                   // [G] rows that took part
     double* out;                      // [nvars][G]
 };
+// with what the orders above 0 add (gpsat_glue_keyed_grad_batch, _hess_batch; vals is the one value [R], nvars 1): from order 1
+// grad [ndim][R] and out_grad [ndim][G]; order 2 hess [npair][R] and out_hess [npair][G], npair = ndim (ndim + 1) / 2 in the
+// order (0,0), (0,1), (1,1); nullptr where the order has none
+struct GlueKeyedOrderArgs : GlueKeyedArgs {
+    const double *grad, *hess;
+    double *out_grad, *out_hess;
+};
 // key_runs on the keys as a caller gave them: key [R], < 0: the row is ignored.  Also the sort of the grouped tracks.
 hipError_t glue_keyed_sort(const KeyRuns& k, const long long* key, void* temp, size_t& temp_bytes, hipEvent_t after_sort, hipStream_t stream);
-// one team of `team` lanes per group, gathering through the permutation; team in {1, 4, 8, 16, 32, 64}
-hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream);
+// one team of `team` lanes per group, gathering through the permutation; team in {1, 4, 8, 16, 32, 64}.  order 0: the glued
+// columns; 1: the glued value and the exact slope of the glued map; 2: its second derivatives as well.  What an order shares
+// with the one below holds the same bytes.
+hipError_t launch_glue_keyed(const GlueKeyedOrderArgs& a, long long G, int team, int order, hipStream_t stream);
 int glue_keyed_team();                // the team width of the product
-// the glued value and the exact slope of the glued map (gpsat_glue_keyed_grad_batch): a.vals is the value [R], a.nvars 1,
-// a.out the glued value [G]; grad [ndim][R] in source order, out_grad [ndim][G].  The teams and the tree of launch_glue_keyed.
-hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
-                                  hipStream_t stream);
-// the same with the second derivatives of the glued map (gpsat_glue_keyed_hess_batch): hess [npair][R] in source order,
-// npair = ndim (ndim + 1) / 2 in the order (0,0), (0,1), (1,1); out_hess [npair][G].  a.out and out_grad: the bytes of
-// launch_glue_keyed_grad.
-hipError_t launch_glue_keyed_hess(const GlueKeyedArgs& a, long long G, int team, const double* grad, const double* hess,
-                                  double* out_grad, double* out_hess, hipStream_t stream);
 
 // raw rows to x / y and track numbers (gpsat_prep.hip); device pointers.  The scalars come from gpsat_prep_plan.h.
 struct ProjectArgs {

@@ -377,24 +377,18 @@ static hipError_t dispatch_team(int team, Launch launch) {
     return hipGetLastError();
 }
 
-hipError_t launch_glue_keyed(const GlueKeyedArgs& a, long long G, int team, hipStream_t stream) {
+// The kernels take the GlueKeyedArgs part of `a` by value and the order's columns as arguments of their own.
+hipError_t launch_glue_keyed(const GlueKeyedOrderArgs& a, long long G, int team, int order, hipStream_t stream) {
     if (G <= 0) return hipSuccess;
+    if (order < 0 || order > 2) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
-    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_kernel<decltype(w)::value>, grid, block, 0, stream, a, G); });
-}
-
-hipError_t launch_glue_keyed_grad(const GlueKeyedArgs& a, long long G, int team, const double* grad, double* out_grad,
-                                  hipStream_t stream) {
-    if (G <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
-    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_grad_kernel<decltype(w)::value>, grid, block, 0, stream, a, G, grad, out_grad); });
-}
-
-hipError_t launch_glue_keyed_hess(const GlueKeyedArgs& a, long long G, int team, const double* grad, const double* hess,
-                                  double* out_grad, double* out_hess, hipStream_t stream) {
-    if (G <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((G * team + 255) / 256)), block(256);
-    return dispatch_team(team, [&](auto w) { hipLaunchKernelGGL(glue_keyed_hess_kernel<decltype(w)::value>, grid, block, 0, stream, a, G, grad, hess, out_grad, out_hess); });
+    const GlueKeyedArgs& base = a;
+    return dispatch_team(team, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (order == 0) hipLaunchKernelGGL(glue_keyed_kernel<W>, grid, block, 0, stream, base, G);
+        else if (order == 1) hipLaunchKernelGGL(glue_keyed_grad_kernel<W>, grid, block, 0, stream, base, G, a.grad, a.out_grad);
+        else hipLaunchKernelGGL(glue_keyed_hess_kernel<W>, grid, block, 0, stream, base, G, a.grad, a.hess, a.out_grad, a.out_hess);
+    });
 }
 
 }  // namespace gpsat

@@ -779,40 +779,45 @@ class Engine:
             raise GpsatError(f"gpsat_glue_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
         return out
 
-    def glue_keyed_batch(self, key, pred, xprt, vals, sigma, max_dist=None):
-        """Weighted combination of overlapping predictions grouped by an integer key on the device
-        (gpsat_glue_keyed_batch): rows in any order; key [R] (negative: the row is ignored); pred, xprt [ndim, R];
-        vals [nvars, R]; sigma scalar or per row [R]; max_dist: rows at that distance from their expert or beyond stay
-        out (None: no limit).  Returns (keys [G] ascending, counts [G] rows that took part, out [nvars, G])."""
-        if not hasattr(self._lib, "gpsat_glue_keyed_batch"):
-            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_batch: rebuild the library (there is no host fallback)")
+    def _glue_keyed(self, entry, key, pred, xprt, cols, sigma, max_dist):
+        """What the keyed glues share.  entry: the C entry point; cols: its value columns in the order of its arguments,
+        as (array, rows) with [R] behind the rows -- rows 0: none, [R] alone; a function of ndim; or None: the array's own first
+        axis, which the entry point takes behind ndim; every column has an output of its own shape with [G] behind the rows.
+        Returns (keys [G], counts [G]) and those outputs."""
+        if not hasattr(self._lib, entry):
+            raise GpsatError(f"{L.LIB_PATH} does not export {entry}: rebuild the library (there is no host fallback)")
         key = np.ascontiguousarray(key, dtype=np.int64)
         pred = np.ascontiguousarray(pred, dtype=np.float64)
         xprt = np.ascontiguousarray(xprt, dtype=np.float64)
-        vals = np.ascontiguousarray(vals, dtype=np.float64)
         ndim, R = pred.shape
-        nvars = vals.shape[0]
-        assert key.shape == (R,) and xprt.shape == pred.shape and vals.shape[1] == R
+        assert key.shape == (R,) and xprt.shape == pred.shape
+        cols = [(np.ascontiguousarray(c, dtype=np.float64), rows) for c, rows in cols]
+        dims = [c.shape[0] for c, rows in cols if rows is None]
+        cols = [(c, c.shape[:1] if rows is None else (rows(ndim),) if callable(rows) else ()) for c, rows in cols]
+        assert all(c.shape == lead + (R,) for c, lead in cols)
         srow = None
         if np.ndim(sigma) > 0:
             srow = np.ascontiguousarray(sigma, dtype=np.float64)
             assert srow.shape == (R,)
         md = float("inf") if max_dist is None else float(max_dist)
-
-        def call(cap):
-            keys, counts = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int32)
-            out = np.empty((nvars, cap), dtype=np.float64)
-            n = C.c_int64(0)
-            rc = self._lib.gpsat_glue_keyed_batch(self._h, R, ndim, nvars, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(vals),
-                                                  0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
-                                                  md, cap, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out))
-            return rc, int(n.value), keys, counts, out
-
         # capacity R always suffices; only the first G records of the outputs are ever written (untouched pages cost nothing)
-        rc, n, keys, counts, out = call(R)
+        keys, counts = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int32)
+        outs = [np.empty(lead + (R,), dtype=np.float64) for _, lead in cols]
+        n = C.c_int64(0)
+        rc = getattr(self._lib, entry)(self._h, R, ndim, *dims, _ptr(key), _ptr(pred), _ptr(xprt), *(_ptr(c) for c, _ in cols),
+                                       0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
+                                       md, R, C.byref(n), _ptr(keys), _ptr(counts), *(_ptr(o) for o in outs))
         if rc != 0:
-            raise GpsatError(f"gpsat_glue_keyed_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
-        return keys[:n].copy(), counts[:n].copy(), np.ascontiguousarray(out[:, :n])
+            raise GpsatError(f"{entry} failed ({rc}): {self._lib.gpsat_last_error().decode()}")
+        n = int(n.value)
+        return (keys[:n].copy(), counts[:n].copy()) + tuple(o[..., :n].copy() for o in outs)
+
+    def glue_keyed_batch(self, key, pred, xprt, vals, sigma, max_dist=None):
+        """Weighted combination of overlapping predictions grouped by an integer key on the device
+        (gpsat_glue_keyed_batch): rows in any order; key [R] (negative: the row is ignored); pred, xprt [ndim, R];
+        vals [nvars, R]; sigma scalar or per row [R]; max_dist: rows at that distance from their expert or beyond stay
+        out (None: no limit).  Returns (keys [G] ascending, counts [G] rows that took part, out [nvars, G])."""
+        return self._glue_keyed("gpsat_glue_keyed_batch", key, pred, xprt, [(vals, None)], sigma, max_dist)
 
     def glue_keyed_grad_batch(self, key, pred, xprt, val, grad, sigma, max_dist=None):
         """The glued value and the exact slope of the glued map per key (gpsat_glue_keyed_grad_batch): the arguments of
@@ -820,31 +825,7 @@ class Engine:
         (keys [G] ascending, counts [G], out_val [G], out_grad [ndim, G]); out_val holds the bytes glue_keyed_batch returns
         for val, out_grad the derivative of that formula with respect to the prediction location, the term from the
         weights' own dependence on it included."""
-        if not hasattr(self._lib, "gpsat_glue_keyed_grad_batch"):
-            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_grad_batch: rebuild the library (there is no host fallback)")
-        key = np.ascontiguousarray(key, dtype=np.int64)
-        pred = np.ascontiguousarray(pred, dtype=np.float64)
-        xprt = np.ascontiguousarray(xprt, dtype=np.float64)
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        grad = np.ascontiguousarray(grad, dtype=np.float64)
-        ndim, R = pred.shape
-        assert key.shape == (R,) and xprt.shape == pred.shape and val.shape == (R,) and grad.shape == pred.shape
-        srow = None
-        if np.ndim(sigma) > 0:
-            srow = np.ascontiguousarray(sigma, dtype=np.float64)
-            assert srow.shape == (R,)
-        md = float("inf") if max_dist is None else float(max_dist)
-        # capacity R always suffices (glue_keyed_batch)
-        keys, counts = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int32)
-        out_val, out_grad = np.empty(R, dtype=np.float64), np.empty((ndim, R), dtype=np.float64)
-        n = C.c_int64(0)
-        rc = self._lib.gpsat_glue_keyed_grad_batch(self._h, R, ndim, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(val), _ptr(grad),
-                                                   0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
-                                                   md, R, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out_val), _ptr(out_grad))
-        if rc != 0:
-            raise GpsatError(f"gpsat_glue_keyed_grad_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
-        n = int(n.value)
-        return keys[:n].copy(), counts[:n].copy(), out_val[:n].copy(), np.ascontiguousarray(out_grad[:, :n])
+        return self._glue_keyed("gpsat_glue_keyed_grad_batch", key, pred, xprt, [(val, 0), (grad, lambda ndim: ndim)], sigma, max_dist)
 
     def glue_keyed_hess_batch(self, key, pred, xprt, val, grad, hess, sigma, max_dist=None):
         """The glued value, the exact slope and the exact second derivatives of the glued map per key
@@ -853,35 +834,8 @@ class Engine:
         (keys [G] ascending, counts [G], out_val [G], out_grad [ndim, G], out_hess [npair, G]); out_val and out_grad hold the
         bytes glue_keyed_grad_batch returns, out_hess the second derivative of that formula with respect to the prediction
         location, the terms from the weights' first and second derivatives included."""
-        if not hasattr(self._lib, "gpsat_glue_keyed_hess_batch"):
-            raise GpsatError(f"{L.LIB_PATH} does not export gpsat_glue_keyed_hess_batch: rebuild the library (there is no host fallback)")
-        key = np.ascontiguousarray(key, dtype=np.int64)
-        pred = np.ascontiguousarray(pred, dtype=np.float64)
-        xprt = np.ascontiguousarray(xprt, dtype=np.float64)
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        grad = np.ascontiguousarray(grad, dtype=np.float64)
-        hess = np.ascontiguousarray(hess, dtype=np.float64)
-        ndim, R = pred.shape
-        npair = ndim * (ndim + 1) // 2
-        assert key.shape == (R,) and xprt.shape == pred.shape and val.shape == (R,) and grad.shape == pred.shape
-        assert hess.shape == (npair, R)
-        srow = None
-        if np.ndim(sigma) > 0:
-            srow = np.ascontiguousarray(sigma, dtype=np.float64)
-            assert srow.shape == (R,)
-        md = float("inf") if max_dist is None else float(max_dist)
-        # capacity R always suffices (glue_keyed_batch)
-        keys, counts = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.int32)
-        out_val, out_grad, out_hess = np.empty(R, dtype=np.float64), np.empty((ndim, R), dtype=np.float64), np.empty((npair, R), dtype=np.float64)
-        n = C.c_int64(0)
-        rc = self._lib.gpsat_glue_keyed_hess_batch(self._h, R, ndim, _ptr(key), _ptr(pred), _ptr(xprt), _ptr(val), _ptr(grad), _ptr(hess),
-                                                   0.0 if srow is not None else float(sigma), _ptr(srow) if srow is not None else None,
-                                                   md, R, C.byref(n), _ptr(keys), _ptr(counts), _ptr(out_val), _ptr(out_grad), _ptr(out_hess))
-        if rc != 0:
-            raise GpsatError(f"gpsat_glue_keyed_hess_batch failed ({rc}): {self._lib.gpsat_last_error().decode()}")
-        n = int(n.value)
-        return (keys[:n].copy(), counts[:n].copy(), out_val[:n].copy(), np.ascontiguousarray(out_grad[:, :n]),
-                np.ascontiguousarray(out_hess[:, :n]))
+        return self._glue_keyed("gpsat_glue_keyed_hess_batch", key, pred, xprt,
+                                [(val, 0), (grad, lambda ndim: ndim), (hess, lambda ndim: ndim * (ndim + 1) // 2)], sigma, max_dist)
 
     def glue_keyed_timing(self):
         """(sort, run detection, reduce) milliseconds of the last glue_keyed_batch, glue_keyed_grad_batch or

@@ -253,6 +253,87 @@ def _location_keys(pred):
     return rank[code], loc[order]
 
 
+def _glue_local_derivatives(order, preds_df, pred_loc_cols, xprt_loc_cols, inference_radius, R, *, value_col, grad_cols, mean_col,
+                            obs_scale, also_glue, max_dist, engine, hess_cols=None, other_coords=None):
+    """``glue_local_gradient`` (``order`` 1: ``hess_cols`` and ``other_coords`` are not read) and ``glue_local_hessian``
+    (``order`` 2): the arguments normalised and refused under the order's noun, the columns of ``preds_df`` in raw units,
+    the rows keyed by prediction location, one device call of that order, and the frame."""
+    with_hess = order == 2
+    noun = "Hessian" if with_hess else "gradient"
+    eng = engine or default_engine()
+    pcols = [pred_loc_cols] if isinstance(pred_loc_cols, str) else list(pred_loc_cols)
+    xcols = [xprt_loc_cols] if isinstance(xprt_loc_cols, str) else list(xprt_loc_cols)
+    if isinstance(inference_radius, bool) or not isinstance(inference_radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"inference_radius must be one number: per-expert radii are not built for the glued {noun}")
+    if not 1 <= len(pcols) <= 2:
+        raise ValueError(f"the glued {noun} takes 1 or 2 glue axes, got pred_loc_cols {pcols}")
+    if len(xcols) != len(pcols):
+        raise ValueError(f"xprt_loc_cols {xcols} and pred_loc_cols {pcols} must name the same number of glue axes")
+    axes = [c[len("pred_loc_"):] if c.startswith("pred_loc_") else c for c in pcols]
+    if grad_cols is None:
+        grad_cols = [f"{value_col}_grad_{c}" for c in axes]
+    gcols = [grad_cols] if isinstance(grad_cols, str) else list(grad_cols)
+    if len(gcols) != len(pcols):
+        raise ValueError(f"grad_cols {gcols} must name one gradient column per glue axis {pcols}")
+    hcols, pairs, tcols = [], [], {}
+    if with_hess:
+        pairs = [(a, b) for a in range(len(axes)) for b in range(a, len(axes))]   # the order of variants.pred_hess_pairs
+        if hess_cols is None:
+            hess_cols = [f"{value_col}_hess_{axes[a]}_{axes[b]}" for a, b in pairs]
+        hcols = [hess_cols] if isinstance(hess_cols, str) else list(hess_cols)
+        if len(hcols) != len(pairs):
+            raise ValueError(f"hess_cols {hcols} must name one column per pair a <= b of the glue axes {pcols}: {len(pairs)}")
+        others = [] if other_coords is None else ([other_coords] if isinstance(other_coords, str) else list(other_coords))
+        if any(t in axes for t in others):
+            raise ValueError(f"other_coords {others} must not name a glue axis {axes}")
+        tcols = {t: ([f"{value_col}_grad_{t}", f"{value_col}_hess_{t}_{t}"], [f"{value_col}_hess_{c}_{t}" for c in axes]) for t in others}
+    extra = [] if also_glue is None else ([also_glue] if isinstance(also_glue, str) else list(also_glue))
+    needed = (pcols + xcols + [value_col] + gcols + hcols + ([mean_col] if mean_col is not None else [])
+              + [c for plain, mixed in tcols.values() for c in plain + mixed] + extra)
+    missing = [c for c in needed if c not in preds_df.columns]
+    if missing:
+        raise ValueError(f"preds_df has no column {missing} (columns: {list(preds_df.columns)})")
+    col = lambda c: preds_df[c].values.astype(np.float64)
+    pred, xprt = np.stack([col(c) for c in pcols]), np.stack([col(c) for c in xcols])
+    osc = float(obs_scale)
+    val = osc * col(value_col) if mean_col is None else col(mean_col) + osc * col(value_col)
+    grad = np.stack([osc * col(c) for c in gcols])
+    key, loc = _location_keys(pred)
+    sigma = float(inference_radius) / R
+    n = len(loc)
+
+    def placed(keys, rows):                                 # by key: every location has one, so this is the identity
+        out = np.full(rows.shape[:-1] + (n,), np.nan)
+        out[..., keys] = rows
+        return out
+
+    if with_hess:
+        hess = np.stack([osc * col(c) for c in hcols])
+        keys, counts, gval, ggrad, ghess = eng.glue_keyed_hess_batch(key, pred, xprt, val, grad, hess, sigma, max_dist)
+    else:
+        keys, counts, gval, ggrad = eng.glue_keyed_grad_batch(key, pred, xprt, val, grad, sigma, max_dist)
+    fr = {c: loc[:, i] for i, c in enumerate(pcols)}
+    fr[value_col] = placed(keys, gval)
+    fr.update({c: placed(keys, ggrad)[i] for i, c in enumerate(gcols)})
+    if with_hess:
+        ghess = placed(keys, ghess)
+        fr.update({c: ghess[k] for k, c in enumerate(hcols)})
+        fr[f"{value_col}_lap"] = sum(ghess[k] for k, (a, b) in enumerate(pairs) if a == b)
+    n_experts = np.zeros(n, dtype=np.int64)
+    n_experts[keys] = counts
+    fr["n_experts"] = n_experts
+    for t, (plain, mixed) in tcols.items():
+        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([osc * col(c) for c in plain]), sigma, max_dist)
+        fr.update({c: placed(keys, out)[j] for j, c in enumerate(plain)})
+        keys, _, _, out = eng.glue_keyed_grad_batch(key, pred, xprt, osc * col(plain[0]), np.stack([osc * col(c) for c in mixed]), sigma, max_dist)
+        fr.update({c: placed(keys, out)[j] for j, c in enumerate(mixed)})
+    for i in range(0, len(extra), GLUE_MAXVARS):
+        names = extra[i:i + GLUE_MAXVARS]
+        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([col(c) for c in names]), sigma, max_dist)
+        fr.update({c: placed(keys, out)[j] for j, c in enumerate(names)})
+    return pd.DataFrame(fr)
+
+
 def glue_local_gradient(preds_df: pd.DataFrame, pred_loc_cols: List[str], xprt_loc_cols: List[str], inference_radius: float,
                         R=3, value_col: str = "f*", grad_cols: Optional[List[str]] = None, mean_col: Optional[str] = "f_bar",
                         obs_scale: float = 1.0, also_glue: Optional[List[str]] = None, max_dist: Optional[float] = None,
@@ -279,51 +360,8 @@ def glue_local_gradient(preds_df: pd.DataFrame, pred_loc_cols: List[str], xprt_l
     Returns one row per unique prediction location, the rows and their order those of ``glue_local_predictions_1d`` /
     ``_2d``: the ``pred_loc_cols``, ``value_col``, the ``grad_cols``, ``n_experts`` (rows that took part; 0: NaN values) and
     the ``also_glue`` columns."""
-    eng = engine or default_engine()
-    pcols = [pred_loc_cols] if isinstance(pred_loc_cols, str) else list(pred_loc_cols)
-    xcols = [xprt_loc_cols] if isinstance(xprt_loc_cols, str) else list(xprt_loc_cols)
-    if isinstance(inference_radius, bool) or not isinstance(inference_radius, (int, float, np.integer, np.floating)):
-        raise TypeError("inference_radius must be one number: per-expert radii are not built for the glued gradient")
-    if not 1 <= len(pcols) <= 2:
-        raise ValueError(f"the glued gradient takes 1 or 2 glue axes, got pred_loc_cols {pcols}")
-    if len(xcols) != len(pcols):
-        raise ValueError(f"xprt_loc_cols {xcols} and pred_loc_cols {pcols} must name the same number of glue axes")
-    if grad_cols is None:
-        grad_cols = [f"{value_col}_grad_{c[len('pred_loc_'):] if c.startswith('pred_loc_') else c}" for c in pcols]
-    gcols = [grad_cols] if isinstance(grad_cols, str) else list(grad_cols)
-    if len(gcols) != len(pcols):
-        raise ValueError(f"grad_cols {gcols} must name one gradient column per glue axis {pcols}")
-    extra = [] if also_glue is None else ([also_glue] if isinstance(also_glue, str) else list(also_glue))
-    needed = pcols + xcols + [value_col] + gcols + ([mean_col] if mean_col is not None else []) + extra
-    missing = [c for c in needed if c not in preds_df.columns]
-    if missing:
-        raise ValueError(f"preds_df has no column {missing} (columns: {list(preds_df.columns)})")
-    col = lambda c: preds_df[c].values.astype(np.float64)
-    pred, xprt = np.stack([col(c) for c in pcols]), np.stack([col(c) for c in xcols])
-    osc = float(obs_scale)
-    val = osc * col(value_col) if mean_col is None else col(mean_col) + osc * col(value_col)
-    grad = np.stack([osc * col(c) for c in gcols])
-    key, loc = _location_keys(pred)
-    sigma = float(inference_radius) / R
-    n = len(loc)
-
-    def placed(keys, rows):                                 # by key: every location has one, so this is the identity
-        out = np.full(rows.shape[:-1] + (n,), np.nan)
-        out[..., keys] = rows
-        return out
-
-    keys, counts, gval, ggrad = eng.glue_keyed_grad_batch(key, pred, xprt, val, grad, sigma, max_dist)
-    fr = {c: loc[:, i] for i, c in enumerate(pcols)}
-    fr[value_col] = placed(keys, gval)
-    fr.update({c: placed(keys, ggrad)[i] for i, c in enumerate(gcols)})
-    n_experts = np.zeros(n, dtype=np.int64)
-    n_experts[keys] = counts
-    fr["n_experts"] = n_experts
-    for i in range(0, len(extra), GLUE_MAXVARS):
-        names = extra[i:i + GLUE_MAXVARS]
-        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([col(c) for c in names]), sigma, max_dist)
-        fr.update({c: placed(keys, out)[j] for j, c in enumerate(names)})
-    return pd.DataFrame(fr)
+    return _glue_local_derivatives(1, preds_df, pred_loc_cols, xprt_loc_cols, inference_radius, R, value_col=value_col, grad_cols=grad_cols,
+                                   mean_col=mean_col, obs_scale=obs_scale, also_glue=also_glue, max_dist=max_dist, engine=engine)
 
 
 def glue_local_hessian(preds_df: pd.DataFrame, pred_loc_cols: List[str], xprt_loc_cols: List[str], inference_radius: float,
@@ -355,72 +393,9 @@ def glue_local_hessian(preds_df: pd.DataFrame, pred_loc_cols: List[str], xprt_lo
     ``_2d``: the ``pred_loc_cols``, ``value_col``, the ``grad_cols``, the ``hess_cols``, ``<value_col>_lap`` (the sum of the
     glued ``f*_hess_<a>_<a>`` over the glue axes, formed on the host), ``n_experts`` (rows that took part; 0: NaN values),
     the columns of the ``other_coords`` and the ``also_glue`` columns."""
-    eng = engine or default_engine()
-    pcols = [pred_loc_cols] if isinstance(pred_loc_cols, str) else list(pred_loc_cols)
-    xcols = [xprt_loc_cols] if isinstance(xprt_loc_cols, str) else list(xprt_loc_cols)
-    if isinstance(inference_radius, bool) or not isinstance(inference_radius, (int, float, np.integer, np.floating)):
-        raise TypeError("inference_radius must be one number: per-expert radii are not built for the glued Hessian")
-    if not 1 <= len(pcols) <= 2:
-        raise ValueError(f"the glued Hessian takes 1 or 2 glue axes, got pred_loc_cols {pcols}")
-    if len(xcols) != len(pcols):
-        raise ValueError(f"xprt_loc_cols {xcols} and pred_loc_cols {pcols} must name the same number of glue axes")
-    axes = [c[len("pred_loc_"):] if c.startswith("pred_loc_") else c for c in pcols]
-    pairs = [(a, b) for a in range(len(axes)) for b in range(a, len(axes))]       # the order of variants.pred_hess_pairs
-    if grad_cols is None:
-        grad_cols = [f"{value_col}_grad_{c}" for c in axes]
-    gcols = [grad_cols] if isinstance(grad_cols, str) else list(grad_cols)
-    if len(gcols) != len(pcols):
-        raise ValueError(f"grad_cols {gcols} must name one gradient column per glue axis {pcols}")
-    if hess_cols is None:
-        hess_cols = [f"{value_col}_hess_{axes[a]}_{axes[b]}" for a, b in pairs]
-    hcols = [hess_cols] if isinstance(hess_cols, str) else list(hess_cols)
-    if len(hcols) != len(pairs):
-        raise ValueError(f"hess_cols {hcols} must name one column per pair a <= b of the glue axes {pcols}: {len(pairs)}")
-    others = [] if other_coords is None else ([other_coords] if isinstance(other_coords, str) else list(other_coords))
-    if any(t in axes for t in others):
-        raise ValueError(f"other_coords {others} must not name a glue axis {axes}")
-    tcols = {t: ([f"{value_col}_grad_{t}", f"{value_col}_hess_{t}_{t}"], [f"{value_col}_hess_{c}_{t}" for c in axes]) for t in others}
-    extra = [] if also_glue is None else ([also_glue] if isinstance(also_glue, str) else list(also_glue))
-    needed = (pcols + xcols + [value_col] + gcols + hcols + ([mean_col] if mean_col is not None else [])
-              + [c for plain, mixed in tcols.values() for c in plain + mixed] + extra)
-    missing = [c for c in needed if c not in preds_df.columns]
-    if missing:
-        raise ValueError(f"preds_df has no column {missing} (columns: {list(preds_df.columns)})")
-    col = lambda c: preds_df[c].values.astype(np.float64)
-    pred, xprt = np.stack([col(c) for c in pcols]), np.stack([col(c) for c in xcols])
-    osc = float(obs_scale)
-    val = osc * col(value_col) if mean_col is None else col(mean_col) + osc * col(value_col)
-    grad = np.stack([osc * col(c) for c in gcols])
-    hess = np.stack([osc * col(c) for c in hcols])
-    key, loc = _location_keys(pred)
-    sigma = float(inference_radius) / R
-    n = len(loc)
-
-    def placed(keys, rows):                                 # by key: every location has one, so this is the identity
-        out = np.full(rows.shape[:-1] + (n,), np.nan)
-        out[..., keys] = rows
-        return out
-
-    keys, counts, gval, ggrad, ghess = eng.glue_keyed_hess_batch(key, pred, xprt, val, grad, hess, sigma, max_dist)
-    fr = {c: loc[:, i] for i, c in enumerate(pcols)}
-    fr[value_col] = placed(keys, gval)
-    fr.update({c: placed(keys, ggrad)[i] for i, c in enumerate(gcols)})
-    ghess = placed(keys, ghess)
-    fr.update({c: ghess[k] for k, c in enumerate(hcols)})
-    fr[f"{value_col}_lap"] = sum(ghess[k] for k, (a, b) in enumerate(pairs) if a == b)
-    n_experts = np.zeros(n, dtype=np.int64)
-    n_experts[keys] = counts
-    fr["n_experts"] = n_experts
-    for t, (plain, mixed) in tcols.items():
-        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([osc * col(c) for c in plain]), sigma, max_dist)
-        fr.update({c: placed(keys, out)[j] for j, c in enumerate(plain)})
-        keys, _, _, out = eng.glue_keyed_grad_batch(key, pred, xprt, osc * col(plain[0]), np.stack([osc * col(c) for c in mixed]), sigma, max_dist)
-        fr.update({c: placed(keys, out)[j] for j, c in enumerate(mixed)})
-    for i in range(0, len(extra), GLUE_MAXVARS):
-        names = extra[i:i + GLUE_MAXVARS]
-        keys, _, out = eng.glue_keyed_batch(key, pred, xprt, np.stack([col(c) for c in names]), sigma, max_dist)
-        fr.update({c: placed(keys, out)[j] for j, c in enumerate(names)})
-    return pd.DataFrame(fr)
+    return _glue_local_derivatives(2, preds_df, pred_loc_cols, xprt_loc_cols, inference_radius, R, value_col=value_col, grad_cols=grad_cols,
+                                   mean_col=mean_col, obs_scale=obs_scale, also_glue=also_glue, max_dist=max_dist, engine=engine,
+                                   hess_cols=hess_cols, other_coords=other_coords)
 
 
 def glue_local_predictions_1d(preds_df: pd.DataFrame, pred_loc_col: str, xprt_loc_col: str,

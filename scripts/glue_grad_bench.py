@@ -7,7 +7,7 @@ about the same sort and about the same reduction are expected; no threshold is s
 after a warm-up at that size, the two calls taken in turn inside every repetition so that drift hits them alike: wall,
 events (copies + kernels, kernels) and the kernels split into sort, run detection and reduce (gpsat_glue_keyed_timing).
 
-    python scripts/glue_grad_bench.py [--rows 20000000] [--reps 5]
+    python scripts/glue_grad_bench.py [--rows 20000000] [--reps 5] [--max-dist 2.39e5]
 """
 import argparse
 import ctypes as C
@@ -51,7 +51,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[20_000_000])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--max-dist", type=float, default=None, help="rows at that distance from their expert or beyond stay out "
+                    "(2.39e5 leaves out about half of these rows)")
     args = ap.parse_args()
+    md = args.max_dist
     eng = default_engine()
     print(f"device {eng.device_name}", flush=True)
     for R in args.rows:
@@ -59,8 +62,8 @@ def main():
         key, pred, xprt, val, grad, sigma, G = make_rows(R)
         vals = np.ascontiguousarray(np.concatenate([val[None], grad]))
         print(f"\n{R} rows, {G} groups of 4..16 rows, ndim {NDIM} (made in {time.perf_counter() - t0:.1f} s)", flush=True)
-        calls = {"glue_keyed_grad_batch (value, slope of the glued map)": lambda: eng.glue_keyed_grad_batch(key, pred, xprt, val, grad, sigma),
-                 "glue_keyed_batch, nvars 3 (value, plain average of the gradients)": lambda: eng.glue_keyed_batch(key, pred, xprt, vals, sigma)}
+        calls = {"glue_keyed_grad_batch (value, slope of the glued map)": lambda: eng.glue_keyed_grad_batch(key, pred, xprt, val, grad, sigma, md),
+                 "glue_keyed_batch, nvars 3 (value, plain average of the gradients)": lambda: eng.glue_keyed_batch(key, pred, xprt, vals, sigma, md)}
         ref = {name: fn() for name, fn in calls.items()}             # warm-up: workspace, rocPRIM kernels, both code objects
         rec = {name: dict(wall=[], kern=[], total=[], split=[]) for name in calls}
         for _ in range(args.reps):
@@ -80,7 +83,9 @@ def main():
                 print(f"    {what}: {med(split[:, j]):.3f} ms (min {split[:, j].min():.3f}, max {split[:, j].max():.3f})", flush=True)
         a, b = ref.values()
         assert a[2].tobytes() == b[2][0].tobytes(), "the glued value is not the keyed glue's"
-        miss = np.abs(a[3] - b[2][1:]).max(axis=1) / np.abs(a[3]).max(axis=1)
+        if md is not None:
+            print(f"  max_dist {md:g}: {a[1].sum() / R:.2f} of the rows take part, {np.mean(a[1] == 0):.3f} of the groups have none (NaN)")
+        miss = np.nanmax(np.abs(a[3] - b[2][1:]), axis=1) / np.nanmax(np.abs(a[3]), axis=1)
         print(f"  the glued value: the same bytes; the plain average of the gradients misses the slope of the glued map by up to "
               f"{miss[0]:.2f} and {miss[1]:.2f} of its largest value on these rows", flush=True)
 
