@@ -9,6 +9,7 @@ import pytest
 
 from gpsat_amd.local_experts import BatchedLocalExpertOI, DynamicSelect, LocalSelector
 from oracle import gp_oracle as go
+import select_numpy
 from test_dynamic_select_cpu import _restate
 
 pytestmark = pytest.mark.gpu
@@ -51,6 +52,10 @@ def _device_and_host(eng, df, xl, check):
     ho, hi = LocalSelector(df, LOCAL, interval_codes=codes).select(xl.iloc[check], bounds=b[check])
     for j, e in enumerate(check):
         np.testing.assert_array_equal(idx[off[e]:off[e + 1]], hi[ho[j]:ho[j + 1]])
+    # EVERY expert against the NumPy restatement (the host selector above, a KD-tree query per expert, answers the sample)
+    w_off, w_idx = select_numpy.select_frames(df, LOCAL, xl, interval_codes=codes, bounds=b)
+    np.testing.assert_array_equal(off, w_off)
+    np.testing.assert_array_equal(idx, w_idx)
     return off, idx
 
 
